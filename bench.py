@@ -215,6 +215,45 @@ def whole_job_value(pixels_per_rank_step, steps, world, seconds):
     return pixels_per_rank_step * steps * world / seconds / 1e6
 
 
+DUMP_BYTES = 60 << 20  # --dump-outputs: what one run writes in all stays under 64 MB
+DUMP_SEED = 20240601  # which pictures and which sample positions --dump-outputs keeps: fixed, so two builds write the same set
+
+
+def dump_pictures(candidates, n=4):
+    """The pictures --dump-outputs keeps: the first candidate and a fixed seeded choice of n - 1 others."""
+    rest = candidates[1:]
+    pick = np.random.default_rng(DUMP_SEED).choice(len(rest), min(n - 1, len(rest)), replace=False) if rest else []
+    return candidates[:1] + sorted(rest[int(k)] for k in pick)
+
+
+def dump_outputs(out_dir, ids, arrays):
+    """--dump-outputs: arrays = {name: [one 2-D integer plane per picture of ids]}.  Writes DIR/<name>.npy (float32, one row
+    per picture: every sample, or a fixed seeded sample of the positions when the plane is larger than its share of
+    DUMP_BYTES), DIR/<name>_digest.npy (float64, per picture: sum and sum of squares over EVERY sample) and DIR/pictures.npy
+    (the picture indices).  Returns the bytes written."""
+    os.makedirs(out_dir, exist_ok=True)
+    per_name = DUMP_BYTES // max(1, len(arrays)) // max(1, len(ids)) // 4
+    total = 0
+
+    def save(name, a):
+        nonlocal total
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        total += a.nbytes
+
+    save("pictures", np.asarray(ids, np.float64))
+    for name, planes in arrays.items():
+        flat = [np.ascontiguousarray(p).reshape(-1) for p in planes]
+        n = flat[0].size
+        if n > per_name:
+            pos = np.sort(np.random.default_rng(DUMP_SEED).choice(n, per_name, replace=False))
+            flat_s = [f[pos] for f in flat]
+        else:
+            flat_s = flat
+        save(name, np.stack(flat_s).astype(np.float32))
+        save(name + "_digest", np.array([[f.sum(dtype=np.int64), np.square(f.astype(np.int64)).sum()] for f in flat], np.float64))
+    return total
+
+
 def launch_ranks(n):
     """Start the N ranks of a multi-GPU run: a CHILD process running torch.distributed.run (this process has not
     touched the GPU and never will; nothing is exec'ed over a process that has).  Returns the child's exit code."""
@@ -229,10 +268,11 @@ def launch_ranks(n):
     return subprocess.call(cmd, env=env)
 
 
-def run_random_access(args, torch, dist, rank, local_rank, world, workload_name, segments, steps, warmup):
+def run_random_access(args, torch, dist, rank, local_rank, world, workload_name, segments, steps, warmup, dump_dir=None):
     """configs[3]: one step = every rank codes its intra-period segments (I pictures through the intra
     chain, B/P pictures through MC + residual transform + reconstruction); boundary I pictures travel
-    between ranks by RCCL send/recv.  Weak scaling: `segments` segments PER RANK.  Returns the result object."""
+    between ranks by RCCL send/recv.  Weak scaling: `segments` segments PER RANK.  dump_dir: rank 0 writes the
+    reconstructions of some of its pictures after the timed steps (dump_outputs).  Returns the result object."""
     from thevc_amd import capi
     from thevc_amd import ra_pipeline as ra
     w, h, B, qp, cfg_name = WORKLOADS[workload_name]
@@ -274,6 +314,12 @@ def run_random_access(args, torch, dist, rank, local_rank, world, workload_name,
         exch = pipe.exchange_stats()
         pipe.check()  # the abort word of every context the steps ran on
         sb = pipe.step_bytes()
+        dumped = None
+        if dump_dir and rank == 0:
+            pocs = dump_pictures(sorted(pipe.rec))
+            recs = [pipe.rec[poc].download() for poc in pocs]
+            nbytes = dump_outputs(dump_dir, pocs, {f"reconstruction_{c}": [r[p] for r in recs] for p, c in enumerate(("y", "cb", "cr"))})
+            dumped = {"dir": dump_dir, "pictures": pocs, "bytes": nbytes}
     out = {
         "metric": METRIC,
         "value": round(px / dt / 1e6, 2), "unit": "Mpixels/s", "n_gpus": world, "steps": steps, "warmup": warmup,
@@ -288,6 +334,8 @@ def run_random_access(args, torch, dist, rank, local_rank, world, workload_name,
                    "width": w, "height": h, "bit_depth": B, "qp": qp},
         "exchange": exch,
     }
+    if dumped is not None:
+        out["dump_outputs"] = dumped
     # Roofline of the whole step: the inter workloads have no single dominant kernel (motion compensation, the inter block chain, the
     # border extension and the I pictures' intra chain share the step; profiles/r03_ra2160p8_kernel_stats.csv has their split), so the
     # algorithmic bytes of every stage are priced against the step the driver clocks.
@@ -394,7 +442,12 @@ def main():
     ap.add_argument("--ra-segments", type=int, default=16, help="segments (32 pictures each) per GPU of the random-access leg")
     ap.add_argument("--verify", action="store_true", help="the cpu_baseline leg also checks a picture of every packing group")
     ap.add_argument("--rehearse-cpu", action="store_true", help="no GPU: run the rank launcher, sharding, exchange and reporting with gloo and the CPU oracle")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (reconstruction and levels of a fixed set of pictures, "
+                         "sampled to at most 64 MB in all) as DIR/<name>.npy; pass --frames too, or the batch size follows the free HBM")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(launch_ranks(args.gpus))  # before anything touches the GPU
@@ -421,7 +474,8 @@ def main():
     from thevc_amd import capi, workload
 
     if args.workload.startswith(("ra", "ldp")):
-        out = run_random_access(args, torch, dist, rank, local_rank, world, args.workload, args.segments, args.steps, args.warmup)
+        out = run_random_access(args, torch, dist, rank, local_rank, world, args.workload, args.segments, args.steps, args.warmup,
+                                dump_dir=args.dump_outputs)
         out["note"] = "secondary workload (SURVEY.md 8e): the roofline object prices the WHOLE step's algorithmic bytes (no single dominant kernel)"
         if rank == 0:
             print(json.dumps(out), flush=True)
@@ -543,6 +597,18 @@ def main():
     sched, groups = C.c_int(), C.c_int()
     L.hmx_last_call_shape(ctx.h, C.byref(sched), C.byref(groups))  # how the library issued the timed calls
     dt = max_over_ranks(dt, world, "cuda")
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # what the last timed step left: the reconstruction and the levels (plane geometry) of a fixed set of pictures; picture i's
+        # inputs depend on i alone (plan i mod PLANS, source i mod DISTINCT), so the set is the same for any batch of 64 or more
+        ids = dump_pictures(list(range(min(F, 64))))
+        recs = [reconstruction(i) for i in ids]
+        levs = [lev_slab.picture(i).to_planes(tus_list[i % n_plans]) for i in ids]
+        arrays = {}
+        for p, c in enumerate(("y", "cb", "cr")):
+            arrays[f"reconstruction_{c}"] = [r[p] for r in recs]
+            arrays[f"levels_{c}"] = [lv[p] for lv in levs]
+        dumped = {"dir": args.dump_outputs, "pictures": ids, "bytes": dump_outputs(args.dump_outputs, ids, arrays)}
 
     # ---- fresh decisions: nothing carried over from step to step (round-2 verdict, item 1) ----
     # Every picture of the batch has its own decision list in HBM (F distinct structures); a step analyses them on the device
@@ -674,6 +740,8 @@ def main():
         }
         if fresh is not None:
             out["fresh_decisions"] = fresh
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if world == 1 and (args.verify or not args.no_cpu_baseline):
             # --verify: one picture of every few packing groups, first and last included
             # default: three pictures (the first, one from the middle of the batch -- another packing group, another plan -- and the last)
