@@ -126,7 +126,9 @@ __device__ __forceinline__ void wave_chain_valu(char *smem, const SRC &src, cons
         fwd_tq_block<N>(L, gl, active, row, ts, luma, luma, scan_idx, ts, P);
         rdoq_wave_tiles<N, SL>(reinterpret_cast<TuLds<N> *>(smem), src.rdoq_lds(), src.rdoq(), P, lane);
       } else {
-        fwd_tq_block<N>(L, gl, active, row, ts, luma, luma, scan_idx, true, P);
+        // 16x16: the scan is diagonal, the quantiser decides sign-bit hiding in the lane that holds the group (transform-skip
+        // blocks keep the general routine)
+        fwd_tq_block<N>(L, gl, active, row, ts, luma, luma, scan_idx, true, P, (N == 16 && !__any(ts)) ? lane : -1);
       }
       HMX_MARK(N, 5);
       if (active) {
@@ -818,6 +820,7 @@ __device__ __forceinline__ void wave_chain_32(char *smem, const SRC &src, const 
   TuLds<32> &L = *reinterpret_cast<TuLds<32> *>(smem);
   constexpr int LG = 5;
   for (int i = 0; ONCE ? i < 1 : i < count; i++) {
+    HMX_MARK(32, 0);
     const FTu ft = src.desc(i);
     const hmx_tu t = ft.t;
     const int pl = t.plane, x = t.x, y = t.y;
@@ -853,6 +856,7 @@ __device__ __forceinline__ void wave_chain_32(char *smem, const SRC &src, const 
       int coef[16];
 #pragma unroll
       for (int s = 0; s < 16; s++) v[s] = wrap16((int)org4[s >> 2][s & 3] - pred[s]);
+      HMX_MARK(32, 1);
       fwd32_mfma(v, r, h, P.bit_depth, coef);
       if constexpr (SRC::kRdoq) {
         wave_sync();
@@ -862,8 +866,8 @@ __device__ __forceinline__ void wave_chain_32(char *smem, const SRC &src, const 
         wave_sync();
         rdoq_wave_tiles<32, 1>(&L, src.rdoq_lds(), src.rdoq(), P, lane);
       } else {
-        quant_sbh_block<32, 64, 16, false>(
-            L, lane, true, coef, [&](int k) { return mrow(k, h); }, [&](int) { return r; }, luma, 0, P);
+        HMX_MARK(32, 2);
+        quant_sbh_diag<32, 16>(L, lane, lane, true, coef, [&](int k) { return mrow(k, h); }, [&](int) { return r; }, luma, diag_group_org<32>(lane), P);
       }
 #pragma unroll
       for (int g = 0; g < 16; g++) {
@@ -874,6 +878,7 @@ __device__ __forceinline__ void wave_chain_32(char *smem, const SRC &src, const 
 #pragma unroll
       for (int g = 0; g < 16; g++) v[g] = lev0[__umul24((unsigned)mrow(g, h), (unsigned)lstep)];
     }
+    HMX_MARK(32, 3);
     const int tshift = 15 - P.bit_depth - LG;
     const QuantDev qd = pick_qd(P, luma);
     int out[16];

@@ -268,6 +268,74 @@ __device__ __forceinline__ int quant_sbh_block(LT &L, int gl, bool active, const
   return sum;
 }
 
+// The same for a block whose scan is diagonal whatever its mode (N = 16, 32) and whose NG = (N/4)^2 lanes are consecutive in
+// the wave: lane gl decides for group gl of the diagonal group scan, whose first coefficient sits at word g_org of the tile
+// (diag_group_org).  What quant_sbh_block spends on a run-time scan -- a table load, byte extraction and an address per
+// coefficient, the LDS atomic of the group mask and a third pass -- becomes sixteen loads at compile-time offsets, a ballot
+// shifted by the lane ("a later group holds a level": the reference's lastCG) and one store of the changed word.
+template <int N, int NCOEF, typename LT, typename RowFn, typename ColFn>
+__device__ __forceinline__ int quant_sbh_diag(LT &L, int gl, int lane, bool active, const int *coef, RowFn row_of, ColFn col_of,
+                                              bool luma, int g_org, const PicDev &P) {
+  constexpr int LG = Log2<N>::v, NL = (N / 4) * (N / 4);
+  static_assert(NL == 16 || NL == 64, "one lane per coefficient group");
+  const int tshift = 15 - P.bit_depth - LG;
+  const QuantDev qd = pick_qd(P, luma);
+  const int qbits = 14 + qd.per_qbits + tshift;
+  int sum = 0;
+  if (active) {
+#pragma unroll
+    for (int k = 0; k < NCOEF; k++) {
+      int al;
+      L.tile[row_of(k)][col_of(k)] = quant_one<false>(coef[k], qd.q, qbits, qd.rnd_factor, al);
+      sum += al;
+    }
+  }
+  sum = group_sum(active ? sum : 0, NL);
+  wave_sync();
+#ifdef HMX_X_NO_SBH /* timing experiment (results wrong): the quantiser without sign-bit hiding */
+  const bool hide = false;
+#else
+  const bool hide = P.sign_hide && sum >= 2; // uniform over the block's lanes
+#endif
+  if (hide) {
+    constexpr unsigned long long kDiag4 = 0xfbe7ad369c258140ull; // nibble i: raster position y * 4 + x of scan entry i of a group
+    int *const go = &L.tile[0][0] + g_org;
+    int w[16];
+    unsigned nzb = 0;
+#pragma unroll
+    for (int i = 0; i < 16; i++) {
+      const int p = (int)((kDiag4 >> (4 * i)) & 15);
+      w[i] = go[(p >> 2) * (N + 1) + (p & 3)];
+      nzb |= (unsigned)w[i];
+    }
+    const bool nz = (nzb & 0xffffu) != 0;
+    const unsigned long long later = (__ballot(nz) >> lane) >> 1; // lanes gl + 1, ... (and, for N = 16, the next blocks')
+    const bool last = (NL == 64 ? later : later & ((1ull << (NL - 1 - gl)) - 1)) == 0;
+    if (active && nz) {
+      int nw;
+      const int bi = sbh_decide(w, last, nw);
+      if (bi >= 0) {
+        const int p = (int)((kDiag4 >> (4 * bi)) & 15);
+        go[(p >> 2) * (N + 1) + (p & 3)] = nw;
+      }
+    }
+  }
+  wave_sync();
+  return sum;
+}
+
+// word offset in TuLds<N>::tile of the first coefficient of group g of the diagonal group scan (N = 16, 32)
+template <int N>
+__device__ __forceinline__ int diag_group_org(int g) {
+  if constexpr (N == 16) { // the group scan of a 4x4 grid of groups is the coefficient scan of a group
+    const int p = (int)((0xfbe7ad369c258140ull >> (4 * g)) & 15);
+    return (p >> 2) * 4 * (N + 1) + (p & 3) * 4;
+  } else {
+    const int p = kScan32.t[0][g * 16];
+    return (p / N) * (N + 1) + p % N;
+  }
+}
+
 // ---------------------------------------------------------------------------------------------
 // VALU path (N = 4, 8, 16; also 32 in the list kernels): lane gl owns row/column gl of the block.
 // transformNxN core: residual row -> final levels in L.tile.  ts = transform skip (:1622),
@@ -275,7 +343,7 @@ __device__ __forceinline__ int quant_sbh_block(LT &L, int gl, bool active, const
 // ---------------------------------------------------------------------------------------------
 template <int N>
 __device__ __forceinline__ int fwd_tq_block(TuLds<N> &L, int gl, bool active, const int *x, bool ts, bool use_dst,
-                                            bool luma, int scan_idx, bool do_quant, const PicDev &P) {
+                                            bool luma, int scan_idx, bool do_quant, const PicDev &P, int diag_lane = -1) {
   // everything quantised here went through a forward pass (int16) or transform skip (|x| << shift
   // with |x| < 2^(B+1)), so the 32-bit quantiser is exact
   constexpr int LG = Log2<N>::v;
@@ -310,6 +378,10 @@ __device__ __forceinline__ int fwd_tq_block(TuLds<N> &L, int gl, bool active, co
     }
     wave_sync();
     return 0;
+  }
+  if constexpr (N == 16) {
+    if (diag_lane >= 0) // diag_lane: the lane in the wave; the caller saw no transform-skip block in it
+      return quant_sbh_diag<N, N>(L, gl, diag_lane, active, coef, [](int k) { return k; }, [&](int) { return gl; }, luma, diag_group_org<N>(gl), P);
   }
   return quant_sbh_block<N, N, N, false>(
       L, gl, active, coef, [&](int k) { return ts ? gl : k; }, [&](int k) { return ts ? k : gl; }, luma, scan_idx, P);
