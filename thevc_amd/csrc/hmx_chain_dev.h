@@ -287,26 +287,23 @@ __device__ __forceinline__ void wave_chain_8x2(char *smem, const SRC &src, const
       }
       const bool nz = (nzb & 0xffffu) != 0;
       sum = group_sum(active ? sum : 0, NL);
+#ifdef HMX_X_NO_SBH /* timing experiment (results wrong): the quantiser without sign-bit hiding */
+      const bool hide = false;
+#else
       const bool hide = P.sign_hide && sum >= 2; // uniform over the block's lanes
+#endif
       // which groups of the block hold a level, in the order of the block's group scan (diagonal and vertical: gx * 2 + gy = gl;
       // horizontal: gy * 2 + gx)
       const unsigned nzq = (unsigned)(__ballot(nz) >> (lane & ~3)) & 15u;
-      const bool hor = scan_idx == 1, ver = scan_idx == 2;
+      const bool hor = scan_idx == 1;
       const unsigned nzs = hor ? ((nzq & 9u) | ((nzq & 2u) << 1) | ((nzq & 4u) >> 1)) : nzq;
       const int sidx = hor ? (((gl & 1) << 1) | (gl >> 1)) : gl;
       if (hide && nz) {
-        constexpr int dg[16] = {0, 4, 1, 8, 5, 2, 12, 9, 6, 3, 13, 10, 7, 14, 11, 15};
         int ws[16];
-#pragma unroll
-        for (int k = 0; k < 16; k++) {
-          const int d = w[dg[k]], hv = w[k], vv = w[((k & 3) << 2) | (k >> 2)];
-          ws[k] = hor ? hv : (ver ? vv : d);
-        }
-        int nw;
-        const int bi = sbh_decide(ws, (nzs >> (sidx + 1)) == 0, nw);
+        scan4_order(w, scan_idx, ws);
+        const int bi = sbh_pick(ws, ScanOrder(), (nzs >> (sidx + 1)) == 0);
         if (bi >= 0) {
-          const int bd = (int)((0xfbe7ad369c258140ull >> (4 * bi)) & 15); // dg[bi], one nibble per entry
-          const int bp = hor ? bi : (ver ? (((bi & 3) << 2) | (bi >> 2)) : bd);
+          const int nw = sbh_apply(select16(ws, bi)), bp = scan4_raster(scan_idx, bi);
 #pragma unroll
           for (int q = 0; q < 16; q++) w[q] = (q == bp) ? nw : w[q];
         }
@@ -474,22 +471,16 @@ __device__ __forceinline__ void lane4_forward(const int *resid, bool use_dst, bo
     w[k] = quant_one<false>(coef[k], qd.q, qbits, qd.rnd_factor, al);
     sum += al;
   }
+#ifdef HMX_X_NO_SBH /* timing experiment (results wrong): the quantiser without sign-bit hiding */
+  if (false) {
+#else
   if (P.sign_hide && sum >= 2) { // one coefficient group = the whole block; it is "the last group"
-    // the scan differs per lane, but there are only three of them: scan entry k of each is a
-    // compile-time register, so the reorder is two selects per entry
-    constexpr int dg[16] = {0, 4, 1, 8, 5, 2, 12, 9, 6, 3, 13, 10, 7, 14, 11, 15};
-    const bool hor = scan_idx == 1, ver = scan_idx == 2;
+#endif
     int ws[16];
-#pragma unroll
-    for (int k = 0; k < 16; k++) {
-      const int d = w[dg[k]], hv = w[k], vv = w[((k & 3) << 2) | (k >> 2)];
-      ws[k] = hor ? hv : (ver ? vv : d);
-    }
-    int nw;
-    const int bi = sbh_decide(ws, true, nw);
+    scan4_order(w, scan_idx, ws);
+    const int bi = sbh_pick(ws, ScanOrder(), true);
     if (bi >= 0) {
-      const int bd = (int)((0xfbe7ad369c258140ull >> (4 * bi)) & 15); // dg[bi], one nibble per entry
-      const int bp = hor ? bi : (ver ? (((bi & 3) << 2) | (bi >> 2)) : bd);
+      const int nw = sbh_apply(select16(ws, bi)), bp = scan4_raster(scan_idx, bi);
 #pragma unroll
       for (int q = 0; q < 16; q++) w[q] = (q == bp) ? nw : w[q];
     }

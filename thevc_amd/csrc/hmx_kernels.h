@@ -255,11 +255,10 @@ __device__ __forceinline__ int quant_sbh_block(LT &L, int gl, bool active, const
       const int g = gl + q * NL;
       if (g < NG && ((mask >> g) & 1)) {
         const bool higher = g < 63 ? (mask >> (g + 1)) != 0 : false;
-        int nw;
-        const int bi = sbh_decide(w[q], !higher, nw);
+        const int bi = sbh_pick(w[q], ScanOrder(), !higher, [&](int i) { const int p = pos[q].at_dyn(i); return L.tile[p / N][p % N]; });
         if (bi >= 0) {
           const int p = pos[q].at_dyn(bi);
-          L.tile[p / N][p % N] = nw;
+          L.tile[p / N][p % N] = sbh_apply(L.tile[p / N][p % N]);
         }
       }
     }
@@ -312,12 +311,12 @@ __device__ __forceinline__ int quant_sbh_diag(LT &L, int gl, int lane, bool acti
     const unsigned long long later = (__ballot(nz) >> lane) >> 1; // lanes gl + 1, ... (and, for N = 16, the next blocks')
     const bool last = (NL == 64 ? later : later & ((1ull << (NL - 1 - gl)) - 1)) == 0;
     if (active && nz) {
-      int nw;
-      const int bi = sbh_decide(w, last, nw);
-      if (bi >= 0) {
-        const int p = (int)((kDiag4 >> (4 * bi)) & 15);
-        go[(p >> 2) * (N + 1) + (p & 3)] = nw;
-      }
+      const auto at = [&](int i) -> int & {
+        const int p = (int)((kDiag4 >> (4 * i)) & 15);
+        return go[(p >> 2) * (N + 1) + (p & 3)];
+      };
+      const int bi = sbh_pick(w, ScanOrder(), last, [&](int i) { return at(i); });
+      if (bi >= 0) at(bi) = sbh_apply(at(bi));
     }
   }
   wave_sync();
