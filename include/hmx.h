@@ -289,8 +289,11 @@ int hmx_batch_invtransformNxN(hmx_ctx *ctx, const hmx_tu_list *list, const hmx_l
  * NULL) receives block i's absolute sum.  side[i] carries what the reference reads from the CU for block i
  * and which bit-estimate table (est[side[i].est_idx], host array) applies.  8x8 and larger blocks: a wave shares 8 / 4 / 1
  * blocks in LDS, coefficient groups walked in parallel (thevc_amd/csrc/hmx_rdoq_core.h); 4x4 blocks: one lane per block.
- * Coefficients are what xT / xTransformSkip produce: |c| <= 32768 (levels of 8x8 and larger blocks travel as 16-bit words
- * inside the kernel).  The block list and the tables stay resident on the device while the arguments repeat. */
+ * Coefficients are what xT / xTransformSkip produce: |c| <= 32768.  Levels are Int as in the reference, not clipped: when the
+ * QP, bit depth and block sizes of a call allow |level| = (32768 * quantScale) >> qbits > 32767 (e.g. 10 bit, QP < 5 with 32x32
+ * blocks), whose levels the wave-cooperative routine would keep in 16 bits, every block of the call runs one lane per block
+ * instead (the same holds for hmx_xRateDistOptQuant).  The block list and the tables stay resident on the device while the
+ * arguments repeat. */
 typedef struct hmx_rdoq_side {
   uint16_t est_idx;
   uint8_t root_cbf, cbf_ctx;

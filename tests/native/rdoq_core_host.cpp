@@ -311,10 +311,10 @@ static void rdoq_block_rewalk(const int *src, int *dst, int N, int B, const hmo_
 int main(int argc, char **argv) {
   const int rounds = argc > 1 ? atoi(argv[1]) : 400;
   std::mt19937_64 rng(20260101);
-  long checked = 0, nonzero = 0, zeroed_like = 0;
+  long checked = 0, nonzero = 0, zeroed_like = 0, wide = 0;
   for (int it = 0; it < rounds; it++)
     for (int lg = 2; lg <= 5; lg++) {
-      const int N = 1 << lg, B = (it & 1) ? 10 : 8;
+      const int N = 1 << lg, B = it % 4 == 3 ? 12 : (it & 1) ? 10 : 8;
       hmo_est_bits est;
       auto pair = [&](int32_t *d) {
         const double p = 0.03 + 0.94 * (rng() % 10000) / 10000.0;
@@ -329,7 +329,8 @@ int main(int argc, char **argv) {
       for (int i = 0; i < 32; i++) est.last_x[i] = (int32_t)((8000 + rng() % 52000) * (1 + i / 4)), est.last_y[i] = (int32_t)((8000 + rng() % 52000) * (1 + i / 4));
       pair(est.scan_zigzag), pair(est.scan_nonzigzag);
       hmo_rdoq_cfg cfg;
-      const int qp = (int)(rng() % 52) + 6 * (B - 8);
+      // the scaled QP from 0 (QP_Y = -QpBdOffset: per 0, where levels of deep bit depths exceed 16 bits) to 51 + QpBdOffset
+      const int qp = (int)(rng() % (52 + 6 * (B - 8)));
       cfg.per = qp / 6, cfg.rem = qp % 6;
       cfg.is_luma = (int)(rng() % 3 != 0);
       cfg.is_intra = (int)(rng() & 1);
@@ -340,13 +341,16 @@ int main(int argc, char **argv) {
       cfg.sign_hide = (int)(rng() % 4 != 0);
       cfg.lambda = 4.0 + (rng() % 200000) / 1000.0;
       std::vector<int32_t> src(N * N), want(N * N), got(N * N);
-      const int style = (int)(rng() % 5); // sparse, decaying, dense small, dense large, mostly zero with outliers
+      // sparse, decaying, dense small, dense large, mostly zero with outliers, low frequencies near +-32768 (the transform's extremes)
+      const int style = (int)(rng() % 6);
       for (int y = 0; y < N; y++)
         for (int x = 0; x < N; x++) {
-          int amp = style == 0 ? 60 : style == 1 ? 4000 / (1 + x + y) : style == 2 ? 90 : style == 3 ? 30000 : 8;
+          int amp = style == 0 ? 60 : style == 1 ? 4000 / (1 + x + y) : style == 2 ? 90 : style == 3 ? 30000 : style == 4 ? 8 : 32768 >> (x + y);
           int v = (int)(rng() % (2 * amp + 1)) - amp;
           if (style == 0 && rng() % 8) v = 0;
           if (style == 4 && rng() % 50 == 0) v = (int)(rng() % 2001) - 1000;
+          if (style == 5 && x + y < 2) v = rng() & 1 ? 32767 - (int)(rng() % 16) : -32768 + (int)(rng() % 16);
+          if (style == 5 && v > 32767) v = 32767;
           src[y * N + x] = v;
         }
       if (it % 17 == 3) std::fill(src.begin(), src.end(), 0);
@@ -381,13 +385,15 @@ int main(int argc, char **argv) {
       }
       checked++;
       nonzero += s_want > 0;
+      for (int i = 0; i < N * N; i++) wide += want[i] > 32767 || want[i] < -32768;
       (void)zeroed_like;
     }
   printf("rdoq_core_host: %ld blocks identical to the oracle (%ld with levels; %ld groups zeroed by the group decision, %ld entered with a carry, "
          "%ld changed by sign hiding)\n", checked, nonzero, g_zeroed_groups, g_carried_groups, g_sign_hidden);
   printf("re-walk decomposition: identical too (%ld groups beyond the search records walked again for the last position, %ld for sign hiding)\n", g_rewalk_last, g_rewalk_hide);
   printf("rounds: %ld, %.2f groups and %.1f lanes per round and block\n", g_rounds, (double)g_round_groups / g_rounds, (double)g_round_tasks / g_rounds);
-  if (!g_zeroed_groups || !g_carried_groups || !g_sign_hidden || !g_rewalk_hide) {
+  printf("levels beyond 16 bits: %ld\n", wide);
+  if (!g_zeroed_groups || !g_carried_groups || !g_sign_hidden || !g_rewalk_hide || !wide) {
     printf("coverage hole\n");
     return 2;
   }

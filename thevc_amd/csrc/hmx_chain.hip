@@ -99,8 +99,8 @@ static int issue_packed(hmx_ctx *c, const hmx_intra_plan *const *plans, int plan
     G.slots4 = 64; // a 4x4 block's RDOQ runs inside one lane
     // Inside the kernel RDOQ's levels travel as 16-bit words (hmx_rdoq.h); the reference keeps TCoeff = Int.  A level can reach
     // (32768 * q) >> qbits: at the lowest QPs of deep bit depths that exceeds 32767 for the large transforms (10 bit, per = 0, 32x32:
-    // ~52000) and would wrap silently -- refuse the call instead (the scalar and block-list entries carry 32-bit levels for 4x4 and
-    // the same bound otherwise: include/hmx.h).
+    // ~52000) and would wrap silently -- refuse the call instead (the scalar and block-list entries send such calls through the
+    // one-lane-per-block kernel, whose levels are 32-bit: include/hmx.h).
     for (int t = 0; t < 2; t++)
       for (int lg = 2; lg <= 5; lg++) {
         if (!sz[lg - 2]) continue;

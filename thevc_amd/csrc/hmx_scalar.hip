@@ -279,7 +279,16 @@ static int rdoq_issue(hmx_ctx *c, RdoqArgs A) {
   // blocks arrive sorted by size, largest first: 8x8 and larger go through the wave-cooperative routine (the decomposition
   // of hmx_rdoq_core.h), 4x4 blocks -- a single coefficient group, nothing to decompose -- one LANE per block (k_rdoq)
   const size_t n_wave = c->rdoq_class_n[0] + c->rdoq_class_n[1] + c->rdoq_class_n[2], n_all = n_wave + c->rdoq_class_n[3];
-  const bool lane_only = c->knob.rdoq_lane_only || A.qtab; // per-position tables: the sequential kernel reads them
+  // The wave-cooperative routine keeps levels as 16-bit words; the reference's are Int.  At the lowest QPs of deep bit depths a
+  // level of an 8x8 or larger block can reach (32768 * q) >> qbits > 32767 (10 bit, per 0, 32x32: ~52000): those calls go through
+  // the sequential kernel, whose levels are 32-bit (the bound of the whole-picture chain, hmx_chain.hip, which refuses instead)
+  bool wide_levels = false;
+  for (int t = 0; t < 2; t++)
+    for (int lg = 3; lg <= 5; lg++) {
+      const int qbits = 14 + A.per[t] + 15 - A.bit_depth - lg;
+      if (c->rdoq_class_n[5 - lg] && (qbits < 0 || ((32768ll * A.q[t]) >> qbits) > 32767)) wide_levels = true;
+    }
+  const bool lane_only = c->knob.rdoq_lane_only || A.qtab || wide_levels; // per-position tables: the sequential kernel reads them
   if (n_wave && !lane_only) {
     // 8x8 and larger: the wave-cooperative routine of the whole-picture chain (rdoq_wave_tiles), a wave per 8 / 4 / 1 blocks
     if (!c->rdoq_consts && hipMalloc((void **)&c->rdoq_consts, 4 * sizeof(double)) != hipSuccess) return fail(c, HMX_ERR_NOMEM, "hipMalloc RDOQ constants");
