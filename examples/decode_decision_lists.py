@@ -6,6 +6,11 @@ parameters per picture).  thevc_amd/decisions.py turns them into libhmx calls pi
 the reference decoder's pictures (the fixture carries them, --check compares).
 
   python examples/decode_decision_lists.py tests/golden/stream_randomaccess_main_q34_full.npz out.yuv --check
+
+Streams with several slices, several tiles or constrained intra prediction (tests/golden/layout_*.npz) carry their layout
+(region per CTU, constrained_intra_pred_flag); decode_sequence passes it to the intra plans:
+
+  python examples/decode_decision_lists.py tests/golden/layout_intra_he10_q32_tiles_slices.npz out.yuv --check
 """
 import argparse
 import os

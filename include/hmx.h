@@ -177,6 +177,33 @@ int hmx_invtransformNxN(hmx_ctx *ctx, int trans_quant_bypass, int text_type, uns
  * for luma, the [1 2 1]-smoothed copy behind it.  adi must hold 2*(2n+1)^2 ints. */
 int hmx_initAdiPattern(hmx_ctx *ctx, const hmx_pel *rec, int stride, int x, int y, int n, int is_chroma,
                        int pic_w_luma, int pic_h_luma, int32_t *adi);
+/* Slices, tiles and constrained intra prediction in the availability of intra neighbours.  HM marks a neighbour unit
+ * unavailable when it lies in another slice or another tile (TComDataCU.cpp:1221-1735, getPU* with bEnforceSliceRestriction
+ * and the getTileIdxMap checks), or, with constrained_intra_pred_flag, when it is not intra-coded (TComPattern.cpp:607-786).
+ * A region is one (independent slice, tile) pair: dependent slices do not split regions (TComPattern calls getPU* with
+ * bEnforceDependentSliceRestriction = false).  Slices start at CTU boundaries (SliceGranularity 0).  The layout only ever
+ * REMOVES units from the geometric availability of hmx_intra_avail_mask.  A NULL layout, or one with both maps NULL, is one
+ * region with CIP off and gives exactly what the entry points without a layout give.  A layout whose sizes do not fit the
+ * picture, or that turns CIP on without a map, is refused with HMX_ERR_ARG. */
+typedef struct {
+  const uint32_t *ctu_region; /* region id of every CTU in raster order (n_ctu entries); NULL = one region */
+  int n_ctu;                  /* entries of ctu_region: ceil(pic_w / ctu) * ceil(pic_h / ctu) */
+  int constrained_intra_pred; /* PPS constrained_intra_pred_flag; 1 needs intra_unit */
+  const uint8_t *intra_unit;  /* nonzero = the 4x4 luma unit (ux, uy) is intra-coded: intra_unit[uy * intra_stride + ux] */
+  int intra_stride;           /* >= ceil(pic_w / 4) */
+  int intra_rows;             /* rows of intra_unit, >= ceil(pic_h / 4) */
+} hmx_avail_layout;
+/* fillReferenceSamples (TLibCommon/TComPattern.cpp:368-552) in the reference's own argument order: the reference line of an
+ * N x N block from HOST samples around rec (= sample (0,0) of the block; rows above and columns left of it are read where
+ * flagged), with the caller's bNeighborFlags (4 * N / unit + 1 bytes, below-left bottom first, left, corner, above,
+ * above-right), iNumIntraNeighbor = n_avail and iUnitSize = unit (4 luma, 2 chroma; N = 64 with unit 4 is the 64 x 64 luma
+ * prediction unit).  adi receives the (2N+1)^2 border buffer (no smoothing: that is initAdiPattern's). */
+int hmx_fillReferenceSamples(hmx_ctx *ctx, const hmx_pel *rec, int stride, const uint8_t *flags, int n_avail, int unit, int n,
+                             int32_t *adi);
+/* hmx_initAdiPattern with the slice / tile / CIP layout of the picture (TComPattern.cpp:213-366 with the availability of
+ * :607-786); luma is smoothed as hmx_initAdiPattern smooths it.  layout = NULL: hmx_initAdiPattern. */
+int hmx_initAdiPattern_layout(hmx_ctx *ctx, const hmx_pel *rec, int stride, int x, int y, int n, int is_chroma,
+                              int pic_w_luma, int pic_h_luma, const hmx_avail_layout *layout, int32_t *adi);
 /* predIntraLumaAng / predIntraChromaAng (TLibCommon/TComPrediction.cpp:338-386) */
 int hmx_predIntraLumaAng(hmx_ctx *ctx, const int32_t *adi, unsigned dir_mode, hmx_pel *pred, unsigned stride,
                          int w, int h);
@@ -317,6 +344,14 @@ int hmx_batch_predIntra(hmx_ctx *ctx, const hmx_tu_list *list, const hmx_pic *re
  * + k] (device).  The 35 predictions stay in registers: 35x less write traffic than hmx_batch_predIntra. */
 int hmx_batch_predIntra_cost(hmx_ctx *ctx, const hmx_tu_list *list, const hmx_pic *rec, const hmx_pic *org,
                              const hmx_pic_param *pp, const uint8_t *d_modes, int n_modes, uint32_t *d_satd);
+/* The two calls above with the slice / tile / CIP layout of the picture (maps in HOST memory; see hmx_avail_layout).
+ * layout = NULL: the calls above, unchanged. */
+int hmx_batch_predIntra_layout(hmx_ctx *ctx, const hmx_tu_list *list, const hmx_pic *rec, const hmx_pic *pred,
+                               const hmx_pic_param *pp, const hmx_avail_layout *layout, const uint8_t *d_modes, int n_modes,
+                               const size_t mode_plane_elems[3]);
+int hmx_batch_predIntra_cost_layout(hmx_ctx *ctx, const hmx_tu_list *list, const hmx_pic *rec, const hmx_pic *org,
+                                    const hmx_pic_param *pp, const hmx_avail_layout *layout, const uint8_t *d_modes, int n_modes,
+                                    uint32_t *d_satd);
 /* Whole-picture all-intra reconstruction from decisions: for every block, refs <- recon, predict,
  * residual, T, Q, IQ, IT, recon (ENC/TEncSearch.cpp:1006-1165 with RDOQ off; DEC/TDecCu.cpp:469-687 for
  * the decode direction).  Blocks are given per picture in coding order on the HOST; the library
@@ -335,6 +370,10 @@ unsigned long long hmx_intra_dependency_mask(int n_samples, int is_luma, int mod
  * the unit-by-unit rule (TComPattern.cpp:607-786); 1: the closed form the device plan builder uses.  Pure host functions,
  * exported for the test that holds one against the other. */
 unsigned long long hmx_intra_avail_mask(int x, int y, int size_luma, int pic_w, int pic_h, int closed_form);
+/* The same with the slice / tile / CIP layout of the picture (CTU size 64; maps in HOST memory): a subset of
+ * hmx_intra_avail_mask(..., 0).  size_luma = 64: the 64 x 64 prediction unit, in units of EIGHT samples (33 bits).  Returns
+ * ~0ull for an invalid layout or block. */
+unsigned long long hmx_intra_avail_mask_layout(int x, int y, int size_luma, int pic_w, int pic_h, const hmx_avail_layout *layout);
 int hmx_intra_plan_create(hmx_ctx *ctx, const hmx_tu *tus, int n_tu, const hmx_pic_param *pp,
                           hmx_intra_plan **plan);
 /* The plans of n_pics pictures (picture i: tus[i][0 .. n_tu[i])): the dependency analysis -- host work, about 43 ms per
@@ -353,6 +392,16 @@ int hmx_intra_plan_create_multi(hmx_ctx *ctx, const hmx_tu *const *tus, const in
  * each with hmx_intra_plan_destroy (the memory is kept for the next call of this context). */
 int hmx_intra_plan_create_device(hmx_ctx *ctx, const hmx_tu *d_tus, const uint32_t *offsets, int n_pics, const hmx_pic_param *pp,
                                  hmx_intra_plan **plans);
+/* The three plan builders with the slice / tile / CIP layout of each picture (see hmx_avail_layout): a block's dependencies
+ * follow the availability with the layout, so a block never waits on another region, and the plans serve every schedule
+ * as before.  _layout / _multi_layout: maps in HOST memory (layouts[i] for picture i); _device_layout: layouts is a HOST
+ * array whose maps are in DEVICE memory.  layouts = NULL (or a NULL entry): the plans of the calls without a layout. */
+int hmx_intra_plan_create_layout(hmx_ctx *ctx, const hmx_tu *tus, int n_tu, const hmx_pic_param *pp, const hmx_avail_layout *layout,
+                                 hmx_intra_plan **plan);
+int hmx_intra_plan_create_multi_layout(hmx_ctx *ctx, const hmx_tu *const *tus, const int *n_tu, int n_pics, const hmx_pic_param *pp,
+                                       const hmx_avail_layout *const *layouts, hmx_intra_plan **plans);
+int hmx_intra_plan_create_device_layout(hmx_ctx *ctx, const hmx_tu *d_tus, const uint32_t *offsets, int n_pics, const hmx_pic_param *pp,
+                                        const hmx_avail_layout *const *layouts, hmx_intra_plan **plans);
 void hmx_intra_plan_destroy(hmx_ctx *ctx, hmx_intra_plan *plan);
 /* The plans of a batch at once (waits ONCE for the context's stream: hmx_intra_plan_destroy does so per plan). */
 void hmx_intra_plan_destroy_many(hmx_ctx *ctx, hmx_intra_plan *const *plans, int n);

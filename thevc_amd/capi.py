@@ -83,6 +83,34 @@ class McJob(C.Structure):  # hmx_mc_job
 _lib = None
 
 
+class AvailLayout(C.Structure):  # hmx_avail_layout
+    _fields_ = [("ctu_region", C.c_void_p), ("n_ctu", C.c_int), ("constrained_intra_pred", C.c_int), ("intra_unit", C.c_void_p),
+                ("intra_stride", C.c_int), ("intra_rows", C.c_int)]
+
+
+class Layout:
+    """The slice / tile / constrained-intra layout of one picture (hmx_avail_layout) over numpy arrays it keeps alive:
+    region = region id per CTU (raster order) or None, intra = per-4x4-luma-unit intra flags (2-D) or None (CIP off)."""
+
+    def __init__(self, region=None, intra=None):
+        self.region = None if region is None else np.ascontiguousarray(region, np.uint32).reshape(-1)
+        self.intra = None if intra is None else np.ascontiguousarray(intra, np.uint8)
+        self.s = AvailLayout()
+        if self.region is not None:
+            self.s.ctu_region, self.s.n_ctu = self.region.ctypes.data, self.region.size
+        if self.intra is not None:
+            self.s.constrained_intra_pred = 1
+            self.s.intra_unit = self.intra.ctypes.data
+            self.s.intra_rows, self.s.intra_stride = self.intra.shape
+
+    def ref(self):
+        return C.byref(self.s)
+
+
+def _layout_ref(layout):
+    return None if layout is None else layout.ref()
+
+
 def lib():
     """Load libhmx.so; fails loudly when the HIP library has not been built."""
     global _lib
@@ -163,6 +191,17 @@ def lib():
         L.hmx_intra_plan_create_multi.argtypes = [vp, C.POINTER(vp), C.POINTER(ci), ci, C.POINTER(PicParam), C.POINTER(vp)]
         L.hmx_intra_plan_create_device.argtypes = [vp, vp, C.POINTER(C.c_uint32), ci, C.POINTER(PicParam), C.POINTER(vp)]
         L.hmx_intra_plan_download.argtypes = [vp, vp, vp, vp]
+        LP = C.POINTER(AvailLayout)
+        L.hmx_intra_avail_mask_layout.argtypes = [ci, ci, ci, ci, ci, LP]
+        L.hmx_intra_avail_mask_layout.restype = C.c_uint64
+        L.hmx_intra_plan_create_layout.argtypes = [vp, vp, ci, C.POINTER(PicParam), LP, C.POINTER(vp)]
+        L.hmx_intra_plan_create_multi_layout.argtypes = [vp, C.POINTER(vp), C.POINTER(ci), ci, C.POINTER(PicParam), C.POINTER(LP), C.POINTER(vp)]
+        L.hmx_intra_plan_create_device_layout.argtypes = [vp, vp, C.POINTER(C.c_uint32), ci, C.POINTER(PicParam), C.POINTER(LP), C.POINTER(vp)]
+        L.hmx_batch_predIntra_layout.argtypes = [vp, vp, C.POINTER(Pic), C.POINTER(Pic), C.POINTER(PicParam), LP, vp, ci,
+                                                 C.POINTER(C.c_size_t * 3)]
+        L.hmx_batch_predIntra_cost_layout.argtypes = [vp, vp, C.POINTER(Pic), C.POINTER(Pic), C.POINTER(PicParam), LP, vp, ci, vp]
+        L.hmx_fillReferenceSamples.argtypes = [vp, vp, ci, vp, ci, ci, ci, vp]
+        L.hmx_initAdiPattern_layout.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, ci, LP, vp]
         L.hmx_intra_plan_destroy_many.argtypes = [vp, C.POINTER(vp), ci]
         L.hmx_intra_plan_destroy_many.restype = None
         L.hmx_last_call_tables_ms.argtypes = [vp, C.POINTER(C.c_float)]
@@ -412,6 +451,23 @@ class Context:
         self._chk(lib().hmx_initAdiPattern(self.h, _hp(rec), stride, x, y, n, is_chroma, pic_w, pic_h, _hp(adi)))
         return adi
 
+    def initAdiPattern_layout(self, rec, stride, x, y, n, is_chroma, pic_w, pic_h, layout=None):
+        rec = np.ascontiguousarray(rec, np.int16)
+        W = 2 * n + 1
+        adi = np.zeros(2 * W * W, np.int32)
+        self._chk(lib().hmx_initAdiPattern_layout(self.h, _hp(rec), stride, x, y, n, is_chroma, pic_w, pic_h, _layout_ref(layout), _hp(adi)))
+        return adi
+
+    def fillReferenceSamples(self, rec, origin, stride, flags, n_avail, unit, n, adi=None):
+        """hmx_fillReferenceSamples: rec = flat int16 plane, origin = element offset of the block's sample (0,0).  Only the
+        border cells of adi (row 0, column 0) are written, as the reference writes them."""
+        rec = np.ascontiguousarray(rec, np.int16)
+        flags = np.ascontiguousarray(flags, np.uint8)
+        W = 2 * n + 1
+        adi = np.zeros(W * W, np.int32) if adi is None else adi
+        self._chk(lib().hmx_fillReferenceSamples(self.h, C.c_void_p(rec.ctypes.data + 2 * origin), stride, _hp(flags), n_avail, unit, n, _hp(adi)))
+        return adi
+
     def predIntraLumaAng(self, adi, mode, stride, n):
         adi = np.ascontiguousarray(adi, np.int32)
         pred = np.zeros(n * stride, np.int16)
@@ -468,20 +524,29 @@ class Context:
         self._chk(lib().hmx_tu_list_create(self.h, _hp(tus), len(tus), C.byref(h)))
         return h
 
-    def intra_plan(self, tus, pp):
+    def intra_plan(self, tus, pp, layout=None):
+        """hmx_intra_plan_create (layout None) / hmx_intra_plan_create_layout (a Layout)."""
         tus = np.ascontiguousarray(tus, TU_DTYPE)
         h = C.c_void_p()
-        self._chk(lib().hmx_intra_plan_create(self.h, _hp(tus), len(tus), C.byref(pp), C.byref(h)))
+        if layout is None:
+            self._chk(lib().hmx_intra_plan_create(self.h, _hp(tus), len(tus), C.byref(pp), C.byref(h)))
+        else:
+            self._chk(lib().hmx_intra_plan_create_layout(self.h, _hp(tus), len(tus), C.byref(pp), layout.ref(), C.byref(h)))
         return h
 
-    def intra_plans(self, tus_list, pp):
-        """hmx_intra_plan_create_multi: the plans of several pictures, their host-side analysis on all host threads."""
+    def intra_plans(self, tus_list, pp, layouts=None):
+        """hmx_intra_plan_create_multi: the plans of several pictures, their host-side analysis on all host threads.
+        layouts: None, or one Layout (or None) per picture (hmx_intra_plan_create_multi_layout)."""
         arrs = [np.ascontiguousarray(t, TU_DTYPE) for t in tus_list]
         n = len(arrs)
         ptrs = (C.c_void_p * n)(*[a.ctypes.data for a in arrs])
         cnts = (C.c_int * n)(*[len(a) for a in arrs])
         out = (C.c_void_p * n)()
-        self._chk(lib().hmx_intra_plan_create_multi(self.h, ptrs, cnts, n, C.byref(pp), out))
+        if layouts is None:
+            self._chk(lib().hmx_intra_plan_create_multi(self.h, ptrs, cnts, n, C.byref(pp), out))
+        else:
+            lp = (C.POINTER(AvailLayout) * n)(*[C.pointer(l.s) if l is not None else C.POINTER(AvailLayout)() for l in layouts])
+            self._chk(lib().hmx_intra_plan_create_multi_layout(self.h, ptrs, cnts, n, C.byref(pp), lp, out))
         return [C.c_void_p(out[i]) for i in range(n)]
 
 
@@ -492,6 +557,39 @@ class Context:
         off = (C.c_uint32 * (n + 1))(*[int(o) for o in offsets])
         out = (C.c_void_p * n)()
         self._chk(lib().hmx_intra_plan_create_device(self.h, d_tus, off, n, C.byref(pp), out))
+        return [C.c_void_p(out[i]) for i in range(n)]
+
+    def intra_plans_device_layout(self, d_tus, offsets, pp, layouts):
+        """hmx_intra_plan_create_device_layout: as intra_plans_device, with one Layout (or None) per picture whose maps are
+        copied to the device for the call."""
+        n = len(offsets) - 1
+        off = (C.c_uint32 * (n + 1))(*[int(o) for o in offsets])
+        out = (C.c_void_p * n)()
+        keep, structs = [], []
+        for l in layouts:
+            if l is None:
+                structs.append(C.POINTER(AvailLayout)())
+                continue
+            s = AvailLayout()
+            s.n_ctu, s.constrained_intra_pred, s.intra_stride, s.intra_rows = l.s.n_ctu, l.s.constrained_intra_pred, l.s.intra_stride, l.s.intra_rows
+            if l.region is not None:
+                d = self.to_device(l.region)
+                keep.append(d)
+                s.ctu_region = d.ptr
+            if l.intra is not None:
+                d = self.to_device(l.intra)
+                keep.append(d)
+                s.intra_unit = d.ptr
+            keep.append(s)
+            structs.append(C.pointer(s))
+        lp = (C.POINTER(AvailLayout) * n)(*structs)
+        try:
+            self._chk(lib().hmx_intra_plan_create_device_layout(self.h, d_tus, off, n, C.byref(pp), lp, out))
+        finally:
+            self.sync()
+            for d in keep:
+                if isinstance(d, DevBuf):
+                    d.free()
         return [C.c_void_p(out[i]) for i in range(n)]
 
 

@@ -428,6 +428,87 @@ __host__ __device__ __forceinline__ unsigned long long intra_avail_mask_ctu(int 
   return m;
 }
 
+// Slices, tiles and constrained intra prediction (hmx_avail_layout, packed by the host entry points).  A region is one
+// (independent slice, tile) pair; CTUs see each other only inside their region (TComDataCU.cpp:1221-1735: getPU* with
+// bEnforceSliceRestriction / the getTileIdxMap checks; TComPattern calls them with bEnforceDependentSliceRestriction = false,
+// so dependent slices do not split regions).  With constrained_intra_pred_flag a neighbour unit that is not intra-coded is
+// unavailable (TComPattern.cpp:607-786, isAbove/Left/AboveLeft...Available).  The intra flags are kept twice, bit-packed along
+// unit rows (the above run of a block is one 64-bit window) and along unit columns (the left run likewise).
+struct AvailDev {
+  const uint32_t *region; // region id per CTU, raster order; NULL = one region
+  const uint32_t *rows;   // intra flag of 4x4 luma unit (ux, uy): bit ux & 31 of rows[uy * row_words + (ux >> 5)]; NULL = CIP off
+  const uint32_t *cols;   // the same transposed: bit uy & 31 of cols[ux * col_words + (uy >> 5)]
+  int row_words, col_words;
+  int cw, ctu_log2; // CTUs per row, log2 of the CTU size
+};
+// 64 bits of a packed line from bit `pos` on (at least 33 of them; bits past the line's end read as 0)
+__host__ __device__ __forceinline__ unsigned long long avail_bits64(const uint32_t *line, int words, int pos) {
+  const int w = pos >> 5, s = pos & 31;
+  unsigned long long v = w < words ? line[w] : 0u;
+  if (w + 1 < words) v |= (unsigned long long)line[w + 1] << 32;
+  return v >> s;
+}
+__host__ __device__ __forceinline__ unsigned avail_even_bits(unsigned long long v) { // bits 0, 2, 4, .. 62 -> 0 .. 31
+  v &= 0x5555555555555555ull;
+  v = (v | (v >> 1)) & 0x3333333333333333ull;
+  v = (v | (v >> 2)) & 0x0f0f0f0f0f0f0f0full;
+  v = (v | (v >> 4)) & 0x00ff00ff00ff00ffull;
+  v = (v | (v >> 8)) & 0x0000ffff0000ffffull;
+  return (unsigned)(v | (v >> 16));
+}
+__host__ __device__ __forceinline__ unsigned avail_rev32(unsigned v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __brev(v);
+#else
+  v = ((v >> 1) & 0x55555555u) | ((v & 0x55555555u) << 1);
+  v = ((v >> 2) & 0x33333333u) | ((v & 0x33333333u) << 2);
+  v = ((v >> 4) & 0x0f0f0f0fu) | ((v & 0x0f0f0f0fu) << 4);
+  v = ((v >> 8) & 0x00ff00ffu) | ((v & 0x00ff00ffu) << 8);
+  return (v >> 16) | (v << 16);
+#endif
+}
+// The geometric mask m of a block at luma (x, y), luma size `size`, in units of 1 << ulog2 luma samples (2: the 4n + 1 units of
+// intra_avail_mask, 3: the 64 x 64 prediction unit of intra_avail_mask_ctu), cut down to the layout: a subset of m, never more
+// (a unit that geometry says is not yet coded stays unavailable, so every schedule built on m stays valid).  At most four region
+// lookups (left, above-left, above, above-right CTU) and three windows of the intra bitmaps.
+__host__ __device__ __forceinline__ unsigned long long intra_avail_mask_layout(unsigned long long m, int x, int y, int size, int ulog2,
+                                                                              const AvailDev &L) {
+  const int n = size >> ulog2, cl = L.ctu_log2;
+  const unsigned long long left_run = (1ull << (2 * n)) - 1, corner = 1ull << (2 * n), above_run = ((1ull << (2 * n)) - 1) << (2 * n + 1);
+  if (L.region && m) {
+    const int cx = x >> cl, cy = y >> cl;
+    const uint32_t r = L.region[cy * L.cw + cx];
+    // left and below-left: the available ones lie in the CTU row of the block, in CTU ((x - 1) >> cl)
+    if ((m & left_run) && ((x - 1) >> cl) != cx && L.region[cy * L.cw + cx - 1] != r) m &= ~left_run;
+    if (m & corner) {
+      const int ax = (x - 1) >> cl, ay = (y - 1) >> cl;
+      if ((ax != cx || ay != cy) && L.region[ay * L.cw + ax] != r) m &= ~corner;
+    }
+    if ((m & above_run) && ((y - 1) >> cl) != cy) { // the above run in the CTU row above: CTU cx, then cx + 1 (above-right)
+      const int ay = (y - 1) >> cl, k = (((cx + 1) << cl) - x) >> ulog2; // units of the run above CTU cx
+      const unsigned long long own = k >= 2 * n ? above_run : (((1ull << k) - 1) << (2 * n + 1));
+      if ((m & own) && L.region[ay * L.cw + cx] != r) m &= ~own;
+      if ((m & above_run & ~own) && L.region[ay * L.cw + cx + 1] != r) m &= ~(above_run & ~own);
+    }
+  }
+  if (L.rows && m) {
+    const int ux = x >> 2, uy = y >> 2, run = 2 * n;
+    unsigned long long keep = 0;
+    if (y > 0) { // above and above-right: unit row uy - 1 from column ux
+      const unsigned long long a = avail_bits64(L.rows + (size_t)(uy - 1) * L.row_words, L.row_words, ux);
+      keep |= ((ulog2 == 3 ? (unsigned long long)avail_even_bits(a) : a) & left_run) << (2 * n + 1);
+    }
+    if (x > 0) { // left and below-left: unit column ux - 1 from row uy; the mask counts from the bottom
+      const unsigned long long l = avail_bits64(L.cols + (size_t)(ux - 1) * L.col_words, L.col_words, uy);
+      const unsigned v = (unsigned)((ulog2 == 3 ? (unsigned long long)avail_even_bits(l) : l) & left_run);
+      keep |= (unsigned long long)(avail_rev32(v) >> (32 - run));
+      if (y > 0 && ((L.rows[(size_t)(uy - 1) * L.row_words + ((ux - 1) >> 5)] >> ((ux - 1) & 31)) & 1u)) keep |= corner;
+    }
+    m &= keep;
+  }
+  return m;
+}
+
 // Reference line of a block: L[0..4N], L[0] = lowest below-left sample, L[2N] = corner,
 // L[4N] = right-most above-right sample (fillReferenceSamples, TComPattern.cpp:368-552).
 // Every sample is one independent load: an unavailable sample copies the nearest available

@@ -51,7 +51,7 @@ static_assert(64 * sizeof(TuLds<4>) <= HMX_SMEM_BYTES && 32 * sizeof(TuLds<8>) <
                   4 * sizeof(TuLds<32>) <= HMX_SMEM_BYTES && sizeof(TuLds<64>) <= HMX_SMEM_BYTES,
               "LDS scratch");
 
-enum ListOp { OP_TRANSFORM_NXN, OP_INVTRANSFORM_NXN, OP_XT, OP_XIT, OP_XQUANT, OP_XDEQUANT, OP_PRED, OP_TRANSFORM_RECON };
+enum ListOp { OP_TRANSFORM_NXN, OP_INVTRANSFORM_NXN, OP_XT, OP_XIT, OP_XQUANT, OP_XDEQUANT, OP_PRED, OP_TRANSFORM_RECON, OP_PRED_LAYOUT };
 
 struct ListPic { // planes of one picture of a multi-picture list call
   PlanesDev a, b;
@@ -76,6 +76,7 @@ struct ListArgs {
   int n_modes;
   size_t mode_elems[3];
   PicDev P;
+  AvailDev lay; // OP_PRED_LAYOUT: the slice / tile / CIP layout of the picture
 };
 
 template <typename T>
@@ -394,6 +395,14 @@ int pack_group_size(const hmx_ctx *c, int n_pics);
 int launch_op(hmx_ctx *c, int op, int log2n, const ListArgs &A);                  // hmx_list.hip
 unsigned long long intra_dependency_mask(int n_s, bool luma, int mode, unsigned long long avail); // hmx_plan.hip
 int plan_host_tables(hmx_ctx *c, const hmx_intra_plan *pl); // device-built plan: fetch the level table for the level schedule / queries
+// a slice / tile / CIP layout (hmx_avail_layout) checked against the picture and packed for intra_avail_mask_layout; H.D points
+// into H's vectors (host use), layout_to_device puts a copy of the maps in the argument arena (device use)   // hmx_plan.hip
+struct LayoutHost {
+  std::vector<uint32_t> region, rows, cols;
+  AvailDev D{};
+};
+const char *layout_pack(const hmx_avail_layout *L, int pic_w, int pic_h, int ctu, LayoutHost &H, bool maps_on_device = false);
+int layout_to_device(hmx_ctx *c, const LayoutHost &H, AvailDev &D);
 // the packed schedule's kernel with RDOQ as the quantiser lives in hmx_chain_rdoq.hip
 struct PackArgs;
 int packed_rdoq_max_blocks(int *nb);

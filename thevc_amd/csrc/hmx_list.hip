@@ -115,11 +115,13 @@ __global__ __launch_bounds__(256) void k_list(ListArgs A) {
       }
       store_row32<N>(lev2_p + (size_t)(y + gl) * lev2_s + x, row);
     }
-  } else { // OP_PRED
+  } else { // OP_PRED, OP_PRED_LAYOUT
     const int sh = luma ? 0 : 1;
     unsigned long long avail = 0;
     if constexpr (N == 64) avail = active ? intra_avail_mask_ctu(x, y, A.P) : 0; // a whole CTU, luma (hmx_tu_list_create checks)
     else avail = active ? intra_avail_mask(x << sh, y << sh, N << sh, A.P) : 0;
+    if constexpr (OP == OP_PRED_LAYOUT) // slices, tiles, constrained intra pred: a subset of the geometric mask
+      avail = active ? intra_avail_mask_layout(avail, x << sh, y << sh, N << sh, N == 64 ? 3 : 2, A.lay) : 0;
     const short *rec0 = a_p + (size_t)y * a_s + x;
     const int rst = a_s;
     intra_refs<N, N>(L, gl, active, [&](int dx, int dy) { return (int)rec0[(ptrdiff_t)dy * rst + dx]; }, luma, avail, A.P);
@@ -282,7 +284,7 @@ static int launch_list(hmx_ctx *c, int log2n, const ListArgs &A) {
   case 4: hipLaunchKernelGGL((k_list<16, OP>), dim3((A.n + Slots<16>::v - 1) / Slots<16>::v, ny), blk, 0, c->stream, A); break;
   case 5: hipLaunchKernelGGL((k_list<32, OP>), dim3((A.n + Slots<32>::v - 1) / Slots<32>::v, ny), blk, 0, c->stream, A); break;
   case 6: // 64 x 64: the luma prediction unit of a 64 x 64 coding unit (TEncSearch.cpp:2509-2540); no transform of that size exists
-    if constexpr (OP == OP_PRED) {
+    if constexpr (OP == OP_PRED || OP == OP_PRED_LAYOUT) {
       hipLaunchKernelGGL((k_list<64, OP>), dim3((unsigned)A.n, ny), blk, 0, c->stream, A);
       break;
     } else {
@@ -303,6 +305,7 @@ int launch_op(hmx_ctx *c, int op, int log2n, const ListArgs &A) {
   case OP_XQUANT: return launch_list<OP_XQUANT>(c, log2n, A);
   case OP_XDEQUANT: return launch_list<OP_XDEQUANT>(c, log2n, A);
   case OP_TRANSFORM_RECON: return launch_list<OP_TRANSFORM_RECON>(c, log2n, A);
+  case OP_PRED_LAYOUT: return launch_list<OP_PRED_LAYOUT>(c, log2n, A);
   default: return launch_list<OP_PRED>(c, log2n, A);
   }
 }
@@ -356,7 +359,7 @@ extern "C" void hmx_tu_list_destroy(hmx_ctx *c, hmx_tu_list *l) {
 }
 
 static int run_list(hmx_ctx *c, int op, const hmx_tu_list *l, ListArgs A) {
-  if (l->cnt[4] && op != OP_PRED) return fail(c, HMX_ERR_ARG, "the list holds 64x64 blocks: intra prediction only (the largest transform is 32x32)");
+  if (l->cnt[4] && op != OP_PRED && op != OP_PRED_LAYOUT) return fail(c, HMX_ERR_ARG, "the list holds 64x64 blocks: intra prediction only (the largest transform is 32x32)");
   for (int s = 0; s < 5; s++) {
     if (!l->cnt[s]) continue;
     A.tus = l->d + l->off[s];
@@ -494,3 +497,42 @@ extern "C" int hmx_batch_predIntra_cost(hmx_ctx *c, const hmx_tu_list *l, const 
   return run_list(c, OP_PRED, l, A);
 }
 
+
+// The two prediction calls with a slice / tile / CIP layout: the maps travel in the argument arena, the kernels AND the layout
+// onto the geometric availability (OP_PRED_LAYOUT; the calls without a layout keep their instantiations)
+static int pred_layout(hmx_ctx *c, const hmx_tu_list *l, ListArgs &A, const hmx_pic_param *pp, const hmx_avail_layout *layout) {
+  if (!layout) return run_list(c, OP_PRED, l, A);
+  LayoutHost H;
+  if (const char *e = layout_pack(layout, pp->pic_w, pp->pic_h, c->cfg.ctu_size, H)) return fail(c, HMX_ERR_ARG, e);
+  if (int r = layout_to_device(c, H, A.lay)) return r;
+  return run_list(c, OP_PRED_LAYOUT, l, A);
+}
+
+extern "C" int hmx_batch_predIntra_layout(hmx_ctx *c, const hmx_tu_list *l, const hmx_pic *rec, const hmx_pic *pred,
+                                          const hmx_pic_param *pp, const hmx_avail_layout *layout, const uint8_t *d_modes, int n_modes,
+                                          const size_t mode_plane_elems[3]) {
+  if (!c || !l || !rec || !pred || !pp) return fail(c, HMX_ERR_ARG, "hmx_batch_predIntra_layout: null argument");
+  ListArgs A{};
+  A.a = to_dev(rec);
+  A.b = to_dev(pred);
+  A.P = make_picdev(c, pp);
+  A.modes = d_modes;
+  A.n_modes = d_modes ? n_modes : 0;
+  for (int i = 0; i < 3; i++) A.mode_elems[i] = mode_plane_elems ? mode_plane_elems[i] : 0;
+  return pred_layout(c, l, A, pp, layout);
+}
+
+extern "C" int hmx_batch_predIntra_cost_layout(hmx_ctx *c, const hmx_tu_list *l, const hmx_pic *rec, const hmx_pic *org,
+                                               const hmx_pic_param *pp, const hmx_avail_layout *layout, const uint8_t *d_modes, int n_modes,
+                                               uint32_t *d_satd) {
+  if (!c || !l || !rec || !org || !pp || !d_satd || (d_modes && (n_modes <= 0 || n_modes > 35)))
+    return fail(c, HMX_ERR_ARG, "hmx_batch_predIntra_cost_layout: bad argument");
+  ListArgs A{};
+  A.a = to_dev(rec);
+  A.org = to_dev(org);
+  A.cost = d_satd;
+  A.P = make_picdev(c, pp);
+  A.modes = d_modes;
+  A.n_modes = d_modes ? n_modes : 0;
+  return pred_layout(c, l, A, pp, layout);
+}

@@ -100,6 +100,52 @@ extern "C" unsigned long long hmx_intra_dependency_mask(int n_samples, int is_lu
   return intra_dependency_mask(n_samples, is_luma != 0, mode, avail);
 }
 
+// A slice / tile / CIP layout checked against the picture and packed for intra_avail_mask_layout (hmx_device.h): the region map as
+// it is, the intra flags as two bitmaps (along unit rows and along unit columns).  NULL maps: nothing to pack, H.D is all NULL and
+// the layout mask is the geometric one.
+const char *layout_pack(const hmx_avail_layout *L, int pic_w, int pic_h, int ctu, LayoutHost &H, bool maps_on_device) {
+  H = LayoutHost{};
+  if (!L) return nullptr;
+  if (ctu != 16 && ctu != 32 && ctu != 64) return "hmx_avail_layout: CTU size 16, 32 or 64";
+  const int cw = (pic_w + ctu - 1) / ctu, ch = (pic_h + ctu - 1) / ctu, uw = (pic_w + 3) / 4, uh = (pic_h + 3) / 4;
+  H.D.cw = cw;
+  H.D.ctu_log2 = ilog2i(ctu);
+  if (L->ctu_region) {
+    if (L->n_ctu != cw * ch) return "hmx_avail_layout: n_ctu is not the picture's number of CTUs";
+    if (!maps_on_device) H.region.assign(L->ctu_region, L->ctu_region + (size_t)cw * ch);
+  } else if (L->n_ctu != 0 && L->n_ctu != cw * ch) {
+    return "hmx_avail_layout: n_ctu is not the picture's number of CTUs";
+  }
+  if (L->constrained_intra_pred) {
+    if (!L->intra_unit) return "hmx_avail_layout: constrained intra pred needs the intra_unit map";
+    if (L->intra_stride < uw || L->intra_rows < uh) return "hmx_avail_layout: intra_unit smaller than the picture's 4x4 units";
+    H.D.row_words = (uw + 31) / 32, H.D.col_words = (uh + 31) / 32;
+    if (maps_on_device) return nullptr; // (packed by k_pack_intra)
+    H.rows.assign((size_t)uh * H.D.row_words, 0u);
+    H.cols.assign((size_t)uw * H.D.col_words, 0u);
+    for (int uy = 0; uy < uh; uy++)
+      for (int ux = 0; ux < uw; ux++)
+        if (L->intra_unit[(size_t)uy * L->intra_stride + ux]) {
+          H.rows[(size_t)uy * H.D.row_words + (ux >> 5)] |= 1u << (ux & 31);
+          H.cols[(size_t)ux * H.D.col_words + (uy >> 5)] |= 1u << (uy & 31);
+        }
+  }
+  H.D.region = H.region.empty() ? nullptr : H.region.data();
+  H.D.rows = H.rows.empty() ? nullptr : H.rows.data();
+  H.D.cols = H.cols.empty() ? nullptr : H.cols.data();
+  return nullptr;
+}
+int layout_to_device(hmx_ctx *c, const LayoutHost &H, AvailDev &D) {
+  D = H.D;
+  auto put = [&](const std::vector<uint32_t> &v, const uint32_t *&dst) -> bool {
+    if (v.empty()) return true;
+    dst = static_cast<const uint32_t *>(arena_push(c, v.data(), v.size() * sizeof(uint32_t)));
+    return dst != nullptr;
+  };
+  if (!put(H.region, D.region) || !put(H.rows, D.rows) || !put(H.cols, D.cols)) return fail(c, HMX_ERR_NOMEM, "argument arena (layout maps)");
+  return HMX_OK;
+}
+
 // The host half of a plan: the dependency analysis of one picture's decisions.  Touches nothing of the context but its
 // configuration, so the pictures of a batch are analysed on as many host threads as there are (hmx_intra_plan_create_multi):
 // 45 ms per 2160p picture on one core is 500x the picture's share of a whole-picture call.
@@ -113,8 +159,12 @@ struct PlanHost {
   PicDev P;
   int n_tu = 0;
 };
-static const char *plan_build_host(const hmx_ctx *c, const hmx_tu *tus, int n_tu, const hmx_pic_param *pp, PlanHost &H) {
+static const char *plan_build_host(const hmx_ctx *c, const hmx_tu *tus, int n_tu, const hmx_pic_param *pp, PlanHost &H,
+                                   const hmx_avail_layout *layout = nullptr) {
   const int ctu = c->cfg.ctu_size, U = ctu / 4;
+  LayoutHost lay;
+  if (const char *e = layout_pack(layout, pp->pic_w, pp->pic_h, ctu, lay)) return e;
+  const bool use_layout = lay.D.region || lay.D.rows;
   const int cw = (pp->pic_w + ctu - 1) / ctu, ch = (pp->pic_h + ctu - 1) / ctu, n_ctu = cw * ch;
   PicDev P = make_picdev(c, pp);
   // bucket blocks per (CTU, plane), keeping coding order
@@ -143,6 +193,7 @@ static const char *plan_build_host(const hmx_ctx *c, const hmx_tu *tus, int n_tu
       const int sh = t.plane ? 1 : 0, lx = t.x << sh, ly = t.y << sh, ls = (1 << t.log2n) << sh;
       const int n = ls / 4, cx = (lx % ctu) / 4, cy = (ly % ctu) / 4;
       unsigned long long m = intra_avail_mask(lx, ly, ls, P);
+      if (use_layout) m = intra_avail_mask_layout(m, lx, ly, ls, 2, lay.D); // a subset: the schedules below stay valid
       masks[id] = m;
       m = intra_dependency_mask(1 << t.log2n, t.plane == 0, t.mode, m); // the order follows what the mode reads
       deps[id] = m;
@@ -322,8 +373,25 @@ extern "C" int hmx_intra_plan_create(hmx_ctx *c, const hmx_tu *tus, int n_tu, co
   if (const char *e = plan_build_host(c, tus, n_tu, pp, H)) return fail(c, HMX_ERR_ARG, e);
   return plan_upload(c, H, pp, out);
 }
+extern "C" int hmx_intra_plan_create_layout(hmx_ctx *c, const hmx_tu *tus, int n_tu, const hmx_pic_param *pp, const hmx_avail_layout *layout,
+                                            hmx_intra_plan **out) {
+  if (!c || !tus || !pp || !out || n_tu <= 0) return fail(c, HMX_ERR_ARG, "hmx_intra_plan_create_layout: bad argument");
+  PlanHost H;
+  if (const char *e = plan_build_host(c, tus, n_tu, pp, H, layout)) return fail(c, HMX_ERR_ARG, e);
+  return plan_upload(c, H, pp, out);
+}
+static int plan_create_multi(hmx_ctx *c, const hmx_tu *const *tus, const int *n_tu, int n_pics, const hmx_pic_param *pp,
+                             const hmx_avail_layout *const *layouts, hmx_intra_plan **out);
 extern "C" int hmx_intra_plan_create_multi(hmx_ctx *c, const hmx_tu *const *tus, const int *n_tu, int n_pics, const hmx_pic_param *pp,
                                            hmx_intra_plan **out) {
+  return plan_create_multi(c, tus, n_tu, n_pics, pp, nullptr, out);
+}
+extern "C" int hmx_intra_plan_create_multi_layout(hmx_ctx *c, const hmx_tu *const *tus, const int *n_tu, int n_pics, const hmx_pic_param *pp,
+                                                  const hmx_avail_layout *const *layouts, hmx_intra_plan **out) {
+  return plan_create_multi(c, tus, n_tu, n_pics, pp, layouts, out);
+}
+static int plan_create_multi(hmx_ctx *c, const hmx_tu *const *tus, const int *n_tu, int n_pics, const hmx_pic_param *pp,
+                             const hmx_avail_layout *const *layouts, hmx_intra_plan **out) {
   if (!c || !tus || !n_tu || !pp || !out || n_pics <= 0) return fail(c, HMX_ERR_ARG, "hmx_intra_plan_create_multi: bad argument");
   for (int i = 0; i < n_pics; i++) {
     out[i] = nullptr;
@@ -344,7 +412,7 @@ extern "C" int hmx_intra_plan_create_multi(hmx_ctx *c, const hmx_tu *const *tus,
       auto work = [&](int t) {
         for (int i = t; i < n; i += T) {
           try {
-            err[i] = plan_build_host(c, tus[base + i], n_tu[base + i], pp, H[i]);
+            err[i] = plan_build_host(c, tus[base + i], n_tu[base + i], pp, H[i], layouts ? layouts[base + i] : nullptr);
           } catch (...) {
             err[i] = kOom;
           }
@@ -526,6 +594,24 @@ struct PlanGeomDev {
 };
 enum PlanErr { PLAN_OK = 0, PLAN_BAD_BLOCK = 1, PLAN_CROSSES_CTU = 2, PLAN_OUTSIDE = 3, PLAN_ORDER = 4, PLAN_TOO_LARGE = 5 };
 
+// The intra flags of a layout whose maps are in device memory, bit-packed as layout_pack packs them: one thread per word of the row
+// bitmap, then per word of the column bitmap.
+__global__ __launch_bounds__(256) void k_pack_intra(const uint8_t *src, int stride, int uw, int uh, uint32_t *rows, int row_words,
+                                                    uint32_t *cols, int col_words) {
+  const int i = blockIdx.x * 256 + threadIdx.x, n_rows = uh * row_words;
+  if (i < n_rows) {
+    const int uy = i / row_words, ux0 = (i - uy * row_words) * 32;
+    uint32_t w = 0;
+    for (int k = 0; k < 32 && ux0 + k < uw; k++) w |= (src[(size_t)uy * stride + ux0 + k] ? 1u : 0u) << k;
+    rows[i] = w;
+  } else if (i < n_rows + uw * col_words) {
+    const int j = i - n_rows, ux = j / col_words, uy0 = (j - ux * col_words) * 32;
+    uint32_t w = 0;
+    for (int k = 0; k < 32 && uy0 + k < uh; k++) w |= (src[(size_t)(uy0 + k) * stride + ux] ? 1u : 0u) << k;
+    cols[j] = w;
+  }
+}
+
 __device__ __forceinline__ int plan_ctu_of(const hmx_tu &t, int cw) {
   const int sh = t.plane ? 1 : 0;
   return ((t.y << sh) >> 6) * cw + ((t.x << sh) >> 6);
@@ -548,8 +634,11 @@ __device__ __forceinline__ unsigned long long plan_dep_mask(const unsigned long 
 // What the level walk needs of a block, one 64-bit word: bits 0..39 the units it depends on (4n + 1 <= 33 of them), 40..43 / 44..47
 // its unit column / row inside the CTU, 48..51 its size n in units (1..8), 52..53 its plane, 54..55 its transform size class.  Formed here, one thread per block,
 // so that the walk -- sequential per CTU -- is left with LDS reads and one maximum per dependency.
+// LAYOUT: each picture's slice / tile / CIP layout (lays[pic]) cuts the availability down; the plain instantiation is the one without.
+template <bool LAYOUT>
 __global__ __launch_bounds__(256) void k_plan_ctus(const hmx_tu *tus, const uint32_t *pic_off, uint32_t *ctu_start, uint32_t *size_total,
-                                                   uint32_t *err, const unsigned long long *need, unsigned long long *rec, FTu *ftu, PlanGeomDev G) {
+                                                   uint32_t *err, const unsigned long long *need, unsigned long long *rec, FTu *ftu, PlanGeomDev G,
+                                                   const AvailDev *lays) {
   const int pic = blockIdx.y;
   const uint32_t b0 = pic_off[pic], n = pic_off[pic + 1] - b0, i = blockIdx.x * 256 + threadIdx.x;
   uint32_t *cs = ctu_start + (size_t)pic * (G.n_ctu + 1);
@@ -571,7 +660,8 @@ __global__ __launch_bounds__(256) void k_plan_ctus(const hmx_tu *tus, const uint
       const int ctu = plan_ctu_of(t, G.cw);
       {
         const int sh = t.plane ? 1 : 0, lx = t.x << sh, ly = t.y << sh, ls = (1 << t.log2n) << sh;
-        const unsigned long long avail = intra_avail_mask_fast(lx, ly, ls, G.P);
+        unsigned long long avail = intra_avail_mask_fast(lx, ly, ls, G.P);
+        if constexpr (LAYOUT) avail = intra_avail_mask_layout(avail, lx, ly, ls, 2, lays[pic]);
         const unsigned long long dep = plan_dep_mask(need, t.log2n, t.plane == 0, t.mode, avail);
         ftu[b0 + i] = FTu{t, (uint32_t)dep, (uint32_t)(dep >> 32)}; // the descriptor as the chain wants it (plan_build_host: the units read stand for the availability), moved into place by k_plan_gather
         rec[b0 + i] = dep | (unsigned long long)((lx & 63) >> 2) << 40 | (unsigned long long)((ly & 63) >> 2) << 44 | (unsigned long long)(ls >> 2) << 48 |
@@ -918,8 +1008,58 @@ void *plan_slab(hmx_ctx *c, size_t bytes, size_t *got) { // a cached slab that f
 }
 } // namespace
 
+static int plan_create_device(hmx_ctx *c, const hmx_tu *d_tus, const uint32_t *offsets, int n_pics, const hmx_pic_param *pp,
+                              const AvailDev *d_lays, hmx_intra_plan **out);
 extern "C" int hmx_intra_plan_create_device(hmx_ctx *c, const hmx_tu *d_tus, const uint32_t *offsets, int n_pics, const hmx_pic_param *pp,
                                             hmx_intra_plan **out) {
+  return plan_create_device(c, d_tus, offsets, n_pics, pp, nullptr, out);
+}
+// The layouts' maps are in device memory: the region maps are read where they are, the intra flags are packed into one temporary
+// buffer first (k_pack_intra), and the per-picture AvailDev records go up beside them.
+extern "C" int hmx_intra_plan_create_device_layout(hmx_ctx *c, const hmx_tu *d_tus, const uint32_t *offsets, int n_pics, const hmx_pic_param *pp,
+                                                   const hmx_avail_layout *const *layouts, hmx_intra_plan **out) {
+  if (!c || !pp || n_pics <= 0) return fail(c, HMX_ERR_ARG, "hmx_intra_plan_create_device_layout: bad argument");
+  if (!layouts) return plan_create_device(c, d_tus, offsets, n_pics, pp, nullptr, out);
+  std::vector<AvailDev> lays(n_pics);
+  size_t words = 0;
+  bool any = false;
+  for (int i = 0; i < n_pics; i++) {
+    LayoutHost H;
+    if (const char *e = layout_pack(layouts[i], pp->pic_w, pp->pic_h, c->cfg.ctu_size, H, true)) return fail(c, HMX_ERR_ARG, e);
+    lays[i] = H.D;
+    if (layouts[i] && layouts[i]->ctu_region) lays[i].region = layouts[i]->ctu_region, any = true;
+    if (layouts[i] && layouts[i]->constrained_intra_pred) {
+      const int uw = (pp->pic_w + 3) / 4, uh = (pp->pic_h + 3) / 4;
+      words += (size_t)uh * H.D.row_words + (size_t)uw * H.D.col_words;
+      any = true;
+    }
+  }
+  if (!any) return plan_create_device(c, d_tus, offsets, n_pics, pp, nullptr, out);
+  const size_t rec_bytes = ((sizeof(AvailDev) * n_pics + 255) & ~(size_t)255);
+  char *tmp = nullptr;
+  if (hipMalloc((void **)&tmp, rec_bytes + words * 4) != hipSuccess) return fail(c, HMX_ERR_NOMEM, "hipMalloc layout maps");
+  uint32_t *bits = (uint32_t *)(tmp + rec_bytes);
+  hipError_t e = hipSuccess;
+  for (int i = 0; i < n_pics && e == hipSuccess; i++) {
+    if (!layouts[i] || !layouts[i]->constrained_intra_pred) continue;
+    const int uw = (pp->pic_w + 3) / 4, uh = (pp->pic_h + 3) / 4, nr = uh * lays[i].row_words, nc = uw * lays[i].col_words;
+    uint32_t *rows = bits, *cols = bits + nr;
+    bits += nr + nc;
+    hipLaunchKernelGGL(k_pack_intra, dim3((unsigned)((nr + nc + 255) / 256)), dim3(256), 0, c->stream, layouts[i]->intra_unit, layouts[i]->intra_stride,
+                       uw, uh, rows, lays[i].row_words, cols, lays[i].col_words);
+    e = hipGetLastError();
+    lays[i].rows = rows, lays[i].cols = cols;
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(tmp, lays.data(), sizeof(AvailDev) * n_pics, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream); // pageable source
+  int r = e == hipSuccess ? plan_create_device(c, d_tus, offsets, n_pics, pp, (const AvailDev *)tmp, out)
+                          : fail(c, HMX_ERR_DEVICE, "hmx_intra_plan_create_device_layout: layout maps", e);
+  hipStreamSynchronize(c->stream); // the plan kernels have read the maps
+  hipFree(tmp);
+  return r;
+}
+static int plan_create_device(hmx_ctx *c, const hmx_tu *d_tus, const uint32_t *offsets, int n_pics, const hmx_pic_param *pp,
+                              const AvailDev *d_lays, hmx_intra_plan **out) {
   if (!c || !d_tus || !offsets || !pp || !out || n_pics <= 0) return fail(c, HMX_ERR_ARG, "hmx_intra_plan_create_device: bad argument");
   if (c->cfg.ctu_size != 64) return fail(c, HMX_ERR_ARG, "hmx_intra_plan_create_device: CTU size 64 only");
   for (int i = 0; i < n_pics; i++) out[i] = nullptr;
@@ -1010,7 +1150,11 @@ extern "C" int hmx_intra_plan_create_device(hmx_ctx *c, const hmx_tu *d_tus, con
     if (e1 == hipSuccess) e1 = hipMemsetAsync(d_bot, 0, sizeof(unsigned short) * (size_t)n_pics * 3 * G.ch * G.uw, st);
     if (e1 == hipSuccess) e1 = hipMemsetAsync(d_right, 0, sizeof(unsigned short) * (size_t)n_pics * 3 * G.n_ctu * 16, st);
     if (e1 == hipSuccess) e1 = hipMemsetAsync(set->d_ltab, 0, sizeof(LevelRow) * rows, st);
-    hipLaunchKernelGGL(k_plan_ctus, per_block, dim3(256), 0, st, tus0, d_off, d_ctu, d_size_total, d_err, c->pd.d_need, d_rec, d_ftu, G);
+    if (d_lays)
+      hipLaunchKernelGGL(k_plan_ctus<true>, per_block, dim3(256), 0, st, tus0, d_off, d_ctu, d_size_total, d_err, c->pd.d_need, d_rec, d_ftu, G, d_lays);
+    else
+      hipLaunchKernelGGL(k_plan_ctus<false>, per_block, dim3(256), 0, st, tus0, d_off, d_ctu, d_size_total, d_err, c->pd.d_need, d_rec, d_ftu, G,
+                         (const AvailDev *)nullptr);
     PlanLevelArgs LA{d_rec, d_off, d_ctu, d_level, d_bot, d_right, d_pic_max, set->d_ltab, cap, d_overflow, G};
     // A block depends on blocks of its own plane only: the luma walk and the chroma walk are two independent chains of launches,
     // on two streams (one fills the tail of the other's rounds: a wave holds 39 KB / 23 KB of LDS for as long as it walks)
@@ -1149,4 +1293,17 @@ extern "C" unsigned long long hmx_intra_avail_mask(int x, int y, int size_luma, 
   PicDev P{};
   P.pic_w = pic_w, P.pic_h = pic_h, P.ctu = 64;
   return closed_form ? intra_avail_mask_fast(x, y, size_luma, P) : intra_avail_mask(x, y, size_luma, P);
+}
+
+// test hook (host arithmetic only): the availability with a slice / tile / CIP layout
+extern "C" unsigned long long hmx_intra_avail_mask_layout(int x, int y, int size_luma, int pic_w, int pic_h, const hmx_avail_layout *layout) {
+  if (x < 0 || y < 0 || pic_w <= 0 || pic_h <= 0 || x >= pic_w || y >= pic_h || (size_luma != 4 && size_luma != 8 && size_luma != 16 && size_luma != 32 && size_luma != 64) ||
+      x % size_luma || y % size_luma)
+    return ~0ull;
+  LayoutHost lay;
+  if (layout_pack(layout, pic_w, pic_h, 64, lay)) return ~0ull;
+  PicDev P{};
+  P.pic_w = pic_w, P.pic_h = pic_h, P.ctu = 64;
+  if (size_luma == 64) return intra_avail_mask_layout(intra_avail_mask_ctu(x, y, P), x, y, 64, 3, lay.D);
+  return intra_avail_mask_layout(intra_avail_mask(x, y, size_luma, P), x, y, size_luma, 2, lay.D);
 }

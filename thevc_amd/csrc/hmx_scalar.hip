@@ -582,7 +582,7 @@ extern "C" int hmx_invtransformNxN(hmx_ctx *c, int bypass, int text_type, unsign
 // =============================================================================================
 template <int N>
 __global__ __launch_bounds__(64) void k_adi(const short *win, int stride, int bx, int by, int x, int y, int chroma,
-                                            PicDev P, int *adi) {
+                                            PicDev P, int *adi, AvailDev lay, int use_layout) {
   __shared__ TuLds<N> L;
   const int gl = threadIdx.x;
   const bool on = gl < N;
@@ -591,6 +591,7 @@ __global__ __launch_bounds__(64) void k_adi(const short *win, int stride, int bx
     unsigned long long avail;
     if constexpr (N == 64) avail = intra_avail_mask_ctu(x, y, P); // a whole CTU, luma: units of eight samples
     else avail = intra_avail_mask(x << chroma, y << chroma, N << chroma, P);
+    if (use_layout) avail = intra_avail_mask_layout(avail, x << chroma, y << chroma, N << chroma, N == 64 ? 3 : 2, lay);
     const short *rec0 = win + (size_t)by * stride + bx;
     build_ref_line<N, N>([&](int dx, int dy) { return (int)rec0[(ptrdiff_t)dy * stride + dx]; }, avail, N == 64 ? 3 : chroma ? 1 : 2,
                          P.bit_depth, gl, L.line);
@@ -652,8 +653,8 @@ __global__ __launch_bounds__(64) void k_pred_adi(const int *adi, int mode, int l
   }
 }
 
-extern "C" int hmx_initAdiPattern(hmx_ctx *c, const hmx_pel *rec, int stride, int x, int y, int n, int is_chroma,
-                                  int pic_w, int pic_h, int32_t *adi) {
+static int init_adi(hmx_ctx *c, const hmx_pel *rec, int stride, int x, int y, int n, int is_chroma, int pic_w, int pic_h,
+                    const hmx_avail_layout *layout, int32_t *adi) {
   if (!c || !rec || !adi || !size_ok_intra(n, n)) return fail(c, HMX_ERR_ARG, "hmx_initAdiPattern: unsupported size or null");
   if (n == 64 && (is_chroma || c->cfg.ctu_size != 64 || x % 64 || y % 64))
     return fail(c, HMX_ERR_ARG, "hmx_initAdiPattern: a 64x64 block is the luma prediction unit of a whole CTU (CTU size 64, aligned)");
@@ -669,15 +670,106 @@ extern "C" int hmx_initAdiPattern(hmx_ctx *c, const hmx_pel *rec, int stride, in
   hmx_pic_param pp{pic_w, pic_h, 0, 0, HMX_I_SLICE, 0};
   PicDev P = make_picdev(c, &pp);
   const int bx = x - x0, by = y - y0;
+  AvailDev lay{};
+  int use_layout = 0;
+  if (layout) {
+    LayoutHost H;
+    if (const char *e = layout_pack(layout, pic_w, pic_h, c->cfg.ctu_size, H)) return fail(c, HMX_ERR_ARG, e);
+    if ((r = layout_to_device(c, H, lay))) return r;
+    use_layout = 1;
+  }
   switch (n) {
-  case 4: hipLaunchKernelGGL(k_adi<4>, dim3(1), dim3(64), 0, c->stream, d_win, ww, bx, by, x, y, is_chroma, P, d_adi); break;
-  case 8: hipLaunchKernelGGL(k_adi<8>, dim3(1), dim3(64), 0, c->stream, d_win, ww, bx, by, x, y, is_chroma, P, d_adi); break;
-  case 16: hipLaunchKernelGGL(k_adi<16>, dim3(1), dim3(64), 0, c->stream, d_win, ww, bx, by, x, y, is_chroma, P, d_adi); break;
-  case 32: hipLaunchKernelGGL(k_adi<32>, dim3(1), dim3(64), 0, c->stream, d_win, ww, bx, by, x, y, is_chroma, P, d_adi); break;
-  default: hipLaunchKernelGGL(k_adi<64>, dim3(1), dim3(64), 0, c->stream, d_win, ww, bx, by, x, y, is_chroma, P, d_adi); break;
+  case 4: hipLaunchKernelGGL(k_adi<4>, dim3(1), dim3(64), 0, c->stream, d_win, ww, bx, by, x, y, is_chroma, P, d_adi, lay, use_layout); break;
+  case 8: hipLaunchKernelGGL(k_adi<8>, dim3(1), dim3(64), 0, c->stream, d_win, ww, bx, by, x, y, is_chroma, P, d_adi, lay, use_layout); break;
+  case 16: hipLaunchKernelGGL(k_adi<16>, dim3(1), dim3(64), 0, c->stream, d_win, ww, bx, by, x, y, is_chroma, P, d_adi, lay, use_layout); break;
+  case 32: hipLaunchKernelGGL(k_adi<32>, dim3(1), dim3(64), 0, c->stream, d_win, ww, bx, by, x, y, is_chroma, P, d_adi, lay, use_layout); break;
+  default: hipLaunchKernelGGL(k_adi<64>, dim3(1), dim3(64), 0, c->stream, d_win, ww, bx, by, x, y, is_chroma, P, d_adi, lay, use_layout); break;
   }
   HIPCHK(c, hipGetLastError());
   return hmx_download(c, adi, d_adi, sizeof(int) * 2 * W * W);
+}
+extern "C" int hmx_initAdiPattern(hmx_ctx *c, const hmx_pel *rec, int stride, int x, int y, int n, int is_chroma,
+                                  int pic_w, int pic_h, int32_t *adi) {
+  return init_adi(c, rec, stride, x, y, n, is_chroma, pic_w, pic_h, nullptr, adi);
+}
+extern "C" int hmx_initAdiPattern_layout(hmx_ctx *c, const hmx_pel *rec, int stride, int x, int y, int n, int is_chroma, int pic_w, int pic_h,
+                                         const hmx_avail_layout *layout, int32_t *adi) {
+  return init_adi(c, rec, stride, x, y, n, is_chroma, pic_w, pic_h, layout, adi);
+}
+
+// fillReferenceSamples with the caller's flags: the reference line from a (2N+1) x (2N+1) window whose cell (1,1) is the block's
+// sample (0,0), border cells only (the reference leaves the rest of the buffer alone)
+template <int N>
+__global__ __launch_bounds__(64) void k_fill_ref(const short *win, unsigned long long avail, int unit_log2, int bit_depth, int *adi) {
+  __shared__ int line[4 * N + 1];
+  const int gl = threadIdx.x;
+  constexpr int W = 2 * N + 1;
+  if (gl < N) {
+    const short *rec0 = win + W + 1;
+    build_ref_line<N, N>([&](int dx, int dy) { return (int)rec0[dy * W + dx]; }, avail, unit_log2, bit_depth, gl, line);
+  }
+  __syncthreads();
+  if (gl < N)
+    for (int p = gl; p <= 4 * N; p += N) adi[p >= 2 * N ? p - 2 * N : (2 * N - p) * W] = line[p];
+}
+extern "C" int hmx_fillReferenceSamples(hmx_ctx *c, const hmx_pel *rec, int stride, const uint8_t *flags, int n_avail, int unit, int n,
+                                        int32_t *adi) {
+  if (!c || !rec || !flags || !adi || !size_ok_intra(n, n) || (unit != 2 && unit != 4) || n / unit < 1)
+    return fail(c, HMX_ERR_ARG, "hmx_fillReferenceSamples: unsupported size / unit or null");
+  int nu = n / unit, total = 4 * nu + 1, ulog2 = unit == 4 ? 2 : 1;
+  // iNumIntraNeighbor decides first (TComPattern.cpp:374-395): none -> the DC value everywhere, all -> every sample as it is
+  std::vector<uint8_t> f(flags, flags + total);
+  if (n_avail == 0) std::fill(f.begin(), f.end(), 0);
+  else if (n_avail == total) std::fill(f.begin(), f.end(), 1);
+  if (total > 64) { // 65 units do not fit the mask: pairs of equal flags become units of twice the size (the 64 x 64 prediction unit)
+    for (int u = 0; u < 2 * nu; u += 2)
+      if (f[u] != f[u + 1] || f[2 * nu + 1 + u] != f[2 * nu + 2 + u])
+        return fail(c, HMX_ERR_ARG, "hmx_fillReferenceSamples: 65 units with flags that differ inside a pair of units");
+    std::vector<uint8_t> g(2 * nu + 1);
+    for (int u = 0; u < nu; u++) g[u] = f[2 * u], g[nu + 1 + u] = f[2 * nu + 1 + 2 * u];
+    g[nu] = f[2 * nu];
+    f.swap(g);
+    nu /= 2, total = 4 * nu + 1, ulog2++;
+  }
+  unsigned long long avail = 0;
+  for (int u = 0; u < total; u++)
+    if (f[u]) avail |= 1ull << u;
+  // the flagged samples only: the window's other cells are never read (the caller's plane need not extend there)
+  const int W = 2 * n + 1, us = 1 << ulog2;
+  std::vector<short> win((size_t)W * W, 0);
+  for (int u = 0; u < total; u++) {
+    if (!f[u]) continue;
+    if (u < 2 * nu) {
+      for (int k = 0; k < us; k++) {
+        const int dy = (2 * nu - 1 - u) * us + k;
+        win[(size_t)(dy + 1) * W] = rec[(ptrdiff_t)dy * stride - 1];
+      }
+    } else if (u == 2 * nu) {
+      win[0] = rec[-(ptrdiff_t)stride - 1];
+    } else {
+      for (int k = 0; k < us; k++) {
+        const int dx = (u - 2 * nu - 1) * us + k;
+        win[1 + dx] = rec[dx - (ptrdiff_t)stride];
+      }
+    }
+  }
+  Scratch s{c};
+  short *d_win = s.take<short>((size_t)W * W);
+  int *d_adi = s.take<int>((size_t)W * W);
+  int r = hmx_upload(c, d_win, win.data(), sizeof(short) * W * W);
+  if (r) return r;
+  switch (n) {
+  case 4: hipLaunchKernelGGL(k_fill_ref<4>, dim3(1), dim3(64), 0, c->stream, d_win, avail, ulog2, c->cfg.bit_depth, d_adi); break;
+  case 8: hipLaunchKernelGGL(k_fill_ref<8>, dim3(1), dim3(64), 0, c->stream, d_win, avail, ulog2, c->cfg.bit_depth, d_adi); break;
+  case 16: hipLaunchKernelGGL(k_fill_ref<16>, dim3(1), dim3(64), 0, c->stream, d_win, avail, ulog2, c->cfg.bit_depth, d_adi); break;
+  case 32: hipLaunchKernelGGL(k_fill_ref<32>, dim3(1), dim3(64), 0, c->stream, d_win, avail, ulog2, c->cfg.bit_depth, d_adi); break;
+  default: hipLaunchKernelGGL(k_fill_ref<64>, dim3(1), dim3(64), 0, c->stream, d_win, avail, ulog2, c->cfg.bit_depth, d_adi); break;
+  }
+  HIPCHK(c, hipGetLastError());
+  std::vector<int32_t> out((size_t)W * W);
+  if ((r = hmx_download(c, out.data(), d_adi, sizeof(int32_t) * W * W))) return r;
+  for (int k = 0; k < W; k++) adi[k] = out[k], adi[(size_t)k * W] = out[(size_t)k * W];
+  return HMX_OK;
 }
 
 static int pred_from_adi(hmx_ctx *c, const int32_t *adi, unsigned mode, hmx_pel *pred, unsigned stride, int w, int h,

@@ -11,7 +11,9 @@ order, with libhmx's own earlier outputs as reference pictures:
 A picture is a dict: poc, w, h, B, qp, ctu, slice_type (0 B, 1 P, 2 I), tus (hmx_tu records; flags bit 1 = block of
 an inter coding unit, bit 7 = luma coded-block flag), pus / cus (records of the tap), lev (three arrays in the
 reference's per-CTU coefficient layout), sao ([3][n_ctu] hmx_sao_lcu records), dbk ([disabled, beta_offset_div2,
-tc_offset_div2]).  load_pictures() reads the .npz fixtures of tests/golden/make_stream_golden.py.  The numpy helpers
+tc_offset_div2]), and the layout of its slices, tiles and constrained intra prediction: region (region id per CTU in
+raster order, or None: one region) and cip (constrained_intra_pred_flag).  load_pictures() reads the .npz fixtures of
+tests/golden/make_stream_golden.py and tests/golden/make_stream_layout_golden.py.  The numpy helpers
 import nothing of the GPU side; decode_sequence() needs libhmx."""
 import ctypes as C
 
@@ -42,7 +44,60 @@ def load_pictures(path):
     for i in range(int(d["n"])):
         poc, w, h, B, qp, ctu, slice_type = (int(v) for v in d[f"hdr{i}"])
         yield dict(poc=poc, w=w, h=h, B=B, qp=qp, ctu=ctu, slice_type=slice_type, pus=d[f"pus{i}"], cus=d[f"cus{i}"], tus=d[f"tus{i}"], lev=[d[f"lev{i}_{k}"] for k in range(3)],
-                   rec=[d[f"rec{i}_{k}"] for k in range(3)], org=[d[f"org{i}_{k}"] for k in range(3)] if f"org{i}_0" in d else None, sao=np.ascontiguousarray(d[f"sao{i}"]), dbk=[int(v) for v in d[f"dbk{i}"]])
+                   rec=[d[f"rec{i}_{k}"] for k in range(3)], org=[d[f"org{i}_{k}"] for k in range(3)] if f"org{i}_0" in d else None, sao=np.ascontiguousarray(d[f"sao{i}"]), dbk=[int(v) for v in d[f"dbk{i}"]],
+                   region=np.ascontiguousarray(d[f"region{i}"], np.uint32) if f"region{i}" in d else None, cip=bool(int(d[f"cip{i}"])) if f"cip{i}" in d else False)
+
+
+def tile_scan(cw, ch, col_bounds, row_bounds):
+    """CtbAddrTsToRs (H.265 6.5.1): CTU raster addresses in tile-scan order, with the tile index of each.  col_bounds /
+    row_bounds = the CTU columns / rows where tiles start, 0 first (e.g. [0, 3, 5] for three tile columns)."""
+    cb, rb = list(col_bounds) + [cw], list(row_bounds) + [ch]
+    order, tile = [], []
+    for j in range(len(rb) - 1):
+        for i in range(len(cb) - 1):
+            for y in range(rb[j], rb[j + 1]):
+                for x in range(cb[i], cb[i + 1]):
+                    order.append(y * cw + x)
+                    tile.append(j * (len(cb) - 1) + i)
+    return np.array(order, np.int64), np.array(tile, np.int64)
+
+
+def uniform_bounds(n_ctu, n_tiles):
+    """Tile boundaries with uniform spacing (H.265 6.5.1, uniform_spacing_flag = 1)."""
+    return [(i * n_ctu) // n_tiles for i in range(n_tiles)]
+
+
+def region_map(w, h, ctu, slice_starts=(0,), col_bounds=(0,), row_bounds=(0,)):
+    """Region id of every CTU in raster order: one region per (independent slice, tile) pair.  slice_starts = tile-scan CTU
+    addresses where independent slices begin (slices start at CTU boundaries; dependent slices are not listed: they do
+    not split regions)."""
+    cw, ch = -(-w // ctu), -(-h // ctu)
+    order, tile = tile_scan(cw, ch, col_bounds, row_bounds)
+    starts = np.array(sorted(set(int(s) for s in slice_starts) | {0}), np.int64)
+    sl = np.searchsorted(starts, np.arange(cw * ch), side="right") - 1  # slice of each tile-scan address
+    n_tiles = int(tile.max()) + 1
+    region = np.zeros(cw * ch, np.uint32)
+    region[order] = (sl * n_tiles + tile).astype(np.uint32)
+    return region
+
+
+def intra_unit_map(p):
+    """The intra flag of every 4x4 luma unit of a picture, from its coding units (constrained intra prediction)."""
+    uw, uh = -(-p["w"] // 4), -(-p["h"] // 4)
+    m = np.zeros((uh, uw), np.uint8)
+    for c in p["cus"]:
+        n, x, y = (1 << int(c["log2size"])) // 4, int(c["x"]) // 4, int(c["y"]) // 4
+        m[y:y + n, x:x + n] = 1 if c["intra"] else 0
+    return m
+
+
+def layout_of(p):
+    """The capi.Layout of a picture, or None for one region without constrained intra prediction."""
+    region, cip = p.get("region"), p.get("cip", False)
+    if region is None and not cip:
+        return None
+    from thevc_amd import capi
+    return capi.Layout(region, intra_unit_map(p) if cip else None)
 
 
 def deblock_maps(p):
@@ -182,7 +237,7 @@ def decode_sequence(pics):
                     keep += [d_lp]
                 keep += [d_pred, d_pus]
             if len(intra_tus):
-                plan = ctx.intra_plan(intra_tus, capi.PicParam(w, h, p["qp"], 0, capi.I_SLICE, 1))
+                plan = ctx.intra_plan(intra_tus, capi.PicParam(w, h, p["qp"], 0, capi.I_SLICE, 1), layout=layout_of(p))
                 d_lev = capi.DevLevelsZ(ctx, w, h, p["ctu"])
                 for k in range(3):
                     assert d_lev.elems[k] == len(p["lev"][k]), "levels are not in the per-CTU layout of this picture size"
