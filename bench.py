@@ -9,16 +9,20 @@ region starts.  Every picture follows its own decisions: by default 64 distinct 
 all different) and 64 distinct source pictures.  Weak scaling: every rank (one process per GPU) owns
 its own batch (IntraPeriod 1 => pictures are independent, no data-path collective).
 
-    python bench.py --gpus N --steps K --warmup W [--workload ai2160p10|ai2160p8|ai1080p8] [--frames F]
+    python bench.py --gpus N --steps K --warmup W [--workload ai2160p10|ai2160p8|ai1080p8] [--frames F] [--full]
     python bench.py --workload ra2160p8|ra1080p8|ldp1080p8 [--segments S]     (secondary workloads)
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N ranks itself (a child
 `python -m torch.distributed.run`, before this process touches the GPU).  Prints ONE JSON line on rank 0.
-`roofline` prices the dominant kernel (k_intra_packed, one persistent launch per step) against the HBM
-peak with ALGORITHMIC bytes; `cpu_baseline` times the reference's own CPU functions
-(oracle/_ref, kind "reference") or, if that library is absent, the CPU oracle (kind "port") on a bounded
-sample of the same workload, rank 0 at N=1 only: one core in-process (which doubles as a bit-exactness
-check of what the GPU wrote), then all host cores as independent worker processes.
+A plain run does what the headline needs: set up, warm up, time the steps, write --dump-outputs, print the line.
+Its `roofline` prices the dominant kernel (k_intra_packed, one persistent launch per step) against the HBM
+peak with ALGORITHMIC bytes, from the events of the timed steps.
+`--full` adds three legs after the timed steps (each can be skipped with its --no-* option):
+`fresh_decisions` (new decisions every step: plans and tables built on the device), `cpu_baseline` and
+`random_access` (ra2160p8).  `cpu_baseline` times the reference's own CPU functions (oracle/_ref, kind
+"reference") or, if that library is absent, the CPU oracle (kind "port") on a bounded sample of the same
+workload, rank 0 at N=1 only: one core in-process (which doubles as a bit-exactness check of what the GPU
+wrote), then all host cores as independent worker processes.
 """
 import argparse
 import ctypes as C
@@ -430,17 +434,22 @@ def main():
     ap.add_argument("--planar", action="store_true",
                     help="hand the pictures over in the reference's plane geometry (TComPicYuv): every call converts them into and out "
                          "of the working layout; default: pictures resident in the working layout (hmx_tpool)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the fresh-decisions, cpu_baseline and random-access legs of the all-intra "
+                         "workloads (what the headline figure does not need); --no-fresh, --no-cpu-baseline and --no-ra skip one")
     ap.add_argument("--no-fresh", action="store_true",
-                    help="skip the fresh-decisions leg (every picture of every step brings NEW decisions: the plans are analysed on the "
-                         "device and the packed schedule's tables rebuilt inside each timed step; reported as \"fresh_decisions\")")
+                    help="with --full: skip the fresh-decisions leg (every picture of every step brings NEW decisions: the plans are "
+                         "analysed on the device and the packed schedule's tables rebuilt inside each timed step; reported as "
+                         "\"fresh_decisions\")")
     ap.add_argument("--fresh-steps", type=int, default=3, help="timed steps of the fresh-decisions leg")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the cpu_baseline leg")
     ap.add_argument("--one-core-only", action="store_true", help="cpu_baseline: skip the all-cores leg")
     ap.add_argument("--cpu-cores", type=int, default=16, help="cpu_baseline: worker processes of the all-cores leg (the host-core share of one GPU)")
-    ap.add_argument("--no-ra", action="store_true", help="skip the random-access leg (ra2160p8, segments sharded over the ranks, RCCL exchange of the "
-                                                         "boundary I pictures when N > 1) that follows the all-intra measurement")
+    ap.add_argument("--no-ra", action="store_true", help="with --full: skip the random-access leg (ra2160p8, segments sharded over the ranks, RCCL "
+                                                         "exchange of the boundary I pictures when N > 1) that follows the all-intra measurement")
     ap.add_argument("--ra-segments", type=int, default=16, help="segments (32 pictures each) per GPU of the random-access leg")
-    ap.add_argument("--verify", action="store_true", help="the cpu_baseline leg also checks a picture of every packing group")
+    ap.add_argument("--verify", action="store_true", help="check a picture of every packing group against the CPU (in the cpu_baseline "
+                                                          "object; its timing is a single picture's unless --full runs the leg)")
     ap.add_argument("--rehearse-cpu", action="store_true", help="no GPU: run the rank launcher, sharding, exchange and reporting with gloo and the CPU oracle")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one computed (reconstruction and levels of a fixed set of pictures, "
@@ -504,9 +513,11 @@ def main():
     # tiled working pool 6.2 bytes per luma sample, plus 16 B per block of the packed schedule's item table).
     F = args.frames if args.frames else ((2048 if w >= 3840 else 8192) if not args.planar else (1536 if w >= 3840 else 4096))
     free_b, _total_b = torch.cuda.mem_get_info()
-    fresh_leg = not args.no_fresh and not args.planar and not args.decode and not args.rdoq
-    # (+ 72 B per block for the fresh-decisions leg: the decision lists, two generations of device-built plans and the builder's work buffers)
-    per_pic = int((18.3 if args.planar else 12.3) * w * h_c) + 18 * max(len(t) for t in tus_list) + (72 * int(np.mean([len(t) for t in tus_list])) if fresh_leg else 0)
+    fresh_applies = not args.no_fresh and not args.planar and not args.decode and not args.rdoq
+    fresh_leg = args.full and fresh_applies
+    # (+ 72 B per block for the fresh-decisions leg: the decision lists, two generations of device-built plans and the builder's work buffers;
+    # reserved whether or not --full runs the leg, so that a plain run and a --full run time the same batch)
+    per_pic = int((18.3 if args.planar else 12.3) * w * h_c) + 18 * max(len(t) for t in tus_list) + (72 * int(np.mean([len(t) for t in tus_list])) if fresh_applies else 0)
     if not args.frames and F * per_pic > 0.92 * free_b:
         F = max(8, int(0.92 * free_b / per_pic) // 64 * 64 or 8)
     n_plans = min(n_plans, F)
@@ -742,13 +753,14 @@ def main():
             out["fresh_decisions"] = fresh
         if dumped is not None:
             out["dump_outputs"] = dumped
-        if world == 1 and (args.verify or not args.no_cpu_baseline):
+        cpu_leg = args.full and not args.no_cpu_baseline
+        if world == 1 and (args.verify or cpu_leg):
             # --verify: one picture of every few packing groups, first and last included
             # default: three pictures (the first, one from the middle of the batch -- another packing group, another plan -- and the last)
             idx = sorted({0, F - 1} | set(range(0, F, max(64, F // 6 // 64 * 64 or 64)))) if args.verify else sorted({0, F // 2 + 1, F - 1})
             checks = [(i, tus_list[i % n_plans], plan_seeds[i % n_plans], seeds[i], src[i],
                        (reconstruction(i), lev_slab.picture(i).to_planes(tus_list[i % n_plans]))) for i in idx]
-            out["cpu_baseline"] = cpu_baseline(w, h_c, B, qp, args.tiling, checks, 0.0 if args.no_cpu_baseline else 10.0,
+            out["cpu_baseline"] = cpu_baseline(w, h_c, B, qp, args.tiling, checks, 10.0 if cpu_leg else 0.0,
                                                all_cores=not args.one_core_only, max_cores=args.cpu_cores, rdoq=args.rdoq)
             if args.verify:
                 cb = out["cpu_baseline"]
@@ -764,7 +776,7 @@ def main():
         L.hmx_intra_plan_destroy(ctx.h, p)
     ctx.close()
     torch.cuda.set_stream(torch.cuda.default_stream())
-    if not args.no_ra:
+    if args.full and not args.no_ra:
         # north_star's second claim: frame-sharded random access with the reference-picture exchange over RCCL/xGMI.
         # A secondary leg: whatever happens in it, the all-intra line above is still printed.
         try:

@@ -4,6 +4,7 @@
 # (copy them into profiles/).   usage: tools/final_profiles.sh TAG [bench args...]
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 TAG=${1:-r02}; shift
+set -- --full "$@"  # the round's bench line carries every leg; the profiled runs below skip them (--no-*)
 mkdir -p gpurun_out/final
 timeout -k 10 900 python3 bench.py "$@" > gpurun_out/final/${TAG}_bench_default.json 2> gpurun_out/fp_bench.err || { tail -5 gpurun_out/fp_bench.err; exit 1; }
 tail -1 gpurun_out/final/${TAG}_bench_default.json | cut -c1-600

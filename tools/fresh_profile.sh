@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 F=${1:-2048}
 O=gpurun_out/fresh_prof_$F
 rm -rf $O
-rocprofv3 --kernel-trace --stats --output-format csv -d $O -- python3 bench.py --frames $F --steps 1 --warmup 0 --fresh-steps 2 --no-ra --no-cpu-baseline > $O.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O -- python3 bench.py --full --frames $F --steps 1 --warmup 0 --fresh-steps 2 --no-ra --no-cpu-baseline > $O.log 2>&1
 tail -c 1200 $O.log
 python3 - "$O" <<'PY'
 import csv, glob, sys
