@@ -584,6 +584,35 @@ typedef struct hmx_sao_lcu {
 int hmx_sao_picture(hmx_ctx *ctx, const hmx_pic *in, const hmx_pic *out, int pic_w, int pic_h, const hmx_sao_lcu *d_params,
                     int n_lcu);
 
+/* Sample adaptive offset, the encoder's statistics pass: TEncSampleAdaptiveOffset::calcSaoStatsCuOrg
+ * (TLibEncoder/TEncSampleAdaptiveOffset.cpp:859-1124 with SAO_SKIP_RIGHT, TLibCommon/TypeDef.h:123), which rdoSaoUnitAll
+ * (:1617, via calcSaoStatsCu) runs for every CTU and component between deblocking and the parameter search.  For every CTU
+ * and component of n_pics pictures: the sum of org - rec and the sample count of every edge and band class.
+ * org / rec: host arrays [n_pics] of descriptors of device planes (each picture its own planes and strides; margins and
+ * unaligned planes allowed; org == rec allowed); rec is the deblocked picture, its samples in [0, 2^B).
+ * d_out (device): [pic][component][CTU in raster order][HMX_SAO_STAT_BINS]; every bin is written, zeros included.
+ * Per CTU of a plane (chroma 4:2:0: sizes and positions >> 1): W x H = the CTU cut at the picture edge; L / T / R / Bt = it
+ * touches the left / top / right / bottom picture edge; s = 4 (luma) or 2 (chroma) bottom rows and r = 5 or 3 right
+ * columns are skipped, both 0 when lcu_based == 0 (SAOLcuBasedOptimization = 0, :886-896).  CTU-local ranges:
+ *   band (type 4)   x in [0, R ? W : W-r)    y in [0, Bt ? H : H-s)      class 1 + (rec >> (B - 5))
+ *   EO_0 (type 0)   x in [L, R ? W-1 : W-r)  y in [0, H-s)  (bottom rows skipped even on the picture edge, :971)
+ *   EO_1 (type 1)   x in [0, R ? W : W-r)    y in [T, Bt ? H-1 : H-s)
+ *   EO_2, EO_3      x in [L, R ? W-1 : W-r)  y in [T, Bt ? H-1 : H-s)
+ * Edge class = m_auiEoTable[sign(c - a) + sign(c - b) + 2] (TComSampleAdaptiveOffset.cpp:94; {1, 2, 0, 3, 4}), class 0
+ * ("no edge") included; neighbours a, b: (x-1,y),(x+1,y) | (x,y-1),(x,y+1) | (x-1,y-1),(x+1,y+1) | (x+1,y-1),(x-1,y+1), read
+ * from the picture across CTU edges.  Not covered: the NIF path (calcSaoStatsBlock: slice / tile boundaries not crossed,
+ * TComSampleAdaptiveOffset.cpp:500) and everything after the statistics (offset estimation, estSaoDist, merge, CABAC rates,
+ * the quadtree part sums of SAOLcuBasedOptimization = 0: the host sums these per-CTU bins).  |diff| <= 64*64*(2^12 - 1)
+ * fits int32.  HMX_ERR_ARG: a null pointer, n_pics < 1, pic_w or pic_h not a positive multiple of 8. */
+typedef struct hmx_sao_stat {
+  int32_t diff, count;
+} hmx_sao_stat;
+#define HMX_SAO_STAT_BINS 52 /* bin 5*t + c: edge type t 0..3, class c 0..4 (after m_auiEoTable); bin 20 + k - 1: band class k 1..32 */
+int hmx_sao_stats_multi(hmx_ctx *ctx, int n_pics, const hmx_pic *org, const hmx_pic *rec, int pic_w, int pic_h, int lcu_based,
+                        hmx_sao_stat *d_out);
+int hmx_sao_stats(hmx_ctx *ctx, const hmx_pic *org, const hmx_pic *rec, int pic_w, int pic_h, int lcu_based,
+                  hmx_sao_stat *d_out); /* = _multi with n_pics = 1 */
+
 /* Planar 4:2:0 YUV frames, the format either side of the path (TLibVideoIO/TVideoIOYuv.cpp:226-480, SURVEY.md
  * 8f rank 4).  d_file (device) holds one frame as the file does: 8-bit or 16-bit little-endian samples, Y then
  * Cb then Cr.  unpack = TVideoIOYuv::read: the file's (w_full - pad_x) x (h_full - pad_y) samples are padded to

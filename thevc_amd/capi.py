@@ -236,6 +236,8 @@ def lib():
                                                       C.POINTER(PicParam)]
         L.hmx_pic_extend_border_multi.argtypes = [vp, ci, C.POINTER(Pic), ci, ci, ci, ci]
         L.hmx_sao_picture.argtypes = [vp, C.POINTER(Pic), C.POINTER(Pic), ci, ci, vp, ci]
+        L.hmx_sao_stats_multi.argtypes = [vp, ci, C.POINTER(Pic), C.POINTER(Pic), ci, ci, ci, vp]
+        L.hmx_sao_stats.argtypes = [vp, C.POINTER(Pic), C.POINTER(Pic), ci, ci, ci, vp]
         L.hmx_deblock_strengths.argtypes = [vp, vp, vp, vp, ci, ci, ci, vp, vp]
         L.hmx_deblock_picture.argtypes = [vp, C.POINTER(Pic), ci, ci, vp, vp, vp, vp, ci, ci]
         L.hmx_yuv_frame_bytes.argtypes = [ci, ci, ci]
@@ -306,6 +308,7 @@ class Context:
             raise HmxError(f"hmx_create failed ({rc}): no usable HIP device?")
         self.h = h
         self.bit_depth = bit_depth
+        self.ctu_size = ctu_size
 
     def _chk(self, rc):
         if rc != 0:
@@ -602,6 +605,41 @@ class Context:
         levels = np.zeros((nl.value, 8), np.uint32)
         self._chk(lib().hmx_intra_plan_download(self.h, plan, _hp(blocks), _hp(levels)))
         return blocks, levels
+
+    def sao_stats(self, orgs, recs, w, h, lcu_based=True):
+        """hmx_sao_stats_multi: the encoder's SAO statistics of n pictures (DevPictures, org and deblocked rec) as an int32
+        array (n, 3 components, n_lcu, SAO_STAT_BINS, 2): [..., 0] = sum of org - rec, [..., 1] = count; bins as in
+        include/hmx.h (sao_stats_to_hm spreads them into the reference's own arrays)."""
+        n = len(orgs)
+        assert n == len(recs) and n > 0
+        ctu = self.ctu_size
+        n_lcu = -(-w // ctu) * -(-h // ctu)
+        o, r = (Pic * n)(*[p.as_pic() for p in orgs]), (Pic * n)(*[p.as_pic() for p in recs])
+        out = self.alloc(n * 3 * n_lcu * SAO_STAT_BINS * 8)
+        try:
+            self._chk(lib().hmx_sao_stats_multi(self.h, n, o, r, w, h, 1 if lcu_based else 0, out.ptr))
+            self.sync()
+            return out.download(np.int32).reshape(n, 3, n_lcu, SAO_STAT_BINS, 2)
+        finally:
+            out.free()
+
+
+SAO_STAT_BINS = 52  # HMX_SAO_STAT_BINS
+SAO_EO_TABLE = (1, 2, 0, 3, 4)  # m_auiEoTable (TComSampleAdaptiveOffset.cpp:94): sign(c - a) + sign(c - b) + 2 -> class
+
+
+def sao_stats_to_hm(a):
+    """The bins of hmx_sao_stats* ([..., SAO_STAT_BINS, 2]) as the reference's per-CTU arrays m_iOffsetOrg and m_iCount
+    (TEncSampleAdaptiveOffset.h: [type][class], types SAO_EO_0..3 then SAO_BO, 33 classes): two int64 arrays
+    [..., 5, 33].  Edge types fill classes 0..4, the band type classes 1..32; the rest are zero."""
+    a = np.asarray(a)
+    assert a.shape[-2:] == (SAO_STAT_BINS, 2), a.shape
+    stats = np.zeros(a.shape[:-2] + (5, 33), np.int64)
+    count = np.zeros_like(stats)
+    eo = a[..., :20, :].reshape(a.shape[:-2] + (4, 5, 2)).astype(np.int64)
+    stats[..., :4, :5], count[..., :4, :5] = eo[..., 0], eo[..., 1]
+    stats[..., 4, 1:], count[..., 4, 1:] = a[..., 20:, 0], a[..., 20:, 1]
+    return stats, count
 
 
 def qp_for(qpy, text_type, bit_depth, chroma_qp_offset=0):

@@ -238,6 +238,183 @@ extern "C" int hmx_sao_picture(hmx_ctx *c, const hmx_pic *in, const hmx_pic *out
   return HMX_OK;
 }
 
+// ---- SAO statistics of the encoder (TLibEncoder/TEncSampleAdaptiveOffset.cpp:859-1124, calcSaoStatsCuOrg, SAO_SKIP_RIGHT) ----
+// One workgroup per (CTU, component, picture), ending in plain stores of its 52 bins.  A thread owns a strip of 8 columns
+// and `rows` rows of the CTU and walks it downwards with the rows above and below in registers: every sign of a neighbour
+// difference is formed once and serves the samples on both sides of it (what the reference's m_iUpBuff1 does incrementally).
+// Edge classes, per type: s = sign(c - a) + sign(c - b) in -2..2.  Counts go to 6-bit fields of one register (field s + 2; a
+// sample outside the type's range goes to bits 30-31, never read; a thread sees at most 32 samples).  Diffs go to the five
+// moments M_j = sum(diff * s^j), j = 0..4, from which the five class sums follow exactly at the end (sao_stats_solve).
+// Band classes: a per-wave LDS histogram of (count << 40) + diff in 64 bits.
+constexpr int kSaoStatThreads = 128;
+struct SaoStatArgs {
+  const PlanesDev *pics; // [n_pics] originals, then [n_pics] reconstructions
+  hmx_sao_stat *out;
+  int n_pics, pic_w, pic_h, ctu, B, lcu_based, n_lcu, cw;
+};
+__device__ __forceinline__ int sao_sign(int a, int b) { return min(max(a - b, -1), 1); }
+// samples x0-1 .. x0+8 of a row into r[0..9] (addresses clamped to the plane; what lies outside is masked off by the ranges)
+__device__ __forceinline__ void sao_row(const short *row, int x0, int w, bool vec, int r[10]) {
+  if (vec) {
+    const s8v v = *reinterpret_cast<const s8v *>(row + x0);
+#pragma unroll
+    for (int k = 0; k < 8; k++) r[k + 1] = v[k];
+  } else {
+#pragma unroll
+    for (int k = 0; k < 8; k++) r[k + 1] = row[min(x0 + k, w - 1)];
+  }
+  r[0] = row[max(x0 - 1, 0)];
+  r[9] = row[min(x0 + 8, w - 1)];
+}
+// signs of a row against the row below: d1[i] = sign(c_i - below_i) (i = 1..8), d2[i] = sign(c_i - below_{i+1}) (0..8),
+// d3[i] = sign(c_i - below_{i-1}) (1..9); i indexes r[] (i = 1 is column x0)
+__device__ __forceinline__ void sao_vsigns(const int u[10], const int l[10], int d1[10], int d2[10], int d3[10]) {
+#pragma unroll
+  for (int i = 0; i < 10; i++) {
+    d1[i] = i >= 1 && i <= 8 ? sao_sign(u[i], l[i]) : 0;
+    d2[i] = i <= 8 ? sao_sign(u[i], l[i + 1]) : 0;
+    d3[i] = i >= 1 ? sao_sign(u[i], l[i - 1]) : 0;
+  }
+}
+// bits k of the 8 columns x0 + k that lie in [lo, hi)
+__device__ __forceinline__ unsigned sao_xmask(int lo, int hi, int x0) {
+  lo = min(max(lo - x0, 0), 8), hi = min(max(hi - x0, 0), 8);
+  return ((1u << hi) - 1) & ~((1u << lo) - 1);
+}
+__device__ __forceinline__ void sao_acc(int m[5], unsigned &cnt, bool ok, int s, int diff) {
+  const int dm = ok ? diff : 0, s2 = __mul24(s, s);
+  cnt += 1u << (ok ? __mul24(s + 2, 6) : 30);
+  m[0] += dm;
+  m[1] += __mul24(dm, s);
+  m[2] += __mul24(dm, s2);
+  m[3] += __mul24(dm, __mul24(s2, s));
+  m[4] += __mul24(dm, __mul24(s2, s2));
+}
+// class sums D_s (s = -2..2) from M_j = sum_s D_s s^j: with P_k = D_k + D_-k, Q_k = D_k - D_-k, M2 = P1 + 4 P2, M4 = P1 + 16 P2,
+// M1 = Q1 + 2 Q2, M3 = Q1 + 8 Q2, M0 = D0 + P1 + P2 (every division is exact)
+__device__ __forceinline__ void sao_stats_solve(const int M[5], int D[5]) {
+  const int P2 = (M[4] - M[2]) / 12, P1 = M[2] - 4 * P2, Q2 = (M[3] - M[1]) / 6, Q1 = M[1] - 2 * Q2;
+  D[0] = (P2 - Q2) / 2, D[1] = (P1 - Q1) / 2, D[2] = M[0] - P1 - P2, D[3] = (P1 + Q1) / 2, D[4] = (P2 + Q2) / 2;
+}
+__global__ __launch_bounds__(kSaoStatThreads) void k_sao_stats(SaoStatArgs A) {
+  constexpr int kWaves = kSaoStatThreads / 64;
+  __shared__ unsigned long long hist[kWaves][32];
+  __shared__ int part[kWaves][40];
+  const int lcu = blockIdx.x, p = blockIdx.y, pic = blockIdx.z, t = threadIdx.x, wave = t >> 6;
+  for (int i = t; i < kWaves * 32; i += kSaoStatThreads) (&hist[0][0])[i] = 0;
+  __syncthreads();
+  // the CTU in this plane (:898-909) and the ranges of the five passes (CTU-local, end exclusive; include/hmx.h)
+  const int sh = p ? 1 : 0, w = A.pic_w >> sh, h = A.pic_h >> sh, cs = A.ctu >> sh;
+  const int lx = (lcu % A.cw) * cs, ty = (lcu / A.cw) * cs, W = min(cs, w - lx), H = min(cs, h - ty);
+  const bool isL = lx == 0, isT = ty == 0, isR = lx + W == w, isB = ty + H == h;
+  const int skip_b = A.lcu_based ? (p ? 2 : 4) : 0, skip_r = A.lcu_based ? (p ? 3 : 5) : 0;
+  const int xe_full = isR ? W : W - skip_r, xe_in = isR ? W - 1 : W - skip_r, xs = isL ? 1 : 0;
+  const int ye_bo = isB ? H : H - skip_b, ye_eo0 = H - skip_b, ys = isT ? 1 : 0, ye_v = isB ? H - 1 : H - skip_b;
+  const int strips = cs >> 3, rows = max(1, cs * strips / kSaoStatThreads);
+  const int x0 = (t % strips) * 8, y0 = (t / strips) * rows;
+  int mom[4][5] = {};
+  unsigned cnt[4] = {0, 0, 0, 0};
+  if (x0 < W && y0 < H) {
+    const PlanesDev *O = A.pics + pic, *R = A.pics + A.n_pics + pic; // indexed in memory: a copy indexed by p would live in scratch
+    const int gx = lx + x0, so = O->s[p], sr = R->s[p], bshift = A.B - 5;
+    const short *po = O->p[p] + gx, *pr = R->p[p]; // pr: column 0 of the plane (sao_row indexes it with gx)
+    const bool vo = gx + 8 <= w && (((uintptr_t)po | (uintptr_t)(2 * so)) & 15) == 0;
+    const bool vr = gx + 8 <= w && (((uintptr_t)(pr + gx) | (uintptr_t)(2 * sr)) & 15) == 0;
+    const unsigned m_full = sao_xmask(0, xe_full, x0), m_in = sao_xmask(xs, xe_in, x0);
+    int up[10], cur[10], dn[10], u1[10], u2[10], u3[10];
+    sao_row(pr + (size_t)max(ty + y0 - 1, 0) * sr, gx, w, vr, up);
+    sao_row(pr + (size_t)(ty + y0) * sr, gx, w, vr, cur);
+    sao_vsigns(up, cur, u1, u2, u3); // signs of the row above against this one: negated, they are this row's "up" signs
+#pragma unroll 1
+    for (int j = 0; j < rows; j++) {
+      const int y = y0 + j, gy = ty + y;
+      if (y >= H) break;
+      sao_row(pr + (size_t)min(gy + 1, h - 1) * sr, gx, w, vr, dn);
+      int org[8];
+      const short *orow = po + (size_t)gy * so;
+      if (vo) {
+        const s8v v = *reinterpret_cast<const s8v *>(orow);
+#pragma unroll
+        for (int k = 0; k < 8; k++) org[k] = v[k];
+      } else {
+#pragma unroll
+        for (int k = 0; k < 8; k++) org[k] = orow[min(k, w - 1 - gx)];
+      }
+      int d1[10], d2[10], d3[10], g[10];
+      sao_vsigns(cur, dn, d1, d2, d3);
+#pragma unroll
+      for (int i = 0; i < 9; i++) g[i] = sao_sign(cur[i], cur[i + 1]); // sign(c_i - right)
+      const bool vrow = y >= ys && y < ye_v;
+      const unsigned mb = y < ye_bo ? m_full : 0, m0 = y < ye_eo0 ? m_in : 0, m1 = vrow ? m_full : 0, m23 = vrow ? m_in : 0;
+#pragma unroll
+      for (int k = 0; k < 8; k++) {
+        const int i = k + 1, c = cur[i], diff = org[k] - c;
+        sao_acc(mom[0], cnt[0], (m0 >> k) & 1, g[i] - g[i - 1], diff);
+        sao_acc(mom[1], cnt[1], (m1 >> k) & 1, d1[i] - u1[i], diff);
+        sao_acc(mom[2], cnt[2], (m23 >> k) & 1, d2[i] - u2[i - 1], diff);
+        sao_acc(mom[3], cnt[3], (m23 >> k) & 1, d3[i] - u3[i + 1], diff);
+        if ((mb >> k) & 1) atomicAdd(&hist[wave][(c >> bshift) & 31], (1ull << 40) + (unsigned long long)(long long)diff);
+      }
+#pragma unroll
+      for (int i = 0; i < 10; i++) cur[i] = dn[i], u1[i] = d1[i], u2[i] = d2[i], u3[i] = d3[i];
+    }
+  }
+  // moments and counts summed over the wave, then over the waves
+#pragma unroll
+  for (int ty4 = 0; ty4 < 4; ty4++) {
+#pragma unroll
+    for (int j = 0; j < 5; j++) {
+      const int m = group_sum(mom[ty4][j], 64), n = group_sum((int)((cnt[ty4] >> (6 * j)) & 63), 64);
+      if ((t & 63) == 0) part[wave][10 * ty4 + j] = m, part[wave][10 * ty4 + 5 + j] = n;
+    }
+  }
+  __syncthreads();
+  hmx_sao_stat *out = A.out + (((size_t)pic * 3 + p) * A.n_lcu + lcu) * HMX_SAO_STAT_BINS;
+  if (t < 32) { // band class t + 1
+    unsigned long long v = 0;
+#pragma unroll
+    for (int q = 0; q < kWaves; q++) v += hist[q][t];
+    const long long n = (long long)((v + (1ull << 39)) >> 40);
+    out[20 + t] = hmx_sao_stat{(int32_t)((long long)v - (n << 40)), (int32_t)n};
+  } else if (t >= 64 && t < 68) { // edge type t - 64: raw class s + 2 -> m_auiEoTable {1, 2, 0, 3, 4}
+    const int ty4 = t - 64;
+    int M[5], N[5], D[5];
+#pragma unroll
+    for (int j = 0; j < 5; j++) {
+      M[j] = 0, N[j] = 0;
+#pragma unroll
+      for (int q = 0; q < kWaves; q++) M[j] += part[q][10 * ty4 + j], N[j] += part[q][10 * ty4 + 5 + j];
+    }
+    sao_stats_solve(M, D);
+    const int cls[5] = {1, 2, 0, 3, 4};
+#pragma unroll
+    for (int e = 0; e < 5; e++) out[5 * ty4 + cls[e]] = hmx_sao_stat{D[e], N[e]};
+  }
+}
+extern "C" int hmx_sao_stats_multi(hmx_ctx *c, int n_pics, const hmx_pic *org, const hmx_pic *rec, int pic_w, int pic_h, int lcu_based,
+                                   hmx_sao_stat *d_out) {
+  if (!c || !org || !rec || !d_out) return fail(c, HMX_ERR_ARG, "hmx_sao_stats_multi: null argument");
+  if (n_pics < 1 || n_pics > 65535) return fail(c, HMX_ERR_ARG, "hmx_sao_stats_multi: n_pics must be 1..65535");
+  if (pic_w <= 0 || pic_h <= 0 || (pic_w & 7) || (pic_h & 7))
+    return fail(c, HMX_ERR_ARG, "hmx_sao_stats_multi: picture size must be a positive multiple of 8");
+  std::vector<PlanesDev> t(2 * (size_t)n_pics);
+  for (int i = 0; i < n_pics; i++) {
+    for (int p = 0; p < 3; p++)
+      if (!org[i].plane[p] || !rec[i].plane[p]) return fail(c, HMX_ERR_ARG, "hmx_sao_stats_multi: null plane");
+    t[i] = to_dev(&org[i]), t[n_pics + i] = to_dev(&rec[i]);
+  }
+  const PlanesDev *d = static_cast<const PlanesDev *>(arena_push(c, t.data(), sizeof(PlanesDev) * t.size()));
+  if (!d) return fail(c, HMX_ERR_NOMEM, "argument arena");
+  const int ctu = c->cfg.ctu_size, cw = (pic_w + ctu - 1) / ctu, n_lcu = cw * ((pic_h + ctu - 1) / ctu);
+  SaoStatArgs A{d, d_out, n_pics, pic_w, pic_h, ctu, c->cfg.bit_depth, lcu_based ? 1 : 0, n_lcu, cw};
+  hipLaunchKernelGGL(k_sao_stats, dim3((unsigned)n_lcu, 3, (unsigned)n_pics), dim3(kSaoStatThreads), 0, c->stream, A);
+  HIPCHK(c, hipGetLastError());
+  return HMX_OK;
+}
+extern "C" int hmx_sao_stats(hmx_ctx *c, const hmx_pic *org, const hmx_pic *rec, int pic_w, int pic_h, int lcu_based, hmx_sao_stat *d_out) {
+  return hmx_sao_stats_multi(c, 1, org, rec, pic_w, pic_h, lcu_based, d_out);
+}
+
 // ---- planar 4:2:0 YUV frames (TLibVideoIO/TVideoIOYuv.cpp:226-480) ----
 // A frame travels as the bytes of the file (1 or 2 bytes per sample, Y then Cb then Cr): half or a quarter of
 // the PCIe traffic of int16 planes; widening, bit-depth scaling and the right/bottom padding happen in HBM.

@@ -235,4 +235,28 @@ private:
   Context &m_c;
 };
 
+// TEncSampleAdaptiveOffset, the statistics pass (TEncSampleAdaptiveOffset.cpp:859-1124, calcSaoStatsCuOrg with SAO_SKIP_RIGHT):
+// one call for every CTU and component of a picture, on the device; the parameter search (rdoSaoUnitAll's offset estimation,
+// distortion, merge and rates) stays with the caller and reads the downloaded bins through ctuStats.
+typedef long long Int64;
+class TEncSampleAdaptiveOffset {
+public:
+  explicit TEncSampleAdaptiveOffset(Context &c) : m_c(c) {}
+  // org, rec (deblocked): device pictures; d_out (device): [component][CTU in raster order][HMX_SAO_STAT_BINS]
+  void calcSaoStatsPicture(const hmx_pic *org, const hmx_pic *rec, Int picWidth, Int picHeight, Bool lcuBasedOptimization,
+                           hmx_sao_stat *d_out) {
+    m_c.check(hmx_sao_stats(m_c.get(), org, rec, picWidth, picHeight, lcuBasedOptimization ? 1 : 0, d_out), "calcSaoStatsPicture");
+  }
+  // adds one CTU's downloaded bins to m_iOffsetOrg / m_iCount [SAO_EO_0..3, SAO_BO][MAX_NUM_SAO_CLASS] of that CTU, which
+  // rdoSaoUnitAll clears before each CTU (the reference's calcSaoStatsCu accumulates the same way)
+  static inline void ctuStats(const hmx_sao_stat *ctuBins, Int64 stats[5][33], Int64 count[5][33]) {
+    for (int t = 0; t < 4; t++)
+      for (int c = 0; c < 5; c++) stats[t][c] += ctuBins[5 * t + c].diff, count[t][c] += ctuBins[5 * t + c].count;
+    for (int k = 1; k <= 32; k++) stats[4][k] += ctuBins[20 + k - 1].diff, count[4][k] += ctuBins[20 + k - 1].count;
+  }
+
+private:
+  Context &m_c;
+};
+
 } // namespace hmx_hm
