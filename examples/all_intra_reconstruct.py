@@ -2,7 +2,7 @@
 a planar YUV file out -- every stage through the C-ABI (thevc_amd/capi.py), nothing computed on the CPU.
 
     python examples/all_intra_reconstruct.py in.yuv out.yuv --width 416 --height 240 [--file-bits 8] [--bit-depth 8]
-                                             [--qp 32] [--frames N]
+                                             [--qp 32] [--frames N] [--batch 8]
 
 Decisions (block structure, intra modes, SAO parameters) are synthetic and seeded: libhmx accelerates the block
 path, it does not search.  Deblocking strengths follow from the decisions: every block is intra, so every
@@ -37,35 +37,45 @@ def run(args):
     tus = workload.make_tus(args.seed, pw, ph, "mix")
     pp = capi.PicParam(pw, ph, args.qp, 0, capi.I_SLICE, 1)
     plan = ctx.intra_plan(tus, pp)
-    org, rec, out = (capi.DevPicture(ctx, pw, ph) for _ in range(3))
+    G = max(1, getattr(args, "batch", 8))  # pictures whose loop filters run in one launch each
+    org = capi.DevPicture(ctx, pw, ph)
+    recs, outs = [capi.DevPicture(ctx, pw, ph) for _ in range(G)], [capi.DevPicture(ctx, pw, ph) for _ in range(G)]
     lev = capi.DevLevelsZ(ctx, pw, ph)
     uw, uh = pw // 4, ph // 4
     ev, eh = edge_maps(tus, pw, ph)
     units = np.zeros(uw * uh, np.dtype([("intra", "u1"), ("cbf", "u1"), ("ref", "i1", 2), ("mv", "<i2", (2, 2))]))
     units["intra"] = 1
-    d_units, d_ev, d_eh = ctx.to_device(units), ctx.to_device(ev), ctx.to_device(eh)
-    d_bv, d_bh = ctx.alloc(uw * uh), ctx.alloc(uw * uh)
-    d_qp = ctx.to_device(np.full(uw * uh, args.qp, np.int8))
+    per_pic = lambda a: ctx.to_device(np.ascontiguousarray(np.broadcast_to(a, (G,) + a.shape)))  # the maps are [picture][unit]
+    d_units, d_ev, d_eh = per_pic(units), per_pic(ev), per_pic(eh)
+    d_bv, d_bh = ctx.alloc(G * uw * uh), ctx.alloc(G * uw * uh)
+    d_qp = per_pic(np.full(uw * uh, args.qp, np.int8))
     rng = np.random.default_rng(args.seed)
     n_lcu = -(-pw // 64) * -(-ph // 64)
     sao = np.zeros((3, n_lcu), np.dtype([("type", "i1"), ("band", "u1"), ("offset", "i1", 4)]))
     sao["type"] = rng.integers(-1, 5, (3, n_lcu))
     sao["band"] = rng.integers(0, 32, (3, n_lcu))
     sao["offset"] = rng.integers(-2, 3, (3, n_lcu, 4))
-    d_sao = ctx.to_device(np.ascontiguousarray(sao))
+    d_sao = per_pic(sao)
     rd = yuvio.YuvReader(ctx, args.input, w, h, args.file_bits)
     wr = yuvio.YuvWriter(ctx, args.output, args.file_bits)
-    n = 0
+    n, more = 0, True
     A = lambda x, T: (T * 1)(x.as_pic())
-    while (args.frames <= 0 or n < args.frames) and rd.read(org, pw - w, ph - h):
-        ctx._chk(L.hmx_frame_intra_encode(ctx.h, plan, 1, A(org, capi.Pic), A(rec, capi.Pic), A(lev, capi.Levels)))
-        ctx._chk(L.hmx_deblock_strengths(ctx.h, d_units.ptr, d_ev.ptr, d_eh.ptr, pw, ph, 0, d_bv.ptr, d_bh.ptr))
-        p = rec.as_pic()
-        ctx._chk(L.hmx_deblock_picture(ctx.h, C.byref(p), pw, ph, d_bv.ptr, d_bh.ptr, d_qp.ptr, None, 0, 0))
-        q = out.as_pic()
-        ctx._chk(L.hmx_sao_picture(ctx.h, C.byref(p), C.byref(q), pw, ph, d_sao.ptr, n_lcu))
-        wr.write(out, pw, ph, pw - w, ph - h)
-        n += 1
+    while more:
+        g = 0
+        while g < G and (args.frames <= 0 or n + g < args.frames):
+            more = rd.read(org, pw - w, ph - h)
+            if not more:
+                break
+            ctx._chk(L.hmx_frame_intra_encode(ctx.h, plan, 1, A(org, capi.Pic), A(recs[g], capi.Pic), A(lev, capi.Levels)))
+            g += 1
+        more = more and g == G
+        if g:
+            ctx.deblock_strengths(g, d_units, d_ev, d_eh, pw, ph, np.zeros(g, np.uint8), d_bv, d_bh)
+            ctx.deblock_pictures(recs[:g], pw, ph, d_bv, d_bh, d_qp)
+            ctx.sao_pictures(recs[:g], outs[:g], pw, ph, d_sao)
+            for out in outs[:g]:
+                wr.write(out, pw, ph, pw - w, ph - h)
+            n += g
     ctx.sync()
     rd.close(), wr.close()
     L.hmx_intra_plan_destroy(ctx.h, plan)
@@ -84,5 +94,6 @@ if __name__ == "__main__":
     ap.add_argument("--qp", type=int, default=32)
     ap.add_argument("--frames", type=int, default=0)
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--batch", type=int, default=8, help="pictures per loop-filter launch")
     a = ap.parse_args()
     print(f"{run(a)[0]} frame(s) written to {a.output}")

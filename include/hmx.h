@@ -569,6 +569,22 @@ int hmx_deblock_strengths(hmx_ctx *ctx, const hmx_dbk_unit *d_units, const uint8
 int hmx_deblock_picture(hmx_ctx *ctx, const hmx_pic *rec, int pic_w, int pic_h, const uint8_t *d_bs_ver,
                         const uint8_t *d_bs_hor, const int8_t *d_qp, const uint8_t *d_no_filter, int beta_offset_div2,
                         int tc_offset_div2);
+/* The same for n_pics (1..65535) pictures of one size in one launch each (loopFilterPic :153-201 per picture; the
+ * deblocking filters both directions of a picture in one pass).  Picture i of the batch gets what the single-picture call
+ * gives for picture i's arguments; the single-picture calls are these with n_pics = 1.
+ * rec: host array [n_pics] of descriptors of device planes (each picture its own planes and strides; margins and unaligned
+ * planes allowed).  Two entries of rec must not alias (they are filtered in place, concurrently); this is not checked.
+ * Device maps are contiguous per picture, [pic][4x4 unit in raster order]: d_units, d_edge_ver, d_edge_hor, d_bs_ver,
+ * d_bs_hor, d_qp, d_no_filter (may be NULL, for all pictures).  is_b_slice, beta_offset_div2, tc_offset_div2: host arrays
+ * [n_pics] (slice-level values, slice_deblocking_filter offsets :593-594); the two offset arrays may be NULL = 0.
+ * HMX_ERR_ARG, before anything is launched: a null pointer, a null plane, n_pics out of range, pic_w or pic_h not a
+ * positive multiple of 8. */
+int hmx_deblock_strengths_multi(hmx_ctx *ctx, int n_pics, const hmx_dbk_unit *d_units, const uint8_t *d_edge_ver,
+                                const uint8_t *d_edge_hor, int pic_w, int pic_h, const uint8_t *is_b_slice,
+                                uint8_t *d_bs_ver, uint8_t *d_bs_hor);
+int hmx_deblock_picture_multi(hmx_ctx *ctx, int n_pics, const hmx_pic *rec, int pic_w, int pic_h, const uint8_t *d_bs_ver,
+                              const uint8_t *d_bs_hor, const int8_t *d_qp, const uint8_t *d_no_filter,
+                              const int8_t *beta_offset_div2, const int8_t *tc_offset_div2);
 
 /* Sample adaptive offset, the application part (TLibCommon/TComSampleAdaptiveOffset.cpp:781-1240: SAOProcess,
  * processSaoUnitAll, processSaoCuOrg), from the deblocked picture `in` to `out` (different
@@ -583,6 +599,14 @@ typedef struct hmx_sao_lcu {
 } hmx_sao_lcu;
 int hmx_sao_picture(hmx_ctx *ctx, const hmx_pic *in, const hmx_pic *out, int pic_w, int pic_h, const hmx_sao_lcu *d_params,
                     int n_lcu);
+/* The same for n_pics (1..65535) pictures of one size in one launch (SAOProcess :781 per picture); hmx_sao_picture is this
+ * with n_pics = 1.  in / out: host arrays [n_pics] of descriptors of device planes (each picture its own planes and strides;
+ * margins and unaligned planes allowed).  d_params (device): [pic][component][CTU in raster order].  Two entries of out
+ * must not alias, and no entry of out may alias an entry of in; only in[i] against out[i] is checked.
+ * HMX_ERR_ARG, before anything is launched: a null pointer, a null plane, n_pics out of range, an odd or non-positive size,
+ * n_lcu not the CTU count of a picture, in[i] and out[i] sharing a plane. */
+int hmx_sao_picture_multi(hmx_ctx *ctx, int n_pics, const hmx_pic *in, const hmx_pic *out, int pic_w, int pic_h,
+                          const hmx_sao_lcu *d_params, int n_lcu);
 
 /* Sample adaptive offset, the encoder's statistics pass: TEncSampleAdaptiveOffset::calcSaoStatsCuOrg
  * (TLibEncoder/TEncSampleAdaptiveOffset.cpp:859-1124 with SAO_SKIP_RIGHT, TLibCommon/TypeDef.h:123), which rdoSaoUnitAll

@@ -240,6 +240,12 @@ def lib():
         L.hmx_sao_stats.argtypes = [vp, C.POINTER(Pic), C.POINTER(Pic), ci, ci, ci, vp]
         L.hmx_deblock_strengths.argtypes = [vp, vp, vp, vp, ci, ci, ci, vp, vp]
         L.hmx_deblock_picture.argtypes = [vp, C.POINTER(Pic), ci, ci, vp, vp, vp, vp, ci, ci]
+        for name, at in (("hmx_deblock_strengths_multi", [vp, ci, vp, vp, vp, ci, ci, vp, vp, vp]),
+                         ("hmx_deblock_picture_multi", [vp, ci, C.POINTER(Pic), ci, ci, vp, vp, vp, vp, vp, vp]),
+                         ("hmx_sao_picture_multi", [vp, ci, C.POINTER(Pic), C.POINTER(Pic), ci, ci, vp, ci])):
+            if "HMX_LIB_PATH" in os.environ and not hasattr(L, name):
+                continue  # an older build loaded for an A/B run (tools/filters_bench.py): calling the entry still raises
+            getattr(L, name).argtypes = at
         L.hmx_yuv_frame_bytes.argtypes = [ci, ci, ci]
         L.hmx_yuv_frame_bytes.restype = C.c_size_t
         L.hmx_yuv_unpack.argtypes = [vp, vp, ci, C.POINTER(Pic), ci, ci, ci, ci]
@@ -622,6 +628,37 @@ class Context:
             return out.download(np.int32).reshape(n, 3, n_lcu, SAO_STAT_BINS, 2)
         finally:
             out.free()
+
+    def deblock_strengths(self, n, d_units, d_edge_ver, d_edge_hor, w, h, is_b, d_bs_ver, d_bs_hor):
+        """hmx_deblock_strengths_multi: the boundary strengths of n pictures in one launch.  The maps are DevBufs (or device
+        addresses) laid out [pic][4x4 unit]; is_b: one flag per picture (B slice)."""
+        is_b = np.ascontiguousarray(is_b, np.uint8)
+        assert n > 0 and is_b.shape == (n,)
+        ptr = lambda d: getattr(d, "ptr", d)
+        self._chk(lib().hmx_deblock_strengths_multi(self.h, n, ptr(d_units), ptr(d_edge_ver), ptr(d_edge_hor), w, h, _hp(is_b),
+                                                    ptr(d_bs_ver), ptr(d_bs_hor)))
+
+    def deblock_pictures(self, recs, w, h, d_bs_ver, d_bs_hor, d_qp, d_no_filter=None, beta_offset_div2=None, tc_offset_div2=None):
+        """hmx_deblock_picture_multi: n pictures (DevPictures) deblocked in place in one launch.  The maps are DevBufs (or
+        device addresses) laid out [pic][4x4 unit]; the offsets: one per picture, or None for 0."""
+        n = len(recs)
+        assert n > 0
+        r = (Pic * n)(*[p.as_pic() for p in recs])
+        ptr = lambda d: getattr(d, "ptr", d)
+        offs = [None if o is None else np.ascontiguousarray(o, np.int8) for o in (beta_offset_div2, tc_offset_div2)]
+        assert all(o is None or o.shape == (n,) for o in offs)
+        self._chk(lib().hmx_deblock_picture_multi(self.h, n, r, w, h, ptr(d_bs_ver), ptr(d_bs_hor), ptr(d_qp), ptr(d_no_filter),
+                                                  *[None if o is None else _hp(o) for o in offs]))
+
+    def sao_pictures(self, ins, outs, w, h, d_params):
+        """hmx_sao_picture_multi: SAO from n deblocked pictures to n output pictures (DevPictures) in one launch.  d_params: a
+        DevBuf (or device address) of hmx_sao_lcu laid out [pic][component][CTU]."""
+        n = len(ins)
+        assert n == len(outs) and n > 0
+        ctu = self.ctu_size
+        n_lcu = -(-w // ctu) * -(-h // ctu)
+        a, b = (Pic * n)(*[p.as_pic() for p in ins]), (Pic * n)(*[p.as_pic() for p in outs])
+        self._chk(lib().hmx_sao_picture_multi(self.h, n, a, b, w, h, getattr(d_params, "ptr", d_params), n_lcu))
 
 
 SAO_STAT_BINS = 52  # HMX_SAO_STAT_BINS

@@ -2,11 +2,24 @@
 #include "hmx_host.h"
 
 // ---- deblocking filter, application part (TLibCommon/TComLoopFilter.cpp:571-922) ----
-// One launch per direction over the whole picture (loopFilterPic :153-201 filters every vertical edge of the
-// picture before the first horizontal one).  Work item = one 4x4 luma unit whose left (top) side is an edge of
-// the 8x8 grid with a non-zero strength: the thread filters the unit's four luma lines and, on the chroma grid
-// with strength 2, two lines of Cb and Cr.  Edges are 8 samples apart and a filter reads 4 and writes 3 samples
-// per side, so the work items of one launch touch disjoint samples.
+// One launch per batch, grid = (windows of a picture, pictures); both directions in one pass through LDS (loopFilterPic
+// :153-201 filters every vertical edge of the picture before the first horizontal one).  A workgroup owns the 64x64 luma
+// window [x0-4, x0+60) x [y0-4, y0+60) clipped to the picture and the 32x32 windows of Cb and Cr at (x0/2-2, y0/2-2).  Edges
+// are 8 samples apart and a luma filter reads 4 and writes 3 samples per side (chroma: reads 2, writes 1), so with that shift
+// every edge of the 8x8 grid inside a window has its whole support inside it, and a horizontal edge reads only samples whose
+// vertical-edge filtering (decided per 4 lines, and the window starts on a multiple of 4) happened in the same window.  The
+// windows of a picture are disjoint and cover it: the picture is read once and written once, in place, with no halo.
+//   load -> vertical edges in LDS -> barrier -> horizontal edges -> barrier -> store
+// Work item of a direction = one 4x4 luma unit whose left (top) side is an edge of the 8x8 grid with a non-zero strength:
+// its four luma lines (threads 0..127: 8 edges x 16 segments of a window) or, on the chroma grid with strength 2, its two lines
+// of Cb or Cr (threads 128..255: 2 planes x 4 edges x 16 segments).
+// LDS rows: luma pitch 72 shorts (144 B), chroma 40 (80 B).  Vertical luma edges are read with one 16-byte access per line at
+// row * 144 + 16 * edge: four lines are 576 = 64 mod 256 bytes apart, and with edge = lane & 3 (+ 4 * wave), segment =
+// lane >> 2 each of the hardware's 16-lane groups of that access covers all 64 banks once.  Horizontal luma edges read 8 bytes
+// per row at row * 144 + 8 * segment: two edges (8 rows = 1152 = 128 mod 256 bytes apart) x 16 segments fill the banks of a
+// 32-lane group once.  (A pitch of 64 shorts puts every row of a column on one bank.)  Chroma: the vertical pass is
+// conflict-free at pitch 40 (2 rows = 160 B, 4 edges x 16 B); its horizontal pass reads dwords 2-way (8 rows = 640 B = 0 mod 128).
+typedef short s8v __attribute__((ext_vector_type(8)));
 static __constant__ unsigned char kDbkTc[54] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 1, 1, 1, 1, 1,
                                          2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 5, 5, 6, 6, 7, 8, 9, 10, 11, 13, 14, 16, 18, 20, 22, 24};
 static __constant__ unsigned char kDbkBeta[52] = {0,  0,  0,  0,  0,  0,  0,  0,  0,  0,  0,  0,  0,  0,  0,  0,  6,  7,  8,  9,  10, 11, 12, 13, 14, 15,
@@ -14,87 +27,252 @@ static __constant__ unsigned char kDbkBeta[52] = {0,  0,  0,  0,  0,  0,  0,  0,
 static __constant__ unsigned char kChromaScale[58] = {0,  1,  2,  3,  4,  5,  6,  7,  8,  9,  10, 11, 12, 13, 14, 15, 16, 17, 18, 19,
                                                20, 21, 22, 23, 24, 25, 26, 27, 28, 29, 29, 30, 31, 32, 33, 33, 34, 34, 35, 35,
                                                36, 36, 37, 37, 38, 39, 40, 41, 42, 43, 44, 45, 46, 47, 48, 49, 50, 51};
-struct DbkArgs {
+constexpr int kDbkLumaPitch = 72, kDbkChromaPitch = 40; // shorts
+constexpr int kDbkLumaChunks = 9, kDbkChromaChunks = 5; // aligned 8-sample runs of the picture that a window row touches
+struct DbkPic { // one picture of the batch (in the argument arena)
   PlanesDev rec;
-  const unsigned char *bs; // of this direction
-  const signed char *qp;
-  const unsigned char *no_filter;
-  int uw, uh, dir, B, boff, toff;
+  int boff, toff;
 };
-__global__ __launch_bounds__(256) void k_deblock(DbkArgs A) {
-  const int u = blockIdx.x * blockDim.x + threadIdx.x;
-  if (u >= A.uw * A.uh) return;
-  const int ux = u % A.uw, uy = u / A.uw, dir = A.dir;
-  const int b = A.bs[u];
-  if (!b || ((dir ? uy : ux) & 1)) return;
-  const int up = dir ? u - A.uw : u - 1;
-  const bool pn = A.no_filter && A.no_filter[up], qn = A.no_filter && A.no_filter[u];
-  const int q_avg = ((int)A.qp[up] + (int)A.qp[u] + 1) >> 1;
-  const int B = A.B, scale = 1 << (B - 8), maxv = (1 << B) - 1;
-  {
-    const int tc = kDbkTc[clip3(0, 53, q_avg + 2 * (b - 1) + (A.toff << 1))] * scale;
-    const int beta = kDbkBeta[clip3(0, 51, q_avg + (A.boff << 1))] * scale;
-    const int side = (beta + (beta >> 1)) >> 3, cut = tc * 10;
-    const int st = A.rec.s[0], across = dir ? st : 1, along = dir ? 1 : st;
-    short *s = A.rec.p[0] + (size_t)(4 * uy) * st + 4 * ux;
-    int m[4][8];
+struct DbkArgs {
+  const DbkPic *pics;                   // [n_pics]
+  const unsigned char *bs_ver, *bs_hor; // [pic][unit]
+  const signed char *qp;
+  const unsigned char *no_filter; // or null
+  int w, h, uw, uh, tiles_x, B;
+};
+struct DbkUnit { // what an edge segment takes from the maps
+  int b, q_avg;
+  bool pn, qn;
+};
+__device__ __forceinline__ DbkUnit dbk_unit(const DbkArgs &A, const unsigned char *bs, size_t base, int u, int up) {
+  DbkUnit e;
+  e.b = bs[base + u];
+  e.pn = A.no_filter && A.no_filter[base + up], e.qn = A.no_filter && A.no_filter[base + u];
+  e.q_avg = ((int)A.qp[base + up] + (int)A.qp[base + u] + 1) >> 1;
+  return e;
+}
+// four lines across a luma edge, m[l][0..3] the P side and m[l][4..7] the Q side (xEdgeFilterLuma :626-700, xPelFilterLuma
+// :780-850), filtered in the registers; false = the edge stays as it is
+__device__ __forceinline__ bool dbk_luma(int m[4][8], const DbkUnit &e, int boff, int toff, int B) {
+  const int scale = 1 << (B - 8), maxv = (1 << B) - 1;
+  const int tc = kDbkTc[clip3(0, 53, e.q_avg + 2 * (e.b - 1) + (toff << 1))] * scale;
+  const int beta = kDbkBeta[clip3(0, 51, e.q_avg + (boff << 1))] * scale;
+  const int side = (beta + (beta >> 1)) >> 3, cut = tc * 10;
+  const int dp0 = abs(m[0][1] - 2 * m[0][2] + m[0][3]), dq0 = abs(m[0][4] - 2 * m[0][5] + m[0][6]);
+  const int dp3 = abs(m[3][1] - 2 * m[3][2] + m[3][3]), dq3 = abs(m[3][4] - 2 * m[3][5] + m[3][6]);
+  const int d0 = dp0 + dq0, d3 = dp3 + dq3, dp = dp0 + dp3, dq = dq0 + dq3, d = d0 + d3;
+  if (d >= beta) return false;
+  const bool fp = dp < side, fq = dq < side;
+  const bool s0 = (abs(m[0][0] - m[0][3]) + abs(m[0][7] - m[0][4]) < (beta >> 3)) && (2 * d0 < (beta >> 2)) &&
+                  (abs(m[0][3] - m[0][4]) < ((tc * 5 + 1) >> 1));
+  const bool s3 = (abs(m[3][0] - m[3][3]) + abs(m[3][7] - m[3][4]) < (beta >> 3)) && (2 * d3 < (beta >> 2)) &&
+                  (abs(m[3][3] - m[3][4]) < ((tc * 5 + 1) >> 1));
+  const bool strong = s0 && s3;
 #pragma unroll
-    for (int l = 0; l < 4; l++)
-#pragma unroll
-      for (int k = 0; k < 8; k++) m[l][k] = s[(ptrdiff_t)l * along + (ptrdiff_t)(k - 4) * across];
-    const int dp0 = abs(m[0][1] - 2 * m[0][2] + m[0][3]), dq0 = abs(m[0][4] - 2 * m[0][5] + m[0][6]);
-    const int dp3 = abs(m[3][1] - 2 * m[3][2] + m[3][3]), dq3 = abs(m[3][4] - 2 * m[3][5] + m[3][6]);
-    const int d0 = dp0 + dq0, d3 = dp3 + dq3, dp = dp0 + dp3, dq = dq0 + dq3, d = d0 + d3;
-    if (d < beta) {
-      const bool fp = dp < side, fq = dq < side;
-      const bool s0 = (abs(m[0][0] - m[0][3]) + abs(m[0][7] - m[0][4]) < (beta >> 3)) && (2 * d0 < (beta >> 2)) &&
-                      (abs(m[0][3] - m[0][4]) < ((tc * 5 + 1) >> 1));
-      const bool s3 = (abs(m[3][0] - m[3][3]) + abs(m[3][7] - m[3][4]) < (beta >> 3)) && (2 * d3 < (beta >> 2)) &&
-                      (abs(m[3][3] - m[3][4]) < ((tc * 5 + 1) >> 1));
-      const bool strong = s0 && s3;
-#pragma unroll
-      for (int l = 0; l < 4; l++) {
-        const int m0 = m[l][0], m1 = m[l][1], m2 = m[l][2], m3 = m[l][3], m4 = m[l][4], m5 = m[l][5], m6 = m[l][6], m7 = m[l][7];
-        int n1 = m1, n2 = m2, n3 = m3, n4 = m4, n5 = m5, n6 = m6;
-        if (strong) {
-          n3 = clip3(m3 - 2 * tc, m3 + 2 * tc, (m1 + 2 * m2 + 2 * m3 + 2 * m4 + m5 + 4) >> 3);
-          n4 = clip3(m4 - 2 * tc, m4 + 2 * tc, (m2 + 2 * m3 + 2 * m4 + 2 * m5 + m6 + 4) >> 3);
-          n2 = clip3(m2 - 2 * tc, m2 + 2 * tc, (m1 + m2 + m3 + m4 + 2) >> 2);
-          n5 = clip3(m5 - 2 * tc, m5 + 2 * tc, (m3 + m4 + m5 + m6 + 2) >> 2);
-          n1 = clip3(m1 - 2 * tc, m1 + 2 * tc, (2 * m0 + 3 * m1 + m2 + m3 + m4 + 4) >> 3);
-          n6 = clip3(m6 - 2 * tc, m6 + 2 * tc, (m3 + m4 + m5 + 3 * m6 + 2 * m7 + 4) >> 3);
-        } else {
-          int delta = (9 * (m4 - m3) - 3 * (m5 - m2) + 8) >> 4;
-          if (abs(delta) < cut) {
-            delta = clip3(-tc, tc, delta);
-            n3 = clip3(0, maxv, m3 + delta);
-            n4 = clip3(0, maxv, m4 - delta);
-            const int tc2 = tc >> 1;
-            if (fp) n2 = clip3(0, maxv, m2 + clip3(-tc2, tc2, ((((m1 + m3 + 1) >> 1) - m2 + delta) >> 1)));
-            if (fq) n5 = clip3(0, maxv, m5 + clip3(-tc2, tc2, ((((m6 + m4 + 1) >> 1) - m5 - delta) >> 1)));
-          }
-        }
-        short *pl = s + (ptrdiff_t)l * along;
-        if (!pn) pl[-across] = (short)n3, pl[-2 * across] = (short)n2, pl[-3 * across] = (short)n1;
-        if (!qn) pl[0] = (short)n4, pl[across] = (short)n5, pl[2 * across] = (short)n6;
+  for (int l = 0; l < 4; l++) {
+    const int m0 = m[l][0], m1 = m[l][1], m2 = m[l][2], m3 = m[l][3], m4 = m[l][4], m5 = m[l][5], m6 = m[l][6], m7 = m[l][7];
+    int n1 = m1, n2 = m2, n3 = m3, n4 = m4, n5 = m5, n6 = m6;
+    if (strong) {
+      n3 = clip3(m3 - 2 * tc, m3 + 2 * tc, (m1 + 2 * m2 + 2 * m3 + 2 * m4 + m5 + 4) >> 3);
+      n4 = clip3(m4 - 2 * tc, m4 + 2 * tc, (m2 + 2 * m3 + 2 * m4 + 2 * m5 + m6 + 4) >> 3);
+      n2 = clip3(m2 - 2 * tc, m2 + 2 * tc, (m1 + m2 + m3 + m4 + 2) >> 2);
+      n5 = clip3(m5 - 2 * tc, m5 + 2 * tc, (m3 + m4 + m5 + m6 + 2) >> 2);
+      n1 = clip3(m1 - 2 * tc, m1 + 2 * tc, (2 * m0 + 3 * m1 + m2 + m3 + m4 + 4) >> 3);
+      n6 = clip3(m6 - 2 * tc, m6 + 2 * tc, (m3 + m4 + m5 + 3 * m6 + 2 * m7 + 4) >> 3);
+    } else {
+      int delta = (9 * (m4 - m3) - 3 * (m5 - m2) + 8) >> 4;
+      if (abs(delta) < cut) {
+        delta = clip3(-tc, tc, delta);
+        n3 = clip3(0, maxv, m3 + delta);
+        n4 = clip3(0, maxv, m4 - delta);
+        const int tc2 = tc >> 1;
+        if (fp) n2 = clip3(0, maxv, m2 + clip3(-tc2, tc2, ((((m1 + m3 + 1) >> 1) - m2 + delta) >> 1)));
+        if (fq) n5 = clip3(0, maxv, m5 + clip3(-tc2, tc2, ((((m6 + m4 + 1) >> 1) - m5 - delta) >> 1)));
       }
     }
+    if (!e.pn) m[l][3] = n3, m[l][2] = n2, m[l][1] = n1;
+    if (!e.qn) m[l][4] = n4, m[l][5] = n5, m[l][6] = n6;
   }
-  if (b > 1 && !((dir ? uy : ux) & 3)) { // chroma: its own 8x8 grid, strength 2 only (:709-712, :740)
-    const int qc = kChromaScale[clip3(0, 51, q_avg)];
-    const int tc = kDbkTc[clip3(0, 53, qc + 2 * (b - 1) + (A.toff << 1))] * scale;
+  return true;
+}
+// tc of a chroma edge: its own 8x8 grid, strength 2 only (:709-712, :740); one line m2 m3 | m4 m5 (xPelFilterChroma :861-878)
+__device__ __forceinline__ int dbk_chroma_tc(const DbkUnit &e, int toff, int B) {
+  const int qc = kChromaScale[clip3(0, 51, e.q_avg)];
+  return kDbkTc[clip3(0, 53, qc + 2 * (e.b - 1) + (toff << 1))] * (1 << (B - 8));
+}
+__device__ __forceinline__ void dbk_chroma(int m2, int &m3, int &m4, int m5, const DbkUnit &e, int tc, int B) {
+  const int maxv = (1 << B) - 1;
+  const int delta = clip3(-tc, tc, ((((m4 - m3) << 2) + m2 - m5 + 4) >> 3));
+  const int n3 = clip3(0, maxv, m3 + delta), n4 = clip3(0, maxv, m4 - delta);
+  if (!e.pn) m3 = n3;
+  if (!e.qn) m4 = n4;
+}
+// The run of 8 samples number i of a workgroup's three windows: luma 64 rows x 9 runs, then Cb and Cr 32 rows x 5 runs each.
+// A run starts on a multiple of 8 of the plane (16-byte accesses on aligned planes); the window starts 4 (chroma: 6) samples
+// into the first run and ends 4 (6) samples into the last.
+constexpr int kDbkRuns = 64 * kDbkLumaChunks + 2 * 32 * kDbkChromaChunks;
+struct DbkRun {
+  short *g;   // the run in the plane, or null when no sample of it is in the window
+  short *lds; // where sample 0 of the run would go (it may lie before the row: lo says where the window begins)
+  int lo, hi; // samples [lo, hi) of the run are in the window and the plane (even)
+  bool vec;   // the whole run is in the plane and 16-byte aligned
+};
+__device__ __forceinline__ DbkRun dbk_run(const DbkArgs &A, const PlanesDev *R, int i, int x0, int y0, short *sy, short *sc) {
+  int p = 0, r, j;
+  if (i < 64 * kDbkLumaChunks) {
+    r = i / kDbkLumaChunks, j = i - r * kDbkLumaChunks;
+  } else {
+    int k = i - 64 * kDbkLumaChunks;
+    p = 1 + k / (32 * kDbkChromaChunks), k -= (p - 1) * (32 * kDbkChromaChunks);
+    r = k / kDbkChromaChunks, j = k - r * kDbkChromaChunks;
+  }
+  const int sh = p ? 1 : 0, off = 4 >> sh, ws = 64 >> sh, w = A.w >> sh, h = A.h >> sh;
+  const int y = (y0 >> sh) - off + r, xa = (x0 >> sh) - 8 + 8 * j, col0 = 8 * j - 8 + off; // window column of sample 0
+  DbkRun q;
+  q.g = nullptr;
+  q.lo = max(0, -col0), q.hi = min(min(8, ws - col0), w - xa);
+  if (y < 0 || y >= h || xa < 0 || q.lo >= q.hi) return q;
+  const int st = R->s[p]; // indexed in memory: a copy indexed by p would live in scratch
+  q.g = R->p[p] + (size_t)y * st + xa;
+  q.lds = (p == 0 ? sy + r * kDbkLumaPitch : sc + ((p - 1) * 32 + r) * kDbkChromaPitch) + col0;
+  q.vec = xa + 8 <= w && (((uintptr_t)q.g | (uintptr_t)(2 * st)) & 15) == 0;
+  return q;
+}
+__global__ __launch_bounds__(256) void k_deblock(DbkArgs A) {
+  __shared__ __attribute__((aligned(16))) short sy[64 * kDbkLumaPitch];
+  __shared__ __attribute__((aligned(16))) short sc[2 * 32 * kDbkChromaPitch];
+  const int t = threadIdx.x, pic = blockIdx.y;
+  const int x0 = (blockIdx.x % A.tiles_x) * 64, y0 = (blockIdx.x / A.tiles_x) * 64;
+  const DbkPic *P = A.pics + pic;
+  const PlanesDev *R = &P->rec;
+  const int boff = P->boff, toff = P->toff, B = A.B, uw = A.uw;
+  const size_t base = (size_t)pic * uw * A.uh;
+  for (int i = t; i < kDbkRuns; i += 256) { // the windows into LDS
+    const DbkRun q = dbk_run(A, R, i, x0, y0, sy, sc);
+    if (!q.g) continue;
+    short v[8];
+    if (q.vec) {
+      const s8v iv = *reinterpret_cast<const s8v *>(q.g);
 #pragma unroll
-    for (int p = 1; p < 3; p++) {
-      const int st = A.rec.s[p], across = dir ? st : 1, along = dir ? 1 : st;
-      short *c0 = A.rec.p[p] + (size_t)(2 * uy) * st + 2 * ux;
+      for (int k = 0; k < 8; k++) v[k] = iv[k];
+    } else {
 #pragma unroll
-      for (int k = 0; k < 2; k++) {
-        short *s = c0 + (ptrdiff_t)k * along;
-        const int m2 = s[-2 * across], m3 = s[-across], m4 = s[0], m5 = s[across];
-        const int delta = clip3(-tc, tc, ((((m4 - m3) << 2) + m2 - m5 + 4) >> 3));
-        if (!pn) s[-across] = (short)clip3(0, maxv, m3 + delta);
-        if (!qn) s[0] = (short)clip3(0, maxv, m4 - delta);
+      for (int k = 0; k < 8; k++) v[k] = q.g[min(k, q.hi - 1)];
+    }
+#pragma unroll
+    for (int k = 0; k < 8; k += 2)
+      if (k >= q.lo && k < q.hi) *reinterpret_cast<unsigned *>(q.lds + k) = (unsigned)(unsigned short)v[k] | (unsigned)(unsigned short)v[k + 1] << 16;
+  }
+  __syncthreads();
+#pragma unroll 1
+  for (int dir = 0; dir < 2; dir++) {
+    const unsigned char *bs = dir ? A.bs_hor : A.bs_ver;
+    if (t < 128) {
+      // vertical: edge column x0 + 8e = window column 4 + 8e, lines 4 seg ..; horizontal: edge row y0 + 8e, columns 4 seg ..
+      const int e = dir ? t >> 4 : (t & 3) | ((t >> 6) << 2), seg = dir ? t & 15 : (t >> 2) & 15;
+      const int x = dir ? x0 - 4 + 4 * seg : x0 + 8 * e, y = dir ? y0 + 8 * e : y0 - 4 + 4 * seg;
+      if (x >= 0 && x < A.w && y >= 0 && y < A.h && (dir ? y : x) > 0) {
+        const int u = (y >> 2) * uw + (x >> 2);
+        const DbkUnit E = dbk_unit(A, bs, base, u, dir ? u - uw : u - 1);
+        if (E.b) {
+          int m[4][8];
+          if (!dir) {
+            short *s = sy + (4 * seg) * kDbkLumaPitch + 8 * e;
+#pragma unroll
+            for (int l = 0; l < 4; l++) {
+              const s8v v = *reinterpret_cast<const s8v *>(s + l * kDbkLumaPitch);
+#pragma unroll
+              for (int k = 0; k < 8; k++) m[l][k] = v[k];
+            }
+            if (dbk_luma(m, E, boff, toff, B)) {
+#pragma unroll
+              for (int l = 0; l < 4; l++) {
+                s8v v;
+#pragma unroll
+                for (int k = 0; k < 8; k++) v[k] = (short)m[l][k];
+                *reinterpret_cast<s8v *>(s + l * kDbkLumaPitch) = v;
+              }
+            }
+          } else {
+            short *s = sy + (8 * e) * kDbkLumaPitch + 4 * seg;
+#pragma unroll
+            for (int k = 0; k < 8; k++) {
+              const s4v v = *reinterpret_cast<const s4v *>(s + k * kDbkLumaPitch);
+#pragma unroll
+              for (int l = 0; l < 4; l++) m[l][k] = v[l];
+            }
+            if (dbk_luma(m, E, boff, toff, B)) {
+#pragma unroll
+              for (int k = 1; k < 7; k++) {
+                s4v v;
+#pragma unroll
+                for (int l = 0; l < 4; l++) v[l] = (short)m[l][k];
+                *reinterpret_cast<s4v *>(s + k * kDbkLumaPitch) = v;
+              }
+            }
+          }
+        }
       }
+    } else {
+      // chroma, in chroma samples: vertical edge column x0/2 + 8e = window column 2 + 8e, lines 2 seg, 2 seg + 1; horizontal
+      // edge row y0/2 + 8e, columns 2 seg, 2 seg + 1
+      const int c = t - 128, i = c & 63;
+      short *pl = sc + (c >> 6) * 32 * kDbkChromaPitch;
+      const int e = dir ? i >> 4 : i & 3, seg = dir ? i & 15 : i >> 2;
+      const int x = dir ? (x0 >> 1) - 2 + 2 * seg : (x0 >> 1) + 8 * e, y = dir ? (y0 >> 1) + 8 * e : (y0 >> 1) - 2 + 2 * seg;
+      if (x >= 0 && x < (A.w >> 1) && y >= 0 && y < (A.h >> 1) && (dir ? y : x) > 0) {
+        const int u = (y >> 1) * uw + (x >> 1);
+        const DbkUnit E = dbk_unit(A, bs, base, u, dir ? u - uw : u - 1);
+        if (E.b > 1) {
+          const int tc = dbk_chroma_tc(E, toff, B);
+          if (!dir) {
+            short *s = pl + (2 * seg) * kDbkChromaPitch + 8 * e;
+#pragma unroll
+            for (int k = 0; k < 2; k++) {
+              s4v v = *reinterpret_cast<const s4v *>(s + k * kDbkChromaPitch);
+              int m3 = v[1], m4 = v[2];
+              dbk_chroma(v[0], m3, m4, v[3], E, tc, B);
+              v[1] = (short)m3, v[2] = (short)m4;
+              *reinterpret_cast<s4v *>(s + k * kDbkChromaPitch) = v;
+            }
+          } else {
+            short *s = pl + (8 * e) * kDbkChromaPitch + 2 * seg;
+            unsigned r[4];
+#pragma unroll
+            for (int j = 0; j < 4; j++) r[j] = *reinterpret_cast<const unsigned *>(s + j * kDbkChromaPitch);
+            unsigned o3 = 0, o4 = 0;
+#pragma unroll
+            for (int k = 0; k < 2; k++) {
+              int m3 = (short)(r[1] >> (16 * k)), m4 = (short)(r[2] >> (16 * k));
+              dbk_chroma((short)(r[0] >> (16 * k)), m3, m4, (short)(r[3] >> (16 * k)), E, tc, B);
+              o3 |= (unsigned)(unsigned short)m3 << (16 * k), o4 |= (unsigned)(unsigned short)m4 << (16 * k);
+            }
+            *reinterpret_cast<unsigned *>(s + kDbkChromaPitch) = o3;
+            *reinterpret_cast<unsigned *>(s + 2 * kDbkChromaPitch) = o4;
+          }
+        }
+      }
+    }
+    __syncthreads();
+  }
+  for (int i = t; i < kDbkRuns; i += 256) { // and back: whole runs with one 16-byte store, the cut ones by dwords or samples
+    const DbkRun q = dbk_run(A, R, i, x0, y0, sy, sc);
+    if (!q.g) continue;
+    unsigned v[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) v[k] = (2 * k >= q.lo && 2 * k < q.hi) ? *reinterpret_cast<const unsigned *>(q.lds + 2 * k) : 0;
+    if (q.vec && q.lo == 0 && q.hi == 8) {
+      typedef unsigned u4v __attribute__((ext_vector_type(4)));
+      const u4v ov = {v[0], v[1], v[2], v[3]};
+      *reinterpret_cast<u4v *>(q.g) = ov;
+    } else if ((((uintptr_t)q.g) & 3) == 0) {
+#pragma unroll
+      for (int k = 0; k < 4; k++)
+        if (2 * k >= q.lo && 2 * k < q.hi) *reinterpret_cast<unsigned *>(q.g + 2 * k) = v[k];
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; k++)
+        if (2 * k >= q.lo && 2 * k < q.hi) q.g[2 * k] = (short)(v[k] & 0xffff), q.g[2 * k + 1] = (short)(v[k] >> 16);
     }
   }
 }
@@ -114,9 +292,13 @@ __device__ __forceinline__ int dbk_strength(const hmx_dbk_unit &P, const hmx_dbk
   return (dbk_mv_far(Pm.mv[0], Q.mv[1]) || dbk_mv_far(Pm.mv[1], Q.mv[0])) && (dbk_mv_far(Pm.mv[0], Q.mv[0]) || dbk_mv_far(Pm.mv[1], Q.mv[1]));
 }
 __global__ __launch_bounds__(256) void k_dbk_strengths(const hmx_dbk_unit *units, const unsigned char *edge_ver, const unsigned char *edge_hor,
-                                                       int uw, int uh, int ctu, int is_b, unsigned char *bs_ver, unsigned char *bs_hor) {
-  const int u = blockIdx.x * blockDim.x + threadIdx.x;
+                                                       int uw, int uh, int ctu, const unsigned char *is_b_pic, unsigned char *bs_ver,
+                                                       unsigned char *bs_hor) {
+  const int u = blockIdx.x * blockDim.x + threadIdx.x, pic = blockIdx.y;
   if (u >= uw * uh) return;
+  const size_t base = (size_t)pic * uw * uh; // the maps of this picture
+  units += base, edge_ver += base, edge_hor += base;
+  const bool is_b = is_b_pic[pic] != 0;
   const int ux = u % uw, uy = u / uw;
   const hmx_dbk_unit Q = units[u];
   int bv = 0, bh = 0;
@@ -130,33 +312,56 @@ __global__ __launch_bounds__(256) void k_dbk_strengths(const hmx_dbk_unit *units
     if ((4 * uy) % ctu == 0) um = up - ux + (ux & ~3) + ((ux & 3) < 2 ? 0 : 3); // compressed motion of the CTU row above: [0 0 3 3]
     bh = dbk_strength(units[up], units[um], Q, (edge_hor[u] >> 1) & 1, is_b);
   }
-  bs_ver[u] = (unsigned char)bv;
-  bs_hor[u] = (unsigned char)bh;
+  bs_ver[base + u] = (unsigned char)bv;
+  bs_hor[base + u] = (unsigned char)bh;
+}
+extern "C" int hmx_deblock_strengths_multi(hmx_ctx *c, int n_pics, const hmx_dbk_unit *d_units, const uint8_t *d_edge_ver,
+                                           const uint8_t *d_edge_hor, int pic_w, int pic_h, const uint8_t *is_b_slice, uint8_t *d_bs_ver,
+                                           uint8_t *d_bs_hor) {
+  if (!c || !d_units || !d_edge_ver || !d_edge_hor || !is_b_slice || !d_bs_ver || !d_bs_hor)
+    return fail(c, HMX_ERR_ARG, "hmx_deblock_strengths_multi: null argument");
+  if (n_pics < 1 || n_pics > 65535) return fail(c, HMX_ERR_ARG, "hmx_deblock_strengths_multi: n_pics must be 1..65535");
+  if (pic_w <= 0 || pic_h <= 0 || (pic_w & 7) || (pic_h & 7))
+    return fail(c, HMX_ERR_ARG, "hmx_deblock_strengths_multi: picture size must be a positive multiple of 8");
+  const unsigned char *d_b = static_cast<const unsigned char *>(arena_push(c, is_b_slice, (size_t)n_pics));
+  if (!d_b) return fail(c, HMX_ERR_NOMEM, "argument arena");
+  const int uw = pic_w / 4, uh = pic_h / 4;
+  hipLaunchKernelGGL(k_dbk_strengths, dim3((unsigned)(((size_t)uw * uh + 255) / 256), (unsigned)n_pics), dim3(256), 0, c->stream, d_units,
+                     d_edge_ver, d_edge_hor, uw, uh, c->cfg.ctu_size, d_b, d_bs_ver, d_bs_hor);
+  HIPCHK(c, hipGetLastError());
+  return HMX_OK;
 }
 extern "C" int hmx_deblock_strengths(hmx_ctx *c, const hmx_dbk_unit *d_units, const uint8_t *d_edge_ver, const uint8_t *d_edge_hor, int pic_w,
                                      int pic_h, int is_b_slice, uint8_t *d_bs_ver, uint8_t *d_bs_hor) {
-  if (!c || !d_units || !d_edge_ver || !d_edge_hor || !d_bs_ver || !d_bs_hor || pic_w <= 0 || pic_h <= 0 || (pic_w & 7) || (pic_h & 7))
-    return fail(c, HMX_ERR_ARG, "hmx_deblock_strengths: null argument or picture size not a multiple of 8");
-  const int uw = pic_w / 4, uh = pic_h / 4;
-  hipLaunchKernelGGL(k_dbk_strengths, dim3((unsigned)(((size_t)uw * uh + 255) / 256)), dim3(256), 0, c->stream, d_units, d_edge_ver, d_edge_hor,
-                     uw, uh, c->cfg.ctu_size, is_b_slice, d_bs_ver, d_bs_hor);
+  const uint8_t is_b = is_b_slice ? 1 : 0;
+  return hmx_deblock_strengths_multi(c, 1, d_units, d_edge_ver, d_edge_hor, pic_w, pic_h, &is_b, d_bs_ver, d_bs_hor);
+}
+
+extern "C" int hmx_deblock_picture_multi(hmx_ctx *c, int n_pics, const hmx_pic *rec, int pic_w, int pic_h, const uint8_t *d_bs_ver,
+                                         const uint8_t *d_bs_hor, const int8_t *d_qp, const uint8_t *d_no_filter, const int8_t *beta_offset_div2,
+                                         const int8_t *tc_offset_div2) {
+  if (!c || !rec || !d_bs_ver || !d_bs_hor || !d_qp) return fail(c, HMX_ERR_ARG, "hmx_deblock_picture_multi: null argument");
+  if (n_pics < 1 || n_pics > 65535) return fail(c, HMX_ERR_ARG, "hmx_deblock_picture_multi: n_pics must be 1..65535");
+  if (pic_w <= 0 || pic_h <= 0 || (pic_w & 7) || (pic_h & 7))
+    return fail(c, HMX_ERR_ARG, "hmx_deblock_picture_multi: picture size must be a positive multiple of 8");
+  std::vector<DbkPic> t((size_t)n_pics);
+  for (int i = 0; i < n_pics; i++) {
+    for (int p = 0; p < 3; p++)
+      if (!rec[i].plane[p]) return fail(c, HMX_ERR_ARG, "hmx_deblock_picture_multi: null plane");
+    t[i] = DbkPic{to_dev(&rec[i]), beta_offset_div2 ? beta_offset_div2[i] : 0, tc_offset_div2 ? tc_offset_div2[i] : 0};
+  }
+  const DbkPic *d = static_cast<const DbkPic *>(arena_push(c, t.data(), sizeof(DbkPic) * t.size()));
+  if (!d) return fail(c, HMX_ERR_NOMEM, "argument arena");
+  const int tiles_x = (pic_w + 4 + 63) / 64, tiles_y = (pic_h + 4 + 63) / 64; // windows start at 64 k - 4
+  DbkArgs A{d, d_bs_ver, d_bs_hor, d_qp, d_no_filter, pic_w, pic_h, pic_w / 4, pic_h / 4, tiles_x, c->cfg.bit_depth};
+  hipLaunchKernelGGL(k_deblock, dim3((unsigned)(tiles_x * tiles_y), (unsigned)n_pics), dim3(256), 0, c->stream, A);
   HIPCHK(c, hipGetLastError());
   return HMX_OK;
 }
-
 extern "C" int hmx_deblock_picture(hmx_ctx *c, const hmx_pic *rec, int pic_w, int pic_h, const uint8_t *d_bs_ver, const uint8_t *d_bs_hor,
                                    const int8_t *d_qp, const uint8_t *d_no_filter, int beta_offset_div2, int tc_offset_div2) {
-  if (!c || !rec || !d_bs_ver || !d_bs_hor || !d_qp || pic_w <= 0 || pic_h <= 0 || (pic_w & 7) || (pic_h & 7))
-    return fail(c, HMX_ERR_ARG, "hmx_deblock_picture: null argument or picture size not a multiple of 8");
-  DbkArgs A{to_dev(rec), nullptr, d_qp, d_no_filter, pic_w / 4, pic_h / 4, 0, c->cfg.bit_depth, beta_offset_div2, tc_offset_div2};
-  const unsigned blocks = (unsigned)(((size_t)A.uw * A.uh + 255) / 256);
-  for (int dir = 0; dir < 2; dir++) {
-    A.dir = dir;
-    A.bs = dir ? d_bs_hor : d_bs_ver;
-    hipLaunchKernelGGL(k_deblock, dim3(blocks), dim3(256), 0, c->stream, A);
-  }
-  HIPCHK(c, hipGetLastError());
-  return HMX_OK;
+  const int8_t boff = (int8_t)beta_offset_div2, toff = (int8_t)tc_offset_div2;
+  return hmx_deblock_picture_multi(c, 1, rec, pic_w, pic_h, d_bs_ver, d_bs_hor, d_qp, d_no_filter, &boff, &toff);
 }
 
 // ---- sample adaptive offset, application (TLibCommon/TComSampleAdaptiveOffset.cpp:781-1240) ----
@@ -164,8 +369,11 @@ extern "C" int hmx_deblock_picture(hmx_ctx *c, const hmx_pic *rec, int pic_w, in
 // pass from `in` to `out`, a thread per sample.
 // A thread filters 8 consecutive samples of a row (a CTU is a multiple of 8 wide in both planes, so they share their
 // parameters): three 16-byte loads (the row, the rows above and below) and the six samples just outside, one 16-byte store.
-typedef short s8v __attribute__((ext_vector_type(8)));
-__global__ __launch_bounds__(256) void k_sao(PlanesDev in, PlanesDev out, int pic_w, int pic_h, int B, int ctu, const hmx_sao_lcu *prm, int n_lcu) {
+// pics: [n_pics] inputs, then [n_pics] outputs (in the argument arena); the picture is blockIdx.z
+__global__ __launch_bounds__(256) void k_sao(const PlanesDev *pics, int n_pics, int pic_w, int pic_h, int B, int ctu, const hmx_sao_lcu *prm, int n_lcu) {
+  const int pic = blockIdx.z;
+  const PlanesDev &in = pics[pic], &out = pics[n_pics + pic];
+  prm += (size_t)pic * 3 * n_lcu;
   const int p = blockIdx.y, sh = p ? 1 : 0, w = pic_w >> sh, h = pic_h >> sh, cs = ctu >> sh, w8 = (w + 7) >> 3;
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= w8 * h) return;
@@ -225,17 +433,30 @@ __global__ __launch_bounds__(256) void k_sao(PlanesDev in, PlanesDev out, int pi
     for (int k = 0; k < n; k++) d[k] = (short)v[k];
   }
 }
-extern "C" int hmx_sao_picture(hmx_ctx *c, const hmx_pic *in, const hmx_pic *out, int pic_w, int pic_h, const hmx_sao_lcu *d_params, int n_lcu) {
-  const int ctu = c ? c->cfg.ctu_size : 64;
-  if (!c || !in || !out || !d_params || pic_w <= 0 || pic_h <= 0 || (pic_w & 1) || (pic_h & 1) ||
-      n_lcu != ((pic_w + ctu - 1) / ctu) * ((pic_h + ctu - 1) / ctu))
-    return fail(c, HMX_ERR_ARG, "hmx_sao_picture: bad argument (n_lcu must be the CTU count of the picture)");
-  for (int p = 0; p < 3; p++)
-    if (in->plane[p] == out->plane[p]) return fail(c, HMX_ERR_ARG, "hmx_sao_picture: in and out must be different pictures");
-  hipLaunchKernelGGL(k_sao, dim3((unsigned)(((size_t)((pic_w + 7) / 8) * pic_h + 255) / 256), 3), dim3(256), 0, c->stream, to_dev(in), to_dev(out), pic_w, pic_h,
-                     c->cfg.bit_depth, ctu, d_params, n_lcu);
+extern "C" int hmx_sao_picture_multi(hmx_ctx *c, int n_pics, const hmx_pic *in, const hmx_pic *out, int pic_w, int pic_h,
+                                     const hmx_sao_lcu *d_params, int n_lcu) {
+  if (!c || !in || !out || !d_params) return fail(c, HMX_ERR_ARG, "hmx_sao_picture_multi: null argument");
+  if (n_pics < 1 || n_pics > 65535) return fail(c, HMX_ERR_ARG, "hmx_sao_picture_multi: n_pics must be 1..65535");
+  const int ctu = c->cfg.ctu_size;
+  if (pic_w <= 0 || pic_h <= 0 || (pic_w & 1) || (pic_h & 1) || n_lcu != ((pic_w + ctu - 1) / ctu) * ((pic_h + ctu - 1) / ctu))
+    return fail(c, HMX_ERR_ARG, "hmx_sao_picture_multi: bad size (even, and n_lcu must be the CTU count of the picture)");
+  std::vector<PlanesDev> t(2 * (size_t)n_pics);
+  for (int i = 0; i < n_pics; i++) {
+    for (int p = 0; p < 3; p++) {
+      if (!in[i].plane[p] || !out[i].plane[p]) return fail(c, HMX_ERR_ARG, "hmx_sao_picture_multi: null plane");
+      if (in[i].plane[p] == out[i].plane[p]) return fail(c, HMX_ERR_ARG, "hmx_sao_picture_multi: in and out must be different pictures");
+    }
+    t[i] = to_dev(&in[i]), t[n_pics + i] = to_dev(&out[i]);
+  }
+  const PlanesDev *d = static_cast<const PlanesDev *>(arena_push(c, t.data(), sizeof(PlanesDev) * t.size()));
+  if (!d) return fail(c, HMX_ERR_NOMEM, "argument arena");
+  hipLaunchKernelGGL(k_sao, dim3((unsigned)(((size_t)((pic_w + 7) / 8) * pic_h + 255) / 256), 3, (unsigned)n_pics), dim3(256), 0, c->stream, d, n_pics,
+                     pic_w, pic_h, c->cfg.bit_depth, ctu, d_params, n_lcu);
   HIPCHK(c, hipGetLastError());
   return HMX_OK;
+}
+extern "C" int hmx_sao_picture(hmx_ctx *c, const hmx_pic *in, const hmx_pic *out, int pic_w, int pic_h, const hmx_sao_lcu *d_params, int n_lcu) {
+  return hmx_sao_picture_multi(c, 1, in, out, pic_w, pic_h, d_params, n_lcu);
 }
 
 // ---- SAO statistics of the encoder (TLibEncoder/TEncSampleAdaptiveOffset.cpp:859-1124, calcSaoStatsCuOrg, SAO_SKIP_RIGHT) ----

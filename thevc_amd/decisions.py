@@ -4,8 +4,8 @@ order, with libhmx's own earlier outputs as reference pictures:
 
     inter coding units   hmx_batch_motionCompensation_multi, hmx_batch_invtransformNxN_multi
     intra coding units   hmx_frame_intra_decode (intra pictures) / hmx_frame_intra_decode_onto (inside inter pictures)
-    loop filters         hmx_deblock_strengths (inter pictures; intra pictures have strength 2 on every edge),
-                         hmx_deblock_picture, hmx_sao_picture
+    loop filters         hmx_deblock_strengths_multi (inter pictures; intra pictures have strength 2 on every edge),
+                         hmx_deblock_picture_multi, hmx_sao_picture_multi (a decoder holds one picture at a time: batches of 1)
     reference pictures   hmx_pic_extend_border
 
 A picture is a dict: poc, w, h, B, qp, ctu, slice_type (0 B, 1 P, 2 I), tus (hmx_tu records; flags bit 1 = block of
@@ -254,14 +254,14 @@ def decode_sequence(pics):
                 if len(p["pus"]):
                     units, ev, eh = strength_inputs(p)
                     d_u, d_ev, d_eh = ctx.to_device(units), ctx.to_device(ev), ctx.to_device(eh)
-                    ctx._chk(L.hmx_deblock_strengths(ctx.h, d_u.ptr, d_ev.ptr, d_eh.ptr, w, h, int(p["slice_type"] == 0), d_bv.ptr, d_bh.ptr))
-                ctx._chk(L.hmx_deblock_picture(ctx.h, C.byref(rec_arr[0]), w, h, d_bv.ptr, d_bh.ptr, d_qp.ptr, None, p["dbk"][1], p["dbk"][2]))
+                    ctx.deblock_strengths(1, d_u, d_ev, d_eh, w, h, [int(p["slice_type"] == 0)], d_bv, d_bh)
+                ctx.deblock_pictures([d_rec], w, h, d_bv, d_bh, d_qp, None, [p["dbk"][1]], [p["dbk"][2]])
             d_out = d_rec
             if has_sao(p):
                 d_out = capi.DevPicture(ctx, w, h, m, m).zero()
                 d_prm = ctx.to_device(p["sao"])
-                a, b = d_rec.as_pic(), d_out.as_pic()
-                ctx._chk(L.hmx_sao_picture(ctx.h, C.byref(a), C.byref(b), w, h, d_prm.ptr, p["sao"].shape[1]))
+                assert p["sao"].shape[1] == -(-w // p["ctu"]) * -(-h // p["ctu"])
+                ctx.sao_pictures([d_rec], [d_out], w, h, d_prm)
             ctx._chk(L.hmx_pic_extend_border(ctx.h, C.byref(d_out.as_pic()), w, h, m, m))
             ctx.sync()
             refs[p["poc"]] = d_out
