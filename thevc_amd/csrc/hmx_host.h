@@ -11,6 +11,14 @@
 //   hmx_loop.hip        deblocking, SAO, YUV file formats
 // and hmx_lib.hip includes all of them for a single-translation-unit build (-DHMX_PACK_PROFILE builds read device
 // symbols of several parts).  Build: __graft_entry__.build() compiles the parts in parallel and links libhmx.so.
+//
+// Staging of the scalar drop-ins (host pointers in and out): a drop-in carves the context's device scratch (hmx_ctx::d_scratch, 1 MiB)
+// with Scratch -- take / up from the front, take_tail from the end for buffers that outlive one staging round -- runs one block through
+// the batch kernels (run_one for the list kernels, launch_sized / with_size for the size-templated ones) and brings the block back
+// with down2d.  The budget is enforced: a carve that does not fit, like a failed upload, sticks in Scratch::r, which is tested once
+// before the launch, so an overflow is HMX_ERR_NOMEM and never a launch.  The largest drop-in is the 64x64 initAdiPattern, a 129 x 129
+// window of samples (33 KB) and two 129 x 129 border buffers of Int (133 KB); motion compensation adds a tail of 2 x 64 x 64 shorts.
+// A static_assert beside Scratch holds the worst case of every family against the allocation.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -19,8 +27,10 @@
 #include <chrono>
 #include <cstdio>
 #include <cstring>
+#include <initializer_list>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "hmx_kernels.h"
@@ -351,6 +361,7 @@ struct hmx_intra_plan {
 constexpr int kSlots4 = HMX_SLOTS4; // across pictures
 constexpr int kSlots4Own = 64;       // per-picture level kernel: one lane per block (four lanes: 51.5 vs 54.5 Gpx/s at 1024 pictures)
 int fail(hmx_ctx *c, int code, const char *what, hipError_t e = hipSuccess);
+inline int fail(hmx_ctx *c, int code, const std::string &what) { return fail(c, code, what.c_str()); } // messages that name their caller
 static const int kQuantScales[6] = {26214, 23302, 20560, 18396, 16384, 14564}; // TComRom.cpp:293
 static const int kInvQuantScales[6] = {40, 45, 51, 57, 64, 72};                // TComRom.cpp:298
 #define HIPCHK(ctx, call)                                                   \
@@ -409,17 +420,43 @@ int packed_rdoq_max_blocks(int *nb);
 void launch_packed_rdoq(const PackArgs &A, bool sse, unsigned n_wg, hipStream_t st);
 
 // ---- scalar drop-ins: one block through the batch kernels (host pointers in and out) ----
-struct Scratch { // carve the context's device scratch
+struct Scratch { // carve the context's device scratch (the budget: head of this file); the first failure sticks in r
   hmx_ctx *c;
-  size_t off = 0;
+  size_t off = 0, tail = 0;
+  int r = HMX_OK;
+  void claim(size_t front, size_t back) {
+    if (front + back > c->scratch_bytes) r = r ? r : fail(c, HMX_ERR_NOMEM, "device scratch: the block does not fit");
+    else off = front, tail = back;
+  }
   template <typename T>
   T *take(size_t n) {
-    off = (off + 255) & ~(size_t)255;
-    T *p = reinterpret_cast<T *>(c->d_scratch + off);
-    off += n * sizeof(T);
-    return p;
+    const size_t at = (off + 255) & ~(size_t)255;
+    claim(at + n * sizeof(T), tail);
+    return r ? nullptr : reinterpret_cast<T *>(c->d_scratch + at);
   }
+  template <typename T>
+  T *take_tail(size_t n) { // from the end of the scratch: stays claimed across rewind()
+    claim(off, (tail + n * sizeof(T) + 255) & ~(size_t)255);
+    return r ? nullptr : reinterpret_cast<T *>(c->d_scratch + c->scratch_bytes - tail);
+  }
+  void rewind() { off = 0; } // the next staging round of the same call re-uses the front
+  template <typename T>
+  T *up(const T *src, int w, int h, size_t src_stride_elems); // take w x h and fill it from a host block
+  template <typename T>
+  T *up(const T *src, size_t n);                              // the same for n contiguous elements
 };
+constexpr size_t scratch_need(std::initializer_list<size_t> carves) { // the front after these carves, in bytes
+  size_t off = 0;
+  for (size_t b : carves) off = ((off + 255) & ~(size_t)255) + b;
+  return off;
+}
+constexpr size_t kScratchBytes = 1 << 20, kMcTail = 2 * 64 * 64 * sizeof(short); // what hmx_create allocates; hmx_motionCompensation's tail
+static_assert(scratch_need({129 * 129 * 2, 2 * 129 * 129 * 4}) <= kScratchBytes &&                        // initAdiPattern, 64x64
+                  scratch_need({135 * 128 * 2, 128 * 128 * 2}) <= kScratchBytes &&                          // filters, 128x128
+                  scratch_need({128 * 128 * 2, 128 * 128 * 2, 128 * 128 * 2}) <= kScratchBytes &&           // addAvg, 128x128
+                  scratch_need({32 * 32 * 4, 32 * 32 * 4, 32 * 32 * 4, 32 * 32 * 8, 4}) <= kScratchBytes && // RDOQ with tables, 32x32
+                  scratch_need({71 * 71 * 2, 64 * 71 * 2, 64 * 64 * 2}) + kMcTail <= kScratchBytes,         // motion compensation
+              "the worst-case carve of every scalar drop-in fits the device scratch");
 
 inline int up2d(hmx_ctx *c, void *dst, const void *src, size_t elem, int w, int h, size_t src_stride_elems) {
   HIPCHK(c, hipMemcpy2DAsync(dst, w * elem, src, src_stride_elems * elem, w * elem, h, hipMemcpyHostToDevice, c->stream));
@@ -430,12 +467,23 @@ inline int down2d(hmx_ctx *c, void *dst, size_t dst_stride_elems, const void *sr
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return HMX_OK;
 }
+template <typename T>
+T *Scratch::up(const T *src, int w, int h, size_t src_stride_elems) {
+  T *d = take<T>((size_t)w * h);
+  if (!r) r = up2d(c, d, src, sizeof(T), w, h, src_stride_elems);
+  return d;
+}
+template <typename T>
+T *Scratch::up(const T *src, size_t n) {
+  T *d = take<T>(n);
+  if (!r) r = hmx_upload(c, d, src, n * sizeof(T));
+  return d;
+}
 
-struct One { // a one-block launch: dense N x N buffers at plane origin
-  ListArgs A{};
-  DTu *d_tu;
-};
-inline int one_block(hmx_ctx *c, Scratch &s, One &o, int n, int plane, unsigned mode, unsigned flags, const PicDev &P) {
+// One n x n block through a list kernel: its descriptor goes up behind the staged buffers, and the dense buffers (NULL = unused)
+// sit at the origin of `plane` in the four plane slots of the launch.
+inline int run_one(hmx_ctx *c, Scratch &s, int op, int n, int plane, unsigned mode, unsigned flags, const PicDev &P, short *a, short *b,
+                   int *lev, int *lev2, uint32_t *abs_sum = nullptr) {
   DTu h{};
   h.t.x = h.t.y = 0;
   h.t.log2n = (uint8_t)ilog2i(n);
@@ -443,12 +491,40 @@ inline int one_block(hmx_ctx *c, Scratch &s, One &o, int n, int plane, unsigned 
   h.t.mode = (uint8_t)(mode > 255 ? 255 : mode);
   h.t.flags = (uint8_t)flags;
   h.idx = 0;
-  o.d_tu = s.take<DTu>(1);
-  HIPCHK(c, hipMemcpyAsync(o.d_tu, &h, sizeof(h), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream)); // h is a stack object
-  o.A.tus = o.d_tu;
-  o.A.n = 1;
-  o.A.P = P;
+  ListArgs A{};
+  A.tus = s.up(&h, 1); // synchronises: h is a stack object
+  if (s.r) return s.r;
+  A.n = 1;
+  A.P = P;
+  A.a.p[plane] = a, A.b.p[plane] = b, A.lev.p[plane] = lev, A.lev2.p[plane] = lev2;
+  A.a.s[plane] = a ? n : 0, A.b.s[plane] = b ? n : 0, A.lev.s[plane] = lev ? n : 0, A.lev2.s[plane] = lev2 ? n : 0;
+  A.abs_sum = abs_sum;
+  return launch_op(c, op, ilog2i(n), A);
+}
+
+// f(std::integral_constant<int, N>{}) for the block size N of 4, 8, 16, 32 and (Max = 64) 64 that equals n; false, and no call, for
+// any other n.  The size-templated kernels are launched through it: one argument list per kernel family.
+template <int Max, typename F>
+inline bool with_size(int n, F &&f) {
+  static_assert(Max == 32 || Max == 64, "block sizes end at 32 or at 64");
+  switch (n) {
+  case 4: f(std::integral_constant<int, 4>{}); return true;
+  case 8: f(std::integral_constant<int, 8>{}); return true;
+  case 16: f(std::integral_constant<int, 16>{}); return true;
+  case 32: f(std::integral_constant<int, 32>{}); return true;
+  case 64:
+    if constexpr (Max == 64) {
+      f(std::integral_constant<int, 64>{});
+      return true;
+    }
+  }
+  return false;
+}
+// the launch of one kernel family for an n x n block (a size the caller has checked), and its launch error
+template <int Max, typename F>
+inline int launch_sized(hmx_ctx *c, int n, F &&launch) {
+  if (!with_size<Max>(n, launch)) return fail(c, HMX_ERR_ARG, "unsupported block size");
+  HIPCHK(c, hipGetLastError());
   return HMX_OK;
 }
 inline bool size_ok(int w, int h) { return w == h && (w == 4 || w == 8 || w == 16 || w == 32); }

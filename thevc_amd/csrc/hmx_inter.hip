@@ -60,10 +60,8 @@ static int filter_scalar(hmx_ctx *c, const hmx_pel *src, int ss, int16_t *dst, i
   const int before = frac ? (chroma ? 1 : 3) : 0, after = frac ? (chroma ? 2 : 4) : 0;
   const int ww = w + (vertical ? 0 : before + after), wh = h + (vertical ? before + after : 0);
   Scratch s{c};
-  short *d_in = s.take<short>((size_t)ww * wh), *d_out = s.take<short>((size_t)w * h);
-  const hmx_pel *h0 = src - (vertical ? (ptrdiff_t)before * ss : before);
-  int r = up2d(c, d_in, h0, 2, ww, wh, ss);
-  if (r) return r;
+  short *d_in = s.up(src - (vertical ? (ptrdiff_t)before * ss : before), ww, wh, ss), *d_out = s.take<short>((size_t)w * h);
+  if (s.r) return s.r;
   const short *d_org = d_in + (vertical ? before * ww : before);
   hipLaunchKernelGGL(k_filter, dim3((w * h + 255) / 256), dim3(256), 0, c->stream, d_org, ww, d_out, w, w, h, frac, chroma,
                      vertical, first, last, c->cfg.bit_depth);
@@ -91,16 +89,16 @@ extern "C" int hmx_filterVerChroma(hmx_ctx *c, const hmx_pel *src, int ss, int16
 // xPredInterLumaBlk / xPredInterChromaBlk (TComPrediction.cpp:554-642): the window the filters reach goes up once, the
 // one or two filter stages run on the device (the reference's three cases: horizontal only, vertical only, horizontal
 // into the 14-bit intermediate then vertical), the block comes back.  w, h: the block IN ITS PLANE.
-static int pred_inter_blk(hmx_ctx *c, const hmx_pel *ref, int ref_stride, int mvx, int mvy, int w, int h, hmx_pel *dst, int dst_stride, int bi,
-                          int chroma, short *d_keep = nullptr) {
+// s: the caller's scratch, whose front this block re-uses; d_keep: the block stays on the device, there (a tail buffer of s)
+static int pred_inter_blk(hmx_ctx *c, Scratch &s, const hmx_pel *ref, int ref_stride, int mvx, int mvy, int w, int h, hmx_pel *dst, int dst_stride,
+                          int bi, int chroma, short *d_keep = nullptr) {
   if (!c || !ref || (!dst && !d_keep) || w <= 0 || h <= 0 || w > 64 || h > 64) return fail(c, HMX_ERR_ARG, "xPredInterBlk: bad argument");
   const int fb = chroma ? 3 : 2, fm = (1 << fb) - 1, xf = mvx & fm, yf = mvy & fm;
   const int before = chroma ? 1 : 3, after = chroma ? 2 : 4, ww = w + before + after, wh = h + before + after;
-  Scratch s{c};
-  short *d_in = s.take<short>((size_t)ww * wh), *d_tmp = s.take<short>((size_t)w * wh), *d_out = d_keep ? d_keep : s.take<short>((size_t)w * h);
-  const hmx_pel *h0 = ref + (ptrdiff_t)((mvy >> fb) - before) * ref_stride + ((mvx >> fb) - before);
-  int r = up2d(c, d_in, h0, 2, ww, wh, ref_stride);
-  if (r) return r;
+  s.rewind();
+  short *d_in = s.up(ref + (ptrdiff_t)((mvy >> fb) - before) * ref_stride + ((mvx >> fb) - before), ww, wh, ref_stride);
+  short *d_tmp = s.take<short>((size_t)w * wh), *d_out = d_keep ? d_keep : s.take<short>((size_t)w * h);
+  if (s.r) return s.r;
   const short *d_blk = d_in + before * ww + before; // the block's first sample inside the window
   const int B = c->cfg.bit_depth, last = !bi;
   const dim3 g1((w * h + 255) / 256), g2((w * wh + 255) / 256), blk(256);
@@ -117,12 +115,14 @@ static int pred_inter_blk(hmx_ctx *c, const hmx_pel *ref, int ref_stride, int mv
 }
 extern "C" int hmx_xPredInterLumaBlk(hmx_ctx *c, const hmx_pel *ref, int ref_stride, int mv_hor, int mv_ver, int w, int h, hmx_pel *dst,
                                      int dst_stride, int bi) {
-  return pred_inter_blk(c, ref, ref_stride, mv_hor, mv_ver, w, h, dst, dst_stride, bi, 0);
+  Scratch s{c};
+  return pred_inter_blk(c, s, ref, ref_stride, mv_hor, mv_ver, w, h, dst, dst_stride, bi, 0);
 }
 extern "C" int hmx_xPredInterChromaBlk(hmx_ctx *c, const hmx_pel *ref, int ref_stride, int mv_hor, int mv_ver, int w, int h, hmx_pel *dst,
                                        int dst_stride, int bi) {
   if ((w & 1) || (h & 1)) return fail(c, HMX_ERR_ARG, "hmx_xPredInterChromaBlk: odd luma size");
-  return pred_inter_blk(c, ref, ref_stride, mv_hor, mv_ver, w >> 1, h >> 1, dst, dst_stride, bi, 1);
+  Scratch s{c};
+  return pred_inter_blk(c, s, ref, ref_stride, mv_hor, mv_ver, w >> 1, h >> 1, dst, dst_stride, bi, 1);
 }
 __global__ void k_addavg(const short *a, const short *b, short *d, int n, int B);
 // motionCompensation of ONE prediction unit (TComPrediction.cpp:410-552): xPredInterUni per used list (isLast = uni-prediction),
@@ -135,9 +135,10 @@ extern "C" int hmx_motionCompensation(hmx_ctx *c, const hmx_pic *ref0, const int
   const bool bi = ref0 && ref1;
   for (int p = 0; p < 3; p++) {
     const int ch = p ? 1 : 0, pw = w >> ch, ph = h >> ch;
+    Scratch s{c};
     short *d_pred[2] = {nullptr, nullptr};
     if (bi) { // both 14-bit intermediates stay on the device (the tail of the scratch area), addAvg there
-      d_pred[0] = reinterpret_cast<short *>(c->d_scratch + c->scratch_bytes) - 2 * 64 * 64;
+      d_pred[0] = s.take_tail<short>(2 * 64 * 64);
       d_pred[1] = d_pred[0] + 64 * 64;
     }
     for (int l = 0; l < 2; l++) {
@@ -145,12 +146,13 @@ extern "C" int hmx_motionCompensation(hmx_ctx *c, const hmx_pic *ref0, const int
       const int *mv = l ? mv1 : mv0;
       if (!rp) continue;
       const hmx_pel *r0 = rp->plane[p] + (ptrdiff_t)(y >> ch) * rp->stride[p] + (x >> ch);
-      int r = pred_inter_blk(c, r0, rp->stride[p], mv[0], mv[1], pw, ph, dst->plane[p], dst->stride[p], bi, ch, bi ? d_pred[l] : nullptr);
+      int r = pred_inter_blk(c, s, r0, rp->stride[p], mv[0], mv[1], pw, ph, dst->plane[p], dst->stride[p], bi, ch, bi ? d_pred[l] : nullptr);
       if (r) return r;
     }
     if (bi) {
-      Scratch s{c};
+      s.rewind();
       short *d_out = s.take<short>((size_t)pw * ph);
+      if (s.r) return s.r;
       hipLaunchKernelGGL(k_addavg, dim3((pw * ph + 255) / 256), dim3(256), 0, c->stream, d_pred[0], d_pred[1], d_out, pw * ph, c->cfg.bit_depth);
       HIPCHK(c, hipGetLastError());
       int r = down2d(c, dst->plane[p], dst->stride[p], d_out, 2, pw, ph);
@@ -293,10 +295,8 @@ extern "C" int hmx_addAvg(hmx_ctx *c, const hmx_pel *s0, int s0s, const hmx_pel 
                           int h) {
   if (!c || !s0 || !s1 || !dst || w <= 0 || h <= 0 || w > 128 || h > 128) return fail(c, HMX_ERR_ARG, "hmx_addAvg: bad argument");
   Scratch s{c};
-  short *da = s.take<short>((size_t)w * h), *db = s.take<short>((size_t)w * h), *dd = s.take<short>((size_t)w * h);
-  int r = up2d(c, da, s0, 2, w, h, s0s);
-  if (!r) r = up2d(c, db, s1, 2, w, h, s1s);
-  if (r) return r;
+  short *da = s.up(s0, w, h, s0s), *db = s.up(s1, w, h, s1s), *dd = s.take<short>((size_t)w * h);
+  if (s.r) return s.r;
   hipLaunchKernelGGL(k_addavg, dim3((w * h + 255) / 256), dim3(256), 0, c->stream, da, db, dd, w * h, c->cfg.bit_depth);
   HIPCHK(c, hipGetLastError());
   return down2d(c, dst, ds, dd, 2, w, h);

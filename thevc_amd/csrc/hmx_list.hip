@@ -276,22 +276,16 @@ __global__ __launch_bounds__(256) void k_inter4(ListArgs A) {
 template <int OP>
 static int launch_list(hmx_ctx *c, int log2n, const ListArgs &A) {
   if (A.n <= 0) return HMX_OK;
-  dim3 blk(256);
   const unsigned ny = A.pics ? (unsigned)A.n_pics : 1u;
-  switch (log2n) {
-  case 2: hipLaunchKernelGGL((k_list<4, OP>), dim3((A.n + Slots<4>::v - 1) / Slots<4>::v, ny), blk, 0, c->stream, A); break;
-  case 3: hipLaunchKernelGGL((k_list<8, OP>), dim3((A.n + Slots<8>::v - 1) / Slots<8>::v, ny), blk, 0, c->stream, A); break;
-  case 4: hipLaunchKernelGGL((k_list<16, OP>), dim3((A.n + Slots<16>::v - 1) / Slots<16>::v, ny), blk, 0, c->stream, A); break;
-  case 5: hipLaunchKernelGGL((k_list<32, OP>), dim3((A.n + Slots<32>::v - 1) / Slots<32>::v, ny), blk, 0, c->stream, A); break;
-  case 6: // 64 x 64: the luma prediction unit of a 64 x 64 coding unit (TEncSearch.cpp:2509-2540); no transform of that size exists
-    if constexpr (OP == OP_PRED || OP == OP_PRED_LAYOUT) {
-      hipLaunchKernelGGL((k_list<64, OP>), dim3((unsigned)A.n, ny), blk, 0, c->stream, A);
-      break;
-    } else {
-      return fail(c, HMX_ERR_ARG, "64x64 blocks: intra prediction only (the largest transform is 32x32)");
-    }
-  default: return fail(c, HMX_ERR_ARG, "unsupported block size");
-  }
+  int r = HMX_OK;
+  const bool known = with_size<64>(log2n < 2 || log2n > 6 ? 0 : 1 << log2n, [&](auto n) {
+    constexpr int N = n;
+    // 64 x 64: the luma prediction unit of a 64 x 64 coding unit (TEncSearch.cpp:2509-2540); no transform of that size exists
+    if constexpr (N == 64 && OP != OP_PRED && OP != OP_PRED_LAYOUT) r = fail(c, HMX_ERR_ARG, "64x64 blocks: intra prediction only (the largest transform is 32x32)");
+    else hipLaunchKernelGGL((k_list<N, OP>), dim3((A.n + Slots<N>::v - 1) / Slots<N>::v, ny), dim3(256), 0, c->stream, A);
+  });
+  if (!known) return fail(c, HMX_ERR_ARG, "unsupported block size");
+  if (r) return r;
   HIPCHK(c, hipGetLastError());
   return HMX_OK;
 }
@@ -469,37 +463,8 @@ extern "C" int hmx_batch_invtransformNxN_multi(hmx_ctx *c, const hmx_tu_list *l,
   return run_list_multi(c, OP_INVTRANSFORM_NXN, l, n_pics, pred, out, lev, nullptr, pp, pred != nullptr);
 }
 
-extern "C" int hmx_batch_predIntra(hmx_ctx *c, const hmx_tu_list *l, const hmx_pic *rec, const hmx_pic *pred,
-                                   const hmx_pic_param *pp, const uint8_t *d_modes, int n_modes,
-                                   const size_t mode_plane_elems[3]) {
-  if (!c || !l || !rec || !pred || !pp) return fail(c, HMX_ERR_ARG, "hmx_batch_predIntra: null argument");
-  ListArgs A{};
-  A.a = to_dev(rec);
-  A.b = to_dev(pred);
-  A.P = make_picdev(c, pp);
-  A.modes = d_modes;
-  A.n_modes = d_modes ? n_modes : 0;
-  for (int i = 0; i < 3; i++) A.mode_elems[i] = mode_plane_elems ? mode_plane_elems[i] : 0;
-  return run_list(c, OP_PRED, l, A);
-}
-
-extern "C" int hmx_batch_predIntra_cost(hmx_ctx *c, const hmx_tu_list *l, const hmx_pic *rec, const hmx_pic *org,
-                                        const hmx_pic_param *pp, const uint8_t *d_modes, int n_modes, uint32_t *d_satd) {
-  if (!c || !l || !rec || !org || !pp || !d_satd || (d_modes && (n_modes <= 0 || n_modes > 35)))
-    return fail(c, HMX_ERR_ARG, "hmx_batch_predIntra_cost: bad argument");
-  ListArgs A{};
-  A.a = to_dev(rec);
-  A.org = to_dev(org);
-  A.cost = d_satd;
-  A.P = make_picdev(c, pp);
-  A.modes = d_modes;
-  A.n_modes = d_modes ? n_modes : 0;
-  return run_list(c, OP_PRED, l, A);
-}
-
-
-// The two prediction calls with a slice / tile / CIP layout: the maps travel in the argument arena, the kernels AND the layout
-// onto the geometric availability (OP_PRED_LAYOUT; the calls without a layout keep their instantiations)
+// The prediction calls, with or without a slice / tile / CIP layout: with one the maps travel in the argument arena and the kernels AND
+// the layout onto the geometric availability (OP_PRED_LAYOUT; the calls without a layout keep their instantiations)
 static int pred_layout(hmx_ctx *c, const hmx_tu_list *l, ListArgs &A, const hmx_pic_param *pp, const hmx_avail_layout *layout) {
   if (!layout) return run_list(c, OP_PRED, l, A);
   LayoutHost H;
@@ -507,11 +472,9 @@ static int pred_layout(hmx_ctx *c, const hmx_tu_list *l, ListArgs &A, const hmx_
   if (int r = layout_to_device(c, H, A.lay)) return r;
   return run_list(c, OP_PRED_LAYOUT, l, A);
 }
-
-extern "C" int hmx_batch_predIntra_layout(hmx_ctx *c, const hmx_tu_list *l, const hmx_pic *rec, const hmx_pic *pred,
-                                          const hmx_pic_param *pp, const hmx_avail_layout *layout, const uint8_t *d_modes, int n_modes,
-                                          const size_t mode_plane_elems[3]) {
-  if (!c || !l || !rec || !pred || !pp) return fail(c, HMX_ERR_ARG, "hmx_batch_predIntra_layout: null argument");
+static int pred_intra(hmx_ctx *c, const char *fn, const hmx_tu_list *l, const hmx_pic *rec, const hmx_pic *pred, const hmx_pic_param *pp,
+                      const hmx_avail_layout *layout, const uint8_t *d_modes, int n_modes, const size_t mode_plane_elems[3]) {
+  if (!c || !l || !rec || !pred || !pp) return fail(c, HMX_ERR_ARG, std::string(fn) + ": null argument");
   ListArgs A{};
   A.a = to_dev(rec);
   A.b = to_dev(pred);
@@ -521,12 +484,10 @@ extern "C" int hmx_batch_predIntra_layout(hmx_ctx *c, const hmx_tu_list *l, cons
   for (int i = 0; i < 3; i++) A.mode_elems[i] = mode_plane_elems ? mode_plane_elems[i] : 0;
   return pred_layout(c, l, A, pp, layout);
 }
-
-extern "C" int hmx_batch_predIntra_cost_layout(hmx_ctx *c, const hmx_tu_list *l, const hmx_pic *rec, const hmx_pic *org,
-                                               const hmx_pic_param *pp, const hmx_avail_layout *layout, const uint8_t *d_modes, int n_modes,
-                                               uint32_t *d_satd) {
+static int pred_intra_cost(hmx_ctx *c, const char *fn, const hmx_tu_list *l, const hmx_pic *rec, const hmx_pic *org, const hmx_pic_param *pp,
+                           const hmx_avail_layout *layout, const uint8_t *d_modes, int n_modes, uint32_t *d_satd) {
   if (!c || !l || !rec || !org || !pp || !d_satd || (d_modes && (n_modes <= 0 || n_modes > 35)))
-    return fail(c, HMX_ERR_ARG, "hmx_batch_predIntra_cost_layout: bad argument");
+    return fail(c, HMX_ERR_ARG, std::string(fn) + ": bad argument");
   ListArgs A{};
   A.a = to_dev(rec);
   A.org = to_dev(org);
@@ -535,4 +496,24 @@ extern "C" int hmx_batch_predIntra_cost_layout(hmx_ctx *c, const hmx_tu_list *l,
   A.modes = d_modes;
   A.n_modes = d_modes ? n_modes : 0;
   return pred_layout(c, l, A, pp, layout);
+}
+
+extern "C" int hmx_batch_predIntra(hmx_ctx *c, const hmx_tu_list *l, const hmx_pic *rec, const hmx_pic *pred,
+                                   const hmx_pic_param *pp, const uint8_t *d_modes, int n_modes,
+                                   const size_t mode_plane_elems[3]) {
+  return pred_intra(c, "hmx_batch_predIntra", l, rec, pred, pp, nullptr, d_modes, n_modes, mode_plane_elems);
+}
+extern "C" int hmx_batch_predIntra_cost(hmx_ctx *c, const hmx_tu_list *l, const hmx_pic *rec, const hmx_pic *org,
+                                        const hmx_pic_param *pp, const uint8_t *d_modes, int n_modes, uint32_t *d_satd) {
+  return pred_intra_cost(c, "hmx_batch_predIntra_cost", l, rec, org, pp, nullptr, d_modes, n_modes, d_satd);
+}
+extern "C" int hmx_batch_predIntra_layout(hmx_ctx *c, const hmx_tu_list *l, const hmx_pic *rec, const hmx_pic *pred,
+                                          const hmx_pic_param *pp, const hmx_avail_layout *layout, const uint8_t *d_modes, int n_modes,
+                                          const size_t mode_plane_elems[3]) {
+  return pred_intra(c, "hmx_batch_predIntra_layout", l, rec, pred, pp, layout, d_modes, n_modes, mode_plane_elems);
+}
+extern "C" int hmx_batch_predIntra_cost_layout(hmx_ctx *c, const hmx_tu_list *l, const hmx_pic *rec, const hmx_pic *org,
+                                               const hmx_pic_param *pp, const hmx_avail_layout *layout, const uint8_t *d_modes, int n_modes,
+                                               uint32_t *d_satd) {
+  return pred_intra_cost(c, "hmx_batch_predIntra_cost_layout", l, rec, org, pp, layout, d_modes, n_modes, d_satd);
 }

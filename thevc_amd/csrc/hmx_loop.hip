@@ -315,14 +315,41 @@ __global__ __launch_bounds__(256) void k_dbk_strengths(const hmx_dbk_unit *units
   bs_ver[base + u] = (unsigned char)bv;
   bs_hor[base + u] = (unsigned char)bh;
 }
+// What the _multi entry points share, with the messages of `fn`, the entry point: the range of n_pics (grid.y or grid.z), the
+// picture size (dims_ok, what it has to be in size_rule) ...
+static int multi_shape(hmx_ctx *c, const char *fn, int n_pics, bool dims_ok, const char *size_rule) {
+  if (n_pics < 1 || n_pics > 65535) return fail(c, HMX_ERR_ARG, std::string(fn) + ": n_pics must be 1..65535");
+  if (!dims_ok) return fail(c, HMX_ERR_ARG, std::string(fn) + ": " + size_rule);
+  return HMX_OK;
+}
+// ... and the pictures: no null plane in a[] (nor in b[], when there is one; with `distinct` a rule that a[i] and b[i] share none), then
+// the table in the argument arena, make(a[i], i) for every picture and behind them make(b[i], i)
+template <typename T, typename Make>
+static int multi_pics(hmx_ctx *c, const char *fn, int n_pics, bool dims_ok, const char *size_rule, const hmx_pic *a, const hmx_pic *b,
+                      const char *distinct, Make make, const T **d) {
+  if (int r = multi_shape(c, fn, n_pics, dims_ok, size_rule)) return r;
+  std::vector<T> t((b ? 2 : 1) * (size_t)n_pics);
+  for (int i = 0; i < n_pics; i++) {
+    for (int p = 0; p < 3; p++) {
+      if (!a[i].plane[p] || (b && !b[i].plane[p])) return fail(c, HMX_ERR_ARG, std::string(fn) + ": null plane");
+      if (b && distinct && a[i].plane[p] == b[i].plane[p]) return fail(c, HMX_ERR_ARG, std::string(fn) + ": " + distinct);
+    }
+    t[i] = make(a[i], i);
+    if (b) t[n_pics + i] = make(b[i], i);
+  }
+  *d = static_cast<const T *>(arena_push(c, t.data(), sizeof(T) * t.size()));
+  return *d ? HMX_OK : fail(c, HMX_ERR_NOMEM, "argument arena");
+}
+static bool multiple_of(int pic_w, int pic_h, int m) { return pic_w > 0 && pic_h > 0 && pic_w % m == 0 && pic_h % m == 0; }
+static const char *const kMultipleOf8 = "picture size must be a positive multiple of 8";
+static PlanesDev planes_of(const hmx_pic &p, int) { return to_dev(&p); }
+
 extern "C" int hmx_deblock_strengths_multi(hmx_ctx *c, int n_pics, const hmx_dbk_unit *d_units, const uint8_t *d_edge_ver,
                                            const uint8_t *d_edge_hor, int pic_w, int pic_h, const uint8_t *is_b_slice, uint8_t *d_bs_ver,
                                            uint8_t *d_bs_hor) {
   if (!c || !d_units || !d_edge_ver || !d_edge_hor || !is_b_slice || !d_bs_ver || !d_bs_hor)
     return fail(c, HMX_ERR_ARG, "hmx_deblock_strengths_multi: null argument");
-  if (n_pics < 1 || n_pics > 65535) return fail(c, HMX_ERR_ARG, "hmx_deblock_strengths_multi: n_pics must be 1..65535");
-  if (pic_w <= 0 || pic_h <= 0 || (pic_w & 7) || (pic_h & 7))
-    return fail(c, HMX_ERR_ARG, "hmx_deblock_strengths_multi: picture size must be a positive multiple of 8");
+  if (int r = multi_shape(c, "hmx_deblock_strengths_multi", n_pics, multiple_of(pic_w, pic_h, 8), kMultipleOf8)) return r;
   const unsigned char *d_b = static_cast<const unsigned char *>(arena_push(c, is_b_slice, (size_t)n_pics));
   if (!d_b) return fail(c, HMX_ERR_NOMEM, "argument arena");
   const int uw = pic_w / 4, uh = pic_h / 4;
@@ -341,17 +368,9 @@ extern "C" int hmx_deblock_picture_multi(hmx_ctx *c, int n_pics, const hmx_pic *
                                          const uint8_t *d_bs_hor, const int8_t *d_qp, const uint8_t *d_no_filter, const int8_t *beta_offset_div2,
                                          const int8_t *tc_offset_div2) {
   if (!c || !rec || !d_bs_ver || !d_bs_hor || !d_qp) return fail(c, HMX_ERR_ARG, "hmx_deblock_picture_multi: null argument");
-  if (n_pics < 1 || n_pics > 65535) return fail(c, HMX_ERR_ARG, "hmx_deblock_picture_multi: n_pics must be 1..65535");
-  if (pic_w <= 0 || pic_h <= 0 || (pic_w & 7) || (pic_h & 7))
-    return fail(c, HMX_ERR_ARG, "hmx_deblock_picture_multi: picture size must be a positive multiple of 8");
-  std::vector<DbkPic> t((size_t)n_pics);
-  for (int i = 0; i < n_pics; i++) {
-    for (int p = 0; p < 3; p++)
-      if (!rec[i].plane[p]) return fail(c, HMX_ERR_ARG, "hmx_deblock_picture_multi: null plane");
-    t[i] = DbkPic{to_dev(&rec[i]), beta_offset_div2 ? beta_offset_div2[i] : 0, tc_offset_div2 ? tc_offset_div2[i] : 0};
-  }
-  const DbkPic *d = static_cast<const DbkPic *>(arena_push(c, t.data(), sizeof(DbkPic) * t.size()));
-  if (!d) return fail(c, HMX_ERR_NOMEM, "argument arena");
+  const DbkPic *d;
+  const auto entry = [&](const hmx_pic &p, int i) { return DbkPic{to_dev(&p), beta_offset_div2 ? beta_offset_div2[i] : 0, tc_offset_div2 ? tc_offset_div2[i] : 0}; };
+  if (int r = multi_pics(c, "hmx_deblock_picture_multi", n_pics, multiple_of(pic_w, pic_h, 8), kMultipleOf8, rec, nullptr, nullptr, entry, &d)) return r;
   const int tiles_x = (pic_w + 4 + 63) / 64, tiles_y = (pic_h + 4 + 63) / 64; // windows start at 64 k - 4
   DbkArgs A{d, d_bs_ver, d_bs_hor, d_qp, d_no_filter, pic_w, pic_h, pic_w / 4, pic_h / 4, tiles_x, c->cfg.bit_depth};
   hipLaunchKernelGGL(k_deblock, dim3((unsigned)(tiles_x * tiles_y), (unsigned)n_pics), dim3(256), 0, c->stream, A);
@@ -436,20 +455,12 @@ __global__ __launch_bounds__(256) void k_sao(const PlanesDev *pics, int n_pics, 
 extern "C" int hmx_sao_picture_multi(hmx_ctx *c, int n_pics, const hmx_pic *in, const hmx_pic *out, int pic_w, int pic_h,
                                      const hmx_sao_lcu *d_params, int n_lcu) {
   if (!c || !in || !out || !d_params) return fail(c, HMX_ERR_ARG, "hmx_sao_picture_multi: null argument");
-  if (n_pics < 1 || n_pics > 65535) return fail(c, HMX_ERR_ARG, "hmx_sao_picture_multi: n_pics must be 1..65535");
   const int ctu = c->cfg.ctu_size;
-  if (pic_w <= 0 || pic_h <= 0 || (pic_w & 1) || (pic_h & 1) || n_lcu != ((pic_w + ctu - 1) / ctu) * ((pic_h + ctu - 1) / ctu))
-    return fail(c, HMX_ERR_ARG, "hmx_sao_picture_multi: bad size (even, and n_lcu must be the CTU count of the picture)");
-  std::vector<PlanesDev> t(2 * (size_t)n_pics);
-  for (int i = 0; i < n_pics; i++) {
-    for (int p = 0; p < 3; p++) {
-      if (!in[i].plane[p] || !out[i].plane[p]) return fail(c, HMX_ERR_ARG, "hmx_sao_picture_multi: null plane");
-      if (in[i].plane[p] == out[i].plane[p]) return fail(c, HMX_ERR_ARG, "hmx_sao_picture_multi: in and out must be different pictures");
-    }
-    t[i] = to_dev(&in[i]), t[n_pics + i] = to_dev(&out[i]);
-  }
-  const PlanesDev *d = static_cast<const PlanesDev *>(arena_push(c, t.data(), sizeof(PlanesDev) * t.size()));
-  if (!d) return fail(c, HMX_ERR_NOMEM, "argument arena");
+  const bool dims_ok = multiple_of(pic_w, pic_h, 2) && n_lcu == ((pic_w + ctu - 1) / ctu) * ((pic_h + ctu - 1) / ctu);
+  const PlanesDev *d;
+  if (int r = multi_pics(c, "hmx_sao_picture_multi", n_pics, dims_ok, "bad size (even, and n_lcu must be the CTU count of the picture)", in, out,
+                         "in and out must be different pictures", planes_of, &d))
+    return r;
   hipLaunchKernelGGL(k_sao, dim3((unsigned)(((size_t)((pic_w + 7) / 8) * pic_h + 255) / 256), 3, (unsigned)n_pics), dim3(256), 0, c->stream, d, n_pics,
                      pic_w, pic_h, c->cfg.bit_depth, ctu, d_params, n_lcu);
   HIPCHK(c, hipGetLastError());
@@ -615,17 +626,8 @@ __global__ __launch_bounds__(kSaoStatThreads) void k_sao_stats(SaoStatArgs A) {
 extern "C" int hmx_sao_stats_multi(hmx_ctx *c, int n_pics, const hmx_pic *org, const hmx_pic *rec, int pic_w, int pic_h, int lcu_based,
                                    hmx_sao_stat *d_out) {
   if (!c || !org || !rec || !d_out) return fail(c, HMX_ERR_ARG, "hmx_sao_stats_multi: null argument");
-  if (n_pics < 1 || n_pics > 65535) return fail(c, HMX_ERR_ARG, "hmx_sao_stats_multi: n_pics must be 1..65535");
-  if (pic_w <= 0 || pic_h <= 0 || (pic_w & 7) || (pic_h & 7))
-    return fail(c, HMX_ERR_ARG, "hmx_sao_stats_multi: picture size must be a positive multiple of 8");
-  std::vector<PlanesDev> t(2 * (size_t)n_pics);
-  for (int i = 0; i < n_pics; i++) {
-    for (int p = 0; p < 3; p++)
-      if (!org[i].plane[p] || !rec[i].plane[p]) return fail(c, HMX_ERR_ARG, "hmx_sao_stats_multi: null plane");
-    t[i] = to_dev(&org[i]), t[n_pics + i] = to_dev(&rec[i]);
-  }
-  const PlanesDev *d = static_cast<const PlanesDev *>(arena_push(c, t.data(), sizeof(PlanesDev) * t.size()));
-  if (!d) return fail(c, HMX_ERR_NOMEM, "argument arena");
+  const PlanesDev *d;
+  if (int r = multi_pics(c, "hmx_sao_stats_multi", n_pics, multiple_of(pic_w, pic_h, 8), kMultipleOf8, org, rec, nullptr, planes_of, &d)) return r;
   const int ctu = c->cfg.ctu_size, cw = (pic_w + ctu - 1) / ctu, n_lcu = cw * ((pic_h + ctu - 1) / ctu);
   SaoStatArgs A{d, d_out, n_pics, pic_w, pic_h, ctu, c->cfg.bit_depth, lcu_based ? 1 : 0, n_lcu, cw};
   hipLaunchKernelGGL(k_sao_stats, dim3((unsigned)n_lcu, 3, (unsigned)n_pics), dim3(kSaoStatThreads), 0, c->stream, A);

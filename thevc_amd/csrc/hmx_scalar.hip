@@ -9,100 +9,58 @@
 // uiMode -> flags: the list kernels derive DST/scan from (plane, INTER flag, mode)
 static unsigned mode_flags(unsigned mode) { return mode == HMX_REG_DCT ? HMX_TU_INTER : 0; }
 
+// xT / xTransformSkip and xIT / xITransformSkip: the same block through OP_XT / OP_XIT, the skip as a flag of the block
+static int fwd_one(hmx_ctx *c, const char *fn, unsigned mode, unsigned flags, const hmx_pel *resi, unsigned stride, int32_t *coef, int w, int h) {
+  if (!c || !resi || !coef || !size_ok(w, h)) return fail(c, HMX_ERR_ARG, std::string(fn) + ": unsupported size or null");
+  Scratch s{c};
+  short *d_in = s.up(resi, w, h, stride);
+  int *d_out = s.take<int>(w * h);
+  if (int r = run_one(c, s, OP_XT, w, 0, mode, flags, scalar_picdev(c, nullptr, -1, HMX_I_SLICE, 0), d_in, nullptr, d_out, nullptr)) return r;
+  return down2d(c, coef, w, d_out, 4, w, h);
+}
+static int inv_one(hmx_ctx *c, const char *fn, unsigned mode, unsigned flags, const int32_t *coef, hmx_pel *resi, unsigned stride, int w, int h) {
+  if (!c || !resi || !coef || !size_ok(w, h)) return fail(c, HMX_ERR_ARG, std::string(fn) + ": unsupported size or null");
+  Scratch s{c};
+  int *d_in = s.up(coef, w, h, w);
+  short *d_out = s.take<short>(w * h);
+  if (int r = run_one(c, s, OP_XIT, w, 0, mode, flags, scalar_picdev(c, nullptr, -1, HMX_I_SLICE, 0), nullptr, d_out, d_in, nullptr)) return r;
+  return down2d(c, resi, stride, d_out, 2, w, h);
+}
 extern "C" int hmx_xT(hmx_ctx *c, unsigned mode, const hmx_pel *resi, unsigned stride, int32_t *coef, int w, int h) {
-  if (!c || !resi || !coef || !size_ok(w, h)) return fail(c, HMX_ERR_ARG, "hmx_xT: unsupported size or null");
-  Scratch s{c};
-  short *d_in = s.take<short>(w * h);
-  int *d_out = s.take<int>(w * h);
-  int r = up2d(c, d_in, resi, 2, w, h, stride);
-  if (r) return r;
-  One o;
-  if ((r = one_block(c, s, o, w, 0, mode, mode_flags(mode), scalar_picdev(c, nullptr, -1, HMX_I_SLICE, 0)))) return r;
-  o.A.a.p[0] = d_in;
-  o.A.a.s[0] = w;
-  o.A.lev.p[0] = d_out;
-  o.A.lev.s[0] = w;
-  if ((r = launch_op(c, OP_XT, ilog2i(w), o.A))) return r;
-  return down2d(c, coef, w, d_out, 4, w, h);
+  return fwd_one(c, "hmx_xT", mode, mode_flags(mode), resi, stride, coef, w, h);
 }
-
 extern "C" int hmx_xIT(hmx_ctx *c, unsigned mode, const int32_t *coef, hmx_pel *resi, unsigned stride, int w, int h) {
-  if (!c || !resi || !coef || !size_ok(w, h)) return fail(c, HMX_ERR_ARG, "hmx_xIT: unsupported size or null");
-  Scratch s{c};
-  int *d_in = s.take<int>(w * h);
-  short *d_out = s.take<short>(w * h);
-  int r = up2d(c, d_in, coef, 4, w, h, w);
-  if (r) return r;
-  One o;
-  if ((r = one_block(c, s, o, w, 0, mode, mode_flags(mode), scalar_picdev(c, nullptr, -1, HMX_I_SLICE, 0)))) return r;
-  o.A.lev.p[0] = d_in;
-  o.A.lev.s[0] = w;
-  o.A.b.p[0] = d_out;
-  o.A.b.s[0] = w;
-  if ((r = launch_op(c, OP_XIT, ilog2i(w), o.A))) return r;
-  return down2d(c, resi, stride, d_out, 2, w, h);
+  return inv_one(c, "hmx_xIT", mode, mode_flags(mode), coef, resi, stride, w, h);
 }
-
 extern "C" int hmx_xTransformSkip(hmx_ctx *c, const hmx_pel *resi, unsigned stride, int32_t *coef, int w, int h) {
-  if (!c || !resi || !coef || !size_ok(w, h)) return fail(c, HMX_ERR_ARG, "hmx_xTransformSkip: unsupported size or null");
-  Scratch s{c};
-  short *d_in = s.take<short>(w * h);
-  int *d_out = s.take<int>(w * h);
-  int r = up2d(c, d_in, resi, 2, w, h, stride);
-  if (r) return r;
-  One o;
-  if ((r = one_block(c, s, o, w, 0, 0, HMX_TU_TRANSFORM_SKIP, scalar_picdev(c, nullptr, -1, HMX_I_SLICE, 0)))) return r;
-  o.A.a.p[0] = d_in;
-  o.A.a.s[0] = w;
-  o.A.lev.p[0] = d_out;
-  o.A.lev.s[0] = w;
-  if ((r = launch_op(c, OP_XT, ilog2i(w), o.A))) return r;
-  return down2d(c, coef, w, d_out, 4, w, h);
+  return fwd_one(c, "hmx_xTransformSkip", 0, HMX_TU_TRANSFORM_SKIP, resi, stride, coef, w, h);
 }
-
 extern "C" int hmx_xITransformSkip(hmx_ctx *c, const int32_t *coef, hmx_pel *resi, unsigned stride, int w, int h) {
-  if (!c || !resi || !coef || !size_ok(w, h)) return fail(c, HMX_ERR_ARG, "hmx_xITransformSkip: unsupported size or null");
-  Scratch s{c};
-  int *d_in = s.take<int>(w * h);
-  short *d_out = s.take<short>(w * h);
-  int r = up2d(c, d_in, coef, 4, w, h, w);
-  if (r) return r;
-  One o;
-  if ((r = one_block(c, s, o, w, 0, 0, HMX_TU_TRANSFORM_SKIP, scalar_picdev(c, nullptr, -1, HMX_I_SLICE, 0)))) return r;
-  o.A.lev.p[0] = d_in;
-  o.A.lev.s[0] = w;
-  o.A.b.p[0] = d_out;
-  o.A.b.s[0] = w;
-  if ((r = launch_op(c, OP_XIT, ilog2i(w), o.A))) return r;
-  return down2d(c, resi, stride, d_out, 2, w, h);
+  return inv_one(c, "hmx_xITransformSkip", 0, HMX_TU_TRANSFORM_SKIP, coef, resi, stride, w, h);
 }
 
 static int plane_of(int text_type) { return text_type == HMX_TEXT_LUMA ? 0 : (text_type == HMX_TEXT_CHROMA_V ? 2 : 1); }
+
+// the tail of the quantisers: the block's sum and its levels come back; uiAcSum / uiAbsSum accumulate by reference
+// (TComTrQuant.cpp:1256, 2187), transformNxN starts its own from zero
+static int sum_and_levels_back(hmx_ctx *c, const uint32_t *d_sum, uint32_t *sum, bool accumulate, const int *d_out, hmx_coeff *dst, int w, int h) {
+  uint32_t hs = 0;
+  HIPCHK(c, hipMemcpyAsync(&hs, d_sum, 4, hipMemcpyDeviceToHost, c->stream));
+  const int r = down2d(c, dst, w, d_out, 4, w, h);
+  *sum = accumulate ? *sum + hs : hs;
+  return r;
+}
 
 extern "C" int hmx_xQuant(hmx_ctx *c, const int32_t *src, hmx_coeff *dst, int w, int h, uint32_t *ac_sum, int text_type,
                           const hmx_quant_param *qp) {
   if (!c || !src || !dst || !qp || !ac_sum || !size_ok(w, h)) return fail(c, HMX_ERR_ARG, "hmx_xQuant: unsupported size or null");
   Scratch s{c};
-  int *d_in = s.take<int>(w * h), *d_out = s.take<int>(w * h);
+  int *d_in = s.up(src, w, h, w), *d_out = s.take<int>(w * h);
   uint32_t *d_sum = s.take<uint32_t>(1);
-  int r = up2d(c, d_in, src, 4, w, h, w);
-  if (r) return r;
-  One o;
-  unsigned flags = qp->is_intra ? 0 : HMX_TU_INTER;
-  if ((r = one_block(c, s, o, w, plane_of(text_type), qp->dir_mode, flags,
-                     scalar_picdev(c, &qp->qp, qp->per_base, qp->slice_type, qp->sign_hide))))
+  if (int r = run_one(c, s, OP_XQUANT, w, plane_of(text_type), qp->dir_mode, qp->is_intra ? 0 : HMX_TU_INTER,
+                      scalar_picdev(c, &qp->qp, qp->per_base, qp->slice_type, qp->sign_hide), nullptr, nullptr, d_in, d_out, d_sum))
     return r;
-  o.A.lev.p[plane_of(text_type)] = d_in;
-  o.A.lev.s[plane_of(text_type)] = w;
-  o.A.lev2.p[plane_of(text_type)] = d_out;
-  o.A.lev2.s[plane_of(text_type)] = w;
-  o.A.abs_sum = d_sum;
-  if ((r = launch_op(c, OP_XQUANT, ilog2i(w), o.A))) return r;
-  uint32_t hs = 0;
-  HIPCHK(c, hipMemcpyAsync(&hs, d_sum, 4, hipMemcpyDeviceToHost, c->stream));
-  r = down2d(c, dst, w, d_out, 4, w, h);
-  *ac_sum += hs; // uiAcSum is accumulated by reference (:1256)
-  return r;
+  return sum_and_levels_back(c, d_sum, ac_sum, true, d_out, dst, w, h);
 }
 
 static int rdoq_scan_index(int n, bool luma, bool intra, int mode);
@@ -128,26 +86,17 @@ extern "C" int hmx_xQuant_scaled(hmx_ctx *c, const int32_t *src, hmx_coeff *dst,
                                  const hmx_quant_param *qp, const int32_t *quant_coef) {
   if (!c || !src || !dst || !qp || !ac_sum || !quant_coef || !size_ok(w, h)) return fail(c, HMX_ERR_ARG, "hmx_xQuant_scaled: unsupported size or null");
   Scratch s{c};
-  int *d_in = s.take<int>(w * h), *d_tab = s.take<int>(w * h), *d_out = s.take<int>(w * h);
+  int *d_in = s.up(src, w, h, w), *d_tab = s.up(quant_coef, w, h, w), *d_out = s.take<int>(w * h);
   uint32_t *d_sum = s.take<uint32_t>(1);
-  int r = up2d(c, d_in, src, 4, w, h, w);
-  if (!r) r = up2d(c, d_tab, quant_coef, 4, w, h, w);
-  if (r) return r;
+  if (s.r) return s.r;
   const PicDev P = scalar_picdev(c, &qp->qp, qp->per_base, qp->slice_type, qp->sign_hide);
   const bool luma = text_type == HMX_TEXT_LUMA;
   const int scan = rdoq_scan_index(w, luma, qp->is_intra != 0, qp->dir_mode); // getCoefScanIdx: 0 diagonal, 1 horizontal, 2 vertical
-  switch (w) {
-  case 4: hipLaunchKernelGGL(k_quant_scaled<4>, dim3(1), dim3(64), 0, c->stream, d_in, d_tab, d_out, d_sum, P, (int)luma, scan); break;
-  case 8: hipLaunchKernelGGL(k_quant_scaled<8>, dim3(1), dim3(64), 0, c->stream, d_in, d_tab, d_out, d_sum, P, (int)luma, scan); break;
-  case 16: hipLaunchKernelGGL(k_quant_scaled<16>, dim3(1), dim3(64), 0, c->stream, d_in, d_tab, d_out, d_sum, P, (int)luma, scan); break;
-  default: hipLaunchKernelGGL(k_quant_scaled<32>, dim3(1), dim3(64), 0, c->stream, d_in, d_tab, d_out, d_sum, P, (int)luma, scan); break;
-  }
-  HIPCHK(c, hipGetLastError());
-  uint32_t hs = 0;
-  HIPCHK(c, hipMemcpyAsync(&hs, d_sum, 4, hipMemcpyDeviceToHost, c->stream));
-  r = down2d(c, dst, w, d_out, 4, w, h);
-  *ac_sum += hs;
-  return r;
+  if (int r = launch_sized<32>(c, w, [&](auto n) {
+        hipLaunchKernelGGL(k_quant_scaled<n>, dim3(1), dim3(64), 0, c->stream, d_in, d_tab, d_out, d_sum, P, (int)luma, scan);
+      }))
+    return r;
+  return sum_and_levels_back(c, d_sum, ac_sum, true, d_out, dst, w, h);
 }
 
 // ---- the pArlDes output of the quantiser (ADAPTIVE_QP_SELECTION) ----
@@ -173,10 +122,8 @@ extern "C" int hmx_arlCoeff(hmx_ctx *c, const int32_t *src, int32_t *arl, int w,
   if (!c || !src || !arl || !qp || !size_ok(w, h)) return fail(c, HMX_ERR_ARG, "hmx_arlCoeff: unsupported size or null");
   if (qp->qp.rem < 0 || qp->qp.rem > 5 || qp->qp.per < 0) return fail(c, HMX_ERR_ARG, "hmx_arlCoeff: bad QP");
   Scratch s{c};
-  int *d_in = s.take<int>(w * h), *d_out = s.take<int>(w * h), *d_tab = quant_coef ? s.take<int>(w * h) : nullptr;
-  int r = up2d(c, d_in, src, 4, w, h, w);
-  if (!r && quant_coef) r = up2d(c, d_tab, quant_coef, 4, w, h, w);
-  if (r) return r;
+  int *d_in = s.up(src, w, h, w), *d_out = s.take<int>(w * h), *d_tab = quant_coef ? s.up(quant_coef, w, h, w) : nullptr;
+  if (s.r) return s.r;
   const int per = rdoq_form ? qp->qp.per : (qp->per_base >= 0 ? qp->per_base : qp->qp.per);
   const int qbits = 14 + per + (15 - c->cfg.bit_depth - ilog2i(w));
   hipLaunchKernelGGL(k_arl, dim3((unsigned)((w * h + 255) / 256)), dim3(256), 0, c->stream, d_in, d_tab, d_out, w * h, kQuantScales[qp->qp.rem], qbits, rdoq_form != 0);
@@ -332,9 +279,11 @@ static int rdoq_issue(hmx_ctx *c, RdoqArgs A) {
           used[4 - lg] = true;
           HIPCHK(c, hipStreamWaitEvent(st, c->ev_fork, 0));
         }
-        if (lg == 5) hipLaunchKernelGGL((k_rdoq_tiles<32, 1>), dim3((unsigned)A.n), dim3(64), 0, st, A, RC, P);
-        else if (lg == 4) hipLaunchKernelGGL((k_rdoq_tiles<16, 4>), dim3((unsigned)((A.n + 3) / 4)), dim3(64), 0, st, A, RC, P);
-        else hipLaunchKernelGGL((k_rdoq_tiles<8, 8>), dim3((unsigned)((A.n + 7) / 8)), dim3(64), 0, st, A, RC, P);
+        // a wave per 1 / 4 / 8 blocks.  A table and not with_size: the block size does not fix the second template argument, and the
+        // kernels keep their place in the code object by being named largest first
+        static void (*const tiles[3])(RdoqArgs, RdoqChain, PicDev) = {k_rdoq_tiles<32, 1>, k_rdoq_tiles<16, 4>, k_rdoq_tiles<8, 8>};
+        const int per = lg == 5 ? 1 : 64 >> lg;
+        hipLaunchKernelGGL(tiles[5 - lg], dim3((unsigned)((A.n + per - 1) / per)), dim3(64), 0, st, A, RC, P);
         HIPCHK(c, hipGetLastError());
       }
       o = e;
@@ -362,64 +311,40 @@ static int rdoq_issue(hmx_ctx *c, RdoqArgs A) {
   return HMX_OK;
 }
 
+// xRateDistOptQuant of one block, flat or under a scaling list: getQuantCoeff and getErrScaleCoeff per position (TComTrQuant.cpp
+// :1759-1762, 1882-1883).  With the two tables the block goes through the sequential lane kernel (k_rdoq), which reads them where it
+// reads the flat values otherwise.
+static int rdoq_one(hmx_ctx *c, const int32_t *src, hmx_coeff *dst, int w, int h, uint32_t *abs_sum, int text_type, const hmx_rdoq_param *rp,
+                    const hmx_est_bits *est, const int32_t *quant_coef, const double *err_scale) {
+  Scratch s{c};
+  int *d_in = s.up(src, w, h, w), *d_out = s.take<int>(w * h);
+  RdoqArgs A{};
+  if (quant_coef) A.qtab = s.up(quant_coef, w, h, w), A.estab = s.up(err_scale, w, h, w);
+  uint32_t *d_sum = s.take<uint32_t>(1);
+  if (s.r) return s.r;
+  const hmx_qp qps[2] = {rp->qp, rp->qp};
+  const double lam[2] = {rp->lambda, rp->lambda};
+  rdoq_constants(A, c->cfg.bit_depth, qps, lam);
+  A.sign_hide = rp->sign_hide;
+  const bool luma = text_type == HMX_TEXT_LUMA;
+  std::vector<RdoqBlock> b(1);
+  b[0] = RdoqBlock{d_in, d_out, w, w, d_sum, (unsigned char)ilog2i(w), (unsigned char)luma,
+                   (unsigned char)rdoq_scan_index(w, luma, rp->is_intra != 0, rp->dir_mode), (unsigned char)(rp->root_cbf != 0),
+                   (unsigned char)rp->cbf_ctx, 0, 0};
+  if (int r = rdoq_launch(c, A, b, est, 1)) return r;
+  return sum_and_levels_back(c, d_sum, abs_sum, true, d_out, dst, w, h);
+}
 extern "C" int hmx_xRateDistOptQuant(hmx_ctx *c, const int32_t *src, hmx_coeff *dst, int w, int h, uint32_t *abs_sum, int text_type,
                                      const hmx_rdoq_param *rp, const hmx_est_bits *est) {
   if (!c || !src || !dst || !rp || !est || !abs_sum || !size_ok(w, h) || !(rp->lambda > 0))
     return fail(c, HMX_ERR_ARG, "hmx_xRateDistOptQuant: unsupported size, null or non-positive lambda");
-  Scratch s{c};
-  int *d_in = s.take<int>(w * h), *d_out = s.take<int>(w * h);
-  uint32_t *d_sum = s.take<uint32_t>(1);
-  int r = up2d(c, d_in, src, 4, w, h, w);
-  if (r) return r;
-  RdoqArgs A{};
-  const hmx_qp qps[2] = {rp->qp, rp->qp};
-  const double lam[2] = {rp->lambda, rp->lambda};
-  rdoq_constants(A, c->cfg.bit_depth, qps, lam);
-  A.sign_hide = rp->sign_hide;
-  const bool luma = text_type == HMX_TEXT_LUMA;
-  std::vector<RdoqBlock> b(1);
-  b[0] = RdoqBlock{d_in, d_out, w, w, d_sum, (unsigned char)ilog2i(w), (unsigned char)luma,
-                   (unsigned char)rdoq_scan_index(w, luma, rp->is_intra != 0, rp->dir_mode), (unsigned char)(rp->root_cbf != 0),
-                   (unsigned char)rp->cbf_ctx, 0, 0};
-  if ((r = rdoq_launch(c, A, b, est, 1))) return r;
-  uint32_t hs = 0;
-  HIPCHK(c, hipMemcpyAsync(&hs, d_sum, 4, hipMemcpyDeviceToHost, c->stream));
-  r = down2d(c, dst, w, d_out, 4, w, h);
-  *abs_sum += hs; // uiAbsSum accumulates (:2187)
-  return r;
+  return rdoq_one(c, src, dst, w, h, abs_sum, text_type, rp, est, nullptr, nullptr);
 }
-
-// xRateDistOptQuant under a scaling list: getQuantCoeff and getErrScaleCoeff per position (TComTrQuant.cpp:1759-1762, 1882-1883).  The
-// block goes through the sequential lane kernel (k_rdoq), which reads the two tables where it reads the flat values otherwise.
 extern "C" int hmx_xRateDistOptQuant_scaled(hmx_ctx *c, const int32_t *src, hmx_coeff *dst, int w, int h, uint32_t *abs_sum, int text_type,
                                             const hmx_rdoq_param *rp, const hmx_est_bits *est, const int32_t *quant_coef, const double *err_scale) {
   if (!c || !src || !dst || !rp || !est || !abs_sum || !quant_coef || !err_scale || !size_ok(w, h) || !(rp->lambda > 0))
     return fail(c, HMX_ERR_ARG, "hmx_xRateDistOptQuant_scaled: unsupported size, null or non-positive lambda");
-  Scratch s{c};
-  int *d_in = s.take<int>(w * h), *d_out = s.take<int>(w * h), *d_q = s.take<int>(w * h);
-  double *d_e = s.take<double>(w * h);
-  uint32_t *d_sum = s.take<uint32_t>(1);
-  int r = up2d(c, d_in, src, 4, w, h, w);
-  if (!r) r = up2d(c, d_q, quant_coef, 4, w, h, w);
-  if (!r) r = up2d(c, d_e, err_scale, 8, w, h, w);
-  if (r) return r;
-  RdoqArgs A{};
-  const hmx_qp qps[2] = {rp->qp, rp->qp};
-  const double lam[2] = {rp->lambda, rp->lambda};
-  rdoq_constants(A, c->cfg.bit_depth, qps, lam);
-  A.sign_hide = rp->sign_hide;
-  A.qtab = d_q, A.estab = d_e;
-  const bool luma = text_type == HMX_TEXT_LUMA;
-  std::vector<RdoqBlock> b(1);
-  b[0] = RdoqBlock{d_in, d_out, w, w, d_sum, (unsigned char)ilog2i(w), (unsigned char)luma,
-                   (unsigned char)rdoq_scan_index(w, luma, rp->is_intra != 0, rp->dir_mode), (unsigned char)(rp->root_cbf != 0),
-                   (unsigned char)rp->cbf_ctx, 0, 0};
-  if ((r = rdoq_launch(c, A, b, est, 1))) return r;
-  uint32_t hs = 0;
-  HIPCHK(c, hipMemcpyAsync(&hs, d_sum, 4, hipMemcpyDeviceToHost, c->stream));
-  r = down2d(c, dst, w, d_out, 4, w, h);
-  *abs_sum += hs;
-  return r;
+  return rdoq_one(c, src, dst, w, h, abs_sum, text_type, rp, est, quant_coef, err_scale);
 }
 
 extern "C" int hmx_batch_xRateDistOptQuant(hmx_ctx *c, const hmx_tu *tus, const hmx_rdoq_side *side, int n, const hmx_levels *coef,
@@ -469,16 +394,8 @@ extern "C" int hmx_batch_xRateDistOptQuant(hmx_ctx *c, const hmx_tu *tus, const 
 extern "C" int hmx_xDeQuant(hmx_ctx *c, const hmx_coeff *src, int32_t *dst, int w, int h, const hmx_qp *qp) {
   if (!c || !src || !dst || !qp || !size_ok(w, h)) return fail(c, HMX_ERR_ARG, "hmx_xDeQuant: unsupported size or null");
   Scratch s{c};
-  int *d_in = s.take<int>(w * h), *d_out = s.take<int>(w * h);
-  int r = up2d(c, d_in, src, 4, w, h, w);
-  if (r) return r;
-  One o;
-  if ((r = one_block(c, s, o, w, 0, 0, 0, scalar_picdev(c, qp, -1, HMX_I_SLICE, 0)))) return r;
-  o.A.lev.p[0] = d_in;
-  o.A.lev.s[0] = w;
-  o.A.lev2.p[0] = d_out;
-  o.A.lev2.s[0] = w;
-  if ((r = launch_op(c, OP_XDEQUANT, ilog2i(w), o.A))) return r;
+  int *d_in = s.up(src, w, h, w), *d_out = s.take<int>(w * h);
+  if (int r = run_one(c, s, OP_XDEQUANT, w, 0, 0, 0, scalar_picdev(c, qp, -1, HMX_I_SLICE, 0), nullptr, nullptr, d_in, d_out)) return r;
   return down2d(c, dst, w, d_out, 4, w, h);
 }
 
@@ -501,10 +418,8 @@ extern "C" int hmx_xDeQuant_scaled(hmx_ctx *c, const hmx_coeff *src, int32_t *ds
   if (!c || !src || !dst || !qp || !dequant_coef || !size_ok(w, h)) return fail(c, HMX_ERR_ARG, "hmx_xDeQuant_scaled: unsupported size or null");
   if (qp->per < 0) return fail(c, HMX_ERR_ARG, "hmx_xDeQuant_scaled: bad QP");
   Scratch s{c};
-  int *d_in = s.take<int>(w * h), *d_tab = s.take<int>(w * h), *d_out = s.take<int>(w * h);
-  int r = up2d(c, d_in, src, 4, w, h, w);
-  if (!r) r = up2d(c, d_tab, dequant_coef, 4, w, h, w);
-  if (r) return r;
+  int *d_in = s.up(src, w, h, w), *d_tab = s.up(dequant_coef, w, h, w), *d_out = s.take<int>(w * h);
+  if (s.r) return s.r;
   const int lg = ilog2i(w), shift = 20 - 14 - (15 - c->cfg.bit_depth - lg) + 4;
   const int bit_range = std::min(15, 12 + lg + c->cfg.bit_depth - qp->per);
   hipLaunchKernelGGL(k_dequant_scaled, dim3((unsigned)((w * h + 255) / 256)), dim3(256), 0, c->stream, d_in, d_tab, d_out, w * h, shift, qp->per, 1 << bit_range);
@@ -526,25 +441,14 @@ extern "C" int hmx_transformNxN(hmx_ctx *c, const hmx_pel *resi, unsigned stride
     return HMX_OK;
   }
   Scratch s{c};
-  const int pl = plane_of(text_type);
-  short *d_in = s.take<short>(w * h);
+  short *d_in = s.up(resi, (int)w, (int)h, stride);
   int *d_out = s.take<int>(w * h);
   uint32_t *d_sum = s.take<uint32_t>(1);
-  int r = up2d(c, d_in, resi, 2, (int)w, (int)h, stride);
-  if (r) return r;
-  One o;
-  unsigned flags = (qp->is_intra ? 0 : HMX_TU_INTER) | (use_ts ? HMX_TU_TRANSFORM_SKIP : 0);
-  if ((r = one_block(c, s, o, (int)w, pl, qp->dir_mode, flags,
-                     scalar_picdev(c, &qp->qp, qp->per_base, qp->slice_type, qp->sign_hide))))
+  const unsigned flags = (qp->is_intra ? 0 : HMX_TU_INTER) | (use_ts ? HMX_TU_TRANSFORM_SKIP : 0);
+  if (int r = run_one(c, s, OP_TRANSFORM_NXN, (int)w, plane_of(text_type), qp->dir_mode, flags,
+                      scalar_picdev(c, &qp->qp, qp->per_base, qp->slice_type, qp->sign_hide), d_in, nullptr, d_out, nullptr, d_sum))
     return r;
-  o.A.a.p[pl] = d_in;
-  o.A.a.s[pl] = (int)w;
-  o.A.lev.p[pl] = d_out;
-  o.A.lev.s[pl] = (int)w;
-  o.A.abs_sum = d_sum;
-  if ((r = launch_op(c, OP_TRANSFORM_NXN, ilog2i((int)w), o.A))) return r;
-  HIPCHK(c, hipMemcpyAsync(abs_sum, d_sum, 4, hipMemcpyDeviceToHost, c->stream));
-  return down2d(c, level, w, d_out, 4, (int)w, (int)h);
+  return sum_and_levels_back(c, d_sum, abs_sum, false, d_out, level, (int)w, (int)h);
 }
 
 extern "C" int hmx_invtransformNxN(hmx_ctx *c, int bypass, int text_type, unsigned mode, hmx_pel *resi, unsigned stride,
@@ -557,23 +461,14 @@ extern "C" int hmx_invtransformNxN(hmx_ctx *c, int bypass, int text_type, unsign
     return HMX_OK;
   }
   Scratch s{c};
-  const int pl = plane_of(text_type);
-  int *d_in = s.take<int>(w * h);
+  int *d_in = s.up(level, (int)w, (int)h, w);
   short *d_out = s.take<short>(w * h);
-  int r = up2d(c, d_in, level, 4, (int)w, (int)h, w);
-  if (r) return r;
-  One o;
   // the caller passes uiMode explicitly here (REG_DCT for chroma / inter), like the reference
-  unsigned flags = (mode == HMX_REG_DCT ? HMX_TU_INTER : 0) | (use_ts ? HMX_TU_TRANSFORM_SKIP : 0);
+  const unsigned flags = (mode == HMX_REG_DCT ? HMX_TU_INTER : 0) | (use_ts ? HMX_TU_TRANSFORM_SKIP : 0);
   // DST is selected by (luma plane && !INTER); a chroma call with a luma mode must still be DCT
-  if ((r = one_block(c, s, o, (int)w, mode == HMX_REG_DCT ? pl : 0, mode, flags, scalar_picdev(c, qp, -1, HMX_I_SLICE, 0))))
+  const int kp = mode == HMX_REG_DCT ? plane_of(text_type) : 0;
+  if (int r = run_one(c, s, OP_INVTRANSFORM_NXN, (int)w, kp, mode, flags, scalar_picdev(c, qp, -1, HMX_I_SLICE, 0), nullptr, d_out, d_in, nullptr))
     return r;
-  const int kp = mode == HMX_REG_DCT ? pl : 0;
-  o.A.lev.p[kp] = d_in;
-  o.A.lev.s[kp] = (int)w;
-  o.A.b.p[kp] = d_out;
-  o.A.b.s[kp] = (int)w;
-  if ((r = launch_op(c, OP_INVTRANSFORM_NXN, ilog2i((int)w), o.A))) return r;
   return down2d(c, resi, stride, d_out, 2, (int)w, (int)h);
 }
 
@@ -663,10 +558,9 @@ static int init_adi(hmx_ctx *c, const hmx_pel *rec, int stride, int x, int y, in
   const int x0 = std::max(x - 1, 0), y0 = std::max(y - 1, 0), x1 = std::min(x + 2 * n, pw), y1 = std::min(y + 2 * n, ph);
   const int ww = x1 - x0, wh = y1 - y0, W = 2 * n + 1;
   Scratch s{c};
-  short *d_win = s.take<short>((size_t)ww * wh);
+  short *d_win = s.up(rec + (size_t)y0 * stride + x0, ww, wh, stride);
   int *d_adi = s.take<int>((size_t)2 * W * W);
-  int r = up2d(c, d_win, rec + (size_t)y0 * stride + x0, 2, ww, wh, stride);
-  if (r) return r;
+  if (s.r) return s.r;
   hmx_pic_param pp{pic_w, pic_h, 0, 0, HMX_I_SLICE, 0};
   PicDev P = make_picdev(c, &pp);
   const int bx = x - x0, by = y - y0;
@@ -675,17 +569,13 @@ static int init_adi(hmx_ctx *c, const hmx_pel *rec, int stride, int x, int y, in
   if (layout) {
     LayoutHost H;
     if (const char *e = layout_pack(layout, pic_w, pic_h, c->cfg.ctu_size, H)) return fail(c, HMX_ERR_ARG, e);
-    if ((r = layout_to_device(c, H, lay))) return r;
+    if (int r = layout_to_device(c, H, lay)) return r;
     use_layout = 1;
   }
-  switch (n) {
-  case 4: hipLaunchKernelGGL(k_adi<4>, dim3(1), dim3(64), 0, c->stream, d_win, ww, bx, by, x, y, is_chroma, P, d_adi, lay, use_layout); break;
-  case 8: hipLaunchKernelGGL(k_adi<8>, dim3(1), dim3(64), 0, c->stream, d_win, ww, bx, by, x, y, is_chroma, P, d_adi, lay, use_layout); break;
-  case 16: hipLaunchKernelGGL(k_adi<16>, dim3(1), dim3(64), 0, c->stream, d_win, ww, bx, by, x, y, is_chroma, P, d_adi, lay, use_layout); break;
-  case 32: hipLaunchKernelGGL(k_adi<32>, dim3(1), dim3(64), 0, c->stream, d_win, ww, bx, by, x, y, is_chroma, P, d_adi, lay, use_layout); break;
-  default: hipLaunchKernelGGL(k_adi<64>, dim3(1), dim3(64), 0, c->stream, d_win, ww, bx, by, x, y, is_chroma, P, d_adi, lay, use_layout); break;
-  }
-  HIPCHK(c, hipGetLastError());
+  if (int r = launch_sized<64>(c, n, [&](auto N) {
+        hipLaunchKernelGGL(k_adi<N>, dim3(1), dim3(64), 0, c->stream, d_win, ww, bx, by, x, y, is_chroma, P, d_adi, lay, use_layout);
+      }))
+    return r;
   return hmx_download(c, adi, d_adi, sizeof(int) * 2 * W * W);
 }
 extern "C" int hmx_initAdiPattern(hmx_ctx *c, const hmx_pel *rec, int stride, int x, int y, int n, int is_chroma,
@@ -754,20 +644,15 @@ extern "C" int hmx_fillReferenceSamples(hmx_ctx *c, const hmx_pel *rec, int stri
     }
   }
   Scratch s{c};
-  short *d_win = s.take<short>((size_t)W * W);
+  short *d_win = s.up(win.data(), (size_t)W * W);
   int *d_adi = s.take<int>((size_t)W * W);
-  int r = hmx_upload(c, d_win, win.data(), sizeof(short) * W * W);
-  if (r) return r;
-  switch (n) {
-  case 4: hipLaunchKernelGGL(k_fill_ref<4>, dim3(1), dim3(64), 0, c->stream, d_win, avail, ulog2, c->cfg.bit_depth, d_adi); break;
-  case 8: hipLaunchKernelGGL(k_fill_ref<8>, dim3(1), dim3(64), 0, c->stream, d_win, avail, ulog2, c->cfg.bit_depth, d_adi); break;
-  case 16: hipLaunchKernelGGL(k_fill_ref<16>, dim3(1), dim3(64), 0, c->stream, d_win, avail, ulog2, c->cfg.bit_depth, d_adi); break;
-  case 32: hipLaunchKernelGGL(k_fill_ref<32>, dim3(1), dim3(64), 0, c->stream, d_win, avail, ulog2, c->cfg.bit_depth, d_adi); break;
-  default: hipLaunchKernelGGL(k_fill_ref<64>, dim3(1), dim3(64), 0, c->stream, d_win, avail, ulog2, c->cfg.bit_depth, d_adi); break;
-  }
-  HIPCHK(c, hipGetLastError());
+  if (s.r) return s.r;
+  if (int r = launch_sized<64>(c, n, [&](auto N) {
+        hipLaunchKernelGGL(k_fill_ref<N>, dim3(1), dim3(64), 0, c->stream, d_win, avail, ulog2, c->cfg.bit_depth, d_adi);
+      }))
+    return r;
   std::vector<int32_t> out((size_t)W * W);
-  if ((r = hmx_download(c, out.data(), d_adi, sizeof(int32_t) * W * W))) return r;
+  if (int r = hmx_download(c, out.data(), d_adi, sizeof(int32_t) * W * W)) return r;
   for (int k = 0; k < W; k++) adi[k] = out[k], adi[(size_t)k * W] = out[(size_t)k * W];
   return HMX_OK;
 }
@@ -779,18 +664,14 @@ static int pred_from_adi(hmx_ctx *c, const int32_t *adi, unsigned mode, hmx_pel 
   Scratch s{c};
   int *d_adi = s.take<int>((size_t)2 * W * W);
   short *d_pred = s.take<short>((size_t)w * h);
-  int r = hmx_upload(c, d_adi, adi, sizeof(int) * (luma ? 2 : 1) * W * W);
-  if (r) return r;
+  if (s.r) return s.r;
+  if (int r = hmx_upload(c, d_adi, adi, sizeof(int) * (luma ? 2 : 1) * W * W)) return r;
   hmx_pic_param pp{1 << 14, 1 << 14, 0, 0, HMX_I_SLICE, 0};
   PicDev P = make_picdev(c, &pp);
-  switch (w) {
-  case 4: hipLaunchKernelGGL(k_pred_adi<4>, dim3(1), dim3(64), 0, c->stream, d_adi, (int)mode, luma, P, d_pred, raw_line); break;
-  case 8: hipLaunchKernelGGL(k_pred_adi<8>, dim3(1), dim3(64), 0, c->stream, d_adi, (int)mode, luma, P, d_pred, raw_line); break;
-  case 16: hipLaunchKernelGGL(k_pred_adi<16>, dim3(1), dim3(64), 0, c->stream, d_adi, (int)mode, luma, P, d_pred, raw_line); break;
-  case 32: hipLaunchKernelGGL(k_pred_adi<32>, dim3(1), dim3(64), 0, c->stream, d_adi, (int)mode, luma, P, d_pred, raw_line); break;
-  default: hipLaunchKernelGGL(k_pred_adi<64>, dim3(1), dim3(64), 0, c->stream, d_adi, (int)mode, luma, P, d_pred, raw_line); break;
-  }
-  HIPCHK(c, hipGetLastError());
+  if (int r = launch_sized<64>(c, w, [&](auto N) {
+        hipLaunchKernelGGL(k_pred_adi<N>, dim3(1), dim3(64), 0, c->stream, d_adi, (int)mode, luma, P, d_pred, raw_line);
+      }))
+    return r;
   return down2d(c, pred, stride, d_pred, 2, w, h);
 }
 extern "C" int hmx_predIntraLumaAng(hmx_ctx *c, const int32_t *adi, unsigned mode, hmx_pel *pred, unsigned stride, int w,
@@ -805,17 +686,22 @@ extern "C" int hmx_predIntraChromaAng(hmx_ctx *c, const int32_t *adi, unsigned m
 // The protected building blocks of the two wrappers above, named by the north star.  `adi` is ONE
 // (2w+1) x (2w+1) border buffer (the caller chose raw or smoothed, as the reference's callers do by
 // passing a pointer); the reference's pSrc is its cell (1,1).
+// predIntraGetPredValDC on one (2w+1) x (2w+1) border buffer: the value into a device word (d_out) or into w x h samples (d_fill)
+static int dc_from_adi(hmx_ctx *c, Scratch &s, const int32_t *adi, int w, int above, int left, int *d_out, short *d_fill) {
+  const int W = 2 * w + 1;
+  const int *d_adi = s.up(adi, (size_t)W * W);
+  if (s.r) return s.r;
+  hipLaunchKernelGGL(k_dcval, dim3(1), dim3(1), 0, c->stream, d_adi, w, above, left, d_out, d_fill);
+  HIPCHK(c, hipGetLastError());
+  return HMX_OK;
+}
 extern "C" int hmx_predIntraGetPredValDC(hmx_ctx *c, const int32_t *adi, int w, int h, int above, int left, hmx_pel *dc) {
   if (!c || !adi || !dc || !size_ok_intra(w, h)) return fail(c, HMX_ERR_ARG, "hmx_predIntraGetPredValDC: unsupported size or null");
-  const int W = 2 * w + 1;
   Scratch s{c};
-  int *d_adi = s.take<int>((size_t)W * W), *d_out = s.take<int>(1);
-  int r = hmx_upload(c, d_adi, adi, sizeof(int) * W * W);
-  if (r) return r;
-  hipLaunchKernelGGL(k_dcval, dim3(1), dim3(1), 0, c->stream, d_adi, w, above, left, d_out, (short *)nullptr);
-  HIPCHK(c, hipGetLastError());
+  int *d_out = s.take<int>(1);
+  if (int r = dc_from_adi(c, s, adi, w, above, left, d_out, nullptr)) return r;
   int v = 0;
-  r = hmx_download(c, &v, d_out, sizeof(int));
+  const int r = hmx_download(c, &v, d_out, sizeof(int));
   *dc = (hmx_pel)v;
   return r;
 }
@@ -827,14 +713,9 @@ extern "C" int hmx_xPredIntraAng(hmx_ctx *c, const int32_t *adi, hmx_pel *pred, 
   if (!c || !adi || !pred || !size_ok_intra(w, h) || dir_mode < 1 || dir_mode > 34)
     return fail(c, HMX_ERR_ARG, "hmx_xPredIntraAng: unsupported size, null or mode outside 1..34");
   if (dir_mode == 1) { // DC from the sides flagged available; no edge smoothing here (xDCPredFiltering is the wrapper's)
-    const int W = 2 * w + 1;
     Scratch s{c};
-    int *d_adi = s.take<int>((size_t)W * W);
     short *d_pred = s.take<short>((size_t)w * h);
-    int r = hmx_upload(c, d_adi, adi, sizeof(int) * W * W);
-    if (r) return r;
-    hipLaunchKernelGGL(k_dcval, dim3(1), dim3(1), 0, c->stream, d_adi, w, above, left, (int *)nullptr, d_pred);
-    HIPCHK(c, hipGetLastError());
+    if (int r = dc_from_adi(c, s, adi, w, above, left, nullptr, d_pred)) return r;
     return down2d(c, pred, stride, d_pred, 2, w, h);
   }
   if (!filter) return pred_from_adi(c, adi, dir_mode, pred, stride, w, h, 0);
@@ -893,17 +774,15 @@ static int dist_scalar(hmx_ctx *c, const hmx_pel *org, int so, const hmx_pel *cu
   if (!c || !org || !cur || !out || w <= 0 || h <= 0 || w > 64 || h > 64 || (hads && ((w | h) & 3)))
     return fail(c, HMX_ERR_ARG, "distortion: unsupported size or null");
   Scratch s{c};
-  short *d_o = s.take<short>((size_t)w * h), *d_c = s.take<short>((size_t)w * h);
+  short *d_o = s.up(org, w, h, so), *d_c = s.up(cur, w, h, sc);
   unsigned *d_out = s.take<unsigned>(1);
-  int r = up2d(c, d_o, org, 2, w, h, so);
-  if (!r) r = up2d(c, d_c, cur, 2, w, h, sc);
-  if (r) return r;
+  if (s.r) return s.r;
   HIPCHK(c, hipMemsetAsync(d_out, 0, 4, c->stream));
   const int items = hads ? (w / 4) * (h / 4) : h;
   hipLaunchKernelGGL(k_dist, dim3((items + 63) / 64), dim3(64), 0, c->stream, d_o, w, d_c, w, w, h, c->cfg.bit_depth - 8, hads, d_out);
   HIPCHK(c, hipGetLastError());
   unsigned v = 0;
-  r = hmx_download(c, &v, d_out, 4);
+  const int r = hmx_download(c, &v, d_out, 4);
   *out = hads ? v >> (c->cfg.bit_depth - 8) : v; // calcHAD returns uiSum >> g_uiBitIncrement (:449)
   return r;
 }
