@@ -517,6 +517,32 @@ int hmx_frame_intra_decode_resident(hmx_ctx *ctx, const hmx_intra_plan *const *p
 int hmx_motionCompensation(hmx_ctx *ctx, const hmx_pic *ref0, const int *mv0, const hmx_pic *ref1, const int *mv1, int x, int y,
                            int w, int h, const hmx_pic *dst);
 
+/* Explicit weighted prediction (TLibCommon/TComWeightPrediction.{h,cpp}), the branch TComPrediction::motionCompensation takes when
+ * the PPS has getUseWP() (P slices) or getWPBiPred() (B slices), TComPrediction.cpp:421-432 and :516-535.  Every used list is
+ * predicted into the 14-bit intermediate (xPredInterUni(..., bi = true)); a unit with one list ends in weightUnidir, a unit with both
+ * lists in weightBidir (TComWeightPrediction.h:82-89) -- always, the identical-motion shortcut being off under WPBiPred (:394).
+ * Supported ranges (anything else is HMX_ERR_ARG, checked on the host before a launch): weight -128..255, offset -128..127,
+ * log2_denom 0..7. */
+typedef struct {            /* wpScalingParam of one (list, reference) (TLibCommon/TComSlice.h), per component Y, Cb, Cr */
+  int16_t weight[3];        /* iWeight */
+  int16_t offset[3];        /* iOffset, 8-bit units */
+  uint8_t log2_denom[3];    /* uiLog2WeightDenom */
+  uint8_t reserved;
+} hmx_wp;
+/* TComWeightPrediction::addWeightUni (TComWeightPrediction.cpp:161-237) for one component: src = 14-bit intermediates (host),
+ * dst = Clip(((weight * (src + 8192) + round) >> (log2_denom + 14 - B)) + offset * 2^(B-8)); the derived fields are getWpScaling's
+ * uni-directional branch (:302-312). */
+int hmx_addWeightUni(hmx_ctx *ctx, const hmx_pel *src, int src_stride, hmx_pel *dst, int dst_stride, int w, int h, int weight,
+                     int offset, int log2_denom);
+/* TComWeightPrediction::addWeightBi (TComWeightPrediction.cpp:61-150, bRound = true) for one component, with getWpScaling's
+ * bi-directional branch (:286-301): shift = log2_denom + 1 + 14 - B (list 0's denominator serves both lists), the offsets summed. */
+int hmx_addWeightBi(hmx_ctx *ctx, const hmx_pel *src0, int s0_stride, const hmx_pel *src1, int s1_stride, hmx_pel *dst,
+                    int dst_stride, int w, int h, int weight0, int weight1, int offset0, int offset1, int log2_denom);
+/* hmx_motionCompensation with the weighting of TComPrediction.cpp:421-432 / :516-535 -> xWeightedPredictionUni / xWeightedPredictionBi
+ * (TComWeightPrediction.cpp:327-386).  wp0 / wp1: the entries of the two references used (NULL where the list is unused). */
+int hmx_motionCompensation_wp(hmx_ctx *ctx, const hmx_pic *ref0, const int *mv0, const hmx_pic *ref1, const int *mv1, int x, int y,
+                              int w, int h, const hmx_pic *dst, const hmx_wp *wp0, const hmx_wp *wp1);
+
 /* Motion compensation of a list of PUs against reference pictures resident in HBM with the
  * reference's margin layout (TLibCommon/TComPicYuv.cpp:82-94): motionCompensation -> xPredInterUni/Bi ->
  * xPredInterLumaBlk/ChromaBlk -> addAvg (TLibCommon/TComPrediction.cpp:410-642). MVs already clipped. */
@@ -666,6 +692,18 @@ typedef struct hmx_mc_job {
  * by the pictures of a call; planes and levels are arrays of n_pics entries.  d_abs_sum, if not NULL,
  * holds n_pics * (blocks of the list) sums, picture-major. */
 int hmx_batch_motionCompensation_multi(hmx_ctx *ctx, int n_jobs, const hmx_mc_job *jobs);
+/* hmx_batch_motionCompensation_multi under explicit weighted prediction (TComPrediction.cpp:421-432, :516-535 ->
+ * TComWeightPrediction.cpp:251-386).  wp: host array [n_jobs], wp[i] = the tables of jobs[i].  Both schedules of hmx_mc_job are
+ * supported.  A job whose tables are both NULL is predicted exactly as hmx_batch_motionCompensation_multi predicts it.  A
+ * weighted job gives l0 (l0 NULL with l1 set is HMX_ERR_ARG); with l1 NULL a unit that uses list 1 all the same is weighted by 1.
+ * The tables are indexed by the same hmx_pu::ref0 / ref1 as hmx_mc_job::refs: a picture that sits in a list twice with different
+ * weights (or in both lists of a B slice, where l0[k] and l1[k] belong to the same refs[k]) is entered in refs[] once per
+ * distinct weight pair. */
+typedef struct {            /* the tables of one hmx_mc_job; both NULL = this job is not weighted */
+  const hmx_wp *l0, *l1;    /* host arrays [n_refs], indexed like hmx_mc_job::refs by hmx_pu::ref0 / ref1; l1 may be NULL
+                               when no unit of the job uses list 1 (P slice) */
+} hmx_mc_wp;
+int hmx_batch_motionCompensation_wp_multi(hmx_ctx *ctx, int n_jobs, const hmx_mc_job *jobs, const hmx_mc_wp *wp);
 int hmx_batch_residual_transformNxN_multi(hmx_ctx *ctx, const hmx_tu_list *list, int n_pics, const hmx_pic *org,
                                           const hmx_pic *pred, const hmx_levels *lev, uint32_t *d_abs_sum,
                                           const hmx_pic_param *pp);

@@ -80,6 +80,42 @@ class McJob(C.Structure):  # hmx_mc_job
                 ("pic_w", C.c_int), ("pic_h", C.c_int)]
 
 
+class Wp(C.Structure):  # hmx_wp: wpScalingParam of one (list, reference), per component Y, Cb, Cr
+    _fields_ = [("weight", C.c_int16 * 3), ("offset", C.c_int16 * 3), ("log2_denom", C.c_uint8 * 3), ("reserved", C.c_uint8)]
+
+
+class McWp(C.Structure):  # hmx_mc_wp: the tables of one hmx_mc_job
+    _fields_ = [("l0", C.POINTER(Wp)), ("l1", C.POINTER(Wp))]
+
+
+WP_DTYPE = np.dtype([("weight", "<i2", 3), ("offset", "<i2", 3), ("log2_denom", "u1", 3), ("reserved", "u1")])  # hmx_wp
+
+
+def wp_entry(weight, offset, log2_denom):
+    """One hmx_wp from three (Y, Cb, Cr) triples."""
+    e = Wp()
+    for k in range(3):
+        e.weight[k], e.offset[k], e.log2_denom[k] = int(weight[k]), int(offset[k]), int(log2_denom[k])
+    return e
+
+
+def mc_wp_array(tables):
+    """The hmx_mc_wp array of a hmx_batch_motionCompensation_wp_multi call.  tables: one item per job, None (the job is not
+    weighted) or (l0, l1) with l1 possibly None; a table is a numpy array of WP_DTYPE, one entry per reference of the job.
+    Returns (array, keep): keep holds the buffers the array points into and must outlive the call."""
+    arr, keep = (McWp * len(tables))(), []
+    for i, t in enumerate(tables):
+        if t is None:
+            continue
+        for name, tab in zip(("l0", "l1"), t):
+            if tab is None:
+                continue
+            tab = np.ascontiguousarray(tab, WP_DTYPE)
+            keep.append(tab)
+            setattr(arr[i], name, C.cast(tab.ctypes.data, C.POINTER(Wp)))
+    return arr, keep
+
+
 _lib = None
 
 
@@ -245,6 +281,14 @@ def lib():
                          ("hmx_sao_picture_multi", [vp, ci, C.POINTER(Pic), C.POINTER(Pic), ci, ci, vp, ci])):
             if "HMX_LIB_PATH" in os.environ and not hasattr(L, name):
                 continue  # an older build loaded for an A/B run (tools/filters_bench.py): calling the entry still raises
+            getattr(L, name).argtypes = at
+        for name, at in (("hmx_addWeightUni", [vp, vp, ci, vp, ci, ci, ci, ci, ci, ci]),
+                         ("hmx_addWeightBi", [vp, vp, ci, vp, ci, vp, ci, ci, ci, ci, ci, ci, ci, ci]),
+                         ("hmx_motionCompensation_wp", [vp, C.POINTER(Pic), C.POINTER(ci), C.POINTER(Pic), C.POINTER(ci), ci, ci, ci, ci,
+                                                        C.POINTER(Pic), C.POINTER(Wp), C.POINTER(Wp)]),
+                         ("hmx_batch_motionCompensation_wp_multi", [vp, ci, C.POINTER(McJob), C.POINTER(McWp)])):
+            if "HMX_LIB_PATH" in os.environ and not hasattr(L, name):
+                continue  # an older build loaded for an A/B run (tools/mc_wp_bench.py): calling the entry still raises
             getattr(L, name).argtypes = at
         L.hmx_yuv_frame_bytes.argtypes = [ci, ci, ci]
         L.hmx_yuv_frame_bytes.restype = C.c_size_t
@@ -525,6 +569,35 @@ class Context:
         d = np.zeros(w * h, np.int16)
         self._chk(lib().hmx_addAvg(self.h, _hp(a), w, _hp(b), w, _hp(d), w, w, h))
         return d
+
+    def addWeightUni(self, a, w, h, weight, offset, log2_denom):
+        """hmx_addWeightUni on a w x h block of 14-bit intermediates."""
+        a = np.ascontiguousarray(a, np.int16)
+        d = np.zeros(w * h, np.int16)
+        self._chk(lib().hmx_addWeightUni(self.h, _hp(a), w, _hp(d), w, w, h, weight, offset, log2_denom))
+        return d
+
+    def addWeightBi(self, a, b, w, h, weight0, weight1, offset0, offset1, log2_denom):
+        """hmx_addWeightBi on two w x h blocks of 14-bit intermediates."""
+        a = np.ascontiguousarray(a, np.int16)
+        b = np.ascontiguousarray(b, np.int16)
+        d = np.zeros(w * h, np.int16)
+        self._chk(lib().hmx_addWeightBi(self.h, _hp(a), w, _hp(b), w, _hp(d), w, w, h, weight0, weight1, offset0, offset1, log2_denom))
+        return d
+
+    def motion_compensation_wp(self, ref0, mv0, ref1, mv1, x, y, w, h, dst, wp0, wp1):
+        """hmx_motionCompensation_wp: ref0 / ref1 / dst = Pic of host planes (None = list unused), mv = (hor, ver), wp = Wp."""
+        m0 = None if ref0 is None else (C.c_int * 2)(*mv0)
+        m1 = None if ref1 is None else (C.c_int * 2)(*mv1)
+        self._chk(lib().hmx_motionCompensation_wp(self.h, None if ref0 is None else C.byref(ref0), m0, None if ref1 is None else C.byref(ref1), m1,
+                                                  x, y, w, h, C.byref(dst), None if wp0 is None else C.byref(wp0),
+                                                  None if wp1 is None else C.byref(wp1)))
+
+    def batch_motion_compensation_wp(self, jobs, tables):
+        """hmx_batch_motionCompensation_wp_multi: jobs = a (McJob * n) array, tables as for mc_wp_array."""
+        arr, keep = mc_wp_array(tables)
+        self._chk(lib().hmx_batch_motionCompensation_wp_multi(self.h, len(tables), jobs, arr))
+        del keep  # the call has copied the tables
 
     # --- batched device path ---
     def tu_list(self, tus):

@@ -125,19 +125,24 @@ extern "C" int hmx_xPredInterChromaBlk(hmx_ctx *c, const hmx_pel *ref, int ref_s
   return pred_inter_blk(c, s, ref, ref_stride, mv_hor, mv_ver, w >> 1, h >> 1, dst, dst_stride, bi, 1);
 }
 __global__ void k_addavg(const short *a, const short *b, short *d, int n, int B);
+__global__ void k_weight_uni(const short *a, short *d, int n, int w, int off, int shift, int B);
+__global__ void k_weight_bi(const short *a, const short *b, short *d, int n, int w0, int w1, int off, int shift, int B);
+static bool wp_ok(int weight, int offset, int log2_denom) {
+  return weight >= -128 && weight <= 255 && offset >= -128 && offset <= 127 && log2_denom >= 0 && log2_denom <= 7;
+}
 // motionCompensation of ONE prediction unit (TComPrediction.cpp:410-552): xPredInterUni per used list (isLast = uni-prediction),
 // TComYuv::addAvg when both lists are used.  ref0 / ref1: planes of the reference pictures (plane[i] at sample (0,0), margins
 // readable), NULL = list unused; (x, y, w, h): the unit in luma samples; dst: plane[i] at the unit's first sample.
-extern "C" int hmx_motionCompensation(hmx_ctx *c, const hmx_pic *ref0, const int *mv0, const hmx_pic *ref1, const int *mv1, int x, int y, int w,
-                                      int h, const hmx_pic *dst) {
-  if (!c || !dst || (!ref0 && !ref1) || (ref0 && !mv0) || (ref1 && !mv1) || w <= 0 || h <= 0 || w > 64 || h > 64 || (w & 1) || (h & 1))
-    return fail(c, HMX_ERR_ARG, "hmx_motionCompensation: bad argument");
-  const bool bi = ref0 && ref1;
+// weighted (:421-432, :516-535): every list makes 14-bit samples, addWeightUni / addWeightBi with the entries wp0 / wp1 end it.
+static int mc_one(hmx_ctx *c, const hmx_pic *ref0, const int *mv0, const hmx_pic *ref1, const int *mv1, int x, int y, int w, int h,
+                  const hmx_pic *dst, bool weighted, const hmx_wp *wp0, const hmx_wp *wp1) {
+  const bool bi = ref0 && ref1, mid = bi || weighted; // mid: the lists' predictions stay 14-bit on the device
+  const int B = c->cfg.bit_depth, head = 14 - B;
   for (int p = 0; p < 3; p++) {
     const int ch = p ? 1 : 0, pw = w >> ch, ph = h >> ch;
     Scratch s{c};
     short *d_pred[2] = {nullptr, nullptr};
-    if (bi) { // both 14-bit intermediates stay on the device (the tail of the scratch area), addAvg there
+    if (mid) { // both 14-bit intermediates stay on the device (the tail of the scratch area), addAvg there
       d_pred[0] = s.take_tail<short>(2 * 64 * 64);
       d_pred[1] = d_pred[0] + 64 * 64;
     }
@@ -146,20 +151,51 @@ extern "C" int hmx_motionCompensation(hmx_ctx *c, const hmx_pic *ref0, const int
       const int *mv = l ? mv1 : mv0;
       if (!rp) continue;
       const hmx_pel *r0 = rp->plane[p] + (ptrdiff_t)(y >> ch) * rp->stride[p] + (x >> ch);
-      int r = pred_inter_blk(c, s, r0, rp->stride[p], mv[0], mv[1], pw, ph, dst->plane[p], dst->stride[p], bi, ch, bi ? d_pred[l] : nullptr);
+      int r = pred_inter_blk(c, s, r0, rp->stride[p], mv[0], mv[1], pw, ph, dst->plane[p], dst->stride[p], mid, ch, mid ? d_pred[l] : nullptr);
       if (r) return r;
     }
-    if (bi) {
+    if (mid) {
       s.rewind();
       short *d_out = s.take<short>((size_t)pw * ph);
       if (s.r) return s.r;
-      hipLaunchKernelGGL(k_addavg, dim3((pw * ph + 255) / 256), dim3(256), 0, c->stream, d_pred[0], d_pred[1], d_out, pw * ph, c->cfg.bit_depth);
+      const dim3 grid((pw * ph + 255) / 256), blk(256);
+      if (!weighted) {
+        hipLaunchKernelGGL(k_addavg, grid, blk, 0, c->stream, d_pred[0], d_pred[1], d_out, pw * ph, B);
+      } else if (bi) { // getWpScaling :286-300: list 0's denominator, the sum of both offsets
+        const int off = (wp0->offset[p] + wp1->offset[p]) * (1 << (B - 8));
+        hipLaunchKernelGGL(k_weight_bi, grid, blk, 0, c->stream, d_pred[0], d_pred[1], d_out, pw * ph, (int)wp0->weight[p], (int)wp1->weight[p], off,
+                           wp0->log2_denom[p] + 1 + head, B);
+      } else {
+        const hmx_wp *e = ref0 ? wp0 : wp1;
+        hipLaunchKernelGGL(k_weight_uni, grid, blk, 0, c->stream, d_pred[ref0 ? 0 : 1], d_out, pw * ph, (int)e->weight[p], e->offset[p] * (1 << (B - 8)),
+                           e->log2_denom[p] + head, B);
+      }
       HIPCHK(c, hipGetLastError());
       int r = down2d(c, dst->plane[p], dst->stride[p], d_out, 2, pw, ph);
       if (r) return r;
     }
   }
   return HMX_OK;
+}
+static bool mc_one_args_ok(hmx_ctx *c, const hmx_pic *ref0, const int *mv0, const hmx_pic *ref1, const int *mv1, int w, int h, const hmx_pic *dst) {
+  return c && dst && (ref0 || ref1) && (!ref0 || mv0) && (!ref1 || mv1) && w > 0 && h > 0 && w <= 64 && h <= 64 && !(w & 1) && !(h & 1);
+}
+extern "C" int hmx_motionCompensation(hmx_ctx *c, const hmx_pic *ref0, const int *mv0, const hmx_pic *ref1, const int *mv1, int x, int y, int w,
+                                      int h, const hmx_pic *dst) {
+  if (!mc_one_args_ok(c, ref0, mv0, ref1, mv1, w, h, dst)) return fail(c, HMX_ERR_ARG, "hmx_motionCompensation: bad argument");
+  return mc_one(c, ref0, mv0, ref1, mv1, x, y, w, h, dst, false, nullptr, nullptr);
+}
+extern "C" int hmx_motionCompensation_wp(hmx_ctx *c, const hmx_pic *ref0, const int *mv0, const hmx_pic *ref1, const int *mv1, int x, int y,
+                                         int w, int h, const hmx_pic *dst, const hmx_wp *wp0, const hmx_wp *wp1) {
+  if (!mc_one_args_ok(c, ref0, mv0, ref1, mv1, w, h, dst) || (ref0 && !wp0) || (ref1 && !wp1))
+    return fail(c, HMX_ERR_ARG, "hmx_motionCompensation_wp: bad argument");
+  for (int l = 0; l < 2; l++)
+    for (int p = 0; p < 3; p++) {
+      const hmx_wp *e = l ? wp1 : wp0;
+      if ((l ? ref1 : ref0) && !wp_ok(e->weight[p], e->offset[p], e->log2_denom[p]))
+        return fail(c, HMX_ERR_ARG, "hmx_motionCompensation_wp: weight outside -128..255, offset outside -128..127 or log2_denom > 7");
+    }
+  return mc_one(c, ref0, mv0, ref1, mv1, x, y, w, h, dst, true, wp0, wp1);
 }
 
 // ---- the encoder's sub-pel refinement fan-out (HOT LOOP C) ----
@@ -287,6 +323,15 @@ __device__ __forceinline__ int add_avg(int a, int b, int B) { // TComYuv.cpp:539
   const int sh = 15 - B, off = (1 << (sh - 1)) + 2 * 8192;
   return clip3(0, (1 << B) - 1, (a + b + off) >> sh);
 }
+// weightUnidir / weightBidir (TComWeightPrediction.h:82-89) on 14-bit intermediates; shift = log2 denominator + (14 - B)
+// (+ 1 for two lists), off = the offset(s) at the bit depth.  The reference's offset << (shift - 1) is a product here.
+__device__ __forceinline__ int weight_uni(int p, int w, int off, int shift, int B) {
+  const int round = shift ? 1 << (shift - 1) : 0;
+  return clip3(0, (1 << B) - 1, ((w * (p + 8192) + round) >> shift) + off);
+}
+__device__ __forceinline__ int weight_bi(int p0, int p1, int w0, int w1, int off, int shift, int B) {
+  return clip3(0, (1 << B) - 1, (w0 * (p0 + 8192) + w1 * (p1 + 8192) + (1 + off) * (1 << (shift - 1))) >> shift);
+}
 __global__ void k_addavg(const short *a, const short *b, short *d, int n, int B) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) d[i] = (short)add_avg(a[i], b[i], B);
@@ -298,6 +343,45 @@ extern "C" int hmx_addAvg(hmx_ctx *c, const hmx_pel *s0, int s0s, const hmx_pel 
   short *da = s.up(s0, w, h, s0s), *db = s.up(s1, w, h, s1s), *dd = s.take<short>((size_t)w * h);
   if (s.r) return s.r;
   hipLaunchKernelGGL(k_addavg, dim3((w * h + 255) / 256), dim3(256), 0, c->stream, da, db, dd, w * h, c->cfg.bit_depth);
+  HIPCHK(c, hipGetLastError());
+  return down2d(c, dst, ds, dd, 2, w, h);
+}
+
+// TComWeightPrediction::addWeightUni / addWeightBi (TComWeightPrediction.cpp:61-237) of one component: src = 14-bit intermediates,
+// weight / offset / log2_denom = iWeight / iOffset (8-bit units) / uiLog2WeightDenom of the entries getWpScaling derives from
+__global__ void k_weight_uni(const short *a, short *d, int n, int w, int off, int shift, int B) {
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) d[i] = (short)weight_uni(a[i], w, off, shift, B);
+}
+__global__ void k_weight_bi(const short *a, const short *b, short *d, int n, int w0, int w1, int off, int shift, int B) {
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) d[i] = (short)weight_bi(a[i], b[i], w0, w1, off, shift, B);
+}
+extern "C" int hmx_addWeightUni(hmx_ctx *c, const hmx_pel *src, int ss, hmx_pel *dst, int ds, int w, int h, int weight, int offset,
+                                int log2_denom) {
+  if (!c || !src || !dst || w <= 0 || h <= 0 || w > 128 || h > 128) return fail(c, HMX_ERR_ARG, "hmx_addWeightUni: bad argument");
+  if (!wp_ok(weight, offset, log2_denom))
+    return fail(c, HMX_ERR_ARG, "hmx_addWeightUni: weight outside -128..255, offset outside -128..127 or log2_denom > 7");
+  const int B = c->cfg.bit_depth;
+  Scratch s{c};
+  short *da = s.up(src, w, h, ss), *dd = s.take<short>((size_t)w * h);
+  if (s.r) return s.r;
+  hipLaunchKernelGGL(k_weight_uni, dim3((w * h + 255) / 256), dim3(256), 0, c->stream, da, dd, w * h, weight, offset * (1 << (B - 8)),
+                     log2_denom + 14 - B, B);
+  HIPCHK(c, hipGetLastError());
+  return down2d(c, dst, ds, dd, 2, w, h);
+}
+extern "C" int hmx_addWeightBi(hmx_ctx *c, const hmx_pel *s0, int s0s, const hmx_pel *s1, int s1s, hmx_pel *dst, int ds, int w, int h,
+                               int weight0, int weight1, int offset0, int offset1, int log2_denom) {
+  if (!c || !s0 || !s1 || !dst || w <= 0 || h <= 0 || w > 128 || h > 128) return fail(c, HMX_ERR_ARG, "hmx_addWeightBi: bad argument");
+  if (!wp_ok(weight0, offset0, log2_denom) || !wp_ok(weight1, offset1, log2_denom))
+    return fail(c, HMX_ERR_ARG, "hmx_addWeightBi: weight outside -128..255, offset outside -128..127 or log2_denom > 7");
+  const int B = c->cfg.bit_depth;
+  Scratch s{c};
+  short *da = s.up(s0, w, h, s0s), *db = s.up(s1, w, h, s1s), *dd = s.take<short>((size_t)w * h);
+  if (s.r) return s.r;
+  hipLaunchKernelGGL(k_weight_bi, dim3((w * h + 255) / 256), dim3(256), 0, c->stream, da, db, dd, w * h, weight0, weight1,
+                     (offset0 + offset1) * (1 << (B - 8)), log2_denom + 1 + 14 - B, B);
   HIPCHK(c, hipGetLastError());
   return down2d(c, dst, ds, dd, 2, w, h);
 }
@@ -315,7 +399,17 @@ struct McArgs {
   const PlanesDev *refs; // all jobs' reference tables, back to back
   int B;
 };
-
+// Explicit weighted prediction (TComWeightPrediction.cpp:61-313): one entry per (reference, list), next to McArgs::refs
+// and indexed like it, [2 * (J.ref_off + ref) + list]; o is iOffset already scaled to the bit depth.
+struct alignas(16) WpDev { // one 16-byte load
+  short w[3], o[3];
+  unsigned char d[3], pad;
+};
+struct McArgsWp : McArgs {
+  const WpDev *wp;
+};
+template <bool WP>
+using McArgsOf = std::conditional_t<WP, McArgsWp, McArgs>;
 // ---- the prediction of one cell, on packed 16-bit pairs ----
 // A cell is 4x4 luma samples (2x2 chroma) of one PU.  Its reference window is read row by row with
 // DWORD-ALIGNED wide loads (x4 + x2 / x3 per row: tools/loadshape_probe.hip measures 41 cycles per wave-row
@@ -450,22 +544,44 @@ __device__ __forceinline__ void mc_cell(const int *lds_taps, const short *ref, i
 // Prediction of one plane's W x H cell from both lists (+ addAvg) into dst.  Pass one runs for every lane: the
 // only list of a uni-predicted PU (final samples, stored) or list 0 of a bi-predicted one (14-bit samples, kept
 // packed two per register); pass two runs list 1 for the bi-predicted lanes and stores addAvg rows.
-template <int NTAP, int W, int H>
-__device__ __forceinline__ void mc_cell_plane(const int *lds_taps, const McArgs &A, const McJob &J, const hmx_pu &u, int pl, int x, int y) {
+// WP (explicit weighted prediction, TComPrediction.cpp:421-432, :516-535): pass one makes 14-bit samples for every lane
+// (xPredInterUni(..., bi = true)); a uni-predicted lane stores weight_uni of them, pass two stores weight_bi instead of addAvg.
+template <int NTAP, int W, int H, bool WP = false>
+__device__ __forceinline__ void mc_cell_plane(const int *lds_taps, const McArgsOf<WP> &A, const McJob &J, const hmx_pu &u, int pl, int x, int y) {
   typedef __attribute__((address_space(1))) short gpel;
   const bool bi = u.ref0 != 255 && u.ref1 != 255, first1 = u.ref0 == 255;
   gpel *d = (gpel *)J.dst.p[pl] + (size_t)y * J.dst.s[pl] + x;
   const int ds = J.dst.s[pl];
   unsigned keep[H * W / 2];
+  int w0 = 0, w1 = 0, woff = 0, wshift = 0; // this plane's weights (WP only)
+  if constexpr (WP) {
+    typedef int i4v __attribute__((ext_vector_type(4)));
+    typedef __attribute__((address_space(1))) const i4v gwp;
+    const gwp *tab = (const gwp *)A.wp + 2 * J.ref_off;
+    const int head = 14 - A.B;
+    if (bi) { // list 0's denominator serves both lists (getWpScaling :295-299)
+      const WpDev e0 = __builtin_bit_cast(WpDev, (i4v)tab[2 * u.ref0]), e1 = __builtin_bit_cast(WpDev, (i4v)tab[2 * u.ref1 + 1]);
+      w0 = e0.w[pl], w1 = e1.w[pl], woff = e0.o[pl] + e1.o[pl], wshift = e0.d[pl] + 1 + head;
+    } else {
+      const WpDev e = __builtin_bit_cast(WpDev, (i4v)tab[first1 ? 2 * u.ref1 + 1 : 2 * u.ref0]);
+      w0 = e.w[pl], woff = e.o[pl], wshift = e.d[pl] + head;
+    }
+  }
   {
     const PlanesDev &R = A.refs[J.ref_off + (first1 ? u.ref1 : u.ref0)];
     mc_cell<NTAP, W, H>(lds_taps, R.p[pl] + (ptrdiff_t)y * R.s[pl] + x, R.s[pl], first1 ? u.mv1x : u.mv0x, first1 ? u.mv1y : u.mv0y,
-                        bi, A.B, [&](int r, const int *v) {
+                        WP || bi, A.B, [&](int r, const int *v) {
                           short row[W];
 #pragma unroll
                           for (int c = 0; c < W; c++) row[c] = (short)v[c];
 #pragma unroll
                           for (int c = 0; c < W; c += 2) keep[(r * W + c) / 2] = (unsigned)(unsigned short)row[c] | ((unsigned)(unsigned short)row[c + 1] << 16);
+                          if constexpr (WP) {
+                            if (!bi) {
+#pragma unroll
+                              for (int c = 0; c < W; c++) row[c] = (short)weight_uni(v[c], w0, woff, wshift, A.B);
+                            }
+                          }
                           if (!bi) __builtin_memcpy(d + (size_t)r * ds, row, W * 2); // one 8-byte (4-byte) store per row
                         });
   }
@@ -476,8 +592,13 @@ __device__ __forceinline__ void mc_cell_plane(const int *lds_taps, const McArgs 
 #pragma unroll
       for (int c = 0; c < W; c += 2) {
         const unsigned k = keep[(r * W + c) / 2];
-        row[c] = (short)add_avg((int)(short)(k & 0xffff), v[c], A.B);
-        row[c + 1] = (short)add_avg((int)(short)(k >> 16), v[c + 1], A.B);
+        if constexpr (WP) {
+          row[c] = (short)weight_bi((int)(short)(k & 0xffff), v[c], w0, w1, woff, wshift, A.B);
+          row[c + 1] = (short)weight_bi((int)(short)(k >> 16), v[c + 1], w0, w1, woff, wshift, A.B);
+        } else {
+          row[c] = (short)add_avg((int)(short)(k & 0xffff), v[c], A.B);
+          row[c + 1] = (short)add_avg((int)(short)(k >> 16), v[c + 1], A.B);
+        }
       }
       __builtin_memcpy(d + (size_t)r * ds, row, W * 2);
     });
@@ -504,7 +625,8 @@ __global__ __launch_bounds__(256) void k_mc_map(McArgs A) { // 16 threads per PU
       if ((u.x >> 2) + i < J.cw) J.map[(size_t)cy * J.cw + (u.x >> 2) + i] = pi;
   }
 }
-__global__ __launch_bounds__(256) void k_mc_cells(McArgs A) {
+template <bool WP>
+__global__ __launch_bounds__(256) void k_mc_cells(McArgsOf<WP> A) {
   __shared__ int taps[kTapTable];
   fill_tap_table(taps, threadIdx.x, 256);
   const McJob J = A.jobs[blockIdx.y];
@@ -520,22 +642,23 @@ __global__ __launch_bounds__(256) void k_mc_cells(McArgs A) {
   const int x = cx << 2, y = cy << 2;
   if (pi0 >= 0 && pi0 == pi1) {
     const hmx_pu u = J.pus[pi0];
-    mc_cell_plane<8, 4, 8>(taps, A, J, u, 0, x, y);
-    mc_cell_plane<4, 2, 4>(taps, A, J, u, 1, x >> 1, y >> 1);
-    mc_cell_plane<4, 2, 4>(taps, A, J, u, 2, x >> 1, y >> 1);
+    mc_cell_plane<8, 4, 8, WP>(taps, A, J, u, 0, x, y);
+    mc_cell_plane<4, 2, 4, WP>(taps, A, J, u, 1, x >> 1, y >> 1);
+    mc_cell_plane<4, 2, 4, WP>(taps, A, J, u, 2, x >> 1, y >> 1);
   } else {
 #pragma unroll 1
     for (int k = 0; k < 2; k++) {
       const int pi = k ? pi1 : pi0;
       if (pi < 0) continue;
       const hmx_pu u = J.pus[pi];
-      mc_cell_plane<8, 4, 4>(taps, A, J, u, 0, x, y + 4 * k);
-      mc_cell_plane<4, 2, 2>(taps, A, J, u, 1, x >> 1, (y >> 1) + 2 * k);
-      mc_cell_plane<4, 2, 2>(taps, A, J, u, 2, x >> 1, (y >> 1) + 2 * k);
+      mc_cell_plane<8, 4, 4, WP>(taps, A, J, u, 0, x, y + 4 * k);
+      mc_cell_plane<4, 2, 2, WP>(taps, A, J, u, 1, x >> 1, (y >> 1) + 2 * k);
+      mc_cell_plane<4, 2, 2, WP>(taps, A, J, u, 2, x >> 1, (y >> 1) + 2 * k);
     }
   }
 }
-__global__ __launch_bounds__(64) void k_mc(McArgs A) {
+template <bool WP>
+__global__ __launch_bounds__(64) void k_mc(McArgsOf<WP> A) {
   __shared__ int taps[kTapTable];
   fill_tap_table(taps, threadIdx.x, 64);
   const McJob J = A.jobs[blockIdx.y];
@@ -545,33 +668,65 @@ __global__ __launch_bounds__(64) void k_mc(McArgs A) {
   const int cw = u.w >> 2, cells = cw * (u.h >> 2);
   for (int i = threadIdx.x; i < cells; i += 64) {
     const int x = u.x + ((i % cw) << 2), y = u.y + ((i / cw) << 2);
-    mc_cell_plane<8, 4, 4>(taps, A, J, u, 0, x, y);
-    mc_cell_plane<4, 2, 2>(taps, A, J, u, 1, x >> 1, y >> 1);
-    mc_cell_plane<4, 2, 2>(taps, A, J, u, 2, x >> 1, y >> 1);
+    mc_cell_plane<8, 4, 4, WP>(taps, A, J, u, 0, x, y);
+    mc_cell_plane<4, 2, 2, WP>(taps, A, J, u, 1, x >> 1, y >> 1);
+    mc_cell_plane<4, 2, 2, WP>(taps, A, J, u, 2, x >> 1, y >> 1);
   }
 }
 
-extern "C" int hmx_batch_motionCompensation_multi(hmx_ctx *c, int n_jobs, const hmx_mc_job *jobs) {
-  if (!c || !jobs || n_jobs <= 0 || n_jobs > 65535) return fail(c, HMX_ERR_ARG, "hmx_batch_motionCompensation_multi: bad argument");
+// One table entry checked and brought to the device form (getWpScaling :286-312: o = iOffset * (1 << (B - 8))).
+static bool wp_entry(const hmx_wp &e, int B, WpDev *out) {
+  for (int k = 0; k < 3; k++) {
+    if (e.weight[k] < -128 || e.weight[k] > 255 || e.offset[k] < -128 || e.offset[k] > 127 || e.log2_denom[k] > 7) return false;
+    out->w[k] = e.weight[k];
+    out->o[k] = (short)(e.offset[k] * (1 << (B - 8)));
+    out->d[k] = e.log2_denom[k];
+  }
+  out->pad = 0;
+  return true;
+}
+// The jobs of one call, weighted ones (wp && wp[i].l0) first: the two kinds go to their own instantiations of the
+// prediction kernel, so an unweighted job of a weighted call runs the very code of the unweighted call.
+static int mc_multi(hmx_ctx *c, int n_jobs, const hmx_mc_job *jobs, const hmx_mc_wp *wp) {
   std::vector<McJob> hj(n_jobs);
   std::vector<PlanesDev> hr;
-  int max_n = 0;
-  size_t map_cells = 0, max_cells = 0, max_tiles = 0;
+  std::vector<WpDev> hw;
+  int n_kind[2] = {0, 0}, max_n[2] = {0, 0}; // [1] = weighted
+  size_t map_cells = 0, max_tiles[2] = {0, 0};
   bool mapped = true;
+  if (wp)
+    for (int i = 0; i < n_jobs; i++) {
+      if (!wp[i].l0 && wp[i].l1) return fail(c, HMX_ERR_ARG, "hmx_batch_motionCompensation_wp_multi: a weighted job needs the list 0 table (l0 NULL, l1 not)");
+      n_kind[1] += wp[i].l0 != nullptr;
+    }
+  n_kind[0] = n_jobs - n_kind[1];
+  int next[2] = {n_kind[1], 0}; // weighted jobs take the front of hj
   for (int i = 0; i < n_jobs; i++) {
     const hmx_mc_job &j = jobs[i];
     if (j.n_pus < 0 || (j.n_pus > 0 && !j.d_pus) || !j.refs || j.n_refs <= 0 || j.n_refs > 16 || !j.dst || j.pic_w < 0 || j.pic_h < 0)
       return fail(c, HMX_ERR_ARG, "hmx_batch_motionCompensation_multi: bad job");
-    hj[i] = McJob{j.d_pus, j.n_pus, (int)hr.size(), to_dev(j.dst), nullptr, (j.pic_w + 3) / 4, (j.pic_h + 3) / 4};
+    const int kind = wp && wp[i].l0;
+    McJob &h = hj[next[kind]++];
+    h = McJob{j.d_pus, j.n_pus, (int)hr.size(), to_dev(j.dst), nullptr, (j.pic_w + 3) / 4, (j.pic_h + 3) / 4};
     for (int k = 0; k < j.n_refs; k++) hr.push_back(to_dev(&j.refs[k]));
-    max_n = std::max(max_n, j.n_pus);
-    const size_t cells = (size_t)hj[i].cw * hj[i].ch;
+    if (wp) { // entries of unweighted jobs are never read; a missing list 1 table holds the unit weight
+      const hmx_wp unit = {{1, 1, 1}, {0, 0, 0}, {0, 0, 0}, 0};
+      for (int k = 0; k < j.n_refs; k++)
+        for (int l = 0; l < 2; l++) {
+          const hmx_wp *t = l ? wp[i].l1 : wp[i].l0;
+          WpDev e;
+          if (!wp_entry(kind && t ? t[k] : unit, c->cfg.bit_depth, &e))
+            return fail(c, HMX_ERR_ARG, "hmx_batch_motionCompensation_wp_multi: weight outside -128..255, offset outside -128..127 or log2_denom > 7");
+          hw.push_back(e);
+        }
+    }
+    max_n[kind] = std::max(max_n[kind], j.n_pus);
+    const size_t cells = (size_t)h.cw * h.ch;
     mapped = mapped && cells > 0;
     map_cells += cells;
-    max_cells = std::max(max_cells, cells);
-    max_tiles = std::max(max_tiles, (size_t)((hj[i].cw + 15) / 16) * ((hj[i].ch + 31) / 32)); // 64 x 128 luma samples
+    max_tiles[kind] = std::max(max_tiles[kind], (size_t)((h.cw + 15) / 16) * ((h.ch + 31) / 32)); // 64 x 128 luma samples
   }
-  if (!max_n) return HMX_OK;
+  if (!max_n[0] && !max_n[1]) return HMX_OK;
   if (mapped) { // cell maps of all jobs, back to back, in a grow-only scratch buffer
     if (map_cells > c->mcmap_cap) {
       HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -588,25 +743,40 @@ extern "C" int hmx_batch_motionCompensation_multi(hmx_ctx *c, int n_jobs, const 
       off += (size_t)hj[i].cw * hj[i].ch;
     }
   }
-  // both tables in one copy
-  const size_t jb = (sizeof(McJob) * hj.size() + 255) & ~(size_t)255;
-  std::vector<char> blob(jb + sizeof(PlanesDev) * hr.size());
+  // all tables in one copy
+  const size_t jb = (sizeof(McJob) * hj.size() + 255) & ~(size_t)255, rb = (sizeof(PlanesDev) * hr.size() + 15) & ~(size_t)15;
+  std::vector<char> blob(jb + rb + sizeof(WpDev) * hw.size());
   memcpy(blob.data(), hj.data(), sizeof(McJob) * hj.size());
   memcpy(blob.data() + jb, hr.data(), sizeof(PlanesDev) * hr.size());
+  if (!hw.empty()) memcpy(blob.data() + jb + rb, hw.data(), sizeof(WpDev) * hw.size());
   char *d = static_cast<char *>(arena_push(c, blob.data(), blob.size()));
   if (!d) return fail(c, HMX_ERR_NOMEM, "argument arena");
-  McArgs A;
+  McArgsWp A;
   A.jobs = reinterpret_cast<const McJob *>(d);
   A.refs = reinterpret_cast<const PlanesDev *>(d + jb);
   A.B = c->cfg.bit_depth;
+  A.wp = reinterpret_cast<const WpDev *>(d + jb + rb);
+  McArgs U = A; // the unweighted jobs: the tail of the job table
+  U.jobs = A.jobs + n_kind[1];
   if (mapped) {
-    hipLaunchKernelGGL(k_mc_map, dim3((unsigned)((max_n + 15) / 16), (unsigned)n_jobs), dim3(256), 0, c->stream, A);
-    hipLaunchKernelGGL(k_mc_cells, dim3((unsigned)max_tiles, (unsigned)n_jobs), dim3(256), 0, c->stream, A);
+    hipLaunchKernelGGL(k_mc_map, dim3((unsigned)((std::max(max_n[0], max_n[1]) + 15) / 16), (unsigned)n_jobs), dim3(256), 0, c->stream, static_cast<McArgs>(A));
+    if (max_n[1]) hipLaunchKernelGGL(k_mc_cells<true>, dim3((unsigned)max_tiles[1], (unsigned)n_kind[1]), dim3(256), 0, c->stream, A);
+    if (max_n[0]) hipLaunchKernelGGL(k_mc_cells<false>, dim3((unsigned)max_tiles[0], (unsigned)n_kind[0]), dim3(256), 0, c->stream, U);
   } else {
-    hipLaunchKernelGGL(k_mc, dim3((unsigned)max_n, (unsigned)n_jobs), dim3(64), 0, c->stream, A);
+    if (max_n[1]) hipLaunchKernelGGL(k_mc<true>, dim3((unsigned)max_n[1], (unsigned)n_kind[1]), dim3(64), 0, c->stream, A);
+    if (max_n[0]) hipLaunchKernelGGL(k_mc<false>, dim3((unsigned)max_n[0], (unsigned)n_kind[0]), dim3(64), 0, c->stream, U);
   }
   HIPCHK(c, hipGetLastError());
   return HMX_OK;
+}
+extern "C" int hmx_batch_motionCompensation_multi(hmx_ctx *c, int n_jobs, const hmx_mc_job *jobs) {
+  if (!c || !jobs || n_jobs <= 0 || n_jobs > 65535) return fail(c, HMX_ERR_ARG, "hmx_batch_motionCompensation_multi: bad argument");
+  return mc_multi(c, n_jobs, jobs, nullptr);
+}
+// motionCompensation with TComWeightPrediction (TComPrediction.cpp:421-432, :516-535) over PU lists: wp[i] = the tables of jobs[i]
+extern "C" int hmx_batch_motionCompensation_wp_multi(hmx_ctx *c, int n_jobs, const hmx_mc_job *jobs, const hmx_mc_wp *wp) {
+  if (!c || !jobs || !wp || n_jobs <= 0 || n_jobs > 65535) return fail(c, HMX_ERR_ARG, "hmx_batch_motionCompensation_wp_multi: bad argument");
+  return mc_multi(c, n_jobs, jobs, wp);
 }
 
 extern "C" int hmx_batch_motionCompensation(hmx_ctx *c, const hmx_pu *d_pus, int n, const hmx_pic *refs, int n_refs,

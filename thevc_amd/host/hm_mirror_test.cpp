@@ -44,7 +44,64 @@ static int recur_main(int argc, char **argv) {
   return 0;
 }
 
+// Usage: hm_mirror_test wp <bitDepth> <seed>: a 16x8 unit of random 14-bit intermediates of two lists through
+// TComWeightPrediction::xWeightedPredictionUni (list 0's row) and xWeightedPredictionBi (both rows).  Prints the two rows
+// (weight offset log2Denom per component), the derived offset / shift / round of the bi case, the six source planes and the
+// six result planes, one line each.
+static int wp_main(int argc, char **argv) {
+  if (argc < 4) return 2;
+  const int B = atoi(argv[2]), W = 16, H = 8;
+  unsigned seed = (unsigned)atoi(argv[3]);
+  auto next = [&]() { return (seed = seed * 1664525u + 1013904223u) >> 8; };
+  hmx_hm::Context ctx(B);
+  hmx_hm::TComWeightPrediction wp(ctx);
+  hmx_hm::wpScalingParam row[2][3] = {};
+  for (int yuv = 0; yuv < 3; yuv++) {
+    const unsigned d = next() % 8; // one denominator per component for both lists, as the slice header codes it
+    for (int l = 0; l < 2; l++) {
+      row[l][yuv].bPresentFlag = true;
+      row[l][yuv].uiLog2WeightDenom = d;
+      row[l][yuv].iWeight = (int)(next() % 384) - 128;
+      row[l][yuv].iOffset = (int)(next() % 256) - 128;
+    }
+  }
+  std::vector<short> buf[2][3], out[2][3];
+  hmx_pic src[2], dst[2];
+  for (int l = 0; l < 2; l++)
+    for (int yuv = 0; yuv < 3; yuv++) {
+      const int w = W >> (yuv ? 1 : 0), h = H >> (yuv ? 1 : 0);
+      buf[l][yuv].resize(w * h);
+      out[l][yuv].assign(w * h, 0);
+      for (auto &v : buf[l][yuv]) v = (short)((int)(next() % 16384) - 8192);
+      src[l].plane[yuv] = buf[l][yuv].data(), src[l].stride[yuv] = w;
+      dst[l].plane[yuv] = out[l][yuv].data(), dst[l].stride[yuv] = w;
+    }
+  wp.xWeightedPredictionUni(&src[0], W, H, row[0], &dst[0]);
+  wp.xWeightedPredictionBi(&src[0], &src[1], row[0], row[1], W, H, &dst[1]);
+  for (int l = 0; l < 2; l++) {
+    for (int yuv = 0; yuv < 3; yuv++) printf("%d %d %u ", row[l][yuv].iWeight, row[l][yuv].iOffset, row[l][yuv].uiLog2WeightDenom);
+    printf("\n");
+  }
+  for (int yuv = 0; yuv < 3; yuv++) printf("%d %d %d ", row[0][yuv].offset, row[0][yuv].shift, row[0][yuv].round);
+  printf("\n");
+  for (auto *set : {buf, out})
+    for (int l = 0; l < 2; l++)
+      for (int yuv = 0; yuv < 3; yuv++) {
+        for (int v : set[l][yuv]) printf("%d ", v);
+        printf("\n");
+      }
+  return 0;
+}
+
 int main(int argc, char **argv) {
+  if (argc >= 2 && std::string(argv[1]) == "wp") {
+    try {
+      return wp_main(argc, argv);
+    } catch (const std::exception &e) {
+      fprintf(stderr, "error: %s\n", e.what());
+      return 1;
+    }
+  }
   if (argc >= 2 && std::string(argv[1]) == "recur") {
     try {
       return recur_main(argc, argv);

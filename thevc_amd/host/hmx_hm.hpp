@@ -188,6 +188,98 @@ public:
     m_c.check(hmx_motionCompensation(m_c.get(), ref0, mv0, ref1, mv1, x, y, width, height, pred), "motionCompensation");
   }
 
+  // motionCompensation under getUseWP() / getWPBiPred() (TComPrediction.cpp:421-432, :516-535): the same with the table entries of
+  // the two references used (what TComSlice::getWpScaling returns for (list, refIdx)); NULL where the list is unused
+  void motionCompensation(const hmx_pic *ref0, const Int mv0[2], const hmx_pic *ref1, const Int mv1[2], Int x, Int y, Int width, Int height,
+                          const hmx_pic *pred, const hmx_wp *wp0, const hmx_wp *wp1) {
+    m_c.check(hmx_motionCompensation_wp(m_c.get(), ref0, mv0, ref1, mv1, x, y, width, height, pred, wp0, wp1), "motionCompensation (weighted)");
+  }
+
+private:
+  Context &m_c;
+};
+
+// wpScalingParam (TComSlice.h): the coded fields, then the ones getWpScaling derives
+struct wpScalingParam {
+  Bool bPresentFlag;
+  UInt uiLog2WeightDenom;
+  Int iWeight, iOffset;
+  Int w, o, offset, shift, round;
+};
+// TComWeightPrediction (TComWeightPrediction.h:49-89).  What the reference reads through pcCU->getSlice() is passed in: the
+// wpScalingParam[3] rows of the references used.  TComYuv arguments become the three planes of a hmx_pic at the unit's first sample
+// (14-bit intermediates in, samples out; host memory).
+class TComWeightPrediction {
+public:
+  explicit TComWeightPrediction(Context &c) : m_c(c) {}
+  // getWpScaling (:251-313): wp0 / wp1 = the rows of (list 0, iRefIdx0) / (list 1, iRefIdx1), NULL = list unused; fills w, o, offset,
+  // shift, round.  (The reference keeps 1 << log2Denom in `round` for two lists and recomputes it from shift in addWeightBi.)
+  void getWpScaling(wpScalingParam *wp0, wpScalingParam *wp1) {
+    const int ibdi = m_c.bitDepth();
+    if (wp0 && wp1) {
+      for (int yuv = 0; yuv < 3; yuv++) {
+        wp0[yuv].w = wp0[yuv].iWeight;
+        wp0[yuv].o = wp0[yuv].iOffset * (1 << (ibdi - 8));
+        wp1[yuv].w = wp1[yuv].iWeight;
+        wp1[yuv].o = wp1[yuv].iOffset * (1 << (ibdi - 8));
+        wp0[yuv].offset = wp1[yuv].offset = wp0[yuv].o + wp1[yuv].o;
+        wp0[yuv].shift = wp1[yuv].shift = (Int)wp0[yuv].uiLog2WeightDenom + 1;
+        wp0[yuv].round = wp1[yuv].round = 1 << wp0[yuv].uiLog2WeightDenom;
+      }
+    } else if (wpScalingParam *pwp = wp0 ? wp0 : wp1) {
+      for (int yuv = 0; yuv < 3; yuv++) {
+        pwp[yuv].w = pwp[yuv].iWeight;
+        pwp[yuv].offset = pwp[yuv].iOffset * (1 << (ibdi - 8));
+        pwp[yuv].shift = (Int)pwp[yuv].uiLog2WeightDenom;
+        pwp[yuv].round = pwp[yuv].uiLog2WeightDenom >= 1 ? 1 << (pwp[yuv].uiLog2WeightDenom - 1) : 0;
+      }
+    }
+  }
+  // addWeightUni (:161-237): iWidth x iHeight luma samples, chroma at half size
+  void addWeightUni(const hmx_pic *pcYuvSrc0, UInt iWidth, UInt iHeight, const wpScalingParam *wp0, const hmx_pic *rpcYuvDst) {
+    for (int yuv = 0; yuv < 3; yuv++) {
+      const int s = yuv ? 1 : 0;
+      m_c.check(hmx_addWeightUni(m_c.get(), pcYuvSrc0->plane[yuv], pcYuvSrc0->stride[yuv], rpcYuvDst->plane[yuv], rpcYuvDst->stride[yuv],
+                                 (int)iWidth >> s, (int)iHeight >> s, wp0[yuv].iWeight, wp0[yuv].iOffset, (int)wp0[yuv].uiLog2WeightDenom),
+                "addWeightUni");
+    }
+  }
+  // addWeightBi (:61-150)
+  void addWeightBi(const hmx_pic *pcYuvSrc0, const hmx_pic *pcYuvSrc1, UInt iWidth, UInt iHeight, const wpScalingParam *wp0,
+                   const wpScalingParam *wp1, const hmx_pic *rpcYuvDst) {
+    for (int yuv = 0; yuv < 3; yuv++) {
+      const int s = yuv ? 1 : 0;
+      m_c.check(hmx_addWeightBi(m_c.get(), pcYuvSrc0->plane[yuv], pcYuvSrc0->stride[yuv], pcYuvSrc1->plane[yuv], pcYuvSrc1->stride[yuv],
+                                rpcYuvDst->plane[yuv], rpcYuvDst->stride[yuv], (int)iWidth >> s, (int)iHeight >> s, wp0[yuv].iWeight,
+                                wp1[yuv].iWeight, wp0[yuv].iOffset, wp1[yuv].iOffset, (int)wp0[yuv].uiLog2WeightDenom),
+                "addWeightBi");
+    }
+  }
+  // xWeightedPredictionUni (:366-386): pwp = the row of (eRefPicList, iRefIdx)
+  void xWeightedPredictionUni(const hmx_pic *pcYuvSrc, Int iWidth, Int iHeight, wpScalingParam *pwp, const hmx_pic *rpcYuvPred) {
+    getWpScaling(pwp, nullptr);
+    addWeightUni(pcYuvSrc, iWidth, iHeight, pwp, rpcYuvPred);
+  }
+  // xWeightedPredictionBi (:327-352): a NULL row = that list unused (iRefIdx < 0)
+  void xWeightedPredictionBi(const hmx_pic *pcYuvSrc0, const hmx_pic *pcYuvSrc1, wpScalingParam *pwp0, wpScalingParam *pwp1, Int iWidth,
+                             Int iHeight, const hmx_pic *rpcYuvDst) {
+    if (!pwp0 && !pwp1) throw std::runtime_error("xWeightedPredictionBi: no list");
+    getWpScaling(pwp0, pwp1);
+    if (pwp0 && pwp1) addWeightBi(pcYuvSrc0, pcYuvSrc1, iWidth, iHeight, pwp0, pwp1, rpcYuvDst);
+    else if (pwp0) addWeightUni(pcYuvSrc0, iWidth, iHeight, pwp0, rpcYuvDst);
+    else addWeightUni(pcYuvSrc1, iWidth, iHeight, pwp1, rpcYuvDst);
+  }
+  // the hmx_wp of a row, for TComPrediction::motionCompensation's weighted overload and hmx_mc_wp tables
+  static hmx_wp entry(const wpScalingParam *wp) {
+    hmx_wp e{};
+    for (int yuv = 0; yuv < 3; yuv++) {
+      e.weight[yuv] = (int16_t)wp[yuv].iWeight;
+      e.offset[yuv] = (int16_t)wp[yuv].iOffset;
+      e.log2_denom[yuv] = (uint8_t)wp[yuv].uiLog2WeightDenom;
+    }
+    return e;
+  }
+
 private:
   Context &m_c;
 };
