@@ -228,6 +228,12 @@ int hmx_calcHAD(hmx_ctx *ctx, const hmx_pel *pi0, int stride0, const hmx_pel *pi
                 uint32_t *satd);
 int hmx_getSSE(hmx_ctx *ctx, const hmx_pel *cur, int cur_stride, const hmx_pel *org, int org_stride, int w, int h,
                uint32_t *sse);
+/* TComRdCost::xGetSAD4/8/12/16/24/32/48/64 (TComRdCost.cpp:518-..., dispatch :298-329), bApplyWeight false: the sum of
+ * |org - cur| over all w columns of the rows 0, 2^sub_shift, 2 * 2^sub_shift, ... < h; *sad = (sum << sub_shift) >> (bit
+ * depth - 8), UInt arithmetic.  w, h from {4, 8, 12, 16, 24, 32, 48, 64}; sub_shift 0, or 1 with h > 8 (what xPatternSearch
+ * sets under getUseFastEnc(), TEncSearch.cpp:4245-4251; the reference never sub-samples 8 rows or fewer: HMX_ERR_ARG). */
+int hmx_getSAD(hmx_ctx *ctx, const hmx_pel *cur, int cur_stride, const hmx_pel *org, int org_stride, int w, int h, int sub_shift,
+               uint32_t *sad);
 
 /* ------------------------------------------------------------------------------------------------
  * Scalar drop-ins, TComInterpolationFilter (TLibCommon/TComInterpolationFilter.cpp:323-415) and
@@ -568,6 +574,48 @@ int hmx_batch_motionCompensation(hmx_ctx *ctx, const hmx_pu *d_pus, int n, const
  * refs / org: device pictures; the references with the reference's margins. */
 int hmx_batch_subpel_cost(hmx_ctx *ctx, const hmx_pu *pus, int n, const hmx_pic *refs, int n_refs, const hmx_pic *org,
                           const int8_t *offs, int n_cand, int use_had, uint32_t *d_cost);
+
+/* ------------------------------------------------------------------------------------------------
+ * Full-search integer motion estimation: the stage of TEncSearch::xMotionEstimation (TLibEncoder/TEncSearch.cpp:4120-4206)
+ * in front of the sub-pel fan-out above.  All arithmetic is uint32_t, wrapping like the reference's UInt.
+ * ---------------------------------------------------------------------------------------------- */
+/* Host helpers, no context.  TComRdCost::getBits(x, y) (TComRdCost.h:201-211) with xGetComponentBits (TComRdCost.cpp:270-284)
+ * in closed form: bits(v) = 2 * floor(log2 t) + 1, t = v <= 0 ? ((-v) << 1) + 1 : v << 1; hmx_mvBits = bits((x << cost_scale)
+ * - pred_x) + bits((y << cost_scale) - pred_y), the predictor (setPredictor) in quarter samples. */
+uint32_t hmx_mvBits(int x, int y, int pred_x, int pred_y, int cost_scale);
+/* TComRdCost::getCost(x, y) (TComRdCost.h:185-193): (lambda * hmx_mvBits(...)) >> 16; lambda = m_uiLambdaMotionSAD =
+ * floor(65536 * sqrt(lambda)) (getMotionCost(1, 0), :171).  The integer search runs at cost_scale 2 (TEncSearch.cpp:4172). */
+uint32_t hmx_mvCost(uint32_t lambda, int x, int y, int pred_x, int pred_y, int cost_scale);
+/* TEncSearch::xSetSearchRange (TEncSearch.cpp:4209-4225) for the unit's CU at (cu_x, cu_y): the predictor (quarter samples)
+ * clipped with hmx_clipMv, -/+ (range << 2), both corners clipped with hmx_clipMv, arithmetic >> 2: the inclusive box in
+ * integer samples. */
+void hmx_setSearchRange(int pred_x, int pred_y, int range, int cu_x, int cu_y, int pic_w, int pic_h, int ctu_size, int *left,
+                        int *top, int *right, int *bottom);
+typedef struct {
+  uint16_t x, y;          /* unit position, luma samples */
+  uint8_t  w, h;          /* {4,8,12,16,24,32,48,64} */
+  uint8_t  ref;           /* index into refs[] */
+  uint8_t  sub_shift;     /* 0 | 1 */
+  int16_t  pred_x, pred_y;            /* predictor of the bits term, quarter samples */
+  int16_t  left, top, right, bottom;  /* search box, integer samples, inclusive */
+} hmx_me_unit;             /* 20 bytes */
+typedef struct { int16_t mvx, mvy; uint32_t sad; uint32_t cost; } hmx_me_result; /* 12 bytes */
+/* TEncSearch::xPatternSearch (TEncSearch.cpp:4227-4283) for every unit of `units` (HOST array): for y = top..bottom and, inside
+ * that, x = left..right, cost = SAD(original block at the unit, reference block displaced by (x, y)) + hmx_mvCost(lambda, x,
+ * y, pred_x, pred_y, 2), SAD as hmx_getSAD with the unit's sub_shift; the winner is the first candidate in that raster order
+ * with the strictly smallest cost.  d_result[i] (device) = {mv, sad = cost - vector cost (ruiSAD), cost}.  d_cost_map (device,
+ * may be NULL) receives the cost of every candidate: unit i's box row by row, box width right - left + 1, starting at the sum
+ * of the box areas of units 0..i-1.  refs (n_refs <= 4) / org: device pictures, the references with margins of margin_x /
+ * margin_y luma samples and samples in [0, 2^B); org may hold any value in [-2^B, 2^(B+1)) -- bi-prediction refinement
+ * searches against 2 * org - other prediction (removeHighFreq, :4147), which the caller passes as org.  Weighted SAD
+ * (xGetSADw), chroma and xTZSearch are not covered.
+ * n >= 1 and the boxes together hold fewer than 2^32 candidates; anything else is HMX_ERR_ARG.
+ * HMX_ERR_ARG, on the host before anything is launched, with the unit named in hmx_last_error: a size outside the set, ref >=
+ * n_refs, sub_shift other than 0 or (1 with h > 8), an empty box, a box side above 129 (search range 64), the unit outside the
+ * picture, a candidate block reaching outside [-margin, pic + margin) of the reference in either direction. */
+int hmx_batch_fullpel_search(hmx_ctx *ctx, const hmx_me_unit *units, int n, const hmx_pic *refs, int n_refs, const hmx_pic *org,
+                             int pic_w, int pic_h, int margin_x, int margin_y, uint32_t lambda, hmx_me_result *d_result,
+                             uint32_t *d_cost_map);
 
 /* Deblocking filter, the application part (TLibCommon/TComLoopFilter.cpp:571-922: xEdgeFilterLuma, xEdgeFilterChroma,
  * the pel filters, the strong/weak decision), in place on a reconstructed picture whose size

@@ -88,6 +88,20 @@ class McWp(C.Structure):  # hmx_mc_wp: the tables of one hmx_mc_job
     _fields_ = [("l0", C.POINTER(Wp)), ("l1", C.POINTER(Wp))]
 
 
+class MeUnit(C.Structure):  # hmx_me_unit
+    _fields_ = [("x", C.c_uint16), ("y", C.c_uint16), ("w", C.c_uint8), ("h", C.c_uint8), ("ref", C.c_uint8), ("sub_shift", C.c_uint8),
+                ("pred_x", C.c_int16), ("pred_y", C.c_int16), ("left", C.c_int16), ("top", C.c_int16), ("right", C.c_int16),
+                ("bottom", C.c_int16)]
+
+
+class MeResult(C.Structure):  # hmx_me_result
+    _fields_ = [("mvx", C.c_int16), ("mvy", C.c_int16), ("sad", C.c_uint32), ("cost", C.c_uint32)]
+
+
+ME_UNIT_DTYPE = np.dtype([("x", "<u2"), ("y", "<u2"), ("w", "u1"), ("h", "u1"), ("ref", "u1"), ("sub_shift", "u1"), ("pred_x", "<i2"),
+                          ("pred_y", "<i2"), ("left", "<i2"), ("top", "<i2"), ("right", "<i2"), ("bottom", "<i2")])  # hmx_me_unit
+ME_RESULT_DTYPE = np.dtype([("mvx", "<i2"), ("mvy", "<i2"), ("sad", "<u4"), ("cost", "<u4")])  # hmx_me_result
+
 WP_DTYPE = np.dtype([("weight", "<i2", 3), ("offset", "<i2", 3), ("log2_denom", "u1", 3), ("reserved", "u1")])  # hmx_wp
 
 
@@ -290,6 +304,15 @@ def lib():
             if "HMX_LIB_PATH" in os.environ and not hasattr(L, name):
                 continue  # an older build loaded for an A/B run (tools/mc_wp_bench.py): calling the entry still raises
             getattr(L, name).argtypes = at
+        u32 = C.c_uint32
+        for name, at, rt in (("hmx_mvBits", [ci, ci, ci, ci, ci], u32), ("hmx_mvCost", [u32, ci, ci, ci, ci, ci], u32),
+                             ("hmx_setSearchRange", [ci] * 8 + [C.POINTER(ci)] * 4, None),
+                             ("hmx_getSAD", [vp, vp, ci, vp, ci, ci, ci, ci, C.POINTER(u32)], ci),
+                             ("hmx_batch_fullpel_search", [vp, vp, ci, C.POINTER(Pic), ci, C.POINTER(Pic), ci, ci, ci, ci, u32, vp, vp], ci)):
+            if "HMX_LIB_PATH" in os.environ and not hasattr(L, name):
+                continue  # an older build loaded for an A/B run: calling the entry still raises
+            getattr(L, name).argtypes = at
+            getattr(L, name).restype = rt
         L.hmx_yuv_frame_bytes.argtypes = [ci, ci, ci]
         L.hmx_yuv_frame_bytes.restype = C.c_size_t
         L.hmx_yuv_unpack.argtypes = [vp, vp, ci, C.POINTER(Pic), ci, ci, ci, ci]
@@ -685,6 +708,37 @@ class Context:
         self._chk(lib().hmx_intra_plan_download(self.h, plan, _hp(blocks), _hp(levels)))
         return blocks, levels
 
+    def getSAD(self, cur, cur_stride, org, org_stride, w, h, sub_shift=0):
+        """hmx_getSAD of one block; cur, org: int16 arrays holding the block at their start with the given strides."""
+        cur, org = np.ascontiguousarray(cur, np.int16), np.ascontiguousarray(org, np.int16)
+        v = C.c_uint32()
+        self._chk(lib().hmx_getSAD(self.h, _hp(cur), cur_stride, _hp(org), org_stride, w, h, sub_shift, C.byref(v)))
+        return v.value
+
+    def batch_fullpel_search(self, units, refs, org, pic_w, pic_h, margin_x, margin_y, lambda_, want_map=False):
+        """hmx_batch_fullpel_search: units = array of ME_UNIT_DTYPE (host), refs = DevPictures with margins, org = DevPicture.
+        Returns the results (ME_RESULT_DTYPE) and, with want_map, (results, map, first): the cost of every candidate, unit i's
+        box row by row at map[first[i]:first[i + 1]].  At least one unit: the entry refuses n = 0."""
+        units = np.ascontiguousarray(units, ME_UNIT_DTYPE)
+        n = len(units)
+        if n == 0:
+            raise ValueError("batch_fullpel_search: at least one unit")
+        area = (units["right"].astype(np.int64) - units["left"] + 1) * (units["bottom"].astype(np.int64) - units["top"] + 1)
+        first = np.concatenate([[0], np.cumsum(np.maximum(area, 0))])
+        ref_arr = (Pic * len(refs))(*[r.as_pic() for r in refs])
+        d_res = self.alloc(n * ME_RESULT_DTYPE.itemsize)
+        d_map = self.alloc(int(first[-1]) * 4) if want_map else None
+        try:
+            self._chk(lib().hmx_batch_fullpel_search(self.h, units.ctypes.data, n, ref_arr, len(refs), C.byref(org.as_pic()), pic_w, pic_h,
+                                                     margin_x, margin_y, int(lambda_) & 0xFFFFFFFF, d_res.ptr, d_map.ptr if d_map else None))
+            self.sync()
+            res = d_res.download(ME_RESULT_DTYPE, n)
+            return (res, d_map.download(np.uint32, int(first[-1])), first) if want_map else res
+        finally:
+            d_res.free()
+            if d_map:
+                d_map.free()
+
     def sao_stats(self, orgs, recs, w, h, lcu_based=True):
         """hmx_sao_stats_multi: the encoder's SAO statistics of n pictures (DevPictures, org and deblocked rec) as an int32
         array (n, 3 components, n_lcu, SAO_STAT_BINS, 2): [..., 0] = sum of org - rec, [..., 1] = count; bins as in
@@ -750,6 +804,23 @@ def sao_stats_to_hm(a):
     stats[..., :4, :5], count[..., :4, :5] = eo[..., 0], eo[..., 1]
     stats[..., 4, 1:], count[..., 4, 1:] = a[..., 20:, 0], a[..., 20:, 1]
     return stats, count
+
+
+def mv_bits(x, y, pred_x, pred_y, cost_scale):
+    """hmx_mvBits: TComRdCost::getBits(x, y) with the predictor in quarter samples."""
+    return lib().hmx_mvBits(x, y, pred_x, pred_y, cost_scale)
+
+
+def mv_cost(lambda_, x, y, pred_x, pred_y, cost_scale):
+    """hmx_mvCost: TComRdCost::getCost(x, y) = (lambda * bits) >> 16 in uint32."""
+    return lib().hmx_mvCost(int(lambda_) & 0xFFFFFFFF, x, y, pred_x, pred_y, cost_scale)
+
+
+def set_search_range(pred_x, pred_y, range_, cu_x, cu_y, pic_w, pic_h, ctu_size=64):
+    """hmx_setSearchRange: (left, top, right, bottom) in integer samples, inclusive."""
+    o = [C.c_int() for _ in range(4)]
+    lib().hmx_setSearchRange(pred_x, pred_y, range_, cu_x, cu_y, pic_w, pic_h, ctu_size, *[C.byref(v) for v in o])
+    return tuple(v.value for v in o)
 
 
 def qp_for(qpy, text_type, bit_depth, chroma_qp_offset=0):

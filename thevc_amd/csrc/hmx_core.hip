@@ -131,6 +131,7 @@ extern "C" void hmx_destroy(hmx_ctx *c) {
   if (c->arena_h) hipHostFree(c->arena_h);
   hipFree(c->arena_d);
   hipFree(c->d_mcmap);
+  hipFree(c->d_me_keys);
   hipFree(c->rdoq_wd);
   hipFree(c->rdoq_wi);
   hipFree(c->rdoq_blocks);

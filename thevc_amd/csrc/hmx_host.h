@@ -8,6 +8,7 @@
 //   hmx_chain_rdoq.hip  the packed schedule's kernel with xRateDistOptQuant as its quantiser (a translation unit of its own:
 //                       its instantiations take as long to compile as everything else together)
 //   hmx_inter.hip       interpolation filters, motion compensation, sub-pel cost fan-out, border extension
+//   hmx_me.hip          full-search integer motion estimation (SAD, vector-bits cost, search box)
 //   hmx_loop.hip        deblocking, SAO, YUV file formats
 // and hmx_lib.hip includes all of them for a single-translation-unit build (-DHMX_PACK_PROFILE builds read device
 // symbols of several parts).  Build: __graft_entry__.build() compiles the parts in parallel and links libhmx.so.
@@ -257,6 +258,8 @@ struct hmx_ctx {
   double *rdoq_consts = nullptr; // k_rdoq_tiles: lambda [luma, chroma], then the Int64 factors of sign hiding
   int *d_mcmap = nullptr; // cell -> PU maps of the last motion-compensation call
   size_t mcmap_cap = 0;
+  unsigned long long *d_me_keys = nullptr; // hmx_batch_fullpel_search: one (cost, raster index) word per unit
+  size_t me_keys_cap = 0;
   char *arena_h = nullptr, *arena_d = nullptr;
   size_t arena_cap = 0, arena_head = 0;
   // packed schedule (k_intra_packed): tables of the last call; rebuilt on the device when the pictures / plans change

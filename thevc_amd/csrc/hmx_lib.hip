@@ -11,4 +11,5 @@
 #include "hmx_chain.hip"
 #include "hmx_chain_rdoq.hip"
 #include "hmx_inter.hip"
+#include "hmx_me.hip"
 #include "hmx_loop.hip"

@@ -1,0 +1,266 @@
+// hmx_me.hip: full-search integer motion estimation (TEncSearch::xPatternSearch), SAD, vector-bits cost, search box -- part of libhmx
+// (include/hmx.h), gfx950.  See hmx_host.h for how the library is cut into translation units.
+#include "hmx_host.h"
+
+// =============================================================================================
+// Vector cost (TComRdCost.h:185-211, TComRdCost.cpp:270-284) and search box (TEncSearch.cpp:4209-4225): host helpers
+// =============================================================================================
+// xGetComponentBits in closed form: the halving loop adds 2 per bit of uiTemp above the lowest
+__host__ __device__ __forceinline__ uint32_t me_comp_bits(int v) {
+  const uint32_t t = v <= 0 ? ((uint32_t)(-v) << 1) + 1 : (uint32_t)v << 1;
+#ifdef __HIP_DEVICE_COMPILE__
+  return 2u * (31u - (uint32_t)__clz((int)t)) + 1u;
+#else
+  return 2u * (31u - (uint32_t)__builtin_clz(t)) + 1u;
+#endif
+}
+__host__ __device__ __forceinline__ uint32_t me_mv_bits(int x, int y, int px, int py, int sc) {
+  return me_comp_bits(x * (1 << sc) - px) + me_comp_bits(y * (1 << sc) - py);
+}
+__host__ __device__ __forceinline__ uint32_t me_mv_cost(uint32_t lambda, int x, int y, int px, int py, int sc) {
+  return (lambda * me_mv_bits(x, y, px, py, sc)) >> 16; // UInt product, wraps as the reference's
+}
+extern "C" uint32_t hmx_mvBits(int x, int y, int pred_x, int pred_y, int cost_scale) { return me_mv_bits(x, y, pred_x, pred_y, cost_scale); }
+extern "C" uint32_t hmx_mvCost(uint32_t lambda, int x, int y, int pred_x, int pred_y, int cost_scale) {
+  return me_mv_cost(lambda, x, y, pred_x, pred_y, cost_scale);
+}
+extern "C" void hmx_setSearchRange(int pred_x, int pred_y, int range, int cu_x, int cu_y, int pic_w, int pic_h, int ctu, int *left, int *top,
+                                   int *right, int *bottom) {
+  hmx_clipMv(&pred_x, &pred_y, cu_x, cu_y, pic_w, pic_h, ctu);
+  int lx = pred_x - (range << 2), ty = pred_y - (range << 2), rx = pred_x + (range << 2), by = pred_y + (range << 2);
+  hmx_clipMv(&lx, &ty, cu_x, cu_y, pic_w, pic_h, ctu);
+  hmx_clipMv(&rx, &by, cu_x, cu_y, pic_w, pic_h, ctu);
+  *left = lx >> 2, *top = ty >> 2, *right = rx >> 2, *bottom = by >> 2;
+}
+
+static bool me_size_ok(int v) { return v == 4 || v == 8 || v == 12 || v == 16 || v == 24 || v == 32 || v == 48 || v == 64; }
+
+// =============================================================================================
+// xGetSAD4 .. xGetSAD64 (TComRdCost.cpp:518-..., dispatch :298-329) of ONE block, host pointers
+// =============================================================================================
+__global__ void k_sad(const short *org, const short *cur, int w, int h, int step, unsigned *out) {
+  const int r = (blockIdx.x * blockDim.x + threadIdx.x) * step; // one thread per row that is summed
+  if (r >= h) return;
+  unsigned sum = 0;
+  for (int k = 0; k < w; k++) sum += (unsigned)abs(org[r * w + k] - cur[r * w + k]);
+  atomicAdd(out, sum);
+}
+extern "C" int hmx_getSAD(hmx_ctx *c, const hmx_pel *cur, int cur_stride, const hmx_pel *org, int org_stride, int w, int h, int sub_shift,
+                          uint32_t *sad) {
+  if (!c || !cur || !org || !sad) return fail(c, HMX_ERR_ARG, "hmx_getSAD: null argument");
+  if (!me_size_ok(w) || !me_size_ok(h)) return fail(c, HMX_ERR_ARG, "hmx_getSAD: width and height come from {4, 8, 12, 16, 24, 32, 48, 64}");
+  if (sub_shift < 0 || sub_shift > 1 || (sub_shift && h <= 8)) return fail(c, HMX_ERR_ARG, "hmx_getSAD: sub_shift is 0, or 1 with more than 8 rows");
+  Scratch s{c};
+  short *d_o = s.up(org, w, h, org_stride), *d_c = s.up(cur, w, h, cur_stride);
+  unsigned *d_out = s.take<unsigned>(1);
+  if (s.r) return s.r;
+  HIPCHK(c, hipMemsetAsync(d_out, 0, 4, c->stream));
+  hipLaunchKernelGGL(k_sad, dim3(1), dim3(64), 0, c->stream, d_o, d_c, w, h, 1 << sub_shift, d_out);
+  HIPCHK(c, hipGetLastError());
+  unsigned v = 0;
+  const int r = hmx_download(c, &v, d_out, 4);
+  *sad = (v << sub_shift) >> (c->cfg.bit_depth - 8);
+  return r;
+}
+
+// =============================================================================================
+// xPatternSearch (TEncSearch.cpp:4227-4283) over unit lists
+// =============================================================================================
+// One workgroup (two waves) = one unit and one tile of 32 x 32 candidates of its box.  The unit's original block and the
+// (w + 31) x (h + 31) reference window of the tile are staged in LDS once, both with 2^B added, so that the original --
+// which may be 2 * org - other prediction, negative or above the sample range -- and the reference are unsigned 16-bit values
+// with the differences unchanged: v_sad_u16 then sums two absolute differences and the accumulator per instruction.
+// A lane owns EIGHT candidates of one candidate row: x = 16 * half + p + 2 * j, j = 0..7 (p: parity, half: left or right 16
+// candidates; four lanes a row, sixteen rows a wave).  Per original row it reads its stretch of the window row once with
+// 16-byte LDS reads -- the stretch starts on a dword for every lane -- and brings it to its parity with one v_alignbit per
+// dword (shift 0 or 16), so all eight candidates, whose first samples are whole dwords apart, read their sample pairs from
+// registers: per eight samples one window read, one (broadcast) read of the original and 4 alignbit feed 32 v_sad_u16.
+// Window rows are kMeWinPitch samples = 12 sixteen-byte slots apart: the sixteen lanes of a 16-byte read's lane group
+// (MI355X: four groups of sixteen) then fall on different slots.
+constexpr int kMeTile = 32, kMeWinPitch = 96, kMeWinRows = 64 + kMeTile - 1, kMeThreads = 128;
+struct MeArgs {
+  const hmx_me_unit *units;
+  const uint32_t *tile_first; // [n + 1] prefix of tiles per unit
+  const uint32_t *map_first;  // [n + 1] prefix of box areas (the host refuses a call whose sum does not fit 32 bits)
+  int n;
+  PlanesDev refs[4];
+  PlanesDev org;
+  int B;
+  uint32_t lambda;
+  unsigned long long *keys; // [n]: (cost << 32) | raster index in the box, all ones before the launch
+  uint32_t *cost_map;       // NULL = none
+};
+typedef unsigned u4v __attribute__((ext_vector_type(4)));
+
+template <int W>
+__device__ __forceinline__ void me_rows(const u4v *win, const u4v *org, int h, int step, unsigned sh, unsigned (&acc)[8]) {
+  constexpr int ND = (W / 2 + 8 + 3) / 4 * 4, OD = (W / 2 + 3) / 4 * 4; // dwords read per window row / original row
+  for (int r = 0; r < h; r += step) {
+    unsigned d[ND], o[OD];
+#pragma unroll
+    for (int k = 0; k < ND / 4; k++) {
+      const u4v v = win[r * (kMeWinPitch / 8) + k];
+      d[4 * k] = v.x, d[4 * k + 1] = v.y, d[4 * k + 2] = v.z, d[4 * k + 3] = v.w;
+    }
+#pragma unroll
+    for (int k = 0; k < OD / 4; k++) {
+      const u4v v = org[r * (OD / 4) + k];
+      o[4 * k] = v.x, o[4 * k + 1] = v.y, o[4 * k + 2] = v.z, o[4 * k + 3] = v.w;
+    }
+    unsigned e[W / 2 + 7];
+#pragma unroll
+    for (int i = 0; i < W / 2 + 7; i++) e[i] = __builtin_amdgcn_alignbit(d[i + 1], d[i], sh);
+#pragma unroll
+    for (int i = 0; i < W / 2; i++)
+#pragma unroll
+      for (int j = 0; j < 8; j++) acc[j] = __builtin_amdgcn_sad_u16(e[i + j], o[i], acc[j]);
+  }
+}
+
+__global__ __launch_bounds__(kMeThreads) void k_me_search(MeArgs A) {
+  __shared__ __attribute__((aligned(16))) unsigned short s_win[kMeWinRows * kMeWinPitch];
+  __shared__ __attribute__((aligned(16))) unsigned short s_org[64 * 64];
+  __shared__ unsigned long long s_key[kMeThreads / 64];
+  const uint32_t wg = blockIdx.x;
+  int lo = 0, hi = A.n; // the unit this tile belongs to
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (A.tile_first[mid] <= wg) lo = mid;
+    else hi = mid;
+  }
+  const hmx_me_unit u = A.units[lo];
+  const int w = u.w, h = u.h, bw = u.right - u.left + 1, bh = u.bottom - u.top + 1, tiles_x = (bw + kMeTile - 1) / kMeTile;
+  const int t = (int)(wg - A.tile_first[lo]), tx0 = (t % tiles_x) * kMeTile, ty0 = (t / tiles_x) * kMeTile;
+  const int nx = min(kMeTile, bw - tx0), ny = min(kMeTile, bh - ty0); // candidates of this tile
+  const int tid = threadIdx.x, bias = 1 << A.B;
+  typedef __attribute__((address_space(1))) const short gpel;
+  { // the window: rows and columns no candidate of the tile reaches are zero and never read from memory
+    const PlanesDev &R = A.refs[u.ref < 4 ? u.ref : 0];
+    const gpel *src = (const gpel *)R.p[0] + (ptrdiff_t)(u.y + u.top + ty0) * R.s[0] + (u.x + u.left + tx0);
+    const int vx = nx + w - 1, vy = ny + h - 1, cols = min(kMeWinPitch, w + 40), rows = h + kMeTile - 1;
+    for (int wy = tid >> 5; wy < rows; wy += kMeThreads / 32)
+      for (int wx = tid & 31; wx < cols; wx += 32)
+        s_win[wy * kMeWinPitch + wx] = (wx < vx && wy < vy) ? (unsigned short)(src[(ptrdiff_t)wy * R.s[0] + wx] + bias) : (unsigned short)0;
+  }
+  const int op = ((w / 2 + 3) / 4 * 4) * 2; // samples per staged original row
+  {
+    const gpel *src = (const gpel *)A.org.p[0] + (size_t)u.y * A.org.s[0] + u.x;
+    for (int ry = tid >> 5; ry < h; ry += kMeThreads / 32)
+      for (int rx = tid & 31; rx < op; rx += 32) s_org[ry * op + rx] = rx < w ? (unsigned short)(src[(size_t)ry * A.org.s[0] + rx] + bias) : (unsigned short)0;
+  }
+  __syncthreads();
+  const int row = tid >> 2, half = (tid >> 1) & 1, p = tid & 1;
+  unsigned acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  const u4v *win = reinterpret_cast<const u4v *>(s_win + row * kMeWinPitch + 16 * half), *org = reinterpret_cast<const u4v *>(s_org);
+  const int step = 1 << u.sub_shift;
+  const unsigned sh = p ? 16u : 0u;
+  // a wave holds sixteen candidate rows: one whose rows all lie below the tile's last candidate row (the fifth tile row of a 129-high
+  // box has one, a +-1 box three) sums nothing -- uniform over the wave; its lanes keep acc = 0 and are masked out below
+  if ((tid >> 6) * 16 < ny) {
+    switch (w) { // uniform over the workgroup
+    case 4: me_rows<4>(win, org, h, step, sh, acc); break;
+    case 8: me_rows<8>(win, org, h, step, sh, acc); break;
+    case 12: me_rows<12>(win, org, h, step, sh, acc); break;
+    case 16: me_rows<16>(win, org, h, step, sh, acc); break;
+    case 24: me_rows<24>(win, org, h, step, sh, acc); break;
+    case 32: me_rows<32>(win, org, h, step, sh, acc); break;
+    case 48: me_rows<48>(win, org, h, step, sh, acc); break;
+    default: me_rows<64>(win, org, h, step, sh, acc); break;
+    }
+  }
+  // cost = SAD + getCost(x, y) at cost scale 2 (TEncSearch.cpp:4172, :4268); first minimum in raster order = minimum of
+  // (cost, raster index)
+  unsigned long long best = ~0ull;
+  typedef __attribute__((address_space(1))) uint32_t gu32;
+  gu32 *map = A.cost_map ? (gu32 *)A.cost_map + A.map_first[lo] : nullptr;
+#pragma unroll
+  for (int j = 0; j < 8; j++) {
+    const int cx = 16 * half + p + 2 * j;
+    if (cx < nx && row < ny) {
+      const int bx = tx0 + cx, by = ty0 + row;
+      const uint32_t sad = (acc[j] << u.sub_shift) >> (A.B - 8);
+      const uint32_t cost = sad + me_mv_cost(A.lambda, u.left + bx, u.top + by, u.pred_x, u.pred_y, 2);
+      const uint32_t idx = (uint32_t)(by * bw + bx);
+      if (map) map[idx] = cost;
+      const unsigned long long key = ((unsigned long long)cost << 32) | idx;
+      best = key < best ? key : best;
+    }
+  }
+#pragma unroll
+  for (int m = 1; m < 64; m <<= 1) {
+    const unsigned long long other = __shfl_xor(best, m, 64);
+    best = other < best ? other : best;
+  }
+  if ((tid & 63) == 0) s_key[tid >> 6] = best;
+  __syncthreads();
+  if (tid == 0) atomicMin(&A.keys[lo], s_key[1] < s_key[0] ? s_key[1] : s_key[0]);
+}
+
+__global__ void k_me_unpack(const hmx_me_unit *units, const unsigned long long *keys, int n, uint32_t lambda, hmx_me_result *out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const hmx_me_unit u = units[i];
+  const unsigned long long key = keys[i];
+  const int bw = u.right - u.left + 1, idx = (int)(uint32_t)key;
+  const int x = u.left + idx % bw, y = u.top + idx / bw;
+  const uint32_t cost = (uint32_t)(key >> 32);
+  hmx_me_result r;
+  r.mvx = (int16_t)x, r.mvy = (int16_t)y;
+  r.cost = cost;
+  r.sad = cost - me_mv_cost(lambda, x, y, u.pred_x, u.pred_y, 2); // ruiSAD (:4281)
+  out[i] = r;
+}
+
+extern "C" int hmx_batch_fullpel_search(hmx_ctx *c, const hmx_me_unit *units, int n, const hmx_pic *refs, int n_refs, const hmx_pic *org, int pic_w,
+                                        int pic_h, int margin_x, int margin_y, uint32_t lambda, hmx_me_result *d_result, uint32_t *d_cost_map) {
+  if (!c || !units || !refs || !org || !d_result) return fail(c, HMX_ERR_ARG, "hmx_batch_fullpel_search: null argument");
+  if (n <= 0) return fail(c, HMX_ERR_ARG, "hmx_batch_fullpel_search: n must be at least 1");
+  if (n_refs <= 0 || n_refs > 4) return fail(c, HMX_ERR_ARG, "hmx_batch_fullpel_search: n_refs must be 1 .. 4");
+  if (pic_w <= 0 || pic_h <= 0 || margin_x < 0 || margin_y < 0)
+    return fail(c, HMX_ERR_ARG, "hmx_batch_fullpel_search: picture size must be positive and margins not negative");
+  if (!org->plane[0]) return fail(c, HMX_ERR_ARG, "hmx_batch_fullpel_search: the original has no luma plane");
+  for (int r = 0; r < n_refs; r++)
+    if (!refs[r].plane[0]) return fail(c, HMX_ERR_ARG, "hmx_batch_fullpel_search: a reference has no luma plane");
+  std::vector<uint32_t> tile_first((size_t)n + 1, 0), map_first((size_t)n + 1, 0);
+  uint64_t area = 0; // the kernel's offsets into the cost map are 32-bit
+  for (int i = 0; i < n; i++) {
+    const hmx_me_unit &u = units[i];
+    const std::string at = "hmx_batch_fullpel_search: unit " + std::to_string(i) + ": ";
+    if (!me_size_ok(u.w) || !me_size_ok(u.h)) return fail(c, HMX_ERR_ARG, at + "width and height come from {4, 8, 12, 16, 24, 32, 48, 64}");
+    if (u.ref >= n_refs) return fail(c, HMX_ERR_ARG, at + "reference index outside refs[]");
+    if (u.sub_shift > 1 || (u.sub_shift && u.h <= 8)) return fail(c, HMX_ERR_ARG, at + "sub_shift is 0, or 1 with more than 8 rows");
+    if (u.right < u.left || u.bottom < u.top) return fail(c, HMX_ERR_ARG, at + "empty search box");
+    const int bw = u.right - u.left + 1, bh = u.bottom - u.top + 1;
+    if (bw > 129 || bh > 129) return fail(c, HMX_ERR_ARG, at + "search box side above 129 (search range 64)");
+    if (u.x + u.w > pic_w || u.y + u.h > pic_h) return fail(c, HMX_ERR_ARG, at + "the unit lies outside the picture");
+    if (u.x + u.left < -margin_x || u.x + u.right + u.w > pic_w + margin_x || u.y + u.top < -margin_y || u.y + u.bottom + u.h > pic_h + margin_y)
+      return fail(c, HMX_ERR_ARG, at + "a candidate block reaches outside the reference's margins");
+    tile_first[i + 1] = tile_first[i] + (uint32_t)(((bw + kMeTile - 1) / kMeTile) * ((bh + kMeTile - 1) / kMeTile));
+    map_first[i + 1] = map_first[i] + (uint32_t)(bw * bh);
+    area += (uint64_t)(bw * bh);
+  }
+  if (area > 0xffffffffull) return fail(c, HMX_ERR_ARG, "hmx_batch_fullpel_search: the boxes hold more than 2^32 - 1 candidates: split the call");
+  void *keys = c->d_me_keys;
+  const int gr = grow_dev(c, &keys, &c->me_keys_cap, sizeof(unsigned long long) * (size_t)n);
+  c->d_me_keys = static_cast<unsigned long long *>(keys);
+  if (gr) return gr;
+  MeArgs A{};
+  const size_t prefix_bytes = sizeof(uint32_t) * ((size_t)n + 1);
+  // unit list and prefixes through the argument arena (the caller's host array, and tables made from it)
+  A.units = static_cast<const hmx_me_unit *>(arena_push(c, units, sizeof(hmx_me_unit) * (size_t)n));
+  A.tile_first = static_cast<const uint32_t *>(arena_push(c, tile_first.data(), prefix_bytes));
+  A.map_first = static_cast<const uint32_t *>(arena_push(c, map_first.data(), prefix_bytes));
+  if (!A.units || !A.tile_first || !A.map_first) return fail(c, HMX_ERR_NOMEM, "argument arena (unit list too long: split the call)");
+  A.n = n;
+  for (int r = 0; r < n_refs; r++) A.refs[r] = to_dev(&refs[r]);
+  A.org = to_dev(org);
+  A.B = c->cfg.bit_depth;
+  A.lambda = lambda;
+  A.keys = c->d_me_keys;
+  A.cost_map = d_cost_map;
+  HIPCHK(c, hipMemsetAsync(c->d_me_keys, 0xff, sizeof(unsigned long long) * (size_t)n, c->stream));
+  hipLaunchKernelGGL(k_me_search, dim3(tile_first[n]), dim3(kMeThreads), 0, c->stream, A);
+  hipLaunchKernelGGL(k_me_unpack, dim3((n + 255) / 256), dim3(256), 0, c->stream, A.units, (const unsigned long long *)c->d_me_keys, n, lambda, d_result);
+  HIPCHK(c, hipGetLastError());
+  return HMX_OK;
+}

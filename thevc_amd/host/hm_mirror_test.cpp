@@ -93,7 +93,59 @@ static int wp_main(int argc, char **argv) {
   return 0;
 }
 
+// Usage: hm_mirror_test me <bitDepth> <seed>: the integer stage of xMotionEstimation for one 16x16 unit of a 64x64 picture
+// (margin 24): setLambda, xSetSearchRange (range 6), getMotionCost(1, 0), setPredictor, setCostScale(2), xPatternSearch.
+// Prints the unit as hmx_me_unit fields with the cost multiplier and the geometry, the original plane, the reference plane
+// with its margins, and "mvx mvy sad", one line each.
+static int me_main(int argc, char **argv) {
+  if (argc < 4) return 2;
+  const int B = atoi(argv[2]), W = 64, H = 64, M = 24, S = W + 2 * M;
+  unsigned seed = (unsigned)atoi(argv[3]);
+  const bool fastEnc = (seed & 1) != 0; // getUseFastEnc(): rows > 8 are sub-sampled
+  auto next = [&]() { return (seed = seed * 1664525u + 1013904223u) >> 8; };
+  hmx_hm::Context ctx(B);
+  hmx_hm::TComRdCost rd(ctx);
+  hmx_hm::TEncSearch search(ctx, rd, {W, H, M, M, 64}, fastEnc);
+  std::vector<short> org(W * H), ref(S * (H + 2 * M));
+  for (auto &v : org) v = (short)(next() % (1u << B));
+  for (auto &v : ref) v = (short)(next() % (1u << B));
+  short *d_org = nullptr, *d_ref = nullptr;
+  ctx.check(hmx_malloc(ctx.get(), org.size() * 2, (void **)&d_org), "malloc");
+  ctx.check(hmx_malloc(ctx.get(), ref.size() * 2, (void **)&d_ref), "malloc");
+  ctx.check(hmx_upload(ctx.get(), d_org, org.data(), org.size() * 2), "upload");
+  ctx.check(hmx_upload(ctx.get(), d_ref, ref.data(), ref.size() * 2), "upload");
+  hmx_pic po{}, pr{};
+  po.plane[0] = d_org, po.stride[0] = W;
+  pr.plane[0] = d_ref + M * S + M, pr.stride[0] = S;
+  const int x = 24, y = 16, w = 16, h = 16, predHor = (int)(next() % 41) - 20, predVer = (int)(next() % 41) - 20;
+  rd.setLambda(20.0 + next() % 40);
+  int lt[2], rb[2], mv[2];
+  search.xSetSearchRange(x, y, predHor, predVer, 6, lt, rb);
+  rd.getMotionCost(true, 0);
+  rd.setPredictor(predHor, predVer);
+  rd.setCostScale(2);
+  hmx_hm::UInt sad = 0;
+  search.xPatternSearch(&po, &pr, x, y, w, h, lt, rb, mv, sad);
+  printf("%d %d %d %d %d %d %d %d %d %d %d %u %d %d %d\n", x, y, w, h, fastEnc ? 1 : 0, predHor, predVer, lt[0], lt[1], rb[0], rb[1],
+         rd.motionCostMultiplier(), W, H, M);
+  for (int v : org) printf("%d ", v);
+  printf("\n");
+  for (int v : ref) printf("%d ", v);
+  printf("\n%d %d %u\n", mv[0], mv[1], sad);
+  hmx_free(ctx.get(), d_org);
+  hmx_free(ctx.get(), d_ref);
+  return 0;
+}
+
 int main(int argc, char **argv) {
+  if (argc >= 2 && std::string(argv[1]) == "me") {
+    try {
+      return me_main(argc, argv);
+    } catch (const std::exception &e) {
+      fprintf(stderr, "error: %s\n", e.what());
+      return 1;
+    }
+  }
   if (argc >= 2 && std::string(argv[1]) == "wp") {
     try {
       return wp_main(argc, argv);

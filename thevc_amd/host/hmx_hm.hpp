@@ -6,6 +6,7 @@
 // explicit state here (setBlockState(), the context).  Every call goes to libhmx (HIP); nothing is
 // computed on the host.  Errors: the reference returns Void and asserts; these wrappers throw.
 #pragma once
+#include <cmath>
 #include <stdexcept>
 #include <string>
 
@@ -284,10 +285,31 @@ private:
   Context &m_c;
 };
 
-// TComRdCost, the two distortion entry points next to the path (TComRdCost.cpp:404-478)
+// TComRdCost: the two distortion entry points next to the path (TComRdCost.cpp:404-478), SAD, and the motion-vector cost the
+// searches add to a distortion (TComRdCost.h:183-211; TComMv is a pair of Int here)
 class TComRdCost {
 public:
   explicit TComRdCost(Context &c) : m_c(c) {}
+  // setLambda (TComRdCost.cpp:167-173), the two integer multipliers only
+  void setLambda(Double dLambda) {
+    m_uiLambdaMotionSAD = (UInt)std::floor(65536.0 * std::sqrt(dLambda));
+    m_uiLambdaMotionSSE = (UInt)std::floor(65536.0 * dLambda);
+  }
+  void getMotionCost(Bool bSad, Int iAdd) { m_uiCost = (bSad ? m_uiLambdaMotionSAD + iAdd : m_uiLambdaMotionSSE + iAdd); }
+  void setPredictor(Int iHor, Int iVer) { m_iPredHor = iHor, m_iPredVer = iVer; } // quarter samples
+  void setCostScale(Int iCostScale) { m_iCostScale = iCostScale; }
+  UInt getCost(Int x, Int y) const { return hmx_mvCost(m_uiCost, x, y, m_iPredHor, m_iPredVer, m_iCostScale); }
+  UInt getCost(UInt b) const { return (m_uiCost * b) >> 16; }
+  UInt getBits(Int x, Int y) const { return hmx_mvBits(x, y, m_iPredHor, m_iPredVer, m_iCostScale); }
+  UInt motionCostMultiplier() const { return m_uiCost; }
+  Int predictorHor() const { return m_iPredHor; }
+  Int predictorVer() const { return m_iPredVer; }
+  // xGetSAD4..64 with DistParam::iSubShift (TComRdCost.cpp:518-...), bApplyWeight false
+  UInt getSAD(Pel *piOrg, Int iStrideOrg, Pel *piCur, Int iStrideCur, Int iCols, Int iRows, Int iSubShift = 0) {
+    uint32_t v = 0;
+    m_c.check(hmx_getSAD(m_c.get(), piCur, iStrideCur, piOrg, iStrideOrg, iCols, iRows, iSubShift, &v), "xGetSAD");
+    return v;
+  }
   UInt calcHAD(Pel *pi0, Int iStride0, Pel *pi1, Int iStride1, Int iWidth, Int iHeight) {
     uint32_t v = 0;
     m_c.check(hmx_calcHAD(m_c.get(), pi0, iStride0, pi1, iStride1, iWidth, iHeight, &v), "calcHAD");
@@ -302,6 +324,55 @@ public:
 
 private:
   Context &m_c;
+  UInt m_uiLambdaMotionSAD = 0, m_uiLambdaMotionSSE = 0, m_uiCost = 0;
+  Int m_iPredHor = 0, m_iPredVer = 0, m_iCostScale = 0;
+};
+
+// TEncSearch, the integer stage of xMotionEstimation (TEncSearch.cpp:4120-4283) for ONE unit over hmx_batch_fullpel_search.
+// What the reference reads through pcCU, the pattern key and the slice is explicit: the unit's position and size, the
+// pictures (DEVICE pictures: the original, and the reference with its margins) and their geometry.
+class TEncSearch {
+public:
+  struct Geometry {
+    Int picWidth, picHeight, marginX, marginY, ctuSize;
+  };
+  TEncSearch(Context &c, TComRdCost &rd, const Geometry &g, Bool useFastEnc = false) : m_c(c), m_rd(rd), m_g(g), m_fastEnc(useFastEnc) {
+    m_c.check(hmx_malloc(m_c.get(), sizeof(hmx_me_result), (void **)&m_dResult), "TEncSearch");
+  }
+  ~TEncSearch() { hmx_free(m_c.get(), m_dResult); }
+  TEncSearch(const TEncSearch &) = delete;
+  TEncSearch &operator=(const TEncSearch &) = delete;
+  // xSetSearchRange (:4209-4225): cMvPred in quarter samples, the corners in integer samples
+  void xSetSearchRange(Int cuX, Int cuY, Int mvPredHor, Int mvPredVer, Int iSrchRng, Int rcMvSrchRngLT[2], Int rcMvSrchRngRB[2]) const {
+    hmx_setSearchRange(mvPredHor, mvPredVer, iSrchRng, cuX, cuY, m_g.picWidth, m_g.picHeight, m_g.ctuSize, &rcMvSrchRngLT[0], &rcMvSrchRngLT[1],
+                       &rcMvSrchRngRB[0], &rcMvSrchRngRB[1]);
+  }
+  // xPatternSearch (:4227-4283): the unit (x, y, iRoiWidth, iRoiHeight) of pcOrg against pcRef inside the box; rcMv (integer
+  // samples) and ruiSAD as the reference leaves them.  The vector cost is the one m_pcRdCost holds: the caller has run
+  // getMotionCost(1, 0), setPredictor and setCostScale(2) as xMotionEstimation does (:4169-4172).
+  void xPatternSearch(const hmx_pic *pcOrg, const hmx_pic *pcRef, Int x, Int y, Int iRoiWidth, Int iRoiHeight, const Int pcMvSrchRngLT[2],
+                      const Int pcMvSrchRngRB[2], Int rcMv[2], UInt &ruiSAD) {
+    hmx_me_unit u{};
+    u.x = (uint16_t)x, u.y = (uint16_t)y, u.w = (uint8_t)iRoiWidth, u.h = (uint8_t)iRoiHeight;
+    u.ref = 0;
+    u.sub_shift = (m_fastEnc && iRoiHeight > 8) ? 1 : 0; // :4245-4251
+    u.pred_x = (int16_t)m_rd.predictorHor(), u.pred_y = (int16_t)m_rd.predictorVer();
+    u.left = (int16_t)pcMvSrchRngLT[0], u.top = (int16_t)pcMvSrchRngLT[1], u.right = (int16_t)pcMvSrchRngRB[0], u.bottom = (int16_t)pcMvSrchRngRB[1];
+    m_c.check(hmx_batch_fullpel_search(m_c.get(), &u, 1, pcRef, 1, pcOrg, m_g.picWidth, m_g.picHeight, m_g.marginX, m_g.marginY,
+                                       m_rd.motionCostMultiplier(), m_dResult, nullptr),
+              "xPatternSearch");
+    hmx_me_result r;
+    m_c.check(hmx_download(m_c.get(), &r, m_dResult, sizeof(r)), "xPatternSearch");
+    rcMv[0] = r.mvx, rcMv[1] = r.mvy;
+    ruiSAD = r.sad;
+  }
+
+private:
+  Context &m_c;
+  TComRdCost &m_rd;
+  Geometry m_g;
+  Bool m_fastEnc;
+  hmx_me_result *m_dResult = nullptr;
 };
 
 // TComInterpolationFilter (TComInterpolationFilter.cpp:323-415): identical signatures

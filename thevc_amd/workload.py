@@ -159,6 +159,29 @@ def make_pus(seed, pic_w, pic_h, n_refs=1, bi_frac=0.0, mv_range=64, ctu=64):
     return pus
 
 
+def make_me_units(seed, w, h, n_refs, range_, ctu=64):
+    """Units for hmx_batch_fullpel_search covering the picture: every CTU is cut into one random PU shape as in make_pus
+    (clipped sizes outside the motion-search set {4, 8, 12, 16, 24, 32, 48, 64} are dropped), each with a random predictor
+    (quarter samples, up to +-range_ integer samples), the box xSetSearchRange gives it (capi.set_search_range, the unit's
+    origin as CU origin) and sub_shift 1 for about half of the units taller than 8 rows."""
+    from . import capi
+    rng = np.random.default_rng([seed, 1])  # a stream of its own beside the one make_pus draws from
+    pus = make_pus(seed, w, h, n_refs=n_refs, mv_range=range_, ctu=ctu)
+    ok = np.isin(pus["w"], (4, 8, 12, 16, 24, 32, 48, 64)) & np.isin(pus["h"], (4, 8, 12, 16, 24, 32, 48, 64))
+    pus = pus[ok]
+    n = len(pus)
+    u = np.zeros(n, capi.ME_UNIT_DTYPE)
+    for k in ("x", "y", "w", "h"):
+        u[k] = pus[k]
+    u["ref"] = pus["ref0"]
+    u["sub_shift"] = (pus["h"] > 8) & (rng.random(n) < 0.5)
+    u["pred_x"], u["pred_y"] = pus["mv0x"], pus["mv0y"]
+    for i in range(n):
+        u[i]["left"], u[i]["top"], u[i]["right"], u[i]["bottom"] = capi.set_search_range(int(u[i]["pred_x"]), int(u[i]["pred_y"]), range_, int(u[i]["x"]),
+                                                                                         int(u[i]["y"]), w, h, ctu)
+    return u
+
+
 # --- what RDOQ takes from the encoder's live state (hmx_set_rdoq), synthesised --------------------------------------
 def make_est_bits(seed):
     """A plausible bit-estimate table (estBitsSbacStruct): every context holds a probability p of the bin being 1,
