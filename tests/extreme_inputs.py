@@ -184,3 +184,219 @@ def search_sbh_on_clip(rng, N, B, n_want=3, max_tries=600):
             if len(found) >= n_want:
                 break
     return found
+
+
+# ================================================================================================================================
+# The sample domain: inter prediction, the loop filters, the SAO statistics and the motion search at the range ends
+# ================================================================================================================================
+
+# m_lumaFilter / m_chromaFilter (TComInterpolationFilter.cpp:51-69); row 0 is the zero fraction written as a filter, {.., 64, ..}
+LUMA_TAPS = ((0, 0, 0, 64, 0, 0, 0, 0), (-1, 4, -10, 58, 17, -5, 1, 0), (-1, 4, -11, 40, 40, -11, 4, -1), (0, 1, -5, 17, 58, -10, 4, -1))
+CHROMA_TAPS = ((0, 64, 0, 0), (-2, 58, 10, -2), (-4, 54, 16, -2), (-6, 46, 28, -4), (-4, 36, 36, -4), (-4, 28, 46, -6), (-2, 16, 54, -4),
+               (-2, 10, 58, -2))
+PLANE_KINDS = ("zero", "max", "binary", "border")
+
+
+def extreme_plane(rng, w, h, B, kind):
+    """A plane at the range ends.  zero / max: constant 0 / 2^B - 1 (every filter output equals the input: the clip is met from
+    inside); binary: every sample 0 or 2^B - 1 (the filters over- and undershoot wherever the signs of the taps line up with
+    the samples); border: binary noise with one-sample-wide rows and columns of 2^B - 1 at the picture border, so that the
+    margins that hmx_pic_extend_border makes are whole bands of the maximum next to noise."""
+    mx = (1 << B) - 1
+    if kind in ("zero", "max"):
+        return np.full((h, w), mx if kind == "max" else 0, np.int16)
+    p = (rng.integers(0, 2, (h, w)) * mx).astype(np.int16)
+    if kind == "border":
+        p[0, :] = p[-1, :] = p[:, 0] = p[:, -1] = mx
+    return p
+
+
+def overshoot_plane(rng, w, h, B, taps_x, taps_y, sign):
+    """A plane of binary noise in which, around a lattice of output positions, the sample under tap (i, j) is 2^B - 1 where
+    sign * taps_x[i] * taps_y[j] > 0 and 0 elsewhere: at those positions the separable filter gives its largest (sign = +1) or
+    smallest (sign = -1) value -- 88 * maxv and -24 * maxv for the luma half-sample filter in one dimension, beyond the range
+    after the shift, so that the final clip binds; and the one-dimensional intermediate of the first stage is at its
+    closed-form extreme on the rows (columns) that a {.., 64, ..} filter of the other direction selects.  The lattice step is
+    odd, so positions of both parities occur.  Returns (plane, [(x, y), ...])."""
+    mx = (1 << B) - 1
+    tx, ty = np.asarray(taps_x, np.int64), np.asarray(taps_y, np.int64)
+    nx, ny = len(tx), len(ty)
+    p = extreme_plane(rng, w, h, B, "binary")
+    pat = np.where(sign * np.outer(ty, tx) > 0, mx, 0).astype(np.int16)
+    pos = []
+    for y in range(ny // 2 - 1, h - ny // 2, ny + 3):
+        for x in range(nx // 2 - 1, w - nx // 2, nx + 3):
+            p[y - (ny // 2 - 1):y + ny // 2 + 1, x - (nx // 2 - 1):x + nx // 2 + 1] = pat
+            pos.append((x, y))
+    return p, pos
+
+
+def interp_unclipped(plane, mvx, mvy, w, h, B, chroma, x0=0, y0=0):
+    """The reference's two-stage interpolation (TComInterpolationFilter::filter, TComPrediction::xPredInterLumaBlk /
+    xPredInterChromaBlk) in int64 with neither the narrowing to 16 bits nor the final clip; a zero fraction is the filter
+    {.., 64, ..}, which gives what the reference's one-stage and copy cases give.  plane: 2-D, margins included; (x0, y0): the
+    block's first sample in it, in this plane's units; (w, h): the block in this plane's units; mv in quarter (luma) or eighth
+    (chroma) samples.  Returns (final, mid): final = the uni-predicted output before Clip(0, maxv); mid = the first stage's
+    intermediates for the h + taps - 1 rows the second stage reads.  ONLY for counting how often an edge is reached."""
+    taps = CHROMA_TAPS if chroma else LUMA_TAPS
+    fb = 3 if chroma else 2
+    n = len(taps[0])
+    tx, ty = np.asarray(taps[mvx & ((1 << fb) - 1)], np.int64), np.asarray(taps[mvy & ((1 << fb) - 1)], np.int64)
+    X, Y = x0 + (mvx >> fb) - (n // 2 - 1), y0 + (mvy >> fb) - (n // 2 - 1)
+    win = np.asarray(plane, np.int64)[Y:Y + h + n - 1, X:X + w + n - 1]
+    assert win.shape == (h + n - 1, w + n - 1), "the window leaves the plane"
+    head = 14 - B
+    s1 = sum(int(tx[i]) * win[:, i:i + w] for i in range(n))
+    mid = (s1 >> (6 - head)) - 8192  # isFirst, not isLast: shift 6 - headroom, offset -IF_INTERNAL_OFFS << shift
+    s2 = sum(int(ty[j]) * mid[j:j + h, :] for j in range(n))
+    final = (s2 + (1 << (5 + head)) + (8192 << 6)) >> (6 + head)  # not isFirst, isLast
+    return final, mid
+
+
+def count_outside(v, B):
+    """(values below 0, values above 2^B - 1)"""
+    v = np.asarray(v)
+    return int((v < 0).sum()), int((v > (1 << B) - 1).sum())
+
+
+def mid_extremes(taps, B):
+    """The closed-form extremes of the one-dimensional 14-bit intermediate on samples 0..maxv: (min, max)."""
+    mx, t = (1 << B) - 1, np.asarray(taps, np.int64)
+    return (int(t[t < 0].sum()) * mx >> (B - 8)) - 8192, (int(t[t > 0].sum()) * mx >> (B - 8)) - 8192
+
+
+# ---- deblocking ----------------------------------------------------------------------------------------------------------------
+
+DBK_TC = (0,) * 18 + (1,) * 9 + (2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 5, 5, 6, 6, 7, 8, 9, 10, 11, 13, 14, 16, 18, 20, 22, 24)  # sm_tcTable
+DBK_BETA = (0,) * 16 + tuple(range(6, 19)) + tuple(range(20, 66, 2))  # sm_betaTable
+CHROMA_QP = tuple(range(30)) + (29, 30, 31, 32, 33, 33, 34, 34, 35, 35, 36, 36, 37) + tuple(range(37, 46))  # g_aucChromaScale
+
+
+def _edge_plane(rng, w, h, B, region):
+    """8x8 blocks within a few tc of 0 or of 2^B - 1 (the same end over region x region samples, the ends in a checkerboard, so
+    that the steps between the blocks of a region stay below the decision thresholds): flat blocks and blocks with a short linear ramp that leaves the range end from one of
+    their four sides.  Flat beside a ramp: the second differences are 0, so d < beta holds, while the weak filter's delta
+    (or the chroma delta) carries the sample next to the edge beyond the range end."""
+    mx, sc = (1 << B) - 1, 1 << (B - 8)
+    p = np.zeros((-(-h // 8) * 8, -(-w // 8) * 8), np.int64)
+    c = np.arange(8)
+    for by in range(0, p.shape[0], 8):
+        for bx in range(0, p.shape[1], 8):
+            a = int(rng.integers(0, 3)) * sc + int(rng.integers(0, sc))
+            kind, slope = int(rng.integers(0, 7)), int(rng.integers(2, 15)) * sc
+            ramp = (c, 7 - c)[kind & 1] * slope
+            blk = a + (ramp[None, :] if kind < 2 else ramp[:, None] if kind < 4 else np.zeros((8, 8), np.int64))
+            p[by:by + 8, bx:bx + 8] = blk + rng.integers(0, 2, (8, 8)) * (rng.random() < 0.15)
+    hi = ((np.arange(p.shape[0])[:, None] // region + np.arange(p.shape[1])[None, :] // region) & 1) == 1
+    return np.clip(np.where(hi, mx - p, p), 0, mx)[:h, :w].astype(np.int16)
+
+
+def dbk_edge_content(rng, w, h, B):
+    """A picture and maps for the deblocking filter at the range ends, in the layout of tests/test_gpu_loop_multi.py::dbk_inputs:
+    planes as _edge_plane makes them (chroma likewise, on its own 8x8 grid), strengths 0 / 1 / 2 with 2 the most frequent (chroma
+    is filtered at strength 2 only), a QP per 8x8 over the whole range 0..51, so that tc = 0 and beta = 0 stand next to
+    active edges, and a no-filter map."""
+    uw, uh = w // 4, h // 4
+    planes = [_edge_plane(rng, w, h, B, 32), _edge_plane(rng, w // 2, h // 2, B, 16), _edge_plane(rng, w // 2, h // 2, B, 16)]
+    strength = lambda: np.minimum(rng.integers(0, 6, (uh, uw)), 2).astype(np.uint8)
+    bsv, bsh = strength(), strength()
+    bsv[:, 0] = 0
+    bsh[0, :] = 0
+    c2 = lambda n: -(-n // 2)
+    qp = rng.integers(0, 52, (c2(uh), c2(uw)))
+    qp = np.where(rng.random(qp.shape) < 0.6, rng.integers(38, 52, qp.shape), qp)  # most of them where tc is large
+    qp = qp.repeat(2, 0).repeat(2, 1)[:uh, :uw].astype(np.int8)
+    nof = (rng.random((c2(uh), c2(uw))) < 0.08).repeat(2, 0).repeat(2, 1)[:uh, :uw].astype(np.uint8)
+    return dict(planes=planes, bsv=np.ascontiguousarray(bsv), bsh=np.ascontiguousarray(bsh), qp=np.ascontiguousarray(qp), nof=np.ascontiguousarray(nof))
+
+
+def dbk_count_outside(d, w, h, B, use_nof, boff, toff):
+    """The vertical edges of a picture (they are filtered first, on the input, and do not reach each other), restated from
+    TComLoopFilter.cpp:571-922: per line that the WEAK luma filter or the chroma filter changes, whether m3 + delta or m4 - delta
+    before Clip(0, maxv) lies outside the range.  Returns dict(luma=(below, above), chroma=(below, above)) in lines."""
+    mx, sc, uw = (1 << B) - 1, 1 << (B - 8), w // 4
+    Y, bs, qp, nof = d["planes"][0].astype(np.int64), d["bsv"], d["qp"].astype(np.int64), d["nof"] if use_nof else np.zeros_like(d["nof"])
+    lo = dict(luma=0, chroma=0)
+    hi = dict(luma=0, chroma=0)
+
+    def tally(key, vals):
+        lo[key] += any(v < 0 for v in vals)
+        hi[key] += any(v > mx for v in vals)
+
+    for uy in range(h // 4):
+        for ux in range(2, uw, 2):
+            b = int(bs[uy, ux])
+            if not b:
+                continue
+            qa = int(qp[uy, ux - 1] + qp[uy, ux] + 1) >> 1
+            pn, qn = int(nof[uy, ux - 1]), int(nof[uy, ux])
+            tc = DBK_TC[min(53, max(0, qa + 2 * (b - 1) + 2 * toff))] * sc
+            beta = DBK_BETA[min(51, max(0, qa + 2 * boff))] * sc
+            m = Y[4 * uy:4 * uy + 4, 4 * ux - 4:4 * ux + 4]  # m[l][0..7] = P3..P0, Q0..Q3
+            dp0, dq0 = abs(m[0, 1] - 2 * m[0, 2] + m[0, 3]), abs(m[0, 4] - 2 * m[0, 5] + m[0, 6])
+            dp3, dq3 = abs(m[3, 1] - 2 * m[3, 2] + m[3, 3]), abs(m[3, 4] - 2 * m[3, 5] + m[3, 6])
+            if dp0 + dq0 + dp3 + dq3 < beta:
+                strong = all(abs(m[l, 0] - m[l, 3]) + abs(m[l, 7] - m[l, 4]) < (beta >> 3) and 2 * dd < (beta >> 2)
+                             and abs(m[l, 3] - m[l, 4]) < ((tc * 5 + 1) >> 1) for l, dd in ((0, dp0 + dq0), (3, dp3 + dq3)))
+                for l in range(0 if not strong else 4, 4):
+                    delta = (9 * (m[l, 4] - m[l, 3]) - 3 * (m[l, 5] - m[l, 2]) + 8) >> 4
+                    if abs(delta) < 10 * tc:
+                        delta = min(tc, max(-tc, delta))
+                        tally("luma", ([m[l, 3] + delta] if not pn else []) + ([m[l, 4] - delta] if not qn else []))
+            if b > 1 and ux % 4 == 0:
+                tcc = DBK_TC[min(53, max(0, CHROMA_QP[min(51, max(0, qa))] + 2 * (b - 1) + 2 * toff))] * sc
+                for p in (1, 2):
+                    for k in range(2):
+                        c = d["planes"][p].astype(np.int64)[2 * uy + k, 2 * ux - 2:2 * ux + 2]
+                        delta = min(tcc, max(-tcc, (((c[2] - c[1]) << 2) + c[0] - c[3] + 4) >> 3))
+                        tally("chroma", ([c[1] + delta] if not pn else []) + ([c[2] - delta] if not qn else []))
+    return dict(luma=(lo["luma"], hi["luma"]), chroma=(lo["chroma"], hi["chroma"]))
+
+
+# ---- SAO, SAO statistics, motion search ----------------------------------------------------------------------------------------
+
+def sao_edge_content(rng, w, h, B):
+    """Three planes of 2x2 cells, each cell within the largest offset (7 << (B - min(B, 10))) of 0, within it of 2^B - 1, or anywhere
+    in the range (a third each), plus +-1 noise: every band occurs, every edge class occurs at both range ends, and an offset of
+    either sign carries samples over either end."""
+    mx, big = (1 << B) - 1, 7 << (B - min(B, 10))
+    out = []
+    for pw, ph in ((w, h), (w // 2, h // 2), (w // 2, h // 2)):
+        shape = (-(-ph // 2), -(-pw // 2))
+        which = rng.integers(0, 3, shape)
+        v = np.where(which == 0, rng.integers(0, big + 1, shape), np.where(which == 1, mx - rng.integers(0, big + 1, shape), rng.integers(0, mx + 1, shape)))
+        v = v.repeat(2, 0).repeat(2, 1)[:ph, :pw] + rng.integers(-1, 2, (ph, pw))
+        out.append(np.clip(v, 0, mx).astype(np.int16))
+    return out
+
+
+def sao_unclipped(planes, prm, w, h, B, ctu=64):
+    """SAO (TComSampleAdaptiveOffset.cpp:781-1240) per sample in int64 WITHOUT the clip, offsets scaled by 1 << (B - min(B, 10));
+    prm: [3, CTUs] records (type -1..4, band, offset[4]).  Returns (values, applied offsets (0 where none)) per plane."""
+    eo = np.array((1, 2, 0, 3, 4))
+    up, cw, out = B - min(B, 10), -(-w // ctu), []
+    for p, pl in enumerate(planes):
+        c = np.asarray(pl, np.int64)
+        ph, pw = c.shape
+        cs = ctu >> (1 if p else 0)
+        q = prm[p][(np.arange(ph)[:, None] // cs) * cw + np.arange(pw)[None, :] // cs]
+        typ, band, offs = q["type"].astype(np.int64), q["band"].astype(np.int64), q["offset"].astype(np.int64)
+        pad = np.pad(c, 1, mode="edge")
+        add = np.zeros_like(c)
+        inside = lambda dx, dy: (np.arange(ph)[:, None] + dy >= 0) & (np.arange(ph)[:, None] + dy < ph) & (np.arange(pw)[None, :] + dx >= 0) & (np.arange(pw)[None, :] + dx < pw)
+        for t, (dx, dy) in enumerate(((1, 0), (0, 1), (1, 1), (-1, 1))):
+            a, b = pad[1 - dy:1 - dy + ph, 1 - dx:1 - dx + pw], pad[1 + dy:1 + dy + ph, 1 + dx:1 + dx + pw]
+            slot = eo[np.sign(c - a) + np.sign(c - b) + 2]
+            use = (typ == t) & inside(dx, dy) & inside(-dx, -dy) & (slot > 0)
+            add = np.where(use, np.take_along_axis(offs, np.maximum(slot - 1, 0)[..., None], -1)[..., 0], add)
+        k = ((c >> (B - 5)) - band) & 31
+        add = np.where((typ == 4) & (k < 4), np.take_along_axis(offs, np.minimum(k, 3)[..., None], -1)[..., 0], add)
+        out.append((c + (add << up), add))
+    return [o[0] for o in out], [o[1] for o in out]
+
+
+def opposite_ends(w, h, B):
+    """(all 2^B - 1, all 0) as 4:2:0 pictures: |org - rec| = 2^B - 1 on every sample, the largest sums of the SAO statistics
+    (count * maxv per bin) and the largest SAD (64 * 64 * 4095 at 12 bit for one 64x64 unit, before << sub_shift and >> 4)."""
+    zero = [np.zeros((ph, pw), np.int16) for pw, ph in ((w, h), (w // 2, h // 2), (w // 2, h // 2))]
+    return [np.full_like(z, (1 << B) - 1) for z in zero], zero

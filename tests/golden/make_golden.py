@@ -15,6 +15,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
+import extreme_inputs as xi  # noqa: E402
 import oracle_lib as ol  # noqa: E402
 from thevc_amd import workload  # noqa: E402
 
@@ -218,24 +219,36 @@ def arl(R, B, rng):
     return out
 
 
-def deblock(R, B, rng):
-    """The reference's deblocking edge filters on a 128x64 picture, driven with random boundary strengths."""
-    w, h = 128, 64
-    R.ref_init(B, w, h, 1)
+def _deblock_random(rng, w, h, B):
     mx = (1 << B) - 1
     uw, uh = w // 4, h // 4
+    ramp = (np.arange(w)[None, :] // 8 + np.arange(h)[:, None] // 8) * (2 << (B - 8))
+    y = np.clip(rng.integers(0, 24 << (B - 8), (h // 8, w // 8)).repeat(8, 0).repeat(8, 1) + rng.integers(-2, 3, (h, w)) + (90 << (B - 8)) + ramp, 0, mx).astype(np.int16)
+    cb = np.clip(rng.integers(0, mx // 4, (h // 16, w // 16)).repeat(8, 0).repeat(8, 1) + rng.integers(0, 5, (h // 2, w // 2)), 0, mx).astype(np.int16)
+    cr = np.clip(rng.integers(0, mx // 4, (h // 16, w // 16)).repeat(8, 0).repeat(8, 1) + rng.integers(0, 5, (h // 2, w // 2)), 0, mx).astype(np.int16)
+    bs_v, bs_h = rng.integers(0, 3, (uh, uw)).astype(np.uint8), rng.integers(0, 3, (uh, uw)).astype(np.uint8)
+    bs_v[:, 0] = 0
+    bs_h[0, :] = 0
+    qp = rng.integers(20, 46, (uh // 2, uw // 2)).repeat(2, 0).repeat(2, 1).astype(np.int8)
+    nof = (rng.random((uh // 2, uw // 2)) < 0.1).repeat(2, 0).repeat(2, 1).astype(np.uint8)
+    return y, cb, cr, bs_v, bs_h, qp, nof
+
+
+def deblock(R, B, rng, edge=False):
+    """The reference's deblocking edge filters on a 128x64 picture, driven with random boundary strengths.  edge: the content
+    and maps of extreme_inputs.dbk_edge_content (blocks within a few tc of either range end, QPs 0..51) and offsets of -6 / 6."""
+    w, h = 128, 64
+    R.ref_init(B, w, h, 1)
     vp = lambda a: a.ctypes.data_as(C.c_void_p)
     out = {}
-    for k, (boff, toff, use_nof) in enumerate([(0, 0, 0), (1, -2, 1)]):
-        ramp = (np.arange(w)[None, :] // 8 + np.arange(h)[:, None] // 8) * (2 << (B - 8))
-        y = np.clip(rng.integers(0, 24 << (B - 8), (h // 8, w // 8)).repeat(8, 0).repeat(8, 1) + rng.integers(-2, 3, (h, w)) + (90 << (B - 8)) + ramp, 0, mx).astype(np.int16)
-        cb = np.clip(rng.integers(0, mx // 4, (h // 16, w // 16)).repeat(8, 0).repeat(8, 1) + rng.integers(0, 5, (h // 2, w // 2)), 0, mx).astype(np.int16)
-        cr = np.clip(rng.integers(0, mx // 4, (h // 16, w // 16)).repeat(8, 0).repeat(8, 1) + rng.integers(0, 5, (h // 2, w // 2)), 0, mx).astype(np.int16)
-        bs_v, bs_h = rng.integers(0, 3, (uh, uw)).astype(np.uint8), rng.integers(0, 3, (uh, uw)).astype(np.uint8)
-        bs_v[:, 0] = 0
-        bs_h[0, :] = 0
-        qp = rng.integers(20, 46, (uh // 2, uw // 2)).repeat(2, 0).repeat(2, 1).astype(np.int8)
-        nof = (rng.random((uh // 2, uw // 2)) < 0.1).repeat(2, 0).repeat(2, 1).astype(np.uint8)
+    for k, (boff, toff, use_nof) in enumerate([(-6, 6, 0), (6, -6, 1)] if edge else [(0, 0, 0), (1, -2, 1)]):
+        if edge:
+            d = xi.dbk_edge_content(rng, w, h, B)
+            cnt = xi.dbk_count_outside(d, w, h, B, use_nof, boff, toff)
+            assert min(cnt["luma"] + cnt["chroma"]) > 0, cnt  # lines that need the final clip: both ends, luma and chroma
+            (y, cb, cr), bs_v, bs_h, qp, nof = d["planes"], d["bsv"], d["bsh"], d["qp"], d["nof"]
+        else:
+            y, cb, cr, bs_v, bs_h, qp, nof = _deblock_random(rng, w, h, B)
         R.ref_set_recon(y.reshape(-1), cb.reshape(-1), cr.reshape(-1))
         ry, rcb, rcr = np.zeros_like(y), np.zeros_like(cb), np.zeros_like(cr)
         R.ref_deblock_picture(vp(bs_v), vp(bs_h), vp(qp), vp(nof) if use_nof else None, boff, toff, vp(ry), vp(rcb), vp(rcr))
@@ -245,8 +258,10 @@ def deblock(R, B, rng):
     return out
 
 
-def sao(R, B, rng):
-    """SAOProcess of the reference on a 136x72 picture (cut CTUs), random per-CTU parameters."""
+def sao(R, B, rng, edge=False):
+    """SAOProcess of the reference on a 136x72 picture (cut CTUs), random per-CTU parameters.  edge: the planes of
+    extreme_inputs.sao_edge_content (samples within the largest scaled offset of either range end), every type once in every
+    component, offsets of 7 and -7 among the random ones."""
     w, h = 136, 72
     R.ref_init(B, w, h, 1)
     mx = (1 << B) - 1
@@ -260,10 +275,18 @@ def sao(R, B, rng):
     prm["type"] = rng.integers(-1, 5, (3, n_lcu))
     prm["band"] = rng.integers(0, 32, (3, n_lcu))
     prm["offset"] = rng.integers(-7, 8, (3, n_lcu, 4))
+    if edge:
+        y, cb, cr = xi.sao_edge_content(rng, w, h, B)
+        for c in range(3):
+            prm["type"][c, rng.permutation(n_lcu)] = np.arange(-1, 5)
+            prm["offset"][c, :, 0], prm["offset"][c, :, 3] = 7, -7
     prm = np.ascontiguousarray(prm)
     R.ref_set_recon(y.reshape(-1), cb.reshape(-1), cr.reshape(-1))
     ry, rcb, rcr = np.zeros_like(y), np.zeros_like(cb), np.zeros_like(cr)
     R.ref_sao_picture(vp(prm), n_lcu, vp(ry), vp(rcb), vp(rcr))
+    if edge:  # the clip binds at both ends in every plane
+        unc, _ = xi.sao_unclipped([y, cb, cr], prm, w, h, B)
+        assert all(min(xi.count_outside(u, B)) > 0 for u in unc)
     return {"y": y, "cb": cb, "cr": cr, "prm": prm.view(np.uint8).reshape(3, n_lcu, 6), "oy": ry, "ocb": rcb, "ocr": rcr}
 
 
@@ -353,11 +376,16 @@ def intra(R, B, rng):
     return out
 
 
-def inter(R, B, rng):
+def inter(R, B, rng, edge=False):
+    """edge: planes of 0 and 2^B - 1 only (extreme_inputs.extreme_plane; luma and Cb with border lines of the maximum), so that
+    the filters over- and undershoot and the final clip binds."""
     out = {}
     w, h = 128, 96
     R.ref_init(B, w, h, 1)
-    y, cb, cr = (rng.integers(0, 1 << B, n).astype(np.int16) for n in (w * h, w * h // 4, w * h // 4))
+    if edge:
+        y, cb, cr = (xi.extreme_plane(rng, pw, ph, B, kind).reshape(-1) for pw, ph, kind in ((w, h, "border"), (w // 2, h // 2, "border"), (w // 2, h // 2, "binary")))
+    else:
+        y, cb, cr = (rng.integers(0, 1 << B, n).astype(np.int16) for n in (w * h, w * h // 4, w * h // 4))
     R.ref_set_recon(y, cb, cr)
     out["pic_y"], out["pic_cb"], out["pic_cr"] = y.reshape(h, w), cb.reshape(h // 2, w // 2), cr.reshape(h // 2, w // 2)
     shapes = [(64, 64), (32, 16), (16, 32), (8, 8), (8, 4), (4, 8), (16, 12), (24, 32), (64, 16), (16, 16)]
@@ -381,6 +409,11 @@ def inter(R, B, rng):
         padc[:pw * ph // 4] = b
         padc[1024:1024 + pw * ph // 4] = c
         oc.append(padc)
+    if edge:  # uni-predicted outputs at both clips, luma and chroma
+        mx = (1 << B) - 1
+        for o, n in ((oy, 1), (oc, 4)):
+            v = np.concatenate([a[:p[2] * p[3] // n] for a, p in zip(o, pus) if not p[8]])
+            assert (v == 0).any() and (v == mx).any()
     out["pu"] = np.array(pus, np.int32)
     out["pu_y"] = np.stack(oy)
     out["pu_c"] = np.stack(oc)
@@ -408,16 +441,27 @@ def frame(R, B, qp, pic, tiling, seed):
             "lev_y": lev[0].astype(np.int16), "lev_cb": lev[1].astype(np.int16), "lev_cr": lev[2].astype(np.int16)}
 
 
+def edges(R, B=12):
+    """inter_edge / deblock_edge / sao_edge: the layouts of inter(), deblock() and sao() on the content of tests/extreme_inputs.py"""
+    R.ref_init(B, 416, 240, 1)
+    np.savez_compressed(os.path.join(HERE, f"inter_edge_b{B}.npz"), **inter(R, B, np.random.default_rng(12288 + B), edge=True))
+    np.savez_compressed(os.path.join(HERE, f"deblock_edge_b{B}.npz"), **deblock(R, B, np.random.default_rng(13348 + B), edge=True))  # a seed at which both cases reach both ends
+    np.savez_compressed(os.path.join(HERE, f"sao_edge_b{B}.npz"), **sao(R, B, np.random.default_rng(14336 + B), edge=True))
+
+
 def main():
     assert ol.have_ref(), "build oracle/_ref first: bash oracle/build_ref.sh"
     R = ol.ref()
+    if sys.argv[1:] == ["edges"]:  # content at the range ends, 12 bit
+        edges(R)
+        return
     if sys.argv[1:] == ["rdoq"]:  # added after the first set: generate only the RDOQ vectors
         for B in (8, 10):
             R.ref_init(B, 416, 240, 1)
             np.savez_compressed(os.path.join(HERE, f"rdoq_b{B}.npz"), **rdoq(R, B, np.random.default_rng(4048 + B)))
         return
     if sys.argv[1:] == ["sao"]:
-        for B in (8, 10):
+        for B in (8, 10, 12):
             np.savez_compressed(os.path.join(HERE, f"sao_b{B}.npz"), **sao(R, B, np.random.default_rng(7096 + B)))
         return
     if sys.argv[1:] == ["intra64"]:  # round 3: the 64x64 luma prediction units
@@ -440,7 +484,7 @@ def main():
             np.savez_compressed(os.path.join(HERE, f"dequant_scaled_b{B}.npz"), **dequant_scaled(R, B, np.random.default_rng(10168 + B)))
         return
     if sys.argv[1:] == ["deblock"]:
-        for B in (8, 10):
+        for B in (8, 10, 12):
             np.savez_compressed(os.path.join(HERE, f"deblock_b{B}.npz"), **deblock(R, B, np.random.default_rng(6072 + B)))
         return
     for B in (8, 10):
@@ -450,6 +494,12 @@ def main():
         np.savez_compressed(os.path.join(HERE, f"quant_b{B}.npz"), **quant(R, B, rng))
         np.savez_compressed(os.path.join(HERE, f"intra_b{B}.npz"), **intra(R, B, rng))
         np.savez_compressed(os.path.join(HERE, f"inter_b{B}.npz"), **inter(R, B, rng))
+    # 12 bit, for the inter path and the loop filters only: seeds of their own
+    R.ref_init(12, 416, 240, 1)
+    np.savez_compressed(os.path.join(HERE, "inter_b12.npz"), **inter(R, 12, np.random.default_rng(2024 + 12)))
+    np.savez_compressed(os.path.join(HERE, "deblock_b12.npz"), **deblock(R, 12, np.random.default_rng(6072 + 12)))
+    np.savez_compressed(os.path.join(HERE, "sao_b12.npz"), **sao(R, 12, np.random.default_rng(7096 + 12)))
+    edges(R)
     np.savez_compressed(os.path.join(HERE, "frame_416x240_mix_b8.npz"), **frame(R, 8, 32, (416, 240), "mix", 3))
     np.savez_compressed(os.path.join(HERE, "frame_200x136_mix_b10.npz"), **frame(R, 10, 27, (200, 136), "mix", 4))
     for f in sorted(os.listdir(HERE)):

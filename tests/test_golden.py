@@ -6,6 +6,7 @@ import os
 import numpy as np
 import pytest
 
+import extreme_inputs as xi
 import oracle_lib as ol
 
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -135,9 +136,16 @@ def _deblock_case(g, k):
     return int(par[0]), int(par[1]), int(par[2]), ins, outs
 
 
-@pytest.mark.parametrize("B", [8, 10])
+EDGE = "edge_b12"  # the same layouts on the content of tests/extreme_inputs.py, 12 bit
+
+
+@pytest.mark.parametrize("B", [8, 10, 12])
 def test_oracle_deblock(B):
-    g, O = load(f"deblock_b{B}.npz"), ol.oracle()
+    _oracle_deblock(f"deblock_b{B}.npz", B)
+
+
+def _oracle_deblock(name, B):
+    g, O = load(name), ol.oracle()
     P3, I3 = C.c_void_p * 3, C.c_int * 3
     vp = lambda a: a.ctypes.data_as(C.c_void_p)
     for k in range(2):
@@ -150,9 +158,13 @@ def test_oracle_deblock(B):
             assert np.array_equal(a, b), k
 
 
-@pytest.mark.parametrize("B", [8, 10])
+@pytest.mark.parametrize("B", [8, 10, 12])
 def test_oracle_sao(B):
-    g, O = load(f"sao_b{B}.npz"), ol.oracle()
+    _oracle_sao(f"sao_b{B}.npz", B)
+
+
+def _oracle_sao(name, B):
+    g, O = load(name), ol.oracle()
     P3, I3 = C.c_void_p * 3, C.c_int * 3
     y, cb, cr = (np.ascontiguousarray(g[k]) for k in ("y", "cb", "cr"))
     prm = np.ascontiguousarray(g["prm"])
@@ -210,9 +222,13 @@ def _ext_planes(g, O):
     return planes
 
 
-@pytest.mark.parametrize("B", [8, 10])
+@pytest.mark.parametrize("B", [8, 10, 12])
 def test_oracle_inter(B):
-    g, O = load(f"inter_b{B}.npz"), ol.oracle()
+    _oracle_inter(f"inter_b{B}.npz", B)
+
+
+def _oracle_inter(name, B):
+    g, O = load(name), ol.oracle()
     planes = _ext_planes(g, O)
     assert np.array_equal(planes[0][0].reshape(g["ext_y"].shape), g["ext_y"])
     h, w = g["pic_y"].shape
@@ -232,6 +248,31 @@ def test_oracle_inter(B):
     o = np.zeros(256, np.int16)
     O.hmo_addAvg(np.ascontiguousarray(g["avg_a"]), 16, np.ascontiguousarray(g["avg_b"]), 16, o, 16, 16, 16, B)
     assert np.array_equal(o, g["avg_o"])
+
+
+def _edge_vectors_reach_the_ends(B=12):
+    """What the edge fixtures are for, read off the reference's own outputs: uni-predicted samples at 0 and at 2^B - 1 in luma
+    and chroma, deblocking lines that need the final clip, SAO outputs at both ends in every plane."""
+    mx = (1 << B) - 1
+    g = load(f"inter_{EDGE}.npz")
+    uni = g["pu"][:, 8] == 0
+    assert all((v[uni] == e).any() for v in (g["pu_y"], g["pu_c"]) for e in (0, mx))
+    assert set(np.unique(g["pic_y"])) == {0, mx}
+    g = load(f"deblock_{EDGE}.npz")
+    for k in range(2):  # lines whose weak luma or chroma result before the clip lies outside the range: both ends, luma and chroma
+        boff, toff, use_nof, (y, cb, cr, bsv, bsh, qp, nof), outs = _deblock_case(g, k)
+        cnt = xi.dbk_count_outside(dict(planes=[y, cb, cr], bsv=bsv, bsh=bsh, qp=qp, nof=nof), y.shape[1], y.shape[0], B, use_nof, boff, toff)
+        assert min(cnt["luma"] + cnt["chroma"]) > 0, cnt
+        assert all((o != i).any() for o, i in zip(outs, (y, cb, cr)))
+    g = load(f"sao_{EDGE}.npz")
+    assert all((g[n] == e).any() for n in ("oy", "ocb", "ocr") for e in (0, mx))
+
+
+def test_oracle_edge_vectors():
+    _edge_vectors_reach_the_ends()
+    _oracle_inter(f"inter_{EDGE}.npz", 12)
+    _oracle_deblock(f"deblock_{EDGE}.npz", 12)
+    _oracle_sao(f"sao_{EDGE}.npz", 12)
 
 
 FRAMES = [("frame_416x240_mix_b8.npz", 8), ("frame_200x136_mix_b10.npz", 10)]
@@ -338,9 +379,13 @@ def test_gpu_intra(gctx):
 
 @pytest.mark.gpu
 def test_gpu_inter(gctx):
+    _gpu_inter(gctx, f"inter_b{gctx.bit_depth}.npz")
+
+
+def _gpu_inter(gctx, name):
     from thevc_amd import capi
     B, L = gctx.bit_depth, capi.lib()
-    g = load(f"inter_b{B}.npz")
+    g = load(name)
     h, w = g["pic_y"].shape
     d_ref = capi.DevPicture(gctx, w, h, 80, 80).upload([g["pic_y"], g["pic_cb"], g["pic_cr"]])
     gctx._chk(L.hmx_pic_extend_border(gctx.h, C.byref(d_ref.as_pic()), w, h, 80, 80))
@@ -473,9 +518,13 @@ def test_gpu_rdoq(gctx):
 @pytest.mark.gpu
 def test_gpu_deblock(gctx):
     """hmx_deblock_picture vs the reference's edge filters (golden), luma and chroma, with and without no-filter units."""
+    _gpu_deblock(gctx, f"deblock_b{gctx.bit_depth}.npz")
+
+
+def _gpu_deblock(gctx, name):
     from thevc_amd import capi
-    B, L = gctx.bit_depth, capi.lib()
-    g = load(f"deblock_b{B}.npz")
+    L = capi.lib()
+    g = load(name)
     for k in range(2):
         boff, toff, use_nof, (y, cb, cr, bsv, bsh, qp, nof), outs = _deblock_case(g, k)
         h, w = y.shape
@@ -495,9 +544,13 @@ def test_gpu_deblock(gctx):
 @pytest.mark.gpu
 def test_gpu_sao(gctx):
     """hmx_sao_picture vs the reference's SAOProcess (golden): all edge classes, band offset, cut CTUs, chroma."""
+    _gpu_sao(gctx, f"sao_b{gctx.bit_depth}.npz")
+
+
+def _gpu_sao(gctx, name):
     from thevc_amd import capi
-    B, L = gctx.bit_depth, capi.lib()
-    g = load(f"sao_b{B}.npz")
+    L = capi.lib()
+    g = load(name)
     y, cb, cr = g["y"], g["cb"], g["cr"]
     h, w = y.shape
     src = capi.DevPicture(gctx, w, h).upload([y, cb, cr])
@@ -510,3 +563,17 @@ def test_gpu_sao(gctx):
     for x, k in zip(got, ("oy", "ocb", "ocr")):
         assert np.array_equal(x, g[k]), k
     src.free(), dst.free(), d_prm.free()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("tag", ["b12", EDGE])
+def test_gpu_12bit_vectors(tag):
+    """The 12-bit vectors of the inter path and the loop filters, on random content and on content at the range ends."""
+    from thevc_amd import capi
+    ctx = capi.Context(bit_depth=12)
+    try:
+        _gpu_inter(ctx, f"inter_{tag}.npz")
+        _gpu_deblock(ctx, f"deblock_{tag}.npz")
+        _gpu_sao(ctx, f"sao_{tag}.npz")
+    finally:
+        ctx.close()

@@ -69,8 +69,8 @@ def boxed(x, y, w, h, ref, s, px, py, rng_):
     return unit(x, y, w, h, ref, s, px, py, *capi.set_search_range(px, py, rng_, x, y, W, H, 64))
 
 
-@pytest.fixture(scope="module")
-def textured(ctx):
+def make_textured(ctx):
+    """The textured pictures on the device (the caller frees them); tests/test_gpu_inter_loop_edges.py makes them at 12 bit."""
     B = ctx.bit_depth
     rng = np.random.default_rng(800 + B)
     # smooth texture plus noise, so that costs have structure and a real minimum; margins hold samples of their own
@@ -80,7 +80,12 @@ def textured(ctx):
         base = (np.sin(xx / (5.0 + k)) + np.cos(yy / (7.0 - k))) * (1 << (B - 3)) + (1 << (B - 1))
         refs.append(np.clip(base + rng.integers(-(1 << (B - 4)), 1 << (B - 4), base.shape), 0, (1 << B) - 1).astype(np.int16))
     org = np.clip(refs[0][M + 3:M + 3 + H, M - 2:M - 2 + W].astype(np.int32) + rng.integers(-6, 7, (H, W)), 0, (1 << B) - 1).astype(np.int16)
-    p = Pictures(ctx, refs, org)
+    return Pictures(ctx, refs, org)
+
+
+@pytest.fixture(scope="module")
+def textured(ctx):
+    p = make_textured(ctx)
     yield p
     p.free()
 

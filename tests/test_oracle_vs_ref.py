@@ -555,8 +555,12 @@ def test_distortion(B):
 
 
 def test_pred_inter_blocks_and_border():
+    _pred_inter_blocks_and_border((8, 10))
+
+
+def _pred_inter_blocks_and_border(bits):  # tests/test_oracle_vs_ref_sample_edges.py runs it with (12,)
     R, O = ol.ref(), ol.oracle()
-    for B in (8, 10):
+    for B in bits:
         w, h = 192, 128
         R.ref_init(B, w, h, 1)
         rng = np.random.default_rng(1100 + B)
@@ -699,12 +703,16 @@ def _deblock_inputs(rng, w, h, B, smooth):
 
 
 def test_deblock_application():
+    _deblock_application((8, 10))
+
+
+def _deblock_application(bits):  # tests/test_oracle_vs_ref_sample_edges.py runs it with (12,)
     """The deblocking edge filters (xEdgeFilterLuma / xEdgeFilterChroma and the pel filters) of the reference,
     driven with random boundary strengths per 4x4 unit, vs the oracle's picture-level restatement."""
     R, O = ol.ref(), ol.oracle()
     P3, I3 = C.c_void_p * 3, C.c_int * 3
     vp = lambda a: a.ctypes.data_as(C.c_void_p)
-    for B in (8, 10):
+    for B in bits:
         w, h = 192, 128
         R.ref_init(B, w, h, 1)
         rng = np.random.default_rng(2100 + B)
@@ -790,12 +798,16 @@ def _sao_params(rng, n_lcu):
 
 
 def test_sao_application():
+    _sao_application((8, 10))
+
+
+def _sao_application(bits):  # tests/test_oracle_vs_ref_sample_edges.py runs it with (12,)
     """SAOProcess of the reference (edge offset classes, band offset, off; luma and chroma; a picture that is not a
     whole number of CTUs) vs the oracle's out-of-place restatement."""
     R, O = ol.ref(), ol.oracle()
     P3, I3 = C.c_void_p * 3, C.c_int * 3
     vp = lambda a: a.ctypes.data_as(C.c_void_p)
-    for B in (8, 10):
+    for B in bits:
         for (w, h) in ((192, 128), (200, 136)):
             R.ref_init(B, w, h, 1)
             rng = np.random.default_rng(2500 + B + w)

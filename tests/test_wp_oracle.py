@@ -12,7 +12,7 @@ def _planes(rng, w, h, lo=-32768, hi=32768):
     return [rng.integers(lo, hi, (h >> (1 if c else 0), w >> (1 if c else 0))).astype(np.int16) for c in range(3)]
 
 
-@pytest.mark.parametrize("B", [8, 10])
+@pytest.mark.parametrize("B", [8, 10, 12])
 def test_loop_equals_vec(B):
     rng = np.random.default_rng(4100 + B)
     for it in range(24):
@@ -67,7 +67,7 @@ def _pred(O, planes, m, x, y, w, h, mvx, mvy, bi, B):
     return out
 
 
-@pytest.mark.parametrize("B", [8, 10])
+@pytest.mark.parametrize("B", [8, 10, 12])
 def test_unit_weights_are_the_unweighted_prediction(B):
     """Uni with weight = 1 << d, offset 0 is the oracle's own bi = 0 prediction (its last-stage rounding), d = 0..7;
     bi with both weights 1 << d, offsets 0 is hmo_addAvg."""

@@ -130,6 +130,17 @@ CLIP_CASES = [
     (8, "bi", (-8192, -8192, 255, 255, 127, 127, 7), 127),    # P = -8192: 255 * 8192 >> 14
     (8, "bi", (-5632, -3072, -64, 192, -128, 0, 6), 36),      # (-163840 + 983040 - 127 * 4096) >> 13
     (10, "bi", (-8192, -8192, 1, 1, 127, 127, 0), 508),       # (1 + 1016) * 16 >> 5
+    # B = 12: head = 2, offsets times 16
+    (12, "uni", (8191, -128, 0, 0), 0),       # (-128 * 16383 + 2) >> 2 < 0
+    (12, "uni", (8191, 255, 127, 0), 4095),   # (255 * 16383 + 2) >> 2 = 1044416, + 2032: above 4095
+    (12, "uni", (8191, 1, -128, 0), 2048),    # (16383 + 2) >> 2 = 4096, - 2048
+    (12, "uni", (-8192, 255, 127, 7), 2032),  # P = -8192: 256 >> 9 = 0, + 127 * 16
+    (12, "uni", (-1792, 64, 127, 6), 3632),   # (64 * 6400 + 128) >> 8 = 1600, + 2032
+    (12, "uni", (4608, 128, -128, 7), 1152),  # (128 * 12800 + 256) >> 9 = 3200, - 2048
+    (12, "bi", (8191, 8191, -128, -128, -128, -128, 0), 0),   # (-4194048 + 4 - 4096 * 4) >> 3 < 0
+    (12, "bi", (8191, 8191, 255, 255, 127, 127, 7), 4095),    # (8355330 + 512 + 4064 * 512) >> 10 = 10191: above 4095
+    (12, "bi", (-8192, -8192, 1, 1, 127, 127, 0), 2032),      # (4 + 4064 * 4) >> 3
+    (12, "bi", (-1792, -1728, 128, 128, 127, -128, 7), 1600), # offsets sum to -1: (1646592 + 512 - 16 * 512) >> 10 = 1600
 ]
 
 
