@@ -435,6 +435,30 @@ int hmx_last_call_timing(hmx_ctx *ctx, float *to_tiled_ms, float *chain_ms, floa
 /* Packed schedule: the part of chain_ms the LAST timed call spent building its schedule tables on the device (0 when it re-used
  * the tables of an earlier call with the same pictures and plans). */
 int hmx_last_call_tables_ms(hmx_ctx *ctx, float *ms);
+/* Packed schedule: the schedule tables of the LAST whole-picture call copied to the HOST, read-only (for the test that holds
+ * them against the plans of the call; nothing is rebuilt or invalidated).  The call waits for the context's stream.  Use it
+ * twice: with hdr = rows = descs = items = done = NULL it fills *geom only, so that the caller can allocate; any non-NULL
+ * pointer then receives its table.  HMX_ERR_ARG when the last whole-picture call did not run the packed schedule or its
+ * tables are not valid (the call failed, or a pool it used was destroyed since).
+ *   geom   the shape of the tables: pictures form n_groups groups of I (the last one may be ragged), group g belongs to
+ *          shard g mod n_shards; a ROW is (dependency level L, group g), index L * n_groups + g, n_rows = max_levels * n_groups.
+ *   hdr    12 x uint32: shard_base[9] (the wave-items of shard s are [shard_base[s], shard_base[s + 1]); entries n_shards .. 8
+ *          hold the total), total_items, the abort word (non-zero: a dependency wait of the call timed out), 0.
+ *   rows   n_rows x 12 x uint32: wave_base (first wave-item), n_waves, item_base[4] (first item per transform size 4, 8, 16,
+ *          32), count[4] (blocks per size), 2 words of padding.  Wave-items and items are numbered in TICKET order: shard after
+ *          shard, inside a shard level after level, inside a level the shard's groups in ascending order.
+ *   descs  n_waves x 4 x uint32, one per wave-item: item_off (first item), n_items | size class << 28, row, dep_target (the
+ *          wave-items of row (L - 1, g) that must have completed before this one starts; 0: nothing to wait for).  A row's
+ *          wave-items follow each other from wave_base, sizes 32, 16, 8, 4 in that order, at most slots(size) items each
+ *          (slots4, slots8, 4 per 16x16, 1 per 32x32).
+ *   items  n_items x 16 bytes: a block as hmx_intra_plan_download gives it (hmx_tu + 64-bit mask), with the picture's index
+ *          inside its group in bits 2..7 of `plane`.
+ *   done   n_rows x uint32: the completion counter of every row as the call left it (= n_waves once the call has finished). */
+typedef struct hmx_pack_geom {
+  int n_pics, I, n_groups, n_shards, max_levels, slots4, slots8;
+  int n_rows, n_waves, n_items;
+} hmx_pack_geom;
+int hmx_last_call_pack_tables(hmx_ctx *ctx, hmx_pack_geom *geom, void *hdr, void *rows, void *descs, void *items, uint32_t *done);
 /* Which schedule a whole-picture call with n_pics pictures uses: 1 = level, 0 = wave. */
 int hmx_intra_schedule_for(const hmx_ctx *ctx, int n_pics);
 /* n_pics pictures share one plan (same block structure); org/rec/lev are arrays of n_pics entries. */

@@ -65,6 +65,40 @@ def test_dependency_mask_covers_what_the_prediction_reads(N, luma):
     assert pruned > 0  # the mask does rule units out
 
 
+@pytest.mark.parametrize("N,luma", [(4, True), (8, True), (16, True), (32, True), (4, False), (8, False), (16, False)])
+def test_dependency_mask_in_the_availability_s_place(N, luma):
+    """A plan stores the dependency mask where the chains expect the availability flags (hmx_plan.hip, plan_build_host: "the
+    chains gather and pad with it exactly as with the availability").  That holds when the oracle's prediction with the MASK as
+    the flags (and its popcount as the number of available units) equals the prediction with the true flags: the padding
+    then fills every position the mode reads with the value the true flags would have given it.  All 35 modes, the seven
+    fixed patterns of the test above and ten random ones; the mask must differ from the flags in at least a quarter of the
+    cases (with every neighbour available it does for each mode that does not read the whole line), or the test says nothing."""
+    O, L = ol.oracle(), capi.lib()
+    B, U = 10, 4 if luma else 2
+    n = N // U
+    rng = np.random.default_rng(100 + N * 2 + luma)
+    x0 = y0 = 2 * N + 8
+    side = 4 * N + 32
+    patterns = [[1] * (4 * n + 1), [0] * n + [1] * (3 * n + 1), [1] * (3 * n + 1) + [0] * n, [0] * n + [1] * (2 * n + 1) + [0] * n,
+                [0] * (2 * n + 1) + [1] * (2 * n), [1] * (2 * n) + [0] * (2 * n + 1), [0] * (2 * n) + [1] + [0] * (2 * n)]
+    patterns += [list(rng.integers(0, 2, 4 * n + 1)) for _ in range(10)]
+    cases = other_mask = 0
+    for flags in patterns:
+        avail = sum(int(b) << u for u, b in enumerate(flags))
+        plane = rng.integers(0, 1 << B, (side, side)).astype(np.int16)
+        for mode in range(35):
+            dep = L.hmx_intra_dependency_mask(N, int(luma), mode, avail)
+            dep_flags = [(dep >> u) & 1 for u in range(4 * n + 1)]
+            assert sum(dep_flags) == bin(dep).count("1")  # no bit beyond the 4n + 1 units
+            want = _predict(O, plane, x0, y0, N, luma, mode, flags, B)
+            got = _predict(O, plane, x0, y0, N, luma, mode, dep_flags, B)
+            assert np.array_equal(got, want), (N, luma, mode, flags, hex(dep))
+            cases += 1
+            other_mask += dep != avail
+    print(f"N={N} luma={luma}: {cases} cases, mask != availability in {other_mask}")
+    assert cases == 17 * 35 and 4 * other_mask >= cases, (cases, other_mask)
+
+
 @pytest.mark.parametrize("pic", [(416, 240), (200, 136), (64, 64), (1920, 1080), (72, 200)])
 def test_availability_closed_form(pic):
     """The closed form of the neighbour-availability mask (a Z-order argument on the block's position, used by the device plan

@@ -157,6 +157,16 @@ class Layout:
         return C.byref(self.s)
 
 
+class PackGeom(C.Structure):  # hmx_pack_geom
+    _fields_ = [(n, C.c_int) for n in ("n_pics", "I", "n_groups", "n_shards", "max_levels", "slots4", "slots8", "n_rows", "n_waves", "n_items")]
+
+
+PLAN_BLOCK_DTYPE = np.dtype(TU_DTYPE.descr + [("avail", "<u8")])  # a block of hmx_intra_plan_download / an item of the packed schedule
+PACK_ROW_DTYPE = np.dtype([("wave_base", "<u4"), ("n_waves", "<u4"), ("item_base", "<u4", 4), ("count", "<u4", 4), ("pad", "<u4", 2)])
+PACK_DESC_DTYPE = np.dtype([("item_off", "<u4"), ("n_s", "<u4"), ("row", "<u4"), ("dep_target", "<u4")])
+PACK_HDR_DTYPE = np.dtype([("shard_base", "<u4", 9), ("total_items", "<u4"), ("abort", "<u4"), ("reserved", "<u4")])
+
+
 def _layout_ref(layout):
     return None if layout is None else layout.ref()
 
@@ -255,6 +265,8 @@ def lib():
         L.hmx_intra_plan_destroy_many.argtypes = [vp, C.POINTER(vp), ci]
         L.hmx_intra_plan_destroy_many.restype = None
         L.hmx_last_call_tables_ms.argtypes = [vp, C.POINTER(C.c_float)]
+        if not ("HMX_LIB_PATH" in os.environ and not hasattr(L, "hmx_last_call_pack_tables")):  # (an older build loaded for an A/B run)
+            L.hmx_last_call_pack_tables.argtypes = [vp, C.POINTER(PackGeom), vp, vp, vp, vp, vp]
         L.hmx_intra_plan_destroy.argtypes = [vp, vp]
         L.hmx_intra_plan_destroy.restype = None
         L.hmx_intra_plan_info.argtypes = [vp, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)]
@@ -703,10 +715,22 @@ class Context:
         `avail`), levels: per dependency level start[4], count[4]."""
         nb, nl, nd = C.c_int(), C.c_int(), C.c_int()
         lib().hmx_intra_plan_info(plan, C.byref(nb), C.byref(nl), C.byref(nd))
-        blocks = np.zeros(nb.value, np.dtype(TU_DTYPE.descr + [("avail", "<u8")]))
+        blocks = np.zeros(nb.value, PLAN_BLOCK_DTYPE)
         levels = np.zeros((nl.value, 8), np.uint32)
         self._chk(lib().hmx_intra_plan_download(self.h, plan, _hp(blocks), _hp(levels)))
         return blocks, levels
+
+    def pack_tables(self):
+        """hmx_last_call_pack_tables: the packed schedule's tables of the last whole-picture call as (geom, hdr, rows, descs,
+        items, done) -- geom a PackGeom, hdr one PACK_HDR_DTYPE record, the rest numpy arrays of PACK_ROW_DTYPE,
+        PACK_DESC_DTYPE, PLAN_BLOCK_DTYPE and uint32.  Waits for the stream; raises when the last call was not packed."""
+        g = PackGeom()
+        self._chk(lib().hmx_last_call_pack_tables(self.h, C.byref(g), None, None, None, None, None))
+        hdr = np.zeros(1, PACK_HDR_DTYPE)
+        rows, descs = np.zeros(g.n_rows, PACK_ROW_DTYPE), np.zeros(g.n_waves, PACK_DESC_DTYPE)
+        items, done = np.zeros(g.n_items, PLAN_BLOCK_DTYPE), np.zeros(g.n_rows, np.uint32)
+        self._chk(lib().hmx_last_call_pack_tables(self.h, C.byref(g), _hp(hdr), _hp(rows), _hp(descs), _hp(items), _hp(done)))
+        return g, hdr[0], rows, descs, items, done
 
     def getSAD(self, cur, cur_stride, org, org_stride, w, h, sub_shift=0):
         """hmx_getSAD of one block; cur, org: int16 arrays holding the block at their start with the given strides."""

@@ -283,6 +283,32 @@ static int issue_packed(hmx_ctx *c, const hmx_intra_plan *const *plans, int plan
   c->pk_pending = true;
   return HMX_OK;
 }
+// The packed schedule's tables of the last call, copied out for the test that checks them against the plans (include/hmx.h has
+// the record layouts).  Reads only: neither the tables nor the cache key nor the sticky abort word change.
+extern "C" int hmx_last_call_pack_tables(hmx_ctx *c, hmx_pack_geom *geom, void *hdr, void *rows, void *descs, void *items, uint32_t *done) {
+  if (!c || !geom) return fail(c, HMX_ERR_ARG, "hmx_last_call_pack_tables: bad argument");
+  const auto &pk = c->pk;
+  if (c->last_schedule != 3 || !pk.valid || !pk.d_hdr)
+    return fail(c, HMX_ERR_ARG, "hmx_last_call_pack_tables: the last whole-picture call did not run the packed schedule, or its tables are not valid");
+  static_assert(sizeof(PackRow) == 48 && sizeof(PackDesc) == 16 && sizeof(FTu) == 16 && offsetof(PackHdr, total_items) == 36, "record layouts documented in include/hmx.h");
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  uint32_t h[12] = {};
+  HIPCHK(c, hipMemcpy(h, pk.d_hdr, 10 * sizeof(uint32_t), hipMemcpyDeviceToHost)); // shard_base[9], total_items
+  HIPCHK(c, hipMemcpy(&h[10], &pk.d_hdr->abort, sizeof(uint32_t), hipMemcpyDeviceToHost));
+  const size_t n_rows = (size_t)pk.G.max_levels * pk.G.n_groups;
+  if (h[8] > pk.waves_bound || (size_t)h[8] * sizeof(PackDesc) > pk.cap_descs || (size_t)h[9] * sizeof(FTu) > pk.cap_items || n_rows * sizeof(PackRow) > pk.cap_rows)
+    return fail(c, HMX_ERR_DEVICE, "hmx_last_call_pack_tables: the header's totals exceed the tables");
+  geom->n_pics = pk.G.n_pics, geom->I = pk.G.I, geom->n_groups = pk.G.n_groups, geom->n_shards = pk.G.n_shards;
+  geom->max_levels = pk.G.max_levels, geom->slots4 = pk.G.slots4, geom->slots8 = pk.G.slots8;
+  geom->n_rows = (int)n_rows, geom->n_waves = (int)h[8], geom->n_items = (int)h[9];
+  if (hdr) memcpy(hdr, h, sizeof(h));
+  if (rows && n_rows) HIPCHK(c, hipMemcpy(rows, pk.d_rows, sizeof(PackRow) * n_rows, hipMemcpyDeviceToHost));
+  if (descs && h[8]) HIPCHK(c, hipMemcpy(descs, pk.d_descs, sizeof(PackDesc) * h[8], hipMemcpyDeviceToHost));
+  if (items && h[9]) HIPCHK(c, hipMemcpy(items, pk.d_items, sizeof(FTu) * h[9], hipMemcpyDeviceToHost));
+  if (done && n_rows) // word 0 of every row's 128-byte counter line
+    HIPCHK(c, hipMemcpy2D(done, sizeof(uint32_t), pk.d_done, sizeof(uint32_t) * kDoneStride, sizeof(uint32_t), n_rows, hipMemcpyDeviceToHost));
+  return HMX_OK;
+}
 
 // The across schedule with the layout conversions pipelined by CTU row.  The chain is latency-bound and leaves the
 // memory system idle; the conversions are pure traffic.  CTU row r is converted in (stream `conv`) before the first

@@ -11,35 +11,23 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import oracle_lib as ol  # noqa: E402
-from thevc_amd import capi  # noqa: E402
 from thevc_amd.decisions import load_pictures, split_blocks  # noqa: E402
 
-O, L = ol.oracle(), capi.lib()
+import plan_check  # noqa: E402
+
+O = ol.oracle()
 
 
 def levels(tus, w, h, by_mode):
-    uw, uh = (w + 63) // 64 * 16 + 2, (h + 63) // 64 * 16 + 2
-    g = [np.zeros((uh, uw), np.int32) for _ in range(3)]
-    top = 0
-    for t in tus:
-        pl = int(t["plane"])
-        sh = 1 if pl else 0
-        N = 1 << int(t["log2n"])
-        lx, ly, ls = int(t["x"]) << sh, int(t["y"]) << sh, N << sh
-        n, ux, uy = ls // 4, lx // 4, ly // 4
-        flags = np.zeros(4 * n + 1, np.uint8)
+    """Number of dependency levels (plan_check.plan_levels: the derivation the tests hold the plans against)."""
+    def mask_of(t):
+        sh = 1 if t["plane"] else 0
+        lx, ly, ls = int(t["x"]) << sh, int(t["y"]) << sh, (1 << int(t["log2n"])) << sh
+        flags = np.zeros(4 * (ls // 4) + 1, np.uint8)
         O.hmo_intra_avail(lx, ly, ls, w, h, 64, flags)
-        m = sum(int(b) << u for u, b in enumerate(flags))
-        if by_mode:
-            m = L.hmx_intra_dependency_mask(N, int(pl == 0), int(t["mode"]), m)
-        lv = 0
-        for u in range(4 * n + 1):
-            if (m >> u) & 1:
-                qx, qy = (ux - 1, uy + 2 * n - 1 - u) if u < 2 * n else ((ux - 1, uy - 1) if u == 2 * n else (ux + (u - 2 * n - 1), uy - 1))
-                lv = max(lv, int(g[pl][qy, qx]))
-        g[pl][uy:uy + n, ux:ux + n] = lv + 1
-        top = max(top, lv + 1)
-    return top
+        return plan_check.dependency_mask(t, flags) if by_mode else plan_check.flags_to_mask(flags)
+
+    return 1 + max(plan_check.plan_levels(tus, w, h, mask_of))
 
 
 for path in sorted(glob.glob(os.path.join(ROOT, "tests", "golden", "stream_intra*.npz"))):
