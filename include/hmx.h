@@ -371,6 +371,12 @@ typedef struct hmx_intra_plan hmx_intra_plan;
  * The dependency order of a plan follows these bits, not the availability flags (a horizontal mode does not wait for the
  * block above-right).  Pure host function (no device work); exported for the test that holds it against the oracle. */
 unsigned long long hmx_intra_dependency_mask(int n_samples, int is_luma, int mode, unsigned long long avail);
+/* 1 when the units the mode reads with every neighbour available are not all available, that is when
+ * hmx_intra_dependency_mask(.., avail) differs from hmx_intra_dependency_mask(.., all 4n+1 bits set): the padding of the reference
+ * line then changes a sample the prediction looks at.  0: the padding is the identity on every position the mode reads, and the
+ * whole-picture chains skip it (the plans carry this bit per block and sort by it).  An empty availability gives 1, and so does a
+ * size or mode the function does not know.  Pure host function. */
+int hmx_intra_reads_unavailable(int n_samples, int is_luma, int mode, unsigned long long avail);
 /* The availability flags of initAdiPattern for a block at luma position (x, y) of luma size size_luma (a chroma block: its
  * luma-scaled position and size), CTU size 64: bit u in the bNeighborFlags order, units of four luma samples.  closed_form 0:
  * the unit-by-unit rule (TComPattern.cpp:607-786); 1: the closed form the device plan builder uses.  Pure host functions,

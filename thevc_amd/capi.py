@@ -246,6 +246,9 @@ def lib():
         L.hmx_intra_plan_create.argtypes = [vp, vp, ci, C.POINTER(PicParam), C.POINTER(vp)]
         L.hmx_intra_dependency_mask.argtypes = [ci, ci, ci, C.c_uint64]
         L.hmx_intra_dependency_mask.restype = C.c_uint64
+        if hasattr(L, "hmx_intra_reads_unavailable"):  # (absent from an older build loaded for an A/B run)
+            L.hmx_intra_reads_unavailable.argtypes = [ci, ci, ci, C.c_uint64]
+            L.hmx_intra_reads_unavailable.restype = ci
         L.hmx_intra_avail_mask.argtypes = [ci, ci, ci, ci, ci, ci]
         L.hmx_intra_avail_mask.restype = C.c_uint64
         L.hmx_intra_plan_create_multi.argtypes = [vp, C.POINTER(vp), C.POINTER(ci), ci, C.POINTER(PicParam), C.POINTER(vp)]

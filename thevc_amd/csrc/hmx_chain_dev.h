@@ -100,7 +100,8 @@ __device__ __forceinline__ void wave_chain_valu(char *smem, const SRC &src, cons
     const int pl = t.plane, x = t.x, y = t.y;
     const bool luma = pl == 0, ts = t.flags & HMX_TU_TRANSFORM_SKIP;
     const int scan_idx = coef_scan_idx(N, luma, true, t.mode);
-    const unsigned long long avail = (unsigned long long)ft.avail_lo | ((unsigned long long)ft.avail_hi << 32);
+    const unsigned long long avail = (unsigned long long)ft.avail_lo | ((unsigned long long)(ft.avail_hi & ~kFtuPads) << 32);
+    const bool pads = ft.avail_hi & kFtuPads;
     const PlaneView V = src.view(active ? i : 0, pl);
     const TiledPlane &R = V.rec;
     const unsigned b0 = tile_base(R.ctu_w, R.clog, x, y); // same geometry for org and rec
@@ -111,9 +112,10 @@ __device__ __forceinline__ void wave_chain_valu(char *smem, const SRC &src, cons
     HMX_MARK(N, 1);
     src.wait(); // packed schedule: the blocks this one predicts from belong to earlier rows of the same launch
     HMX_MARK(N, 2);
-    intra_refs_tiled<N, N, SRC::kCoherent>(L, gl, active, R, x, y, pb0, luma, avail, P);
+    const bool filt = N > 4 && luma && use_filtered_refs(t.mode, Log2<N>::v);
+    intra_refs_tiled<N, N, SRC::kCoherent>(L, gl, active, R, x, y, pb0, luma, avail, pads, filt, P);
     HMX_MARK(N, 3);
-    intra_pred_block<N>(L, gl, t.mode, luma, P, pred);
+    intra_pred_block_sel<N>(L, gl, t.mode, luma, filt, wave_needs(t.mode == 1), P, pred);
     HMX_MARK(N, 4);
     if (ENC) {
 #pragma unroll
@@ -196,7 +198,8 @@ __device__ __forceinline__ void wave_chain_8x2(char *smem, const SRC &src, const
   const int pl = t.plane, x = t.x, y = t.y;
   const bool luma = pl == 0, ts = t.flags & HMX_TU_TRANSFORM_SKIP;
   const int scan_idx = coef_scan_idx(N, luma, true, t.mode);
-  const unsigned long long avail = (unsigned long long)ft.avail_lo | ((unsigned long long)ft.avail_hi << 32);
+  const unsigned long long avail = (unsigned long long)ft.avail_lo | ((unsigned long long)(ft.avail_hi & ~kFtuPads) << 32);
+  const bool pads = ft.avail_hi & kFtuPads;
   const PlaneView V = src.view(active ? slot : 0, pl);
   const TiledPlane &R = V.rec;
   const unsigned b0 = tile_base(R.ctu_w, R.clog, x, y);
@@ -210,11 +213,12 @@ __device__ __forceinline__ void wave_chain_8x2(char *smem, const SRC &src, const
   HMX_MARK(82, 1);
   src.wait();
   HMX_MARK(82, 2);
-  intra_refs_tiled<N, NL, SRC::kCoherent>(L, gl, active, R, x, y, pb0, luma, avail, P);
+  const bool filt = luma && use_filtered_refs(t.mode, LG);
+  intra_refs_tiled<N, NL, SRC::kCoherent>(L, gl, active, R, x, y, pb0, luma, avail, pads, filt, P);
   HMX_MARK(82, 3);
   {
-    const int *RL = (luma && use_filtered_refs(t.mode, LG)) ? L.fline : L.line;
-    const int dcs = dc_sum_block<N, NL>(L, gl);
+    const int *RL = filt ? L.fline : L.line;
+    const int dcs = wave_needs(t.mode == 1) ? dc_sum_block<N, NL>(L, gl) : 0; // only when a block of the wave is DC
     build_main_ref<N, NL>(RL, L.me, t.mode, gl);
     wave_sync();
     intra_pred_samples<N, 16>(RL, L.me, t.mode, luma, B, dcs, [&](int s) { return r0 + (s >> 3); }, [](int s) { return s & 7; }, pred);
@@ -534,6 +538,8 @@ __device__ __forceinline__ void wave_chain_4_lane(char *smem, const SRC &src, co
     const int pl = t.plane, x = t.x, y = t.y, mode = t.mode;
     const bool luma = pl == 0, ts = t.flags & HMX_TU_TRANSFORM_SKIP;
     const unsigned avail = ft.avail_lo; // 4n+1 <= 9 units
+    // wave-uniform: the padding loops run only when a block of the wave reads an unavailable unit, the DC sum when one is DC
+    const bool pad_pass = wave_needs(active && (ft.avail_hi & kFtuPads)), any_dc = wave_needs(mode == 1);
     const PlaneView V = src.view(active ? i : 0, pl);
     const TiledPlane &R = V.rec;
     const unsigned b0 = tile_base(R.ctu_w, R.clog, x, y);
@@ -660,36 +666,43 @@ __device__ __forceinline__ void wave_chain_4_lane(char *smem, const SRC &src, co
         for (int k = 0; k < 4; k++) raw[9 + k] = va[k], raw[13 + k] = var[k];
         raw[8] = vc[3];
       }
-      const int dc = 1 << (B - 1);
-      int carry = dc;
-      bool have = false;
-      int lead = dc; // value of a leading unavailable run = first sample of the first available unit
+      if (!pad_pass) { // every position a mode of this wave reads holds its own sample (see intra_refs_tiled)
 #pragma unroll
-      for (int p = 16; p >= 0; p--) {
-        const int u = p < 8 ? (p >> ul) : (p == 8 ? 2 * n : 2 * n + 1 + ((p - 9) >> ul));
-        const bool first_of_unit = p < 8 ? (p & ((1 << ul) - 1)) == 0 : (p == 8 ? true : ((p - 9) & ((1 << ul) - 1)) == 0);
-        if (((avail >> u) & 1) && first_of_unit) lead = raw[p];
-      }
+        for (int p = 0; p <= 16; p++) line[p] = raw[p];
+      } else {
+        const int dc = 1 << (B - 1);
+        int carry = dc;
+        bool have = false;
+        int lead = dc; // value of a leading unavailable run = first sample of the first available unit
 #pragma unroll
-      for (int p = 0; p <= 16; p++) {
-        const int u = p < 8 ? (p >> ul) : (p == 8 ? 2 * n : 2 * n + 1 + ((p - 9) >> ul));
-        int val;
-        if ((avail >> u) & 1) {
-          val = raw[p];
-          have = true;
-        } else {
-          val = have ? carry : lead; // an unavailable unit repeats the last sample before it
+        for (int p = 16; p >= 0; p--) {
+          const int u = p < 8 ? (p >> ul) : (p == 8 ? 2 * n : 2 * n + 1 + ((p - 9) >> ul));
+          const bool first_of_unit = p < 8 ? (p & ((1 << ul) - 1)) == 0 : (p == 8 ? true : ((p - 9) & ((1 << ul) - 1)) == 0);
+          if (((avail >> u) & 1) && first_of_unit) lead = raw[p];
         }
-        carry = val;
-        line[p] = avail ? val : dc;
+#pragma unroll
+        for (int p = 0; p <= 16; p++) {
+          const int u = p < 8 ? (p >> ul) : (p == 8 ? 2 * n : 2 * n + 1 + ((p - 9) >> ul));
+          int val;
+          if ((avail >> u) & 1) {
+            val = raw[p];
+            have = true;
+          } else {
+            val = have ? carry : lead; // an unavailable unit repeats the last sample before it
+          }
+          carry = val;
+          line[p] = avail ? val : dc;
+        }
       }
     }
     // ---- prediction (4x4 never uses the smoothed line)
     int pred[16];
     {
       int dcs = 0;
+      if (any_dc) {
 #pragma unroll
-      for (int k = 1; k <= 4; k++) dcs += line[8 + k] + line[8 - k];
+        for (int k = 1; k <= 4; k++) dcs += line[8 + k] + line[8 - k];
+      }
       int *me = LS.me[lane];
       build_main_ref<4, 1>(line, me, mode, 0);
       intra_pred_samples<4, 16>(line, me, mode, luma, B, dcs, [](int s) { return s >> 2; }, [](int s) { return s & 3; }, pred);
@@ -816,7 +829,8 @@ __device__ __forceinline__ void wave_chain_32(char *smem, const SRC &src, const 
     const hmx_tu t = ft.t;
     const int pl = t.plane, x = t.x, y = t.y;
     const bool luma = pl == 0;
-    const unsigned long long avail = (unsigned long long)ft.avail_lo | ((unsigned long long)ft.avail_hi << 32);
+    const unsigned long long avail = (unsigned long long)ft.avail_lo | ((unsigned long long)(ft.avail_hi & ~kFtuPads) << 32);
+    const bool pads = ft.avail_hi & kFtuPads;
     const PlaneView V = src.view(i, pl);
     const TiledPlane &R = V.rec;
     const unsigned b0 = tile_base(R.ctu_w, R.clog, x, y);
@@ -830,9 +844,10 @@ __device__ __forceinline__ void wave_chain_32(char *smem, const SRC &src, const 
         org4[q] = stream_load(reinterpret_cast<const s4v *>(V.org + row_off + trel<32>(R.qstride, tile_in_block(2 * q + h, r >> 2))));
     }
     src.wait();
-    intra_refs_tiled<32, 64, SRC::kCoherent>(L, lane, true, R, x, y, tphys(R.qstride, b0), luma, avail, P);
-    const int *RL = (luma && use_filtered_refs(t.mode, LG)) ? L.fline : L.line;
-    const int dcs = dc_sum_block<32, 64>(L, lane);
+    const bool filt = luma && use_filtered_refs(t.mode, LG);
+    intra_refs_tiled<32, 64, SRC::kCoherent>(L, lane, true, R, x, y, tphys(R.qstride, b0), luma, avail, pads, filt, P);
+    const int *RL = filt ? L.fline : L.line;
+    const int dcs = wave_needs(t.mode == 1) ? dc_sum_block<32, 64>(L, lane) : 0;
     build_main_ref<32, 64>(RL, L.me, t.mode, lane);
     wave_sync();
     intra_pred_samples<32, 16>(RL, L.me, t.mode, luma, P.bit_depth, dcs, [&](int) { return r; }, [&](int s) { return mrow(s, h); }, pred);

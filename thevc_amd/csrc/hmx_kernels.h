@@ -449,19 +449,28 @@ __device__ __forceinline__ void intra_refs(TuLds<N> &L, int gl, bool active, Fet
 // Units outside the mask are not loaded (one address stands in for all of them); the reference's
 // padding rule then runs on the raw samples in LDS: position p copies sample q(p), the nearest available sample
 // before it (the first available one for a leading run), exactly as build_ref_line picks its load address.
-// pb0 = element index of the block's first sample.  Leaves L.line (raw) and L.fline (smoothed, luma N > 4).
-template <int N, int NL, bool COH, typename LT>
-__device__ __forceinline__ void intra_refs_tiled(LT &L, int gl, bool active, const TiledPlane &R, int x, int y, size_t pb0,
-                                                 bool luma, unsigned long long avail, const PicDev &P) {
+// pb0 = element index of the block's first sample.  Leaves L.line (raw) and L.fline (smoothed, where a block uses it).
+// Three things are done for the WAVE only when one of its blocks needs them (wave-uniform branches):
+//   the padding pass   pads = the block's mode reads a unit outside the mask (FTu's kFtuPads).  Without it every position the mode
+//                      reads holds its own gathered sample, the rule is the identity there, and the samples go straight into L.line;
+//                      the other positions keep whatever the stand-in load returned, and no mode looks at them;
+//   the smoothed line  smooth = the block predicts from L.fline (use_filtered_refs, luma, N > 4);
+//   64-bit masks       M = unsigned wherever the 4n+1 units fit 32 bits (N <= 8, 16x16 luma).
+#ifndef HMX_X_REFS
+#define HMX_X_REFS 0 /* timing and static-count experiments: 1 every wave takes the three skips (results wrong), 2 none does */
+#endif
+__device__ __forceinline__ bool wave_needs(bool v) { return HMX_X_REFS == 1 ? false : HMX_X_REFS == 2 ? true : __any(v); } // some lane of the wave
+__device__ __forceinline__ int mask_top(unsigned m) { return 31 - __clz((int)m); } // highest / lowest set bit of a mask that has one
+__device__ __forceinline__ int mask_top(unsigned long long m) { return 63 - __clzll((long long)m); }
+__device__ __forceinline__ int mask_first(unsigned m) { return __ffs((int)m) - 1; }
+__device__ __forceinline__ int mask_first(unsigned long long m) { return __ffsll((long long)m) - 1; }
+template <int N, int NL, bool COH, typename M, typename LT>
+__device__ __forceinline__ void refs_gather_pad(LT &L, int gl, bool active, const TiledPlane &R, int x, int y, const short *idle, bool luma,
+                                                M avail, bool pad_pass, int bit_depth) {
   constexpr int T = 2 * N + 1 + N / 2, IT = (T + NL - 1) / NL;
   const int ul = luma ? 2 : 1, n = N >> ul;
-  // loads of units outside the mask name ONE address in the whole wave (the first lane's block: a valid address in any picture's
-  // pool), which the memory pipe serves as a single request
-  const short *own = R.p + pb0;
-  const short *idle = reinterpret_cast<const short *>((uintptr_t)(((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)((uintptr_t)own >> 32)) << 32) |
-                                                                 (unsigned)__builtin_amdgcn_readfirstlane((int)(uintptr_t)own)));
+  s4v v[IT];
   if (active) {
-    s4v v[IT];
 #pragma unroll
     for (int it = 0; it < IT; it++) {
       const int t = gl + it * NL;
@@ -480,20 +489,28 @@ __device__ __forceinline__ void intra_refs_tiled(LT &L, int gl, bool active, con
         v[it] = ld_rec4<COH>(on ? R.p + tphys(R.qstride, tile_base(R.ctu_w, R.clog, tx, ty) + ((unsigned)(ty & 3) << 2)) : idle);
       }
     }
+  }
+  const auto put = [&](int *dst) {
 #pragma unroll
-    for (int it = 0; it < IT; it++) { // raw samples wait in L.fline (free until the smoothing pass)
+    for (int it = 0; it < IT; it++) {
       const int t = gl + it * NL;
       if (t <= 2 * N) {
-        L.fline[t] = v[it][3];
+        dst[t] = v[it][3];
       } else if (t < T) {
         const int p0 = 2 * N + 1 + 4 * (t - 2 * N - 1);
-        L.fline[p0] = v[it][0], L.fline[p0 + 1] = v[it][1], L.fline[p0 + 2] = v[it][2], L.fline[p0 + 3] = v[it][3];
+        dst[p0] = v[it][0], dst[p0 + 1] = v[it][1], dst[p0 + 2] = v[it][2], dst[p0 + 3] = v[it][3];
       }
     }
+  };
+  if (!pad_pass) { // no block of the wave pads
+    if (active) put(L.line);
+    wave_sync();
+    return;
   }
+  if (active) put(L.fline); // raw samples wait in L.fline (free until the smoothing pass)
   wave_sync();
   if (active) {
-    const int unit = 1 << ul, dcv = 1 << (P.bit_depth - 1);
+    const int unit = 1 << ul, dcv = 1 << (bit_depth - 1);
 #pragma unroll
     for (int it = 0; it < (4 * N + 1 + NL - 1) / NL; it++) {
       const int p = gl + it * NL;
@@ -503,12 +520,12 @@ __device__ __forceinline__ void intra_refs_tiled(LT &L, int gl, bool active, con
           const int u = p < 2 * N ? (p >> ul) : (p == 2 * N ? 2 * n : 2 * n + 1 + ((p - 2 * N - 1) >> ul));
           int q = p;
           if (!((avail >> u) & 1)) {
-            const unsigned long long lower = avail & ((1ull << u) - 1);
+            const M lower = avail & ((M(1) << u) - 1);
             if (lower) {
-              const int u2 = 63 - __clzll((long long)lower); // last sample of the nearest available unit below
+              const int u2 = mask_top(lower); // last sample of the nearest available unit below
               q = u2 < 2 * n ? (u2 << ul) + unit - 1 : (u2 == 2 * n ? 2 * N : 2 * N + ((u2 - 2 * n) << ul));
             } else {
-              const int u2 = __ffsll((long long)avail) - 1; // first sample of the first available unit
+              const int u2 = mask_first(avail); // first sample of the first available unit
               q = u2 < 2 * n ? (u2 << ul) : (u2 == 2 * n ? 2 * N : 2 * N + 1 + ((u2 - 2 * n - 1) << ul));
             }
           }
@@ -519,8 +536,24 @@ __device__ __forceinline__ void intra_refs_tiled(LT &L, int gl, bool active, con
     }
   }
   wave_sync();
-  if (active && luma && N > 4) smooth_ref_line<N, NL>(L.line, L.fline, gl); // 4x4 never uses the smoothed line
-  wave_sync();
+}
+template <int N, int NL, bool COH, typename LT>
+__device__ __forceinline__ void intra_refs_tiled(LT &L, int gl, bool active, const TiledPlane &R, int x, int y, size_t pb0,
+                                                 bool luma, unsigned long long avail, bool pads, bool smooth, const PicDev &P) {
+  // loads of units outside the mask name ONE address in the whole wave (the first lane's block: a valid address in any picture's
+  // pool), which the memory pipe serves as a single request
+  const short *own = R.p + pb0;
+  const short *idle = reinterpret_cast<const short *>((uintptr_t)(((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)((uintptr_t)own >> 32)) << 32) |
+                                                                 (unsigned)__builtin_amdgcn_readfirstlane((int)(uintptr_t)own)));
+  const bool pad_pass = wave_needs(active && pads);
+  if (N <= 8 || (N == 16 && __all(luma))) // 4n+1 <= 17 units; 32x32 luma and 16x16 chroma have 33
+    refs_gather_pad<N, NL, COH, unsigned>(L, gl, active, R, x, y, idle, luma, (unsigned)avail, pad_pass, P.bit_depth);
+  else
+    refs_gather_pad<N, NL, COH, unsigned long long>(L, gl, active, R, x, y, idle, luma, avail, pad_pass, P.bit_depth);
+  if (N > 4 && wave_needs(active && smooth)) { // 4x4 never uses the smoothed line
+    if (active && smooth) smooth_ref_line<N, NL>(L.line, L.fline, gl);
+    wave_sync();
+  }
 }
 
 // sum of the N above + N left neighbours, shared by the block's NL lanes (DC mode)
@@ -531,16 +564,22 @@ __device__ __forceinline__ int dc_sum_block(const LT &L, int gl) {
   return group_sum(s, NL);
 }
 
-// luma: edge filters of the angular/DC modes (bFilter) and, unless raw_line, the smoothed reference line
-// where getPredictorPtr picks it
+// filt = predict from the smoothed line; need_dc (wave-uniform) = form the DC sum: its shuffles are executed by every lane of the
+// wave.  The whole-picture chains pass what they evaluated for intra_refs_tiled and form the sum only when a block of the wave is DC.
 template <int N>
-__device__ __forceinline__ void intra_pred_block(TuLds<N> &L, int gl, int mode, bool luma, const PicDev &P, int *p, bool raw_line = false) {
-  const int *R = (luma && !raw_line && use_filtered_refs(mode, Log2<N>::v)) ? L.fline : L.line;
-  const int dcs = dc_sum_block<N, N>(L, gl); // shuffles: every lane of the wave executes this
+__device__ __forceinline__ void intra_pred_block_sel(TuLds<N> &L, int gl, int mode, bool luma, bool filt, bool need_dc, const PicDev &P, int *p) {
+  const int *R = filt ? L.fline : L.line;
+  const int dcs = need_dc ? dc_sum_block<N, N>(L, gl) : 0;
   build_main_ref<N, N>(R, L.me, mode, gl);
   wave_sync();
   intra_pred_samples<N, N>(R, L.me, mode, luma, P.bit_depth, dcs, [&](int) { return gl; }, [](int s) { return s; }, p);
   wave_sync(); // L.me is rebuilt by the next call (mode fan-out)
+}
+// luma: edge filters of the angular/DC modes (bFilter) and, unless raw_line, the smoothed reference line
+// where getPredictorPtr picks it
+template <int N>
+__device__ __forceinline__ void intra_pred_block(TuLds<N> &L, int gl, int mode, bool luma, const PicDev &P, int *p, bool raw_line = false) {
+  intra_pred_block_sel<N>(L, gl, mode, luma, luma && !raw_line && use_filtered_refs(mode, Log2<N>::v), true, P, p);
 }
 
 // calcHAD of an N x N block (TComRdCost.cpp:404-450): Hadamard SATD over its 8x8 sub-blocks (4x4 for N = 4),

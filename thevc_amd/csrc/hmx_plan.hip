@@ -74,9 +74,9 @@ static unsigned long long intra_needed_units(int n_s, bool luma, int mode) {
     if (need[p]) units |= 1ull << (p < 2 * N ? p / U : p == 2 * N ? 2 * n : 2 * n + 1 + (p - 2 * N - 1) / U);
   return units;
 }
-unsigned long long intra_dependency_mask(int n_s, bool luma, int mode, unsigned long long avail) {
-  if ((n_s != 4 && n_s != 8 && n_s != 16 && n_s != 32) || mode < 0 || mode > 34) return avail; // not a mode this function knows: every neighbour
-  struct Table { // what a mode reads depends on (size, texture type, mode) only: 280 masks, formed once
+// what a mode reads depends on (size, texture type, mode) only: 280 masks, formed once
+static unsigned long long intra_reach_mask(int n_s, bool luma, int mode) {
+  struct Table {
     unsigned long long u[4][2][35];
     Table() {
       for (int lg = 2; lg <= 5; lg++)
@@ -85,8 +85,12 @@ unsigned long long intra_dependency_mask(int n_s, bool luma, int mode, unsigned 
     }
   };
   static const Table T;
+  return T.u[ilog2i(n_s) - 2][luma ? 1 : 0][mode];
+}
+unsigned long long intra_dependency_mask(int n_s, bool luma, int mode, unsigned long long avail) {
+  if ((n_s != 4 && n_s != 8 && n_s != 16 && n_s != 32) || mode < 0 || mode > 34) return avail; // not a mode this function knows: every neighbour
   const int n = n_s / (luma ? 4 : 2);
-  const unsigned long long units = T.u[ilog2i(n_s) - 2][luma ? 1 : 0][mode];
+  const unsigned long long units = intra_reach_mask(n_s, luma, mode);
   unsigned long long dep = units & avail;
   if (!(units & ~avail)) return dep;
   for (int u = 0; u <= 4 * n; u++) // padding: the value of an unavailable unit that is read
@@ -98,6 +102,16 @@ unsigned long long intra_dependency_mask(int n_s, bool luma, int mode, unsigned 
 }
 extern "C" unsigned long long hmx_intra_dependency_mask(int n_samples, int is_luma, int mode, unsigned long long avail) {
   return intra_dependency_mask(n_samples, is_luma != 0, mode, avail);
+}
+// The mask above differs from the one with every unit available exactly when a unit the mode reads is missing: with all of them
+// there it is the reach itself; with one missing it is a subset of the availability and so lacks that unit.
+bool intra_reads_unavailable(int n_s, bool luma, int mode, unsigned long long avail) {
+  if ((n_s != 4 && n_s != 8 && n_s != 16 && n_s != 32) || mode < 0 || mode > 34) return true; // not a mode this function knows: pad
+  if (!luma && n_s == 32) return true; // 65 units do not fit the mask (no such block in 4:2:0 with 32x32 luma transforms): pad
+  return (intra_reach_mask(n_s, luma, mode) & ~avail) != 0;
+}
+extern "C" int hmx_intra_reads_unavailable(int n_samples, int is_luma, int mode, unsigned long long avail) {
+  return intra_reads_unavailable(n_samples, is_luma != 0, mode, avail) ? 1 : 0;
 }
 
 // A slice / tile / CIP layout checked against the picture and packed for intra_avail_mask_layout (hmx_device.h): the region map as
@@ -181,6 +195,8 @@ static const char *plan_build_host(const hmx_ctx *c, const hmx_tu *tus, int n_tu
   std::vector<FTu> stus;
   stus.reserve(n_tu);
   std::vector<unsigned long long> masks(n_tu), deps(n_tu);
+  std::vector<uint8_t> pads(n_tu); // the mode reads an unavailable unit: FTu's kFtuPads
+  auto desc_of = [&](int i) { return FTu{tus[i], (uint32_t)deps[i], (uint32_t)(deps[i] >> 32) | (pads[i] ? kFtuPads : 0u)}; };
   std::vector<Seg> segs;
   std::vector<uint32_t> seg_range((size_t)n_ctu * 3 * 2);
   std::vector<int> level(n_tu);
@@ -195,6 +211,7 @@ static const char *plan_build_host(const hmx_ctx *c, const hmx_tu *tus, int n_tu
       unsigned long long m = intra_avail_mask(lx, ly, ls, P);
       if (use_layout) m = intra_avail_mask_layout(m, lx, ly, ls, 2, lay.D); // a subset: the schedules below stay valid
       masks[id] = m;
+      pads[id] = intra_reads_unavailable(1 << t.log2n, t.plane == 0, t.mode, m);
       m = intra_dependency_mask(1 << t.log2n, t.plane == 0, t.mode, m); // the order follows what the mode reads
       deps[id] = m;
       int lv = 0;
@@ -231,7 +248,7 @@ static const char *plan_build_host(const hmx_ctx *c, const hmx_tu *tus, int n_tu
       s.new_level = (k == 0 || level[ids[k]] != level[ids[k - 1]]) ? 1 : 0;
       segs.push_back(s);
       for (size_t q = k; q < e; q++)
-        stus.push_back(FTu{tus[ids[q]], (uint32_t)deps[ids[q]], (uint32_t)(deps[ids[q]] >> 32)}); // (see ltus below)
+        stus.push_back(desc_of(ids[q])); // (see ltus below)
       k = e;
     }
     seg_range[(size_t)b * 2 + 1] = (uint32_t)segs.size();
@@ -292,16 +309,19 @@ static const char *plan_build_host(const hmx_ctx *c, const hmx_tu *tus, int n_tu
     }
     // Blocks of one (level, size) bucket are independent: order them so that the 64/N blocks that
     // share a wave take the same code paths (plane class = DST vs DCT and chroma rules, transform
-    // skip, prediction mode class, then mode) instead of diverging.
+    // skip, padding pass or none, prediction mode class, then mode) instead of diverging.  Cb and Cr run the same code: blocks
+    // of one mode keep their coding order whichever of the two they belong to (the device builder's key has no room for both
+    // that bit and the padding one, and the two builders give the same order).
     auto mode_class = [](int m) { return m == 0 ? 0 : m == 1 ? 1 : (m == 10 || m == 26) ? 2 : (m > 10 && m < 26) ? 3 : 4; };
-    auto path_key = [&](const hmx_tu &t) {
-      return (uint32_t)((t.plane ? 1u : 0u) << 24 | (uint32_t)(t.flags & 1u) << 20 | (uint32_t)mode_class(t.mode) << 16 |
-                        (uint32_t)t.mode << 8 | t.plane);
+    auto path_key = [&](int i) {
+      const hmx_tu &t = tus[i];
+      return (uint32_t)((t.plane ? 1u : 0u) << 24 | (uint32_t)(t.flags & 1u) << 20 | (pads[i] ? 1u : 0u) << 19 |
+                        (uint32_t)mode_class(t.mode) << 16 | (uint32_t)t.mode << 8);
     };
     // one 64-bit key per block (level | size | path | coding order): a plain sort of integers, no comparator that chases indices
     std::vector<uint64_t> order(n_tu);
     for (int i = 0; i < n_tu; i++)
-      order[i] = ((uint64_t)(uint32_t)glevel[i] << 48) | ((uint64_t)(tus[i].log2n - 2) << 46) | ((uint64_t)(path_key(tus[i]) & 0x3ffffffu) << 20) |
+      order[i] = ((uint64_t)(uint32_t)glevel[i] << 48) | ((uint64_t)(tus[i].log2n - 2) << 46) | ((uint64_t)(path_key(i) & 0x3ffffffu) << 20) |
                  (uint64_t)(uint32_t)i;
     static_assert(sizeof(int) == 4, "block index in the low 20 bits needs n_tu < 2^20");
     if (n_tu >= (1 << 20) || max_level >= (1 << 16)) return "hmx_intra_plan_create: picture too large for one plan";
@@ -312,7 +332,7 @@ static const char *plan_build_host(const hmx_ctx *c, const hmx_tu *tus, int n_tu
       // with the availability (the mask is closed under the padding rule: the source of every padded unit that is read is in it, and it
       // is the nearest unit of the mask before the padded one because it is the nearest available one), positions the mode does not read
       // get padded values instead of samples nobody looks at -- and a third to a half of the reference loads are not made at all.
-      ltus[k] = FTu{tus[i], (uint32_t)deps[i], (uint32_t)(deps[i] >> 32)};
+      ltus[k] = desc_of(i);
     }
   }
   // CTU diagonals d = X + 2Y: (X,Y) needs (X-1,Y), (X-1,Y-1), (X,Y-1), (X+1,Y-1)
@@ -581,7 +601,7 @@ static void plan_release(hmx_ctx *c, hmx_intra_plan *pl) {
 //                   the keys broadcast to the wave as scalars) -> position; the block descriptor moves there.
 // The result is the host's table entry for entry: the same levels (the longest path in the dependency graph does not depend
 // on the visiting order as long as every dependency precedes its dependent, which coding order guarantees) and the same
-// order inside a bucket (plane class, transform skip, mode class, mode, plane, coding index).
+// order inside a bucket (plane class, transform skip, padding pass, mode class, mode, coding index).
 // Reference for what is reproduced: TLibCommon/TComPattern.cpp:389-425 (which neighbours a block reads), :607-786 + TComDataCU.cpp
 // :1221-1735 (availability), TComPrediction.cpp:179-290, 689-730 (what a mode reads of them).
 // =============================================================================================
@@ -663,7 +683,8 @@ __global__ __launch_bounds__(256) void k_plan_ctus(const hmx_tu *tus, const uint
         unsigned long long avail = intra_avail_mask_fast(lx, ly, ls, G.P);
         if constexpr (LAYOUT) avail = intra_avail_mask_layout(avail, lx, ly, ls, 2, lays[pic]);
         const unsigned long long dep = plan_dep_mask(need, t.log2n, t.plane == 0, t.mode, avail);
-        ftu[b0 + i] = FTu{t, (uint32_t)dep, (uint32_t)(dep >> 32)}; // the descriptor as the chain wants it (plan_build_host: the units read stand for the availability), moved into place by k_plan_gather
+        const bool pads = t.mode > 34 || (t.plane != 0 && t.log2n == 5) || (need[((t.log2n - 2) * 2 + (t.plane == 0 ? 1 : 0)) * 35 + t.mode] & ~avail) != 0; // intra_reads_unavailable
+        ftu[b0 + i] = FTu{t, (uint32_t)dep, (uint32_t)(dep >> 32) | (pads ? kFtuPads : 0u)}; // the descriptor as the chain wants it (plan_build_host: the units read stand for the availability), moved into place by k_plan_gather
         rec[b0 + i] = dep | (unsigned long long)((lx & 63) >> 2) << 40 | (unsigned long long)((ly & 63) >> 2) << 44 | (unsigned long long)(ls >> 2) << 48 |
                       (unsigned long long)t.plane << 52 | (unsigned long long)(t.log2n - 2) << 54;
       }
@@ -885,10 +906,11 @@ __global__ __launch_bounds__(1024) void k_plan_scan(PlanTabArgs A) {
       at += tab[l].count[s];
     }
 }
-// the order inside a bucket: plane class, transform skip, mode class, mode, plane (plan_build_host's path_key), 12 bits
-__device__ __forceinline__ uint32_t plan_path_key(const hmx_tu &t) {
+// the order inside a bucket: plane class, transform skip, padding pass, mode class, mode (plan_build_host's path_key), 12 bits
+__device__ __forceinline__ uint32_t plan_path_key(const FTu &f) {
+  const hmx_tu &t = f.t;
   const int m = t.mode, mc = m == 0 ? 0 : m == 1 ? 1 : (m == 10 || m == 26) ? 2 : (m > 10 && m < 26) ? 3 : 4;
-  return (t.plane ? 1u : 0u) << 11 | (uint32_t)(t.flags & 1u) << 10 | (uint32_t)mc << 7 | (uint32_t)(m & 63) << 1 | (t.plane == 2 ? 1u : 0u);
+  return (t.plane ? 1u : 0u) << 11 | (uint32_t)(t.flags & 1u) << 10 | (f.avail_hi & kFtuPads ? 1u : 0u) << 9 | (uint32_t)mc << 6 | (uint32_t)(m & 63);
 }
 // Scatter and gather permute a picture's blocks inside its own few megabytes: random 4- and 16-byte accesses, each of which
 // costs a whole 128-byte line when it comes from HBM.  Workgroups are dealt to the XCDs round-robin by their id, so the id is
@@ -906,9 +928,9 @@ __global__ __launch_bounds__(256) void k_plan_scatter(PlanTabArgs A, uint32_t pe
   if (!plan_xcd_picture(per_pic, A.G.n_pics, pic, chunk)) return;
   const uint32_t b0 = A.pic_off[pic], n = A.pic_off[pic + 1] - b0, i = chunk * 256 + threadIdx.x;
   if (i >= n) return;
-  const hmx_tu t = A.tus[b0 + i];
-  const uint32_t pos = atomicAdd(&A.cursor[((size_t)A.ltab_off[pic] + A.level[b0 + i]) * 4 + (t.log2n - 2)], 1u);
-  A.keys[b0 + pos] = plan_path_key(t) << 20 | i;
+  const FTu f = A.ftu[b0 + i]; // (the block as given, and whether it pads)
+  const uint32_t pos = atomicAdd(&A.cursor[((size_t)A.ltab_off[pic] + A.level[b0 + i]) * 4 + (f.t.log2n - 2)], 1u);
+  A.keys[b0 + pos] = plan_path_key(f) << 20 | i;
 }
 // The order inside a bucket, one WAVE per (level, size) bucket: a block's place is the number of keys of its bucket below its own
 // (the keys of a picture are distinct: the coding index is part of them).  A wave holds 64 keys at a time and counts against
@@ -1283,7 +1305,10 @@ int plan_host_tables(hmx_ctx *c, const hmx_intra_plan *cpl) {
 extern "C" int hmx_intra_plan_download(hmx_ctx *c, const hmx_intra_plan *pl, void *blocks, void *levels) {
   if (!c || !pl) return fail(c, HMX_ERR_ARG, "hmx_intra_plan_download: bad argument");
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (blocks) HIPCHK(c, hipMemcpy(blocks, pl->d_ltus, sizeof(FTu) * (size_t)pl->n_tu, hipMemcpyDeviceToHost));
+  if (blocks) {
+    HIPCHK(c, hipMemcpy(blocks, pl->d_ltus, sizeof(FTu) * (size_t)pl->n_tu, hipMemcpyDeviceToHost));
+    for (int i = 0; i < pl->n_tu; i++) static_cast<FTu *>(blocks)[i].avail_hi &= ~kFtuPads; // the caller gets the mask alone
+  }
   if (levels) HIPCHK(c, hipMemcpy(levels, pl->d_ltab, sizeof(LevelRow) * (size_t)pl->n_levels, hipMemcpyDeviceToHost));
   return HMX_OK;
 }
