@@ -646,6 +646,35 @@ typedef struct { int16_t mvx, mvy; uint32_t sad; uint32_t cost; } hmx_me_result;
 int hmx_batch_fullpel_search(hmx_ctx *ctx, const hmx_me_unit *units, int n, const hmx_pic *refs, int n_refs, const hmx_pic *org,
                              int pic_w, int pic_h, int margin_x, int margin_y, uint32_t lambda, hmx_me_result *d_result,
                              uint32_t *d_cost_map);
+/* TEncSearch::xPatternSearchFracDIF (TEncSearch.cpp:4476-4514) for every unit of `units`, both stages and both decisions of
+ * xPatternRefinement (:711-760) in one launch, from the integer winners where hmx_batch_fullpel_search left them.
+ * units: the HOST array given to the integer search (position, size, ref, predictor, box; sub_shift is ignored: setDistParam
+ * sets iSubShift = 0 for the refinement, TComRdCost.cpp:380).  d_int (DEVICE): d_int[i].mvx / mvy = the integer vector (ix, iy)
+ * of unit i, the only fields read; normally the search's own d_result.  lambda: m_uiLambdaMotionSAD, as for the integer stage.
+ * D(mv) = the distortion hmx_batch_subpel_cost documents (two-stage prediction, Hadamard sum (use_had = 1) or SAD (0) over
+ * 8x8 / 4x4 sub-blocks, >> (bit depth - 8)).  All arithmetic uint32_t.  Nine candidates per stage in table order:
+ *   half    (s_acMvRefineH, :47-58)  k = (0,0) (0,-1) (0,1) (-1,0) (1,0) (-1,-1) (1,-1) (-1,1) (1,1)
+ *           cost = D(4ix + 2dx, 4iy + 2dy) + hmx_mvCost(lambda, 2ix + dx, 2iy + dy, pred, 1); winner (hx, hy)
+ *   quarter (s_acMvRefineQ, :60-71)  k = (0,0) (0,-1) (0,1) (-1,-1) (1,-1) (-1,0) (1,0) (-1,1) (1,1), base = (4ix + 2hx, 4iy + 2hy)
+ *           cost = D(base + q) + hmx_mvCost(lambda, base.x + qx, base.y + qy, pred, 0)
+ * The winner of a stage is the first candidate in table order with the strictly smallest cost (uiDistBest = MAX_UINT).
+ * d_result[i] (device) = {the winning quarter-sample vector, dist = cost - hmx_mvCost(lambda, mvx, mvy, pred, 0), cost = the
+ * winning quarter-stage cost}.  d_stage_cost (device, may be NULL): [i * 18 + k] = half-stage cost k, [i * 18 + 9 + k] =
+ * quarter-stage cost k.  The tail of xMotionEstimation (:4197-4205: getBits, the fWeight floor) stays with the caller.
+ * refs / org as for hmx_batch_fullpel_search (org may be 2 * org - other prediction).  Not covered: weighted distortion
+ * (xGetSADw, bApplyWeight) and the non-square Hadamard shapes of NS_HAD with UseNSQT.
+ * The 18 candidates read the (w + 8) x (h + 8) window from 4 samples left of and above the displaced block.  The integer
+ * vectors are device data the host cannot see, so the host checks the box: a unit whose integer vector lies OUTSIDE its own
+ * box is not refined and reads no reference sample: its result is {4 * ix, 4 * iy truncated to int16_t, dist = cost =
+ * 0xFFFFFFFF} and its 18 stage costs are 0xFFFFFFFF; the other units of the call are unaffected.
+ * HMX_ERR_ARG, on the host before anything is launched, with the unit named in hmx_last_error: a NULL pointer other than
+ * d_stage_cost, n < 1, n_refs outside 1..4, use_had other than 0 or 1, a size outside the set, ref >= n_refs, an empty box, the
+ * unit outside the picture, the box grown by the window (columns x + left - 4 .. x + right + w + 3, rows likewise) reaching
+ * outside [-margin, pic + margin) in either direction. */
+typedef struct { int16_t mvx, mvy; uint32_t dist; uint32_t cost; } hmx_subpel_result; /* quarter samples; 12 bytes */
+int hmx_batch_subpel_search(hmx_ctx *ctx, const hmx_me_unit *units, int n, const hmx_me_result *d_int, const hmx_pic *refs,
+                            int n_refs, const hmx_pic *org, int pic_w, int pic_h, int margin_x, int margin_y, uint32_t lambda,
+                            int use_had, hmx_subpel_result *d_result, uint32_t *d_stage_cost);
 
 /* Deblocking filter, the application part (TLibCommon/TComLoopFilter.cpp:571-922: xEdgeFilterLuma, xEdgeFilterChroma,
  * the pel filters, the strong/weak decision), in place on a reconstructed picture whose size

@@ -1,0 +1,318 @@
+"""hmx_batch_subpel_search on the GPU against tests/subpel_oracle.py, everything compared for equality: every unit size with
+all 18 stage costs, the stage costs against the pinned hmx_batch_subpel_cost, the chain from hmx_batch_fullpel_search without a
+download between the calls, ties that the table order decides, originals outside the sample range, 12 bit at the range ends,
+d_stage_cost = NULL and determinism, every refusal of the host and the sentinel for an integer vector outside its box, and
+xMotionEstimation through the C++ host mirror.  A 192 x 128 picture with margin 80 (the pictures of tests/test_gpu_me.py)."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import me_oracle as mo
+import subpel_oracle as so
+import test_gpu_me as tgm
+from thevc_amd import capi
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+EXE = os.path.join(ROOT, "thevc_amd", "host", "hm_mirror_test")
+W, H, M = tgm.W, tgm.H, tgm.M
+ONES = 0xFFFFFFFF
+OFFS49 = [(dx, dy) for dy in range(-3, 4) for dx in range(-3, 4)]
+
+
+@pytest.fixture(scope="module", params=[8, 10])
+def ctx(request):
+    c = capi.Context(bit_depth=request.param)
+    yield c
+    c.close()
+
+
+@pytest.fixture(scope="module")
+def textured(ctx):
+    p = tgm.make_textured(ctx)
+    yield p
+    p.free()
+
+
+def ints_of(vectors):
+    a = np.zeros(len(vectors), capi.ME_RESULT_DTYPE)
+    a["mvx"], a["mvy"] = [v[0] for v in vectors], [v[1] for v in vectors]
+    a["sad"], a["cost"] = 0xDEADBEEF, 0xDEADBEEF  # the entry reads the vector alone
+    return a
+
+
+def expect(pics, units, ints, lam, use_had):
+    """The oracle's results, stage costs and winners of every unit."""
+    B = pics.ctx.bit_depth
+    return [so.refine_unit(pics.org_h, pics.full[int(u["ref"])], (M, M), u, int(v["mvx"]), int(v["mvy"]), lam, B, use_had) for u, v in zip(units, ints)]
+
+
+def check(pics, units, ints, lam, use_had, label):
+    res, costs = pics.ctx.batch_subpel_search(units, ints, pics.refs, pics.org, W, H, M, M, lam, use_had, want_stage_costs=True)
+    want = expect(pics, units, ints, lam, use_had)
+    for i, (r, wnt) in enumerate(zip(res, want)):
+        assert [int(c) for c in costs[i]] == wnt[1], (label, i, units[i], ints[i])
+        assert (int(r["mvx"]), int(r["mvy"]), int(r["dist"]), int(r["cost"])) == wnt[0], (label, i, units[i], ints[i])
+    return res, costs, want
+
+
+def size_units(rng):
+    """At least 40 units: every width and height of the set, both references, vectors inside the box and at its corners, and
+    units at the four picture corners whose windows reach the outermost sample of the margins."""
+    shapes = [(8, 4), (4, 8), (12, 16), (16, 4), (24, 32), (64, 48), (64, 64), (4, 4), (8, 8), (16, 12), (32, 24), (48, 64), (32, 32), (16, 16),
+              (48, 16), (16, 64), (24, 8), (12, 48)]
+    assert {s[0] for s in shapes} == set(mo.SIZES) == {s[1] for s in shapes}
+    units, vecs = [], []
+    for k, (w, h) in enumerate(shapes * 2):
+        x, y = int(rng.integers(0, (W - w) // 4 + 1)) * 4, int(rng.integers(0, (H - h) // 4 + 1)) * 4
+        l, t = int(rng.integers(-12, 1)), int(rng.integers(-12, 1))
+        r, b = l + int(rng.integers(0, 14)), t + int(rng.integers(0, 14))
+        units.append(tgm.unit(x, y, w, h, k % 2, k % 2 if h > 8 else 0, int(rng.integers(-60, 61)), int(rng.integers(-60, 61)), l, t, r, b))
+        corners = [(l, t), (r, t), (l, b), (r, b)]
+        vecs.append(corners[k % 4] if k % 3 == 0 else (int(rng.integers(l, r + 1)), int(rng.integers(t, b + 1))))
+    for k, (w, h) in enumerate(((16, 16), (64, 64), (4, 4), (8, 16))):  # the picture corners; the box ends where the window meets the margin's end
+        for (x, y, sx, sy) in ((0, 0, -1, -1), (W - w, 0, 1, -1), (0, H - h, -1, 1), (W - w, H - h, 1, 1)):
+            ex, ey = sx * (M - 4), sy * (M - 4)
+            l, r, t, b = min(ex, ex - 3 * sx), max(ex, ex - 3 * sx), min(ey, ey - 3 * sy), max(ey, ey - 3 * sy)
+            units.append(tgm.unit(x, y, w, h, (k + (x > 0)) % 2, 0, 4 * ex + 3, 4 * ey - 5, l, t, r, b))
+            vecs.append((ex, ey))
+    units = np.concatenate(units)
+    assert len(units) >= 40 and set(units["ref"]) == {0, 1}
+    return units, ints_of(vecs)
+
+
+# ---- 1. every size against the oracle ----
+@pytest.mark.parametrize("use_had", [1, 0])
+def test_sizes_vs_oracle(ctx, textured, use_had):
+    units, ints = size_units(np.random.default_rng(900 + ctx.bit_depth))
+    _, _, want = check(textured, units, ints, 1234567, use_had, "sizes")
+    assert any(w[2][0] != (0, 0) for w in want) and any(w[2][1] != (0, 0) for w in want)  # a half and a quarter vector off the centre
+
+
+# ---- 2. the stage costs against hmx_batch_subpel_cost, which is pinned on the compiled reference ----
+@pytest.mark.parametrize("use_had", [1, 0])
+def test_stage_costs_vs_pinned_entry(ctx, textured, use_had):
+    units, ints = size_units(np.random.default_rng(900 + ctx.bit_depth))
+    lam = 1234567
+    res, costs = ctx.batch_subpel_search(units, ints, textured.refs, textured.org, W, H, M, M, lam, use_had, want_stage_costs=True)
+    pus = np.zeros(len(units), capi.PU_DTYPE)
+    for i, (u, v) in enumerate(zip(units, ints)):
+        pus[i] = (u["x"], u["y"], u["w"], u["h"], u["ref"], 255, 4 * int(v["mvx"]), 4 * int(v["mvy"]), 0, 0)
+    offs = np.array(OFFS49, np.int8)
+    d_cost = ctx.alloc(4 * len(pus) * 49)
+    ref_arr = (capi.Pic * 2)(*[r.as_pic() for r in textured.refs])
+    ctx._chk(capi.lib().hmx_batch_subpel_cost(ctx.h, pus.ctypes.data, len(pus), ref_arr, 2, C.byref(textured.org.as_pic()), offs.ctypes.data, 49,
+                                             use_had, d_cost.ptr))
+    ctx.sync()
+    pinned = d_cost.download(np.uint32).reshape(len(pus), 49)
+    d_cost.free()
+    seen = set()
+    for i, (u, v) in enumerate(zip(units, ints)):
+        ix, iy, px, py = int(v["mvx"]), int(v["mvy"]), int(u["pred_x"]), int(u["pred_y"])
+        hx, hy = so.REFINE_H[int(np.argmin(costs[i][:9]))]
+        for k in range(9):
+            dx, dy = so.REFINE_H[k]
+            d = (int(costs[i][k]) - capi.mv_cost(lam, 2 * ix + dx, 2 * iy + dy, px, py, 1)) & ONES
+            assert d == int(pinned[i][OFFS49.index((2 * dx, 2 * dy))]), ("half", i, k)
+            qx, qy = so.REFINE_Q[k]
+            ox, oy = 2 * hx + qx, 2 * hy + qy
+            d = (int(costs[i][9 + k]) - capi.mv_cost(lam, 4 * ix + ox, 4 * iy + oy, px, py, 0)) & ONES
+            assert d == int(pinned[i][OFFS49.index((ox, oy))]), ("quarter", i, k)
+            seen.add(d)
+        assert (int(res[i]["mvx"]), int(res[i]["mvy"])) == (4 * ix + 2 * hx + so.REFINE_Q[int(np.argmin(costs[i][9:]))][0],
+                                                           4 * iy + 2 * hy + so.REFINE_Q[int(np.argmin(costs[i][9:]))][1])
+    assert len(seen) > 100  # not a comparison of constants
+
+
+# ---- 3. chained behind hmx_batch_fullpel_search, no download between the calls ----
+def test_chained_from_fullpel_search(ctx, textured):
+    from thevc_amd import workload
+    units = workload.make_me_units(910 + ctx.bit_depth, W, H, 2, 4)
+    assert len(units) >= 6
+    lam = 2222222
+    d_int = ctx.batch_fullpel_search_device(units, textured.refs, textured.org, W, H, M, M, lam)
+    try:
+        res, costs = ctx.batch_subpel_search(units, d_int, textured.refs, textured.org, W, H, M, M, lam, 1, want_stage_costs=True)
+        ints = d_int.download(capi.ME_RESULT_DTYPE, len(units))
+    finally:
+        d_int.free()
+    assert np.array_equal(ints, ctx.batch_fullpel_search(units, textured.refs, textured.org, W, H, M, M, lam))
+    for i, wnt in enumerate(expect(textured, units, ints, lam, 1)):
+        assert [int(c) for c in costs[i]] == wnt[1], (i, units[i])
+        assert (int(res[i]["mvx"]), int(res[i]["mvy"]), int(res[i]["dist"]), int(res[i]["cost"])) == wnt[0], (i, units[i])
+
+
+# ---- 4. ties: the table order decides ----
+def minima(c):
+    return [k for k in range(9) if c[k] == min(c)]
+
+
+@pytest.mark.parametrize("use_had", [1, 0])
+def test_ties(ctx, use_had):
+    B = ctx.bit_depth
+    p = tgm.Pictures(ctx, [np.full((H + 2 * M, W + 2 * M), (1 << B) - 3, np.int16)], np.full((H, W), 5, np.int16))
+    cases = [((-4, -7), [3, 5], [3, 5], (-3, -1)), ((-4, -8), [5], [3, 5, 7], (-3, -3)), ((-8, -6), [3, 5], list(range(9)), (-2, 0)),
+             ((0, 0), [0], [0], (0, 0))]
+    units, vecs = [], []
+    for k, (rel, _, _, _) in enumerate(cases):
+        ix, iy = (3, -2, 0, -5)[k], (-4, 1, 0, 6)[k]
+        units.append(tgm.unit(64, 32, (16, 8, 32, 4)[k], (16, 8, 8, 4)[k], 0, 0, rel[0] + 4 * ix, rel[1] + 4 * iy, -8, -8, 8, 8))
+        vecs.append((ix, iy))
+    units, ints = np.concatenate(units), ints_of(vecs)
+    res, _, want = check(p, units, ints, 65536, use_had, "ties")
+    for k, (rel, th, tq, off) in enumerate(cases):
+        assert minima(want[k][1][:9]) == th and minima(want[k][1][9:]) == tq, (k, want[k][1])  # the ties occurred
+        assert (int(res[k]["mvx"]) - 4 * vecs[k][0], int(res[k]["mvy"]) - 4 * vecs[k][1]) == off, k
+    assert want[0][2] == ((-1, 0), (-1, -1))  # where a raster-ordered minimum would take (-1, 0)
+    units = np.concatenate([tgm.unit(64, 32, 8, 8, 0, 0, 9, -13, -8, -8, 8, 8), tgm.unit(64, 32, 64, 64, 0, 0, -3, 7, -8, -8, 8, 8)])
+    ints = ints_of([(2, 3), (-7, 8)])
+    res, _, want = check(p, units, ints, 0, use_had, "lambda 0")
+    for k in range(2):
+        assert len(set(want[k][1])) == 1  # all eighteen costs equal
+        assert (int(res[k]["mvx"]), int(res[k]["mvy"])) == (4 * int(ints[k]["mvx"]), 4 * int(ints[k]["mvy"]))  # the centre wins twice
+    p.free()
+
+
+# ---- 5. originals outside the sample range ----
+@pytest.mark.parametrize("use_had", [1, 0])
+def test_signed_originals(ctx, use_had):
+    B = ctx.bit_depth
+    rng = np.random.default_rng(940 + B)
+    org = rng.integers(-(1 << B), 1 << (B + 1), (H, W)).astype(np.int16)
+    org[0:64, 0:64] = -(1 << B)               # the extremes, a whole 64 x 64 block of each
+    org[64:128, 0:64] = (1 << (B + 1)) - 1
+    refs = [rng.integers(0, 1 << B, (H + 2 * M, W + 2 * M)).astype(np.int16), np.full((H + 2 * M, W + 2 * M), (1 << B) - 1, np.int16)]
+    p = tgm.Pictures(ctx, refs, org)
+    units = np.concatenate([tgm.unit(0, 0, 64, 64, 1, 0, 3, -2, -4, -4, 4, 4), tgm.unit(0, 64, 64, 64, 0, 0, 0, 0, -4, -4, 4, 4),
+                            tgm.unit(64, 0, 64, 64, 0, 0, -9, 2, -4, -4, 4, 4), tgm.unit(128, 16, 16, 16, 0, 0, 5, 5, -4, -4, 4, 4),
+                            tgm.unit(132, 40, 4, 8, 1, 0, 1, 1, -4, -4, 4, 4), tgm.unit(160, 64, 16, 16, 1, 0, 0, -7, -4, -4, 4, 4)])
+    res, _, _ = check(p, units, ints_of([(0, 0), (1, -3), (-4, 4), (2, 2), (-1, 0), (4, -4)]), 500000, use_had, "signed originals")
+    if not use_had:  # |-2^B - (2^B - 1)| on every sample, whatever the fraction
+        assert int(res[0]["dist"]) == (64 * 64 * ((1 << B) + (1 << B) - 1)) >> (B - 8)
+    p.free()
+
+
+# ---- 6. 12 bit, original and reference at opposite ends of the range ----
+def test_twelve_bit_range_ends():
+    import extreme_inputs as ei
+    ctx12 = capi.Context(bit_depth=12)
+    hi, lo = ei.opposite_ends(W, H, 12)
+    units = np.concatenate([tgm.unit(64, 32, 64, 64, 0, 0, 7, -9, -3, -3, 3, 3), tgm.unit(8, 8, 4, 4, 0, 0, -2, 2, -3, -3, 3, 3)])
+    ints = ints_of([(1, -2), (-3, 3)])
+    try:
+        for ref_v, org_p in ((4095, lo[0]), (0, hi[0])):
+            p = tgm.Pictures(ctx12, [np.full((H + 2 * M, W + 2 * M), ref_v, np.int16)], org_p)
+            for use_had in (1, 0):
+                res, _, _ = check(p, units, ints, 700000, use_had, "12 bit")
+                if not use_had:
+                    assert int(res[0]["dist"]) == (64 * 64 * 4095) >> 4 and int(res[1]["dist"]) == (16 * 4095) >> 4
+            p.free()
+    finally:
+        ctx12.close()
+
+
+# ---- 7. d_stage_cost = NULL; calling twice ----
+def test_null_stage_costs_and_determinism(ctx, textured):
+    units, ints = size_units(np.random.default_rng(900 + ctx.bit_depth))
+    args = (units, ints, textured.refs, textured.org, W, H, M, M, 1234567, 1)
+    a, ca = ctx.batch_subpel_search(*args, want_stage_costs=True)
+    b, cb = ctx.batch_subpel_search(*args, want_stage_costs=True)
+    plain = ctx.batch_subpel_search(*args)
+    assert a.tobytes() == b.tobytes() == plain.tobytes() and ca.tobytes() == cb.tobytes()
+
+
+# ---- 8. refusals, and the vector outside its box ----
+def test_refusals_and_sentinel(ctx, textured):
+    L = capi.lib()
+    good = tgm.unit(64, 32, 16, 16, 0, 0, 0, 0, -4, -4, 4, 4)
+    ref_arr = (capi.Pic * 2)(*[r.as_pic() for r in textured.refs])
+    org_pic = textured.org.as_pic()
+    d_int = ctx.to_device(ints_of([(0, 0)]))
+    sentinel = np.full(3, 0x5A5A5A5A, np.uint32)
+    d_res = ctx.to_device(sentinel)
+
+    def refused(msg, u=good, n=1, n_refs=2, use_had=1, units_p=True, int_p=True, refs_p=True, org_p=True, res_p=True):
+        rc = L.hmx_batch_subpel_search(ctx.h, u.ctypes.data if units_p else None, n, d_int.ptr if int_p else None, ref_arr if refs_p else None,
+                                       n_refs, C.byref(org_pic) if org_p else None, W, H, M, M, 0, use_had, d_res.ptr if res_p else None, None)
+        assert rc == -1, (msg, rc)  # HMX_ERR_ARG
+        assert msg in L.hmx_last_error(ctx.h).decode(), (msg, L.hmx_last_error(ctx.h).decode())
+        ctx.sync()
+        assert np.array_equal(d_res.download(np.uint32), sentinel), msg  # nothing was launched
+
+    def bad(msg, **kw):
+        u = good.copy()
+        for k, v in kw.items():
+            u[0][k] = v
+        refused(msg, u)
+        assert "unit 0: " in L.hmx_last_error(ctx.h).decode()  # the unit is named
+
+    for k in ("units_p", "int_p", "refs_p", "org_p", "res_p"):
+        refused("null argument", **{k: False})
+    refused("n must be at least 1", n=0)
+    refused("n_refs must be 1 .. 4", n_refs=0)
+    refused("n_refs must be 1 .. 4", n_refs=5)
+    refused("use_had is 0 or 1", use_had=2)
+    refused("use_had is 0 or 1", use_had=-1)
+    bad("width and height", w=20)
+    bad("width and height", h=6)
+    bad("reference index", ref=2)
+    bad("empty search box", left=5)
+    bad("empty search box", bottom=-5)
+    bad("outside the picture", x=W - 8)
+    bad("outside the picture", y=H - 12)
+    bad("outside the reference's margins", x=0, left=-M + 3)
+    bad("outside the reference's margins", x=W - 16, right=M - 3)
+    bad("outside the reference's margins", y=0, top=-M + 3)
+    bad("outside the reference's margins", y=H - 16, bottom=M - 3)
+    d_int.free()
+    d_res.free()
+    # sub_shift is ignored, the margin's last sample is legal, and the context still works; then the same call with the vector of
+    # unit 1 one sample outside its box: that unit comes back as the sentinel, the others as before
+    units = np.concatenate([tgm.unit(0, 0, 16, 16, 0, 1, 0, 0, -M + 4, -M + 4, -M + 6, -M + 6), tgm.unit(96, 64, 32, 32, 1, 0, 10, -10, -2, -3, 5, 4),
+                            tgm.unit(W - 16, H - 16, 16, 16, 1, 1, 0, 0, M - 6, M - 6, M - 4, M - 4), good])
+    inside = ints_of([(-M + 4, -M + 4), (5, 4), (M - 4, M - 4), (-4, 4)])
+    res, costs, _ = check(textured, units, inside, 99999, 1, "after refused calls")
+    for vec in ((6, 4), (5, 5), (-3, 0), (0, -4), (300, -300), (-32768 // 4 - 1, 9000)):
+        ints = inside.copy()
+        ints[1]["mvx"], ints[1]["mvy"] = vec
+        got, gc = ctx.batch_subpel_search(units, ints, textured.refs, textured.org, W, H, M, M, 99999, 1, want_stage_costs=True)
+        keep = [0, 2, 3]
+        assert np.array_equal(got[keep], res[keep]) and np.array_equal(gc[keep], costs[keep]), vec
+        want_mv = tuple((4 * v + 32768) % 65536 - 32768 for v in vec)  # 4 * ix, 4 * iy truncated to int16
+        assert (int(got[1]["mvx"]), int(got[1]["mvy"]), int(got[1]["dist"]), int(got[1]["cost"])) == (want_mv[0], want_mv[1], ONES, ONES), vec
+        assert [int(c) for c in gc[1]] == [ONES] * 18, vec
+        plain = ctx.batch_subpel_search(units, ints, textured.refs, textured.org, W, H, M, M, 99999, 1)
+        assert plain.tobytes() == got.tobytes(), vec
+
+
+# ---- 9. xMotionEstimation through the C++ host mirror ----
+def check_mirror_output(out, B):
+    lines = out.strip().split("\n")
+    assert len(lines) == 5
+    p = [int(v) for v in lines[0].split()]
+    u = dict(zip(("x", "y", "w", "h", "sub_shift", "pred_x", "pred_y"), p[:7]))
+    lam, w, h, m, use_had, rng_, bits_in, start_x, start_y = p[7:]
+    u["ref"] = 0
+    org = np.array(lines[1].split(), np.int64).reshape(h, w).astype(np.int16)
+    ref = np.array(lines[2].split(), np.int64).reshape(h + 2 * m, w + 2 * m).astype(np.int16)
+    assert lam > 65536
+    for line, (bi, weight) in zip(lines[3:], ((0, 1.0), (1, 0.5))):
+        got = [int(v) for v in line.split()]
+        centre = (start_x, start_y) if bi else (u["pred_x"], u["pred_y"])  # xSetSearchRange around rcMv when bBi (:4166)
+        u["left"], u["top"], u["right"], u["bottom"] = mo.set_search_range(centre[0], centre[1], rng_, u["x"], u["y"], w, h)
+        (ix, iy, _, _), _ = mo.search(org, ref, (m, m), u, lam, B)
+        (mvx, mvy, _, cost), _, _ = so.refine_unit(org, ref, (m, m), u, ix, iy, lam, B, use_had)
+        bits, total = so.me_tail(lam, (u["pred_x"], u["pred_y"]), mvx, mvy, cost, bits_in, weight)
+        assert got == [mvx, mvy, bits, total], (bi, got, [mvx, mvy, bits, total])
+
+
+@pytest.mark.parametrize("B,seed", [(8, 4), (10, 7), (8, 9)])
+def test_mirror_motion_estimation(B, seed):
+    import __graft_entry__ as g
+    g.build()
+    out = subprocess.run([EXE, "frac", str(B), str(seed)], capture_output=True, text=True, check=True).stdout
+    check_mirror_output(out, B)

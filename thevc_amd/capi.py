@@ -98,9 +98,14 @@ class MeResult(C.Structure):  # hmx_me_result
     _fields_ = [("mvx", C.c_int16), ("mvy", C.c_int16), ("sad", C.c_uint32), ("cost", C.c_uint32)]
 
 
+class SubpelResult(C.Structure):  # hmx_subpel_result
+    _fields_ = [("mvx", C.c_int16), ("mvy", C.c_int16), ("dist", C.c_uint32), ("cost", C.c_uint32)]
+
+
 ME_UNIT_DTYPE = np.dtype([("x", "<u2"), ("y", "<u2"), ("w", "u1"), ("h", "u1"), ("ref", "u1"), ("sub_shift", "u1"), ("pred_x", "<i2"),
                           ("pred_y", "<i2"), ("left", "<i2"), ("top", "<i2"), ("right", "<i2"), ("bottom", "<i2")])  # hmx_me_unit
 ME_RESULT_DTYPE = np.dtype([("mvx", "<i2"), ("mvy", "<i2"), ("sad", "<u4"), ("cost", "<u4")])  # hmx_me_result
+SUBPEL_RESULT_DTYPE = np.dtype([("mvx", "<i2"), ("mvy", "<i2"), ("dist", "<u4"), ("cost", "<u4")])  # hmx_subpel_result, quarter samples
 
 WP_DTYPE = np.dtype([("weight", "<i2", 3), ("offset", "<i2", 3), ("log2_denom", "u1", 3), ("reserved", "u1")])  # hmx_wp
 
@@ -323,7 +328,8 @@ def lib():
         for name, at, rt in (("hmx_mvBits", [ci, ci, ci, ci, ci], u32), ("hmx_mvCost", [u32, ci, ci, ci, ci, ci], u32),
                              ("hmx_setSearchRange", [ci] * 8 + [C.POINTER(ci)] * 4, None),
                              ("hmx_getSAD", [vp, vp, ci, vp, ci, ci, ci, ci, C.POINTER(u32)], ci),
-                             ("hmx_batch_fullpel_search", [vp, vp, ci, C.POINTER(Pic), ci, C.POINTER(Pic), ci, ci, ci, ci, u32, vp, vp], ci)):
+                             ("hmx_batch_fullpel_search", [vp, vp, ci, C.POINTER(Pic), ci, C.POINTER(Pic), ci, ci, ci, ci, u32, vp, vp], ci),
+                             ("hmx_batch_subpel_search", [vp, vp, ci, vp, C.POINTER(Pic), ci, C.POINTER(Pic), ci, ci, ci, ci, u32, ci, vp, vp], ci)):
             if "HMX_LIB_PATH" in os.environ and not hasattr(L, name):
                 continue  # an older build loaded for an A/B run: calling the entry still raises
             getattr(L, name).argtypes = at
@@ -765,6 +771,54 @@ class Context:
             d_res.free()
             if d_map:
                 d_map.free()
+
+    def batch_fullpel_search_device(self, units, refs, org, pic_w, pic_h, margin_x, margin_y, lambda_):
+        """hmx_batch_fullpel_search with the results left on the device: returns the DevBuf of len(units) hmx_me_result (the
+        caller frees it), issued on the context's stream and not waited for -- what batch_subpel_search takes as d_int."""
+        units = np.ascontiguousarray(units, ME_UNIT_DTYPE)
+        n = len(units)
+        if n == 0:
+            raise ValueError("batch_fullpel_search_device: at least one unit")
+        ref_arr = (Pic * len(refs))(*[r.as_pic() for r in refs])
+        d_res = self.alloc(n * ME_RESULT_DTYPE.itemsize)
+        try:
+            self._chk(lib().hmx_batch_fullpel_search(self.h, units.ctypes.data, n, ref_arr, len(refs), C.byref(org.as_pic()), pic_w, pic_h,
+                                                     margin_x, margin_y, int(lambda_) & 0xFFFFFFFF, d_res.ptr, None))
+        except Exception:
+            d_res.free()
+            raise
+        return d_res
+
+    def batch_subpel_search(self, units, d_int, refs, org, pic_w, pic_h, margin_x, margin_y, lambda_, use_had, want_stage_costs=False):
+        """hmx_batch_subpel_search: units = array of ME_UNIT_DTYPE (host); d_int = the integer vectors, either a device buffer
+        of hmx_me_result (a DevBuf or a device address, used as it is: batch_fullpel_search_device's return) or an
+        ME_RESULT_DTYPE array, which is uploaded.  Returns the results (SUBPEL_RESULT_DTYPE) and, with want_stage_costs,
+        (results, costs): uint32 (n, 18), the nine half-stage then the nine quarter-stage costs in table order."""
+        units = np.ascontiguousarray(units, ME_UNIT_DTYPE)
+        n = len(units)
+        if n == 0:
+            raise ValueError("batch_subpel_search: at least one unit")
+        own_int = isinstance(d_int, np.ndarray)
+        if own_int:
+            if len(d_int) != n:
+                raise ValueError("batch_subpel_search: one integer vector per unit")
+            d_int = self.to_device(np.ascontiguousarray(d_int, ME_RESULT_DTYPE))
+        ref_arr = (Pic * len(refs))(*[r.as_pic() for r in refs])
+        d_res = self.alloc(n * SUBPEL_RESULT_DTYPE.itemsize)
+        d_costs = self.alloc(n * 18 * 4) if want_stage_costs else None
+        try:
+            self._chk(lib().hmx_batch_subpel_search(self.h, units.ctypes.data, n, getattr(d_int, "ptr", d_int), ref_arr, len(refs),
+                                                    C.byref(org.as_pic()), pic_w, pic_h, margin_x, margin_y, int(lambda_) & 0xFFFFFFFF,
+                                                    int(use_had), d_res.ptr, d_costs.ptr if d_costs else None))
+            self.sync()
+            res = d_res.download(SUBPEL_RESULT_DTYPE, n)
+            return (res, d_costs.download(np.uint32, n * 18).reshape(n, 18)) if want_stage_costs else res
+        finally:
+            d_res.free()
+            if d_costs:
+                d_costs.free()
+            if own_int:
+                d_int.free()
 
     def sao_stats(self, orgs, recs, w, h, lcu_based=True):
         """hmx_sao_stats_multi: the encoder's SAO statistics of n pictures (DevPictures, org and deblocked rec) as an int32

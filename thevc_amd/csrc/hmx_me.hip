@@ -1,4 +1,5 @@
-// hmx_me.hip: full-search integer motion estimation (TEncSearch::xPatternSearch), SAD, vector-bits cost, search box -- part of libhmx
+// hmx_me.hip: full-search integer motion estimation (TEncSearch::xPatternSearch), SAD, vector-bits cost, search box, and the fused
+// half- and quarter-sample refinement behind it (TEncSearch::xPatternSearchFracDIF) -- part of libhmx
 // (include/hmx.h), gfx950.  See hmx_host.h for how the library is cut into translation units.
 #include "hmx_host.h"
 
@@ -261,6 +262,283 @@ extern "C" int hmx_batch_fullpel_search(hmx_ctx *c, const hmx_me_unit *units, in
   HIPCHK(c, hipMemsetAsync(c->d_me_keys, 0xff, sizeof(unsigned long long) * (size_t)n, c->stream));
   hipLaunchKernelGGL(k_me_search, dim3(tile_first[n]), dim3(kMeThreads), 0, c->stream, A);
   hipLaunchKernelGGL(k_me_unpack, dim3((n + 255) / 256), dim3(256), 0, c->stream, A.units, (const unsigned long long *)c->d_me_keys, n, lambda, d_result);
+  HIPCHK(c, hipGetLastError());
+  return HMX_OK;
+}
+
+// =============================================================================================
+// xPatternSearchFracDIF (TEncSearch.cpp:4476-4514) over unit lists: both stages and both decisions in one launch
+// =============================================================================================
+// One workgroup (four waves) = one unit.  The (w + 8) x (h + 8) reference window around the integer-displaced block and the
+// original block are staged in LDS once; the integer vector is device data, so a unit whose vector lies outside the box the
+// host checked is answered with the all-ones sentinel before any reference sample is read.  The horizontal 8-tap stage
+// (filterHorLuma, isLast = false) is run once per phase into a 14-bit plane in LDS and shared by every candidate that uses it:
+// phase 2 for the half stage (columns -1 .. w - 1, all h + 8 rows), phases 1 and 3 once the half-sample winner (hx, hy) is
+// known (w columns from the one column offset and only the rows the nine quarter candidates reach); phase 0 is a shift of the
+// window and has no plane.  A candidate's distortion is then vertical taps over a plane: S lanes (S = 8, or 4 when a side is
+// not a multiple of 8) share one S x S sub-block of one candidate, a lane owning a column -- S + 7 intermediates, S
+// differences; the Hadamard sum runs down the column in registers and across the S lanes by lane exchange -- and the
+// sub-block sums meet in LDS counters (integer adds: the order does not matter).  Wave 0 adds the vector cost and takes the
+// minimum of (cost, table index) -- the tables of the two stages differ, so the index is the table's, never a raster
+// position -- and writes costs and result with plain stores.  The zero-fraction vertical step (filterCopy, isLast) equals the
+// general step with the taps {0, 0, 0, 64, 0, 0, 0, 0} for bit depths below 14: 64 * (t + 8192 + 2^(head-1)) >> (6 + head).
+// LDS (dynamic, sized for the largest unit of the call): window, original, planes 2, 1, 3 = 46352 bytes at 64 x 64: three
+// workgroups = twelve waves per CU (160 KB); 1440 bytes at 8 x 8, where the registers (eight workgroups per CU) bind first.
+constexpr int kSpThreads = 256;
+struct SpArgs {
+  const hmx_me_unit *units;
+  const hmx_me_result *ints; // device: the integer vectors
+  PlanesDev refs[4];
+  PlanesDev org;
+  int B, use_had;
+  uint32_t lambda;
+  hmx_subpel_result *result;
+  uint32_t *stage_cost; // [n][18], NULL = none
+};
+static size_t sp_lds_bytes(int w, int h) { return sizeof(short) * (size_t)((w + 8) * (h + 8) + w * h + (w + 1) * (h + 8) + 2 * w * (h + 8)); }
+struct SpDiv { // n / d for n < 4096 * d and n * d < 2^20, by one multiplication
+  unsigned d, m;
+  __device__ __forceinline__ explicit SpDiv(int dd) : d((unsigned)dd), m(((1u << 20) + (unsigned)dd - 1) / (unsigned)dd) {}
+  __device__ __forceinline__ int div(int n) const { return (int)(((unsigned)n * m) >> 20); }
+};
+__host__ __device__ constexpr int sp_luma_tap(int frac, int q) {
+  constexpr signed char k[4][8] = {{0, 0, 0, 64, 0, 0, 0, 0}, {-1, 4, -10, 58, 17, -5, 1, 0}, {-1, 4, -11, 40, 40, -11, 4, -1},
+                                   {0, 1, -5, 17, 58, -10, 4, -1}};
+  return k[frac][q];
+}
+__host__ __device__ constexpr unsigned sp_tap_word(int frac, int half) { // four taps as signed bytes
+  return ((unsigned)sp_luma_tap(frac, 4 * half) & 255u) | (((unsigned)sp_luma_tap(frac, 4 * half + 1) & 255u) << 8) |
+         (((unsigned)sp_luma_tap(frac, 4 * half + 2) & 255u) << 16) | (((unsigned)sp_luma_tap(frac, 4 * half + 3) & 255u) << 24);
+}
+// s_acMvRefineH / s_acMvRefineQ (TEncSearch.cpp:47-71), component + 1 in two bits per entry; the x components agree
+__host__ __device__ constexpr unsigned sp_pack9(int a0, int a1, int a2, int a3, int a4, int a5, int a6, int a7, int a8) {
+  return (unsigned)(a0 + 1) | (unsigned)(a1 + 1) << 2 | (unsigned)(a2 + 1) << 4 | (unsigned)(a3 + 1) << 6 | (unsigned)(a4 + 1) << 8 |
+         (unsigned)(a5 + 1) << 10 | (unsigned)(a6 + 1) << 12 | (unsigned)(a7 + 1) << 14 | (unsigned)(a8 + 1) << 16;
+}
+constexpr unsigned kSpCandX = sp_pack9(0, 0, 0, -1, 1, -1, 1, -1, 1);
+constexpr unsigned kSpCandYH = sp_pack9(0, -1, 1, 0, 0, -1, -1, 1, 1), kSpCandYQ = sp_pack9(0, -1, 1, -1, -1, 0, 0, 1, 1);
+__device__ __forceinline__ void sp_cand(int stage, int k, int &dx, int &dy) {
+  dx = (int)((kSpCandX >> (2 * k)) & 3u) - 1;
+  dy = (int)(((stage ? kSpCandYQ : kSpCandYH) >> (2 * k)) & 3u) - 1;
+}
+
+// filterHorLuma(frac, isLast = false) of plane rows r0 .. r1 - 1 (row r = window row r) and `cols` columns, column c at window
+// column wc0 + c, into dst (pitch dp)
+template <int FRAC>
+__device__ __forceinline__ void sp_hor_plane(const short *win, int wp, short *dst, int dp, int cols, int wc0, int r0, int r1, int B, int tid) {
+  const int shift = B - 8, offset = -(8192 << shift), n = (r1 - r0) * cols;
+  const SpDiv dc(cols);
+  for (int i = tid; i < n; i += kSpThreads) {
+    const int r = dc.div(i), c = i - r * cols;
+    const short *s = win + (r0 + r) * wp + wc0 + c - 3;
+    int sum = 0;
+#pragma unroll
+    for (int q = 0; q < 8; q++) sum += s[q] * sp_luma_tap(FRAC, q);
+    dst[(r0 + r) * dp + c] = (short)((sum + offset) >> shift);
+  }
+}
+
+struct SpLds {
+  const short *win, *org, *p1, *p2, *p3;
+  int w, h;
+};
+// the nine candidates of one stage: s_cost[k] += the sub-block sums of candidate k
+template <int S>
+__device__ __forceinline__ void sp_stage(const SpLds &L, int stage, int hx, int hy, int c1, int c3, int B, int use_had, unsigned *s_cost, int tid) {
+  const int w = L.w, bw = w / S, nsb = bw * (L.h / S), total = 9 * nsb, lane = tid & (S - 1);
+  const SpDiv dn(nsb), db(bw);
+  const int head = 14 - B, shift = 6 + head, offset = (1 << (shift - 1)) + (8192 << 6), maxv = (1 << B) - 1;
+  for (int base = 0; base < total; base += kSpThreads / S) {
+    if (base + (tid & ~63) / S >= total) break; // no sub-block left for this wave (uniform over the wave)
+    int g = base + tid / S;
+    const bool act = g < total; // idle lanes of a busy wave redo the last item and add nothing
+    g = act ? g : total - 1;
+    const int k = dn.div(g), sb = g - k * nsb, sby = db.div(sb), sx = (sb - sby * bw) * S, sy = sby * S;
+    int dx, dy;
+    sp_cand(stage, k, dx, dy);
+    const int ox = stage ? 2 * hx + dx : 2 * dx, oy = stage ? 2 * hy + dy : 2 * dy; // quarter samples from the integer vector
+    const int xf = ox & 3, cx = ox >> 2, yf = oy & 3, iy = oy >> 2;
+    const int rb = sy + iy + 1, col = sx + lane + cx; // plane row of the first intermediate: sample row sy + iy - 3
+    const short *src;
+    int pitch;
+    if (xf == 0) src = L.win + rb * (w + 8) + col + 4, pitch = w + 8;
+    else if (xf == 2) src = L.p2 + rb * (w + 1) + col + 1, pitch = w + 1;
+    else if (xf == 1) src = L.p1 + rb * w + col - c1, pitch = w;
+    else src = L.p3 + rb * w + col - c3, pitch = w;
+    int t[S + 7];
+#pragma unroll
+    for (int q = 0; q < S + 7; q++) {
+      const int v = src[q * pitch];
+      t[q] = xf == 0 ? (v << head) - 8192 : v; // filterCopy, isFirst (:112-122)
+    }
+    unsigned tw[2];
+    tw[0] = yf == 0 ? sp_tap_word(0, 0) : yf == 1 ? sp_tap_word(1, 0) : yf == 2 ? sp_tap_word(2, 0) : sp_tap_word(3, 0);
+    tw[1] = yf == 0 ? sp_tap_word(0, 1) : yf == 1 ? sp_tap_word(1, 1) : yf == 2 ? sp_tap_word(2, 1) : sp_tap_word(3, 1);
+    int tap[8];
+#pragma unroll
+    for (int q = 0; q < 8; q++) tap[q] = (int)(signed char)(tw[q >> 2] >> (8 * (q & 3)));
+    const short *o = L.org + sy * w + sx + lane;
+    int d[S];
+#pragma unroll
+    for (int r = 0; r < S; r++) {
+      int sum = 0;
+#pragma unroll
+      for (int q = 0; q < 8; q++) sum += t[r + q] * tap[q];
+      d[r] = o[r * w] - clip3(0, maxv, wrap16((sum + offset) >> shift));
+    }
+    int s = 0;
+    if (use_had) { // the sum of magnitudes of the 2-D transform: down the column here, then across the S lanes
+      wht_regs<S>(d);
+#pragma unroll
+      for (int m = 1; m < S; m <<= 1)
+#pragma unroll
+        for (int r = 0; r < S; r++) {
+          const int other = __shfl_xor(d[r], m, 64);
+          d[r] = (lane & m) ? other - d[r] : d[r] + other;
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < S; r++) s += abs(d[r]);
+    s = group_sum(s, S);
+    if (use_had) s = S == 8 ? (s + 2) >> 2 : (s + 1) >> 1; // rounded per sub-block (TComRdCost.cpp:2083, :1991)
+    if (act && lane == 0) atomicAdd(&s_cost[k], (unsigned)s);
+  }
+}
+
+// xPatternRefinement's loop (:725-757) over the nine costs of a stage, by the first 16 lanes of wave 0: the costs to the
+// caller's array, and the winner's table index with its cost (every lane of the 16 returns them)
+__device__ __forceinline__ unsigned long long sp_decide(const unsigned *s_cost, int stage, int bx, int by, const hmx_me_unit &u, const SpArgs &A,
+                                                        uint32_t *costs, int tid) {
+  unsigned long long key = ~0ull;
+  if (tid < 9) {
+    int dx, dy;
+    sp_cand(stage, tid, dx, dy);
+    const uint32_t cost = (s_cost[tid] >> (A.B - 8)) + me_mv_cost(A.lambda, bx + dx, by + dy, u.pred_x, u.pred_y, stage ? 0 : 1);
+    if (costs) costs[tid] = cost;
+    key = ((unsigned long long)cost << 32) | (unsigned)tid;
+  }
+#pragma unroll
+  for (int m = 1; m < 16; m <<= 1) {
+    const unsigned long long other = __shfl_xor(key, m, 64);
+    key = other < key ? other : key;
+  }
+  return key;
+}
+
+__global__ __launch_bounds__(kSpThreads) void k_subpel_search(SpArgs A) {
+  extern __shared__ __attribute__((aligned(16))) short s_sp[];
+  __shared__ unsigned s_cost[18];
+  __shared__ int s_half;
+  const int i = blockIdx.x, tid = threadIdx.x;
+  const hmx_me_unit u = A.units[i];
+  const int ix = A.ints[i].mvx, iy = A.ints[i].mvy, w = u.w, h = u.h, B = A.B;
+  typedef __attribute__((address_space(1))) uint32_t gu32;
+  gu32 *costs = A.stage_cost ? (gu32 *)A.stage_cost + (size_t)i * 18 : nullptr;
+  if (ix < u.left || ix > u.right || iy < u.top || iy > u.bottom) { // uniform over the workgroup: nothing was checked for this vector
+    if (tid < 18 && costs) costs[tid] = 0xffffffffu;
+    if (tid == 0) {
+      hmx_subpel_result r;
+      r.mvx = (int16_t)(4 * ix), r.mvy = (int16_t)(4 * iy), r.dist = r.cost = 0xffffffffu;
+      A.result[i] = r;
+    }
+    return;
+  }
+  const int wp = w + 8, rows = h + 8;
+  short *win = s_sp, *org = win + wp * rows, *p2 = org + w * h, *p1 = p2 + (w + 1) * rows, *p3 = p1 + w * rows;
+  typedef __attribute__((address_space(1))) const short gpel;
+  {
+    const PlanesDev &R = A.refs[u.ref < 4 ? u.ref : 0];
+    const gpel *src = (const gpel *)R.p[0] + (ptrdiff_t)(u.y + iy - 4) * R.s[0] + (u.x + ix - 4);
+    const SpDiv dc(wp);
+    for (int k = tid; k < wp * rows; k += kSpThreads) {
+      const int r = dc.div(k), c = k - r * wp;
+      win[k] = src[(ptrdiff_t)r * R.s[0] + c];
+    }
+    const gpel *so = (const gpel *)A.org.p[0] + (size_t)u.y * A.org.s[0] + u.x;
+    const SpDiv dw(w);
+    for (int k = tid; k < w * h; k += kSpThreads) {
+      const int r = dw.div(k), c = k - r * w;
+      org[k] = so[(size_t)r * A.org.s[0] + c];
+    }
+  }
+  if (tid < 18) s_cost[tid] = 0;
+  __syncthreads();
+  sp_hor_plane<2>(win, wp, p2, w + 1, w + 1, 3, 0, rows, B, tid); // column c = sample column c - 1
+  __syncthreads();
+  const bool s8 = (w % 8 == 0) && (h % 8 == 0);
+  SpLds L{win, org, p1, p2, p3, w, h};
+  if (s8) sp_stage<8>(L, 0, 0, 0, 0, 0, B, A.use_had, s_cost, tid);
+  else sp_stage<4>(L, 0, 0, 0, 0, 0, B, A.use_had, s_cost, tid);
+  __syncthreads();
+  if (tid < 16) {
+    const int kb = (int)(uint32_t)sp_decide(s_cost, 0, 2 * ix, 2 * iy, u, A, (uint32_t *)costs, tid);
+    if (tid == 0) s_half = kb;
+  }
+  __syncthreads();
+  int hx, hy;
+  sp_cand(0, s_half, hx, hy);
+  // the quarter stage's columns: phase 1 is reached at +1 (hx = 0, 1: sample column 0) or -3 (hx = -1: column -1), phase 3 at
+  // -1 (hx = 0, -1: column -1) or +3 (hx = 1: column 0); its rows: all but the last below hy = -1, all but the first above hy = 1
+  const int c1 = hx < 0 ? -1 : 0, c3 = hx > 0 ? 0 : -1, r0 = hy > 0 ? 1 : 0, r1 = hy < 0 ? rows - 1 : rows;
+  sp_hor_plane<1>(win, wp, p1, w, w, 4 + c1, r0, r1, B, tid);
+  sp_hor_plane<3>(win, wp, p3, w, w, 4 + c3, r0, r1, B, tid);
+  __syncthreads();
+  if (s8) sp_stage<8>(L, 1, hx, hy, c1, c3, B, A.use_had, s_cost + 9, tid);
+  else sp_stage<4>(L, 1, hx, hy, c1, c3, B, A.use_had, s_cost + 9, tid);
+  __syncthreads();
+  if (tid < 16) {
+    const int bx = 4 * ix + 2 * hx, by = 4 * iy + 2 * hy;
+    const unsigned long long key = sp_decide(s_cost + 9, 1, bx, by, u, A, costs ? (uint32_t *)(costs + 9) : nullptr, tid);
+    if (tid == 0) {
+      int qx, qy;
+      sp_cand(1, (int)(uint32_t)key, qx, qy);
+      hmx_subpel_result r;
+      r.mvx = (int16_t)(bx + qx), r.mvy = (int16_t)(by + qy);
+      r.cost = (uint32_t)(key >> 32);
+      r.dist = r.cost - me_mv_cost(A.lambda, bx + qx, by + qy, u.pred_x, u.pred_y, 0);
+      A.result[i] = r;
+    }
+  }
+}
+
+extern "C" int hmx_batch_subpel_search(hmx_ctx *c, const hmx_me_unit *units, int n, const hmx_me_result *d_int, const hmx_pic *refs, int n_refs,
+                                       const hmx_pic *org, int pic_w, int pic_h, int margin_x, int margin_y, uint32_t lambda, int use_had,
+                                       hmx_subpel_result *d_result, uint32_t *d_stage_cost) {
+  if (!c || !units || !d_int || !refs || !org || !d_result) return fail(c, HMX_ERR_ARG, "hmx_batch_subpel_search: null argument");
+  if (n <= 0) return fail(c, HMX_ERR_ARG, "hmx_batch_subpel_search: n must be at least 1");
+  if (n_refs <= 0 || n_refs > 4) return fail(c, HMX_ERR_ARG, "hmx_batch_subpel_search: n_refs must be 1 .. 4");
+  if (use_had != 0 && use_had != 1) return fail(c, HMX_ERR_ARG, "hmx_batch_subpel_search: use_had is 0 or 1");
+  if (pic_w <= 0 || pic_h <= 0 || margin_x < 0 || margin_y < 0)
+    return fail(c, HMX_ERR_ARG, "hmx_batch_subpel_search: picture size must be positive and margins not negative");
+  if (!org->plane[0]) return fail(c, HMX_ERR_ARG, "hmx_batch_subpel_search: the original has no luma plane");
+  for (int r = 0; r < n_refs; r++)
+    if (!refs[r].plane[0]) return fail(c, HMX_ERR_ARG, "hmx_batch_subpel_search: a reference has no luma plane");
+  size_t lds = 0;
+  for (int i = 0; i < n; i++) {
+    const hmx_me_unit &u = units[i];
+    const std::string at = "hmx_batch_subpel_search: unit " + std::to_string(i) + ": ";
+    if (!me_size_ok(u.w) || !me_size_ok(u.h)) return fail(c, HMX_ERR_ARG, at + "width and height come from {4, 8, 12, 16, 24, 32, 48, 64}");
+    if (u.ref >= n_refs) return fail(c, HMX_ERR_ARG, at + "reference index outside refs[]");
+    if (u.right < u.left || u.bottom < u.top) return fail(c, HMX_ERR_ARG, at + "empty search box");
+    if (u.x + u.w > pic_w || u.y + u.h > pic_h) return fail(c, HMX_ERR_ARG, at + "the unit lies outside the picture");
+    // the window of every integer vector of the box: columns x + left - 4 .. x + right + w + 3, rows likewise
+    if (u.x + u.left - 4 < -margin_x || u.x + u.right + u.w + 4 > pic_w + margin_x || u.y + u.top - 4 < -margin_y ||
+        u.y + u.bottom + u.h + 4 > pic_h + margin_y)
+      return fail(c, HMX_ERR_ARG, at + "the interpolation window of a vector of the box reaches outside the reference's margins");
+    lds = std::max(lds, sp_lds_bytes(u.w, u.h));
+  }
+  SpArgs A{};
+  A.units = static_cast<const hmx_me_unit *>(arena_push(c, units, sizeof(hmx_me_unit) * (size_t)n)); // the caller's host array
+  if (!A.units) return fail(c, HMX_ERR_NOMEM, "argument arena (unit list too long: split the call)");
+  A.ints = d_int;
+  for (int r = 0; r < n_refs; r++) A.refs[r] = to_dev(&refs[r]);
+  A.org = to_dev(org);
+  A.B = c->cfg.bit_depth;
+  A.use_had = use_had;
+  A.lambda = lambda;
+  A.result = d_result;
+  A.stage_cost = d_stage_cost;
+  hipLaunchKernelGGL(k_subpel_search, dim3((unsigned)n), dim3(kSpThreads), lds, c->stream, A);
   HIPCHK(c, hipGetLastError());
   return HMX_OK;
 }

@@ -2,6 +2,7 @@
 // does (ENC/TEncSearch.cpp:1006-1165): setQPforQuant, transformNxN, invtransformNxN on one block, and
 // prints the results as text so that tests/test_host_mirror.py can compare them with the oracle.
 // Usage: hm_mirror_test <bitDepth> <N> <qp> <mode> <seed>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <string>
@@ -137,7 +138,72 @@ static int me_main(int argc, char **argv) {
   return 0;
 }
 
+// Usage: hm_mirror_test frac <bitDepth> <seed>: xMotionEstimation for one 16x8 (odd seed: 8x16) unit of a 64x64 picture
+// (margin 24), search range 5, once uni-predicted (fWeight 1.0) and once as the bi-prediction refinement (fWeight 0.5, the
+// range centred on a start vector), on a reference that is the original displaced by a fractional vector plus noise.
+// Prints "x y w h sub_shift predHor predVer multiplier W H M useHADME range bitsIn startHor startVer", the original plane, the
+// reference plane with its margins, and per run "mvHor mvVer bits cost", one line each.
+static int frac_main(int argc, char **argv) {
+  if (argc < 4) return 2;
+  const int B = atoi(argv[2]), W = 64, H = 64, M = 24, S = W + 2 * M, RANGE = 5;
+  unsigned seed = (unsigned)atoi(argv[3]);
+  const bool fastEnc = (seed & 1) != 0, hadME = (seed & 2) == 0;
+  auto next = [&]() { return (seed = seed * 1664525u + 1013904223u) >> 8; };
+  hmx_hm::Context ctx(B);
+  hmx_hm::TComRdCost rd(ctx);
+  hmx_hm::TEncSearch search(ctx, rd, {W, H, M, M, 64}, fastEnc, hadME);
+  std::vector<short> org(W * H), ref(S * (H + 2 * M));
+  const int maxv = (1 << B) - 1;
+  for (int r = 0; r < H + 2 * M; r++) // a smooth surface plus noise: the costs have a real minimum between samples
+    for (int c = 0; c < S; c++) {
+      const int v = (maxv / 2) + (int)((maxv / 3) * std::sin(c / 3.7) * std::cos(r / 4.3)) + (int)(next() % 5) - 2;
+      ref[r * S + c] = (short)(v < 0 ? 0 : v > maxv ? maxv : v);
+    }
+  const int sx = (int)(next() % 5) - 2, sy = (int)(next() % 5) - 2;
+  for (int r = 0; r < H; r++)
+    for (int c = 0; c < W; c++) { // between the sample at (sx, sy) and its right / lower neighbour
+      const int a = ref[(M + r + sy) * S + M + c + sx], b = ref[(M + r + sy) * S + M + c + sx + 1], d = ref[(M + r + sy + 1) * S + M + c + sx];
+      org[r * W + c] = (short)((2 * a + b + d + 2) >> 2);
+    }
+  short *d_org = nullptr, *d_ref = nullptr;
+  ctx.check(hmx_malloc(ctx.get(), org.size() * 2, (void **)&d_org), "malloc");
+  ctx.check(hmx_malloc(ctx.get(), ref.size() * 2, (void **)&d_ref), "malloc");
+  ctx.check(hmx_upload(ctx.get(), d_org, org.data(), org.size() * 2), "upload");
+  ctx.check(hmx_upload(ctx.get(), d_ref, ref.data(), ref.size() * 2), "upload");
+  hmx_pic po{}, pr{};
+  po.plane[0] = d_org, po.stride[0] = W;
+  pr.plane[0] = d_ref + M * S + M, pr.stride[0] = S;
+  const int x = 24, y = 16, w = fastEnc ? 8 : 16, h = fastEnc ? 16 : 8;
+  const int pred[2] = {(int)(next() % 25) - 12, (int)(next() % 25) - 12}, start[2] = {4 * sx + (int)(next() % 9) - 4, 4 * sy + (int)(next() % 9) - 4};
+  const unsigned bitsIn = next() % 7;
+  rd.setLambda(20.0 + next() % 40);
+  rd.getMotionCost(true, 0);
+  printf("%d %d %d %d %d %d %d %u %d %d %d %d %d %u %d %d\n", x, y, w, h, (fastEnc && h > 8) ? 1 : 0, pred[0], pred[1], rd.motionCostMultiplier(), W, H, M,
+         hadME ? 1 : 0, RANGE, bitsIn, start[0], start[1]);
+  for (int v : org) printf("%d ", v);
+  printf("\n");
+  for (int v : ref) printf("%d ", v);
+  printf("\n");
+  for (int bi = 0; bi < 2; bi++) {
+    int mv[2] = {start[0], start[1]};
+    hmx_hm::UInt bits = bitsIn, cost = 0;
+    search.xMotionEstimation(&po, &pr, x, y, w, h, pred, RANGE, bi != 0, mv, bits, cost);
+    printf("%d %d %u %u\n", mv[0], mv[1], bits, cost);
+  }
+  hmx_free(ctx.get(), d_org);
+  hmx_free(ctx.get(), d_ref);
+  return 0;
+}
+
 int main(int argc, char **argv) {
+  if (argc >= 2 && std::string(argv[1]) == "frac") {
+    try {
+      return frac_main(argc, argv);
+    } catch (const std::exception &e) {
+      fprintf(stderr, "error: %s\n", e.what());
+      return 1;
+    }
+  }
   if (argc >= 2 && std::string(argv[1]) == "me") {
     try {
       return me_main(argc, argv);

@@ -328,7 +328,8 @@ private:
   Int m_iPredHor = 0, m_iPredVer = 0, m_iCostScale = 0;
 };
 
-// TEncSearch, the integer stage of xMotionEstimation (TEncSearch.cpp:4120-4283) for ONE unit over hmx_batch_fullpel_search.
+// TEncSearch, xMotionEstimation (TEncSearch.cpp:4120-4283, :4476-4514) for ONE unit: the integer stage over
+// hmx_batch_fullpel_search, the fractional stage over hmx_batch_subpel_search.
 // What the reference reads through pcCU, the pattern key and the slice is explicit: the unit's position and size, the
 // pictures (DEVICE pictures: the original, and the reference with its margins) and their geometry.
 class TEncSearch {
@@ -336,10 +337,15 @@ public:
   struct Geometry {
     Int picWidth, picHeight, marginX, marginY, ctuSize;
   };
-  TEncSearch(Context &c, TComRdCost &rd, const Geometry &g, Bool useFastEnc = false) : m_c(c), m_rd(rd), m_g(g), m_fastEnc(useFastEnc) {
+  TEncSearch(Context &c, TComRdCost &rd, const Geometry &g, Bool useFastEnc = false, Bool useHADME = true)
+      : m_c(c), m_rd(rd), m_g(g), m_fastEnc(useFastEnc), m_useHADME(useHADME) {
     m_c.check(hmx_malloc(m_c.get(), sizeof(hmx_me_result), (void **)&m_dResult), "TEncSearch");
+    m_c.check(hmx_malloc(m_c.get(), sizeof(hmx_subpel_result) + 18 * sizeof(uint32_t), (void **)&m_dFrac), "TEncSearch");
   }
-  ~TEncSearch() { hmx_free(m_c.get(), m_dResult); }
+  ~TEncSearch() {
+    hmx_free(m_c.get(), m_dResult);
+    hmx_free(m_c.get(), m_dFrac);
+  }
   TEncSearch(const TEncSearch &) = delete;
   TEncSearch &operator=(const TEncSearch &) = delete;
   // xSetSearchRange (:4209-4225): cMvPred in quarter samples, the corners in integer samples
@@ -366,13 +372,70 @@ public:
     rcMv[0] = r.mvx, rcMv[1] = r.mvy;
     ruiSAD = r.sad;
   }
+  // xPatternSearchFracDIF (:4476-4514): both stages of xPatternRefinement around pcMvInt (integer samples) in one device call
+  // (getUseHADME() is the constructor's flag).  ruiCost = the winning quarter-stage cost.  The device returns the refined
+  // vector; rcMvHalf and rcMvQter (each component -1..1), which the reference's caller only adds up again (:4198-4200), are
+  // split from it with the half-stage costs: the half-sample winner is the first strictly smallest of the nine.  The vector
+  // cost is m_pcRdCost's: getMotionCost(1, 0) and setPredictor as xMotionEstimation has left them (:4186); the cost scales
+  // 1 and 0 of the two stages are the entry's own.
+  void xPatternSearchFracDIF(const hmx_pic *pcOrg, const hmx_pic *pcRef, Int x, Int y, Int iRoiWidth, Int iRoiHeight, const Int pcMvInt[2],
+                             Int rcMvHalf[2], Int rcMvQter[2], UInt &ruiCost) {
+    hmx_me_unit u{};
+    u.x = (uint16_t)x, u.y = (uint16_t)y, u.w = (uint8_t)iRoiWidth, u.h = (uint8_t)iRoiHeight;
+    u.pred_x = (int16_t)m_rd.predictorHor(), u.pred_y = (int16_t)m_rd.predictorVer();
+    u.left = u.right = (int16_t)pcMvInt[0], u.top = u.bottom = (int16_t)pcMvInt[1]; // the box of one vector: the host checks its window
+    hmx_me_result in{};
+    in.mvx = (int16_t)pcMvInt[0], in.mvy = (int16_t)pcMvInt[1];
+    m_c.check(hmx_upload(m_c.get(), m_dResult, &in, sizeof(in)), "xPatternSearchFracDIF");
+    uint32_t *dCosts = reinterpret_cast<uint32_t *>(m_dFrac + 1);
+    m_c.check(hmx_batch_subpel_search(m_c.get(), &u, 1, m_dResult, pcRef, 1, pcOrg, m_g.picWidth, m_g.picHeight, m_g.marginX, m_g.marginY,
+                                      m_rd.motionCostMultiplier(), m_useHADME ? 1 : 0, m_dFrac, dCosts),
+              "xPatternSearchFracDIF");
+    struct {
+      hmx_subpel_result r;
+      uint32_t costs[18];
+    } out;
+    m_c.check(hmx_download(m_c.get(), &out, m_dFrac, sizeof(out)), "xPatternSearchFracDIF");
+    static const Int refineH[9][2] = {{0, 0}, {0, -1}, {0, 1}, {-1, 0}, {1, 0}, {-1, -1}, {1, -1}, {-1, 1}, {1, 1}}; // s_acMvRefineH (:47-58)
+    Int best = 0;
+    for (Int i = 1; i < 9; i++)
+      if (out.costs[i] < out.costs[best]) best = i;
+    rcMvHalf[0] = refineH[best][0], rcMvHalf[1] = refineH[best][1];
+    rcMvQter[0] = out.r.mvx - 4 * pcMvInt[0] - 2 * rcMvHalf[0], rcMvQter[1] = out.r.mvy - 4 * pcMvInt[1] - 2 * rcMvHalf[1];
+    ruiCost = out.r.cost;
+  }
+  // xMotionEstimation (:4120-4206) against one reference picture: xSetSearchRange (around rcMv when bBi, :4166), the integer
+  // stage, the fractional stage, then :4197-4205 on the host.  pcMvPred: the predictor, quarter samples.  rcMv: in (bBi only) the
+  // vector the range is centred on, out the refined vector, both in quarter samples.  ruiBits: in the bits before the vector,
+  // out with the vector's bits added.  bBi: the caller passes 2 * org - other prediction as pcOrg (removeHighFreq, :4147) and
+  // the cost takes fWeight = 0.5 (:4148).  The full search serves both cases (m_iFastSearch = 0).
+  void xMotionEstimation(const hmx_pic *pcOrg, const hmx_pic *pcRef, Int x, Int y, Int iRoiWidth, Int iRoiHeight, const Int pcMvPred[2], Int iSrchRng,
+                         Bool bBi, Int rcMv[2], UInt &ruiBits, UInt &ruiCost) {
+    const Double fWeight = bBi ? 0.5 : 1.0;
+    Int lt[2], rb[2], mvInt[2], mvHalf[2], mvQter[2];
+    if (bBi) xSetSearchRange(x, y, rcMv[0], rcMv[1], iSrchRng, lt, rb);
+    else xSetSearchRange(x, y, pcMvPred[0], pcMvPred[1], iSrchRng, lt, rb);
+    m_rd.getMotionCost(true, 0);
+    m_rd.setPredictor(pcMvPred[0], pcMvPred[1]);
+    m_rd.setCostScale(2);
+    xPatternSearch(pcOrg, pcRef, x, y, iRoiWidth, iRoiHeight, lt, rb, mvInt, ruiCost);
+    m_rd.getMotionCost(true, 0);
+    m_rd.setCostScale(1);
+    xPatternSearchFracDIF(pcOrg, pcRef, x, y, iRoiWidth, iRoiHeight, mvInt, mvHalf, mvQter, ruiCost);
+    m_rd.setCostScale(0);
+    for (int k = 0; k < 2; k++) rcMv[k] = (mvInt[k] << 2) + (mvHalf[k] << 1) + mvQter[k];
+    const UInt uiMvBits = m_rd.getBits(rcMv[0], rcMv[1]);
+    ruiBits += uiMvBits;
+    ruiCost = (UInt)(std::floor(fWeight * ((Double)ruiCost - (Double)m_rd.getCost(uiMvBits))) + (Double)m_rd.getCost(ruiBits));
+  }
 
 private:
   Context &m_c;
   TComRdCost &m_rd;
   Geometry m_g;
-  Bool m_fastEnc;
+  Bool m_fastEnc, m_useHADME;
   hmx_me_result *m_dResult = nullptr;
+  hmx_subpel_result *m_dFrac = nullptr; // the result, then the 18 stage costs
 };
 
 // TComInterpolationFilter (TComInterpolationFilter.cpp:323-415): identical signatures
