@@ -106,9 +106,10 @@ __device__ __forceinline__ void wave_chain_valu(char *smem, const SRC &src, cons
     const TiledPlane &R = V.rec;
     const unsigned b0 = tile_base(R.ctu_w, R.clog, x, y); // same geometry for org and rec
     int pred[N], row[N];
+    s4v org4[N / 4]; // the original row: loaded before the wait (independent of the references), kept packed until the residual is formed
     int *lev_row = V.lev + lev_row_off<N>(V, x, y, gl);
     const size_t pb0 = tphys(R.qstride, b0);
-    if (ENC && active) tload_row<N>(V.org + pb0, R.qstride, gl, row); // independent of the references
+    if (ENC && active) tload_row_raw<N>(V.org + pb0, R.qstride, gl, org4);
     HMX_MARK(N, 1);
     src.wait(); // packed schedule: the blocks this one predicts from belong to earlier rows of the same launch
     HMX_MARK(N, 2);
@@ -119,7 +120,7 @@ __device__ __forceinline__ void wave_chain_valu(char *smem, const SRC &src, cons
     HMX_MARK(N, 4);
     if (ENC) {
 #pragma unroll
-      for (int k = 0; k < N; k++) row[k] = wrap16(row[k] - pred[k]);
+      for (int k = 0; k < N; k++) row[k] = wrap16((int)org4[k >> 2][k & 3] - pred[k]);
       if constexpr (SRC::kRdoq) { // xRateDistOptQuant in the quantiser's place (transform-skip blocks keep the flat one)
         static_assert(N >= 8, "4x4 blocks with RDOQ run in the lane-per-block chain");
         wave_sync(); // the prediction has read the reference line
@@ -169,7 +170,8 @@ __device__ __forceinline__ void wave_chain_valu(char *smem, const SRC &src, cons
         int o[N];
         unsigned d = 0;
         if (active) {
-          tload_row<N>(V.org + pb0, R.qstride, gl, o); // the original row again (it went into the residual): an L2 hit
+          tload_row_raw<N>(V.org + pb0, R.qstride, gl, org4); // the original row again (it went into the residual): an L2 hit
+          row_unpack<N>(org4, o);
           d = sse_samples<N>(o, row, P.bit_depth);
         }
         d = (unsigned)group_sum((int)d, N);
@@ -206,9 +208,10 @@ __device__ __forceinline__ void wave_chain_8x2(char *smem, const SRC &src, const
   const size_t pb0 = tphys(R.qstride, b0);
   const int B = P.bit_depth, tshift = 15 - B - LG, mx = (1 << B) - 1;
   int pred[16], v[16];
+  s4v org4[4]; // the lane's two original rows, packed until the residual is formed
   if (ENC && active) {
-    tload_row<N>(V.org + pb0, R.qstride, r0, v);
-    tload_row<N>(V.org + pb0, R.qstride, r0 + 1, v + 8);
+    tload_row_raw<N>(V.org + pb0, R.qstride, r0, org4);
+    tload_row_raw<N>(V.org + pb0, R.qstride, r0 + 1, org4 + 2);
   }
   HMX_MARK(82, 1);
   src.wait();
@@ -229,7 +232,7 @@ __device__ __forceinline__ void wave_chain_8x2(char *smem, const SRC &src, const
   if (ENC) {
     int coef[16];
 #pragma unroll
-    for (int k = 0; k < 16; k++) v[k] = wrap16(v[k] - pred[k]);
+    for (int k = 0; k < 16; k++) v[k] = wrap16((int)org4[k >> 2][k & 3] - pred[k]);
     if (ts) {
 #pragma unroll
       for (int k = 0; k < 16; k++) coef[k] = tshift >= 0 ? v[k] << tshift : (v[k] + (1 << (-tshift - 1))) >> (-tshift);
@@ -409,8 +412,9 @@ __device__ __forceinline__ void wave_chain_8x2(char *smem, const SRC &src, const
       int o[16];
       unsigned d = 0;
       if (active) {
-        tload_row<N>(V.org + pb0, R.qstride, r0, o);
-        tload_row<N>(V.org + pb0, R.qstride, r0 + 1, o + 8);
+        tload_row_raw<N>(V.org + pb0, R.qstride, r0, org4);
+        tload_row_raw<N>(V.org + pb0, R.qstride, r0 + 1, org4 + 2);
+        row_unpack<16>(org4, o);
         d = sse_samples<16>(o, out, B);
       }
       d = (unsigned)group_sum((int)d, NL);
@@ -531,6 +535,7 @@ __device__ __forceinline__ void wave_chain_4_lane(char *smem, const SRC &src, co
   const int lane = lane_id();
   const int B = P.bit_depth, mx = (1 << B) - 1;
   for (int base = 0; ONCE ? base < 1 : base < count; base += 64) {
+    HMX_MARK(4, 0);
     const int i = base + lane;
     const bool active = i < count;
     const FTu ft = src.desc(active ? i : 0);
@@ -581,34 +586,9 @@ __device__ __forceinline__ void wave_chain_4_lane(char *smem, const SRC &src, co
         lq[k] = stream_load(from + (lane & 3));
       }
     }
+    HMX_MARK(4, 1);
     src.wait(); // the whole wave (packed schedule): the neighbours belong to earlier rows of the same launch
-    if (ENC && !(HMX_X_SKIP & 4)) {
-      if constexpr (COOP) {
-        wave_sync();
-        co_tile[lane] = o0, co_tile[64 + lane] = o1;
-        wave_sync();
-        o0 = co_tile[2 * lane], o1 = co_tile[2 * lane + 1];
-        wave_sync(); // the reference lines take the scratch
-      }
-      if (COOP || active) {
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-          v[2 * k] = (short)(o0[k] & 0xffff), v[2 * k + 1] = o0[k] >> 16;
-          v[8 + 2 * k] = (short)(o1[k] & 0xffff), v[8 + 2 * k + 1] = o1[k] >> 16;
-        }
-      }
-    }
-    if (!ENC && co_lev) {
-#pragma unroll
-      for (int k = 0; k < 4; k++) *reinterpret_cast<i4v *>(co_rows + (16 * k + (lane >> 2)) * 20 + 4 * (lane & 3)) = lq[k];
-      wave_sync();
-#pragma unroll
-      for (int r = 0; r < 4; r++) {
-        const i4v o = *reinterpret_cast<const i4v *>(co_rows + lane * 20 + 4 * r);
-        w[4 * r] = o[0], w[4 * r + 1] = o[1], w[4 * r + 2] = o[2], w[4 * r + 3] = o[3];
-      }
-      wave_sync(); // the reference lines take the scratch
-    }
+    HMX_MARK(4, 2);
     if (!COOP && !active) continue;
     // ---- reference line (fillReferenceSamples): sequential padding is natural inside one lane.
     int *line = LS.line[lane];
@@ -666,6 +646,36 @@ __device__ __forceinline__ void wave_chain_4_lane(char *smem, const SRC &src, co
         for (int k = 0; k < 4; k++) raw[9 + k] = va[k], raw[13 + k] = var[k];
         raw[8] = vc[3];
       }
+      // The lanes' exchanges through the scratch (originals in, decoder: levels in) come BEHIND the gather's wait: in front of it they
+      // waited for the next wave-item's descriptor, fetched behind the poll, on their own -- one more serial trip to memory.  The
+      // reference lines take the scratch after them.
+      if (ENC && !(HMX_X_SKIP & 4)) {
+        if constexpr (COOP) {
+          wave_sync();
+          co_tile[lane] = o0, co_tile[64 + lane] = o1;
+          wave_sync();
+          o0 = co_tile[2 * lane], o1 = co_tile[2 * lane + 1];
+          wave_sync(); // the reference lines take the scratch
+        }
+        if (COOP || active) {
+#pragma unroll
+          for (int k = 0; k < 4; k++) {
+            v[2 * k] = (short)(o0[k] & 0xffff), v[2 * k + 1] = o0[k] >> 16;
+            v[8 + 2 * k] = (short)(o1[k] & 0xffff), v[8 + 2 * k + 1] = o1[k] >> 16;
+          }
+        }
+      }
+      if (!ENC && co_lev) {
+#pragma unroll
+        for (int k = 0; k < 4; k++) *reinterpret_cast<i4v *>(co_rows + (16 * k + (lane >> 2)) * 20 + 4 * (lane & 3)) = lq[k];
+        wave_sync();
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+          const i4v o = *reinterpret_cast<const i4v *>(co_rows + lane * 20 + 4 * r);
+          w[4 * r] = o[0], w[4 * r + 1] = o[1], w[4 * r + 2] = o[2], w[4 * r + 3] = o[3];
+        }
+        wave_sync(); // the reference lines take the scratch
+      }
       if (!pad_pass) { // every position a mode of this wave reads holds its own sample (see intra_refs_tiled)
 #pragma unroll
         for (int p = 0; p <= 16; p++) line[p] = raw[p];
@@ -695,6 +705,7 @@ __device__ __forceinline__ void wave_chain_4_lane(char *smem, const SRC &src, co
         }
       }
     }
+    HMX_MARK(4, 3);
     // ---- prediction (4x4 never uses the smoothed line)
     int pred[16];
     {
@@ -767,6 +778,7 @@ __device__ __forceinline__ void wave_chain_4_lane(char *smem, const SRC &src, co
         w[4 * r] = o[0], w[4 * r + 1] = o[1], w[4 * r + 2] = o[2], w[4 * r + 3] = o[3];
       }
     }
+    HMX_MARK(4, 4);
     int out[16];
     lane4_inverse(w, luma, ts, luma, P, out);
     i4v r0, r1;
@@ -843,9 +855,12 @@ __device__ __forceinline__ void wave_chain_32(char *smem, const SRC &src, const 
       for (int q = 0; q < 4; q++)
         org4[q] = stream_load(reinterpret_cast<const s4v *>(V.org + row_off + trel<32>(R.qstride, tile_in_block(2 * q + h, r >> 2))));
     }
+    HMX_MARK(32, 1);
     src.wait();
+    HMX_MARK(32, 2);
     const bool filt = luma && use_filtered_refs(t.mode, LG);
     intra_refs_tiled<32, 64, SRC::kCoherent>(L, lane, true, R, x, y, tphys(R.qstride, b0), luma, avail, pads, filt, P);
+    HMX_MARK(32, 3);
     const int *RL = filt ? L.fline : L.line;
     const int dcs = wave_needs(t.mode == 1) ? dc_sum_block<32, 64>(L, lane) : 0;
     build_main_ref<32, 64>(RL, L.me, t.mode, lane);
@@ -862,7 +877,7 @@ __device__ __forceinline__ void wave_chain_32(char *smem, const SRC &src, const 
       int coef[16];
 #pragma unroll
       for (int s = 0; s < 16; s++) v[s] = wrap16((int)org4[s >> 2][s & 3] - pred[s]);
-      HMX_MARK(32, 1);
+      HMX_MARK(32, 4);
       fwd32_mfma(v, r, h, P.bit_depth, coef);
       if constexpr (SRC::kRdoq) {
         wave_sync();
@@ -872,7 +887,7 @@ __device__ __forceinline__ void wave_chain_32(char *smem, const SRC &src, const 
         wave_sync();
         rdoq_wave_tiles<32, 1>(&L, src.rdoq_lds(), src.rdoq(), P, lane);
       } else {
-        HMX_MARK(32, 2);
+        HMX_MARK(32, 5);
         quant_sbh_diag<32, 16>(L, lane, lane, true, coef, [&](int k) { return mrow(k, h); }, [&](int) { return r; }, luma, diag_group_org<32>(lane), P);
       }
 #pragma unroll
@@ -884,7 +899,7 @@ __device__ __forceinline__ void wave_chain_32(char *smem, const SRC &src, const 
 #pragma unroll
       for (int g = 0; g < 16; g++) v[g] = lev0[__umul24((unsigned)mrow(g, h), (unsigned)lstep)];
     }
-    HMX_MARK(32, 3);
+    HMX_MARK(32, 6);
     const int tshift = 15 - P.bit_depth - LG;
     const QuantDev qd = pick_qd(P, luma);
     int out[16];

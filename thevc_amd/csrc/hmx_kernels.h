@@ -140,17 +140,20 @@ __device__ __forceinline__ T stream_load(const T *p) { return *p; }
 template <typename T>
 __device__ __forceinline__ void stream_store(T *p, T v) { *p = v; }
 #endif
-// row r of the aligned N x N block (N >= 8) whose first sample has offset b0; pb = p + tphys(b0)
+// row r of the aligned N x N block whose first sample has offset b0, as its N/4 raw 8-byte words; pb = p + tphys(b0).
+// The whole-picture chains issue these loads BEFORE they wait for the rows they
+// depend on and unpack them (row_unpack) only where the residual is formed.  Unpacked at once, every load had its
+// s_waitcnt right behind it: a serial round trip to HBM per word, in front of the dependency poll and of the ticket atomic
+// whose latency the chain was to hide (vmcnt retires in order).
 template <int N>
-__device__ __forceinline__ void tload_row(const short *pb, unsigned qstride, int r, int *x) {
+__device__ __forceinline__ void tload_row_raw(const short *pb, unsigned qstride, int r, s4v *v) {
 #pragma unroll
-  for (int q = 0; q < N / 4; q++) {
-    const s4v v = stream_load(reinterpret_cast<const s4v *>(pb + trel<N>(qstride, tile_in_block(q, r >> 2) + ((r & 3) << 2))));
-    x[4 * q] = v[0];
-    x[4 * q + 1] = v[1];
-    x[4 * q + 2] = v[2];
-    x[4 * q + 3] = v[3];
-  }
+  for (int q = 0; q < N / 4; q++) v[q] = stream_load(reinterpret_cast<const s4v *>(pb + trel<N>(qstride, tile_in_block(q, r >> 2) + ((r & 3) << 2))));
+}
+template <int N>
+__device__ __forceinline__ void row_unpack(const s4v *v, int *x) {
+#pragma unroll
+  for (int k = 0; k < N; k++) x[k] = v[k >> 2][k & 3];
 }
 template <int N, bool COH = false>
 __device__ __forceinline__ void tstore_row(short *pb, unsigned qstride, int r, const int *x) {
@@ -210,7 +213,13 @@ __device__ __forceinline__ int quant_sbh_block(LT &L, int gl, bool active, const
   const int qbits = 14 + qd.per_qbits + tshift;
   int sum = 0;
   if (active) { // idle lanes may alias another block's scratch: never let them write
-    if (gl == 0) L.nzmask[0] = L.nzmask[1] = 0;
+    if (gl == 0) {
+      // a zero made HERE: a plain constant is hoisted out of the persistent loop of k_intra_packed as a register pair that lives
+      // through all four chains, and, out of registers, was parked in scratch memory and reloaded in front of this store
+      int z = 0;
+      asm volatile("" : "+v"(z));
+      L.nzmask[0] = z, L.nzmask[1] = z;
+    }
 #pragma unroll
     for (int k = 0; k < NCOEF; k++) {
       int al;
@@ -464,32 +473,50 @@ __device__ __forceinline__ int mask_top(unsigned m) { return 31 - __clz((int)m);
 __device__ __forceinline__ int mask_top(unsigned long long m) { return 63 - __clzll((long long)m); }
 __device__ __forceinline__ int mask_first(unsigned m) { return __ffs((int)m) - 1; }
 __device__ __forceinline__ int mask_first(unsigned long long m) { return __ffsll((long long)m) - 1; }
+// An empty instruction that reads and "rewrites" K values (addresses, or the destinations of loads) held in vector registers:
+// every one of them is complete in a register of its own at this point, and nothing that uses one can move above it.
+template <int K, typename V>
+__device__ __forceinline__ void pin_regs(V *v) {
+  if constexpr (K == 1) asm volatile("" : "+v"(v[0]));
+  else if constexpr (K == 2) asm volatile("" : "+v"(v[0]), "+v"(v[1]));
+  else if constexpr (K == 3) asm volatile("" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]));
+  else if constexpr (K == 4) asm volatile("" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]));
+  else if constexpr (K == 5) asm volatile("" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]));
+  else if constexpr (K == 6) asm volatile("" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]));
+  else {
+    pin_regs<6>(v);
+    pin_regs<K - 6>(v + 6);
+  }
+}
 template <int N, int NL, bool COH, typename M, typename LT>
 __device__ __forceinline__ void refs_gather_pad(LT &L, int gl, bool active, const TiledPlane &R, int x, int y, const short *idle, bool luma,
                                                 M avail, bool pad_pass, int bit_depth) {
   constexpr int T = 2 * N + 1 + N / 2, IT = (T + NL - 1) / NL;
   const int ul = luma ? 2 : 1, n = N >> ul;
-  s4v v[IT];
-  if (active) {
+  // Phase 1: the addresses of the lane's IT units, without a branch -- a unit past T, outside the mask or of a lane without a
+  // block names the stand-in address -- so that the rounds are one basic block.
+  const short *a[IT];
 #pragma unroll
-    for (int it = 0; it < IT; it++) {
-      const int t = gl + it * NL;
-      if (t < T) {
-        int tx, ty, u;
-        unsigned um = 1;
-        if (t < 2 * N) { // left column, bottom to top: p = t, sample (x-1, y+2N-1-t)
-          tx = x - 4, ty = y + 2 * N - 1 - t, u = t >> ul;
-        } else if (t == 2 * N) { // corner
-          tx = x - 4, ty = y - 1, u = 2 * n;
-        } else { // tile j of the row above: p = 2N+1+4j .. +3 (one luma unit, two chroma units)
-          const int j = t - 2 * N - 1;
-          tx = x + 4 * j, ty = y - 1, u = 2 * n + 1 + ((4 * j) >> ul), um = luma ? 1u : 3u;
-        }
-        const bool on = ((avail >> u) & um) != 0;
-        v[it] = ld_rec4<COH>(on ? R.p + tphys(R.qstride, tile_base(R.ctu_w, R.clog, tx, ty) + ((unsigned)(ty & 3) << 2)) : idle);
-      }
-    }
+  for (int it = 0; it < IT; it++) {
+    const int t0 = gl + it * NL, t = (it + 1) * NL > T ? min(t0, T - 1) : t0;
+    // t < 2N: left column, bottom to top: p = t, sample (x-1, y+2N-1-t); t = 2N: corner; else tile j of the row above:
+    // p = 2N+1+4j .. +3 (one luma unit, two chroma units)
+    const bool left = t < 2 * N, above = t > 2 * N;
+    const int j = t - 2 * N - 1;
+    const int tx = above ? x + 4 * j : x - 4, ty = left ? y + 2 * N - 1 - t : y - 1;
+    const int u = left ? t >> ul : above ? 2 * n + 1 + ((4 * j) >> ul) : 2 * n;
+    const unsigned um = above && !luma ? 3u : 1u;
+    const bool on = active && t0 < T && ((avail >> u) & um) != 0;
+    a[it] = on ? R.p + tphys(R.qstride, tile_base(R.ctu_w, R.clog, tx, ty) + ((unsigned)(ty & 3) << 2)) : idle;
   }
+  // Phase 2: the IT loads back to back into registers of their own, one wait behind the last.  The two pins keep the compiler from
+  // weaving address arithmetic and unpacking between them: it used to hand a load's destination register to the next load's
+  // address, which put a full wait between any two loads -- IT serial trips to the L2 where one was meant.
+  pin_regs<IT>(a);
+  s4v v[IT];
+#pragma unroll
+  for (int it = 0; it < IT; it++) v[it] = ld_rec4<COH>(as_global(a[it]));
+  pin_regs<IT>(v);
   const auto put = [&](int *dst) {
 #pragma unroll
     for (int it = 0; it < IT; it++) {
@@ -510,29 +537,29 @@ __device__ __forceinline__ void refs_gather_pad(LT &L, int gl, bool active, cons
   if (active) put(L.fline); // raw samples wait in L.fline (free until the smoothing pass)
   wave_sync();
   if (active) {
+    // every position's source is read before the first position is written: written one by one, each read waited for the
+    // write before it (the compiler cannot tell L.fline[q] from L.line[p])
+    constexpr int ITP = (4 * N + 1 + NL - 1) / NL;
     const int unit = 1 << ul, dcv = 1 << (bit_depth - 1);
+    const M some = avail ? avail : M(1); // no unit at all: the positions take dcv, the reads below only have to stay inside the line
+    int val[ITP];
 #pragma unroll
-    for (int it = 0; it < (4 * N + 1 + NL - 1) / NL; it++) {
+    for (int it = 0; it < ITP; it++) {
+      const int p0 = gl + it * NL, p = (it + 1) * NL > 4 * N + 1 ? min(p0, 4 * N) : p0;
+      const int u = p < 2 * N ? (p >> ul) : (p == 2 * N ? 2 * n : 2 * n + 1 + ((p - 2 * N - 1) >> ul));
+      const M lower = some & ((M(1) << u) - 1);
+      // the last sample of the nearest available unit below, or the first sample of the first available unit
+      const int u2 = lower ? mask_top(lower) : mask_first(some);
+      const int d = u2 - 2 * n;
+      const int q_last = d < 0 ? (u2 << ul) + unit - 1 : (d == 0 ? 2 * N : 2 * N + (int)((unsigned)d << ul));
+      const int q_first = d < 0 ? (u2 << ul) : (d == 0 ? 2 * N : 2 * N + 1 + (int)((unsigned)(d - 1) << ul));
+      const int q = ((some >> u) & 1) ? p : (lower ? q_last : q_first);
+      val[it] = L.fline[q];
+    }
+#pragma unroll
+    for (int it = 0; it < ITP; it++) {
       const int p = gl + it * NL;
-      if (p <= 4 * N) {
-        int val = dcv;
-        if (avail != 0) {
-          const int u = p < 2 * N ? (p >> ul) : (p == 2 * N ? 2 * n : 2 * n + 1 + ((p - 2 * N - 1) >> ul));
-          int q = p;
-          if (!((avail >> u) & 1)) {
-            const M lower = avail & ((M(1) << u) - 1);
-            if (lower) {
-              const int u2 = mask_top(lower); // last sample of the nearest available unit below
-              q = u2 < 2 * n ? (u2 << ul) + unit - 1 : (u2 == 2 * n ? 2 * N : 2 * N + ((u2 - 2 * n) << ul));
-            } else {
-              const int u2 = mask_first(avail); // first sample of the first available unit
-              q = u2 < 2 * n ? (u2 << ul) : (u2 == 2 * n ? 2 * N : 2 * N + 1 + ((u2 - 2 * n - 1) << ul));
-            }
-          }
-          val = L.fline[q];
-        }
-        L.line[p] = val;
-      }
+      if ((it + 1) * NL <= 4 * N + 1 || p <= 4 * N) L.line[p] = avail ? val[it] : dcv;
     }
   }
   wave_sync();
