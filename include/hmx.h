@@ -63,7 +63,8 @@ int hmx_sync(hmx_ctx *ctx);
  * HMX_INTRA_ACROSS, HMX_INTRA_STREAMS, HMX_PIPELINE_CONV, HMX_GRAPH (level schedules), HMX_PACK_SLOTS4 = 16 | 64, HMX_PACK_SLOTS8 = 8 | 16,
  * HMX_PACK_GROUP, HMX_PACK_WAVES, HMX_PACK_SLEEP0, HMX_PACK_SLEEP1 (packed schedule), HMX_RDOQ_LANE (RDOQ: every block
  * through the one-lane-per-block kernel), HMX_PLAN_ROWS (device plan builder: rows of the level table per picture to start with), HMX_PLAN_STREAMS (1: its luma and chroma
- * level walks one after the other instead of side by side on two streams). */
+ * level walks one after the other instead of side by side on two streams), HMX_TZ_MAX_PASSES = 1 .. 1024 (hmx_batch_tz_search:
+ * star-refinement passes of one unit before it is answered with the all-ones cost; a guard, not a tuning knob; default 1024). */
 int hmx_set_option(hmx_ctx *ctx, const char *name, const char *value);
 /* device memory + timing plumbing so that callers need no HIP headers */
 int hmx_malloc(hmx_ctx *ctx, size_t bytes, void **dptr);
@@ -638,7 +639,7 @@ typedef struct { int16_t mvx, mvy; uint32_t sad; uint32_t cost; } hmx_me_result;
  * of the box areas of units 0..i-1.  refs (n_refs <= 4) / org: device pictures, the references with margins of margin_x /
  * margin_y luma samples and samples in [0, 2^B); org may hold any value in [-2^B, 2^(B+1)) -- bi-prediction refinement
  * searches against 2 * org - other prediction (removeHighFreq, :4147), which the caller passes as org.  Weighted SAD
- * (xGetSADw), chroma and xTZSearch are not covered.
+ * (xGetSADw) and chroma are not covered; xTZSearch is hmx_batch_tz_search below.
  * n >= 1 and the boxes together hold fewer than 2^32 candidates; anything else is HMX_ERR_ARG.
  * HMX_ERR_ARG, on the host before anything is launched, with the unit named in hmx_last_error: a size outside the set, ref >=
  * n_refs, sub_shift other than 0 or (1 with h > 8), an empty box, a box side above 129 (search range 64), the unit outside the
@@ -646,6 +647,42 @@ typedef struct { int16_t mvx, mvy; uint32_t sad; uint32_t cost; } hmx_me_result;
 int hmx_batch_fullpel_search(hmx_ctx *ctx, const hmx_me_unit *units, int n, const hmx_pic *refs, int n_refs, const hmx_pic *org,
                              int pic_w, int pic_h, int margin_x, int margin_y, uint32_t lambda, hmx_me_result *d_result,
                              uint32_t *d_cost_map);
+/* TEncSearch::xTZSearch (TEncSearch.cpp:4302-4474, through xPatternSearchFast, :4285-4300) for every unit of `units`, as the
+ * reference compiles it: TZ_SEARCH_CONFIGURATION (:293-309) with FASTME_SMOOTHER_MV 1.  The walk of one unit:
+ *   1. the start point tz[i].start (rcMv after clipMv and >>= 2, :4312-4313: the caller makes it with hmx_clipMv), then the zero
+ *      vector (bTestZeroVector), which may lie outside the box;
+ *   2. first search: xTZ8PointDiamondSearch (:536-707) around the better of the two with iDist = 1, 2, 4 ... <= tz[i].range,
+ *      left as soon as uiBestRound >= 3;
+ *   3. xTZ2PointSearch (:351-479) when uiBestDistance == 1;
+ *   4. when uiBestDistance > 5: every fifth candidate of the box, rows from top, columns from left (raster search);
+ *   5. star refinement while uiBestDistance > 0: the diamonds iDist = 1, 2, 4 ... <= range around the best point with no early
+ *      exit, then the 2-point search when uiBestDistance == 1 (and ucPointNr != 0), one PASS each.
+ * Every evaluation is xTZSearchHelp (:312-349): cost = SAD + hmx_mvCost(lambda, x, y, pred_x, pred_y, 2), SAD as hmx_getSAD
+ * with the unit's sub_shift (FEN: 1 for more than 8 rows), all uint32_t; a candidate replaces the best on a strictly smaller
+ * cost only, and then sets uiBestDistance, ucPointNr and uiBestRound = 0.  A pattern point is evaluated when each coordinate
+ * that moves away from the pattern's centre stays on the box's side it moves towards: nothing else is tested, so a walk that
+ * adopts a zero vector outside the box evaluates points outside the box, all of them inside the bounding rectangle of
+ * box U {(0, 0)}.  The other predicted vectors, the zero-vector restart and the raster refinement are compiled off in the
+ * reference and absent here; weighted SAD and chroma are not covered.
+ * units: the HOST array hmx_batch_fullpel_search takes (pred_x / pred_y: the unclipped setPredictor values); tz: HOST array
+ * parallel to it; range is uiSearchRange = m_iSearchRange (m_aaiAdaptSR: per reference picture, hence per unit).
+ * d_result[i] (device) = {iBestX, iBestY, sad = uiBestSad - vector cost (ruiSAD, :4473), cost = uiBestSad}: d_int of
+ * hmx_batch_subpel_search.  d_trace / d_trace_count (device, both or neither NULL): d_trace_count[i] = the number of
+ * evaluations of unit i, all of them; d_trace[i * trace_cap + k] = the k-th evaluated point and its cost, in the reference's
+ * order, for k < min(count, trace_cap); nothing is written beyond.
+ * The star refinement ends because every pass that continues has lowered a uint32_t cost.  The kernel still counts passes
+ * against a cap: HMX_TZ_MAX_PASSES (hmx_set_option, 1 .. 1024, default 1024).  A unit that asks for another pass after `cap`
+ * passes gets {best so far, sad = cost = 0xFFFFFFFF}; its evaluations stay in its trace; other units are unaffected.
+ * HMX_ERR_ARG, on the host before anything is launched, with the unit named in hmx_last_error: what hmx_batch_fullpel_search
+ * refuses for a unit (size, ref, sub_shift, empty box, side above 129, unit outside the picture); a NULL pointer other than the
+ * two trace pointers, exactly one of those NULL, trace_cap < 1 with a trace, n < 1, n_refs outside 1..4, range outside 1..64,
+ * reserved != 0, a start point outside the box, and the bounding rectangle of box U {(0, 0)} grown by the block reaching outside
+ * [-margin, pic + margin) of the reference in either direction. */
+typedef struct { int16_t start_x, start_y; uint16_t range; uint16_t reserved; } hmx_tz_unit; /* 8 bytes */
+typedef struct { int16_t x, y; uint32_t cost; } hmx_tz_point; /* 8 bytes */
+int hmx_batch_tz_search(hmx_ctx *ctx, const hmx_me_unit *units, const hmx_tz_unit *tz, int n, const hmx_pic *refs, int n_refs,
+                        const hmx_pic *org, int pic_w, int pic_h, int margin_x, int margin_y, uint32_t lambda,
+                        hmx_me_result *d_result, hmx_tz_point *d_trace, uint32_t *d_trace_count, int trace_cap);
 /* TEncSearch::xPatternSearchFracDIF (TEncSearch.cpp:4476-4514) for every unit of `units`, both stages and both decisions of
  * xPatternRefinement (:711-760) in one launch, from the integer winners where hmx_batch_fullpel_search left them.
  * units: the HOST array given to the integer search (position, size, ref, predictor, box; sub_shift is ignored: setDistParam

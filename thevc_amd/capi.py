@@ -98,6 +98,14 @@ class MeResult(C.Structure):  # hmx_me_result
     _fields_ = [("mvx", C.c_int16), ("mvy", C.c_int16), ("sad", C.c_uint32), ("cost", C.c_uint32)]
 
 
+class TzUnit(C.Structure):  # hmx_tz_unit
+    _fields_ = [("start_x", C.c_int16), ("start_y", C.c_int16), ("range", C.c_uint16), ("reserved", C.c_uint16)]
+
+
+class TzPoint(C.Structure):  # hmx_tz_point
+    _fields_ = [("x", C.c_int16), ("y", C.c_int16), ("cost", C.c_uint32)]
+
+
 class SubpelResult(C.Structure):  # hmx_subpel_result
     _fields_ = [("mvx", C.c_int16), ("mvy", C.c_int16), ("dist", C.c_uint32), ("cost", C.c_uint32)]
 
@@ -105,6 +113,8 @@ class SubpelResult(C.Structure):  # hmx_subpel_result
 ME_UNIT_DTYPE = np.dtype([("x", "<u2"), ("y", "<u2"), ("w", "u1"), ("h", "u1"), ("ref", "u1"), ("sub_shift", "u1"), ("pred_x", "<i2"),
                           ("pred_y", "<i2"), ("left", "<i2"), ("top", "<i2"), ("right", "<i2"), ("bottom", "<i2")])  # hmx_me_unit
 ME_RESULT_DTYPE = np.dtype([("mvx", "<i2"), ("mvy", "<i2"), ("sad", "<u4"), ("cost", "<u4")])  # hmx_me_result
+TZ_UNIT_DTYPE = np.dtype([("start_x", "<i2"), ("start_y", "<i2"), ("range", "<u2"), ("reserved", "<u2")])  # hmx_tz_unit
+TZ_POINT_DTYPE = np.dtype([("x", "<i2"), ("y", "<i2"), ("cost", "<u4")])  # hmx_tz_point
 SUBPEL_RESULT_DTYPE = np.dtype([("mvx", "<i2"), ("mvy", "<i2"), ("dist", "<u4"), ("cost", "<u4")])  # hmx_subpel_result, quarter samples
 
 WP_DTYPE = np.dtype([("weight", "<i2", 3), ("offset", "<i2", 3), ("log2_denom", "u1", 3), ("reserved", "u1")])  # hmx_wp
@@ -329,7 +339,8 @@ def lib():
                              ("hmx_setSearchRange", [ci] * 8 + [C.POINTER(ci)] * 4, None),
                              ("hmx_getSAD", [vp, vp, ci, vp, ci, ci, ci, ci, C.POINTER(u32)], ci),
                              ("hmx_batch_fullpel_search", [vp, vp, ci, C.POINTER(Pic), ci, C.POINTER(Pic), ci, ci, ci, ci, u32, vp, vp], ci),
-                             ("hmx_batch_subpel_search", [vp, vp, ci, vp, C.POINTER(Pic), ci, C.POINTER(Pic), ci, ci, ci, ci, u32, ci, vp, vp], ci)):
+                             ("hmx_batch_subpel_search", [vp, vp, ci, vp, C.POINTER(Pic), ci, C.POINTER(Pic), ci, ci, ci, ci, u32, ci, vp, vp], ci),
+                             ("hmx_batch_tz_search", [vp, vp, vp, ci, C.POINTER(Pic), ci, C.POINTER(Pic), ci, ci, ci, ci, u32, vp, vp, vp, ci], ci)):
             if "HMX_LIB_PATH" in os.environ and not hasattr(L, name):
                 continue  # an older build loaded for an A/B run: calling the entry still raises
             getattr(L, name).argtypes = at
@@ -789,6 +800,41 @@ class Context:
             raise
         return d_res
 
+    def batch_tz_search(self, units, tz, refs, org, pic_w, pic_h, margin_x, margin_y, lambda_, want_trace=False, trace_cap=256,
+                        keep_on_device=False):
+        """hmx_batch_tz_search: units = array of ME_UNIT_DTYPE, tz = array of TZ_UNIT_DTYPE (tz_units makes it), both host.
+        Returns the results (ME_RESULT_DTYPE) and, with want_trace, (results, counts, trace): counts uint32 (n), trace
+        TZ_POINT_DTYPE (n, trace_cap), of which row i holds min(counts[i], trace_cap) entries (the rest is what the buffer held:
+        zeros here).  keep_on_device: the results stay on the device -- the DevBuf of hmx_me_result comes back in place of the
+        array (the caller frees it), issued on the context's stream and not waited for unless a trace is asked for: what
+        batch_subpel_search takes as d_int."""
+        units, tz = np.ascontiguousarray(units, ME_UNIT_DTYPE), np.ascontiguousarray(tz, TZ_UNIT_DTYPE)
+        n = len(units)
+        if n == 0 or len(tz) != n:
+            raise ValueError("batch_tz_search: at least one unit, and one hmx_tz_unit per unit")
+        ref_arr = (Pic * len(refs))(*[r.as_pic() for r in refs])
+        d_res = self.alloc(n * ME_RESULT_DTYPE.itemsize)
+        d_cnt = self.alloc(n * 4) if want_trace else None
+        d_trace = self.alloc(n * int(trace_cap) * TZ_POINT_DTYPE.itemsize).zero() if want_trace else None
+        keep = False
+        try:
+            self._chk(lib().hmx_batch_tz_search(self.h, units.ctypes.data, tz.ctypes.data, n, ref_arr, len(refs), C.byref(org.as_pic()), pic_w, pic_h,
+                                                margin_x, margin_y, int(lambda_) & 0xFFFFFFFF, d_res.ptr, d_trace.ptr if d_trace else None,
+                                                d_cnt.ptr if d_cnt else None, int(trace_cap) if want_trace else 0))
+            if want_trace or not keep_on_device:
+                self.sync()
+            res = d_res if keep_on_device else d_res.download(ME_RESULT_DTYPE, n)
+            keep = keep_on_device
+            if want_trace:
+                return res, d_cnt.download(np.uint32, n), d_trace.download(TZ_POINT_DTYPE, n * int(trace_cap)).reshape(n, int(trace_cap))
+            return res
+        finally:
+            if not keep:
+                d_res.free()
+            for d in (d_cnt, d_trace):
+                if d:
+                    d.free()
+
     def batch_subpel_search(self, units, d_int, refs, org, pic_w, pic_h, margin_x, margin_y, lambda_, use_had, want_stage_costs=False):
         """hmx_batch_subpel_search: units = array of ME_UNIT_DTYPE (host); d_int = the integer vectors, either a device buffer
         of hmx_me_result (a DevBuf or a device address, used as it is: batch_fullpel_search_device's return) or an
@@ -902,6 +948,24 @@ def set_search_range(pred_x, pred_y, range_, cu_x, cu_y, pic_w, pic_h, ctu_size=
     o = [C.c_int() for _ in range(4)]
     lib().hmx_setSearchRange(pred_x, pred_y, range_, cu_x, cu_y, pic_w, pic_h, ctu_size, *[C.byref(v) for v in o])
     return tuple(v.value for v in o)
+
+
+def clip_mv(mvx, mvy, cu_x, cu_y, pic_w, pic_h, ctu_size=64):
+    """hmx_clipMv (TComDataCU::clipMv): the vector in quarter samples, clipped for the CU at (cu_x, cu_y)."""
+    x, y = C.c_int(mvx), C.c_int(mvy)
+    lib().hmx_clipMv(C.byref(x), C.byref(y), cu_x, cu_y, pic_w, pic_h, ctu_size)
+    return x.value, y.value
+
+
+def tz_units(units, range_, pic_w, pic_h, ctu_size=64):
+    """The hmx_tz_unit array of a unit list as xTZSearch makes its start points (:4312-4313): the predictor clipped with
+    hmx_clipMv (the unit's origin as CU origin, as set_search_range is used) and >> 2; range_ for every unit."""
+    units = np.ascontiguousarray(units, ME_UNIT_DTYPE)
+    tz = np.zeros(len(units), TZ_UNIT_DTYPE)
+    for i, u in enumerate(units):
+        x, y = clip_mv(int(u["pred_x"]), int(u["pred_y"]), int(u["x"]), int(u["y"]), pic_w, pic_h, ctu_size)
+        tz[i] = (x >> 2, y >> 2, range_, 0)
+    return tz
 
 
 def qp_for(qpy, text_type, bit_depth, chroma_qp_offset=0):

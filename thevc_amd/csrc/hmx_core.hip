@@ -54,7 +54,7 @@ PicDev make_picdev(const hmx_ctx *c, const hmx_pic_param *pp) {
 // parity tests that hold the schedules against each other).  value == NULL restores the default.
 static const char *const kKnobNames[] = {"HMX_INTRA_SCHEDULE", "HMX_INTRA_ACROSS", "HMX_INTRA_STREAMS", "HMX_PIPELINE_CONV", "HMX_GRAPH",
                                          "HMX_PACK_SLOTS4",    "HMX_PACK_SLOTS8",    "HMX_PACK_GROUP",      "HMX_PACK_WAVES",    "HMX_PACK_SLEEP0",   "HMX_PACK_SLEEP1",  "HMX_PLAN_ROWS",      "HMX_PLAN_STREAMS",
-                                         "HMX_RDOQ_LANE"};
+                                         "HMX_RDOQ_LANE",      "HMX_TZ_MAX_PASSES"};
 static bool apply_knob(hmx_ctx *c, const char *name, const char *v) {
   auto &k = c->knob;
   const std::string n(name);
@@ -72,6 +72,7 @@ static bool apply_knob(hmx_ctx *c, const char *name, const char *v) {
   else if (n == "HMX_RDOQ_LANE") k.rdoq_lane_only = v && v[0] != '0';
   else if (n == "HMX_PLAN_ROWS") k.plan_rows = v ? std::max(1, atoi(v)) : 0;
   else if (n == "HMX_PLAN_STREAMS") k.plan_one_stream = v && atoi(v) == 1;
+  else if (n == "HMX_TZ_MAX_PASSES") k.tz_max_passes = v ? std::min(1024, std::max(1, atoi(v))) : 1024;
   else return false;
   return true;
 }

@@ -324,6 +324,7 @@ struct hmx_ctx {
     bool plan_one_stream = false; // HMX_PLAN_STREAMS=1: the luma and chroma level walks of the device plan builder one after the other (A/B)
     int plan_rows = 0;     // HMX_PLAN_ROWS: rows of the level table per picture the device plan builder starts with (0: from the picture size)
     bool rdoq_lane_only = false; // HMX_RDOQ_LANE: every block through the one-lane-per-block kernel (round 1's, A/B and cross-check)
+    int tz_max_passes = 1024;    // HMX_TZ_MAX_PASSES: star-refinement passes of a unit of hmx_batch_tz_search before the all-ones answer, 1..1024
   } knob;
 };
 

@@ -542,3 +542,277 @@ extern "C" int hmx_batch_subpel_search(hmx_ctx *c, const hmx_me_unit *units, int
   HIPCHK(c, hipGetLastError());
   return HMX_OK;
 }
+
+// =============================================================================================
+// xTZSearch (TEncSearch.cpp:4302-4474) over unit lists: one wave owns one unit from its start point to its result
+// =============================================================================================
+// One workgroup = one wave = one unit, so the walk's state (uiBestSad, iBestX / iBestY, uiBestDistance, uiBestRound, ucPointNr,
+// the evaluation count) is the same in all 64 lanes by construction and lives in scalar registers; there is no barrier between
+// waves and nothing shared between units.  The original block is staged in LDS once with 2^B added (as k_me_search stages it:
+// v_sad_u16 then serves originals in [-2^B, 2^(B+1))).  The candidates of one pattern are independent of the state -- their
+// centre is fixed before the pattern starts -- so they are costed side by side: a pattern of P points gives each point 64 / P'
+// lanes (P' = 2, 4, 8 or 16: start point + zero vector and the 2-point search, the 4-, 8- and 16-point diamonds; the raster grid
+// goes through in chunks of 16), which share the block's (row, four-sample segment) items, sum with v_sad_u16 and meet by lane
+// exchange.  The costs are then folded into the state in the reference's order with its strict <: the minimum of (cost, lane)
+// over the evaluated points IS that fold, since the points sit in the lanes in evaluation order.  The reference is read
+// straight from global memory in aligned 32-bit words brought to the candidate's parity with v_alignbit; every word read holds
+// at least one sample of the candidate block, so nothing outside the rectangle the host checked (rounded to words) is touched.
+// xTZ8PointDiamondSearch's "whole pattern inside" fast paths and its border paths evaluate the surviving points in the same
+// order, and every border test of the diamonds and of xTZ2PointSearch is one rule: a coordinate that moves away from the centre
+// is tested against the side it moves towards.  So a pattern here is a table of (offset, point number, distance) and that rule.
+// Every loop is bounded in sight: iDist doubles up to range <= 64, the raster grid has at most 26 x 26 points, passes <= cap.
+struct TzArgs {
+  const hmx_me_unit *units;
+  const hmx_tz_unit *tz;
+  PlanesDev refs[4];
+  PlanesDev org;
+  int B, max_passes;
+  uint32_t lambda;
+  hmx_me_result *result;
+  hmx_tz_point *trace; // NULL = none
+  uint32_t *trace_count;
+  int trace_cap;
+};
+struct TzState {
+  uint32_t best;                // uiBestSad
+  int bx, by, dist, round, nr;  // iBestX, iBestY, uiBestDistance, uiBestRound, ucPointNr
+  uint32_t count;               // xTZSearchHelp calls so far
+};
+struct TzUnit {
+  const __attribute__((address_space(1))) short *ref; // the sample the zero vector points at
+  ptrdiff_t stride;
+  const unsigned short *org; // LDS, w samples a row, biased
+  int w, h, sub_shift, B, left, top, right, bottom, pred_x, pred_y;
+  uint32_t lambda;
+  __attribute__((address_space(1))) uint32_t *trace; // this unit's slice of hmx_tz_point as word pairs {x | y << 16, cost}, or NULL
+  uint32_t trace_cap;
+};
+// 16 entries of 2 bits: component + 1
+__host__ __device__ constexpr unsigned tz_pack(int a0, int a1, int a2, int a3, int a4, int a5, int a6, int a7, int a8 = 0, int a9 = 0, int a10 = 0,
+                                               int a11 = 0, int a12 = 0, int a13 = 0, int a14 = 0, int a15 = 0) {
+  return (unsigned)(a0 + 1) | (unsigned)(a1 + 1) << 2 | (unsigned)(a2 + 1) << 4 | (unsigned)(a3 + 1) << 6 | (unsigned)(a4 + 1) << 8 |
+         (unsigned)(a5 + 1) << 10 | (unsigned)(a6 + 1) << 12 | (unsigned)(a7 + 1) << 14 | (unsigned)(a8 + 1) << 16 | (unsigned)(a9 + 1) << 18 |
+         (unsigned)(a10 + 1) << 20 | (unsigned)(a11 + 1) << 22 | (unsigned)(a12 + 1) << 24 | (unsigned)(a13 + 1) << 26 | (unsigned)(a14 + 1) << 28 |
+         (unsigned)(a15 + 1) << 30;
+}
+__device__ __forceinline__ int tz_sign(unsigned table, int k) { return (int)((table >> (2 * k)) & 3u) - 1; }
+// the 4-point diamond (:553-571): top, left, right, bottom = point numbers 2, 4, 5, 7; also the first four of the 16-point one
+constexpr unsigned kTz4X = tz_pack(0, -1, 1, 0, 0, 0, 0, 0), kTz4Y = tz_pack(-1, 0, 0, 1, 0, 0, 0, 0);
+// the 8-point diamond (:574-634) in evaluation order: point numbers 2 1 3 4 5 6 8 7, the diagonal ones at iDist >> 1
+constexpr unsigned kTz8X = tz_pack(0, -1, 1, -1, 1, -1, 1, 0), kTz8Y = tz_pack(-1, -1, -1, 0, 0, 1, 1, 1);
+constexpr unsigned kTz8Nr = 2u | 1u << 4 | 3u << 8 | 4u << 12 | 5u << 16 | 6u << 20 | 8u << 24 | 7u << 28;
+// xTZ2PointSearch (:351-479): entry 2 * (ucPointNr - 1) + p = the p-th point of the case
+constexpr unsigned kTz2X = tz_pack(-1, 0, -1, 1, 0, 1, -1, -1, 1, 1, -1, 0, -1, 1, 1, 0);
+constexpr unsigned kTz2Y = tz_pack(0, -1, -1, -1, -1, 0, 1, -1, -1, 1, 0, 1, 1, 1, 0, 1);
+
+// One batch of xTZSearchHelp calls: the lanes [c * L, (c + 1) * L) hold candidate c = (cx, cy) of the batch, evaluated when
+// `valid`; candidates are in evaluation order.  L is a power of two, the same in all lanes.
+__device__ __forceinline__ void tz_eval(const TzUnit &U, TzState &S, int L, int cx, int cy, bool valid, int nr, int dist) {
+  const int lane = threadIdx.x, sub = lane & (L - 1);
+  unsigned acc = 0;
+  if (valid) {
+    const int segs = U.w >> 2, items = (U.h >> U.sub_shift) * segs;
+    const unsigned inv = 65536u / (unsigned)segs + 1u; // it / segs for it < 1024
+    const unsigned bias2 = (1u << U.B) * 0x00010001u;
+    const __attribute__((address_space(1))) short *base = U.ref + (ptrdiff_t)cy * U.stride + cx;
+    for (int it = sub; it < items; it += L) { // at most 64 rows x 16 segments
+      const int row = (int)(((unsigned)it * inv) >> 16), seg = it - row * segs, r = row << U.sub_shift;
+      const uintptr_t a = (uintptr_t)(base + (ptrdiff_t)r * U.stride + 4 * seg);
+      const unsigned sh = (a & 2) ? 16u : 0u;
+      const __attribute__((address_space(1))) unsigned *q = (const __attribute__((address_space(1))) unsigned *)(a & ~(uintptr_t)3);
+      const unsigned d0 = q[0], d1 = q[1], d2 = sh ? q[2] : 0u; // the third word holds a sample of the segment only at odd parity
+      const unsigned e0 = __builtin_amdgcn_alignbit(d1, d0, sh) + bias2, e1 = __builtin_amdgcn_alignbit(d2, d1, sh) + bias2;
+      const uint2 o = *reinterpret_cast<const uint2 *>(U.org + r * U.w + 4 * seg);
+      acc = __builtin_amdgcn_sad_u16(e0, o.x, acc);
+      acc = __builtin_amdgcn_sad_u16(e1, o.y, acc);
+    }
+  }
+  for (int m = 1; m < L; m <<= 1) acc += (unsigned)__shfl_xor((int)acc, m, 64);
+  const uint32_t cost = ((acc << U.sub_shift) >> (U.B - 8)) + me_mv_cost(U.lambda, cx, cy, U.pred_x, U.pred_y, 2);
+  const bool own = valid && sub == 0;
+  const unsigned long long mask = __ballot(own);
+  if (mask == 0) return; // uniform: nothing evaluated
+  if (U.trace && own) {
+    const uint32_t k = S.count + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
+    if (k < U.trace_cap) U.trace[2 * k] = ((uint32_t)cx & 0xffffu) | ((uint32_t)cy << 16), U.trace[2 * k + 1] = cost;
+  }
+  S.count += (uint32_t)__popcll(mask);
+  unsigned long long key = own ? ((unsigned long long)cost << 32) | (unsigned)lane : ~0ull;
+#pragma unroll
+  for (int m = 1; m < 64; m <<= 1) {
+    const unsigned long long other = __shfl_xor(key, m, 64);
+    key = other < key ? other : key;
+  }
+  const uint32_t wcost = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(key >> 32));
+  if (wcost < S.best) { // uniform.  wcost = 0xFFFFFFFF never passes, and the sentinel key carries that cost
+    const int wl = __builtin_amdgcn_readfirstlane((int)((uint32_t)key & 63u));
+    S.best = wcost;
+    S.bx = __builtin_amdgcn_readfirstlane(__shfl(cx, wl, 64));
+    S.by = __builtin_amdgcn_readfirstlane(__shfl(cy, wl, 64));
+    S.dist = __builtin_amdgcn_readfirstlane(__shfl(dist, wl, 64));
+    S.nr = __builtin_amdgcn_readfirstlane(__shfl(nr, wl, 64));
+    S.round = 0;
+  }
+}
+// the border rule: a coordinate that has moved by d is tested against the side it moved towards
+__device__ __forceinline__ bool tz_inside(const TzUnit &U, int x, int y, int dx, int dy) {
+  return (dx >= 0 || x >= U.left) && (dx <= 0 || x <= U.right) && (dy >= 0 || y >= U.top) && (dy <= 0 || y <= U.bottom);
+}
+// xTZ8PointDiamondSearch (:536-707) around (sx, sy)
+__device__ __forceinline__ void tz_diamond(const TzUnit &U, TzState &S, int sx, int sy, int d) {
+  const int lane = threadIdx.x;
+  S.round += 1;
+  int L, dx, dy, nr, dist = d;
+  if (d == 1) {
+    const int k = lane >> 4;
+    L = 16, dx = tz_sign(kTz4X, k), dy = tz_sign(kTz4Y, k), nr = (int)((0x7542u >> (4 * k)) & 15u);
+  } else if (d <= 8) {
+    const int k = lane >> 3;
+    const bool diag = ((0x66u >> k) & 1u) != 0;
+    dist = diag ? d >> 1 : d;
+    L = 8, dx = tz_sign(kTz8X, k) * dist, dy = tz_sign(kTz8Y, k) * dist, nr = (int)((kTz8Nr >> (4 * k)) & 15u);
+  } else {
+    const int k = lane >> 2;
+    L = 4, nr = 0;
+    if (k < 4) dx = tz_sign(kTz4X, k) * d, dy = tz_sign(kTz4Y, k) * d; // top, left, right, bottom
+    else { // index 1 .. 3 (:644-654): (XL, YT) (XR, YT) (XL, YB) (XR, YB)
+      const int i = ((k - 4) >> 2) + 1, j = (k - 4) & 3, q = (d >> 2) * i;
+      dx = (j & 1) ? q : -q, dy = (j & 2) ? d - q : q - d;
+    }
+  }
+  const int cx = sx + dx, cy = sy + dy;
+  tz_eval(U, S, L, cx, cy, tz_inside(U, cx, cy, dx, dy), nr, dist);
+}
+// xTZ2PointSearch (:351-479) around the best point; ucPointNr = 0 evaluates nothing (the reference asserts: it is unreachable,
+// because uiBestDistance == 1 is only ever set together with a point number of 1 .. 8)
+__device__ __forceinline__ void tz_two_point(const TzUnit &U, TzState &S) {
+  const int p = (int)threadIdx.x >> 5, e = S.nr > 0 ? 2 * (S.nr - 1) + p : 0;
+  const int dx = tz_sign(kTz2X, e), dy = tz_sign(kTz2Y, e), cx = S.bx + dx, cy = S.by + dy;
+  tz_eval(U, S, 32, cx, cy, S.nr > 0 && tz_inside(U, cx, cy, dx, dy), 0, 2);
+}
+
+constexpr int kTzThreads = 64, kTzRaster = 5, kTzPassCap = 1024;
+__global__ __launch_bounds__(kTzThreads) void k_tz_search(TzArgs A) {
+  extern __shared__ __attribute__((aligned(16))) unsigned short s_tz_org[];
+  const int i = blockIdx.x, lane = threadIdx.x;
+  const hmx_me_unit u = A.units[i];
+  const hmx_tz_unit z = A.tz[i];
+  typedef __attribute__((address_space(1))) const short gpel;
+  {
+    const int bias = 1 << A.B;
+    const gpel *src = (const gpel *)A.org.p[0] + (size_t)u.y * A.org.s[0] + u.x;
+    const int lw = u.w == 4 ? 2 : u.w == 8 ? 3 : u.w == 16 ? 4 : u.w == 32 ? 5 : u.w == 64 ? 6 : -1;
+    for (int k = lane; k < u.w * u.h; k += kTzThreads) { // at most 64 rounds
+      const int r = lw >= 0 ? k >> lw : k / u.w, c = k - r * u.w;
+      s_tz_org[k] = (unsigned short)(src[(size_t)r * A.org.s[0] + c] + bias);
+    }
+  }
+  __syncthreads();
+  TzUnit U;
+  const PlanesDev &R = A.refs[u.ref < 4 ? u.ref : 0];
+  U.stride = R.s[0];
+  U.ref = (gpel *)R.p[0] + (ptrdiff_t)u.y * R.s[0] + u.x;
+  U.org = s_tz_org;
+  U.w = u.w, U.h = u.h, U.sub_shift = u.sub_shift, U.B = A.B;
+  U.left = u.left, U.top = u.top, U.right = u.right, U.bottom = u.bottom, U.pred_x = u.pred_x, U.pred_y = u.pred_y;
+  U.lambda = A.lambda;
+  U.trace = A.trace ? (__attribute__((address_space(1))) uint32_t *)A.trace + 2 * (size_t)i * (size_t)A.trace_cap : nullptr;
+  U.trace_cap = (uint32_t)A.trace_cap;
+  TzState S{0xffffffffu, 0, 0, 0, 0, 0, 0u};
+  const int range = z.range;
+  // the start point, then the zero vector (:4321, :4338): neither is tested against the box
+  tz_eval(U, S, 32, lane < 32 ? z.start_x : 0, lane < 32 ? z.start_y : 0, true, 0, 0);
+  int sx = S.bx, sy = S.by;
+  for (int d = 1; d <= range; d *= 2) { // first search (:4347-4362)
+    tz_diamond(U, S, sx, sy, d);
+    if (S.round >= 3) break;
+  }
+  if (S.dist == 1) { // :4383-4387, no test of ucPointNr
+    S.dist = 0;
+    tz_two_point(U, S);
+  }
+  if (S.dist > kTzRaster) { // :4390-4400
+    S.dist = kTzRaster;
+    const int nx = (U.right - U.left) / kTzRaster + 1, ny = (U.bottom - U.top) / kTzRaster + 1, total = nx * ny; // at most 26 x 26
+    for (int c0 = 0; c0 < total; c0 += 16) {
+      const int c = c0 + (lane >> 2), ry = c / nx, rx = c - ry * nx;
+      tz_eval(U, S, 4, U.left + kTzRaster * rx, U.top + kTzRaster * ry, c < total, 0, kTzRaster);
+    }
+  }
+  int passes = 0;
+  bool capped = false;
+  while (S.dist > 0) { // star refinement (:4435-4469)
+    if (passes >= A.max_passes || passes >= kTzPassCap) {
+      capped = true;
+      break;
+    }
+    passes++;
+    sx = S.bx, sy = S.by;
+    S.dist = 0, S.nr = 0;
+    for (int d = 1; d <= range; d *= 2) tz_diamond(U, S, sx, sy, d);
+    if (S.dist == 1) {
+      S.dist = 0;
+      if (S.nr != 0) tz_two_point(U, S);
+    }
+  }
+  if (lane == 0) {
+    hmx_me_result r;
+    r.mvx = (int16_t)S.bx, r.mvy = (int16_t)S.by;
+    r.cost = capped ? 0xffffffffu : S.best;
+    r.sad = capped ? 0xffffffffu : S.best - me_mv_cost(A.lambda, S.bx, S.by, U.pred_x, U.pred_y, 2); // ruiSAD (:4473)
+    A.result[i] = r;
+    if (A.trace_count) A.trace_count[i] = S.count;
+  }
+}
+
+extern "C" int hmx_batch_tz_search(hmx_ctx *c, const hmx_me_unit *units, const hmx_tz_unit *tz, int n, const hmx_pic *refs, int n_refs,
+                                   const hmx_pic *org, int pic_w, int pic_h, int margin_x, int margin_y, uint32_t lambda, hmx_me_result *d_result,
+                                   hmx_tz_point *d_trace, uint32_t *d_trace_count, int trace_cap) {
+  if (!c || !units || !tz || !refs || !org || !d_result) return fail(c, HMX_ERR_ARG, "hmx_batch_tz_search: null argument");
+  if ((d_trace == nullptr) != (d_trace_count == nullptr)) return fail(c, HMX_ERR_ARG, "hmx_batch_tz_search: d_trace and d_trace_count go together");
+  if (d_trace && trace_cap < 1) return fail(c, HMX_ERR_ARG, "hmx_batch_tz_search: trace_cap must be at least 1");
+  if (n <= 0) return fail(c, HMX_ERR_ARG, "hmx_batch_tz_search: n must be at least 1");
+  if (n_refs <= 0 || n_refs > 4) return fail(c, HMX_ERR_ARG, "hmx_batch_tz_search: n_refs must be 1 .. 4");
+  if (pic_w <= 0 || pic_h <= 0 || margin_x < 0 || margin_y < 0)
+    return fail(c, HMX_ERR_ARG, "hmx_batch_tz_search: picture size must be positive and margins not negative");
+  if (!org->plane[0]) return fail(c, HMX_ERR_ARG, "hmx_batch_tz_search: the original has no luma plane");
+  for (int r = 0; r < n_refs; r++)
+    if (!refs[r].plane[0]) return fail(c, HMX_ERR_ARG, "hmx_batch_tz_search: a reference has no luma plane");
+  size_t lds = 0;
+  for (int i = 0; i < n; i++) {
+    const hmx_me_unit &u = units[i];
+    const hmx_tz_unit &z = tz[i];
+    const std::string at = "hmx_batch_tz_search: unit " + std::to_string(i) + ": ";
+    if (!me_size_ok(u.w) || !me_size_ok(u.h)) return fail(c, HMX_ERR_ARG, at + "width and height come from {4, 8, 12, 16, 24, 32, 48, 64}");
+    if (u.ref >= n_refs) return fail(c, HMX_ERR_ARG, at + "reference index outside refs[]");
+    if (u.sub_shift > 1 || (u.sub_shift && u.h <= 8)) return fail(c, HMX_ERR_ARG, at + "sub_shift is 0, or 1 with more than 8 rows");
+    if (u.right < u.left || u.bottom < u.top) return fail(c, HMX_ERR_ARG, at + "empty search box");
+    if (u.right - u.left + 1 > 129 || u.bottom - u.top + 1 > 129) return fail(c, HMX_ERR_ARG, at + "search box side above 129 (search range 64)");
+    if (u.x + u.w > pic_w || u.y + u.h > pic_h) return fail(c, HMX_ERR_ARG, at + "the unit lies outside the picture");
+    if (z.range < 1 || z.range > 64) return fail(c, HMX_ERR_ARG, at + "range must be 1 .. 64");
+    if (z.reserved != 0) return fail(c, HMX_ERR_ARG, at + "reserved must be 0");
+    if (z.start_x < u.left || z.start_x > u.right || z.start_y < u.top || z.start_y > u.bottom)
+      return fail(c, HMX_ERR_ARG, at + "the start point lies outside the search box");
+    // every evaluated point lies in the bounding rectangle of box U {(0, 0)}: the zero vector is evaluated unconditionally
+    const int rl = std::min<int>(u.left, 0), rr = std::max<int>(u.right, 0), rt = std::min<int>(u.top, 0), rb = std::max<int>(u.bottom, 0);
+    if (u.x + rl < -margin_x || u.x + rr + u.w > pic_w + margin_x || u.y + rt < -margin_y || u.y + rb + u.h > pic_h + margin_y)
+      return fail(c, HMX_ERR_ARG, at + "a block of the box or the zero vector's rectangle reaches outside the reference's margins");
+    lds = std::max(lds, sizeof(short) * (size_t)u.w * (size_t)u.h);
+  }
+  TzArgs A{};
+  A.units = static_cast<const hmx_me_unit *>(arena_push(c, units, sizeof(hmx_me_unit) * (size_t)n)); // the caller's host arrays
+  A.tz = static_cast<const hmx_tz_unit *>(arena_push(c, tz, sizeof(hmx_tz_unit) * (size_t)n));
+  if (!A.units || !A.tz) return fail(c, HMX_ERR_NOMEM, "argument arena (unit list too long: split the call)");
+  for (int r = 0; r < n_refs; r++) A.refs[r] = to_dev(&refs[r]);
+  A.org = to_dev(org);
+  A.B = c->cfg.bit_depth;
+  A.max_passes = std::min(kTzPassCap, std::max(1, c->knob.tz_max_passes));
+  A.lambda = lambda;
+  A.result = d_result;
+  A.trace = d_trace;
+  A.trace_count = d_trace_count;
+  A.trace_cap = d_trace ? trace_cap : 0;
+  hipLaunchKernelGGL(k_tz_search, dim3((unsigned)n), dim3(kTzThreads), lds, c->stream, A);
+  HIPCHK(c, hipGetLastError());
+  return HMX_OK;
+}

@@ -143,15 +143,18 @@ static int me_main(int argc, char **argv) {
 // range centred on a start vector), on a reference that is the original displaced by a fractional vector plus noise.
 // Prints "x y w h sub_shift predHor predVer multiplier W H M useHADME range bitsIn startHor startVer", the original plane, the
 // reference plane with its margins, and per run "mvHor mvVer bits cost", one line each.
+// hm_mirror_test tz <bitDepth> <seed>: the same with m_iFastSearch = 1, margin 40, search range 16 and a predictor up to ten
+// samples off: the uni-predicted run takes xTZSearch from the predictor, the bi-prediction refinement still the full search.
 static int frac_main(int argc, char **argv) {
   if (argc < 4) return 2;
-  const int B = atoi(argv[2]), W = 64, H = 64, M = 24, S = W + 2 * M, RANGE = 5;
+  const bool tz = std::string(argv[1]) == "tz";
+  const int B = atoi(argv[2]), W = 64, H = 64, M = tz ? 40 : 24, S = W + 2 * M, RANGE = tz ? 16 : 5;
   unsigned seed = (unsigned)atoi(argv[3]);
   const bool fastEnc = (seed & 1) != 0, hadME = (seed & 2) == 0;
   auto next = [&]() { return (seed = seed * 1664525u + 1013904223u) >> 8; };
   hmx_hm::Context ctx(B);
   hmx_hm::TComRdCost rd(ctx);
-  hmx_hm::TEncSearch search(ctx, rd, {W, H, M, M, 64}, fastEnc, hadME);
+  hmx_hm::TEncSearch search(ctx, rd, {W, H, M, M, 64}, fastEnc, hadME, tz ? 1 : 0);
   std::vector<short> org(W * H), ref(S * (H + 2 * M));
   const int maxv = (1 << B) - 1;
   for (int r = 0; r < H + 2 * M; r++) // a smooth surface plus noise: the costs have a real minimum between samples
@@ -174,7 +177,8 @@ static int frac_main(int argc, char **argv) {
   po.plane[0] = d_org, po.stride[0] = W;
   pr.plane[0] = d_ref + M * S + M, pr.stride[0] = S;
   const int x = 24, y = 16, w = fastEnc ? 8 : 16, h = fastEnc ? 16 : 8;
-  const int pred[2] = {(int)(next() % 25) - 12, (int)(next() % 25) - 12}, start[2] = {4 * sx + (int)(next() % 9) - 4, 4 * sy + (int)(next() % 9) - 4};
+  const int ps = tz ? 40 : 12; // the predictor's reach, quarter samples
+  const int pred[2] = {(int)(next() % (2 * ps + 1)) - ps, (int)(next() % (2 * ps + 1)) - ps}, start[2] = {4 * sx + (int)(next() % 9) - 4, 4 * sy + (int)(next() % 9) - 4};
   const unsigned bitsIn = next() % 7;
   rd.setLambda(20.0 + next() % 40);
   rd.getMotionCost(true, 0);
@@ -196,7 +200,7 @@ static int frac_main(int argc, char **argv) {
 }
 
 int main(int argc, char **argv) {
-  if (argc >= 2 && std::string(argv[1]) == "frac") {
+  if (argc >= 2 && (std::string(argv[1]) == "frac" || std::string(argv[1]) == "tz")) {
     try {
       return frac_main(argc, argv);
     } catch (const std::exception &e) {

@@ -328,8 +328,9 @@ private:
   Int m_iPredHor = 0, m_iPredVer = 0, m_iCostScale = 0;
 };
 
-// TEncSearch, xMotionEstimation (TEncSearch.cpp:4120-4283, :4476-4514) for ONE unit: the integer stage over
-// hmx_batch_fullpel_search, the fractional stage over hmx_batch_subpel_search.
+// TEncSearch, xMotionEstimation (TEncSearch.cpp:4120-4514) for ONE unit: the integer stage over hmx_batch_fullpel_search
+// (xPatternSearch) or hmx_batch_tz_search (xPatternSearchFast -> xTZSearch, m_iFastSearch = 1), the fractional stage over
+// hmx_batch_subpel_search.
 // What the reference reads through pcCU, the pattern key and the slice is explicit: the unit's position and size, the
 // pictures (DEVICE pictures: the original, and the reference with its margins) and their geometry.
 class TEncSearch {
@@ -337,8 +338,8 @@ public:
   struct Geometry {
     Int picWidth, picHeight, marginX, marginY, ctuSize;
   };
-  TEncSearch(Context &c, TComRdCost &rd, const Geometry &g, Bool useFastEnc = false, Bool useHADME = true)
-      : m_c(c), m_rd(rd), m_g(g), m_fastEnc(useFastEnc), m_useHADME(useHADME) {
+  TEncSearch(Context &c, TComRdCost &rd, const Geometry &g, Bool useFastEnc = false, Bool useHADME = true, Int iFastSearch = 0)
+      : m_c(c), m_rd(rd), m_g(g), m_fastEnc(useFastEnc), m_useHADME(useHADME), m_iFastSearch(iFastSearch) {
     m_c.check(hmx_malloc(m_c.get(), sizeof(hmx_me_result), (void **)&m_dResult), "TEncSearch");
     m_c.check(hmx_malloc(m_c.get(), sizeof(hmx_subpel_result) + 18 * sizeof(uint32_t), (void **)&m_dFrac), "TEncSearch");
   }
@@ -369,6 +370,31 @@ public:
               "xPatternSearch");
     hmx_me_result r;
     m_c.check(hmx_download(m_c.get(), &r, m_dResult, sizeof(r)), "xPatternSearch");
+    rcMv[0] = r.mvx, rcMv[1] = r.mvy;
+    ruiSAD = r.sad;
+  }
+  // xTZSearch (:4302-4474) through xPatternSearchFast (:4285-4300), whose three neighbour predictors feed only
+  // bTestOtherPredictedMV, which is compiled off.  rcMv: in the start vector in quarter samples (xMotionEstimation passes
+  // *pcMvPred, :4182), which is clipped for the CU at (x, y) and >>= 2 as the reference does (:4312-4313); out the integer
+  // vector.  iSearchRange: m_iSearchRange (m_aaiAdaptSR of the reference picture).  The vector cost is m_pcRdCost's, as for
+  // xPatternSearch.
+  void xTZSearch(const hmx_pic *pcOrg, const hmx_pic *pcRef, Int x, Int y, Int iRoiWidth, Int iRoiHeight, const Int pcMvSrchRngLT[2],
+                 const Int pcMvSrchRngRB[2], Int iSearchRange, Int rcMv[2], UInt &ruiSAD) {
+    hmx_me_unit u{};
+    u.x = (uint16_t)x, u.y = (uint16_t)y, u.w = (uint8_t)iRoiWidth, u.h = (uint8_t)iRoiHeight;
+    u.ref = 0;
+    u.sub_shift = (m_fastEnc && iRoiHeight > 8) ? 1 : 0; // :323-330
+    u.pred_x = (int16_t)m_rd.predictorHor(), u.pred_y = (int16_t)m_rd.predictorVer();
+    u.left = (int16_t)pcMvSrchRngLT[0], u.top = (int16_t)pcMvSrchRngLT[1], u.right = (int16_t)pcMvSrchRngRB[0], u.bottom = (int16_t)pcMvSrchRngRB[1];
+    int sx = rcMv[0], sy = rcMv[1];
+    hmx_clipMv(&sx, &sy, x, y, m_g.picWidth, m_g.picHeight, m_g.ctuSize);
+    hmx_tz_unit z{};
+    z.start_x = (int16_t)(sx >> 2), z.start_y = (int16_t)(sy >> 2), z.range = (uint16_t)iSearchRange;
+    m_c.check(hmx_batch_tz_search(m_c.get(), &u, &z, 1, pcRef, 1, pcOrg, m_g.picWidth, m_g.picHeight, m_g.marginX, m_g.marginY,
+                                  m_rd.motionCostMultiplier(), m_dResult, nullptr, nullptr, 0),
+              "xTZSearch");
+    hmx_me_result r;
+    m_c.check(hmx_download(m_c.get(), &r, m_dResult, sizeof(r)), "xTZSearch");
     rcMv[0] = r.mvx, rcMv[1] = r.mvy;
     ruiSAD = r.sad;
   }
@@ -408,7 +434,8 @@ public:
   // stage, the fractional stage, then :4197-4205 on the host.  pcMvPred: the predictor, quarter samples.  rcMv: in (bBi only) the
   // vector the range is centred on, out the refined vector, both in quarter samples.  ruiBits: in the bits before the vector,
   // out with the vector's bits added.  bBi: the caller passes 2 * org - other prediction as pcOrg (removeHighFreq, :4147) and
-  // the cost takes fWeight = 0.5 (:4148).  The full search serves both cases (m_iFastSearch = 0).
+  // the cost takes fWeight = 0.5 (:4148).  The integer stage is the full search when !m_iFastSearch || bBi, otherwise xTZSearch
+  // from rcMv = *pcMvPred with the range iSrchRng (:4176-4184).
   void xMotionEstimation(const hmx_pic *pcOrg, const hmx_pic *pcRef, Int x, Int y, Int iRoiWidth, Int iRoiHeight, const Int pcMvPred[2], Int iSrchRng,
                          Bool bBi, Int rcMv[2], UInt &ruiBits, UInt &ruiCost) {
     const Double fWeight = bBi ? 0.5 : 1.0;
@@ -418,7 +445,11 @@ public:
     m_rd.getMotionCost(true, 0);
     m_rd.setPredictor(pcMvPred[0], pcMvPred[1]);
     m_rd.setCostScale(2);
-    xPatternSearch(pcOrg, pcRef, x, y, iRoiWidth, iRoiHeight, lt, rb, mvInt, ruiCost);
+    if (!m_iFastSearch || bBi) xPatternSearch(pcOrg, pcRef, x, y, iRoiWidth, iRoiHeight, lt, rb, mvInt, ruiCost);
+    else {
+      mvInt[0] = pcMvPred[0], mvInt[1] = pcMvPred[1];
+      xTZSearch(pcOrg, pcRef, x, y, iRoiWidth, iRoiHeight, lt, rb, iSrchRng, mvInt, ruiCost);
+    }
     m_rd.getMotionCost(true, 0);
     m_rd.setCostScale(1);
     xPatternSearchFracDIF(pcOrg, pcRef, x, y, iRoiWidth, iRoiHeight, mvInt, mvHalf, mvQter, ruiCost);
@@ -434,6 +465,7 @@ private:
   TComRdCost &m_rd;
   Geometry m_g;
   Bool m_fastEnc, m_useHADME;
+  Int m_iFastSearch; // 1: xTZSearch for uni-predictive units
   hmx_me_result *m_dResult = nullptr;
   hmx_subpel_result *m_dFrac = nullptr; // the result, then the 18 stage costs
 };
