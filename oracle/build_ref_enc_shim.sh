@@ -40,4 +40,10 @@ mkdir -p "$OUT/obj_tap_enc"
 python3 "$HERE/ref_shim_edit.py" TComTrQuant rdoqtap | $CXX $FLAGS -include "$HERE/ref_rdoq_tap.h" -x c++ -c - -o "$OUT/obj_tap_enc/TComTrQuant.o"
 $CXX -o "$OUT/TAppEncoder_rdoqtap" "$OUT"/obj_apps/enc_*.o "$OUT"/obj_apps/TLibEncoder_*.o "$OUT"/obj_apps/TAppCommon_*.o "$OUT/obj_tap_enc/TComTrQuant.o" \
   $(ls "$OUT"/obj/*.o | grep -v -e ref_tap.o -e /TComTrQuant.o)
-echo "build_ref_enc_shim: wrote $OUT/TAppEncoder_hmx and $OUT/TAppEncoder_rdoqtap"
+# The reference encoder with a RECORDER inside its own motion search (oracle/ref_me_tap.h; no libhmx in this binary either): what
+# xMotionEstimation was given, every xTZSearchHelp evaluation, every xPatternRefinement cost and what came back, call by call
+# -> tests/golden/make_me_enc_tap.py -> tests/golden/me_enc_tap.npz
+python3 "$HERE/ref_shim_edit.py" TEncSearch metap | $CXX $FLAGS -I"$SRC/Lib/TLibEncoder" -include "$HERE/ref_me_tap.h" -x c++ -c - -o "$OUT/obj_tap_enc/TEncSearch.o"
+$CXX -o "$OUT/TAppEncoder_metap" "$OUT"/obj_apps/enc_*.o $(ls "$OUT"/obj_apps/TLibEncoder_*.o | grep -v -e /TLibEncoder_TEncSearch.o) "$OUT"/obj_apps/TAppCommon_*.o \
+  "$OUT/obj_tap_enc/TEncSearch.o" $(ls "$OUT"/obj/*.o | grep -v -e ref_tap.o)
+echo "build_ref_enc_shim: wrote $OUT/TAppEncoder_hmx, $OUT/TAppEncoder_rdoqtap and $OUT/TAppEncoder_metap"

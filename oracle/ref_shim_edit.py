@@ -4,12 +4,14 @@
 untouched) and writes the result to stdout for `g++ -x c++ -` (oracle/build_ref_shim.sh): nothing of the reference is
 stored in the repository, and no header, library or generated file of it is substituted.
 UNIT = TComTrQuant | TComPrediction | TComInterpolationFilter | TComYuv | TComRdCost (encoder shim only); a second argument
-`enc` adds the bodies of the members only the encoder calls (ENC_BODIES)."""
+`enc` adds the bodies of the members only the encoder calls (ENC_BODIES).  `TComTrQuant rdoqtap` and `TEncSearch metap` leave
+every body as it is and add recorder statements (TAP_PREFIX, ME_TAP)."""
 import os
 import re
 import sys
 
-SRC = os.path.join(os.environ.get("REF_ROOT", "/root/reference"), "source", "Lib", "TLibCommon")
+LIB = os.path.join(os.environ.get("REF_ROOT", "/root/reference"), "source", "Lib")
+SRC = os.path.join(LIB, "TLibCommon")
 
 BODIES = {
     "TComTrQuant": {
@@ -141,6 +143,75 @@ TAP_PREFIX = {
 }
 
 
+# `ref_shim_edit.py TEncSearch metap`: the UNMODIFIED motion search with recorder statements (oracle/ref_me_tap.h) BETWEEN the
+# reference's own statements: (member, a pattern that names one statement of it or None for the end of the body, what is put
+# after that statement).  Every statement of the reference stays and runs; the recorder only reads.  The cost multiplier
+# m_uiLambdaMotionSAD is private to TComRdCost: at the end of xMotionEstimation m_uiCost still holds it (getMotionCost(1, 0),
+# :4186), and getCost(UInt b) = (m_uiCost * b) >> 16 gives its high half at b = 1 and its low half at b = 65536.
+# tests/golden/make_me_enc_tap.py turns runs of the reference encoder built this way into tests/golden/me_enc_tap.npz.
+_T = "g_hmx_me_tap"
+ME_TAP = [
+    ("TEncSearch::xMotionEstimation", r"setWpScalingDistParam\s*\(", """{
+    TComPic *hmxPic = pcCU->getSlice()->getRefPic( eRefPicList, iRefIdxPred );
+    TComPicYuv *hmxRec = hmxPic->getPicYuvRec();
+    const int hmxOff = (int)(piRefY - hmxRec->getLumaAddr()), hmxMx = hmxRec->getLumaMargin();
+    %(T)s.picture(hmxPic->getPOC(), hmxRec->getBufY(), hmxRec->getWidth(), hmxRec->getHeight(), hmxMx,
+                  (int)(hmxRec->getLumaAddr() - hmxRec->getBufY() - hmxMx) / iRefStride);
+    %(T)s.begin(pcYuv->getLumaAddr( uiPartAddr ), pcYuv->getStride(), iRoiWidth, iRoiHeight);
+    const int hmxV[] = {H_POC, pcCU->getSlice()->getPOC(), H_LIST, (int)eRefPicList, H_REF_IDX, iRefIdxPred, H_REF_POC, hmxPic->getPOC(),
+                        H_CU_X, (int)pcCU->getCUPelX(), H_CU_Y, (int)pcCU->getCUPelY(), H_X, hmxOff %% iRefStride, H_Y, hmxOff / iRefStride,
+                        H_BI, bBi, H_FAST_SEARCH, m_iFastSearch, H_FEN, m_pcEncCfg->getUseFastEnc(), H_HAD_ME, m_pcEncCfg->getUseHADME(),
+                        H_PRED_X, pcMvPred->getHor(), H_PRED_Y, pcMvPred->getVer(), H_MV_IN_X, rcMv.getHor(), H_MV_IN_Y, rcMv.getVer(),
+                        H_RANGE, iSrchRng, H_ADAPT_RANGE, m_iSearchRange, H_BITS_IN, (int)ruiBits,
+                        H_LEFT, cMvSrchRngLT.getHor(), H_TOP, cMvSrchRngLT.getVer(), H_RIGHT, cMvSrchRngRB.getHor(), H_BOTTOM, cMvSrchRngRB.getVer(),
+                        H_BITS, (int)(g_uiBitDepth + g_uiBitIncrement), H_PIC_W, hmxRec->getWidth(), H_PIC_H, hmxRec->getHeight(), H_CTU, (int)g_uiMaxCUWidth};
+    for (unsigned k = 0; k < sizeof(hmxV) / sizeof(int); k += 2) %(T)s.set(hmxV[k], hmxV[k + 1]);
+  }"""),
+    ("TEncSearch::xMotionEstimation", r"setCostScale\s*\(\s*1\s*\)",
+     "%(T)s.set(H_INT_X, rcMv.getHor()), %(T)s.set(H_INT_Y, rcMv.getVer()), %(T)s.set(H_INT_SAD, (int)ruiCost);"),
+    ("TEncSearch::xMotionEstimation", r"setCostScale\s*\(\s*0\s*\)",
+     """%(T)s.set(H_HALF_X, cMvHalf.getHor()), %(T)s.set(H_HALF_Y, cMvHalf.getVer()), %(T)s.set(H_QTER_X, cMvQter.getHor()),
+  %(T)s.set(H_QTER_Y, cMvQter.getVer()), %(T)s.set(H_FRAC_COST, (int)ruiCost);"""),
+    ("TEncSearch::xMotionEstimation", None,
+     """%(T)s.set(H_MV_OUT_X, rcMv.getHor()), %(T)s.set(H_MV_OUT_Y, rcMv.getVer()), %(T)s.set(H_BITS_OUT, (int)ruiBits), %(T)s.set(H_COST_OUT, (int)ruiCost);
+  %(T)s.set(H_LAMBDA, (int)((m_pcRdCost->getCost( 1u ) << 16) | m_pcRdCost->getCost( 65536u )));
+  %(T)s.end();"""),
+    ("TEncSearch::xTZSearchHelp", r"uiSad\s*\+=", "%(T)s.tz_point(iSearchX, iSearchY, uiSad);"),
+    ("TEncSearch::xPatternRefinement", r"uiDist\s*\+=", "%(T)s.frac_cost(uiDist);"),
+]
+
+
+def body_span(text, name):
+    """(index of the opening brace, index of the closing brace) of the member's definition."""
+    m = re.search(r"^[\w \t]*\b" + re.escape(name) + r"\s*\(", text, re.M)
+    if not m:
+        raise SystemExit(f"ref_shim_edit: {name} not found")
+    i = text.index("{", m.end())
+    depth, j = 0, i
+    while True:
+        c = text[j]
+        if c == "{":
+            depth += 1
+        elif c == "}":
+            depth -= 1
+            if depth == 0:
+                return i, j
+        j += 1
+
+
+def insert_after(text, name, pattern, code):
+    """Put `code` after the statement of member `name` that `pattern` names (exactly one must), or at the end of its body."""
+    i, j = body_span(text, name)
+    if pattern is None:
+        at = j
+    else:
+        hits = list(re.finditer(pattern, text[i:j]))
+        if len(hits) != 1:
+            raise SystemExit(f"ref_shim_edit: {len(hits)} statements of {name} match {pattern}")
+        at = text.index(";", i + hits[0].end()) + 1
+    return text[:at] + "\n  " + code + "\n" + text[at:]
+
+
 def prefix_body(text, name, code):
     m = re.search(r"^(?:Void|UInt)\s+" + re.escape(name) + r"\s*\(", text, re.M)
     if not m:
@@ -169,6 +240,12 @@ def replace_body(text, name, body):
 
 def main():
     unit = sys.argv[1]
+    if sys.argv[1:] == ["TEncSearch", "metap"]:
+        text = open(os.path.join(LIB, "TLibEncoder", "TEncSearch.cpp")).read()
+        for name, pattern, code in ME_TAP:
+            text = insert_after(text, name, pattern, code % {"T": _T})
+        sys.stdout.write(text)
+        return
     text = open(os.path.join(SRC, unit + ".cpp")).read()
     if unit == "TComTrQuant":  # the two pre-standard for-scope uses g++ rejects (oracle/build_ref.sh makes the same edit in its stream)
         text = text.replace("for (Int iCGScanPos = uiCGNum-1;", "Int iCGScanPos; for (iCGScanPos = uiCGNum-1;")

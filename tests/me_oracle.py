@@ -7,10 +7,12 @@ hmx_mvCost, hmx_setSearchRange and hmx_batch_fullpel_search:
   set_search_range TEncSearch::xSetSearchRange (TEncSearch.cpp:4209-4225) over clip_mv (TComDataCU.cpp:3505-3517)
   search          TEncSearch::xPatternSearch (:4227-4283), vectorised over the box; search_loop is the loop-for-loop form
 
-Everything is UInt arithmetic modulo 2^32.  This oracle cannot be pinned on the compiled reference: oracle/_ref has no tap
-of TEncSearch or of xGetSAD*, and oracle/ stays as it is.  It is held instead by the second, literal restatement
-(tests/test_me_oracle.py) and, on the GPU, by the cross-check of the cost map against hmx_batch_subpel_cost, which is pinned
-(tests/test_gpu_me.py)."""
+Everything is UInt arithmetic modulo 2^32.  The oracle is pinned on the compiled reference by recorded calls:
+oracle/_ref/TAppEncoder_metap is the reference encoder with a recorder inside its own TEncSearch (oracle/ref_me_tap.h), and
+tests/test_me_enc_tap.py requires of sad, mv_cost, set_search_range and search what its xMotionEstimation did in the calls of
+tests/golden/me_enc_tap.npz: the box, the vector term of the costs, the winning vector and ruiSAD.  The second, literal
+restatement (tests/test_me_oracle.py) and, on the GPU, the cross-check of the cost map against hmx_batch_subpel_cost
+(tests/test_gpu_me.py) cover the sizes and edges the encoder's calls do not reach."""
 import numpy as np
 
 M32 = 0xFFFFFFFF

@@ -10,6 +10,9 @@
   refine_loop  the same candidate by candidate: uiDistBest = MAX_UINT, strict <, the halving loop of the bits
   me_tail      the tail of xMotionEstimation (:4197-4205)
 
+tests/test_me_enc_tap.py pins stage_costs, refine and me_tail on the reference encoder's own calls (tests/golden/me_enc_tap.npz:
+all eighteen uiDist of the two xPatternRefinement calls, rcMvHalf, rcMvQter, ruiBits and ruiCost).
+
 Everything is UInt arithmetic modulo 2^32.  Positions: `ref` is a luma plane WITH its margins, (X, Y) the position in it of
 the block displaced by the integer vector."""
 import ctypes as C

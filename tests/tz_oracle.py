@@ -10,9 +10,12 @@ from the reference, and compares the two traces.
   walk(cost, box, start, range_)   over any cost function cost(x, y) -> UInt
   search(org, ref, margin, u, z, lam, B)   cost = me_oracle.sad + me_oracle.mv_cost at cost scale 2 (xTZSearchHelp, :312-349)
 
-Like tests/me_oracle.py this cannot be pinned on the compiled reference (oracle/_ref has no tap of TEncSearch).  On the GPU every
-trace entry inside the box is held against hmx_batch_fullpel_search's cost map, which is cross-checked against the pinned
-hmx_batch_subpel_cost (tests/test_gpu_tz_search.py).
+Like tests/me_oracle.py this is pinned on the compiled reference by recorded calls: tests/test_me_enc_tap.py requires `search`
+to give, entry for entry, every xTZSearchHelp evaluation (point and cost) that the reference encoder's own xTZSearch made in the
+TZ calls of tests/golden/me_enc_tap.npz (oracle/ref_me_tap.h records them) -- walks that adopt the zero vector, run the raster
+search, two and more star passes and the 2-point search among them -- and its result.  On the GPU every trace entry inside the
+box is also held against hmx_batch_fullpel_search's cost map, which is cross-checked against the pinned hmx_batch_subpel_cost
+(tests/test_gpu_tz_search.py).
 
 The zero vector is evaluated unconditionally and may lie outside the box; the border rule tests only the moving coordinate,
 so a walk that adopts it evaluates points outside the box.  Every evaluated point lies inside the bounding rectangle of

@@ -959,7 +959,8 @@ def clip_mv(mvx, mvy, cu_x, cu_y, pic_w, pic_h, ctu_size=64):
 
 def tz_units(units, range_, pic_w, pic_h, ctu_size=64):
     """The hmx_tz_unit array of a unit list as xTZSearch makes its start points (:4312-4313): the predictor clipped with
-    hmx_clipMv (the unit's origin as CU origin, as set_search_range is used) and >> 2; range_ for every unit."""
+    hmx_clipMv (the unit's origin as CU origin: right for a CU's first partition; for a second partition clip with the CU's
+    origin, as the reference's pcCU->clipMv does) and >> 2; range_ for every unit."""
     units = np.ascontiguousarray(units, ME_UNIT_DTYPE)
     tz = np.zeros(len(units), TZ_UNIT_DTYPE)
     for i, u in enumerate(units):

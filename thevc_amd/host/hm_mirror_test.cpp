@@ -2,6 +2,7 @@
 // does (ENC/TEncSearch.cpp:1006-1165): setQPforQuant, transformNxN, invtransformNxN on one block, and
 // prints the results as text so that tests/test_host_mirror.py can compare them with the oracle.
 // Usage: hm_mirror_test <bitDepth> <N> <qp> <mode> <seed>
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -199,7 +200,67 @@ static int frac_main(int argc, char **argv) {
   return 0;
 }
 
+// Usage: hm_mirror_test calls <file>: xMotionEstimation for calls somebody else recorded (tests/test_me_enc_tap.py writes the
+// file from calls of the reference encoder's own xMotionEstimation).  The file is int32 words {bit depth, picture width,
+// height, margin x, margin y, CTU size, FEN, HadamardME, m_iFastSearch, m_uiLambdaMotionSAD, number of calls}, the reference's
+// luma plane with its margins as int16, then per call 13 words {CU x, CU y, unit x, y, width, height, bBi, predictor hor, ver,
+// rcMv hor, ver as it comes in, search range, ruiBits as it comes in} and the unit's original block as int16 (for bBi it is
+// 2 * org - other).  Prints "mvHor mvVer bits cost" per call.
+static int calls_main(int argc, char **argv) {
+  if (argc < 3) return 2;
+  FILE *f = fopen(argv[2], "rb");
+  if (!f) return 2;
+  int hd[11];
+  if (fread(hd, sizeof(int), 11, f) != 11) return 2;
+  const int B = hd[0], W = hd[1], H = hd[2], MX = hd[3], MY = hd[4], S = W + 2 * MX;
+  std::vector<short> ref((size_t)S * (H + 2 * MY)), org((size_t)W * H);
+  if (fread(ref.data(), sizeof(short), ref.size(), f) != ref.size()) return 2;
+  hmx_hm::Context ctx(B);
+  hmx_hm::TComRdCost rd(ctx);
+  hmx_hm::TEncSearch search(ctx, rd, {W, H, MX, MY, hd[5]}, hd[6] != 0, hd[7] != 0, hd[8]);
+  const double root = ((double)(unsigned)hd[9] + 0.5) / 65536.0; // setLambda floors 65536 * sqrt(lambda): aim at the middle of the step
+  rd.setLambda(root * root);
+  rd.getMotionCost(true, 0);
+  if (rd.motionCostMultiplier() != (unsigned)hd[9]) return 3;
+  short *d_org = nullptr, *d_ref = nullptr;
+  ctx.check(hmx_malloc(ctx.get(), org.size() * 2, (void **)&d_org), "malloc");
+  ctx.check(hmx_malloc(ctx.get(), ref.size() * 2, (void **)&d_ref), "malloc");
+  ctx.check(hmx_upload(ctx.get(), d_ref, ref.data(), ref.size() * 2), "upload");
+  hmx_pic po{}, pr{};
+  po.plane[0] = d_org, po.stride[0] = W;
+  pr.plane[0] = d_ref + MY * S + MX, pr.stride[0] = S;
+  for (int k = 0; k < hd[10]; k++) {
+    int c[13];
+    if (fread(c, sizeof(int), 13, f) != 13) return 2;
+    const int x = c[2], y = c[3], w = c[4], h = c[5];
+    if (x < 0 || y < 0 || w <= 0 || h <= 0 || x + w > W || y + h > H) return 2;
+    std::vector<short> blk((size_t)w * h);
+    if (fread(blk.data(), sizeof(short), blk.size(), f) != blk.size()) return 2;
+    std::fill(org.begin(), org.end(), (short)0);
+    for (int r = 0; r < h; r++)
+      for (int n = 0; n < w; n++) org[(size_t)(y + r) * W + x + n] = blk[(size_t)r * w + n];
+    ctx.check(hmx_upload(ctx.get(), d_org, org.data(), org.size() * 2), "upload");
+    const int pred[2] = {c[7], c[8]};
+    int mv[2] = {c[9], c[10]};
+    hmx_hm::UInt bits = (hmx_hm::UInt)c[12], cost = 0;
+    search.xMotionEstimation(&po, &pr, c[0], c[1], x, y, w, h, pred, c[11], c[6] != 0, mv, bits, cost);
+    printf("%d %d %u %u\n", mv[0], mv[1], bits, cost);
+  }
+  fclose(f);
+  hmx_free(ctx.get(), d_org);
+  hmx_free(ctx.get(), d_ref);
+  return 0;
+}
+
 int main(int argc, char **argv) {
+  if (argc >= 2 && std::string(argv[1]) == "calls") {
+    try {
+      return calls_main(argc, argv);
+    } catch (const std::exception &e) {
+      fprintf(stderr, "error: %s\n", e.what());
+      return 1;
+    }
+  }
   if (argc >= 2 && (std::string(argv[1]) == "frac" || std::string(argv[1]) == "tz")) {
     try {
       return frac_main(argc, argv);

@@ -377,8 +377,13 @@ public:
   // bTestOtherPredictedMV, which is compiled off.  rcMv: in the start vector in quarter samples (xMotionEstimation passes
   // *pcMvPred, :4182), which is clipped for the CU at (x, y) and >>= 2 as the reference does (:4312-4313); out the integer
   // vector.  iSearchRange: m_iSearchRange (m_aaiAdaptSR of the reference picture).  The vector cost is m_pcRdCost's, as for
-  // xPatternSearch.
+  // xPatternSearch.  (cuX, cuY): the origin of the unit's CODING UNIT (getCUPelX / Y), which is what clipMv reads; it is the
+  // unit's own position only for a first partition.
   void xTZSearch(const hmx_pic *pcOrg, const hmx_pic *pcRef, Int x, Int y, Int iRoiWidth, Int iRoiHeight, const Int pcMvSrchRngLT[2],
+                 const Int pcMvSrchRngRB[2], Int iSearchRange, Int rcMv[2], UInt &ruiSAD) {
+    xTZSearch(pcOrg, pcRef, x, y, x, y, iRoiWidth, iRoiHeight, pcMvSrchRngLT, pcMvSrchRngRB, iSearchRange, rcMv, ruiSAD);
+  }
+  void xTZSearch(const hmx_pic *pcOrg, const hmx_pic *pcRef, Int cuX, Int cuY, Int x, Int y, Int iRoiWidth, Int iRoiHeight, const Int pcMvSrchRngLT[2],
                  const Int pcMvSrchRngRB[2], Int iSearchRange, Int rcMv[2], UInt &ruiSAD) {
     hmx_me_unit u{};
     u.x = (uint16_t)x, u.y = (uint16_t)y, u.w = (uint8_t)iRoiWidth, u.h = (uint8_t)iRoiHeight;
@@ -387,7 +392,7 @@ public:
     u.pred_x = (int16_t)m_rd.predictorHor(), u.pred_y = (int16_t)m_rd.predictorVer();
     u.left = (int16_t)pcMvSrchRngLT[0], u.top = (int16_t)pcMvSrchRngLT[1], u.right = (int16_t)pcMvSrchRngRB[0], u.bottom = (int16_t)pcMvSrchRngRB[1];
     int sx = rcMv[0], sy = rcMv[1];
-    hmx_clipMv(&sx, &sy, x, y, m_g.picWidth, m_g.picHeight, m_g.ctuSize);
+    hmx_clipMv(&sx, &sy, cuX, cuY, m_g.picWidth, m_g.picHeight, m_g.ctuSize);
     hmx_tz_unit z{};
     z.start_x = (int16_t)(sx >> 2), z.start_y = (int16_t)(sy >> 2), z.range = (uint16_t)iSearchRange;
     m_c.check(hmx_batch_tz_search(m_c.get(), &u, &z, 1, pcRef, 1, pcOrg, m_g.picWidth, m_g.picHeight, m_g.marginX, m_g.marginY,
@@ -435,20 +440,26 @@ public:
   // vector the range is centred on, out the refined vector, both in quarter samples.  ruiBits: in the bits before the vector,
   // out with the vector's bits added.  bBi: the caller passes 2 * org - other prediction as pcOrg (removeHighFreq, :4147) and
   // the cost takes fWeight = 0.5 (:4148).  The integer stage is the full search when !m_iFastSearch || bBi, otherwise xTZSearch
-  // from rcMv = *pcMvPred with the range iSrchRng (:4176-4184).
+  // from rcMv = *pcMvPred with the range iSrchRng (:4176-4184).  (cuX, cuY): the origin of the unit's coding unit, which
+  // xSetSearchRange and xTZSearch clip against (pcCU->clipMv); the form without it is for a unit that is its CU's first
+  // partition.  A second partition (2NxN, Nx2N, AMP) lies elsewhere, and near the picture border its box differs.
   void xMotionEstimation(const hmx_pic *pcOrg, const hmx_pic *pcRef, Int x, Int y, Int iRoiWidth, Int iRoiHeight, const Int pcMvPred[2], Int iSrchRng,
                          Bool bBi, Int rcMv[2], UInt &ruiBits, UInt &ruiCost) {
+    xMotionEstimation(pcOrg, pcRef, x, y, x, y, iRoiWidth, iRoiHeight, pcMvPred, iSrchRng, bBi, rcMv, ruiBits, ruiCost);
+  }
+  void xMotionEstimation(const hmx_pic *pcOrg, const hmx_pic *pcRef, Int cuX, Int cuY, Int x, Int y, Int iRoiWidth, Int iRoiHeight, const Int pcMvPred[2],
+                         Int iSrchRng, Bool bBi, Int rcMv[2], UInt &ruiBits, UInt &ruiCost) {
     const Double fWeight = bBi ? 0.5 : 1.0;
     Int lt[2], rb[2], mvInt[2], mvHalf[2], mvQter[2];
-    if (bBi) xSetSearchRange(x, y, rcMv[0], rcMv[1], iSrchRng, lt, rb);
-    else xSetSearchRange(x, y, pcMvPred[0], pcMvPred[1], iSrchRng, lt, rb);
+    if (bBi) xSetSearchRange(cuX, cuY, rcMv[0], rcMv[1], iSrchRng, lt, rb);
+    else xSetSearchRange(cuX, cuY, pcMvPred[0], pcMvPred[1], iSrchRng, lt, rb);
     m_rd.getMotionCost(true, 0);
     m_rd.setPredictor(pcMvPred[0], pcMvPred[1]);
     m_rd.setCostScale(2);
     if (!m_iFastSearch || bBi) xPatternSearch(pcOrg, pcRef, x, y, iRoiWidth, iRoiHeight, lt, rb, mvInt, ruiCost);
     else {
       mvInt[0] = pcMvPred[0], mvInt[1] = pcMvPred[1];
-      xTZSearch(pcOrg, pcRef, x, y, iRoiWidth, iRoiHeight, lt, rb, iSrchRng, mvInt, ruiCost);
+      xTZSearch(pcOrg, pcRef, cuX, cuY, x, y, iRoiWidth, iRoiHeight, lt, rb, iSrchRng, mvInt, ruiCost);
     }
     m_rd.getMotionCost(true, 0);
     m_rd.setCostScale(1);
