@@ -124,6 +124,52 @@ def count_sbh_on_clipped(lev_sbh, lev_plain):
     return int(np.count_nonzero((a != b) & ((b == INT16_MAX) | (b == INT16_MIN))))
 
 
+def rdoq_max_level(B, per, rem, log2n):
+    """The largest |level| xRateDistOptQuant can start from for a block of 2^log2n (TComTrQuant.cpp:1749-1757, 1885-1898):
+    uiMaxAbsLevel = (|coef| * g_quantScales[rem] + (1 << (iQBits - 1))) >> iQBits at |coef| = 32768, the largest magnitude a
+    transform coefficient has, with iQBits = QUANT_SHIFT + per + (MAX_TR_DYNAMIC_RANGE - B - log2n) = 29 - B - log2n + per.
+    The per-coefficient decision only lowers it (:2483-2484); sign hiding may add one (:2283-2295)."""
+    qbits = 29 - B - log2n + per
+    return (32768 * QUANT_SCALES[rem] + (1 << (qbits - 1))) >> qbits
+
+
+def rdoq_chain_must_refuse(tus, B, qp, cqo):
+    """True iff some block of the list, by ITS plane and size, can hold an RDOQ level above 32767 at (B, QP_Y, chroma QP offset):
+    the calls a chain that keeps RDOQ's levels in 16-bit words has to refuse -- and the only ones.  Transform-skip blocks, which
+    keep the flat quantiser, are counted like the others (as the library counts them): they are 4x4, whose bound is 26214 at
+    most (qbits >= 15 up to 12 bit), so they never decide."""
+    import oracle_lib as ol
+    O = ol.oracle()
+    bd = qp_bd_offset(B)
+    for chroma in (0, 1):
+        q = O.hmo_setQPforQuant(qp, chroma, bd, cqo if chroma else 0)
+        for lg in np.unique(tus["log2n"][(tus["plane"] != 0) == bool(chroma)]):
+            if rdoq_max_level(B, q.per, q.rem, int(lg)) > INT16_MAX:
+                return True
+    return False
+
+
+# (B, QP_Y, tiling): the lowest QP_Y at which a plan whose largest blocks are N x N passes rdoq_chain_must_refuse.  But for the
+# last one, QP_Y - 1 falls on rem 4 at qbits 14: (32768 * 16384 + 8192) >> 14 = 32768.
+RDOQ_BOUNDARY_CASES = ((10, -7, 32), (10, -12, 16), (12, -7, 32), (12, -13, 16), (12, -19, 8), (12, -24, 4))
+_boundary_cache = {}
+
+
+def rdoq_boundary_case(B, qp, N, n_pics=3):
+    """Inputs of one RDOQ boundary case, the same for the CPU and the GPU test: a uniform N x N tiling of a 128x128 picture with
+    cbf contexts and no transform skip, saturating pictures at that scale, eight bit-estimate tables and the all-intra
+    multipliers of the QP.  -> (tus, [pictures], ests, (lambda luma, lambda chroma)); shared, do not modify."""
+    key = (B, qp, N, n_pics)
+    if key not in _boundary_cache:
+        from thevc_amd import workload
+        rng = np.random.default_rng(1)
+        tus = workload.with_cbf_ctx(workload.make_tus(40 + B, 128, 128, N, ts_prob=0.0))
+        orgs = [saturating_picture(rng, 128, 128, B, scale=N) for _ in range(n_pics)]
+        ests = [workload.make_est_bits(9100 + k) for k in range(8)]
+        _boundary_cache[key] = (tus, orgs, ests, workload.rdoq_lambdas(qp))
+    return _boundary_cache[key]
+
+
 def count_dequant_wrap(levels, N, B, per, rem):
     """Positions whose 32-bit de-quantiser product wraps: clip(level) * (invScale << per) + add leaves Int
     (TComTrQuant.cpp:1346-1353)."""

@@ -243,9 +243,9 @@ def frame_cfg(w, h, B, qp, sign_hide=1, chroma_qp_offset=0, ctu=64, inter_slice=
     return FrameCfg(w, h, ctu, B, qp, chroma_qp_offset, sign_hide, inter_slice)
 
 
-def o_intra_frame_encode(tus, w, h, B, qp, org, sign_hide=1):
+def o_intra_frame_encode(tus, w, h, B, qp, org, sign_hide=1, chroma_qp_offset=0, ctu=64):
     """oracle: decisions + original planes -> (recon planes, level planes)"""
-    cfg = frame_cfg(w, h, B, qp, sign_hide)
+    cfg = frame_cfg(w, h, B, qp, sign_hide, chroma_qp_offset, ctu)
     rec = [np.zeros_like(p) for p in org]
     lev = [np.zeros(p.shape, np.int32) for p in org]
     P3, I3 = C.c_void_p * 3, C.c_int * 3
@@ -256,10 +256,10 @@ def o_intra_frame_encode(tus, w, h, B, qp, org, sign_hide=1):
     return rec, lev
 
 
-def o_intra_frame_encode_rdoq(tus, w, h, B, qp, org, ests, lambdas, sign_hide=1):
+def o_intra_frame_encode_rdoq(tus, w, h, B, qp, org, ests, lambdas, sign_hide=1, chroma_qp_offset=0, ctu=64):
     """oracle: the same chain with xRateDistOptQuant as the quantiser; ests = 8 EstBits [luma, chroma][4 sizes], lambdas = (luma,
     chroma); the blocks' cbf contexts ride in bits 4..7 of tus['flags']"""
-    cfg = frame_cfg(w, h, B, qp, sign_hide)
+    cfg = frame_cfg(w, h, B, qp, sign_hide, chroma_qp_offset, ctu)
     rec = [np.zeros_like(p) for p in org]
     lev = [np.zeros(p.shape, np.int32) for p in org]
     P3, I3 = C.c_void_p * 3, C.c_int * 3

@@ -82,11 +82,13 @@ static int issue_packed(hmx_ctx *c, const hmx_intra_plan *const *plans, int plan
   G.n_groups = (n_pics + G.I - 1) / G.I;
   G.n_shards = std::min(8, G.n_groups);
   uint64_t items = 0, sz[4] = {0, 0, 0, 0};
+  uint32_t tex_sizes = 0;
   for (int i = 0; i < n_pics; i++) {
     const hmx_intra_plan *pl = plans[i * plan_stride];
     G.max_levels = std::max(G.max_levels, pl->n_levels);
     items += (uint64_t)pl->n_tu;
     for (int s = 0; s < 4; s++) sz[s] += pl->size_total[s];
+    tex_sizes |= pl->tex_sizes;
   }
   // one lane per 4x4 block is the throughput shape, four lanes per block make more, shorter waves (small batches)
   // (measured with the mode-aware dependency order, 2160p mix: 64 lanes/wave-item ahead at 8..128 and from 384 pictures,
@@ -100,10 +102,13 @@ static int issue_packed(hmx_ctx *c, const hmx_intra_plan *const *plans, int plan
     // Inside the kernel RDOQ's levels travel as 16-bit words (hmx_rdoq.h); the reference keeps TCoeff = Int.  A level can reach
     // (32768 * q) >> qbits: at the lowest QPs of deep bit depths that exceeds 32767 for the large transforms (10 bit, per = 0, 32x32:
     // ~52000) and would wrap silently -- refuse the call instead (the scalar and block-list entries send such calls through the
-    // one-lane-per-block kernel, whose levels are 32-bit: include/hmx.h).
+    // one-lane-per-block kernel, whose levels are 32-bit: include/hmx.h).  Luma and chroma have QPs of their own: a size counts
+    // for the texture type that holds a block of it (32x32 luma beside a lower chroma QP does not make a 32x32 chroma block).
+    // The plans of a call share the picture parameters (the kernel takes them from the first): so does this check, over the
+    // sizes of all of them.  (sz[] sizes the tables below.)
     for (int t = 0; t < 2; t++)
       for (int lg = 2; lg <= 5; lg++) {
-        if (!sz[lg - 2]) continue;
+        if (!((tex_sizes >> (4 * t + lg - 2)) & 1)) continue;
         const int qbits = 14 + p0->P.qd[t].per_qbits + (15 - p0->P.bit_depth - lg);
         if (((32768ll * p0->P.qd[t].q) >> qbits) > 32767)
           return fail(c, HMX_ERR_ARG, "frame_intra: RDOQ in the chain keeps levels in 16 bits; this QP / bit depth / block size can exceed them (raise the QP or use the flat quantiser)");

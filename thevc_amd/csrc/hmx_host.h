@@ -350,6 +350,7 @@ struct hmx_intra_plan {
   std::vector<uint32_t> level_chunks; // waves needed per level
   std::vector<LevelRow> h_ltab;       // host copy of the level table
   uint64_t size_total[4] = {0, 0, 0, 0}; // blocks per transform size
+  uint32_t tex_sizes = 0;                 // bit 4 * t + log2n - 2: the plan holds a block of that size in luma (t = 0) / chroma (t = 1)
   uint64_t serial = 0;                    // unique per plan: a freed plan's address may be handed out again
   // per CTU row: the first and the last dependency level that touches it (the layout conversions are pipelined by CTU
   // row: a row is converted in before its first level and out after its last one)

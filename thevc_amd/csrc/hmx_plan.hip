@@ -172,6 +172,7 @@ struct PlanHost {
   std::vector<std::pair<uint32_t, uint32_t>> waves;
   PicDev P;
   int n_tu = 0;
+  uint32_t tex_sizes = 0; // hmx_intra_plan::tex_sizes
 };
 static const char *plan_build_host(const hmx_ctx *c, const hmx_tu *tus, int n_tu, const hmx_pic_param *pp, PlanHost &H,
                                    const hmx_avail_layout *layout = nullptr) {
@@ -295,6 +296,7 @@ static const char *plan_build_host(const hmx_ctx *c, const hmx_tu *tus, int n_tu
     }
     ltab.assign((size_t)max_level + 1, LevelRow{{0, 0, 0, 0}, {0, 0, 0, 0}});
     for (int i = 0; i < n_tu; i++) ltab[glevel[i]].count[tus[i].log2n - 2]++;
+    for (int i = 0; i < n_tu; i++) H.tex_sizes |= 1u << ((tus[i].plane ? 4 : 0) + tus[i].log2n - 2);
     uint32_t off = 0;
     level_chunks.resize(ltab.size());
     for (size_t l = 0; l < ltab.size(); l++) {
@@ -364,6 +366,7 @@ static int plan_upload(hmx_ctx *c, PlanHost &H, const hmx_pic_param *pp, hmx_int
   pl->row_last_level = H.row_last;
   pl->P = H.P;
   pl->n_tu = H.n_tu;
+  pl->tex_sizes = H.tex_sizes;
   pl->qp = pp->qp;
   pl->chroma_qp_offset = pp->chroma_qp_offset;
   pl->slice_type = pp->slice_type;
@@ -656,13 +659,13 @@ __device__ __forceinline__ unsigned long long plan_dep_mask(const unsigned long 
 // so that the walk -- sequential per CTU -- is left with LDS reads and one maximum per dependency.
 // LAYOUT: each picture's slice / tile / CIP layout (lays[pic]) cuts the availability down; the plain instantiation is the one without.
 template <bool LAYOUT>
-__global__ __launch_bounds__(256) void k_plan_ctus(const hmx_tu *tus, const uint32_t *pic_off, uint32_t *ctu_start, uint32_t *size_total,
+__global__ __launch_bounds__(256) void k_plan_ctus(const hmx_tu *tus, const uint32_t *pic_off, uint32_t *ctu_start, uint32_t *tex_sizes,
                                                    uint32_t *err, const unsigned long long *need, unsigned long long *rec, FTu *ftu, PlanGeomDev G,
                                                    const AvailDev *lays) {
   const int pic = blockIdx.y;
   const uint32_t b0 = pic_off[pic], n = pic_off[pic + 1] - b0, i = blockIdx.x * 256 + threadIdx.x;
   uint32_t *cs = ctu_start + (size_t)pic * (G.n_ctu + 1);
-  int sz = -1;
+  uint32_t ts = 0;
   if (i < n) {
     const hmx_tu t = tus[b0 + i];
     int e = PLAN_OK;
@@ -676,7 +679,7 @@ __global__ __launch_bounds__(256) void k_plan_ctus(const hmx_tu *tus, const uint
     if (e) {
       atomicMax(err, (uint32_t)e);
     } else {
-      sz = t.log2n - 2;
+      ts = 1u << ((t.plane ? 4 : 0) + t.log2n - 2);
       const int ctu = plan_ctu_of(t, G.cw);
       {
         const int sh = t.plane ? 1 : 0, lx = t.x << sh, ly = t.y << sh, ls = (1 << t.log2n) << sh;
@@ -700,7 +703,10 @@ __global__ __launch_bounds__(256) void k_plan_ctus(const hmx_tu *tus, const uint
         for (int c = ctu + 1; c <= G.n_ctu; c++) cs[c] = n;
     }
   }
-  (void)sz, (void)size_total; // (blocks per size: summed from the level table by k_plan_scan -- atomics here all hit four words per picture)
+  // which (texture type, size) pairs the picture holds (hmx_intra_plan::tex_sizes): one atomic per wave.  (Blocks per size are
+  // summed from the level table by k_plan_scan -- atomics per block here would all hit four words per picture.)
+  for (int o = 32; o; o >>= 1) ts |= (uint32_t)__shfl_xor((int)ts, o);
+  if ((threadIdx.x & 63) == 0 && ts) atomicOr(&tex_sizes[pic], ts);
   if (n == 0 && i == 0)
     for (int c = 0; c <= G.n_ctu; c++) cs[c] = 0;
 }
@@ -1109,9 +1115,9 @@ static int plan_create_device(hmx_ctx *c, const hmx_tu *d_tus, const uint32_t *o
     HIPCHK(c, hipMemcpy(c->pd.d_need, need.data(), need.size() * 8, hipMemcpyHostToDevice));
   }
   // work buffers: picture offsets | CTU starts | levels | bottom edges | right edges | per-picture words (max level, 4 size totals; then
-  // error, overflow) | level-table offsets + level counts | cursors | keys | the level walk's per-block records | descriptors in coding order
+  // error, overflow; then the texture/size bits) | level-table offsets + level counts | cursors | keys | the level walk's per-block records | descriptors in coding order
   enum { B_OFF, B_CTU, B_LEVEL, B_BOT, B_RIGHT, B_META, B_LOFF, B_CURSOR, B_KEYS, B_REC, B_FTU };
-  const size_t meta_words = (size_t)n_pics * 5 + 2;
+  const size_t meta_words = (size_t)n_pics * 6 + 2;
   int r = plan_grow(c, B_OFF, sizeof(uint32_t) * (n_pics + 1));
   if (!r) r = plan_grow(c, B_CTU, sizeof(uint32_t) * (size_t)n_pics * (G.n_ctu + 1));
   if (!r) r = plan_grow(c, B_LEVEL, sizeof(unsigned short) * (size_t)total);
@@ -1125,7 +1131,7 @@ static int plan_create_device(hmx_ctx *c, const hmx_tu *d_tus, const uint32_t *o
   if (r) return r;
   uint32_t *d_off = (uint32_t *)c->pd.buf[B_OFF], *d_ctu = (uint32_t *)c->pd.buf[B_CTU], *d_meta = (uint32_t *)c->pd.buf[B_META];
   unsigned short *d_level = (unsigned short *)c->pd.buf[B_LEVEL], *d_bot = (unsigned short *)c->pd.buf[B_BOT], *d_right = (unsigned short *)c->pd.buf[B_RIGHT];
-  uint32_t *d_pic_max = d_meta, *d_size_total = d_meta + n_pics, *d_err = d_meta + (size_t)n_pics * 5, *d_overflow = d_err + 1;
+  uint32_t *d_pic_max = d_meta, *d_size_total = d_meta + n_pics, *d_err = d_meta + (size_t)n_pics * 5, *d_overflow = d_err + 1, *d_tex_sizes = d_err + 2;
   uint32_t *d_loff = (uint32_t *)c->pd.buf[B_LOFF];
   unsigned long long *d_rec = (unsigned long long *)c->pd.buf[B_REC];
   FTu *d_ftu = (FTu *)c->pd.buf[B_FTU];
@@ -1173,9 +1179,9 @@ static int plan_create_device(hmx_ctx *c, const hmx_tu *d_tus, const uint32_t *o
     if (e1 == hipSuccess) e1 = hipMemsetAsync(d_right, 0, sizeof(unsigned short) * (size_t)n_pics * 3 * G.n_ctu * 16, st);
     if (e1 == hipSuccess) e1 = hipMemsetAsync(set->d_ltab, 0, sizeof(LevelRow) * rows, st);
     if (d_lays)
-      hipLaunchKernelGGL(k_plan_ctus<true>, per_block, dim3(256), 0, st, tus0, d_off, d_ctu, d_size_total, d_err, c->pd.d_need, d_rec, d_ftu, G, d_lays);
+      hipLaunchKernelGGL(k_plan_ctus<true>, per_block, dim3(256), 0, st, tus0, d_off, d_ctu, d_tex_sizes, d_err, c->pd.d_need, d_rec, d_ftu, G, d_lays);
     else
-      hipLaunchKernelGGL(k_plan_ctus<false>, per_block, dim3(256), 0, st, tus0, d_off, d_ctu, d_size_total, d_err, c->pd.d_need, d_rec, d_ftu, G,
+      hipLaunchKernelGGL(k_plan_ctus<false>, per_block, dim3(256), 0, st, tus0, d_off, d_ctu, d_tex_sizes, d_err, c->pd.d_need, d_rec, d_ftu, G,
                          (const AvailDev *)nullptr);
     PlanLevelArgs LA{d_rec, d_off, d_ctu, d_level, d_bot, d_right, d_pic_max, set->d_ltab, cap, d_overflow, G};
     // A block depends on blocks of its own plane only: the luma walk and the chroma walk are two independent chains of launches,
@@ -1273,6 +1279,7 @@ static int plan_create_device(hmx_ctx *c, const hmx_tu *d_tus, const uint32_t *o
     for (int s = 0; s < 4; s++) pl->size_total[s] = sizes[(size_t)i * 4 + s];
     pl->P = G.P;
     pl->n_tu = (int)(offsets[i + 1] - offsets[i]);
+    pl->tex_sizes = meta[(size_t)n_pics * 5 + 2 + i];
     pl->qp = pp->qp, pl->chroma_qp_offset = pp->chroma_qp_offset, pl->slice_type = pp->slice_type;
     out[i] = pl;
   }

@@ -1,5 +1,7 @@
-"""Soak of the packed schedule: random batch sizes, packing groups, persistent-wave counts, 4x4 wave shapes, with and without
-RDOQ and the distortion output, every picture with its own plan -- each run held against the oracle.  python3 tools/soak.py [runs]"""
+"""Soak of the packed schedule: random batch sizes, packing groups, persistent-wave counts, 4x4 wave shapes, bit depths 8 / 10 / 12,
+sign hiding on and off, chroma QP offsets, with and without RDOQ and the distortion output, every picture with its own plan -- each
+run held against the oracle.  12 bit takes the place of the 8 or 10 bit of a third of the runs (it does not add runs); their
+other draws stay.  python3 tools/soak.py [runs]"""
 import ctypes as C
 import os
 import sys
@@ -19,6 +21,7 @@ w, h = 264, 200
 def soak(runs, seed, verbose=True):
   L = capi.lib()
   rng = np.random.default_rng(seed)
+  rng2 = np.random.default_rng([seed, 2])  # the later draws (12 bit, sign hiding, chroma QP offset): a stream of their own, the ones above stay what they were
   cache = {}
   for it in range(runs):
       B = int(rng.choice([8, 10]))
@@ -33,12 +36,16 @@ def soak(runs, seed, verbose=True):
       if rdoq:
           group = min(group, 2)
       qp = int(rng.integers(22, 38))
+      if rng2.integers(0, 3) == 0:               # 8, 10 and 12 bit, a third each: these runs no longer cover the 8 or 10 bit drawn above
+          B = 12
+      sbh = int(rng2.integers(0, 2))
+      cqo = int(rng2.choice([-6, 0, 5]))
       ctx = capi.Context(bit_depth=B)
       ctx.set_option("HMX_PACK_GROUP", group)
       ctx.set_option("HMX_PACK_WAVES", waves)
       ctx.set_option("HMX_PACK_SLOTS4", slots)
       ctx.set_option("HMX_PACK_SLOTS8", slots8)
-      pp = capi.PicParam(w, h, qp, 0, capi.I_SLICE, 1)
+      pp = capi.PicParam(w, h, qp, cqo, capi.I_SLICE, sbh)
       seeds = [int(rng.integers(0, 12)) for _ in range(n)]
       tus = [workload.with_cbf_ctx(workload.make_tus(8000 + sd, w, h, "mix")) for sd in seeds]
       if dev_plans:
@@ -65,19 +72,19 @@ def soak(runs, seed, verbose=True):
       ctx._chk(L.hmx_frame_intra_decode_multi(ctx.h, parr, n, A(d_dec, capi.Pic), A(d_lev, capi.Levels)))
       ctx.sync()
       for i in range(n):
-          key = (B, qp, seeds[i], rdoq)
+          key = (B, qp, seeds[i], rdoq, sbh, cqo)
           if key not in cache:
-              cache[key] = (ol.o_intra_frame_encode_rdoq(tus[i], w, h, B, qp, orgs[i], ests[i], lams) if rdoq
-                            else ol.o_intra_frame_encode(tus[i], w, h, B, qp, orgs[i]))
+              cache[key] = (ol.o_intra_frame_encode_rdoq(tus[i], w, h, B, qp, orgs[i], ests[i], lams, sign_hide=sbh, chroma_qp_offset=cqo) if rdoq
+                            else ol.o_intra_frame_encode(tus[i], w, h, B, qp, orgs[i], sign_hide=sbh, chroma_qp_offset=cqo))
           rr, lr = cache[key]
           rec, dec = d_rec[i].download(), d_dec[i].download()
           lev = d_lev[i].to_planes(tus[i]) if zlev else d_lev[i].download()
           for p in range(3):
               assert np.array_equal(rec[p], rr[p]) and np.array_equal(lev[p], lr[p]) and np.array_equal(dec[p], rr[p]), \
-                  (it, i, p, B, n, group, waves, slots, slots8, zlev, dev_plans, rdoq)
+                  (it, i, p, B, n, group, waves, slots, slots8, zlev, dev_plans, rdoq, qp, sbh, cqo)
       if verbose:
         print(f"run {it}: B {B} pictures {n} group {group} waves {waves} slots4 {slots} slots8 {slots8} zlev {int(zlev)} device plans {int(dev_plans)} "
-              f"rdoq {int(rdoq)} qp {qp}: ok", flush=True)
+              f"rdoq {int(rdoq)} qp {qp} sign hiding {sbh} chroma offset {cqo}: ok", flush=True)
       ctx.close()
   if verbose:
     print("soak: all runs identical to the oracle")
