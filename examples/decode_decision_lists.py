@@ -11,6 +11,11 @@ Streams with several slices, several tiles or constrained intra prediction (test
 (region per CTU, constrained_intra_pred_flag); decode_sequence passes it to the intra plans:
 
   python examples/decode_decision_lists.py tests/golden/layout_intra_he10_q32_tiles_slices.npz out.yuv --check
+
+Streams whose loop filters may not cross slice or tile boundaries (tests/golden/lfx_*.npz) carry the slice and tile of every
+CTU and the flags; decode_sequence drops the deblocking edges on such boundaries and runs SAO on the availability path:
+
+  python examples/decode_decision_lists.py tests/golden/lfx_intra_he10_q37_tiles_slices.npz out.yuv --check
 """
 import argparse
 import os

@@ -779,6 +779,34 @@ int hmx_sao_picture(hmx_ctx *ctx, const hmx_pic *in, const hmx_pic *out, int pic
 int hmx_sao_picture_multi(hmx_ctx *ctx, int n_pics, const hmx_pic *in, const hmx_pic *out, int pic_w, int pic_h,
                           const hmx_sao_lcu *d_params, int n_lcu);
 
+/* Which neighbour CTUs the loop filters of a CTU may read: TComDataCU::setNDBFilterBlockBorderAvailability
+ * (TLibCommon/TComDataCU.cpp:4212-4634, as compiled with MODIFIED_CROSS_SLICE 1 and REMOVE_FGS 1: one block per CTU), called
+ * from TComPic::createNonDBFilterInfo (TComPic.cpp:138-339).  Host only, no context.  avail[CTU in raster order]: bit k set =
+ * neighbour k may be read, k as the SGU_* enumeration (TComDataCU.h:64-72): 0 L, 1 R, 2 T, 3 B, 4 TL, 5 TR, 6 BL, 7 BR.
+ *   a neighbour outside the picture is unavailable (:4271, :4415 ...);
+ *   a neighbour in the same slice is available; one in a LATER slice when that slice's flag is set, one in an EARLIER slice
+ *   when this slice's flag is set (:4299); a picture with one slice skips the slice test (onlyOneSliceInPic, :4220);
+ *   with lf_cross_tiles == 0 the result is ANDed with "same tile" (:4589-4623).
+ * slice_id[CTU in raster order]: index of the CTU's slice in decoding order (slices begin at CTU boundaries; a dependent slice
+ * belongs to its independent slice); slice_lf_cross[n_slices]: slice_loop_filter_across_slices_enabled_flag of each slice;
+ * tile_id[CTU] (may be NULL: one tile); lf_cross_tiles: loop_filter_across_tiles_enabled_flag of the PPS.  The reference takes
+ * the availability path of SAO (m_bUseNIF, TComSampleAdaptiveOffset.cpp:500) as soon as a flag is 0 with more than one slice /
+ * tile; with every bit inside the picture set the two paths give the same pictures.  The deblocking filter drops the left /
+ * top edges of a CTU whose L / T bit is clear (TComLoopFilter.cpp:411, 432, 458, 462: the left and top neighbours are never in
+ * a later slice, so this slice's flag decides there too): clear those entries of d_edge_ver / d_edge_hor or d_bs_ver / d_bs_hor.
+ * HMX_ERR_ARG: a null pointer other than tile_id, a non-positive size or n_slices, a slice id >= n_slices. */
+int hmx_lf_border_avail(int pic_w, int pic_h, int ctu_size, const uint32_t *slice_id, const uint8_t *slice_lf_cross, int n_slices,
+                        const uint32_t *tile_id, int lf_cross_tiles, uint8_t *avail);
+/* hmx_sao_picture_multi on the availability path: processSaoCu -> processSaoBlock (TComSampleAdaptiveOffset.cpp:515-776) for
+ * every CTU (cut at the picture edge) and component; the chroma planes use the CTU's luma byte.  d_avail (device):
+ * [pic][CTU in raster order] bytes of hmx_lf_border_avail.  An edge-offset sample is filtered exactly when each of its two
+ * neighbours lies in its own CTU or in a neighbour CTU whose bit is set, and copied otherwise (what the start / end columns
+ * and the first-line, last-line and corner branches of :573-759 come to); band offset ignores the bytes (:760-772).  No sample
+ * of a CTU whose bit is clear contributes to the output.  A mask with every bit inside the picture set gives what
+ * hmx_sao_picture_multi gives.  HMX_ERR_ARG as for hmx_sao_picture_multi, and for a null d_avail. */
+int hmx_sao_picture_multi_avail(hmx_ctx *ctx, int n_pics, const hmx_pic *in, const hmx_pic *out, int pic_w, int pic_h,
+                                const hmx_sao_lcu *d_params, int n_lcu, const uint8_t *d_avail);
+
 /* Sample adaptive offset, the encoder's statistics pass: TEncSampleAdaptiveOffset::calcSaoStatsCuOrg
  * (TLibEncoder/TEncSampleAdaptiveOffset.cpp:859-1124 with SAO_SKIP_RIGHT, TLibCommon/TypeDef.h:123), which rdoSaoUnitAll
  * (:1617, via calcSaoStatsCu) runs for every CTU and component between deblocking and the parameter search.  For every CTU
@@ -795,8 +823,9 @@ int hmx_sao_picture_multi(hmx_ctx *ctx, int n_pics, const hmx_pic *in, const hmx
  *   EO_2, EO_3      x in [L, R ? W-1 : W-r)  y in [T, Bt ? H-1 : H-s)
  * Edge class = m_auiEoTable[sign(c - a) + sign(c - b) + 2] (TComSampleAdaptiveOffset.cpp:94; {1, 2, 0, 3, 4}), class 0
  * ("no edge") included; neighbours a, b: (x-1,y),(x+1,y) | (x,y-1),(x,y+1) | (x-1,y-1),(x+1,y+1) | (x+1,y-1),(x-1,y+1), read
- * from the picture across CTU edges.  Not covered: the NIF path (calcSaoStatsBlock: slice / tile boundaries not crossed,
- * TComSampleAdaptiveOffset.cpp:500) and everything after the statistics (offset estimation, estSaoDist, merge, CABAC rates,
+ * from the picture across CTU edges.  The NIF path (calcSaoStatsBlock: slice / tile boundaries not crossed,
+ * TComSampleAdaptiveOffset.cpp:500) is hmx_sao_stats_multi_avail below.  Not covered: everything after the statistics (offset
+ * estimation, estSaoDist, merge, CABAC rates,
  * the quadtree part sums of SAOLcuBasedOptimization = 0: the host sums these per-CTU bins).  |diff| <= 64*64*(2^12 - 1)
  * fits int32.  HMX_ERR_ARG: a null pointer, n_pics < 1, pic_w or pic_h not a positive multiple of 8. */
 typedef struct hmx_sao_stat {
@@ -807,6 +836,13 @@ int hmx_sao_stats_multi(hmx_ctx *ctx, int n_pics, const hmx_pic *org, const hmx_
                         hmx_sao_stat *d_out);
 int hmx_sao_stats(hmx_ctx *ctx, const hmx_pic *org, const hmx_pic *rec, int pic_w, int pic_h, int lcu_based,
                   hmx_sao_stat *d_out); /* = _multi with n_pics = 1 */
+/* The statistics on the availability path: calcSaoStatsCu -> calcSaoStatsBlock (TLibEncoder/TEncSampleAdaptiveOffset.cpp
+ * :571-854) for every CTU and component, d_avail (device) as for hmx_sao_picture_multi_avail.  The same 52 bins; no rows or
+ * columns are skipped (the block path has no SAO_SKIP_RIGHT).  Band: every sample of the CTU.  Edge type t: the samples whose
+ * two neighbours each lie in the CTU or in a neighbour CTU whose bit is set.  A mask with every bit inside the picture set
+ * gives what hmx_sao_stats_multi gives with lcu_based = 0.  HMX_ERR_ARG as for hmx_sao_stats_multi, and for a null d_avail. */
+int hmx_sao_stats_multi_avail(hmx_ctx *ctx, int n_pics, const hmx_pic *org, const hmx_pic *rec, int pic_w, int pic_h,
+                              const uint8_t *d_avail, hmx_sao_stat *d_out);
 
 /* Planar 4:2:0 YUV frames, the format either side of the path (TLibVideoIO/TVideoIOYuv.cpp:226-480, SURVEY.md
  * 8f rank 4).  d_file (device) holds one frame as the file does: 8-bit or 16-bit little-endian samples, Y then

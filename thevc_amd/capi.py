@@ -322,7 +322,10 @@ def lib():
         L.hmx_deblock_picture.argtypes = [vp, C.POINTER(Pic), ci, ci, vp, vp, vp, vp, ci, ci]
         for name, at in (("hmx_deblock_strengths_multi", [vp, ci, vp, vp, vp, ci, ci, vp, vp, vp]),
                          ("hmx_deblock_picture_multi", [vp, ci, C.POINTER(Pic), ci, ci, vp, vp, vp, vp, vp, vp]),
-                         ("hmx_sao_picture_multi", [vp, ci, C.POINTER(Pic), C.POINTER(Pic), ci, ci, vp, ci])):
+                         ("hmx_sao_picture_multi", [vp, ci, C.POINTER(Pic), C.POINTER(Pic), ci, ci, vp, ci]),
+                         ("hmx_sao_picture_multi_avail", [vp, ci, C.POINTER(Pic), C.POINTER(Pic), ci, ci, vp, ci, vp]),
+                         ("hmx_sao_stats_multi_avail", [vp, ci, C.POINTER(Pic), C.POINTER(Pic), ci, ci, vp, vp]),
+                         ("hmx_lf_border_avail", [ci, ci, ci, vp, vp, ci, vp, ci, vp])):
             if "HMX_LIB_PATH" in os.environ and not hasattr(L, name):
                 continue  # an older build loaded for an A/B run (tools/filters_bench.py): calling the entry still raises
             getattr(L, name).argtypes = at
@@ -866,22 +869,32 @@ class Context:
             if own_int:
                 d_int.free()
 
-    def sao_stats(self, orgs, recs, w, h, lcu_based=True):
+    def sao_stats(self, orgs, recs, w, h, lcu_based=True, avail=None):
         """hmx_sao_stats_multi: the encoder's SAO statistics of n pictures (DevPictures, org and deblocked rec) as an int32
         array (n, 3 components, n_lcu, SAO_STAT_BINS, 2): [..., 0] = sum of org - rec, [..., 1] = count; bins as in
-        include/hmx.h (sao_stats_to_hm spreads them into the reference's own arrays)."""
+        include/hmx.h (sao_stats_to_hm spreads them into the reference's own arrays).  avail: uint8 (n, n_lcu) bytes of
+        lf_border_avail -> hmx_sao_stats_multi_avail (lcu_based is not used then)."""
         n = len(orgs)
         assert n == len(recs) and n > 0
         ctu = self.ctu_size
         n_lcu = -(-w // ctu) * -(-h // ctu)
         o, r = (Pic * n)(*[p.as_pic() for p in orgs]), (Pic * n)(*[p.as_pic() for p in recs])
         out = self.alloc(n * 3 * n_lcu * SAO_STAT_BINS * 8)
+        d_av = None
         try:
-            self._chk(lib().hmx_sao_stats_multi(self.h, n, o, r, w, h, 1 if lcu_based else 0, out.ptr))
+            if avail is not None:
+                avail = np.ascontiguousarray(avail, np.uint8)
+                assert avail.shape == (n, n_lcu), avail.shape
+                d_av = self.to_device(avail)
+                self._chk(lib().hmx_sao_stats_multi_avail(self.h, n, o, r, w, h, d_av.ptr, out.ptr))
+            else:
+                self._chk(lib().hmx_sao_stats_multi(self.h, n, o, r, w, h, 1 if lcu_based else 0, out.ptr))
             self.sync()
             return out.download(np.int32).reshape(n, 3, n_lcu, SAO_STAT_BINS, 2)
         finally:
             out.free()
+            if d_av is not None:
+                d_av.free()
 
     def deblock_strengths(self, n, d_units, d_edge_ver, d_edge_hor, w, h, is_b, d_bs_ver, d_bs_hor):
         """hmx_deblock_strengths_multi: the boundary strengths of n pictures in one launch.  The maps are DevBufs (or device
@@ -913,6 +926,34 @@ class Context:
         n_lcu = -(-w // ctu) * -(-h // ctu)
         a, b = (Pic * n)(*[p.as_pic() for p in ins]), (Pic * n)(*[p.as_pic() for p in outs])
         self._chk(lib().hmx_sao_picture_multi(self.h, n, a, b, w, h, getattr(d_params, "ptr", d_params), n_lcu))
+
+    def sao_pictures_avail(self, ins, outs, w, h, d_params, d_avail):
+        """hmx_sao_picture_multi_avail: sao_pictures on the availability path.  d_avail: a DevBuf (or device address) of the
+        bytes of lf_border_avail laid out [pic][CTU]."""
+        n = len(ins)
+        assert n == len(outs) and n > 0
+        ctu = self.ctu_size
+        n_lcu = -(-w // ctu) * -(-h // ctu)
+        a, b = (Pic * n)(*[p.as_pic() for p in ins]), (Pic * n)(*[p.as_pic() for p in outs])
+        self._chk(lib().hmx_sao_picture_multi_avail(self.h, n, a, b, w, h, getattr(d_params, "ptr", d_params), n_lcu,
+                                                    getattr(d_avail, "ptr", d_avail)))
+
+
+def lf_border_avail(w, h, ctu, slice_id, slice_lf_cross, tile_id=None, lf_cross_tiles=True):
+    """hmx_lf_border_avail: one byte per CTU, bit k = neighbour CTU k (SGU_L, R, T, B, TL, TR, BL, BR) may be read by the loop
+    filters.  slice_id / tile_id: per CTU in raster order; slice_lf_cross: one flag per slice."""
+    sid = np.ascontiguousarray(slice_id, np.uint32).reshape(-1)
+    flags = np.ascontiguousarray(slice_lf_cross, np.uint8).reshape(-1)
+    tid = None if tile_id is None else np.ascontiguousarray(tile_id, np.uint32).reshape(-1)
+    n_ctu = -(-w // ctu) * -(-h // ctu) if w > 0 and h > 0 and ctu > 0 else 0
+    if len(sid) != n_ctu or (tid is not None and len(tid) != n_ctu):
+        raise ValueError("lf_border_avail: one slice id (and tile id) per CTU")
+    out = np.zeros(n_ctu, np.uint8)
+    r = lib().hmx_lf_border_avail(w, h, ctu, _hp(sid), _hp(flags), len(flags), None if tid is None else _hp(tid),
+                                  1 if lf_cross_tiles else 0, _hp(out))
+    if r != 0:
+        raise HmxError(f"hmx_lf_border_avail: error {r}")
+    return out
 
 
 SAO_STAT_BINS = 52  # HMX_SAO_STAT_BINS

@@ -389,7 +389,22 @@ extern "C" int hmx_deblock_picture(hmx_ctx *c, const hmx_pic *rec, int pic_w, in
 // A thread filters 8 consecutive samples of a row (a CTU is a multiple of 8 wide in both planes, so they share their
 // parameters): three 16-byte loads (the row, the rows above and below) and the six samples just outside, one 16-byte store.
 // pics: [n_pics] inputs, then [n_pics] outputs (in the argument arena); the picture is blockIdx.z
-__global__ __launch_bounds__(256) void k_sao(const PlanesDev *pics, int n_pics, int pic_w, int pic_h, int B, int ctu, const hmx_sao_lcu *prm, int n_lcu) {
+// an availability byte (hmx_lf_border_avail) as the 3x3 CTU neighbourhood in 9 bits, bit (sx + 1) + 3 * (sy + 1) for the CTU at (sx, sy) from this one (the centre is set)
+__device__ __forceinline__ unsigned sao_avail9(unsigned m) {
+  return ((m >> 4) & 1) | ((m >> 2) & 1) << 1 | ((m >> 5) & 1) << 2 | (m & 1) << 3 | 1u << 4 | ((m >> 1) & 1) << 5 | ((m >> 6) & 1) << 6 |
+         ((m >> 3) & 1) << 7 | ((m >> 7) & 1) << 8;
+}
+// may the sample at CTU-local (x, y) be read from a CTU of W x H samples with the neighbourhood a9?
+__device__ __forceinline__ bool sao_may_read(unsigned a9, int x, int y, int W, int H) {
+  const int sx = x < 0 ? 0 : (x >= W ? 2 : 1), sy = y < 0 ? 0 : (y >= H ? 2 : 1);
+  return (a9 >> (sx + 3 * sy)) & 1;
+}
+// AVAIL (processSaoBlock :561-776, the path of m_bUseNIF): avail[pic][CTU] says which of the eight neighbour CTUs may be read
+// (bit k = SGU_L, R, T, B, TL, TR, BL, BR); an edge-offset sample is filtered when each of its two neighbours lies in its own
+// CTU or in a CTU whose bit is set, which takes the place of the in-picture test (a CTU outside the picture has no bit).
+template <bool AVAIL>
+__global__ __launch_bounds__(256) void k_sao(const PlanesDev *pics, int n_pics, int pic_w, int pic_h, int B, int ctu, const hmx_sao_lcu *prm, int n_lcu,
+                                             const uint8_t *avail) {
   const int pic = blockIdx.z;
   const PlanesDev &in = pics[pic], &out = pics[n_pics + pic];
   prm += (size_t)pic * 3 * n_lcu;
@@ -398,6 +413,12 @@ __global__ __launch_bounds__(256) void k_sao(const PlanesDev *pics, int n_pics, 
   if (i >= w8 * h) return;
   const int x0 = (i % w8) << 3, y = i / w8, cw = (pic_w + ctu - 1) / ctu;
   const hmx_sao_lcu q = prm[(size_t)p * n_lcu + (y / cs) * cw + x0 / cs];
+  unsigned a9 = 0;
+  int lx0 = 0, ly = 0, W = 0, H = 0; // the thread's first sample in its CTU, and the CTU cut at the picture edge
+  if constexpr (AVAIL) {
+    a9 = sao_avail9(avail[(size_t)pic * n_lcu + (y / cs) * cw + x0 / cs]);
+    lx0 = x0 % cs, ly = y % cs, W = min(cs, w - (x0 - lx0)), H = min(cs, h - (y - ly));
+  }
   // the four offsets in one register, picked by shifts (an indexed copy of the struct would live in scratch)
   const unsigned offs = (unsigned)(unsigned char)q.offset[0] | (unsigned)(unsigned char)q.offset[1] << 8 | (unsigned)(unsigned char)q.offset[2] << 16 |
                         (unsigned)(unsigned char)q.offset[3] << 24;
@@ -429,7 +450,10 @@ __global__ __launch_bounds__(256) void k_sao(const PlanesDev *pics, int n_pics, 
     int o = c;
     if (q.type >= 0 && q.type < 4) {
       const int dx = q.type == 1 ? 0 : (q.type == 3 ? -1 : 1), dy = q.type == 0 ? 0 : 1; // b = c + d, a = c - d
-      if (x - dx >= 0 && x - dx < w && y - dy >= 0 && x + dx >= 0 && x + dx < w && y + dy < h) {
+      bool both;
+      if constexpr (AVAIL) both = sao_may_read(a9, lx0 + k - dx, ly - dy, W, H) && sao_may_read(a9, lx0 + k + dx, ly + dy, W, H);
+      else both = x - dx >= 0 && x - dx < w && y - dy >= 0 && x + dx >= 0 && x + dx < w && y + dy < h;
+      if (both) {
         // select the neighbours from the register rows (dx, dy are uniform over the thread's samples)
         const int a = dy ? (dx == 0 ? r[0][k + 1] : (dx > 0 ? r[0][k] : r[0][k + 2])) : r[1][k];
         const int bb = dy ? (dx == 0 ? r[2][k + 1] : (dx > 0 ? r[2][k + 2] : r[2][k])) : r[1][k + 2];
@@ -452,19 +476,30 @@ __global__ __launch_bounds__(256) void k_sao(const PlanesDev *pics, int n_pics, 
     for (int k = 0; k < n; k++) d[k] = (short)v[k];
   }
 }
-extern "C" int hmx_sao_picture_multi(hmx_ctx *c, int n_pics, const hmx_pic *in, const hmx_pic *out, int pic_w, int pic_h,
-                                     const hmx_sao_lcu *d_params, int n_lcu) {
-  if (!c || !in || !out || !d_params) return fail(c, HMX_ERR_ARG, "hmx_sao_picture_multi: null argument");
+// d_avail: null = the in-picture test (processSaoCuOrg), else the availability path
+static int sao_picture_multi(hmx_ctx *c, const char *fn, int n_pics, const hmx_pic *in, const hmx_pic *out, int pic_w, int pic_h,
+                             const hmx_sao_lcu *d_params, int n_lcu, const uint8_t *d_avail) {
+  if (!c || !in || !out || !d_params) return fail(c, HMX_ERR_ARG, std::string(fn) + ": null argument");
   const int ctu = c->cfg.ctu_size;
   const bool dims_ok = multiple_of(pic_w, pic_h, 2) && n_lcu == ((pic_w + ctu - 1) / ctu) * ((pic_h + ctu - 1) / ctu);
   const PlanesDev *d;
-  if (int r = multi_pics(c, "hmx_sao_picture_multi", n_pics, dims_ok, "bad size (even, and n_lcu must be the CTU count of the picture)", in, out,
+  if (int r = multi_pics(c, fn, n_pics, dims_ok, "bad size (even, and n_lcu must be the CTU count of the picture)", in, out,
                          "in and out must be different pictures", planes_of, &d))
     return r;
-  hipLaunchKernelGGL(k_sao, dim3((unsigned)(((size_t)((pic_w + 7) / 8) * pic_h + 255) / 256), 3, (unsigned)n_pics), dim3(256), 0, c->stream, d, n_pics,
-                     pic_w, pic_h, c->cfg.bit_depth, ctu, d_params, n_lcu);
+  const dim3 grid((unsigned)(((size_t)((pic_w + 7) / 8) * pic_h + 255) / 256), 3, (unsigned)n_pics);
+  if (d_avail) hipLaunchKernelGGL(k_sao<true>, grid, dim3(256), 0, c->stream, d, n_pics, pic_w, pic_h, c->cfg.bit_depth, ctu, d_params, n_lcu, d_avail);
+  else hipLaunchKernelGGL(k_sao<false>, grid, dim3(256), 0, c->stream, d, n_pics, pic_w, pic_h, c->cfg.bit_depth, ctu, d_params, n_lcu, d_avail);
   HIPCHK(c, hipGetLastError());
   return HMX_OK;
+}
+extern "C" int hmx_sao_picture_multi(hmx_ctx *c, int n_pics, const hmx_pic *in, const hmx_pic *out, int pic_w, int pic_h,
+                                     const hmx_sao_lcu *d_params, int n_lcu) {
+  return sao_picture_multi(c, "hmx_sao_picture_multi", n_pics, in, out, pic_w, pic_h, d_params, n_lcu, nullptr);
+}
+extern "C" int hmx_sao_picture_multi_avail(hmx_ctx *c, int n_pics, const hmx_pic *in, const hmx_pic *out, int pic_w, int pic_h,
+                                           const hmx_sao_lcu *d_params, int n_lcu, const uint8_t *d_avail) {
+  if (!d_avail) return fail(c, HMX_ERR_ARG, "hmx_sao_picture_multi_avail: null argument");
+  return sao_picture_multi(c, "hmx_sao_picture_multi_avail", n_pics, in, out, pic_w, pic_h, d_params, n_lcu, d_avail);
 }
 extern "C" int hmx_sao_picture(hmx_ctx *c, const hmx_pic *in, const hmx_pic *out, int pic_w, int pic_h, const hmx_sao_lcu *d_params, int n_lcu) {
   return hmx_sao_picture_multi(c, 1, in, out, pic_w, pic_h, d_params, n_lcu);
@@ -483,6 +518,7 @@ struct SaoStatArgs {
   const PlanesDev *pics; // [n_pics] originals, then [n_pics] reconstructions
   hmx_sao_stat *out;
   int n_pics, pic_w, pic_h, ctu, B, lcu_based, n_lcu, cw;
+  const uint8_t *avail; // [n_pics][n_lcu] for the availability path (calcSaoStatsBlock), unused otherwise
 };
 __device__ __forceinline__ int sao_sign(int a, int b) { return min(max(a - b, -1), 1); }
 // samples x0-1 .. x0+8 of a row into r[0..9] (addresses clamped to the plane; what lies outside is masked off by the ranges)
@@ -528,6 +564,15 @@ __device__ __forceinline__ void sao_stats_solve(const int M[5], int D[5]) {
   const int P2 = (M[4] - M[2]) / 12, P1 = M[2] - 4 * P2, Q2 = (M[3] - M[1]) / 6, Q1 = M[1] - 2 * Q2;
   D[0] = (P2 - Q2) / 2, D[1] = (P1 - Q1) / 2, D[2] = M[0] - P1 - P2, D[3] = (P1 + Q1) / 2, D[4] = (P2 + Q2) / 2;
 }
+// bits k of the 8 columns x0 + k of a CTU row y whose two neighbours at -+(dx, dy) may both be read (calcSaoStatsBlock :571-815)
+__device__ __forceinline__ unsigned sao_pair_mask(unsigned a9, int x0, int y, int dx, int dy, int W, int H) {
+  unsigned m = 0;
+#pragma unroll
+  for (int k = 0; k < 8; k++)
+    m |= (unsigned)(x0 + k < W && sao_may_read(a9, x0 + k - dx, y - dy, W, H) && sao_may_read(a9, x0 + k + dx, y + dy, W, H)) << k;
+  return m;
+}
+template <bool AVAIL>
 __global__ __launch_bounds__(kSaoStatThreads) void k_sao_stats(SaoStatArgs A) {
   constexpr int kWaves = kSaoStatThreads / 64;
   __shared__ unsigned long long hist[kWaves][32];
@@ -546,6 +591,8 @@ __global__ __launch_bounds__(kSaoStatThreads) void k_sao_stats(SaoStatArgs A) {
   const int x0 = (t % strips) * 8, y0 = (t / strips) * rows;
   int mom[4][5] = {};
   unsigned cnt[4] = {0, 0, 0, 0};
+  unsigned a9 = 0;
+  if constexpr (AVAIL) a9 = sao_avail9(A.avail[(size_t)pic * A.n_lcu + lcu]);
   if (x0 < W && y0 < H) {
     const PlanesDev *O = A.pics + pic, *R = A.pics + A.n_pics + pic; // indexed in memory: a copy indexed by p would live in scratch
     const int gx = lx + x0, so = O->s[p], sr = R->s[p], bshift = A.B - 5;
@@ -577,14 +624,19 @@ __global__ __launch_bounds__(kSaoStatThreads) void k_sao_stats(SaoStatArgs A) {
 #pragma unroll
       for (int i = 0; i < 9; i++) g[i] = sao_sign(cur[i], cur[i + 1]); // sign(c_i - right)
       const bool vrow = y >= ys && y < ye_v;
-      const unsigned mb = y < ye_bo ? m_full : 0, m0 = y < ye_eo0 ? m_in : 0, m1 = vrow ? m_full : 0, m23 = vrow ? m_in : 0;
+      unsigned mb = y < ye_bo ? m_full : 0, m0 = y < ye_eo0 ? m_in : 0, m1 = vrow ? m_full : 0, m2 = vrow ? m_in : 0, m3 = m2;
+      if constexpr (AVAIL) { // no rows or columns skipped; the four edge masks from the neighbourhood
+        mb = sao_xmask(0, W, x0);
+        m0 = sao_pair_mask(a9, x0, y, 1, 0, W, H), m1 = sao_pair_mask(a9, x0, y, 0, 1, W, H);
+        m2 = sao_pair_mask(a9, x0, y, 1, 1, W, H), m3 = sao_pair_mask(a9, x0, y, -1, 1, W, H);
+      }
 #pragma unroll
       for (int k = 0; k < 8; k++) {
         const int i = k + 1, c = cur[i], diff = org[k] - c;
         sao_acc(mom[0], cnt[0], (m0 >> k) & 1, g[i] - g[i - 1], diff);
         sao_acc(mom[1], cnt[1], (m1 >> k) & 1, d1[i] - u1[i], diff);
-        sao_acc(mom[2], cnt[2], (m23 >> k) & 1, d2[i] - u2[i - 1], diff);
-        sao_acc(mom[3], cnt[3], (m23 >> k) & 1, d3[i] - u3[i + 1], diff);
+        sao_acc(mom[2], cnt[2], (m2 >> k) & 1, d2[i] - u2[i - 1], diff);
+        sao_acc(mom[3], cnt[3], (m3 >> k) & 1, d3[i] - u3[i + 1], diff);
         if ((mb >> k) & 1) atomicAdd(&hist[wave][(c >> bshift) & 31], (1ull << 40) + (unsigned long long)(long long)diff);
       }
 #pragma unroll
@@ -623,15 +675,55 @@ __global__ __launch_bounds__(kSaoStatThreads) void k_sao_stats(SaoStatArgs A) {
     for (int e = 0; e < 5; e++) out[5 * ty4 + cls[e]] = hmx_sao_stat{D[e], N[e]};
   }
 }
+// d_avail: null = calcSaoStatsCuOrg, else calcSaoStatsBlock with these availabilities (lcu_based is then 0: nothing is skipped)
+static int sao_stats_multi(hmx_ctx *c, const char *fn, int n_pics, const hmx_pic *org, const hmx_pic *rec, int pic_w, int pic_h, int lcu_based,
+                           const uint8_t *d_avail, hmx_sao_stat *d_out) {
+  if (!c || !org || !rec || !d_out) return fail(c, HMX_ERR_ARG, std::string(fn) + ": null argument");
+  const PlanesDev *d;
+  if (int r = multi_pics(c, fn, n_pics, multiple_of(pic_w, pic_h, 8), kMultipleOf8, org, rec, nullptr, planes_of, &d)) return r;
+  const int ctu = c->cfg.ctu_size, cw = (pic_w + ctu - 1) / ctu, n_lcu = cw * ((pic_h + ctu - 1) / ctu);
+  SaoStatArgs A{d, d_out, n_pics, pic_w, pic_h, ctu, c->cfg.bit_depth, lcu_based ? 1 : 0, n_lcu, cw, d_avail};
+  const dim3 grid((unsigned)n_lcu, 3, (unsigned)n_pics);
+  if (d_avail) hipLaunchKernelGGL(k_sao_stats<true>, grid, dim3(kSaoStatThreads), 0, c->stream, A);
+  else hipLaunchKernelGGL(k_sao_stats<false>, grid, dim3(kSaoStatThreads), 0, c->stream, A);
+  HIPCHK(c, hipGetLastError());
+  return HMX_OK;
+}
 extern "C" int hmx_sao_stats_multi(hmx_ctx *c, int n_pics, const hmx_pic *org, const hmx_pic *rec, int pic_w, int pic_h, int lcu_based,
                                    hmx_sao_stat *d_out) {
-  if (!c || !org || !rec || !d_out) return fail(c, HMX_ERR_ARG, "hmx_sao_stats_multi: null argument");
-  const PlanesDev *d;
-  if (int r = multi_pics(c, "hmx_sao_stats_multi", n_pics, multiple_of(pic_w, pic_h, 8), kMultipleOf8, org, rec, nullptr, planes_of, &d)) return r;
-  const int ctu = c->cfg.ctu_size, cw = (pic_w + ctu - 1) / ctu, n_lcu = cw * ((pic_h + ctu - 1) / ctu);
-  SaoStatArgs A{d, d_out, n_pics, pic_w, pic_h, ctu, c->cfg.bit_depth, lcu_based ? 1 : 0, n_lcu, cw};
-  hipLaunchKernelGGL(k_sao_stats, dim3((unsigned)n_lcu, 3, (unsigned)n_pics), dim3(kSaoStatThreads), 0, c->stream, A);
-  HIPCHK(c, hipGetLastError());
+  return sao_stats_multi(c, "hmx_sao_stats_multi", n_pics, org, rec, pic_w, pic_h, lcu_based, nullptr, d_out);
+}
+extern "C" int hmx_sao_stats_multi_avail(hmx_ctx *c, int n_pics, const hmx_pic *org, const hmx_pic *rec, int pic_w, int pic_h,
+                                         const uint8_t *d_avail, hmx_sao_stat *d_out) {
+  if (!d_avail) return fail(c, HMX_ERR_ARG, "hmx_sao_stats_multi_avail: null argument");
+  return sao_stats_multi(c, "hmx_sao_stats_multi_avail", n_pics, org, rec, pic_w, pic_h, 0, d_avail, d_out);
+}
+
+// ---- border availability of the loop filters (TComDataCU::setNDBFilterBlockBorderAvailability, TComDataCU.cpp:4212-4634, with
+// MODIFIED_CROSS_SLICE and REMOVE_FGS: one block per CTU).  Host only; no context.
+extern "C" int hmx_lf_border_avail(int pic_w, int pic_h, int ctu, const uint32_t *slice_id, const uint8_t *slice_lf_cross, int n_slices,
+                                   const uint32_t *tile_id, int lf_cross_tiles, uint8_t *avail) {
+  if (!slice_id || !slice_lf_cross || !avail || pic_w <= 0 || pic_h <= 0 || ctu <= 0 || n_slices <= 0) return HMX_ERR_ARG;
+  const int cw = (pic_w + ctu - 1) / ctu, ch = (pic_h + ctu - 1) / ctu;
+  for (int a = 0; a < cw * ch; a++)
+    if (slice_id[a] >= (uint32_t)n_slices) return HMX_ERR_ARG;
+  static const int kDx[8] = {-1, 1, 0, 0, -1, 1, -1, 1}, kDy[8] = {0, 0, -1, 1, -1, -1, 1, 1}; // SGU_L, R, T, B, TL, TR, BL, BR
+  for (int y = 0; y < ch; y++)
+    for (int x = 0; x < cw; x++) {
+      const int a = y * cw + x;
+      const uint32_t s = slice_id[a];
+      unsigned m = 0;
+      for (int k = 0; k < 8; k++) {
+        const int nx = x + kDx[k], ny = y + kDy[k];
+        if (nx < 0 || nx >= cw || ny < 0 || ny >= ch) continue; // bPic?Boundary
+        const int n = ny * cw + nx;
+        const uint32_t r = slice_id[n];
+        bool ok = n_slices == 1 || r == s || slice_lf_cross[r > s ? r : s]; // onlyOneSliceInPic; the later slice's flag (:4299)
+        if (!lf_cross_tiles && tile_id && tile_id[n] != tile_id[a]) ok = false; // :4589-4623
+        m |= (unsigned)ok << k;
+      }
+      avail[a] = (uint8_t)m;
+    }
   return HMX_OK;
 }
 extern "C" int hmx_sao_stats(hmx_ctx *c, const hmx_pic *org, const hmx_pic *rec, int pic_w, int pic_h, int lcu_based, hmx_sao_stat *d_out) {

@@ -5,16 +5,21 @@ order, with libhmx's own earlier outputs as reference pictures:
     inter coding units   hmx_batch_motionCompensation_multi, hmx_batch_invtransformNxN_multi
     intra coding units   hmx_frame_intra_decode (intra pictures) / hmx_frame_intra_decode_onto (inside inter pictures)
     loop filters         hmx_deblock_strengths_multi (inter pictures; intra pictures have strength 2 on every edge),
-                         hmx_deblock_picture_multi, hmx_sao_picture_multi (a decoder holds one picture at a time: batches of 1)
+                         hmx_deblock_picture_multi, hmx_sao_picture_multi (a decoder holds one picture at a time: batches of 1);
+                         with slice / tile boundaries the filters may not cross, the edges on them are dropped and SAO is
+                         hmx_sao_picture_multi_avail
     reference pictures   hmx_pic_extend_border
 
 A picture is a dict: poc, w, h, B, qp, ctu, slice_type (0 B, 1 P, 2 I), tus (hmx_tu records; flags bit 1 = block of
 an inter coding unit, bit 7 = luma coded-block flag), pus / cus (records of the tap), lev (three arrays in the
 reference's per-CTU coefficient layout), sao ([3][n_ctu] hmx_sao_lcu records), dbk ([disabled, beta_offset_div2,
 tc_offset_div2]), and the layout of its slices, tiles and constrained intra prediction: region (region id per CTU in
-raster order, or None: one region) and cip (constrained_intra_pred_flag).  load_pictures() reads the .npz fixtures of
-tests/golden/make_stream_golden.py and tests/golden/make_stream_layout_golden.py.  The numpy helpers
-import nothing of the GPU side; decode_sequence() needs libhmx."""
+raster order, or None: one region) and cip (constrained_intra_pred_flag).  For the loop filters: slice_id / tile_id (slice
+index in decoding order / tile index per CTU in raster order, or None: one slice / tile), lf_cross_slice (one
+slice_loop_filter_across_slices_enabled_flag per slice) and lf_cross_tile (loop_filter_across_tiles_enabled_flag); from these
+lf_border_avail() makes the byte per CTU that says which neighbour CTUs deblocking and SAO may read.  load_pictures() reads
+the .npz fixtures of tests/golden/make_stream_golden.py, make_stream_layout_golden.py and make_stream_lf_golden.py.  The
+numpy helpers import nothing of the GPU side; decode_sequence() needs libhmx."""
 import ctypes as C
 
 import numpy as np
@@ -45,7 +50,11 @@ def load_pictures(path):
         poc, w, h, B, qp, ctu, slice_type = (int(v) for v in d[f"hdr{i}"])
         yield dict(poc=poc, w=w, h=h, B=B, qp=qp, ctu=ctu, slice_type=slice_type, pus=d[f"pus{i}"], cus=d[f"cus{i}"], tus=d[f"tus{i}"], lev=[d[f"lev{i}_{k}"] for k in range(3)],
                    rec=[d[f"rec{i}_{k}"] for k in range(3)], org=[d[f"org{i}_{k}"] for k in range(3)] if f"org{i}_0" in d else None, sao=np.ascontiguousarray(d[f"sao{i}"]), dbk=[int(v) for v in d[f"dbk{i}"]],
-                   region=np.ascontiguousarray(d[f"region{i}"], np.uint32) if f"region{i}" in d else None, cip=bool(int(d[f"cip{i}"])) if f"cip{i}" in d else False)
+                   region=np.ascontiguousarray(d[f"region{i}"], np.uint32) if f"region{i}" in d else None, cip=bool(int(d[f"cip{i}"])) if f"cip{i}" in d else False,
+                   slice_id=np.ascontiguousarray(d[f"slice_id{i}"], np.uint32) if f"slice_id{i}" in d else None,
+                   tile_id=np.ascontiguousarray(d[f"tile_id{i}"], np.uint32) if f"tile_id{i}" in d else None,
+                   lf_cross_slice=np.ascontiguousarray(d[f"lf_cross_slice{i}"], np.uint8) if f"lf_cross_slice{i}" in d else None,
+                   lf_cross_tile=bool(int(d[f"lf_cross_tile{i}"])) if f"lf_cross_tile{i}" in d else True)
 
 
 def tile_scan(cw, ch, col_bounds, row_bounds):
@@ -81,6 +90,73 @@ def region_map(w, h, ctu, slice_starts=(0,), col_bounds=(0,), row_bounds=(0,)):
     return region
 
 
+def slice_tile_maps(w, h, ctu, slice_starts=(0,), col_bounds=(0,), row_bounds=(0,)):
+    """(slice index, tile index) of every CTU in raster order; arguments as for region_map."""
+    cw, ch = -(-w // ctu), -(-h // ctu)
+    order, tile = tile_scan(cw, ch, col_bounds, row_bounds)
+    starts = np.array(sorted(set(int(s) for s in slice_starts) | {0}), np.int64)
+    sl = np.searchsorted(starts, np.arange(cw * ch), side="right") - 1
+    slice_id, tile_id = np.zeros(cw * ch, np.uint32), np.zeros(cw * ch, np.uint32)
+    slice_id[order], tile_id[order] = sl.astype(np.uint32), tile.astype(np.uint32)
+    return slice_id, tile_id
+
+
+# neighbour CTU k of the availability byte, (dx, dy): the SGU_* enumeration (COM/TComDataCU.h:64-72)
+SGU_L, SGU_R, SGU_T, SGU_B, SGU_TL, SGU_TR, SGU_BL, SGU_BR = range(8)
+SGU_OFFSETS = ((-1, 0), (1, 0), (0, -1), (0, 1), (-1, -1), (1, -1), (-1, 1), (1, 1))
+
+
+def lf_border_avail(w, h, ctu, slice_id=None, slice_lf_cross=None, tile_id=None, lf_cross_tiles=True):
+    """The numpy twin of hmx_lf_border_avail (TComDataCU::setNDBFilterBlockBorderAvailability, COM/TComDataCU.cpp:4212-4634
+    with MODIFIED_CROSS_SLICE): one byte per CTU in raster order, bit k set = neighbour CTU k may be read.  A neighbour
+    outside the picture: no.  Same slice: yes; a later slice: that slice's flag; an earlier slice: this slice's flag; one
+    slice in the picture: no slice test.  Then ANDed with "same tile" when lf_cross_tiles is false.  slice_id None = one
+    slice: the mask of the picture's geometry alone."""
+    cw, ch = -(-w // ctu), -(-h // ctu)
+    sid = np.zeros((ch, cw), np.int64) if slice_id is None else np.asarray(slice_id, np.int64).reshape(ch, cw)
+    flags = np.ones(1, bool) if slice_lf_cross is None else np.asarray(slice_lf_cross).astype(bool).reshape(-1)
+    if sid.min() < 0 or sid.max() >= len(flags):
+        raise ValueError("lf_border_avail: slice id without a flag")
+    tid = None if tile_id is None else np.asarray(tile_id, np.int64).reshape(ch, cw)
+    out = np.zeros((ch, cw), np.uint8)
+    ys, xs = np.mgrid[0:ch, 0:cw]
+    for k, (dx, dy) in enumerate(SGU_OFFSETS):
+        ny, nx = ys + dy, xs + dx
+        inside = (ny >= 0) & (ny < ch) & (nx >= 0) & (nx < cw)
+        ny, nx = np.clip(ny, 0, ch - 1), np.clip(nx, 0, cw - 1)
+        other = sid[ny, nx]
+        ok = inside & ((len(flags) == 1) | (other == sid) | flags[np.maximum(other, sid)])
+        if tid is not None and not lf_cross_tiles:
+            ok &= tid[ny, nx] == tid
+        out |= (ok.astype(np.uint8) << k).astype(np.uint8)
+    return out.reshape(-1)
+
+
+def picture_avail(p):
+    """The availability bytes of a picture dict (the geometry's alone without slice / tile maps)."""
+    return lf_border_avail(p["w"], p["h"], p["ctu"], p.get("slice_id"), p.get("lf_cross_slice"), p.get("tile_id"), p.get("lf_cross_tile", True))
+
+
+def avail_is_geometry(p, avail):
+    """True when every bit of a neighbour inside the picture is set: the loop filters cross every CTU boundary."""
+    return np.array_equal(avail, lf_border_avail(p["w"], p["h"], p["ctu"]))
+
+
+def _drop_closed_edges(p, ver, hor):
+    """Clears the vertical-edge entries in the first unit column of a CTU whose L bit is clear and the horizontal-edge
+    entries in the first unit row of a CTU whose T bit is clear (COM/TComLoopFilter.cpp:411, 432: getPULeft / getPUAbove
+    return no unit across a slice or tile boundary the filter may not cross; the left and top neighbours are never in a
+    later slice, so the SAO byte serves).  ver / hor: [4x4 unit row][4x4 unit column], modified in place."""
+    avail = picture_avail(p)
+    n, cw = p["ctu"] // 4, -(-p["w"] // p["ctu"])
+    for a, m in enumerate(avail):
+        cy, cx = divmod(a, cw)
+        if cx and not (m >> SGU_L) & 1:
+            ver[cy * n:(cy + 1) * n, cx * n] = 0
+        if cy and not (m >> SGU_T) & 1:
+            hor[cy * n, cx * n:(cx + 1) * n] = 0
+
+
 def intra_unit_map(p):
     """The intra flag of every 4x4 luma unit of a picture, from its coding units (constrained intra prediction)."""
     uw, uh = -(-p["w"] // 4), -(-p["h"] // 4)
@@ -114,6 +190,7 @@ def deblock_maps(p):
             bsv[y:y + n, x] = 2
         if y and y % 2 == 0:
             bsh[y, x:x + n] = 2
+    _drop_closed_edges(p, bsv, bsh)
     return bsv, bsh, np.full((uh, uw), p["qp"], np.int8)
 
 
@@ -153,6 +230,7 @@ def strength_inputs(p):
                 units["mv"][y:y + ht, x:x + wd, l, 0] = int(u[f"mv{l}x"])
                 units["mv"][y:y + ht, x:x + wd, l, 1] = int(u[f"mv{l}y"])
         sides(x, y, wd, ht, 1)
+    _drop_closed_edges(p, ev, eh)
     return np.ascontiguousarray(units), ev, eh
 
 
@@ -261,7 +339,13 @@ def decode_sequence(pics):
                 d_out = capi.DevPicture(ctx, w, h, m, m).zero()
                 d_prm = ctx.to_device(p["sao"])
                 assert p["sao"].shape[1] == -(-w // p["ctu"]) * -(-h // p["ctu"])
-                ctx.sao_pictures([d_rec], [d_out], w, h, d_prm)
+                avail = picture_avail(p)
+                if avail_is_geometry(p, avail):
+                    ctx.sao_pictures([d_rec], [d_out], w, h, d_prm)
+                else:  # a slice or tile boundary the filter may not cross: processSaoBlock
+                    d_av = ctx.to_device(avail)
+                    ctx.sao_pictures_avail([d_rec], [d_out], w, h, d_prm, d_av)
+                    keep += [d_av]
             ctx._chk(L.hmx_pic_extend_border(ctx.h, C.byref(d_out.as_pic()), w, h, m, m))
             ctx.sync()
             refs[p["poc"]] = d_out

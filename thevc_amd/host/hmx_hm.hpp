@@ -504,17 +504,44 @@ private:
   Context &m_c;
 };
 
-// TEncSampleAdaptiveOffset, the statistics pass (TEncSampleAdaptiveOffset.cpp:859-1124, calcSaoStatsCuOrg with SAO_SKIP_RIGHT):
-// one call for every CTU and component of a picture, on the device; the parameter search (rdoSaoUnitAll's offset estimation,
-// distortion, merge and rates) stays with the caller and reads the downloaded bins through ctuStats.
+// TComSampleAdaptiveOffset, the application (TComSampleAdaptiveOffset.cpp:515-1240): SAOProcess for a whole picture on the
+// device.  createPicSaoInfo (:491-505) decides m_bUseNIF per picture; here the caller sets the availability bytes of
+// hmx_lf_border_avail (device, one per CTU) for a picture with a slice or tile boundary the filters may not cross, and
+// processSaoCu's dispatch (:515-548) follows: with bytes set the block path (processSaoBlock), otherwise processSaoCuOrg.
+class TComSampleAdaptiveOffset {
+public:
+  explicit TComSampleAdaptiveOffset(Context &c) : m_c(c) {}
+  void createPicSaoInfo(const uint8_t *d_borderAvail) { m_dAvail = d_borderAvail, m_bUseNIF = d_borderAvail != nullptr; }
+  void destroyPicSaoInfo() { m_dAvail = nullptr, m_bUseNIF = false; }
+  // in (deblocked), out: device pictures; d_params (device): [component][CTU in raster order], merges resolved
+  void SAOProcess(const hmx_pic *in, const hmx_pic *out, Int picWidth, Int picHeight, const hmx_sao_lcu *d_params, Int numLcu) {
+    if (!m_bUseNIF) m_c.check(hmx_sao_picture(m_c.get(), in, out, picWidth, picHeight, d_params, numLcu), "SAOProcess");
+    else m_c.check(hmx_sao_picture_multi_avail(m_c.get(), 1, in, out, picWidth, picHeight, d_params, numLcu, m_dAvail), "SAOProcess (NIF)");
+  }
+
+private:
+  Context &m_c;
+  const uint8_t *m_dAvail = nullptr;
+  Bool m_bUseNIF = false;
+};
+
+// TEncSampleAdaptiveOffset, the statistics pass (TEncSampleAdaptiveOffset.cpp:859-1124, calcSaoStatsCuOrg with SAO_SKIP_RIGHT;
+// :571-854, calcSaoStatsBlock, when m_bUseNIF): one call for every CTU and component of a picture, on the device; the parameter
+// search (rdoSaoUnitAll's offset estimation, distortion, merge and rates) stays with the caller and reads the downloaded bins
+// through ctuStats.
 typedef long long Int64;
 class TEncSampleAdaptiveOffset {
 public:
   explicit TEncSampleAdaptiveOffset(Context &c) : m_c(c) {}
-  // org, rec (deblocked): device pictures; d_out (device): [component][CTU in raster order][HMX_SAO_STAT_BINS]
+  // as TComSampleAdaptiveOffset::createPicSaoInfo: the availability bytes of a picture on the NIF path, or nullptr
+  void createPicSaoInfo(const uint8_t *d_borderAvail) { m_dAvail = d_borderAvail, m_bUseNIF = d_borderAvail != nullptr; }
+  void destroyPicSaoInfo() { m_dAvail = nullptr, m_bUseNIF = false; }
+  // org, rec (deblocked): device pictures; d_out (device): [component][CTU in raster order][HMX_SAO_STAT_BINS].  calcSaoStatsCu's
+  // dispatch (:816-854): the block path skips no rows or columns, so lcuBasedOptimization plays no part in it
   void calcSaoStatsPicture(const hmx_pic *org, const hmx_pic *rec, Int picWidth, Int picHeight, Bool lcuBasedOptimization,
                            hmx_sao_stat *d_out) {
-    m_c.check(hmx_sao_stats(m_c.get(), org, rec, picWidth, picHeight, lcuBasedOptimization ? 1 : 0, d_out), "calcSaoStatsPicture");
+    if (!m_bUseNIF) m_c.check(hmx_sao_stats(m_c.get(), org, rec, picWidth, picHeight, lcuBasedOptimization ? 1 : 0, d_out), "calcSaoStatsPicture");
+    else m_c.check(hmx_sao_stats_multi_avail(m_c.get(), 1, org, rec, picWidth, picHeight, m_dAvail, d_out), "calcSaoStatsPicture (NIF)");
   }
   // adds one CTU's downloaded bins to m_iOffsetOrg / m_iCount [SAO_EO_0..3, SAO_BO][MAX_NUM_SAO_CLASS] of that CTU, which
   // rdoSaoUnitAll clears before each CTU (the reference's calcSaoStatsCu accumulates the same way)
@@ -526,6 +553,8 @@ public:
 
 private:
   Context &m_c;
+  const uint8_t *m_dAvail = nullptr;
+  Bool m_bUseNIF = false;
 };
 
 } // namespace hmx_hm

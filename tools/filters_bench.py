@@ -1,6 +1,7 @@
 """Throughput of the picture-level kernels either side of the chain on one 2160p picture set: deblocking (strengths +
 application), SAO, YUV unpack / pack: picture by picture and, for the loop filters, the whole set in one call.  Every line is
-the median of --repeats timings with their min..max.  With HMX_LIB_PATH naming an older build of the library the batched
+the median of --repeats timings with their min..max; the last line is SAO on the availability path (hmx_sao_picture_multi_avail)
+with the mask of 4 x 4 tiles that the filters may not cross.  With HMX_LIB_PATH naming an older build of the library the batched
 lines are left out: its per-picture lines are the baseline of DESIGN.md section 5."""
 import argparse
 import ctypes as C
@@ -93,3 +94,10 @@ if hasattr(L, "hmx_deblock_picture_multi"):  # the NP pictures in one call each,
     line(f"deblock picture, {NP} a call", t, f"  ({6 * px / np.median(t) / 1e9:.0f} GB/s of 2 B read + 2 B written per sample)")
     t = timed(lambda: ctx.sao_pictures(pics, outs, w, h, m_sao))
     line(f"SAO, {NP} a call", t, f"  ({6 * px / np.median(t) / 1e9:.0f} GB/s of 2 B read + 2 B written per sample)")
+if hasattr(L, "hmx_sao_picture_multi_avail"):  # the same with loop filters that stop at the boundaries of 4 x 4 tiles
+    from thevc_amd import decisions
+    _, tile_id = decisions.slice_tile_maps(w, h, 64, (0,), decisions.uniform_bounds(60, 4), decisions.uniform_bounds(34, 4))
+    avail = decisions.lf_border_avail(w, h, 64, tile_id=tile_id, lf_cross_tiles=False)
+    m_avail = ctx.to_device(np.ascontiguousarray(np.broadcast_to(avail, (NP, n_lcu))))
+    t = timed(lambda: ctx.sao_pictures_avail(pics, outs, w, h, m_sao, m_avail))
+    line(f"SAO avail, {NP} a call", t, f"  ({6 * px / np.median(t) / 1e9:.0f} GB/s of 2 B read + 2 B written per sample)")
