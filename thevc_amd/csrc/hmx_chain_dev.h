@@ -40,6 +40,7 @@ struct OwnPicture {
   static constexpr bool kWriteThrough = false;
   static constexpr bool kSse = false; // distortion output: packed schedule only
   static constexpr bool kRdoq = false; // RDOQ as the chain's quantiser: packed schedule only
+  static constexpr int kPredOpt = 0;   // kPredPairs | kPredMainRef, the batched forms of intra_pred_samples and build_main_ref (hmx_device.h): packed schedule only
   const PicWork &W;
   const FTu *tus;
   __device__ __forceinline__ void wait() const {}
@@ -55,6 +56,7 @@ struct AcrossPictures {
   static constexpr bool kWriteThrough = false;
   static constexpr bool kSse = false;
   static constexpr bool kRdoq = false;
+  static constexpr int kPredOpt = 0;
   __device__ __forceinline__ void wait() const {}
   const PicWork *pics;
   const FTu *ft; // the one block this wave works on (wave-uniform address: scalar loads)
@@ -116,7 +118,7 @@ __device__ __forceinline__ void wave_chain_valu(char *smem, const SRC &src, cons
     const bool filt = N > 4 && luma && use_filtered_refs(t.mode, Log2<N>::v);
     intra_refs_tiled<N, N, SRC::kCoherent>(L, gl, active, R, x, y, pb0, luma, avail, pads, filt, P);
     HMX_MARK(N, 3);
-    intra_pred_block_sel<N>(L, gl, t.mode, luma, filt, wave_needs(t.mode == 1), P, pred);
+    intra_pred_block_sel<N, SRC::kPredOpt>(L, gl, t.mode, luma, filt, wave_needs(t.mode == 1), P, pred);
     HMX_MARK(N, 4);
     if (ENC) {
 #pragma unroll
@@ -222,9 +224,10 @@ __device__ __forceinline__ void wave_chain_8x2(char *smem, const SRC &src, const
   {
     const int *RL = filt ? L.fline : L.line;
     const int dcs = wave_needs(t.mode == 1) ? dc_sum_block<N, NL>(L, gl) : 0; // only when a block of the wave is DC
-    build_main_ref<N, NL>(RL, L.me, t.mode, gl);
+    static_assert(sizeof(L.me) >= main_ref_words(N) * sizeof(int), "the general path may read me[3N + 1]");
+    build_main_ref<N, NL, SRC::kPredOpt>(RL, L.me, t.mode, gl);
     wave_sync();
-    intra_pred_samples<N, 16>(RL, L.me, t.mode, luma, B, dcs, [&](int s) { return r0 + (s >> 3); }, [](int s) { return s & 7; }, pred);
+    intra_pred_samples<N, 16, SRC::kPredOpt>(RL, L.me, t.mode, luma, B, dcs, [&](int s) { return r0 + (s >> 3); }, [](int s) { return s & 7; }, pred);
     wave_sync(); // the main reference shares the tile's memory
   }
   HMX_MARK(82, 4);
@@ -863,9 +866,10 @@ __device__ __forceinline__ void wave_chain_32(char *smem, const SRC &src, const 
     HMX_MARK(32, 3);
     const int *RL = filt ? L.fline : L.line;
     const int dcs = wave_needs(t.mode == 1) ? dc_sum_block<32, 64>(L, lane) : 0;
-    build_main_ref<32, 64>(RL, L.me, t.mode, lane);
+    static_assert(sizeof(L.me) >= main_ref_words(32) * sizeof(int), "the general path may read me[3N + 1]");
+    build_main_ref<32, 64, SRC::kPredOpt>(RL, L.me, t.mode, lane);
     wave_sync();
-    intra_pred_samples<32, 16>(RL, L.me, t.mode, luma, P.bit_depth, dcs, [&](int) { return r; }, [&](int s) { return mrow(s, h); }, pred);
+    intra_pred_samples<32, 16, SRC::kPredOpt>(RL, L.me, t.mode, luma, P.bit_depth, dcs, [&](int) { return r; }, [&](int s) { return mrow(s, h); }, pred);
     const bool zlev = V.lev_stride == 0;
     int *lev0 = V.lev + (zlev ? b0 + r : __umul24((unsigned)y, (unsigned)V.lev_stride) + x + r);
     const int lstep = zlev ? 32 : V.lev_stride;
@@ -1350,6 +1354,9 @@ struct PackedSrc {
   static constexpr bool kWriteThrough = false; // producers and consumers share an XCD's L2: plain stores
   static constexpr bool kSse = SSE;            // a kernel variant of its own: the extra live registers would spill in the common one
   static constexpr bool kRdoq = RDOQ;          // likewise (doubles, and the 4x4 lane's private arrays)
+  // the batched general angular path (kPredPairs, intra_pred_samples) and main reference (kPredMainRef, build_main_ref); the SSE and RDOQ variants have no register to spare and spill with
+  // them (vgpr_spill_count 0 -> 2 and 0 -> 4): they keep the plain forms
+  static constexpr int kPredOpt = (RDOQ || SSE) ? 0 : kPredPairs | kPredMainRef;
   __device__ __forceinline__ bool want_sse() const { return SSE; }
   __device__ __forceinline__ int picture() const { return pic0 + (int)(ft.t.plane >> 2); }
   __device__ __forceinline__ int cbf_ctx() const { return (ft.t.flags >> 4) & 15; } // hmx_tu::flags bits 4..7

@@ -51,6 +51,9 @@ __device__ __forceinline__ int clip3(int lo, int hi, int v) { return min(max(v, 
 __device__ __forceinline__ int mul24(int a, int b) { return __mul24(a, b); }
 __device__ __forceinline__ unsigned umul24(unsigned a, unsigned b) { return __umul24(a, b); }
 __device__ __forceinline__ int wrap16(int v) { return (int)(short)v; }
+// a - b as its low 17 bits, sign-extended (one v_bfe_i32): the difference itself for int16 a and b, and a value the instruction
+// selector knows to fit 24 bits, whatever the words hold
+__device__ __forceinline__ int diff17(int a, int b) { return (int)(((unsigned)a - (unsigned)b) << 15) >> 15; }
 
 // ---------------------------------------------------------------------------------------------
 // 1-D transforms on register arrays (raw sums, no rounding)
@@ -565,6 +568,41 @@ __device__ __forceinline__ bool use_filtered_refs(int mode, int log2n) { // TCom
   return min(abs(mode - 10), abs(mode - 26)) > thr;
 }
 
+// An empty instruction that reads and "rewrites" K values (addresses, or the destinations of loads) held in vector registers:
+// every one of them is complete in a register of its own at this point, and nothing that uses one can move above it.
+template <int K, typename V>
+__device__ __forceinline__ void pin_regs(V *v) {
+  if constexpr (K == 1) asm volatile("" : "+v"(v[0]));
+  else if constexpr (K == 2) asm volatile("" : "+v"(v[0]), "+v"(v[1]));
+  else if constexpr (K == 3) asm volatile("" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]));
+  else if constexpr (K == 4) asm volatile("" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]));
+  else if constexpr (K == 5) asm volatile("" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]));
+  else if constexpr (K == 6) asm volatile("" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]));
+  else {
+    pin_regs<6>(v);
+    pin_regs<K - 6>(v + 6);
+  }
+}
+// K words of an LDS array at run-time indices, read back to back between two pins: every index is complete before the first
+// read, every read has a register of its own, and ONE wait stands behind the last (LDS returns in order; the waits the compiler
+// puts in front of the second pin's pieces have no read between them).  Left to itself the compiler waits behind every read.
+template <int K>
+__device__ __forceinline__ void lds_gather(const int *base, int *idx, int *v) {
+  pin_regs<K>(idx);
+#pragma unroll
+  for (int k = 0; k < K; k++) v[k] = base[idx[k]];
+  pin_regs<K>(v);
+}
+// The same for K adjacent pairs base[idx], base[idx + 1]: one two-word read each
+template <int K>
+__device__ __forceinline__ void lds_gather_pairs(const int *base, int *idx, int *v0, int *v1) {
+  pin_regs<K>(idx);
+#pragma unroll
+  for (int k = 0; k < K; k++) v0[k] = base[idx[k]], v1[k] = base[idx[k] + 1];
+  pin_regs<K>(v0);
+  pin_regs<K>(v1);
+}
+
 // Angular parameters of a mode (TComPrediction.cpp:196-210)
 struct AngParam {
   bool ver;
@@ -592,29 +630,63 @@ __device__ __forceinline__ AngParam ang_param(int mode) {
 // k >= 0: the main reference (above for vertical modes, left for horizontal ones); k < 0 (negative
 // angles only, down to (N*angle)>>5): the side reference projected with the inverse angle.
 // NL lanes of the block fill it together.  R = reference line (top(k) = R[2N+k], left(k) = R[2N-k]).
-template <int N, int NL>
+// OPT (what a caller asks of the prediction, a mask; 0 = the forms every kernel but the packed chain's uses):
+//   kPredPairs    the general angular path reads all its tap pairs in one batch (intra_pred_samples)
+//   kPredMainRef  this routine fully unrolled in three phases, as the padding pass of refs_gather_pad: every source index without a
+//                 branch, all the reads back to back (lds_gather), then the writes, predicated for the entries outside (lim, last];
+//                 an entry that is not written reads the corner, R[2N].  As a run-time loop every entry is a read, a wait and a write.
+constexpr int kPredPairs = 1, kPredMainRef = 2;
+template <int N, int NL, int OPT = 0>
 __device__ __forceinline__ void build_main_ref(const int *R, int *ME, int mode, int gl) {
   if (mode < 2) return;
   const AngParam a = ang_param(mode);
   const int lim = a.angle < 0 ? (N * a.angle) >> 5 : 0, last = a.angle < 0 ? N : 2 * N;
-  for (int e = gl; e <= 3 * N; e += NL) {
-    const int k = e - N;
-    if (k > last || (k < 0 && k <= lim)) continue;
-    int v;
-    if (k >= 0)
-      v = a.ver ? R[2 * N + k] : R[2 * N - k];
-    else {
-      const int j = (128 + mul24(-k, a.inv_angle)) >> 8; // k >= -32, inv_angle <= 4096
-      v = a.ver ? R[2 * N - j] : R[2 * N + j];
+  if constexpr (!(OPT & kPredMainRef)) {
+    for (int e = gl; e <= 3 * N; e += NL) {
+      const int k = e - N;
+      if (k > last || (k < 0 && k <= lim)) continue;
+      int v;
+      if (k >= 0)
+        v = a.ver ? R[2 * N + k] : R[2 * N - k];
+      else {
+        const int j = (128 + mul24(-k, a.inv_angle)) >> 8; // k >= -32, inv_angle <= 4096
+        v = a.ver ? R[2 * N - j] : R[2 * N + j];
+      }
+      ME[e] = (short)v;
     }
-    ME[e] = (short)v;
+    return;
   }
+  constexpr int IT = (3 * N + 1 + NL - 1) / NL;
+  int q[IT], v[IT];
+  bool on[IT];
+  // inv_angle <= 4096 and 0 < -k <= N where j is used: the masks change nothing and show the instruction selector a 24-bit
+  // product (the table value reaches it through a register whose range it does not know: the half-rate v_mad_u64_u32 otherwise)
+  int inv = a.inv_angle;
+  asm("" : "+v"(inv));
+  inv &= 0x1fff;
+#pragma unroll
+  for (int it = 0; it < IT; it++) {
+    const int e = gl + it * NL, k = e - N;
+    // gl < NL: the sign of k is a compile-time fact for most trips (all of them where NL divides N)
+    const bool neg = (it + 1) * NL <= N ? true : it * NL >= N ? false : k < 0;
+    on[it] = ((it + 1) * NL <= 3 * N + 1 || e <= 3 * N) && (neg ? k > lim : k <= last);
+    const int j = (128 + mul24(-k & (2 * N - 1), inv)) >> 8;
+    const int off = neg ? -j : k; // projected onto the side reference, or along the main one
+    q[it] = on[it] ? (a.ver ? 2 * N + off : 2 * N - off) : 2 * N;
+  }
+  lds_gather<IT>(R, q, v);
+#pragma unroll
+  for (int it = 0; it < IT; it++)
+    if (on[it]) ME[gl + it * NL] = (short)v[it];
 }
 
 // NS samples of the N x N prediction (TComPrediction.cpp:129-386, 689-730, 1010-1029):
 // p[s] = pred(row(s), col(s)).  R = reference line (raw or smoothed), ME = extended main reference
 // built from the same line (angular modes), dc_sum = sum of the N above and N left neighbours.
-template <int N, int NS, typename RowFn, typename ColFn>
+// Words of a block's extended main reference that the prediction may READ: ME[0 .. 3N + 1] (the general path reads one past the
+// 3N + 1 entries build_main_ref can write, see there)
+constexpr int main_ref_words(int n) { return 3 * n + 2; }
+template <int N, int NS, int OPT = 0, typename RowFn, typename ColFn>
 __device__ __forceinline__ void intra_pred_samples(const int *R, const int *ME, int mode, bool luma, int bit_depth, int dc_sum,
                                                    RowFn row, ColFn col, int *p) {
   constexpr int LOG2N = N == 4 ? 2 : N == 8 ? 3 : N == 16 ? 4 : N == 32 ? 5 : 6;
@@ -632,6 +704,8 @@ __device__ __forceinline__ void intra_pred_samples(const int *R, const int *ME, 
   }
   if (mode == 1) { // DC (+ edge smoothing for luma, any size)
     const int dc = (dc_sum + N) >> (LOG2N + 1);
+    // (the edge smoothing stays a branch per sample, here and in the pure path below: formed for every sample from batched reads
+    // and taken with a select, the two measured 0.6 % SLOWER on the mixed workload -- DESIGN.md section 5)
 #pragma unroll
     for (int s = 0; s < NS; s++) {
       const int r = row(s), c = col(s);
@@ -662,14 +736,39 @@ __device__ __forceinline__ void intra_pred_samples(const int *R, const int *ME, 
     }
     return;
   }
+  if constexpr (!(OPT & kPredPairs)) {
+#pragma unroll
+    for (int s = 0; s < NS; s++) {
+      const int r = row(s), c = col(s);
+      const int k = a.ver ? r : c, l = a.ver ? c : r;
+      const int pos = mul24(k + 1, a.angle), di = pos >> 5, df = pos & 31; // k < 32, |angle| <= 32
+      const int i = l + di + 1;
+      const int m0 = M0[i];
+      p[s] = df ? (short)((mul24(32 - df, m0) + mul24(df, M0[i + 1]) + 16) >> 5) : m0; // samples: at most 12 bits
+    }
+    return;
+  }
+  // The general path in three phases: (a) every sample's index and weight, (b) the pairs M0[i], M0[i + 1] of all NS samples read
+  // back to back with one wait behind them (lds_gather_pairs), (c) the two-tap form for every sample, with no select on df.  It is
+  // exact: with df = 0 it gives (32 * m0 + 16) >> 5 = m0 for every int16 m0, whatever M0[i + 1] holds.  That read is one the
+  // reference does not make; it reaches M0[2N + 1] = ME[3N + 1] (modes 2 and 34, last row: di = N), which the callers keep inside
+  // the wave's scratch.  The operands are 24-bit by construction (diff17, df < 32): v_mul_i32_i24 / v_mad_i32_i24, where
+  // operands without a known range took the half-rate v_mad_u64_u32.
+  int idx[NS], df[NS], m0[NS], m1[NS];
 #pragma unroll
   for (int s = 0; s < NS; s++) {
     const int r = row(s), c = col(s);
     const int k = a.ver ? r : c, l = a.ver ? c : r;
-    const int pos = mul24(k + 1, a.angle), di = pos >> 5, df = pos & 31; // k < 32, |angle| <= 32
-    const int i = l + di + 1;
-    const int m0 = M0[i];
-    p[s] = df ? (short)((mul24(32 - df, m0) + mul24(df, M0[i + 1]) + 16) >> 5) : m0; // samples: at most 12 bits
+    const int pos = mul24(k + 1, a.angle); // k < 32, |angle| <= 32
+    idx[s] = l + (pos >> 5) + 1;
+    df[s] = pos & 31;
+  }
+  lds_gather_pairs<NS>(M0, idx, m0, m1);
+#pragma unroll
+  for (int s = 0; s < NS; s++) {
+    // (32 - df) * m0 + df * m1 = 32 * m0 + df * (m1 - m0); the result lies between m0 and m1: no wrap to 16 bits to apply.
+    // m0 and m1 are int16 (build_main_ref), their difference has 17 bits; a word m1 that is no sample meets df = 0
+    p[s] = ((m0[s] << 5) + 16 + mul24(df[s], diff17(m1[s], m0[s]))) >> 5;
   }
 }
 

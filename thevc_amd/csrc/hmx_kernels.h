@@ -473,21 +473,7 @@ __device__ __forceinline__ int mask_top(unsigned m) { return 31 - __clz((int)m);
 __device__ __forceinline__ int mask_top(unsigned long long m) { return 63 - __clzll((long long)m); }
 __device__ __forceinline__ int mask_first(unsigned m) { return __ffs((int)m) - 1; }
 __device__ __forceinline__ int mask_first(unsigned long long m) { return __ffsll((long long)m) - 1; }
-// An empty instruction that reads and "rewrites" K values (addresses, or the destinations of loads) held in vector registers:
-// every one of them is complete in a register of its own at this point, and nothing that uses one can move above it.
-template <int K, typename V>
-__device__ __forceinline__ void pin_regs(V *v) {
-  if constexpr (K == 1) asm volatile("" : "+v"(v[0]));
-  else if constexpr (K == 2) asm volatile("" : "+v"(v[0]), "+v"(v[1]));
-  else if constexpr (K == 3) asm volatile("" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]));
-  else if constexpr (K == 4) asm volatile("" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]));
-  else if constexpr (K == 5) asm volatile("" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]));
-  else if constexpr (K == 6) asm volatile("" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]));
-  else {
-    pin_regs<6>(v);
-    pin_regs<K - 6>(v + 6);
-  }
-}
+// (pin_regs, the empty instruction that keeps a batch of loads together, is in hmx_device.h)
 template <int N, int NL, bool COH, typename M, typename LT>
 __device__ __forceinline__ void refs_gather_pad(LT &L, int gl, bool active, const TiledPlane &R, int x, int y, const short *idle, bool luma,
                                                 M avail, bool pad_pass, int bit_depth) {
@@ -593,13 +579,14 @@ __device__ __forceinline__ int dc_sum_block(const LT &L, int gl) {
 
 // filt = predict from the smoothed line; need_dc (wave-uniform) = form the DC sum: its shuffles are executed by every lane of the
 // wave.  The whole-picture chains pass what they evaluated for intra_refs_tiled and form the sum only when a block of the wave is DC.
-template <int N>
+template <int N, int OPT = 0>
 __device__ __forceinline__ void intra_pred_block_sel(TuLds<N> &L, int gl, int mode, bool luma, bool filt, bool need_dc, const PicDev &P, int *p) {
+  static_assert(sizeof(L.me) >= main_ref_words(N) * sizeof(int), "the general path may read me[3N + 1]");
   const int *R = filt ? L.fline : L.line;
   const int dcs = need_dc ? dc_sum_block<N, N>(L, gl) : 0;
-  build_main_ref<N, N>(R, L.me, mode, gl);
+  build_main_ref<N, N, OPT>(R, L.me, mode, gl);
   wave_sync();
-  intra_pred_samples<N, N>(R, L.me, mode, luma, P.bit_depth, dcs, [&](int) { return gl; }, [](int s) { return s; }, p);
+  intra_pred_samples<N, N, OPT>(R, L.me, mode, luma, P.bit_depth, dcs, [&](int) { return gl; }, [](int s) { return s; }, p);
   wave_sync(); // L.me is rebuilt by the next call (mode fan-out)
 }
 // luma: edge filters of the angular/DC modes (bFilter) and, unless raw_line, the smoothed reference line
