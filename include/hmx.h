@@ -378,6 +378,13 @@ unsigned long long hmx_intra_dependency_mask(int n_samples, int is_luma, int mod
  * whole-picture chains skip it (the plans carry this bit per block and sort by it).  An empty availability gives 1, and so does a
  * size or mode the function does not know.  Pure host function. */
 int hmx_intra_reads_unavailable(int n_samples, int is_luma, int mode, unsigned long long avail);
+/* 1 when hmx_intra_reads_unavailable is 1 and no unavailable unit the mode reads lies strictly between the lowest and the highest
+ * unit of hmx_intra_dependency_mask(.., avail), or that mask is empty: the unavailable units read are a leading run, a trailing run
+ * or both, and the padded reference line is raw[clamp(p, lo, hi)] at every position the mode reads, lo / hi being the first sample
+ * of the mask's lowest unit / the last sample of its highest (an empty mask: the mid value everywhere).  0 when a read unit is
+ * missing BETWEEN units of the mask (slices, tiles, constrained intra prediction), when nothing is missing, and for a size or mode
+ * the function does not know.  The plans carry this bit per block next to the one above.  Pure host function. */
+int hmx_intra_pads_simple(int n_samples, int is_luma, int mode, unsigned long long avail);
 /* The availability flags of initAdiPattern for a block at luma position (x, y) of luma size size_luma (a chroma block: its
  * luma-scaled position and size), CTU size 64: bit u in the bNeighborFlags order, units of four luma samples.  closed_form 0:
  * the unit-by-unit rule (TComPattern.cpp:607-786); 1: the closed form the device plan builder uses.  Pure host functions,
@@ -425,6 +432,10 @@ void hmx_intra_plan_destroy_many(hmx_ctx *ctx, hmx_intra_plan *const *plans, int
  * levels[n_levels] = per dependency level {uint32 start[4], count[4]} by transform size (4, 8, 16, 32), starts into blocks.
  * Either pointer may be NULL. */
 int hmx_intra_plan_download(hmx_ctx *ctx, const hmx_intra_plan *plan, void *blocks, void *levels);
+/* The two bits a plan keeps per block beside the mask, which hmx_intra_plan_download leaves out: bits[i] for block i of its sorted
+ * list, bit 0 = hmx_intra_reads_unavailable, bit 1 = hmx_intra_pads_simple of the block's availability.  For tests that hold a
+ * device-built plan against a host-built one. */
+int hmx_intra_plan_pad_bits(hmx_ctx *ctx, const hmx_intra_plan *plan, unsigned char *bits);
 /* Size of the dependency schedules of a plan: blocks, picture-wide dependency levels (= launches of
  * the level schedule) and CTU diagonals (= launches of the wave schedule). */
 int hmx_intra_plan_info(const hmx_intra_plan *plan, int *n_blocks, int *n_levels, int *n_diagonals);

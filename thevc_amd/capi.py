@@ -264,11 +264,16 @@ def lib():
         if hasattr(L, "hmx_intra_reads_unavailable"):  # (absent from an older build loaded for an A/B run)
             L.hmx_intra_reads_unavailable.argtypes = [ci, ci, ci, C.c_uint64]
             L.hmx_intra_reads_unavailable.restype = ci
+        if hasattr(L, "hmx_intra_pads_simple"):
+            L.hmx_intra_pads_simple.argtypes = [ci, ci, ci, C.c_uint64]
+            L.hmx_intra_pads_simple.restype = ci
         L.hmx_intra_avail_mask.argtypes = [ci, ci, ci, ci, ci, ci]
         L.hmx_intra_avail_mask.restype = C.c_uint64
         L.hmx_intra_plan_create_multi.argtypes = [vp, C.POINTER(vp), C.POINTER(ci), ci, C.POINTER(PicParam), C.POINTER(vp)]
         L.hmx_intra_plan_create_device.argtypes = [vp, vp, C.POINTER(C.c_uint32), ci, C.POINTER(PicParam), C.POINTER(vp)]
         L.hmx_intra_plan_download.argtypes = [vp, vp, vp, vp]
+        if hasattr(L, "hmx_intra_plan_pad_bits"):
+            L.hmx_intra_plan_pad_bits.argtypes = [vp, vp, vp]
         LP = C.POINTER(AvailLayout)
         L.hmx_intra_avail_mask_layout.argtypes = [ci, ci, ci, ci, ci, LP]
         L.hmx_intra_avail_mask_layout.restype = C.c_uint64
@@ -742,6 +747,14 @@ class Context:
         levels = np.zeros((nl.value, 8), np.uint32)
         self._chk(lib().hmx_intra_plan_download(self.h, plan, _hp(blocks), _hp(levels)))
         return blocks, levels
+
+    def plan_pad_bits(self, plan):
+        """hmx_intra_plan_pad_bits: per block of plan_tables' list, bit 0 = the block pads, bit 1 = its padding is a clamp"""
+        nb = C.c_int()
+        lib().hmx_intra_plan_info(plan, C.byref(nb), None, None)
+        bits = np.zeros(nb.value, np.uint8)
+        self._chk(lib().hmx_intra_plan_pad_bits(self.h, plan, _hp(bits)))
+        return bits
 
     def pack_tables(self):
         """hmx_last_call_pack_tables: the packed schedule's tables of the last whole-picture call as (geom, hdr, rows, descs,

@@ -311,7 +311,7 @@ extern "C" int hmx_last_call_pack_tables(hmx_ctx *c, hmx_pack_geom *geom, void *
   if (descs && h[8]) HIPCHK(c, hipMemcpy(descs, pk.d_descs, sizeof(PackDesc) * h[8], hipMemcpyDeviceToHost));
   if (items && h[9]) {
     HIPCHK(c, hipMemcpy(items, pk.d_items, sizeof(FTu) * h[9], hipMemcpyDeviceToHost));
-    for (uint32_t i = 0; i < h[9]; i++) static_cast<FTu *>(items)[i].avail_hi &= ~kFtuPads; // the caller gets the mask alone
+    for (uint32_t i = 0; i < h[9]; i++) static_cast<FTu *>(items)[i].avail_hi &= ~kFtuFlagBits; // the caller gets the mask alone
   }
   if (done && n_rows) // word 0 of every row's 128-byte counter line
     HIPCHK(c, hipMemcpy2D(done, sizeof(uint32_t), pk.d_done, sizeof(uint32_t) * kDoneStride, sizeof(uint32_t), n_rows, hipMemcpyDeviceToHost));

@@ -41,6 +41,7 @@ struct OwnPicture {
   static constexpr bool kSse = false; // distortion output: packed schedule only
   static constexpr bool kRdoq = false; // RDOQ as the chain's quantiser: packed schedule only
   static constexpr int kPredOpt = 0;   // kPredPairs | kPredMainRef, the batched forms of intra_pred_samples and build_main_ref (hmx_device.h): packed schedule only
+  static constexpr bool kPadClamp = true; // the index-clamp form of the padding pass (refs_gather_pad)
   const PicWork &W;
   const FTu *tus;
   __device__ __forceinline__ void wait() const {}
@@ -51,12 +52,17 @@ struct OwnPicture {
     return PlaneView{as_global(W.org[pl].p), r, as_global(W.lev[pl]), W.lev_stride[pl]};
   }
 };
+// The CTU-wave schedule keeps the general pass: its encoder kernel is out of registers (22 spilled before), and the clamp's arm cost two more
+struct OwnPictureWave : OwnPicture {
+  static constexpr bool kPadClamp = false;
+};
 struct AcrossPictures {
   static constexpr bool kCoherent = false;
   static constexpr bool kWriteThrough = false;
   static constexpr bool kSse = false;
   static constexpr bool kRdoq = false;
   static constexpr int kPredOpt = 0;
+  static constexpr bool kPadClamp = true;
   __device__ __forceinline__ void wait() const {}
   const PicWork *pics;
   const FTu *ft; // the one block this wave works on (wave-uniform address: scalar loads)
@@ -102,8 +108,8 @@ __device__ __forceinline__ void wave_chain_valu(char *smem, const SRC &src, cons
     const int pl = t.plane, x = t.x, y = t.y;
     const bool luma = pl == 0, ts = t.flags & HMX_TU_TRANSFORM_SKIP;
     const int scan_idx = coef_scan_idx(N, luma, true, t.mode);
-    const unsigned long long avail = (unsigned long long)ft.avail_lo | ((unsigned long long)(ft.avail_hi & ~kFtuPads) << 32);
-    const bool pads = ft.avail_hi & kFtuPads;
+    const unsigned long long avail = (unsigned long long)ft.avail_lo | ((unsigned long long)(ft.avail_hi & ~kFtuFlagBits) << 32);
+    const bool pads = ft.avail_hi & kFtuPads, simple = ft.avail_hi & kFtuPadsSimple;
     const PlaneView V = src.view(active ? i : 0, pl);
     const TiledPlane &R = V.rec;
     const unsigned b0 = tile_base(R.ctu_w, R.clog, x, y); // same geometry for org and rec
@@ -116,7 +122,7 @@ __device__ __forceinline__ void wave_chain_valu(char *smem, const SRC &src, cons
     src.wait(); // packed schedule: the blocks this one predicts from belong to earlier rows of the same launch
     HMX_MARK(N, 2);
     const bool filt = N > 4 && luma && use_filtered_refs(t.mode, Log2<N>::v);
-    intra_refs_tiled<N, N, SRC::kCoherent>(L, gl, active, R, x, y, pb0, luma, avail, pads, filt, P);
+    intra_refs_tiled<N, N, SRC::kCoherent, SRC::kPadClamp>(L, gl, active, R, x, y, pb0, luma, avail, pads, simple, filt, P);
     HMX_MARK(N, 3);
     intra_pred_block_sel<N, SRC::kPredOpt>(L, gl, t.mode, luma, filt, wave_needs(t.mode == 1), P, pred);
     HMX_MARK(N, 4);
@@ -202,8 +208,8 @@ __device__ __forceinline__ void wave_chain_8x2(char *smem, const SRC &src, const
   const int pl = t.plane, x = t.x, y = t.y;
   const bool luma = pl == 0, ts = t.flags & HMX_TU_TRANSFORM_SKIP;
   const int scan_idx = coef_scan_idx(N, luma, true, t.mode);
-  const unsigned long long avail = (unsigned long long)ft.avail_lo | ((unsigned long long)(ft.avail_hi & ~kFtuPads) << 32);
-  const bool pads = ft.avail_hi & kFtuPads;
+  const unsigned long long avail = (unsigned long long)ft.avail_lo | ((unsigned long long)(ft.avail_hi & ~kFtuFlagBits) << 32);
+  const bool pads = ft.avail_hi & kFtuPads, simple = ft.avail_hi & kFtuPadsSimple;
   const PlaneView V = src.view(active ? slot : 0, pl);
   const TiledPlane &R = V.rec;
   const unsigned b0 = tile_base(R.ctu_w, R.clog, x, y);
@@ -219,7 +225,7 @@ __device__ __forceinline__ void wave_chain_8x2(char *smem, const SRC &src, const
   src.wait();
   HMX_MARK(82, 2);
   const bool filt = luma && use_filtered_refs(t.mode, LG);
-  intra_refs_tiled<N, NL, SRC::kCoherent>(L, gl, active, R, x, y, pb0, luma, avail, pads, filt, P);
+  intra_refs_tiled<N, NL, SRC::kCoherent, SRC::kPadClamp>(L, gl, active, R, x, y, pb0, luma, avail, pads, simple, filt, P);
   HMX_MARK(82, 3);
   {
     const int *RL = filt ? L.fline : L.line;
@@ -532,6 +538,11 @@ __device__ __forceinline__ void lane4_inverse(const int *lv, bool use_dst, bool 
   }
 }
 
+template <int P>
+__device__ __forceinline__ void clamp_positions(int *q, int lo, int hi) { // q[p] = clamp(p, lo, hi), p = 0..P: the position is an inline constant
+  q[P] = med3k<P>(lo, hi);
+  if constexpr (P > 0) clamp_positions<P - 1>(q, lo, hi);
+}
 template <bool ENC, bool ONCE = false, typename SRC>
 __device__ __forceinline__ void wave_chain_4_lane(char *smem, const SRC &src, const PicDev &P, int count) {
   Lane4Lds &LS = *reinterpret_cast<Lane4Lds *>(smem);
@@ -547,7 +558,9 @@ __device__ __forceinline__ void wave_chain_4_lane(char *smem, const SRC &src, co
     const bool luma = pl == 0, ts = t.flags & HMX_TU_TRANSFORM_SKIP;
     const unsigned avail = ft.avail_lo; // 4n+1 <= 9 units
     // wave-uniform: the padding loops run only when a block of the wave reads an unavailable unit, the DC sum when one is DC
-    const bool pad_pass = wave_needs(active && (ft.avail_hi & kFtuPads)), any_dc = wave_needs(mode == 1);
+    // (and the general loops only when a padding block of the wave lacks kFtuPadsSimple: see intra_refs_tiled)
+    const bool pads = active && (ft.avail_hi & kFtuPads), any_dc = wave_needs(mode == 1);
+    const int pad_pass = !wave_needs(pads) ? kPadNone : (!SRC::kPadClamp || HMX_X_REFS == 2 || __any(pads && !(ft.avail_hi & kFtuPadsSimple))) ? kPadGeneral : kPadClamp;
     const PlaneView V = src.view(active ? i : 0, pl);
     const TiledPlane &R = V.rec;
     const unsigned b0 = tile_base(R.ctu_w, R.clog, x, y);
@@ -679,7 +692,24 @@ __device__ __forceinline__ void wave_chain_4_lane(char *smem, const SRC &src, co
         }
         wave_sync(); // the reference lines take the scratch
       }
-      if (!pad_pass) { // every position a mode of this wave reads holds its own sample (see intra_refs_tiled)
+      if (pad_pass == kPadNone) { // every position a mode of this wave reads holds its own sample (see intra_refs_tiled)
+#pragma unroll
+        for (int p = 0; p <= 16; p++) line[p] = raw[p];
+      } else if (pad_pass == kPadClamp) {
+        // line[p] = raw[clamp(p, lo, hi)] (refs_gather_pad).  The samples are in registers, and a register array indexed at run time
+        // would live in scratch memory: they go through the lane's LDS line -- raw in, clamped out, every read before the first
+        // write back.  A median and an address per position: 34 VALU instructions, against 52 for selects unit by unit.
+        const unsigned some = avail ? avail : 1u;
+        const int df = mask_first(some) - 2 * n, dt = mask_top(some) - 2 * n;
+        const int lo = df < 0 ? 8 + (int)((unsigned)df << ul) : (df == 0 ? 8 : 9 + (int)((unsigned)(df - 1) << ul));
+        const int hi = !avail ? 0 : dt < 0 ? 8 + (int)((unsigned)dt << ul) + (1 << ul) - 1 : 8 + (int)((unsigned)dt << ul);
+        raw[0] = avail ? raw[0] : 1 << (B - 1); // no unit at all: lo = hi = 0, every position reads the mid value there
+#pragma unroll
+        for (int p = 0; p <= 16; p++) line[p] = raw[p];
+        int q[17];
+        clamp_positions<16>(q, lo, hi);
+        lds_gather<9>(line, q, raw);
+        lds_gather<8>(line, q + 9, raw + 9);
 #pragma unroll
         for (int p = 0; p <= 16; p++) line[p] = raw[p];
       } else {
@@ -844,8 +874,8 @@ __device__ __forceinline__ void wave_chain_32(char *smem, const SRC &src, const 
     const hmx_tu t = ft.t;
     const int pl = t.plane, x = t.x, y = t.y;
     const bool luma = pl == 0;
-    const unsigned long long avail = (unsigned long long)ft.avail_lo | ((unsigned long long)(ft.avail_hi & ~kFtuPads) << 32);
-    const bool pads = ft.avail_hi & kFtuPads;
+    const unsigned long long avail = (unsigned long long)ft.avail_lo | ((unsigned long long)(ft.avail_hi & ~kFtuFlagBits) << 32);
+    const bool pads = ft.avail_hi & kFtuPads, simple = ft.avail_hi & kFtuPadsSimple;
     const PlaneView V = src.view(i, pl);
     const TiledPlane &R = V.rec;
     const unsigned b0 = tile_base(R.ctu_w, R.clog, x, y);
@@ -862,7 +892,7 @@ __device__ __forceinline__ void wave_chain_32(char *smem, const SRC &src, const 
     src.wait();
     HMX_MARK(32, 2);
     const bool filt = luma && use_filtered_refs(t.mode, LG);
-    intra_refs_tiled<32, 64, SRC::kCoherent>(L, lane, true, R, x, y, tphys(R.qstride, b0), luma, avail, pads, filt, P);
+    intra_refs_tiled<32, 64, SRC::kCoherent, SRC::kPadClamp>(L, lane, true, R, x, y, tphys(R.qstride, b0), luma, avail, pads, simple, filt, P);
     HMX_MARK(32, 3);
     const int *RL = filt ? L.fline : L.line;
     const int dcs = wave_needs(t.mode == 1) ? dc_sum_block<32, 64>(L, lane) : 0;
@@ -1084,7 +1114,7 @@ __global__ __launch_bounds__(64, 4) void k_intra_wave(FrameArgs A) {
     // a new dependency level gathers references from the reconstruction written by the previous one
     if (sg.new_level) wave_global_sync();
     wave_sync(); // the LDS scratch is re-interpreted per block size
-    const OwnPicture src{W, tus};
+    const OwnPictureWave src{{W, tus}};
     switch (sg.log2n) {
     case 2: wave_chain_4_lane<ENC>(smem, src, A.P, sg.count); break;
     case 3: wave_chain_valu<8, ENC>(smem, src, A.P, sg.count); break;
@@ -1357,6 +1387,7 @@ struct PackedSrc {
   // the batched general angular path (kPredPairs, intra_pred_samples) and main reference (kPredMainRef, build_main_ref); the SSE and RDOQ variants have no register to spare and spill with
   // them (vgpr_spill_count 0 -> 2 and 0 -> 4): they keep the plain forms
   static constexpr int kPredOpt = (RDOQ || SSE) ? 0 : kPredPairs | kPredMainRef;
+  static constexpr bool kPadClamp = true;
   __device__ __forceinline__ bool want_sse() const { return SSE; }
   __device__ __forceinline__ int picture() const { return pic0 + (int)(ft.t.plane >> 2); }
   __device__ __forceinline__ int cbf_ctx() const { return (ft.t.flags >> 4) & 15; } // hmx_tu::flags bits 4..7

@@ -45,6 +45,20 @@ __host__ __device__ constexpr int dst_coef(int k, int n) {
 }
 
 __device__ __forceinline__ int clip3(int lo, int hi, int v) { return min(max(v, lo), hi); }
+// The median of three in one instruction (v_med3_i32): with lo <= hi it is clip3(lo, hi, v).  The compiler forms it from min(max())
+// only when both bounds are constants.  med3k: v is a constant the instruction takes inline (-16 .. 64).
+__device__ __forceinline__ int med3i(int v, int lo, int hi) {
+  int r;
+  asm("v_med3_i32 %0, %1, %2, %3" : "=v"(r) : "v"(v), "v"(lo), "v"(hi));
+  return r;
+}
+template <int K>
+__device__ __forceinline__ int med3k(int lo, int hi) {
+  static_assert(K >= -16 && K <= 64, "an inline constant");
+  int r;
+  asm("v_med3_i32 %0, %1, %2, %3" : "=v"(r) : "n"(K), "v"(lo), "v"(hi));
+  return r;
+}
 // Full-rate integer multiplies (v_mul_i32_i24 / v_mad_i32_i24 / v_mul_u32_u24; the plain 32-bit multiply
 // v_mul_lo_u32 is a quarter-rate instruction).  Both operands must fit 24 bits; the result is the
 // exact low 32 bits of the product.  Every use states why its operands fit.

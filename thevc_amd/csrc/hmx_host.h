@@ -120,11 +120,17 @@ struct Seg { // a run of same-size blocks of one dependency level of one (CTU, p
 };
 struct FTu { // block descriptor of the frame path: geometry + precomputed neighbour availability
   hmx_tu t;
-  uint32_t avail_lo, avail_hi; // the mask has at most 33 bits; bit 31 of avail_hi is kFtuPads
+  uint32_t avail_lo, avail_hi; // the mask has at most 33 bits; bits 31 / 30 of avail_hi are kFtuPads / kFtuPadsSimple
 };
 // FTu::avail_hi: the block's mode reads a unit that is not available (hmx_intra_reads_unavailable), so its reference line needs
 // the padding pass.  Without the bit every position the mode reads holds a gathered sample and the chains skip the pass.
 constexpr uint32_t kFtuPads = 1u << 31;
+// FTu::avail_hi, only with kFtuPads: no unavailable unit the mode reads lies strictly between the lowest and the highest unit of the
+// mask (or the mask is empty), so the padding rule is line[p] = raw[clamp(p, lo, hi)] with lo / hi the first sample of the lowest /
+// the last sample of the highest unit of the mask (hmx_intra_pads_simple).  Holes between available units --
+// slices, tiles, constrained intra prediction -- clear it, and the block takes the general pass.
+constexpr uint32_t kFtuPadsSimple = 1u << 30;
+constexpr uint32_t kFtuFlagBits = kFtuPads | kFtuPadsSimple; // what is not mask in avail_hi
 struct LevelRow { // blocks of one picture-wide dependency level, bucketed by size (log2n - 2)
   uint32_t start[4];
   uint32_t count[4];
@@ -414,6 +420,7 @@ int pack_group_size(const hmx_ctx *c, int n_pics);
 int launch_op(hmx_ctx *c, int op, int log2n, const ListArgs &A);                  // hmx_list.hip
 unsigned long long intra_dependency_mask(int n_s, bool luma, int mode, unsigned long long avail); // hmx_plan.hip
 bool intra_reads_unavailable(int n_s, bool luma, int mode, unsigned long long avail);             // hmx_plan.hip
+bool intra_pads_simple(int n_s, bool luma, int mode, unsigned long long avail);                  // hmx_plan.hip
 int plan_host_tables(hmx_ctx *c, const hmx_intra_plan *pl); // device-built plan: fetch the level table for the level schedule / queries
 // a slice / tile / CIP layout (hmx_avail_layout) checked against the picture and packed for intra_avail_mask_layout; H.D points
 // into H's vectors (host use), layout_to_device puts a copy of the maps in the argument arena (device use)   // hmx_plan.hip

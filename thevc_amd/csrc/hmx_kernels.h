@@ -463,6 +463,9 @@ __device__ __forceinline__ void intra_refs(TuLds<N> &L, int gl, bool active, Fet
 //   the padding pass   pads = the block's mode reads a unit outside the mask (FTu's kFtuPads).  Without it every position the mode
 //                      reads holds its own gathered sample, the rule is the identity there, and the samples go straight into L.line;
 //                      the other positions keep whatever the stand-in load returned, and no mode looks at them;
+//   its general form   simple = every unit the block's mode reads outside the mask lies below the mask's lowest or above its highest
+//                      unit (FTu's kFtuPadsSimple: any block without slices, tiles or constrained intra prediction).  While every
+//                      padding block of the wave is simple the pass is one index clamp per position;
 //   the smoothed line  smooth = the block predicts from L.fline (use_filtered_refs, luma, N > 4);
 //   64-bit masks       M = unsigned wherever the 4n+1 units fit 32 bits (N <= 8, 16x16 luma).
 #ifndef HMX_X_REFS
@@ -474,9 +477,10 @@ __device__ __forceinline__ int mask_top(unsigned long long m) { return 63 - __cl
 __device__ __forceinline__ int mask_first(unsigned m) { return __ffs((int)m) - 1; }
 __device__ __forceinline__ int mask_first(unsigned long long m) { return __ffsll((long long)m) - 1; }
 // (pin_regs, the empty instruction that keeps a batch of loads together, is in hmx_device.h)
+enum { kPadNone = 0, kPadClamp = 1, kPadGeneral = 2 }; // the wave's padding pass: none, the index clamp, the general rule
 template <int N, int NL, bool COH, typename M, typename LT>
 __device__ __forceinline__ void refs_gather_pad(LT &L, int gl, bool active, const TiledPlane &R, int x, int y, const short *idle, bool luma,
-                                                M avail, bool pad_pass, int bit_depth) {
+                                                M avail, int pad_pass, int bit_depth) {
   constexpr int T = 2 * N + 1 + N / 2, IT = (T + NL - 1) / NL;
   const int ul = luma ? 2 : 1, n = N >> ul;
   // Phase 1: the addresses of the lane's IT units, without a branch -- a unit past T, outside the mask or of a lane without a
@@ -520,12 +524,45 @@ __device__ __forceinline__ void refs_gather_pad(LT &L, int gl, bool active, cons
     wave_sync();
     return;
   }
-  if (active) put(L.fline); // raw samples wait in L.fline (free until the smoothing pass)
+  if (active) {
+    put(L.fline); // raw samples wait in L.fline (free until the smoothing pass)
+    // the clamp of a block without any unit reads position 0 alone (lo = hi = 0): the mid value goes there, once per block instead of
+    // a select per position (the block's lanes store the same word)
+    if (pad_pass == kPadClamp && !avail) {
+      int bd = bit_depth; // made HERE (see quant_sbh_block): hoisted out of the persistent loop the value lived in scratch memory
+      asm volatile("" : "+v"(bd));
+      L.fline[0] = 1 << (bd - 1);
+    }
+  }
   wave_sync();
+  constexpr int ITP = (4 * N + 1 + NL - 1) / NL;
+  if (pad_pass == kPadClamp) {
+    // every padding block of the wave has kFtuPadsSimple: the units of its mask are all the mode reads between the lowest and the
+    // highest of them, so position p copies raw[clamp(p, lo, hi)] -- the first sample of the lowest unit for a leading run, the last
+    // sample of the highest unit for a trailing one, its own sample in between.  A block that does not pad
+    // reads only inside [lo, hi], where the clamp is the identity.
+    if (active) {
+      const int unit = 1 << ul;
+      const M some = avail ? avail : M(1); // no unit at all: lo = 0
+      const int df = mask_first(some) - 2 * n, dt = mask_top(some) - 2 * n;
+      const int lo = df < 0 ? 2 * N + (int)((unsigned)df << ul) : (df == 0 ? 2 * N : 2 * N + 1 + (int)((unsigned)(df - 1) << ul));
+      const int hi = !avail ? 0 : dt < 0 ? 2 * N + (int)((unsigned)dt << ul) + unit - 1 : 2 * N + (int)((unsigned)dt << ul);
+      int q[ITP], val[ITP];
+#pragma unroll
+      for (int it = 0; it < ITP; it++) q[it] = med3i(gl + it * NL, lo, hi); // (a position past 4N clamps into the line as well)
+      lds_gather<ITP>(L.fline, q, val);
+#pragma unroll
+      for (int it = 0; it < ITP; it++) {
+        const int p = gl + it * NL;
+        if ((it + 1) * NL <= 4 * N + 1 || p <= 4 * N) L.line[p] = val[it];
+      }
+    }
+    wave_sync();
+    return;
+  }
   if (active) {
     // every position's source is read before the first position is written: written one by one, each read waited for the
     // write before it (the compiler cannot tell L.fline[q] from L.line[p])
-    constexpr int ITP = (4 * N + 1 + NL - 1) / NL;
     const int unit = 1 << ul, dcv = 1 << (bit_depth - 1);
     const M some = avail ? avail : M(1); // no unit at all: the positions take dcv, the reads below only have to stay inside the line
     int val[ITP];
@@ -550,15 +587,16 @@ __device__ __forceinline__ void refs_gather_pad(LT &L, int gl, bool active, cons
   }
   wave_sync();
 }
-template <int N, int NL, bool COH, typename LT>
+template <int N, int NL, bool COH, bool CLAMP = true, typename LT> // CLAMP = false: a kernel that keeps the general pass for every padding wave
 __device__ __forceinline__ void intra_refs_tiled(LT &L, int gl, bool active, const TiledPlane &R, int x, int y, size_t pb0,
-                                                 bool luma, unsigned long long avail, bool pads, bool smooth, const PicDev &P) {
+                                                 bool luma, unsigned long long avail, bool pads, bool simple, bool smooth, const PicDev &P) {
   // loads of units outside the mask name ONE address in the whole wave (the first lane's block: a valid address in any picture's
   // pool), which the memory pipe serves as a single request
   const short *own = R.p + pb0;
   const short *idle = reinterpret_cast<const short *>((uintptr_t)(((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)((uintptr_t)own >> 32)) << 32) |
                                                                  (unsigned)__builtin_amdgcn_readfirstlane((int)(uintptr_t)own)));
-  const bool pad_pass = wave_needs(active && pads);
+  // pads / simple: FTu's kFtuPads / kFtuPadsSimple.  The general rule runs only when a padding block of the wave lacks the simple bit.
+  const int pad_pass = !wave_needs(active && pads) ? kPadNone : (!CLAMP || HMX_X_REFS == 2 || __any(active && pads && !simple)) ? kPadGeneral : kPadClamp;
   if (N <= 8 || (N == 16 && __all(luma))) // 4n+1 <= 17 units; 32x32 luma and 16x16 chroma have 33
     refs_gather_pad<N, NL, COH, unsigned>(L, gl, active, R, x, y, idle, luma, (unsigned)avail, pad_pass, P.bit_depth);
   else

@@ -113,6 +113,23 @@ bool intra_reads_unavailable(int n_s, bool luma, int mode, unsigned long long av
 extern "C" int hmx_intra_reads_unavailable(int n_samples, int is_luma, int mode, unsigned long long avail) {
   return intra_reads_unavailable(n_samples, is_luma != 0, mode, avail) ? 1 : 0;
 }
+// The padding rule as an index clamp (FTu's kFtuPadsSimple): the units read and missing are all below the lowest or above the highest
+// unit of the stored mask.  A missing unit below the mask's lowest unit is a leading run (first available sample), one above its
+// highest repeats that unit's last sample; only one in between needs the nearest-unit search of the general pass.
+static bool pads_simple_of(unsigned long long dep, unsigned long long miss) {
+  if (!dep) return true;
+  const unsigned long long upto_top = (2ull << (63 - __builtin_clzll(dep))) - 1ull, below_first = (dep & (0 - dep)) - 1ull;
+  return (miss & upto_top & ~below_first) == 0;
+}
+bool intra_pads_simple(int n_s, bool luma, int mode, unsigned long long avail) {
+  if ((n_s != 4 && n_s != 8 && n_s != 16 && n_s != 32) || mode < 0 || mode > 34) return false; // the general pass
+  if (!luma && n_s == 32) return false;
+  const unsigned long long miss = intra_reach_mask(n_s, luma, mode) & ~avail;
+  return miss != 0 && pads_simple_of(intra_dependency_mask(n_s, luma, mode, avail), miss);
+}
+extern "C" int hmx_intra_pads_simple(int n_samples, int is_luma, int mode, unsigned long long avail) {
+  return intra_pads_simple(n_samples, is_luma != 0, mode, avail) ? 1 : 0;
+}
 
 // A slice / tile / CIP layout checked against the picture and packed for intra_avail_mask_layout (hmx_device.h): the region map as
 // it is, the intra flags as two bitmaps (along unit rows and along unit columns).  NULL maps: nothing to pack, H.D is all NULL and
@@ -196,8 +213,8 @@ static const char *plan_build_host(const hmx_ctx *c, const hmx_tu *tus, int n_tu
   std::vector<FTu> stus;
   stus.reserve(n_tu);
   std::vector<unsigned long long> masks(n_tu), deps(n_tu);
-  std::vector<uint8_t> pads(n_tu); // the mode reads an unavailable unit: FTu's kFtuPads
-  auto desc_of = [&](int i) { return FTu{tus[i], (uint32_t)deps[i], (uint32_t)(deps[i] >> 32) | (pads[i] ? kFtuPads : 0u)}; };
+  std::vector<uint8_t> pads(n_tu); // bit 0: the mode reads an unavailable unit (FTu's kFtuPads); bit 1: its padding is a clamp (kFtuPadsSimple)
+  auto desc_of = [&](int i) { return FTu{tus[i], (uint32_t)deps[i], (uint32_t)(deps[i] >> 32) | (pads[i] & 1 ? kFtuPads : 0u) | (pads[i] & 2 ? kFtuPadsSimple : 0u)}; };
   std::vector<Seg> segs;
   std::vector<uint32_t> seg_range((size_t)n_ctu * 3 * 2);
   std::vector<int> level(n_tu);
@@ -212,7 +229,7 @@ static const char *plan_build_host(const hmx_ctx *c, const hmx_tu *tus, int n_tu
       unsigned long long m = intra_avail_mask(lx, ly, ls, P);
       if (use_layout) m = intra_avail_mask_layout(m, lx, ly, ls, 2, lay.D); // a subset: the schedules below stay valid
       masks[id] = m;
-      pads[id] = intra_reads_unavailable(1 << t.log2n, t.plane == 0, t.mode, m);
+      pads[id] = (intra_reads_unavailable(1 << t.log2n, t.plane == 0, t.mode, m) ? 1 : 0) | (intra_pads_simple(1 << t.log2n, t.plane == 0, t.mode, m) ? 2 : 0);
       m = intra_dependency_mask(1 << t.log2n, t.plane == 0, t.mode, m); // the order follows what the mode reads
       deps[id] = m;
       int lv = 0;
@@ -317,7 +334,7 @@ static const char *plan_build_host(const hmx_ctx *c, const hmx_tu *tus, int n_tu
     auto mode_class = [](int m) { return m == 0 ? 0 : m == 1 ? 1 : (m == 10 || m == 26) ? 2 : (m > 10 && m < 26) ? 3 : 4; };
     auto path_key = [&](int i) {
       const hmx_tu &t = tus[i];
-      return (uint32_t)((t.plane ? 1u : 0u) << 24 | (uint32_t)(t.flags & 1u) << 20 | (pads[i] ? 1u : 0u) << 19 |
+      return (uint32_t)((t.plane ? 1u : 0u) << 24 | (uint32_t)(t.flags & 1u) << 20 | (pads[i] & 1 ? 1u : 0u) << 19 |
                         (uint32_t)mode_class(t.mode) << 16 | (uint32_t)t.mode << 8);
     };
     // one 64-bit key per block (level | size | path | coding order): a plain sort of integers, no comparator that chases indices
@@ -686,8 +703,12 @@ __global__ __launch_bounds__(256) void k_plan_ctus(const hmx_tu *tus, const uint
         unsigned long long avail = intra_avail_mask_fast(lx, ly, ls, G.P);
         if constexpr (LAYOUT) avail = intra_avail_mask_layout(avail, lx, ly, ls, 2, lays[pic]);
         const unsigned long long dep = plan_dep_mask(need, t.log2n, t.plane == 0, t.mode, avail);
-        const bool pads = t.mode > 34 || (t.plane != 0 && t.log2n == 5) || (need[((t.log2n - 2) * 2 + (t.plane == 0 ? 1 : 0)) * 35 + t.mode] & ~avail) != 0; // intra_reads_unavailable
-        ftu[b0 + i] = FTu{t, (uint32_t)dep, (uint32_t)(dep >> 32) | (pads ? kFtuPads : 0u)}; // the descriptor as the chain wants it (plan_build_host: the units read stand for the availability), moved into place by k_plan_gather
+        const bool known = t.mode <= 34 && !(t.plane != 0 && t.log2n == 5);
+        const unsigned long long miss = known ? need[((t.log2n - 2) * 2 + (t.plane == 0 ? 1 : 0)) * 35 + t.mode] & ~avail : 0ull;
+        const bool pads = !known || miss != 0; // intra_reads_unavailable
+        bool simple = known && miss != 0;      // intra_pads_simple: no missing unit between the lowest and the highest unit of dep
+        if (simple && dep) simple = (miss & ((2ull << (63 - __clzll((long long)dep))) - 1ull) & ~((dep & (0 - dep)) - 1ull)) == 0;
+        ftu[b0 + i] = FTu{t, (uint32_t)dep, (uint32_t)(dep >> 32) | (pads ? kFtuPads : 0u) | (simple ? kFtuPadsSimple : 0u)}; // the descriptor as the chain wants it (plan_build_host: the units read stand for the availability), moved into place by k_plan_gather
         rec[b0 + i] = dep | (unsigned long long)((lx & 63) >> 2) << 40 | (unsigned long long)((ly & 63) >> 2) << 44 | (unsigned long long)(ls >> 2) << 48 |
                       (unsigned long long)t.plane << 52 | (unsigned long long)(t.log2n - 2) << 54;
       }
@@ -1314,9 +1335,19 @@ extern "C" int hmx_intra_plan_download(hmx_ctx *c, const hmx_intra_plan *pl, voi
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (blocks) {
     HIPCHK(c, hipMemcpy(blocks, pl->d_ltus, sizeof(FTu) * (size_t)pl->n_tu, hipMemcpyDeviceToHost));
-    for (int i = 0; i < pl->n_tu; i++) static_cast<FTu *>(blocks)[i].avail_hi &= ~kFtuPads; // the caller gets the mask alone
+    for (int i = 0; i < pl->n_tu; i++) static_cast<FTu *>(blocks)[i].avail_hi &= ~kFtuFlagBits; // the caller gets the mask alone
   }
   if (levels) HIPCHK(c, hipMemcpy(levels, pl->d_ltab, sizeof(LevelRow) * (size_t)pl->n_levels, hipMemcpyDeviceToHost));
+  return HMX_OK;
+}
+
+// test hook: what hmx_intra_plan_download strips -- per block of the sorted list, bit 0 kFtuPads, bit 1 kFtuPadsSimple
+extern "C" int hmx_intra_plan_pad_bits(hmx_ctx *c, const hmx_intra_plan *pl, unsigned char *bits) {
+  if (!c || !pl || !bits) return fail(c, HMX_ERR_ARG, "hmx_intra_plan_pad_bits: bad argument");
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  std::vector<FTu> b((size_t)pl->n_tu);
+  HIPCHK(c, hipMemcpy(b.data(), pl->d_ltus, sizeof(FTu) * b.size(), hipMemcpyDeviceToHost));
+  for (size_t i = 0; i < b.size(); i++) bits[i] = (unsigned char)((b[i].avail_hi & kFtuPads ? 1 : 0) | (b[i].avail_hi & kFtuPadsSimple ? 2 : 0));
   return HMX_OK;
 }
 

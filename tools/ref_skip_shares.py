@@ -2,7 +2,7 @@
 """tools/ref_skip_shares.py [--pictures 64] [--size 3840x2160] [--tiling mix] [--group 64] [--slots8 16] -- the share of the packed
 schedule's wave-items, per size class, that take each wave-uniform skip of the reference line (hmx_kernels.h, intra_refs_tiled): no
 padding pass (no block of the wave-item reads an unavailable unit), no smoothed line (none predicts from it), no DC sum (none is
-DC).  Counted on the host from the tables of one real call (hmx_last_call_pack_tables) with the bench's plans (seeds 1.., one plan
+DC), and, of those that run the padding pass, the share on its index-clamp path against the general rule.  Counted on the host from the tables of one real call (hmx_last_call_pack_tables) with the bench's plans (seeds 1.., one plan
 per picture), in the shape the bench's 2048 pictures run in: packing groups of 64, sixteen 8x8 blocks per wave-item (a call of 64
 pictures would choose groups of one by itself).  Needs a GPU."""
 import argparse
@@ -69,3 +69,18 @@ for name, flag in (("pads", pads), ("smoothed", smooth), ("DC", dc)):
             blocks = np.concatenate([[0], np.cumsum(flag)])  # share of BLOCKS with the property, for comparison
             nb = (blocks[off[k] + cnt[k]] - blocks[off[k]]).sum()
             print(f"  {name:8s} {4 << s:2d}x{4 << s:<2d}: blocks {nb / cnt[k].sum():.3f}, wave-items with one {some[k].mean():.3f} -> skip taken by {1 - some[k].mean():.3f} of {k.sum()}")
+# the padding pass has three paths: none (above), the index clamp while every padding block of the wave-item is simple
+# (hmx_intra_pads_simple: no unit read and missing between units of the mask), the general rule otherwise
+simple = np.zeros(len(items), bool)
+if hasattr(L, "hmx_intra_pads_simple"):  # (absent from an older build loaded through HMX_LIB_PATH); one call per distinct (size, type, mode, mask)
+    key = np.stack([lg.astype(np.uint64), luma.astype(np.uint64), mode.astype(np.uint64), items["avail"].astype(np.uint64)], axis=1)
+    uniq, inv = np.unique(key, axis=0, return_inverse=True)
+    simple = np.array([L.hmx_intra_pads_simple(4 << int(u[0]), int(u[1]), int(u[2]), int(u[3])) != 0 for u in uniq])[inv.reshape(-1)]
+wave_of = np.repeat(np.arange(len(off)), cnt)  # the wave-item of every item
+any_pad = np.add.reduceat(pads.astype(np.int64), off) > 0
+any_general = np.add.reduceat((pads & ~simple).astype(np.int64), off) > 0
+for s in range(4):
+    k = cls == s
+    if k.any():
+        print(f"  paths    {4 << s:2d}x{4 << s:<2d}: no padding {(~any_pad[k]).mean():.3f}, clamp {(any_pad[k] & ~any_general[k]).mean():.3f}, general {any_general[k].mean():.3f} of {k.sum()} wave-items"
+              f" (blocks that pad: {pads[k[wave_of]].mean():.3f}, of them simple {simple[pads & k[wave_of]].mean():.3f})")
