@@ -154,7 +154,7 @@ static int issue_packed(hmx_ctx *c, const hmx_intra_plan *const *plans, int plan
     // (the completion counters are cleared behind the prep kernels: their array doubles as the scan's scratch)
     hipLaunchKernelGGL(k_pack_scan<false>, dim3(kPackScanWgs), dim3(1024), 0, st, pk.d_rows, pk.d_hdr, G, pk.d_done);
     hipLaunchKernelGGL(k_pack_scan<true>, dim3(kPackScanWgs), dim3(1024), 0, st, pk.d_rows, pk.d_hdr, G, pk.d_done);
-    hipLaunchKernelGGL(k_pack_fill, dim3((unsigned)((G.max_levels + kPackFillLevels - 1) / kPackFillLevels), (unsigned)(G.n_groups * G.I)), dim3(256), 0, st, pk.d_pics, pk.d_rows, pk.d_descs, pk.d_items, G);
+    hipLaunchKernelGGL(k_pack_fill, dim3((unsigned)((G.max_levels + kPackFillLevels - 1) / kPackFillLevels), (unsigned)G.n_groups), dim3(256), 0, st, pk.d_pics, pk.d_rows, pk.d_descs, pk.d_items, G);
     HIPCHK(c, hipGetLastError());
     if (c->timing && c->tev_prep) {
       HIPCHK(c, hipEventRecord(c->tev_prep, st));

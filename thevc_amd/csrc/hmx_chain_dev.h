@@ -1266,29 +1266,47 @@ __global__ __launch_bounds__(1024) void k_pack_scan(PackRow *rows, PackHdr *hdr,
     }
   }
 }
-// prep 3: the wave-item descriptors and the item array of one (row, size class) per wave.  Items of a bucket are ordered
-// by rank inside their picture's bucket, then by picture: pictures that share a plan put the SAME block of consecutive
-// pictures on consecutive lanes (consecutive lines of the interleaved pool, uniform control flow); pictures with their
-// own plans put blocks of similar code path (the plan sorts a bucket by plane, transform skip, mode) next to each other.
-// One workgroup per (dependency level, picture), one wave per size class, a LANE per item (rank r of the picture's bucket, 64 at a
-// time): the item is read where the plan has it and written where its row wants it -- both ends coalesced over the wave.  (The
-// first cut gave each picture of a row ONE lane that walked its bucket entry by entry: a chain of dependent loads per lane,
-// 30 ms per 2048 pictures of 2160p when every step brings new plans.)  The wave of the group's first picture also writes the
-// row's wave-item descriptors.
+// The code-path CLASS of a block: the bits of the plans' sort key above the mode (hmx_plan.hip, plan_path_key) as a dense code --
+// plane class, transform skip, padding pass, mode class with the two angular classes as one.  It grows with the key, so a class is
+// one contiguous run of a picture's (level, size) bucket; it needs the FTu alone, so host- and device-built plans agree on it.
+constexpr int kPackClasses = 32;
+__device__ __forceinline__ uint32_t pack_class(const FTu &f) {
+  const int m = f.t.mode, mc = m == 0 ? 0 : m == 1 ? 1 : (m == 10 || m == 26) ? 2 : 3;
+  return (f.t.plane & 3 ? 1u : 0u) << 4 | (uint32_t)(f.t.flags & 1u) << 3 | (f.avail_hi & kFtuPads ? 1u : 0u) << 2 | (uint32_t)mc;
+}
+// prep 3: the wave-item descriptors and the item array of one (row, size class) per wave.  Items of a bucket are ordered by
+// class, then by rank inside their picture's run of the class, then by picture: item (picture k, class c, rank r' of k's run) goes to
+//   sum over c'' < c, t of n[t][c'']  +  sum over t of min(n[t][c], r')  +  #{t < k : n[t][c] > r'}
+// with n[t][c] the class-c items of picture t's bucket.  A wave-item then holds blocks of one code path, whichever pictures they come
+// from, but for the one that straddles two classes (each picture's runs begin at ranks of their own: ordered by rank alone, most
+// wave-items mixed several paths, and a wave runs every arm one of its lanes takes).  Pictures that share a plan keep rank * I + k:
+// the SAME block of consecutive pictures on consecutive lanes (consecutive lines of the interleaved pool).
+// One workgroup per (8 dependency levels, GROUP), one wave per size class, a LANE per item of the group's bucket -- the pictures'
+// buckets one behind the other, 64 items at a time: an item is read where its plan has it and written where its row wants it, in
+// whole runs of neighbouring lanes at both ends.  A bucket is walked twice.  The first walk counts: a lane that begins a run of one
+// (picture, class) adds the run's length to n[t][c] in LDS, which a prefix over the classes turns into the first rank of every run;
+// nothing of this goes through memory, and nobody but this wave reads the bucket.  The second walk (the items come from the cache)
+// places the items.  A bucket in which a picture holds more than 65535 items (the LDS words have 16 bits), and a group of one
+// picture, keep the order by rank, then picture, which needs the pictures' counts alone.
+// (The first cut gave each picture of a row ONE lane that walked its bucket entry by entry: a chain of dependent loads per lane,
+// 30 ms per 2048 pictures of 2160p when every step brings new plans.)
 constexpr int kPackFillLevels = 8; // levels per workgroup: their table rows are fetched together, then the items move
 __global__ __launch_bounds__(256) void k_pack_fill(const PackPic *pics, const PackRow *rows, PackDesc *descs, FTu *items, PackGeom G) {
-  const int pic = blockIdx.y, s = 3 - (int)(threadIdx.x >> 6), lane = threadIdx.x & 63; // (largest blocks first in a row)
-  const int g = pic / G.I, k = pic - g * G.I, L0 = blockIdx.x * kPackFillLevels;
-  const bool have = pic < G.n_pics; // (a ragged last group)
-  const int n_levels = have ? pics[pic].n_levels : 0;
-  const FTu *ltus0 = have ? as_global(pics[pic].ltus) : nullptr;
-  const LevelRow *ltab = have ? as_global(pics[pic].ltab) : nullptr;
-  // lane q < I looks at picture q of the group: its level table, for the counts of this (level, size) over the group
-  const bool peer = lane < G.I && g * G.I + lane < G.n_pics;
+  // per wave, first[c][t]: the rank at which picture t's run of class c begins (row kPackClasses: its count); rows padded against
+  // bank conflicts between the classes of one picture
+  constexpr int kStride = 66;
+  __shared__ uint16_t first_c[4][(kPackClasses + 1) * kStride];
+  __shared__ uint32_t base_c[4][kPackClasses];
+  const int g = blockIdx.y, w = (int)(threadIdx.x >> 6), s = 3 - w, lane = threadIdx.x & 63; // (largest blocks first in a row)
+  const int L0 = blockIdx.x * kPackFillLevels;
+  uint16_t *first = first_c[w];
+  // lane t < I looks at picture t of the group: its level table, for its bucket of this (level, size)
+  const bool peer = lane < G.I && g * G.I + lane < G.n_pics; // (a ragged last group)
   const int peer_levels = peer ? pics[g * G.I + lane].n_levels : 0;
   const LevelRow *peer_tab = peer ? as_global(pics[g * G.I + lane].ltab) : nullptr;
+  const FTu *peer_tus = peer ? as_global(pics[g * G.I + lane].ltus) : nullptr;
   // phase 1: everything the levels of this workgroup need from the tables, all loads in flight together
-  uint32_t wave_base[kPackFillLevels], item_base[kPackFillLevels], dep[kPackFillLevels], cnt[kPackFillLevels], start[kPackFillLevels], cq[kPackFillLevels];
+  uint32_t wave_base[kPackFillLevels], item_base[kPackFillLevels], dep[kPackFillLevels], cq[kPackFillLevels], sq[kPackFillLevels];
   uint32_t rcount[kPackFillLevels][4];
 #pragma unroll
   for (int q = 0; q < kPackFillLevels; q++) {
@@ -1299,40 +1317,107 @@ __global__ __launch_bounds__(256) void k_pack_fill(const PackPic *pics, const Pa
 #pragma unroll
     for (int t = 0; t < 4; t++) rcount[q][t] = on ? R->count[t] : 0;
     dep[q] = (on && L > 0) ? (R - G.n_groups)->n_waves : 0;
-    const bool mine = on && L < n_levels;
-    cnt[q] = mine ? ltab[L].count[s] : 0, start[q] = mine ? ltab[L].start[s] : 0;
-    cq[q] = (on && L < peer_levels) ? peer_tab[L].count[s] : 0;
+    const bool mine = on && L < peer_levels;
+    cq[q] = mine ? peer_tab[L].count[s] : 0, sq[q] = mine ? peer_tab[L].start[s] : 0;
   }
-  // phase 2: descriptors (the group's first picture) and items
+  // phase 2: descriptors and items
 #pragma unroll
   for (int q = 0; q < kPackFillLevels; q++) {
     const int L = L0 + q;
     if (L >= G.max_levels) break;
-    if (k == 0) { // the row's wave-items of this size class: they follow those of the larger classes
-      const uint32_t sl = pack_slots(s, G.slots4, G.slots8), total = rcount[q][s], nw = (total + sl - 1) / sl;
+    const uint32_t total = rcount[q][s];
+    { // the row's wave-items of this size class: they follow those of the larger classes
+      const uint32_t sl = pack_slots(s, G.slots4, G.slots8), nw = (total + sl - 1) / sl;
       uint32_t woff = 0;
       for (int t = 3; t > s; t--) woff += (rcount[q][t] + pack_slots(t, G.slots4, G.slots8) - 1) / pack_slots(t, G.slots4, G.slots8);
       const uint32_t row = (uint32_t)(L * G.n_groups + g);
       for (uint32_t c = (uint32_t)lane; c < nw; c += 64u)
         descs[wave_base[q] + woff + c] = PackDesc{item_base[q] + c * sl, min(sl, total - c * sl) | ((uint32_t)s << 28), row, dep[q]};
     }
-    // an item (rank r, picture k) sits behind every item of a lower rank and the same-rank items of the pictures before k:
-    //   sum over k' of min(count[k'], r)  +  #{k' < k : count[k'] > r}
-    const FTu *ltus = ltus0 + start[q];
+    if (!total) continue;
     FTu *dst = items + item_base[q];
-    for (uint32_t r0 = 0; r0 < cnt[q]; r0 += 64u) { // (whole rounds: the shuffles below need every lane)
-      const uint32_t r = r0 + (uint32_t)lane;
-      uint32_t off = 0;
-      for (int t = 0; t < G.I; t++) {
-        const uint32_t c2 = (uint32_t)__shfl((int)cq[q], t, 64);
-        off += min(c2, r) + ((t < k && c2 > r) ? 1u : 0u);
+    // the pictures' buckets one behind the other: lane t holds where picture t's begins (pre) and where its items lie (src)
+    uint32_t pre = cq[q];
+    for (int d = 1; d < 64; d <<= 1) {
+      const uint32_t up = (uint32_t)__shfl_up((int)pre, d, 64);
+      if (lane >= d) pre += up;
+    }
+    pre -= cq[q];
+    const unsigned long long src = (unsigned long long)(peer_tus + sq[q]);
+    const auto locate = [&](uint32_t j, int &t, uint32_t &r) { // item j of the group's bucket: rank r of picture t
+      t = 0;
+      for (int u = 1; u < G.I; u++) t += j >= (uint32_t)__shfl((int)pre, u, 64) ? 1 : 0;
+      r = j - (uint32_t)__shfl((int)pre, t, 64);
+      const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)src, t, 64), hi = (uint32_t)__shfl((int)(uint32_t)(src >> 32), t, 64);
+      return (const FTu *)((unsigned long long)hi << 32 | lo) + r;
+    };
+    const bool classed = G.I > 1 && !__any(cq[q] > 0xffffu);
+    if (classed) {
+      for (int c = 0; c <= kPackClasses; c++)
+        if (lane < G.I) first[c * kStride + lane] = 0;
+      wave_sync();
+      for (uint32_t j0 = 0; j0 < total; j0 += 64u) { // whole rounds: the shuffles need every lane
+        const uint32_t j = j0 + (uint32_t)lane, live = min(64u, total - j0);
+        const bool valid = j < total;
+        int t;
+        uint32_t r;
+        const FTu *at = locate(j, t, r);
+        const uint32_t c = valid ? pack_class(*at) : 0u, key = valid ? (uint32_t)t << 8 | c : 0xffffffffu;
+        const uint32_t prev = (uint32_t)__shfl_up((int)key, 1, 64);
+        const bool begins = valid && (lane == 0 || key != prev); // a run of one (picture, class), as far as this round holds it
+        const unsigned long long all = __ballot(begins), later = lane < 63 ? all >> (lane + 1) : 0ull;
+        if (begins) first[(c + 1) * kStride + t] += (uint16_t)((later ? (uint32_t)(lane + 1 + __builtin_ctzll(later)) : live) - (uint32_t)lane);
+        wave_sync(); // (the run may go on in the next round)
       }
-      if (r < cnt[q]) {
-        FTu f = ltus[r];
-        f.t.plane = (uint8_t)(f.t.plane | (k << 2)); // picture of the group in the upper six bits
+      if (lane < G.I) { // counts -> first ranks
+        uint32_t acc = 0;
+        for (int c = 1; c <= kPackClasses; c++) {
+          acc += first[c * kStride + lane];
+          first[c * kStride + lane] = (uint16_t)acc;
+        }
+      }
+      wave_sync();
+      { // where each class begins in the bucket: the exclusive prefix of the group's totals
+        uint32_t n = 0;
+        if (lane < kPackClasses)
+          for (int u = 0; u < G.I; u++) n += (uint32_t)first[(lane + 1) * kStride + u] - (uint32_t)first[lane * kStride + u];
+        uint32_t incl = n;
+        for (int d = 1; d < kPackClasses; d <<= 1) {
+          const uint32_t up = (uint32_t)__shfl_up((int)incl, d, 64);
+          if (lane >= d) incl += up;
+        }
+        if (lane < kPackClasses) base_c[w][lane] = incl - n;
+      }
+      wave_sync();
+    }
+    for (uint32_t j0 = 0; j0 < total; j0 += 64u) {
+      const uint32_t j = j0 + (uint32_t)lane;
+      const bool valid = j < total;
+      int t;
+      uint32_t r;
+      const FTu *at = locate(j, t, r);
+      uint32_t off = 0;
+      FTu f{};
+      if (valid) f = *at;
+      if (classed) {
+        const uint32_t c = valid ? pack_class(f) : 0u, rr = r - first[c * kStride + t];
+        off = base_c[w][c];
+        for (int u = 0; u < G.I; u++) {
+          const uint32_t n = (uint32_t)first[(c + 1) * kStride + u] - (uint32_t)first[c * kStride + u];
+          off += min(n, rr) + ((u < t && n > rr) ? 1u : 0u);
+        }
+      } else { // by rank, then picture:  sum over u of min(count[u], r)  +  #{u < t : count[u] > r}
+        for (int u = 0; u < G.I; u++) {
+          const uint32_t n = (uint32_t)__shfl((int)cq[q], u, 64);
+          off += min(n, r) + ((u < t && n > r) ? 1u : 0u);
+        }
+      }
+      if (valid) {
+        f.t.plane = (uint8_t)(f.t.plane | (t << 2)); // picture of the group in the upper six bits
         dst[off] = f;
       }
     }
+    wave_sync(); // (the next level rewrites the table)
   }
 }
 

@@ -2,7 +2,9 @@
 """tools/ref_skip_shares.py [--pictures 64] [--size 3840x2160] [--tiling mix] [--group 64] [--slots8 16] -- the share of the packed
 schedule's wave-items, per size class, that take each wave-uniform skip of the reference line (hmx_kernels.h, intra_refs_tiled): no
 padding pass (no block of the wave-item reads an unavailable unit), no smoothed line (none predicts from it), no DC sum (none is
-DC), and, of those that run the padding pass, the share on its index-clamp path against the general rule.  Counted on the host from the tables of one real call (hmx_last_call_pack_tables) with the bench's plans (seeds 1.., one plan
+DC), and, of those that run the padding pass, the share on its index-clamp path against the general rule; then the share that hold
+each mode class (planar, DC, pure vertical / horizontal, angular) and a transform-skip block -- a wave runs every prediction and transform
+arm one of its lanes takes -- and the share that hold more than one code-path class (k_pack_fill orders a bucket by that class).  Counted on the host from the tables of one real call (hmx_last_call_pack_tables) with the bench's plans (seeds 1.., one plan
 per picture), in the shape the bench's 2048 pictures run in: packing groups of 64, sixteen 8x8 blocks per wave-item (a call of 64
 pictures would choose groups of one by itself).  Needs a GPU."""
 import argparse
@@ -84,3 +86,20 @@ for s in range(4):
     if k.any():
         print(f"  paths    {4 << s:2d}x{4 << s:<2d}: no padding {(~any_pad[k]).mean():.3f}, clamp {(any_pad[k] & ~any_general[k]).mean():.3f}, general {any_general[k].mean():.3f} of {k.sum()} wave-items"
               f" (blocks that pad: {pads[k[wave_of]].mean():.3f}, of them simple {simple[pads & k[wave_of]].mean():.3f})")
+# the arms of intra_pred_samples and of the 4x4 chain's transform: per lane by mode class and transform skip, so a wave-item runs every
+# one that occurs in it; and the code-path class k_pack_fill orders a bucket by (plane class, transform skip, pads, mode class)
+mc = np.where(mode == 0, 0, np.where(mode == 1, 1, np.where((mode == 10) | (mode == 26), 2, 3)))
+ts = (items["flags"] & 1).astype(np.int64)
+path = ((1 - luma) << 4) | (ts << 3) | (pads.astype(np.int64) << 2) | mc
+for name, flag in (("planar", mc == 0), ("DC", mc == 1), ("pure V/H", mc == 2), ("angular", mc == 3), ("tr. skip", ts == 1)):
+    some = np.add.reduceat(flag.astype(np.int64), off) > 0
+    for s in range(4):
+        k = cls == s
+        if k.any():
+            print(f"  {name:8s} {4 << s:2d}x{4 << s:<2d}: blocks {flag[k[wave_of]].mean():.3f}, wave-items with one {some[k].mean():.3f}")
+arms = sum((np.add.reduceat((mc == v).astype(np.int64), off) > 0).astype(np.int64) for v in range(4))
+lo, hi = np.minimum.reduceat(path, off), np.maximum.reduceat(path, off)
+for s in range(4):
+    k = cls == s
+    if k.any():
+        print(f"  classes  {4 << s:2d}x{4 << s:<2d}: wave-items with more than one code-path class {(lo[k] != hi[k]).mean():.3f}, prediction arms per wave-item {arms[k].mean():.2f} of {k.sum()}")
