@@ -1396,6 +1396,162 @@ def test_frame_intra_decode_onto(ctx, n_pics, schedule, hmx_opts):
         d.free()
 
 
+def test_frame_intra_call_kinds_in_sequence():
+    """Every kind of whole-picture call, one after the other on ONE context: what a call decides (schedule, pools, onto, group
+    size, stream groups) must not reach the next call.  3 pictures of 136x72, 8 bit, "mix" tilings; a shared plan where the call
+    kind needs one, each picture's own plan otherwise; every accepted call bit-exact vs the oracle, and hmx_last_call_shape
+    reports the schedule that ran."""
+    O, L, B = ol.oracle(), capi.lib(), 8
+    O.hmo_getSSE.restype = C.c_uint32
+    w, h, n, qp = 136, 72, 3, 30
+    ctx = capi.Context(bit_depth=B)
+    P3, I3 = C.c_void_p * 3, C.c_int * 3
+    A = lambda lst, T: (T * n)(*[x.as_pic() for x in lst])
+    knobs = ("HMX_INTRA_SCHEDULE", "HMX_INTRA_ACROSS", "HMX_PIPELINE_CONV", "HMX_INTRA_STREAMS", "HMX_PACK_GROUP")
+
+    def opts(**kw):  # these knobs, every other one at its default
+        for k in knobs:
+            ctx.set_option(k, kw.get(k))
+
+    def shape():
+        sched, groups = C.c_int(), C.c_int()
+        L.hmx_last_call_shape(ctx.h, C.byref(sched), C.byref(groups))
+        return sched.value, groups.value
+
+    def same(got, want, what):
+        for i in range(n):
+            for p in range(3):
+                assert np.array_equal(got[i][p], want[i][p]), (what, i, p)
+
+    try:
+        pp = capi.PicParam(w, h, qp, 0, capi.I_SLICE, 1)
+        tus = [workload.make_tus(1700 + i, w, h, "mix") for i in range(n)]
+        plans = [ctx.intra_plan(t, pp) for t in tus]
+        parr = (C.c_void_p * n)(*[p.value for p in plans])
+        shared = plans[0]
+        # a plan that lists only SOME blocks of tus[0] (test_frame_intra_decode_onto): what it leaves out keeps what the planes hold
+        sh = (tus[0]["plane"] != 0).astype(np.int64)
+        region = ((tus[0]["x"].astype(np.int64) << sh) // 16) * 7 + ((tus[0]["y"].astype(np.int64) << sh) // 16) * 3
+        tus_part = np.ascontiguousarray(tus[0][region % 3 != 0])
+        assert 0 < len(tus_part) < len(tus[0])
+        part = ctx.intra_plan(tus_part, pp)
+        untouched = np.ones((h, w), bool)
+        for t in tus_part:
+            if t["plane"] == 0:
+                s = 1 << int(t["log2n"])
+                untouched[int(t["y"]):int(t["y"]) + s, int(t["x"]):int(t["x"]) + s] = False
+        assert untouched.any()
+        orgs = [workload.make_planes(1750 + i, w, h, B, "texture" if i % 2 else "noise") for i in range(n)]
+        held = [workload.make_planes(1760 + i, w, h, B, "texture") for i in range(n)]
+        held2 = [workload.make_planes(1770 + i, w, h, B, "noise") for i in range(n)]
+        # the oracle's answers, once: own plans, the shared plan, the partial plan onto the held pictures
+        ref_own = [ol.o_intra_frame_encode(tus[i], w, h, B, qp, orgs[i]) for i in range(n)]
+        ref_sh = [ol.o_intra_frame_encode(tus[0], w, h, B, qp, orgs[i]) for i in range(n)]
+        ref_onto = []
+        cfg, st, tp = ol.frame_cfg(w, h, B, qp), I3(w, w // 2, w // 2), np.ascontiguousarray(tus_part, ol.TU_DTYPE)
+        for i in range(n):
+            oo = [np.ascontiguousarray(a, np.int16) for a in orgs[i]]
+            rec = [np.ascontiguousarray(a, np.int16).copy() for a in held[i]]
+            lev = [np.zeros(a.shape, np.int32) for a in rec]
+            O.hmo_intra_frame_encode(C.byref(cfg), tp.ctypes.data, len(tp), P3(*[a.ctypes.data for a in oo]), st,
+                                     P3(*[a.ctypes.data for a in rec]), st, P3(*[a.ctypes.data for a in lev]))
+            ref_onto.append((rec, lev))
+        d_org = [capi.DevPicture(ctx, w, h).upload(o) for o in orgs]
+        d_rec = [capi.DevPicture(ctx, w, h) for _ in range(n)]
+        d_lev = [capi.DevPicture(ctx, w, h, dtype=np.int32) for _ in range(n)]
+
+        def run(call, want, what, sched, groups=1, fill=None, levels=True, after=None):
+            """zero (or fill) the outputs, issue the call, compare reconstruction and levels with `want`, check the reported shape"""
+            for i in range(n):
+                d_rec[i].upload(fill[i]) if fill else d_rec[i].zero()
+                if levels:
+                    d_lev[i].zero()
+            ctx._chk(call())
+            if after:
+                after()
+            ctx.sync()
+            assert shape() == (sched, groups), (what, shape())
+            same([d.download() for d in d_rec], [r for r, _ in want], what + ": reconstruction")
+            same([d.download() for d in d_lev], [l for _, l in want], what + ": levels")
+
+        enc_own = lambda: L.hmx_frame_intra_encode_multi(ctx.h, parr, n, A(d_org, capi.Pic), A(d_rec, capi.Pic), A(d_lev, capi.Levels))
+        enc_sh = lambda: L.hmx_frame_intra_encode(ctx.h, shared, n, A(d_org, capi.Pic), A(d_rec, capi.Pic), A(d_lev, capi.Levels))
+        # 1. default packed encode
+        run(enc_own, ref_own, "packed, own plans", 3)
+        # 2. encode onto what the reconstruction planes hold
+        run(lambda: L.hmx_frame_intra_encode_onto(ctx.h, part, n, A(d_org, capi.Pic), A(d_rec, capi.Pic), A(d_lev, capi.Levels)),
+            ref_onto, "encode onto", 3, fill=held)
+        # 3. the same plan through the plain entry point: the planes are outputs only, what they held is NOT taken over ...
+        for i in range(n):
+            d_rec[i].upload(held2[i])
+        ctx._chk(L.hmx_frame_intra_encode(ctx.h, part, n, A(d_org, capi.Pic), A(d_rec, capi.Pic), A(d_lev, capi.Levels)))
+        ctx.sync()
+        for i in range(n):
+            assert not np.array_equal(d_rec[i].download()[0][untouched], np.asarray(held2[i][0])[untouched]), ("plain call behaved as onto", i)
+        run(enc_sh, ref_sh, "packed, shared plan", 3)  # ... and a whole plan gives the oracle's pictures again
+        # 4. resident pools whose group size (2, set when they were created) is not the one the context would choose now (1)
+        opts(HMX_PACK_GROUP="2")
+        p_org, p_rec = capi.ResidentPool(ctx, w, h, n), capi.ResidentPool(ctx, w, h, n)
+        opts()
+        p_org.import_planes(0, d_org)
+        run(lambda: L.hmx_frame_intra_encode_resident(ctx.h, parr, 1, n, p_org.h_, p_rec.h_, A(d_lev, capi.Levels)), ref_own, "resident", 3,
+            after=lambda: p_rec.export_planes(0, d_rec))
+        # 5. plain decode, of other pictures' levels: the context's own pools again, the caller's pool stays as it is
+        for i in range(n):
+            d_lev[i].upload(ref_sh[i][1])
+        run(lambda: L.hmx_frame_intra_decode(ctx.h, shared, n, A(d_rec, capi.Pic), A(d_lev, capi.Levels)), ref_sh, "decode after resident", 3,
+            levels=False)
+        for d in d_rec:
+            d.zero()
+        p_rec.export_planes(0, d_rec)
+        ctx.sync()
+        same([d.download() for d in d_rec], [r for r, _ in ref_own], "resident pool after a plain call")
+        # 6. the level schedules and the wave schedule, then 7. the default again
+        for kw, sched, groups in [(dict(HMX_INTRA_SCHEDULE="level"), 2, 1), (dict(HMX_INTRA_SCHEDULE="level", HMX_INTRA_STREAMS="2"), 2, 2),
+                                  (dict(HMX_INTRA_SCHEDULE="level", HMX_PIPELINE_CONV="1"), 2, 1), (dict(HMX_INTRA_SCHEDULE="level", HMX_INTRA_ACROSS="0"), 1, 1),
+                                  (dict(HMX_INTRA_SCHEDULE="wave"), 0, 1), ({}, 3, 1)]:
+            opts(**kw)
+            run(enc_sh, ref_sh, str(kw), sched, groups)
+        run(enc_own, ref_own, "packed again, own plans", 3)
+        # 8. the distortion output under the level schedule is refused ... 9. and accepted under the packed schedule
+        cw, ch = -(-w // 64), -(-h // 64)
+        d_sse = [[ctx.alloc(4 * u).zero() for u in (cw * ch * 256, cw * ch * 64, cw * ch * 64)] for _ in range(n)]
+        sse_arr = (capi.Sse * n)()
+        for i in range(n):
+            for p in range(3):
+                sse_arr[i].plane[p] = d_sse[i][p].ptr
+        ctx._chk(L.hmx_set_sse_output(ctx.h, sse_arr, n))
+        opts(HMX_INTRA_SCHEDULE="level")
+        assert enc_sh() == -1  # HMX_ERR_ARG
+        assert b"needs the packed schedule" in L.hmx_last_error(ctx.h)
+        opts()
+        d_levz = [capi.DevLevelsZ(ctx, w, h) for _ in range(n)]
+        for d in d_rec:
+            d.zero()
+        ctx._chk(L.hmx_frame_intra_encode(ctx.h, shared, n, A(d_org, capi.Pic), A(d_rec, capi.Pic), A(d_levz, capi.Levels)))
+        ctx.sync()
+        assert shape() == (3, 1)
+        same([d.download() for d in d_rec], [r for r, _ in ref_sh], "packed with distortion output: reconstruction")
+        same([d.to_planes(tus[0]) for d in d_levz], [l for _, l in ref_sh], "packed with distortion output: levels")
+        for i in range(n):
+            got = [d_sse[i][p].download(np.uint32) for p in range(3)]
+            for t in tus[0]:
+                N, p, x, y = 1 << int(t["log2n"]), int(t["plane"]), int(t["x"]), int(t["y"])
+                o = np.ascontiguousarray(orgs[i][p][y:y + N, x:x + N])
+                r = np.ascontiguousarray(ref_sh[i][0][p][y:y + N, x:x + N])
+                want = O.hmo_getSSE(o.ctypes.data_as(C.c_void_p), N, r.ctypes.data_as(C.c_void_p), N, N, N, B)
+                assert int(got[p][d_levz[i].block_offset(p, x, y) // 16]) == want, ("sse", i, p, x, y, N)
+        ctx._chk(L.hmx_set_sse_output(ctx.h, None, 0))
+        for x in (p_org, p_rec):
+            x.free()
+        for pl in plans + [part]:
+            L.hmx_intra_plan_destroy(ctx.h, pl)
+        for d in d_org + d_rec + d_lev + d_levz + [b for row in d_sse for b in row]:
+            d.free()
+    finally:
+        ctx.close()
+
+
 def test_set_rdoq_keeps_its_state_when_it_refuses(ctx):
     """hmx_set_rdoq checks every input before it touches the context (round-2 advisor finding): a good set, then a call with a
     non-positive multiplier is REFUSED and the good set stays in force -- same levels as before the refused call, also when the encode

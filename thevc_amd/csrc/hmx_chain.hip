@@ -66,25 +66,47 @@ int check_packed_abort(hmx_ctx *c) {
   HIPCHK(c, hipMemset(&c->pk.d_hdr->abort, 0, sizeof(ab))); // read and reported: the next call starts clean
   return fail(c, HMX_ERR_DEVICE, "packed schedule: a dependency wait timed out, the outputs of every call since the last hmx_sync are invalid");
 }
+// Everything frame_intra decides for ONE whole-picture call: what the caller passed, the schedule it resolved to, the pools it
+// works on and, once uploaded, its tables on the device.  The issue_* functions read it and nothing else about the call; the
+// context keeps only what outlives a call (what it owns, what it caches, what reports on the last call).
+struct IntraCall {
+  bool enc, onto, resident;
+  const hmx_intra_plan *const *plans; // picture i follows plans[i * plan_stride] (stride 0: one plan for all)
+  int plan_stride, n_pics;
+  const hmx_levels *lev;              // the caller's array, valid while the call is issued
+  int schedule;                       // 3 packed, 2 level across pictures, 1 level per picture, 0 wave (hmx_last_call_shape)
+  bool across, pipeline_conv;         // level schedule: SIMD across pictures; its conversions pipelined by CTU row
+  int groups, I;                      // stream groups of the level schedule; pictures per group of the packed one
+  TiledGeom geom;
+  short *pool_org, *pool_rec;         // the context's own pools or the caller's (hmx_tpool)
+  const PicWork *d_work;
+  const ConvJob *d_jobs;              // [2][n_pics * 3]: to-tiled jobs, then from-tiled jobs
+  bool packed() const { return schedule == 3; }
+  bool use_level() const { return schedule == 1 || schedule == 2; }
+  const hmx_intra_plan *plan(int i) const { return plans[i * plan_stride]; }
+  // the interleave domain of the pool is a group of I pictures (packed), a stream group (across), one picture
+  int group_first(int g) const { return (int)((long long)n_pics * g / groups); }           // stream group g = [first(g), first(g + 1))
+  int group_of(int i) const { return (int)(((long long)(i + 1) * groups - 1) / n_pics); } // the g with first(g) <= i < first(g + 1)
+};
 // Issue the launches of one whole-picture call on `main` (and the side streams).  Also used under
 // stream capture to record the call as a HIP graph.
-static int issue_chain_launches(hmx_ctx *c, const hmx_intra_plan *const *plans, int plan_stride, int n_pics,
-                                const PicWork *d_work, bool enc, bool use_level, int groups, hipStream_t main);
-static int issue_packed(hmx_ctx *c, const hmx_intra_plan *const *plans, int plan_stride, int n_pics, bool enc, hipStream_t st);
+static int issue_chain_launches(hmx_ctx *c, const IntraCall &k, hipStream_t main);
 
 // ---- packed schedule, host side ----
-static int issue_packed(hmx_ctx *c, const hmx_intra_plan *const *plans, int plan_stride, int n_pics, bool enc, hipStream_t st) {
+static int issue_packed(hmx_ctx *c, const IntraCall &k, hipStream_t st) {
   auto &pk = c->pk;
-  const hmx_intra_plan *p0 = plans[0];
+  const hmx_intra_plan *p0 = k.plans[0];
+  const int n_pics = k.n_pics;
+  const bool enc = k.enc;
   PackGeom G{};
   G.n_pics = n_pics;
-  G.I = c->pack_I;
+  G.I = k.I;
   G.n_groups = (n_pics + G.I - 1) / G.I;
   G.n_shards = std::min(8, G.n_groups);
   uint64_t items = 0, sz[4] = {0, 0, 0, 0};
   uint32_t tex_sizes = 0;
   for (int i = 0; i < n_pics; i++) {
-    const hmx_intra_plan *pl = plans[i * plan_stride];
+    const hmx_intra_plan *pl = k.plan(i);
     G.max_levels = std::max(G.max_levels, pl->n_levels);
     items += (uint64_t)pl->n_tu;
     for (int s = 0; s < 4; s++) sz[s] += pl->size_total[s];
@@ -139,8 +161,8 @@ static int issue_packed(hmx_ctx *c, const hmx_intra_plan *const *plans, int plan
     if (r) return r;
     std::vector<PackPic> hp(n_pics);
     for (int i = 0; i < n_pics; i++) {
-      const hmx_intra_plan *pl = plans[i * plan_stride];
-      for (int p = 0; p < 3; p++) hp[i].lev[p] = c->call_lev[i].plane[p], hp[i].lev_stride[p] = c->call_lev[i].stride[p];
+      const hmx_intra_plan *pl = k.plan(i);
+      for (int p = 0; p < 3; p++) hp[i].lev[p] = k.lev[i].plane[p], hp[i].lev_stride[p] = k.lev[i].stride[p];
       hp[i].n_levels = pl->n_levels;
       hp[i].ltab = pl->d_ltab;
       hp[i].ltus = pl->d_ltus;
@@ -201,18 +223,18 @@ static int issue_packed(hmx_ctx *c, const hmx_intra_plan *const *plans, int plan
   A.items = pk.d_items;
   A.done = pk.d_done;
   A.hdr = pk.d_hdr;
-  A.pool_org = c->pool_org;
-  A.pool_rec = c->pool_rec;
-  A.pic_elems = c->tiled_pic_elems;
-  for (int p = 0; p < 3; p++) A.plane_off[p] = c->tiled_plane_off[p];
-  A.ctu_w = c->tiled_cw;
-  A.clog = ilog2i(p0->P.ctu);
+  A.pool_org = k.pool_org;
+  A.pool_rec = k.pool_rec;
+  A.pic_elems = k.geom.pic_elems;
+  for (int p = 0; p < 3; p++) A.plane_off[p] = k.geom.plane_off[p];
+  A.ctu_w = k.geom.cw;
+  A.clog = ilog2i(k.geom.ctu);
   A.n_groups = G.n_groups;
   A.n_shards = G.n_shards;
   A.I = G.I;
   A.want_sse = enc && (int)c->sse_out.size() >= n_pics;
   {
-    const hmx_levels *lv = c->call_lev;
+    const hmx_levels *lv = k.lev;
     bool slab = true;
     for (int p = 0; p < 3 && slab; p++) {
       const ptrdiff_t d = n_pics > 1 ? (const char *)lv[1].plane[p] - (const char *)lv[0].plane[p] : 0;
@@ -270,19 +292,17 @@ static int issue_packed(hmx_ctx *c, const hmx_intra_plan *const *plans, int plan
   const dim3 grid((unsigned)pk.n_wg), blk(64);
   if (rdoq) {
     launch_packed_rdoq(A, A.want_sse != 0, grid.x, st); // hmx_chain_rdoq.hip
-  } else if (G.slots8 == 16) {
-    if (A.want_sse) hipLaunchKernelGGL((k_intra_packed<true, 64, true, false, 16>), grid, blk, 0, st, A);
-    else if (enc) hipLaunchKernelGGL((k_intra_packed<true, 64, false, false, 16>), grid, blk, 0, st, A);
-    else hipLaunchKernelGGL((k_intra_packed<false, 64, false, false, 16>), grid, blk, 0, st, A);
-  } else if (A.want_sse) {
-    if (G.slots4 == 64) hipLaunchKernelGGL((k_intra_packed<true, 64, true>), grid, blk, 0, st, A);
-    else hipLaunchKernelGGL((k_intra_packed<true, 16, true>), grid, blk, 0, st, A);
-  } else if (G.slots4 == 64) {
-    if (enc) hipLaunchKernelGGL((k_intra_packed<true, 64>), grid, blk, 0, st, A);
-    else hipLaunchKernelGGL((k_intra_packed<false, 64>), grid, blk, 0, st, A);
   } else {
-    if (enc) hipLaunchKernelGGL((k_intra_packed<true, 16>), grid, blk, 0, st, A);
-    else hipLaunchKernelGGL((k_intra_packed<false, 16>), grid, blk, 0, st, A);
+    with_bool(enc, [&](auto enc_t) {
+      with_bool(A.want_sse != 0, [&](auto sse_t) {
+        constexpr bool E = decltype(enc_t)::value, S = decltype(sse_t)::value;
+        if constexpr (E || !S) { // the distortion output exists in the encoder direction only
+          if (G.slots8 == 16) hipLaunchKernelGGL((k_intra_packed<E, 64, S, false, 16>), grid, blk, 0, st, A); // (then slots4 is 64)
+          else if (G.slots4 == 64) hipLaunchKernelGGL((k_intra_packed<E, 64, S>), grid, blk, 0, st, A);
+          else hipLaunchKernelGGL((k_intra_packed<E, 16, S>), grid, blk, 0, st, A);
+        }
+      });
+    });
   }
   HIPCHK(c, hipGetLastError());
   c->pk_pending = true;
@@ -318,14 +338,60 @@ extern "C" int hmx_last_call_pack_tables(hmx_ctx *c, hmx_pack_geom *geom, void *
   return HMX_OK;
 }
 
+// ---- level schedules: picture groups on side streams, forked from and joined into `main` through events ----
+static int fork_groups(hmx_ctx *c, int groups, hipStream_t main) { // the groups start after what is already on main
+  HIPCHK(c, hipEventRecord(c->ev_fork, main));
+  for (int g = 0; g < groups; g++) HIPCHK(c, hipStreamWaitEvent(c->side[g], c->ev_fork, 0));
+  return HMX_OK;
+}
+static int join_groups(hmx_ctx *c, int groups, hipStream_t main) {
+  for (int g = 0; g < groups; g++) {
+    HIPCHK(c, hipEventRecord(c->ev_join[g], c->side[g]));
+    HIPCHK(c, hipStreamWaitEvent(main, c->ev_join[g], 0));
+  }
+  return HMX_OK;
+}
+// One plan for every picture: SIMD across pictures (k_intra_level_across); every group of pictures is its own interleave
+// domain of the pool (see build_tables) and walks the levels on its own stream.  What the launches of a call share ...
+static AcrossArgs across_args(const IntraCall &k) {
+  AcrossArgs AA{};
+  AA.ltus = k.plans[0]->d_ltus;
+  AA.pic_elems = k.geom.pic_elems;
+  for (int p = 0; p < 3; p++) AA.plane_off[p] = k.geom.plane_off[p];
+  AA.ctu_w = k.geom.cw;
+  AA.clog = ilog2i(k.geom.ctu);
+  AA.P = k.plans[0]->P;
+  return AA;
+}
+// ... and the launch of dependency level l for picture group g on `st`
+static int launch_across_level(hmx_ctx *c, const IntraCall &k, AcrossArgs AA, size_t l, int g, hipStream_t st) {
+  const int first = k.group_first(g), np = k.group_first(g + 1) - first;
+  if (np <= 0) return HMX_OK;
+  AA.row = k.plans[0]->h_ltab[l];
+  AA.pics = k.d_work + first;
+  AA.n_pics = np;
+  AA.pool_org = k.pool_org + (size_t)first * k.geom.pic_elems;
+  AA.pool_rec = k.pool_rec + (size_t)first * k.geom.pic_elems;
+  uint64_t waves = 0;
+  for (int s = 0; s < 4; s++) {
+    const int slots = s == 0 ? kSlots4 : s == 1 ? 8 : s == 2 ? 4 : 1;
+    AA.cpb[s] = (uint32_t)((np + slots - 1) / slots);
+    waves += (uint64_t)AA.row.count[s] * AA.cpb[s];
+  }
+  if (!waves) return HMX_OK;
+  if (waves > 0x7fffffffull) return fail(c, HMX_ERR_ARG, "frame_intra: level too large for one launch");
+  with_bool(k.enc, [&](auto E) { hipLaunchKernelGGL(k_intra_level_across<E>, dim3((unsigned)waves), dim3(64), 0, st, AA); });
+  return HMX_OK;
+}
+
 // The across schedule with the layout conversions pipelined by CTU row.  The chain is latency-bound and leaves the
 // memory system idle; the conversions are pure traffic.  CTU row r is converted in (stream `conv`) before the first
 // dependency level that touches it and converted out after the last one, so both conversions hide behind the chain:
 //   conv:   in(0) in(1) ... in(R-1)            wait(final 0) out(0)  wait(final 1) out(1) ...
 //   group:  wait(in 0) level 0 ... wait(in r) level first[r] ... level last[r] record(final r) ...
-static int issue_across_pipelined(hmx_ctx *c, const hmx_intra_plan *p0, int n_pics, const PicWork *d_work, const ConvJob *d_jobs,
-                                  bool enc, int groups, hipStream_t main) {
-  const int ctu = p0->P.ctu, cw = (p0->P.pic_w + ctu - 1) / ctu, ch = (p0->P.pic_h + ctu - 1) / ctu;
+static int issue_across_pipelined(hmx_ctx *c, const IntraCall &k, hipStream_t main) {
+  const hmx_intra_plan *p0 = k.plans[0];
+  const int ctu = k.geom.ctu, ch = k.geom.ch, groups = k.groups;
   int prio_lo = 0, prio_hi = 0; // the conversions are background traffic: lowest priority, the chain highest
   hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
   if (!c->conv_stream) HIPCHK(c, hipStreamCreateWithPriority(&c->conv_stream, hipStreamNonBlocking, prio_lo));
@@ -344,28 +410,16 @@ static int issue_across_pipelined(hmx_ctx *c, const hmx_intra_plan *p0, int n_pi
   }
   hipEvent_t *ev_in = c->ev_rows.data(), *ev_final = c->ev_rows.data() + ch; // ev_final[g * ch + r]
   hipStream_t conv = c->conv_stream;
-  const unsigned spr = (unsigned)(cw * ctu + 63) / 64, strip_rows = (unsigned)(ctu + 63) / 64;
-  const dim3 cgrid((unsigned)n_pics, spr * strip_rows, 3);
-  // fork: everything starts after what is already on main
-  HIPCHK(c, hipEventRecord(c->ev_fork, main));
-  HIPCHK(c, hipStreamWaitEvent(conv, c->ev_fork, 0));
-  for (int g = 0; g < groups; g++) HIPCHK(c, hipStreamWaitEvent(c->side[g], c->ev_fork, 0));
+  const dim3 cgrid = convert_grid(k.geom, k.n_pics, ctu); // one CTU row
+  if (int r = fork_groups(c, groups, main)) return r;
+  HIPCHK(c, hipStreamWaitEvent(conv, c->ev_fork, 0)); // the conversions too start after what is already on main
   if (c->timing) HIPCHK(c, hipEventRecord(c->tev[1], main)); // conversion-in is not a separate phase any more
-  if (enc)
+  if (k.enc)
     for (int r = 0; r < ch; r++) {
-      hipLaunchKernelGGL(k_convert_tiled<true>, cgrid, dim3(256), 0, conv, d_jobs, r * ctu, (r + 1) * ctu);
+      hipLaunchKernelGGL(k_convert_tiled<true>, cgrid, dim3(256), 0, conv, k.d_jobs, r * ctu, (r + 1) * ctu);
       HIPCHK(c, hipEventRecord(ev_in[r], conv));
     }
-  AcrossArgs AA{};
-  AA.ltus = p0->d_ltus;
-  AA.pic_elems = c->tiled_pic_elems;
-  for (int p = 0; p < 3; p++) AA.plane_off[p] = c->tiled_plane_off[p];
-  AA.ctu_w = c->tiled_cw;
-  AA.clog = 0;
-  while ((1 << AA.clog) < ctu) AA.clog++;
-  AA.P = p0->P;
-  std::vector<int> first(groups + 1);
-  for (int g = 0; g <= groups; g++) first[g] = (int)((long long)n_pics * g / groups);
+  const AcrossArgs AA = across_args(k);
   // rows in the order their first level comes up / their last level passes
   std::vector<int> by_first(ch), by_last(ch);
   for (int r = 0; r < ch; r++) by_first[r] = by_last[r] = r;
@@ -374,81 +428,45 @@ static int issue_across_pipelined(hmx_ctx *c, const hmx_intra_plan *p0, int n_pi
   int nf = 0, nl = 0;
   const size_t n_levels = p0->h_ltab.size();
   for (size_t l = 0; l < n_levels; l++) {
-    if (enc)
+    if (k.enc)
       for (; nf < ch && p0->row_first_level[by_first[nf]] <= (int)l; nf++)
         for (int g = 0; g < groups; g++) HIPCHK(c, hipStreamWaitEvent(c->side[g], ev_in[by_first[nf]], 0));
-    AA.row = p0->h_ltab[l];
-    for (int g = 0; g < groups; g++) {
-      const int np = first[g + 1] - first[g];
-      if (np <= 0) continue;
-      AA.pics = d_work + first[g];
-      AA.n_pics = np;
-      AA.pool_org = c->pool_org + (size_t)first[g] * c->tiled_pic_elems;
-      AA.pool_rec = c->pool_rec + (size_t)first[g] * c->tiled_pic_elems;
-      uint64_t waves = 0;
-      for (int s2 = 0; s2 < 4; s2++) {
-        const int slots = s2 == 0 ? kSlots4 : s2 == 1 ? 8 : s2 == 2 ? 4 : 1;
-        AA.cpb[s2] = (uint32_t)((np + slots - 1) / slots);
-        waves += (uint64_t)AA.row.count[s2] * AA.cpb[s2];
-      }
-      if (!waves) continue;
-      if (waves > 0x7fffffffull) return fail(c, HMX_ERR_ARG, "frame_intra: level too large for one launch");
-      if (enc)
-        hipLaunchKernelGGL(k_intra_level_across<true>, dim3((unsigned)waves), dim3(64), 0, c->side[g], AA);
-      else
-        hipLaunchKernelGGL(k_intra_level_across<false>, dim3((unsigned)waves), dim3(64), 0, c->side[g], AA);
-    }
+    for (int g = 0; g < groups; g++)
+      if (int r = launch_across_level(c, k, AA, l, g, c->side[g])) return r;
     for (; nl < ch && p0->row_last_level[by_last[nl]] <= (int)l; nl++) { // these rows are final: convert them out
       const int r = by_last[nl];
       for (int g = 0; g < groups; g++) {
         HIPCHK(c, hipEventRecord(ev_final[g * ch + r], c->side[g]));
         HIPCHK(c, hipStreamWaitEvent(conv, ev_final[g * ch + r], 0));
       }
-      hipLaunchKernelGGL(k_convert_tiled<false>, cgrid, dim3(256), 0, conv, d_jobs + (size_t)n_pics * 3, r * ctu, (r + 1) * ctu);
+      hipLaunchKernelGGL(k_convert_tiled<false>, cgrid, dim3(256), 0, conv, k.d_jobs + (size_t)k.n_pics * 3, r * ctu, (r + 1) * ctu);
     }
   }
-  // join
-  for (int g = 0; g < groups; g++) {
-    HIPCHK(c, hipEventRecord(c->ev_join[g], c->side[g]));
-    HIPCHK(c, hipStreamWaitEvent(main, c->ev_join[g], 0));
-  }
+  if (int r = join_groups(c, groups, main)) return r;
   if (c->timing) HIPCHK(c, hipEventRecord(c->tev[2], main)); // the chain is done
   HIPCHK(c, hipEventRecord(c->ev_conv_join, conv));
   HIPCHK(c, hipStreamWaitEvent(main, c->ev_conv_join, 0));
   return HMX_OK;
 }
 
-static int issue_intra_launches(hmx_ctx *c, const hmx_intra_plan *const *plans, int plan_stride, int n_pics,
-                                const PicWork *d_work, const ConvJob *d_jobs, bool enc, bool use_level, int groups,
-                                hipStream_t main) {
+static int issue_intra_launches(hmx_ctx *c, const IntraCall &k, hipStream_t main) {
   // original planes -> tiled working copies (encode), chain, tiled reconstruction -> caller's planes
-  const hmx_intra_plan *p0 = plans[0];
-  const int cw = (p0->P.pic_w + p0->P.ctu - 1) / p0->P.ctu, ch = (p0->P.pic_h + p0->P.ctu - 1) / p0->P.ctu;
-  // 64 x 64 regions of the padded luma plane (the chroma planes need a quarter of them; the rest exit)
-  const unsigned spr = (unsigned)(cw * p0->P.ctu + 63) / 64, rows = (unsigned)(ch * p0->P.ctu + 63) / 64;
-  dim3 cgrid((unsigned)n_pics, spr * rows, 3);
+  const dim3 cgrid = convert_grid(k.geom, k.n_pics, k.geom.ch * k.geom.ctu);
+  const ConvJob *jobs_rec = k.d_jobs + (size_t)k.n_pics * 3;
   const bool tm = c->timing;
   if (tm) HIPCHK(c, hipEventRecord(c->tev[0], main));
-  if (c->across_call && c->pipeline_conv) {
-    int r = issue_across_pipelined(c, p0, n_pics, d_work, d_jobs, enc, groups, main);
-    if (r) return r;
-    if (tm) {
-      HIPCHK(c, hipEventRecord(c->tev[3], main));
-      c->tev_valid = true;
-    }
-    HIPCHK(c, hipGetLastError());
-    return HMX_OK;
+  if (k.across && k.pipeline_conv) {
+    if (int r = issue_across_pipelined(c, k, main)) return r;
+  } else {
+    const bool conv = !k.resident;
+    if (conv && k.enc) hipLaunchKernelGGL(k_convert_tiled<true>, cgrid, dim3(256), 0, main, k.d_jobs, 0, 1 << 30);
+    if (conv && k.onto) // the pool starts from the caller's reconstruction (the inter-coded parts of the picture)
+      hipLaunchKernelGGL(k_convert_tiled<true>, cgrid, dim3(256), 0, main, jobs_rec, 0, 1 << 30);
+    if (tm) HIPCHK(c, hipEventRecord(c->tev[1], main));
+    if (int r = k.packed() ? issue_packed(c, k, main) : issue_chain_launches(c, k, main)) return r;
+    if (tm) HIPCHK(c, hipEventRecord(c->tev[2], main));
+    if (conv) hipLaunchKernelGGL(k_convert_tiled<false>, cgrid, dim3(256), 0, main, jobs_rec, 0, 1 << 30);
   }
-  const bool conv = !c->resident_call;
-  if (conv && enc) hipLaunchKernelGGL(k_convert_tiled<true>, cgrid, dim3(256), 0, main, d_jobs, 0, 1 << 30);
-  if (conv && c->onto_call) // the pool starts from the caller's reconstruction (the inter-coded parts of the picture)
-    hipLaunchKernelGGL(k_convert_tiled<true>, cgrid, dim3(256), 0, main, d_jobs + (size_t)n_pics * 3, 0, 1 << 30);
-  if (tm) HIPCHK(c, hipEventRecord(c->tev[1], main));
-  int r = c->last_schedule == 3 ? issue_packed(c, plans, plan_stride, n_pics, enc, main)
-                                : issue_chain_launches(c, plans, plan_stride, n_pics, d_work, enc, use_level, groups, main);
-  if (r) return r;
-  if (tm) HIPCHK(c, hipEventRecord(c->tev[2], main));
-  if (conv) hipLaunchKernelGGL(k_convert_tiled<false>, cgrid, dim3(256), 0, main, d_jobs + (size_t)n_pics * 3, 0, 1 << 30);
   if (tm) {
     HIPCHK(c, hipEventRecord(c->tev[3], main));
     c->tev_valid = true;
@@ -457,115 +475,69 @@ static int issue_intra_launches(hmx_ctx *c, const hmx_intra_plan *const *plans, 
   return HMX_OK;
 }
 
-static int issue_chain_launches(hmx_ctx *c, const hmx_intra_plan *const *plans, int plan_stride, int n_pics,
-                                const PicWork *d_work, bool enc, bool use_level, int groups, hipStream_t main) {
-  const hmx_intra_plan *p0 = plans[0];
-  if (use_level) {
-    // Pictures are split into groups; each group walks its levels on its own stream.  A launch
-    // of one group fills only part of the chip (its duration is one block-chain latency), so
-    // launches of different groups overlap.  Fork/join through events on the main stream.
-    if (groups > 1) HIPCHK(c, hipEventRecord(c->ev_fork, main));
-    std::vector<int> first(groups + 1);
-    std::vector<size_t> glevels(groups, 0);
-    for (int g = 0; g <= groups; g++) first[g] = (int)((long long)n_pics * g / groups);
-    for (int g = 0; g < groups; g++) {
-      if (groups > 1) HIPCHK(c, hipStreamWaitEvent(c->side[g], c->ev_fork, 0));
-      for (int i = first[g]; i < first[g + 1]; i++) glevels[g] = std::max(glevels[g], (size_t)plans[i * plan_stride]->n_levels);
+static int issue_chain_launches(hmx_ctx *c, const IntraCall &k, hipStream_t main) {
+  const hmx_intra_plan *p0 = k.plans[0];
+  const int groups = k.groups;
+  if (!k.use_level()) { // one launch per CTU diagonal, autonomous waves
+    FrameArgs A;
+    A.pics = k.d_work;
+    A.P = p0->P;
+    for (auto &w : p0->waves) {
+      if (!w.second) continue;
+      A.wave_ctus = p0->d_wave_ctus + w.first;
+      A.n_wave_ctus = (int)w.second;
+      const dim3 grid((unsigned)(w.second * k.n_pics * 3));
+      with_bool(k.enc, [&](auto E) { hipLaunchKernelGGL(k_intra_wave<E>, grid, dim3(64), 0, main, A); });
     }
-    size_t n_levels = 0;
-    for (int g = 0; g < groups; g++) n_levels = std::max(n_levels, glevels[g]);
-    // one plan for every picture: SIMD across pictures (k_intra_level_across); every group of pictures
-    // is its own interleave domain of the pool (see frame_intra) and walks the levels on its own stream
-    if (c->across_call) {
-      AcrossArgs AA{};
-      AA.ltus = p0->d_ltus;
-      AA.pic_elems = c->tiled_pic_elems;
-      for (int p = 0; p < 3; p++) AA.plane_off[p] = c->tiled_plane_off[p];
-      AA.ctu_w = c->tiled_cw;
-      AA.clog = 0;
-      while ((1 << AA.clog) < p0->P.ctu) AA.clog++;
-      AA.P = p0->P;
-      for (size_t l = 0; l < n_levels; l++) {
-        AA.row = p0->h_ltab[l];
-        for (int g = 0; g < groups; g++) {
-          const int np = first[g + 1] - first[g];
-          if (np <= 0) continue;
-          AA.pics = d_work + first[g];
-          AA.n_pics = np;
-          AA.pool_org = c->pool_org + (size_t)first[g] * c->tiled_pic_elems;
-          AA.pool_rec = c->pool_rec + (size_t)first[g] * c->tiled_pic_elems;
-          uint64_t waves = 0;
-          for (int s2 = 0; s2 < 4; s2++) {
-            const int slots = s2 == 0 ? kSlots4 : s2 == 1 ? 8 : s2 == 2 ? 4 : 1;
-            AA.cpb[s2] = (uint32_t)((np + slots - 1) / slots);
-            waves += (uint64_t)AA.row.count[s2] * AA.cpb[s2];
-          }
-          if (!waves) continue;
-          if (waves > 0x7fffffffull) return fail(c, HMX_ERR_ARG, "frame_intra: level too large for one launch");
-          hipStream_t st = groups > 1 ? c->side[g] : main;
-          if (enc)
-            hipLaunchKernelGGL(k_intra_level_across<true>, dim3((unsigned)waves), dim3(64), 0, st, AA);
-          else
-            hipLaunchKernelGGL(k_intra_level_across<false>, dim3((unsigned)waves), dim3(64), 0, st, AA);
-        }
-      }
-      if (groups > 1)
-        for (int g = 0; g < groups; g++) {
-          HIPCHK(c, hipEventRecord(c->ev_join[g], c->side[g]));
-          HIPCHK(c, hipStreamWaitEvent(main, c->ev_join[g], 0));
-        }
-      HIPCHK(c, hipGetLastError());
-      return HMX_OK;
-    }
+    HIPCHK(c, hipGetLastError());
+    return HMX_OK;
+  }
+  // Pictures are split into groups; each group walks its levels on its own stream.  A launch
+  // of one group fills only part of the chip (its duration is one block-chain latency), so
+  // launches of different groups overlap.
+  if (groups > 1)
+    if (int r = fork_groups(c, groups, main)) return r;
+  auto stream_of = [&](int g) { return groups > 1 ? c->side[g] : main; };
+  std::vector<size_t> glevels(groups, 0);
+  size_t n_levels = 0;
+  for (int g = 0; g < groups; g++) {
+    for (int i = k.group_first(g); i < k.group_first(g + 1); i++) glevels[g] = std::max(glevels[g], (size_t)k.plan(i)->n_levels);
+    n_levels = std::max(n_levels, glevels[g]);
+  }
+  if (k.across) {
+    const AcrossArgs AA = across_args(k);
+    for (size_t l = 0; l < n_levels; l++)
+      for (int g = 0; g < groups; g++)
+        if (int r = launch_across_level(c, k, AA, l, g, stream_of(g))) return r;
+  } else {
     LevelArgs LA{};
     LA.P = p0->P;
     for (size_t l = 0; l < n_levels; l++)
       for (int g = 0; g < groups; g++) {
         if (l >= glevels[g]) continue;
+        const int first = k.group_first(g), end = k.group_first(g + 1);
         uint32_t chunks = 0;
-        if (plan_stride == 0)
+        if (k.plan_stride == 0)
           chunks = p0->level_chunks[l];
         else
-          for (int i = first[g]; i < first[g + 1]; i++) {
-            const auto &lc = plans[i]->level_chunks;
+          for (int i = first; i < end; i++) {
+            const auto &lc = k.plan(i)->level_chunks;
             if (l < lc.size()) chunks = std::max(chunks, lc[l]);
           }
         if (!chunks) continue;
-        LA.pics = d_work + first[g];
+        LA.pics = k.d_work + first;
         LA.level = (int)l;
-        LA.shared = plan_stride == 0;
+        LA.shared = k.plan_stride == 0;
         if (LA.shared) {
           LA.row = p0->h_ltab[l];
           LA.ltus = p0->d_ltus;
         }
-        dim3 grid(chunks, (unsigned)(first[g + 1] - first[g]));
-        hipStream_t st = groups > 1 ? c->side[g] : main;
-        if (enc)
-          hipLaunchKernelGGL(k_intra_level<true>, grid, dim3(64), 0, st, LA);
-        else
-          hipLaunchKernelGGL(k_intra_level<false>, grid, dim3(64), 0, st, LA);
+        const dim3 grid(chunks, (unsigned)(end - first));
+        with_bool(k.enc, [&](auto E) { hipLaunchKernelGGL(k_intra_level<E>, grid, dim3(64), 0, stream_of(g), LA); });
       }
-    if (groups > 1)
-      for (int g = 0; g < groups; g++) {
-        HIPCHK(c, hipEventRecord(c->ev_join[g], c->side[g]));
-        HIPCHK(c, hipStreamWaitEvent(main, c->ev_join[g], 0));
-      }
-    HIPCHK(c, hipGetLastError());
-    return HMX_OK;
   }
-  FrameArgs A;
-  A.pics = d_work;
-  A.P = p0->P;
-  for (auto &w : p0->waves) {
-    if (!w.second) continue;
-    A.wave_ctus = p0->d_wave_ctus + w.first;
-    A.n_wave_ctus = (int)w.second;
-    dim3 grid((unsigned)(w.second * n_pics * 3));
-    if (enc)
-      hipLaunchKernelGGL(k_intra_wave<true>, grid, dim3(64), 0, main, A);
-    else
-      hipLaunchKernelGGL(k_intra_wave<false>, grid, dim3(64), 0, main, A);
-  }
+  if (groups > 1)
+    if (int r = join_groups(c, groups, main)) return r;
   HIPCHK(c, hipGetLastError());
   return HMX_OK;
 }
@@ -585,19 +557,11 @@ int pack_group_size(const hmx_ctx *c, int n_pics) {
 extern "C" int hmx_tpool_create(hmx_ctx *c, int pic_w, int pic_h, int n_pics, hmx_tpool **out) {
   if (!c || !out || pic_w <= 0 || pic_h <= 0 || n_pics <= 0) return fail(c, HMX_ERR_ARG, "hmx_tpool_create: bad argument");
   hmx_tpool *t = new hmx_tpool;
-  t->ctu = c->cfg.ctu_size;
-  t->pic_w = pic_w, t->pic_h = pic_h;
-  t->cw = (pic_w + t->ctu - 1) / t->ctu, t->ch = (pic_h + t->ctu - 1) / t->ctu;
+  t->geom = tiled_geom(pic_w, pic_h, c->cfg.ctu_size);
   t->n_pics = n_pics;
   t->I = pack_group_size(c, n_pics);
-  size_t off = 0;
-  for (int p = 0; p < 3; p++) {
-    t->plane_off[p] = (uint32_t)off;
-    off += (size_t)t->cw * t->ch * ((size_t)t->ctu * t->ctu >> (p ? 2 : 0));
-  }
-  t->pic_elems = off;
   const size_t slots = (size_t)(n_pics + t->I - 1) / t->I * t->I;
-  if (hipMalloc((void **)&t->base, off * 2 * slots) != hipSuccess) {
+  if (hipMalloc((void **)&t->base, t->geom.pic_elems * 2 * slots) != hipSuccess) {
     delete t;
     return fail(c, HMX_ERR_NOMEM, "hipMalloc resident pictures");
   }
@@ -619,15 +583,13 @@ static int tpool_convert(hmx_ctx *c, const hmx_tpool *t, int first, int n, const
   std::vector<ConvJob> jobs((size_t)n * 3);
   for (int i = 0; i < n; i++)
     for (int p = 0; p < 3; p++)
-      jobs[(size_t)i * 3 + p] = ConvJob{planes[i].plane[p], planes[i].stride[p], t->pic_w >> (p ? 1 : 0), t->pic_h >> (p ? 1 : 0), tpool_plane(t, first + i, p)};
+      jobs[(size_t)i * 3 + p] = ConvJob{planes[i].plane[p], planes[i].stride[p], t->geom.pic_w >> (p ? 1 : 0), t->geom.pic_h >> (p ? 1 : 0), tpool_plane(t, first + i, p)};
   for (size_t done = 0; done < jobs.size();) { // through the argument arena, a few thousand jobs at a time
     const size_t part = std::min(jobs.size() - done, (size_t)3 * 8192);
     const ConvJob *d = static_cast<const ConvJob *>(arena_push(c, jobs.data() + done, sizeof(ConvJob) * part));
     if (!d) return fail(c, HMX_ERR_NOMEM, "argument arena");
-    const unsigned spr = (unsigned)(t->cw * t->ctu + 63) / 64, rows = (unsigned)(t->ch * t->ctu + 63) / 64;
-    const dim3 grid((unsigned)(part / 3), spr * rows, 3);
-    if (to_tiled) hipLaunchKernelGGL(k_convert_tiled<true>, grid, dim3(256), 0, c->stream, d, 0, 1 << 30);
-    else hipLaunchKernelGGL(k_convert_tiled<false>, grid, dim3(256), 0, c->stream, d, 0, 1 << 30);
+    const dim3 grid = convert_grid(t->geom, (int)(part / 3), t->geom.ch * t->geom.ctu);
+    with_bool(to_tiled, [&](auto T) { hipLaunchKernelGGL(k_convert_tiled<T>, grid, dim3(256), 0, c->stream, d, 0, 1 << 30); });
     done += part;
   }
   HIPCHK(c, hipGetLastError());
@@ -636,80 +598,36 @@ static int tpool_convert(hmx_ctx *c, const hmx_tpool *t, int first, int n, const
 extern "C" int hmx_tpool_import(hmx_ctx *c, hmx_tpool *t, int first, int n, const hmx_pic *src) { return tpool_convert(c, t, first, n, src, true); }
 extern "C" int hmx_tpool_export(hmx_ctx *c, const hmx_tpool *t, int first, int n, const hmx_pic *dst) { return tpool_convert(c, t, first, n, dst, false); }
 
-// org / rec: pictures in plane geometry (converted into / out of the context's own working pools around the chain), or
-// NULL with torg / trec: pictures resident in the working layout (no conversion; packed schedule only)
-static int frame_intra(hmx_ctx *c, const hmx_intra_plan *const *plans, int plan_stride, int n_pics, const hmx_pic *org,
-                       const hmx_pic *rec, const hmx_levels *lev, bool enc, const hmx_tpool *torg = nullptr,
-                       const hmx_tpool *trec = nullptr) {
-  const bool resident = trec != nullptr;
-  if (!c || !plans || !plans[0] || n_pics <= 0 || !lev || (!resident && (!rec || (enc && !org))) || (resident && enc && !torg))
-    return fail(c, HMX_ERR_ARG, "frame_intra: null argument");
-  const hmx_intra_plan *p0 = plans[0];
-  const int ctu = p0->P.ctu, cw = (p0->P.pic_w + ctu - 1) / ctu, ch = (p0->P.pic_h + ctu - 1) / ctu;
-  const int clog = ilog2i(ctu);
+// ---- one whole-picture call, step by step (frame_intra below puts the steps together) ----
+// What the call resolves to -- schedule, groups, group size, geometry -- and whether its pools and plans fit that.
+static int resolve_call(hmx_ctx *c, IntraCall &k, const hmx_tpool *torg, const hmx_tpool *trec) {
+  const hmx_intra_plan *p0 = k.plans[0];
   // Schedules.  "packed" (default): ONE persistent launch, blocks of equal size and dependency level
   // packed into waves across pictures, each picture following its own plan, the dependency order kept by counters in
   // memory.  The level-synchronous schedules stay as cross-checks and for A/B runs (HMX_INTRA_SCHEDULE=level|wave):
   // "level" = one launch per picture-wide dependency level (pictures that share ONE plan run it across pictures on a
   // pool interleaved per stream group), "wave" = one launch per CTU diagonal with autonomous waves.
-  const int sched_base = resident ? 3 : c->knob.schedule >= 0 ? c->knob.schedule : 3;
+  const int sched_base = k.resident ? 3 : c->knob.schedule >= 0 ? c->knob.schedule : 3;
   const bool packed = sched_base == 3, use_level = sched_base == 1;
-  const bool across = use_level && plan_stride == 0 && c->knob.across != 0;
+  k.across = use_level && k.plan_stride == 0 && c->knob.across != 0;
+  k.schedule = packed ? 3 : !use_level ? 0 : (k.across ? 2 : 1);
   // Picture groups of the across schedule on separate streams: measured at 1024 pictures 64.8 / 73.6 / 76.1 / 51.8 Gpx/s
   // with 1 / 2 / 3 / 4 groups.
-  int groups = !across ? 1 : n_pics >= 640 ? 3 : n_pics >= 384 ? 2 : 1;
-  if (use_level && c->knob.streams > 0) groups = std::min(std::max(c->knob.streams, 1), std::min(n_pics, (int)hmx_ctx::kMaxSide));
+  k.groups = !k.across ? 1 : k.n_pics >= 640 ? 3 : k.n_pics >= 384 ? 2 : 1;
+  if (use_level && c->knob.streams > 0) k.groups = std::min(std::max(c->knob.streams, 1), std::min(k.n_pics, (int)hmx_ctx::kMaxSide));
   // packed: groups of I pictures are the interleave domains of the pool and the lanes of the tables' prep kernels
-  const int I = resident ? trec->I : packed ? pack_group_size(c, n_pics) : 1, pool_need = packed ? (n_pics + I - 1) / I * I : n_pics;
-  {
-    size_t off = 0;
-    for (int p = 0; p < 3; p++) {
-      c->tiled_plane_off[p] = (uint32_t)off;
-      off += (size_t)cw * ch * ((size_t)ctu * ctu >> (p ? 2 : 0));
-    }
-    c->tiled_pic_elems = off;
-  }
-  if (resident) { // the caller's pools: same geometry as the plans, at least n_pics pictures, one interleave
-    for (const hmx_tpool *t : {trec, enc ? torg : trec})
-      if (t->cw != cw || t->ch != ch || t->ctu != ctu || t->pic_w != p0->P.pic_w || t->pic_h != p0->P.pic_h || t->n_pics < n_pics || t->I != I)
+  k.I = k.resident ? trec->I : packed ? pack_group_size(c, k.n_pics) : 1;
+  k.geom = tiled_geom(p0->P.pic_w, p0->P.pic_h, p0->P.ctu);
+  if (k.resident) // the caller's pools: same geometry as the plans, at least n_pics pictures, one interleave
+    for (const hmx_tpool *t : {trec, k.enc ? torg : trec})
+      if (!(t->geom == k.geom) || t->n_pics < k.n_pics || t->I != k.I)
         return fail(c, HMX_ERR_ARG, "frame_intra: resident pool does not match the call (picture size, CTU size, pictures, group size)");
-    c->pool_org = enc ? torg->base : nullptr;
-    c->pool_rec = trec->base;
-    c->tiled_cw = cw, c->tiled_ch = ch;
-  } else {
-    // the context's own working pools: one slot per picture, planes padded to whole CTUs
-    if (c->own_cw != cw || c->own_ch != ch || c->pool_pics < pool_need) {
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-      hipFree(c->own_pool_org);
-      hipFree(c->own_pool_rec);
-      c->own_pool_org = c->own_pool_rec = nullptr;
-      c->pool_pics = 0;
-      c->own_cw = cw, c->own_ch = ch;
-      c->table_valid = false;
-      c->pk.valid = false;
-      if (hipMalloc((void **)&c->own_pool_org, c->tiled_pic_elems * 2 * pool_need) != hipSuccess ||
-          hipMalloc((void **)&c->own_pool_rec, c->tiled_pic_elems * 2 * pool_need) != hipSuccess) {
-        hipFree(c->own_pool_org);
-        c->own_pool_org = nullptr;
-        return fail(c, HMX_ERR_NOMEM, "hipMalloc tiled working pictures");
-      }
-      c->pool_pics = pool_need;
-    }
-    c->pool_org = c->own_pool_org, c->pool_rec = c->own_pool_rec;
-    c->tiled_cw = cw, c->tiled_ch = ch;
-  }
-  c->resident_call = resident;
-  c->across_call = across;
-  c->pack_I = I;
-  c->call_lev = lev;
   // Conversions pipelined with the chain, CTU row by CTU row (issue_across_pipelined): opt-in, across schedule only.
-  c->pipeline_conv = c->knob.pipeline_conv && across && !c->knob.graph && !c->onto_call;
-  c->last_schedule = packed ? 3 : !use_level ? 0 : (across ? 2 : 1);
-  c->last_groups = groups;
-  std::vector<PicWork> hw(n_pics);
-  std::vector<ConvJob> jobs((size_t)n_pics * 6);
-  for (int i = 0; i < n_pics; i++) {
-    const hmx_intra_plan *pl = plans[i * plan_stride];
+  k.pipeline_conv = c->knob.pipeline_conv && k.across && !c->knob.graph && !k.onto;
+  c->last_schedule = k.schedule;
+  c->last_groups = k.groups;
+  for (int i = 0; i < k.n_pics; i++) {
+    const hmx_intra_plan *pl = k.plan(i);
     if (!pl || pl->P.pic_w != p0->P.pic_w || pl->P.pic_h != p0->P.pic_h || pl->qp != p0->qp ||
         pl->chroma_qp_offset != p0->chroma_qp_offset || pl->slice_type != p0->slice_type ||
         pl->P.sign_hide != p0->P.sign_hide)
@@ -717,28 +635,70 @@ static int frame_intra(hmx_ctx *c, const hmx_intra_plan *const *plans, int plan_
     if (pl->set && !packed) { // built on the device: the packed schedule's tables only
       if (!use_level) return fail(c, HMX_ERR_ARG, "frame_intra: a plan built on the device has no tables for the wave schedule (HMX_INTRA_SCHEDULE=packed|level)");
       if (int r = plan_host_tables(c, pl)) return r; // the level schedule walks the level table on the host
-      c->pipeline_conv = false;                      // (no per-CTU-row level ranges either)
+      k.pipeline_conv = false;                       // (no per-CTU-row level ranges either)
     }
+  }
+  return HMX_OK;
+}
+// The pools the call works on: the caller's resident ones, or the context's own (one slot per picture, grown when the call needs more)
+static int ensure_pools(hmx_ctx *c, IntraCall &k, const hmx_tpool *torg, const hmx_tpool *trec) {
+  if (k.resident) {
+    k.pool_org = k.enc ? torg->base : nullptr;
+    k.pool_rec = trec->base;
+    return HMX_OK;
+  }
+  const int pool_need = k.packed() ? (k.n_pics + k.I - 1) / k.I * k.I : k.n_pics;
+  if (c->own_cw != k.geom.cw || c->own_ch != k.geom.ch || c->pool_pics < pool_need) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    hipFree(c->own_pool_org);
+    hipFree(c->own_pool_rec);
+    c->own_pool_org = c->own_pool_rec = nullptr;
+    c->pool_pics = 0;
+    c->own_cw = k.geom.cw, c->own_ch = k.geom.ch;
+    c->table_valid = false;
+    c->pk.valid = false;
+    if (hipMalloc((void **)&c->own_pool_org, k.geom.pic_elems * 2 * pool_need) != hipSuccess ||
+        hipMalloc((void **)&c->own_pool_rec, k.geom.pic_elems * 2 * pool_need) != hipSuccess) {
+      hipFree(c->own_pool_org);
+      c->own_pool_org = nullptr;
+      return fail(c, HMX_ERR_NOMEM, "hipMalloc tiled working pictures");
+    }
+    c->pool_pics = pool_need;
+  }
+  k.pool_org = c->own_pool_org, k.pool_rec = c->own_pool_rec;
+  return HMX_OK;
+}
+// The side streams and events of the level schedule's picture groups
+static int ensure_side_streams(hmx_ctx *c, const IntraCall &k) {
+  if (!k.use_level() || k.groups <= 1 || c->n_side >= k.groups) return HMX_OK;
+  if (!c->ev_fork) HIPCHK(c, hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
+  for (int g = c->n_side; g < k.groups; g++) {
+    HIPCHK(c, hipStreamCreateWithFlags(&c->side[g], hipStreamNonBlocking));
+    HIPCHK(c, hipEventCreateWithFlags(&c->ev_join[g], hipEventDisableTiming));
+  }
+  c->n_side = k.groups;
+  return HMX_OK;
+}
+// The picture table (hw) and the conversion jobs of the call: to-tiled jobs of the originals, then the jobs of the reconstruction
+static void build_tables(const IntraCall &k, const hmx_pic *org, const hmx_pic *rec, std::vector<PicWork> &hw, std::vector<ConvJob> &jobs) {
+  hw.resize(k.n_pics);
+  jobs.resize((size_t)k.n_pics * 6);
+  for (int i = 0; i < k.n_pics; i++) {
+    const hmx_intra_plan *pl = k.plan(i);
+    // interleave domain [g0, g1) of picture i: a stream group (across), a group of I pictures (packed), itself
+    int g0 = i, g1 = i + 1;
+    if (k.packed()) g0 = i / k.I * k.I, g1 = g0 + k.I;
+    else if (k.across) g0 = k.group_first(k.group_of(i)), g1 = k.group_first(k.group_of(i) + 1);
     memset(&hw[i], 0, sizeof(PicWork));
     for (int p = 0; p < 3; p++) {
-      const int pclog = p ? clog - 1 : clog, pw = p0->P.pic_w >> (p ? 1 : 0), ph = p0->P.pic_h >> (p ? 1 : 0);
-      // interleave domain [g0, g1) of picture i: a stream group (across), a group of I pictures (packed), itself
-      int g0 = i, g1 = i + 1;
-      if (packed) {
-        g0 = i / I * I, g1 = g0 + I;
-      } else if (across) {
-        const int g = (int)(((long long)(i + 1) * groups - 1) / n_pics); // the g with first[g] <= i < first[g+1]
-        g0 = (int)((long long)n_pics * g / groups), g1 = (int)((long long)n_pics * (g + 1) / groups);
-      }
-      const size_t base = (size_t)g0 * c->tiled_pic_elems + (size_t)c->tiled_plane_off[p] * (g1 - g0) + (size_t)(i - g0) * 64;
-      const unsigned qstride = 64u * (unsigned)(g1 - g0);
-      hw[i].org[p] = TiledPlane{c->pool_org ? c->pool_org + base : nullptr, cw, pclog, qstride};
-      hw[i].rec[p] = TiledPlane{c->pool_rec + base, cw, pclog, qstride};
-      hw[i].lev[p] = lev[i].plane[p];
-      hw[i].lev_stride[p] = lev[i].stride[p];
-      if (!resident) {
-        if (enc) jobs[(size_t)i * 3 + p] = ConvJob{org[i].plane[p], org[i].stride[p], pw, ph, hw[i].org[p]};
-        jobs[(size_t)(n_pics + i) * 3 + p] = ConvJob{rec[i].plane[p], rec[i].stride[p], pw, ph, hw[i].rec[p]};
+      const int pw = k.geom.pic_w >> (p ? 1 : 0), ph = k.geom.pic_h >> (p ? 1 : 0);
+      hw[i].org[p] = tiled_plane(k.geom, k.pool_org, i, p, g0, g1);
+      hw[i].rec[p] = tiled_plane(k.geom, k.pool_rec, i, p, g0, g1);
+      hw[i].lev[p] = k.lev[i].plane[p];
+      hw[i].lev_stride[p] = k.lev[i].stride[p];
+      if (!k.resident) {
+        if (k.enc) jobs[(size_t)i * 3 + p] = ConvJob{org[i].plane[p], org[i].stride[p], pw, ph, hw[i].org[p]};
+        jobs[(size_t)(k.n_pics + i) * 3 + p] = ConvJob{rec[i].plane[p], rec[i].stride[p], pw, ph, hw[i].rec[p]};
       }
     }
     hw[i].tus = pl->d_tus;
@@ -748,20 +708,15 @@ static int frame_intra(hmx_ctx *c, const hmx_intra_plan *const *plans, int plan_
     hw[i].ltab = pl->d_ltab;
     hw[i].n_levels = pl->n_levels;
   }
-  if (use_level && groups > 1 && c->n_side < groups) {
-    if (!c->ev_fork) HIPCHK(c, hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-    for (int g = c->n_side; g < groups; g++) {
-      HIPCHK(c, hipStreamCreateWithFlags(&c->side[g], hipStreamNonBlocking));
-      HIPCHK(c, hipEventCreateWithFlags(&c->ev_join[g], hipEventDisableTiming));
-    }
-    c->n_side = groups;
-  }
-  // Key of the call = the picture table itself (planes, level buffers, plans, schedule).  A steady-state pipeline
-  // re-uses its picture pools: the device copy of the table (and the packed schedule's tables) is then kept as it is,
-  // and the call is queued behind the previous one without any synchronisation.
-  uint64_t key = 1469598103934665603ull;
-  std::vector<unsigned char> kb; // the bytes the key is formed from: two calls are "the same" when these are, not when a hash says so
-  kb.reserve(sizeof(PicWork) * n_pics + sizeof(ConvJob) * jobs.size() + 24 * (size_t)n_pics + 64);
+}
+// Key of the call = the picture table itself (planes, level buffers, plans, schedule).  A steady-state pipeline
+// re-uses its picture pools: the device copy of the table (and the packed schedule's tables) is then kept as it is,
+// and the call is queued behind the previous one without any synchronisation.
+// kb: the bytes the key is formed from: two calls are "the same" when these are, not when a hash says so
+static int table_key_of(hmx_ctx *c, const IntraCall &k, const std::vector<PicWork> &hw, const std::vector<ConvJob> &jobs, uint64_t &key,
+                        std::vector<unsigned char> &kb) {
+  key = 1469598103934665603ull;
+  kb.reserve(sizeof(PicWork) * k.n_pics + sizeof(ConvJob) * jobs.size() + 24 * (size_t)k.n_pics + 64);
   auto mix = [&](const void *p, size_t n) { // FNV-1a over 8-byte words (the table of a 2048-picture call is ~1 MB, hashed on every call)
     const unsigned char *b = (const unsigned char *)p;
     size_t i = 0;
@@ -773,69 +728,74 @@ static int frame_intra(hmx_ctx *c, const hmx_intra_plan *const *plans, int plan_
     for (; i < n; i++) key = (key ^ b[i]) * 1099511628211ull;
     kb.insert(kb.end(), b, b + n);
   };
-  mix(hw.data(), sizeof(PicWork) * n_pics);
+  mix(hw.data(), sizeof(PicWork) * k.n_pics);
   mix(jobs.data(), sizeof(ConvJob) * jobs.size());
-  const int flags[6] = {enc, c->last_schedule, groups, n_pics, across, I};
+  const int flags[6] = {k.enc, k.schedule, k.groups, k.n_pics, k.across, k.I};
   mix(flags, sizeof(flags));
-  if (enc && c->crq.n > 0) {
-    if (!packed) return fail(c, HMX_ERR_ARG, "frame_intra: RDOQ as the quantiser (hmx_set_rdoq) needs the packed schedule");
+  if (k.enc && c->crq.n > 0) {
+    if (!k.packed()) return fail(c, HMX_ERR_ARG, "frame_intra: RDOQ as the quantiser (hmx_set_rdoq) needs the packed schedule");
     mix(&c->crq.serial, sizeof(c->crq.serial)); // 4x4 blocks then always go one per lane: another table
   }
-  if (enc && (int)c->sse_out.size() >= n_pics) {
-    if (!packed) return fail(c, HMX_ERR_ARG, "frame_intra: the distortion output (hmx_set_sse_output) needs the packed schedule");
-    mix(c->sse_out.data(), sizeof(hmx_sse) * n_pics);
+  if (k.enc && (int)c->sse_out.size() >= k.n_pics) {
+    if (!k.packed()) return fail(c, HMX_ERR_ARG, "frame_intra: the distortion output (hmx_set_sse_output) needs the packed schedule");
+    mix(c->sse_out.data(), sizeof(hmx_sse) * k.n_pics);
   }
-  for (int i = 0; i < n_pics; i++) {
-    const hmx_intra_plan *pp = plans[i * plan_stride];
+  for (int i = 0; i < k.n_pics; i++) {
+    const hmx_intra_plan *pp = k.plan(i);
     mix(&pp, sizeof(pp));
     mix(&pp->serial, sizeof(pp->serial)); // a destroyed plan's address may come back
   }
   if (c->table_valid && c->table_key == key && c->table_bytes != kb) // two different calls, one hash: never mistake one for the other
     key = key * 1099511628211ull + ++c->table_salt;
-  const bool use_graph = c->knob.graph && !packed; // measured: replay is not faster than eager launches here
-  hmx_ctx::GraphEntry *hit = nullptr;
+  return HMX_OK;
+}
+// Eager path: the tables go into ONE grow-only allocation of the context, and only when they are not the ones already there
+static int upload_table(hmx_ctx *c, IntraCall &k, const std::vector<PicWork> &hw, const std::vector<ConvJob> &jobs, uint64_t key,
+                        std::vector<unsigned char> &kb) {
+  const size_t work_bytes = sizeof(PicWork) * k.n_pics, table_bytes = work_bytes + sizeof(ConvJob) * jobs.size();
+  if ((int)table_bytes > c->jobs_cap) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    hipFree(c->d_jobs);
+    c->jobs_cap = 0;
+    c->table_valid = false;
+    if (hipMalloc((void **)&c->d_jobs, table_bytes) != hipSuccess) return fail(c, HMX_ERR_NOMEM, "hipMalloc picture table");
+    c->jobs_cap = (int)table_bytes;
+  }
+  char *base = reinterpret_cast<char *>(c->d_jobs);
+  if (!c->table_valid || c->table_key != key) {
+    // earlier calls may still read the table: the copies are ordered behind them on the stream; the host vectors go
+    // out of scope, hence the synchronisation -- on this path only
+    HIPCHK(c, hipMemcpyAsync(base, hw.data(), work_bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(base + work_bytes, jobs.data(), sizeof(ConvJob) * jobs.size(), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->table_key = key;
+    c->table_bytes.swap(kb);
+    c->table_valid = true;
+  }
+  k.d_work = reinterpret_cast<const PicWork *>(base);
+  k.d_jobs = reinterpret_cast<const ConvJob *>(base + work_bytes);
+  return HMX_OK;
+}
+// HMX_GRAPH (level and wave schedules; measured: replay is not faster than eager launches here): the call is recorded as a HIP
+// graph with a table of its own and replayed when the same call comes again; the six most recently used graphs are kept
+static int run_graph(hmx_ctx *c, IntraCall &k, const std::vector<PicWork> &hw, const std::vector<ConvJob> &jobs, uint64_t key) {
   for (auto &e : c->graphs)
-    if (e.key == key && e.n_pics == n_pics) hit = &e;
-  if (use_graph && hit) {
-    hit->stamp = ++c->graph_clock;
-    HIPCHK(c, hipGraphLaunch(hit->exec, c->stream));
-    return HMX_OK;
-  }
+    if (e.key == key && e.n_pics == k.n_pics) {
+      e.stamp = ++c->graph_clock;
+      HIPCHK(c, hipGraphLaunch(e.exec, c->stream));
+      return HMX_OK;
+    }
   PicWork *d_work = nullptr;
-  const size_t table_bytes = sizeof(PicWork) * n_pics + sizeof(ConvJob) * jobs.size();
-  if (!use_graph) { // eager path: one grow-only table in the context
-    if ((int)table_bytes > c->jobs_cap) {
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-      hipFree(c->d_jobs);
-      c->jobs_cap = 0;
-      c->table_valid = false;
-      if (hipMalloc((void **)&c->d_jobs, table_bytes) != hipSuccess) return fail(c, HMX_ERR_NOMEM, "hipMalloc picture table");
-      c->jobs_cap = (int)table_bytes;
-    }
-    char *base = reinterpret_cast<char *>(c->d_jobs);
-    if (!c->table_valid || c->table_key != key) {
-      // earlier calls may still read the table: the copies are ordered behind them on the stream; the host vectors go
-      // out of scope, hence the synchronisation -- on this path only
-      HIPCHK(c, hipMemcpyAsync(base, hw.data(), sizeof(PicWork) * n_pics, hipMemcpyHostToDevice, c->stream));
-      HIPCHK(c, hipMemcpyAsync(base + sizeof(PicWork) * n_pics, jobs.data(), sizeof(ConvJob) * jobs.size(), hipMemcpyHostToDevice,
-                               c->stream));
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-      c->table_key = key;
-      c->table_bytes.swap(kb);
-      c->table_valid = true;
-    }
-    return issue_intra_launches(c, plans, plan_stride, n_pics, reinterpret_cast<PicWork *>(base),
-                                reinterpret_cast<ConvJob *>(base + sizeof(PicWork) * n_pics), enc, use_level, groups, c->stream);
-  }
+  const size_t work_bytes = sizeof(PicWork) * k.n_pics, table_bytes = work_bytes + sizeof(ConvJob) * jobs.size();
   if (hipMalloc((void **)&d_work, table_bytes) != hipSuccess) return fail(c, HMX_ERR_NOMEM, "hipMalloc picture table");
-  HIPCHK(c, hipMemcpyAsync(d_work, hw.data(), sizeof(PicWork) * n_pics, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(reinterpret_cast<char *>(d_work) + sizeof(PicWork) * n_pics, jobs.data(),
-                           sizeof(ConvJob) * jobs.size(), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(d_work, hw.data(), work_bytes, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(reinterpret_cast<char *>(d_work) + work_bytes, jobs.data(), sizeof(ConvJob) * jobs.size(), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream)); // hw / jobs go out of scope
-  const ConvJob *d_jobs = reinterpret_cast<const ConvJob *>(reinterpret_cast<char *>(d_work) + sizeof(PicWork) * n_pics);
+  k.d_work = d_work;
+  k.d_jobs = reinterpret_cast<const ConvJob *>(reinterpret_cast<char *>(d_work) + work_bytes);
   hipGraph_t graph = nullptr;
   HIPCHK(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-  int r = issue_intra_launches(c, plans, plan_stride, n_pics, d_work, d_jobs, enc, use_level, groups, c->stream);
+  int r = issue_intra_launches(c, k, c->stream);
   hipError_t ce = hipStreamEndCapture(c->stream, &graph);
   if (r != HMX_OK || ce != hipSuccess) {
     if (graph) hipGraphDestroy(graph);
@@ -858,9 +818,35 @@ static int frame_intra(hmx_ctx *c, const hmx_intra_plan *const *plans, int plan_
     hipFree(c->graphs[v].d_work);
     c->graphs.erase(c->graphs.begin() + v);
   }
-  c->graphs.push_back(hmx_ctx::GraphEntry{key, n_pics, exec, d_work, ++c->graph_clock});
+  c->graphs.push_back(hmx_ctx::GraphEntry{key, k.n_pics, exec, d_work, ++c->graph_clock});
   HIPCHK(c, hipGraphLaunch(exec, c->stream));
   return HMX_OK;
+}
+
+// org / rec: pictures in plane geometry (converted into / out of the context's own working pools around the chain), or
+// NULL with torg / trec: pictures resident in the working layout (no conversion; packed schedule only).
+// onto: the call reconstructs onto what the reconstruction planes already hold
+static int frame_intra(hmx_ctx *c, const hmx_intra_plan *const *plans, int plan_stride, int n_pics, const hmx_pic *org,
+                       const hmx_pic *rec, const hmx_levels *lev, bool enc, bool onto = false, const hmx_tpool *torg = nullptr,
+                       const hmx_tpool *trec = nullptr) {
+  const bool resident = trec != nullptr;
+  if (!c || !plans || !plans[0] || n_pics <= 0 || !lev || (!resident && (!rec || (enc && !org))) || (resident && enc && !torg))
+    return fail(c, HMX_ERR_ARG, "frame_intra: null argument");
+  IntraCall k{};
+  k.enc = enc, k.onto = onto, k.resident = resident;
+  k.plans = plans, k.plan_stride = plan_stride, k.n_pics = n_pics, k.lev = lev;
+  if (int r = resolve_call(c, k, torg, trec)) return r;
+  if (int r = ensure_pools(c, k, torg, trec)) return r;
+  std::vector<PicWork> hw;
+  std::vector<ConvJob> jobs;
+  build_tables(k, org, rec, hw, jobs);
+  if (int r = ensure_side_streams(c, k)) return r;
+  uint64_t key = 0;
+  std::vector<unsigned char> kb;
+  if (int r = table_key_of(c, k, hw, jobs, key, kb)) return r;
+  if (c->knob.graph && !k.packed()) return run_graph(c, k, hw, jobs, key);
+  if (int r = upload_table(c, k, hw, jobs, key, kb)) return r;
+  return issue_intra_launches(c, k, c->stream);
 }
 
 extern "C" int hmx_frame_intra_encode(hmx_ctx *c, const hmx_intra_plan *pl, int n_pics, const hmx_pic *org,
@@ -875,19 +861,13 @@ extern "C" int hmx_frame_intra_decode_onto(hmx_ctx *c, const hmx_intra_plan *pl,
                                            const hmx_levels *lev) {
   if (!c) return HMX_ERR_ARG;
   if (c->knob.graph) return fail(c, HMX_ERR_ARG, "hmx_frame_intra_decode_onto: not available with HMX_GRAPH");
-  c->onto_call = true;
-  const int r = frame_intra(c, &pl, 0, n_pics, nullptr, rec, lev, false);
-  c->onto_call = false;
-  return r;
+  return frame_intra(c, &pl, 0, n_pics, nullptr, rec, lev, false, true);
 }
 extern "C" int hmx_frame_intra_encode_onto(hmx_ctx *c, const hmx_intra_plan *pl, int n_pics, const hmx_pic *org, const hmx_pic *rec,
                                            const hmx_levels *lev) {
   if (!c) return HMX_ERR_ARG;
   if (c->knob.graph) return fail(c, HMX_ERR_ARG, "hmx_frame_intra_encode_onto: not available with HMX_GRAPH");
-  c->onto_call = true;
-  const int r = frame_intra(c, &pl, 0, n_pics, org, rec, lev, true);
-  c->onto_call = false;
-  return r;
+  return frame_intra(c, &pl, 0, n_pics, org, rec, lev, true, true);
 }
 extern "C" int hmx_frame_intra_encode_multi(hmx_ctx *c, const hmx_intra_plan *const *plans, int n_pics, const hmx_pic *org,
                                             const hmx_pic *rec, const hmx_levels *lev) {
@@ -934,11 +914,11 @@ extern "C" int hmx_set_sse_output(hmx_ctx *c, const hmx_sse *sse, int n_pics) {
 extern "C" int hmx_frame_intra_encode_resident(hmx_ctx *c, const hmx_intra_plan *const *plans, int plan_stride, int n_pics,
                                                const hmx_tpool *org, hmx_tpool *rec, const hmx_levels *lev) {
   if (!org || !rec || (plan_stride != 0 && plan_stride != 1)) return fail(c, HMX_ERR_ARG, "hmx_frame_intra_encode_resident: bad argument");
-  return frame_intra(c, plans, plan_stride, n_pics, nullptr, nullptr, lev, true, org, rec);
+  return frame_intra(c, plans, plan_stride, n_pics, nullptr, nullptr, lev, true, false, org, rec);
 }
 extern "C" int hmx_frame_intra_decode_resident(hmx_ctx *c, const hmx_intra_plan *const *plans, int plan_stride, int n_pics,
                                                hmx_tpool *rec, const hmx_levels *lev) {
   if (!rec || (plan_stride != 0 && plan_stride != 1)) return fail(c, HMX_ERR_ARG, "hmx_frame_intra_decode_resident: bad argument");
-  return frame_intra(c, plans, plan_stride, n_pics, nullptr, nullptr, lev, false, nullptr, rec);
+  return frame_intra(c, plans, plan_stride, n_pics, nullptr, nullptr, lev, false, false, nullptr, rec);
 }
 

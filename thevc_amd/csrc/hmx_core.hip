@@ -115,14 +115,18 @@ extern "C" int hmx_create(const hmx_config *cfg, hmx_ctx **out) {
   return HMX_OK;
 }
 
-extern "C" void hmx_destroy(hmx_ctx *c) {
-  if (!c) return;
-  hipStreamSynchronize(c->stream);
-  hipFree(c->d_scratch);
+void drop_graphs(hmx_ctx *c) {
   for (auto &e : c->graphs) {
     hipGraphExecDestroy(e.exec);
     hipFree(e.d_work);
   }
+  c->graphs.clear();
+}
+extern "C" void hmx_destroy(hmx_ctx *c) {
+  if (!c) return;
+  hipStreamSynchronize(c->stream);
+  hipFree(c->d_scratch);
+  drop_graphs(c);
   hipFree(c->own_pool_org);
   hipFree(c->own_pool_rec);
   hipFree(c->d_jobs);

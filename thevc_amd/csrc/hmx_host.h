@@ -206,20 +206,14 @@ struct hmx_ctx {
   // scratch for the scalar drop-ins (one block): device staging
   char *d_scratch = nullptr;
   size_t scratch_bytes = 0;
-  // working pictures of the whole-picture path in tiled layout (grow-only pool, one slot per picture)
-  // ONE allocation per direction, picture i at element offset i * tiled_pic_elems, its planes at
-  // tiled_plane_off[]: a wave that works across pictures reaches any picture with a multiply-add
-  short *pool_org = nullptr, *pool_rec = nullptr; // pools of the call being issued: the context's own or the caller's (hmx_tpool)
-  short *own_pool_org = nullptr, *own_pool_rec = nullptr; // allocations behind the plane-geometry entry points
+  // working pictures of the whole-picture path in tiled layout (TiledGeom): grow-only pools behind the plane-geometry entry
+  // points, ONE allocation per direction.  What a single call decides travels in its IntraCall (hmx_chain.hip), not here.
+  short *own_pool_org = nullptr, *own_pool_rec = nullptr;
   int pool_pics = 0;
-  size_t tiled_pic_elems = 0;
-  uint32_t tiled_plane_off[3] = {0, 0, 0};
-  int tiled_cw = 0, tiled_ch = 0; // CTU grid of the call being issued
-  int own_cw = 0, own_ch = 0;     // CTU grid the context's own pools were sized for
-  bool resident_call = false;     // the call works on the caller's resident pools: no layout conversion
+  int own_cw = 0, own_ch = 0;     // CTU grid the pools were sized for
   ConvJob *d_jobs = nullptr;      // [2][n_pics*3]: to-tiled jobs, then from-tiled jobs
   int jobs_cap = 0;
-  // whole-picture calls recorded as HIP graphs (see frame_intra)
+  // whole-picture calls recorded as HIP graphs (run_graph, hmx_chain.hip)
   struct GraphEntry {
     uint64_t key;
     int n_pics;
@@ -230,10 +224,6 @@ struct hmx_ctx {
   std::vector<GraphEntry> graphs;
   uint64_t graph_clock = 0;
   int last_schedule = 0, last_groups = 1; // of the last whole-picture call (hmx_last_call_shape)
-  bool onto_call = false;                 // this call reconstructs onto what the reconstruction planes already hold
-  bool pipeline_conv = false;  // this call converts CTU row by CTU row, overlapped with the chain
-  bool across_call = false;    // the call being issued uses the across-pictures schedule (interleaved pool)
-  int level_mode_min_pics = 1; // measured: the level schedule is at least as fast as the wave schedule at every batch size
   // optional timing of the last whole-picture call: events around the layout conversions and the chain
   bool timing = false;
   hipEvent_t tev[4] = {};
@@ -287,8 +277,6 @@ struct hmx_ctx {
     uint64_t waves_bound = 0;
   } pk;
   int max_resident_waves = 0; // of k_intra_packed on this device
-  int pack_I = 1;             // pictures per group (interleave domain of the pool) of the call being issued
-  const hmx_levels *call_lev = nullptr; // the call's level planes (host array, valid while the call is issued)
   bool pk_pending = false;    // a packed launch was issued since the last check of its abort word
   // hmx_set_rdoq: xRateDistOptQuant as the quantiser of the next whole-picture encode calls
   struct ChainRdoq {
@@ -395,18 +383,40 @@ struct hmx_tu_list {
   int off[5] = {0, 0, 0, 0, 0}, cnt[5] = {0, 0, 0, 0, 0}; // size classes 4 .. 64 (64: luma prediction units, hmx_batch_predIntra[_cost] only)
   int n = 0;
 };
+// The tiled working layout of the whole-picture path (TiledPlane): planes padded to whole CTUs, ONE allocation per pool, picture i
+// at element offset i * pic_elems, its planes at plane_off[]: a wave that works across pictures reaches any picture with a
+// multiply-add.  Pictures of one interleave domain [g0, g1) of a pool lie quad by quad beside each other.
+struct TiledGeom {
+  int ctu = 64, cw = 0, ch = 0, pic_w = 0, pic_h = 0;
+  uint32_t plane_off[3] = {0, 0, 0};
+  size_t pic_elems = 0;
+};
+inline TiledGeom tiled_geom(int pic_w, int pic_h, int ctu) {
+  TiledGeom g;
+  g.ctu = ctu, g.pic_w = pic_w, g.pic_h = pic_h;
+  g.cw = (pic_w + ctu - 1) / ctu, g.ch = (pic_h + ctu - 1) / ctu;
+  for (int p = 0; p < 3; p++) {
+    g.plane_off[p] = (uint32_t)g.pic_elems;
+    g.pic_elems += (size_t)g.cw * g.ch * ((size_t)ctu * ctu >> (p ? 2 : 0));
+  }
+  return g;
+}
+inline bool operator==(const TiledGeom &a, const TiledGeom &b) { return a.ctu == b.ctu && a.pic_w == b.pic_w && a.pic_h == b.pic_h; } // the rest follows
+// plane p of picture i, a member of the interleave domain [g0, g1) of the pool at `pool` (NULL: a pool the call does not have)
+inline TiledPlane tiled_plane(const TiledGeom &g, short *pool, int i, int p, int g0, int g1) {
+  const int clog = ilog2i(g.ctu);
+  const size_t base = (size_t)g0 * g.pic_elems + (size_t)g.plane_off[p] * (g1 - g0) + (size_t)(i - g0) * 64;
+  return TiledPlane{pool ? pool + base : nullptr, g.cw, p ? clog - 1 : clog, 64u * (unsigned)(g1 - g0)};
+}
+// 64 x 64 regions of `rows` sample rows of the padded luma plane (the chroma planes need a quarter of them; the rest exit): the
+// grid of k_convert_tiled over n_pics pictures
+inline dim3 convert_grid(const TiledGeom &g, int n_pics, int rows) { return dim3((unsigned)n_pics, (unsigned)(g.cw * g.ctu + 63) / 64 * ((unsigned)(rows + 63) / 64), 3); }
 struct hmx_tpool {
   short *base = nullptr;
   int n_pics = 0, I = 1;   // groups of I pictures are interleaved quad by quad
-  int cw = 0, ch = 0, ctu = 64, pic_w = 0, pic_h = 0;
-  size_t pic_elems = 0;
-  uint32_t plane_off[3] = {0, 0, 0};
+  TiledGeom geom;
 };
-inline TiledPlane tpool_plane(const hmx_tpool *t, int i, int p) {
-  const int g0 = i / t->I * t->I, clog = ilog2i(t->ctu);
-  const size_t base = (size_t)g0 * t->pic_elems + (size_t)t->plane_off[p] * t->I + (size_t)(i - g0) * 64;
-  return TiledPlane{t->base + base, t->cw, p ? clog - 1 : clog, 64u * (unsigned)t->I};
-}
+inline TiledPlane tpool_plane(const hmx_tpool *t, int i, int p) { return tiled_plane(t->geom, t->base, i, p, i / t->I * t->I, i / t->I * t->I + t->I); }
 
 // ---- host helpers that cross translation units ----
 QuantDev make_qd(const hmx_qp &qp, int per_base, int slice_type);                 // hmx_core.hip
@@ -414,6 +424,7 @@ PicDev make_picdev(const hmx_ctx *c, const hmx_pic_param *pp);
 PlanesDev to_dev(const hmx_pic *p);
 LevelsDev to_dev(const hmx_levels *p);
 void *arena_push(hmx_ctx *c, const void *src, size_t bytes);
+void drop_graphs(hmx_ctx *c); // destroy every recorded whole-picture graph (the stream is idle)
 int grow_dev(hmx_ctx *c, void **p, size_t *cap, size_t need);
 int check_packed_abort(hmx_ctx *c);                                               // hmx_chain.hip
 int pack_group_size(const hmx_ctx *c, int n_pics);
@@ -535,6 +546,13 @@ inline bool with_size(int n, F &&f) {
     }
   }
   return false;
+}
+// f(std::true_type{}) or f(std::false_type{}): a kernel with a bool template parameter (encoder / decoder direction) launched from a
+// run-time flag, one argument list for both
+template <typename F>
+inline void with_bool(bool b, F &&f) {
+  if (b) f(std::true_type{});
+  else f(std::false_type{});
 }
 // the launch of one kernel family for an n x n block (a size the caller has checked), and its launch error
 template <int Max, typename F>

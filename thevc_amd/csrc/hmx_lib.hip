@@ -4,6 +4,7 @@
 // RDOQ counters next to the schedule's own) and as a cross-check that the parts do not depend on their build order.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -pthread -DHMX_PACK_PROFILE -o thevc_amd/libhmx_prof.so thevc_amd/csrc/hmx_lib.hip
 #define HMX_RDOQ_KERNELS 1
+#define HMX_CHAIN_MAIN 1 // hmx_list.hip includes hmx_chain_dev.h before hmx_chain.hip does: its non-template kernels are wanted then already
 #include "hmx_core.hip"
 #include "hmx_list.hip"
 #include "hmx_scalar.hip"

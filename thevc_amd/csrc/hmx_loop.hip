@@ -859,22 +859,22 @@ extern "C" int hmx_yuv_pack(hmx_ctx *c, const hmx_pic *src, int w, int h, int cr
 // The same straight into / out of a resident picture: the frame crosses PCIe as file bytes and is widened, scaled, padded and
 // laid out for the block kernels in ONE pass over it; no plane-geometry copy exists on the device.
 extern "C" int hmx_yuv_unpack_resident(hmx_ctx *c, const void *d_file, int file_bits, hmx_tpool *t, int index, int pad_x, int pad_y) {
-  if (!c || !d_file || !t || index < 0 || index >= t->n_pics || file_bits < 8 || file_bits > 16 || (t->pic_w & 1) || (t->pic_h & 1) || pad_x < 0 ||
-      pad_y < 0 || (pad_x & 1) || (pad_y & 1) || pad_x >= t->pic_w || pad_y >= t->pic_h)
+  if (!c || !d_file || !t || index < 0 || index >= t->n_pics || file_bits < 8 || file_bits > 16 || (t->geom.pic_w & 1) || (t->geom.pic_h & 1) || pad_x < 0 ||
+      pad_y < 0 || (pad_x & 1) || (pad_y & 1) || pad_x >= t->geom.pic_w || pad_y >= t->geom.pic_h)
     return fail(c, HMX_ERR_ARG, "hmx_yuv_unpack_resident: bad argument");
   TiledPic TP;
   for (int p = 0; p < 3; p++) TP.T[p] = tpool_plane(t, index, p);
-  hipLaunchKernelGGL(k_yuv_unpack<true>, dim3((unsigned)(((size_t)((t->pic_w + 7) / 8) * t->pic_h + 255) / 256), 3), dim3(256), 0, c->stream,
+  hipLaunchKernelGGL(k_yuv_unpack<true>, dim3((unsigned)(((size_t)((t->geom.pic_w + 7) / 8) * t->geom.pic_h + 255) / 256), 3), dim3(256), 0, c->stream,
                      static_cast<const unsigned char *>(d_file), file_bits > 8 ? 1 : 0, c->cfg.bit_depth - file_bits, c->cfg.bit_depth,
-                     t->pic_w, t->pic_h, pad_x, pad_y, PlanesDev{}, TP);
+                     t->geom.pic_w, t->geom.pic_h, pad_x, pad_y, PlanesDev{}, TP);
   HIPCHK(c, hipGetLastError());
   return HMX_OK;
 }
 extern "C" int hmx_yuv_pack_resident(hmx_ctx *c, const hmx_tpool *t, int index, int crop_right, int crop_bottom, int file_bits, void *d_file) {
   if (!c || !d_file || !t || index < 0 || index >= t->n_pics || file_bits < 8 || file_bits > 16 || crop_right < 0 || crop_bottom < 0 ||
-      crop_right >= t->pic_w || crop_bottom >= t->pic_h || ((t->pic_w - crop_right) & 1) || ((t->pic_h - crop_bottom) & 1))
+      crop_right >= t->geom.pic_w || crop_bottom >= t->geom.pic_h || ((t->geom.pic_w - crop_right) & 1) || ((t->geom.pic_h - crop_bottom) & 1))
     return fail(c, HMX_ERR_ARG, "hmx_yuv_pack_resident: bad argument");
-  const int ww = t->pic_w - crop_right, hh = t->pic_h - crop_bottom;
+  const int ww = t->geom.pic_w - crop_right, hh = t->geom.pic_h - crop_bottom;
   TiledPic TP;
   for (int p = 0; p < 3; p++) TP.T[p] = tpool_plane(t, index, p);
   hipLaunchKernelGGL(k_yuv_pack<true>, dim3((unsigned)(((size_t)((ww + 7) / 8) * hh + 255) / 256), 3), dim3(256), 0, c->stream, PlanesDev{}, TP,

@@ -543,11 +543,7 @@ extern "C" void hmx_intra_plan_destroy(hmx_ctx *c, hmx_intra_plan *pl) {
   if (!pl) return;
   if (c) { // recorded graphs may refer to this plan (and its addresses may be re-used): drop them
     hipStreamSynchronize(c->stream);
-    for (auto &e : c->graphs) {
-      hipGraphExecDestroy(e.exec);
-      hipFree(e.d_work);
-    }
-    c->graphs.clear();
+    drop_graphs(c);
   }
   plan_release(c, pl);
 }
@@ -556,11 +552,7 @@ extern "C" void hmx_intra_plan_destroy_many(hmx_ctx *c, hmx_intra_plan *const *p
   if (!plans || n <= 0) return;
   if (c) {
     hipStreamSynchronize(c->stream);
-    for (auto &e : c->graphs) {
-      hipGraphExecDestroy(e.exec);
-      hipFree(e.d_work);
-    }
-    c->graphs.clear();
+    drop_graphs(c);
   }
   for (int i = 0; i < n; i++)
     if (plans[i]) plan_release(c, plans[i]);
