@@ -4,7 +4,9 @@
 # Missing 2).  Replaced (oracle/ref_shim_edit.py UNIT enc):
 #   TComTrQuant::xT, xIT, xTransformSkip, xITransformSkip, xQuant (flat branch), xRateDistOptQuant, xDeQuant;
 #   TComPrediction::predIntraLumaAng, predIntraChromaAng, xPredInterLumaBlk, xPredInterChromaBlk;
-#   TComInterpolationFilter::filterHor/VerLuma/Chroma (the fractional motion search's calls); TComYuv::addAvg; TComRdCost::calcHAD
+#   TComInterpolationFilter::filterHor/VerLuma/Chroma (the fractional motion search's calls); TComYuv::addAvg; TComRdCost::calcHAD;
+# and oracle/_ref/TAppEncoder_hmx_wp: the same with TComWeightPrediction::addWeightUni, addWeightBi replaced as well (motion compensation of
+# a weighted slice and the AMVP template, TEncSearch.cpp:4092; its object lies in obj_shim_enc_wp/, obj_shim_enc/ holds the units of TAppEncoder_hmx)
 # Everything else -- the RD search, mode decision, motion estimation, CABAC, rate estimation (TEncSbac::estBit fills the bit-estimate
 # table RDOQ reads), loop filters -- is the reference's own code compiled from the sources where they lie.  TEST INFRASTRUCTURE:
 # nothing of the reference is copied into the repository (the edited units exist only in a pipe), its build system is not run,
@@ -28,12 +30,17 @@ UNITS="TComTrQuant TComPrediction TComInterpolationFilter TComYuv TComRdCost"
 for u in $UNITS; do
   python3 "$HERE/ref_shim_edit.py" $u enc | $CXX $FLAGS -I"$ROOT/include" -include "$HERE/ref_shim.h" -x c++ -c - -o "$OUT/obj_shim_enc/$u.o" &
 done
+mkdir -p "$OUT/obj_shim_enc_wp"
+python3 "$HERE/ref_shim_edit.py" TComWeightPrediction enc | $CXX $FLAGS -I"$ROOT/include" -include "$HERE/ref_shim.h" -x c++ -c - -o "$OUT/obj_shim_enc_wp/TComWeightPrediction.o" &
 wait
 EXCL=""
-for u in $UNITS; do EXCL="$EXCL -e /$u.o"; done
+SHIM=""
+for u in $UNITS; do EXCL="$EXCL -e /$u.o"; SHIM="$SHIM $OUT/obj_shim_enc/$u.o"; done
 COMMON=$(ls "$OUT"/obj/*.o | grep -v -e ref_tap.o $EXCL)
-$CXX -o "$OUT/TAppEncoder_hmx" "$OUT"/obj_apps/enc_*.o "$OUT"/obj_apps/TLibEncoder_*.o "$OUT"/obj_apps/TAppCommon_*.o "$OUT"/obj_shim_enc/*.o $COMMON \
+$CXX -o "$OUT/TAppEncoder_hmx" "$OUT"/obj_apps/enc_*.o "$OUT"/obj_apps/TLibEncoder_*.o "$OUT"/obj_apps/TAppCommon_*.o $SHIM $COMMON \
   -L"$ROOT/thevc_amd" -lhmx -Wl,-rpath,'$ORIGIN/../../thevc_amd'
+$CXX -o "$OUT/TAppEncoder_hmx_wp" "$OUT"/obj_apps/enc_*.o "$OUT"/obj_apps/TLibEncoder_*.o "$OUT"/obj_apps/TAppCommon_*.o $SHIM "$OUT/obj_shim_enc_wp/TComWeightPrediction.o" \
+  $(echo "$COMMON" | grep -v -e /TComWeightPrediction.o) -L"$ROOT/thevc_amd" -lhmx -Wl,-rpath,'$ORIGIN/../../thevc_amd'
 # The reference encoder with a RECORDER in front of its own xRateDistOptQuant (oracle/ref_rdoq_tap.h; no libhmx in this binary):
 # what the encoder's live CABAC state feeds RDOQ, block by block -> tests/golden/make_rdoq_enc_tap.py -> tests/golden/rdoq_enc_tap.npz
 mkdir -p "$OUT/obj_tap_enc"
@@ -46,4 +53,4 @@ $CXX -o "$OUT/TAppEncoder_rdoqtap" "$OUT"/obj_apps/enc_*.o "$OUT"/obj_apps/TLibE
 python3 "$HERE/ref_shim_edit.py" TEncSearch metap | $CXX $FLAGS -I"$SRC/Lib/TLibEncoder" -include "$HERE/ref_me_tap.h" -x c++ -c - -o "$OUT/obj_tap_enc/TEncSearch.o"
 $CXX -o "$OUT/TAppEncoder_metap" "$OUT"/obj_apps/enc_*.o $(ls "$OUT"/obj_apps/TLibEncoder_*.o | grep -v -e /TLibEncoder_TEncSearch.o) "$OUT"/obj_apps/TAppCommon_*.o \
   "$OUT/obj_tap_enc/TEncSearch.o" $(ls "$OUT"/obj/*.o | grep -v -e ref_tap.o)
-echo "build_ref_enc_shim: wrote $OUT/TAppEncoder_hmx, $OUT/TAppEncoder_rdoqtap and $OUT/TAppEncoder_metap"
+echo "build_ref_enc_shim: wrote $OUT/TAppEncoder_hmx, $OUT/TAppEncoder_hmx_wp, $OUT/TAppEncoder_rdoqtap and $OUT/TAppEncoder_metap"

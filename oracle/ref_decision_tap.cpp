@@ -11,7 +11,7 @@
 // GPU) and compare with what the reference decoder itself produced.
 //
 // File layout (little endian, int32 unless noted):
-//   magic "HMXD", version 4, n_pictures (patched at the end)
+//   magic "HMXD", version 5, n_pictures (patched at the end)
 //   per picture: poc, width, height, bit_depth, slice_qp, ctu, slice_type (0 B, 1 P, 2 I), n_tu, n_pu, n_cu,
 //                n_tu x { u16 x, u16 y, u8 log2n, u8 plane, u8 mode, u8 flags }      (= hmx_tu, include/hmx.h;
 //                         flags bit 0 transform skip, bit 1 block of an inter coding unit, bit 7 (luma blocks) coded
@@ -27,6 +27,11 @@
 //                                         resolved (= hmx_sao_lcu; type -1 everywhere when SAO is off for the component)
 //                deblocking: int32 disabled (slice flag), beta_offset_div2, tc_offset_div2
 //                3 planes x reconstruction (int16, w x h, no margins)
+//                version 5, explicit weighted prediction: the PPS flags use WP (P slices), WP bi-pred (B slices); the entries of
+//                list 0 and of list 1 (getNumRefIdx); per list, per entry: its POC, then per component Y, Cb, Cr { weight,
+//                offset, log2 denominator } as the slice header coded them (TComSlice::m_weightPredTable); then
+//                n_pu x { i8 refIdx0, i8 refIdx1 } (-1 = list unused): a picture may sit in a list twice with different rows,
+//                which the POC alone does not tell.  One slice per picture: a weighted picture with more is refused.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -104,7 +109,7 @@ void walk(TComDataCU *cu, unsigned part, unsigned depth, unsigned cu_part, int c
 
 // Prediction units of the inter coding unit of `size` samples at (x, y) whose first partition is `part`
 // (TComDataCU::getPartIndexAndSize, COM/TComDataCU.cpp:3180-3250: the eight partition shapes).
-void units_of(TComDataCU *cu, unsigned part, int x, int y, int size, int ctu_x, int ctu_y, int ctu, std::vector<Pu> &out) {
+void units_of(TComDataCU *cu, unsigned part, int x, int y, int size, int ctu_x, int ctu_y, int ctu, std::vector<Pu> &out, std::vector<int8_t> &ref_idx) {
   const int q = size / 4, h2 = size / 2;
   int n = 1, rx[4] = {0, 0, 0, 0}, ry[4] = {0, 0, 0, 0}, rw[4] = {size, 0, 0, 0}, rh[4] = {size, 0, 0, 0};
   switch (cu->getPartitionSize(part)) {
@@ -134,6 +139,7 @@ void units_of(TComDataCU *cu, unsigned part, int x, int y, int size, int ctu_x, 
       *poc[l] = ri < 0 ? (int16_t)-32768 : (int16_t)slice->getRefPOC(l ? REF_PIC_LIST_1 : REF_PIC_LIST_0, ri);
       *mvx[l] = ri < 0 ? 0 : (int16_t)mf->getMv((Int)idx).getHor();
       *mvy[l] = ri < 0 ? 0 : (int16_t)mf->getMv((Int)idx).getVer();
+      ref_idx.push_back((int8_t)(ri < 0 ? -1 : ri));
     }
     out.push_back(u);
   }
@@ -142,7 +148,7 @@ void units_of(TComDataCU *cu, unsigned part, int x, int y, int size, int ctu_x, 
 // The decisions of a picture whose slices have all been decoded; called BEFORE the loop filters run, because
 // TDecGop::filterPicture ends with TComPic::compressMotion (:289), which overwrites the motion of every 16x16 area
 // with that of its first unit.
-int collect(TComPic *pic, std::vector<Tu> &tus, std::vector<Pu> &pus, std::vector<Cu> &cus) {
+int collect(TComPic *pic, std::vector<Tu> &tus, std::vector<Pu> &pus, std::vector<Cu> &cus, std::vector<int8_t> &ref_idx) {
   TComPicYuv *rec = pic->getPicYuvRec();
   const int w = rec->getWidth(), h = rec->getHeight(), ctu = (int)g_uiMaxCUWidth;
   const unsigned n_ctu = pic->getNumCUsInFrame(), per_row = pic->getFrameWidthInCU(), n_part = pic->getNumPartInCU();
@@ -158,10 +164,14 @@ int collect(TComPic *pic, std::vector<Tu> &tus, std::vector<Pu> &pus, std::vecto
           fprintf(stderr, "hm_decision_tap: PCM / lossless coding units are outside the path\n");
           return 1;
         }
+        if (cu->getSlice() != pic->getSlice(0) && pic->getSlice(0)->getPPS()->getUseWP() + pic->getSlice(0)->getPPS()->getWPBiPred()) {
+          fprintf(stderr, "hm_decision_tap: a weighted picture with more than one slice is outside the path\n");
+          return 1;
+        }
         const bool inter = cu->getPredictionMode(part) != MODE_INTRA;
         Cu cc = {(uint16_t)x, (uint16_t)y, (uint8_t)(g_aucConvertToBit[ctu >> depth] + 2), (uint8_t)!inter, (uint8_t)cu->getSkipFlag(part), 0};
         cus.push_back(cc);
-        if (inter) units_of(cu, part, x, y, ctu >> depth, cx, cy, ctu, pus);
+        if (inter) units_of(cu, part, x, y, ctu >> depth, cx, cy, ctu, pus, ref_idx);
         // an inter coding unit without residual has no transform blocks (its reconstruction is its prediction)
         if (!inter || cu->getQtRootCbf(part)) walk(cu, part, depth, part, cx, cy, ctu, inter, tus);
       }
@@ -171,7 +181,8 @@ int collect(TComPic *pic, std::vector<Tu> &tus, std::vector<Pu> &pus, std::vecto
   return 0;
 }
 
-int dump_picture(FILE *f, TComPic *pic, const std::vector<Tu> &tus, const std::vector<Pu> &pus, const std::vector<Cu> &cus) {
+int dump_picture(FILE *f, TComPic *pic, const std::vector<Tu> &tus, const std::vector<Pu> &pus, const std::vector<Cu> &cus,
+                 const std::vector<int8_t> &ref_idx) {
   TComPicYuv *rec = pic->getPicYuvRec();
   const int w = rec->getWidth(), h = rec->getHeight(), ctu = (int)g_uiMaxCUWidth;
   const int B = (int)(g_uiBitDepth + g_uiBitIncrement);
@@ -213,6 +224,20 @@ int dump_picture(FILE *f, TComPic *pic, const std::vector<Tu> &tus, const std::v
     const int s = pl ? rec->getCStride() : rec->getStride(), pw = w >> (pl ? 1 : 0), ph = h >> (pl ? 1 : 0);
     for (int r = 0; r < ph; r++) fwrite(p + (size_t)r * s, sizeof(Pel), pw, f);
   }
+  // explicit weighted prediction (version 5)
+  put32(f, slice->getPPS()->getUseWP() ? 1 : 0), put32(f, slice->getPPS()->getWPBiPred() ? 1 : 0);
+  const bool inter_slice = slice->getSliceType() != I_SLICE;
+  int n_entries[2];
+  for (int l = 0; l < 2; l++) n_entries[l] = inter_slice ? slice->getNumRefIdx(l ? REF_PIC_LIST_1 : REF_PIC_LIST_0) : 0;
+  put32(f, n_entries[0]), put32(f, n_entries[1]);
+  for (int l = 0; l < 2; l++)
+    for (int i = 0; i < n_entries[l]; i++) {
+      wpScalingParam *wp = NULL;
+      slice->getWpScaling(l ? REF_PIC_LIST_1 : REF_PIC_LIST_0, i, wp);
+      put32(f, slice->getRefPOC(l ? REF_PIC_LIST_1 : REF_PIC_LIST_0, i));
+      for (int c = 0; c < 3; c++) put32(f, wp[c].iWeight), put32(f, wp[c].iOffset), put32(f, (int32_t)wp[c].uiLog2WeightDenom);
+    }
+  fwrite(ref_idx.data(), 1, ref_idx.size(), f);
   return 0;
 }
 
@@ -243,7 +268,7 @@ int main(int argc, char **argv) {
   FILE *f = fopen(argv[2], "wb");
   if (!f) return 2;
   fwrite("HMXD", 1, 4, f);
-  put32(f, 4), put32(f, 0);
+  put32(f, 5), put32(f, 0);
   TDecTop dec;
   dec.create();
   dec.init();
@@ -255,12 +280,13 @@ int main(int argc, char **argv) {
     std::vector<Tu> tus;
     std::vector<Pu> pus;
     std::vector<Cu> cus;
-    rc |= collect(cur, tus, pus, cus);
+    std::vector<int8_t> ref_idx;
+    rc |= collect(cur, tus, pus, cus, ref_idx);
     UInt poc = 0;
     TComList<TComPic *> *list = NULL;
     dec.executeDeblockAndAlf(poc, list, skip, last_display); // loop filters; the picture's samples are final after this
     if (!list || rc) return;
-    rc |= dump_picture(f, cur, tus, pus, cus);
+    rc |= dump_picture(f, cur, tus, pus, cus, ref_idx);
     n_pics++;
   };
   for (size_t i = 0; i < units.size() && !rc;) {

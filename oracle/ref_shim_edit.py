@@ -3,7 +3,7 @@
 /root/reference, replaces the BODIES of its hot-path members by the libhmx calls of INTEGRATION.md section 3 (signatures
 untouched) and writes the result to stdout for `g++ -x c++ -` (oracle/build_ref_shim.sh): nothing of the reference is
 stored in the repository, and no header, library or generated file of it is substituted.
-UNIT = TComTrQuant | TComPrediction | TComInterpolationFilter | TComYuv | TComRdCost (encoder shim only); a second argument
+UNIT = TComTrQuant | TComPrediction | TComInterpolationFilter | TComYuv | TComWeightPrediction | TComRdCost (encoder shim only); a second argument
 `enc` adds the bodies of the members only the encoder calls (ENC_BODIES).  `TComTrQuant rdoqtap` and `TEncSearch metap` leave
 every body as it is and add recorder statements (TAP_PREFIX, ME_TAP)."""
 import os
@@ -41,6 +41,19 @@ BODIES = {
         "TComYuv::addAvg": """HMX_SHIM_CHECK(hmx_addAvg(hmx_shim_ctx(), pcYuvSrc0->getLumaAddr(iPartUnitIdx), pcYuvSrc0->getStride(), pcYuvSrc1->getLumaAddr(iPartUnitIdx), pcYuvSrc1->getStride(), getLumaAddr(iPartUnitIdx), getStride(), iWidth, iHeight));
   HMX_SHIM_CHECK(hmx_addAvg(hmx_shim_ctx(), pcYuvSrc0->getCbAddr(iPartUnitIdx), pcYuvSrc0->getCStride(), pcYuvSrc1->getCbAddr(iPartUnitIdx), pcYuvSrc1->getCStride(), getCbAddr(iPartUnitIdx), getCStride(), iWidth >> 1, iHeight >> 1));
   HMX_SHIM_CHECK(hmx_addAvg(hmx_shim_ctx(), pcYuvSrc0->getCrAddr(iPartUnitIdx), pcYuvSrc0->getCStride(), pcYuvSrc1->getCrAddr(iPartUnitIdx), pcYuvSrc1->getCStride(), getCrAddr(iPartUnitIdx), getCStride(), iWidth >> 1, iHeight >> 1));""",
+    },
+    # explicit weighted prediction: the coded fields of the rows getWpScaling picked go in, libhmx derives offset / shift / round itself
+    # (the bi case reads list 0's denominator and both offsets); every caller leaves bRound at its default
+    "TComWeightPrediction": {
+        "TComWeightPrediction::addWeightUni": "\n  ".join(
+            "HMX_SHIM_CHECK(hmx_addWeightUni(hmx_shim_ctx(), pcYuvSrc0->get%(p)sAddr(iPartUnitIdx), pcYuvSrc0->get%(s)sStride(), rpcYuvDst->get%(p)sAddr(iPartUnitIdx), "
+            "rpcYuvDst->get%(s)sStride(), iWidth >> %(h)d, iHeight >> %(h)d, wp0[%(c)d].iWeight, wp0[%(c)d].iOffset, wp0[%(c)d].uiLog2WeightDenom));"
+            % {"p": pl, "s": st, "h": half, "c": c} for c, (pl, st, half) in enumerate((("Luma", "", 0), ("Cb", "C", 1), ("Cr", "C", 1)))),
+        "TComWeightPrediction::addWeightBi": "assert(bRound);\n  " + "\n  ".join(
+            "HMX_SHIM_CHECK(hmx_addWeightBi(hmx_shim_ctx(), pcYuvSrc0->get%(p)sAddr(iPartUnitIdx), pcYuvSrc0->get%(s)sStride(), pcYuvSrc1->get%(p)sAddr(iPartUnitIdx), "
+            "pcYuvSrc1->get%(s)sStride(), rpcYuvDst->get%(p)sAddr(iPartUnitIdx), rpcYuvDst->get%(s)sStride(), iWidth >> %(h)d, iHeight >> %(h)d, wp0[%(c)d].iWeight, "
+            "wp1[%(c)d].iWeight, wp0[%(c)d].iOffset, wp1[%(c)d].iOffset, wp0[%(c)d].uiLog2WeightDenom));"
+            % {"p": pl, "s": st, "h": half, "c": c} for c, (pl, st, half) in enumerate((("Luma", "", 0), ("Cb", "C", 1), ("Cr", "C", 1)))),
     },
 }
 

@@ -658,6 +658,91 @@ void ref_addAvg(const short *a[3], const short *b[3], short *o[3], int w, int h)
   }
 }
 
+// ---- explicit weighted prediction: TComWeightPrediction's own members (TComPrediction inherits them) ----
+// rows = the coded fields of one (list, refIdx): 9 ints [component][weight, offset, log2 denominator].  They are put into the
+// slice's m_weightPredTable and both PPS flags are set for the call, so that getWpScaling, the derived offset / shift / round and
+// the clip are the reference's.  Sources are dense 14-bit planes, w*h luma + (w/2)*(h/2) chroma; ref_init must have made a picture.
+static void wp_rows(TComSlice *sl, int list, int idx, const int *rows) {
+  for (int c = 0; c < 3; c++) {
+    wpScalingParam &p = sl->m_weightPredTable[list][idx][c];
+    p.bPresentFlag = true;
+    p.iWeight = rows[3 * c];
+    p.iOffset = rows[3 * c + 1];
+    p.uiLog2WeightDenom = (UInt)rows[3 * c + 2];
+  }
+}
+static void wp_load(TComYuv *y, const short *const s[3], int w, int h) {
+  for (int j = 0; j < h; j++) memcpy(y->getLumaAddr() + j * y->getStride(), s[0] + j * w, 2 * w);
+  for (int j = 0; j < h / 2; j++) {
+    memcpy(y->getCbAddr() + j * y->getCStride(), s[1] + j * (w / 2), w);
+    memcpy(y->getCrAddr() + j * y->getCStride(), s[2] + j * (w / 2), w);
+  }
+}
+static void wp_store(TComYuv *y, short *const o[3], int w, int h) {
+  for (int j = 0; j < h; j++) memcpy(o[0] + j * w, y->getLumaAddr() + j * y->getStride(), 2 * w);
+  for (int j = 0; j < h / 2; j++) {
+    memcpy(o[1] + j * (w / 2), y->getCbAddr() + j * y->getCStride(), w);
+    memcpy(o[2] + j * (w / 2), y->getCrAddr() + j * y->getCStride(), w);
+  }
+}
+// xWeightedPredictionUni (TComWeightPrediction.cpp:366-386) for list `list`, reference index idx.  Returns -1 on a bad argument.
+int ref_xWeightedPredictionUni(int list, int idx, const int *rows, const short *src[3], short *out[3], int w, int h) {
+  if (!S->pic || list < 0 || list > 1 || idx < 0 || idx >= MAX_NUM_REF || w > 64 || h > 64) return -1;
+  TComDataCU *c = setup_sub(0, 0, 64);
+  TComSlice *sl = c->getSlice();
+  wp_rows(sl, list, idx, rows);
+  S->pps.setUseWP(true);
+  S->pps.setWPBiPred(true);
+  TComYuv *A = &S->yuv[0], *O = &S->yuv[2];
+  wp_load(A, src, w, h);
+  S->pred.xWeightedPredictionUni(c, A, 0, w, h, list ? REF_PIC_LIST_1 : REF_PIC_LIST_0, O, 0, idx);
+  wp_store(O, out, w, h);
+  S->pps.setUseWP(false);
+  S->pps.setWPBiPred(false);
+  return 0;
+}
+// xWeightedPredictionBi (:327-352): both indices >= 0 is addWeightBi, one negative index is its addWeightUni branch on the other
+// list's source (the unused list's rows and source may be NULL).
+int ref_xWeightedPredictionBi(int idx0, int idx1, const int *rows0, const int *rows1, const short *src0[3], const short *src1[3],
+                              short *out[3], int w, int h) {
+  if (!S->pic || idx0 >= MAX_NUM_REF || idx1 >= MAX_NUM_REF || (idx0 < 0 && idx1 < 0) || w > 64 || h > 64) return -1;
+  TComDataCU *c = setup_sub(0, 0, 64);
+  TComSlice *sl = c->getSlice();
+  if (idx0 >= 0) wp_rows(sl, 0, idx0, rows0);
+  if (idx1 >= 0) wp_rows(sl, 1, idx1, rows1);
+  S->pps.setUseWP(true);
+  S->pps.setWPBiPred(true);
+  TComYuv *A = &S->yuv[0], *B = &S->yuv[1], *O = &S->yuv[2];
+  if (idx0 >= 0) wp_load(A, src0, w, h);
+  if (idx1 >= 0) wp_load(B, src1, w, h);
+  S->pred.xWeightedPredictionBi(c, A, B, idx0, idx1, 0, w, h, O);
+  wp_store(O, out, w, h);
+  S->pps.setUseWP(false);
+  S->pps.setWPBiPred(false);
+  return 0;
+}
+// the derived fields getWpScaling (:251-313) leaves for the two indices: out[list][component] = {w, o, offset, shift, round}
+int ref_getWpScaling(int idx0, int idx1, const int *rows0, const int *rows1, int *out) {
+  if (!S->pic || idx0 >= MAX_NUM_REF || idx1 >= MAX_NUM_REF || (idx0 < 0 && idx1 < 0)) return -1;
+  TComDataCU *c = setup_sub(0, 0, 64);
+  TComSlice *sl = c->getSlice();
+  if (idx0 >= 0) wp_rows(sl, 0, idx0, rows0);
+  if (idx1 >= 0) wp_rows(sl, 1, idx1, rows1);
+  S->pps.setUseWP(true);
+  S->pps.setWPBiPred(true);
+  wpScalingParam *p[2] = {NULL, NULL};
+  S->pred.getWpScaling(c, idx0, idx1, p[0], p[1]);
+  for (int l = 0; l < 2; l++)
+    for (int k = 0; k < 3; k++) {
+      int *o = out + (l * 3 + k) * 5;
+      if (!p[l]) continue;
+      o[0] = p[l][k].w, o[1] = p[l][k].o, o[2] = p[l][k].offset, o[3] = p[l][k].shift, o[4] = p[l][k].round;
+    }
+  S->pps.setUseWP(false);
+  S->pps.setWPBiPred(false);
+  return 0;
+}
+
 // recon plane with margins after extendPicBorder: copies (w+2mx)*(h+2my) luma samples out
 void ref_extended_luma(short *out) {
   TComPicYuv *r = S->pic->getPicYuvRec();

@@ -7,7 +7,7 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
-from make_stream_golden import synthetic_clip  # noqa: E402
+from make_stream_golden import fading_clip, synthetic_clip  # noqa: E402
 
 CASES = [
     # all-intra, 8 bit: 64x64 coding units down to 4x4 transform blocks, RDOQ fed by the live CABAC state, transform skip, sign hiding
@@ -23,12 +23,18 @@ CASES = [
     {"name": "intra_scalinglist_q30", "seed": 55, "w": 128, "h": 64, "frames": 1, "bits": 8, "qp": 30, "inter": False, "extra": ["--ScalingList=1"]},
     {"name": "lowdelay_P_scalinglist_q32", "seed": 56, "w": 128, "h": 128, "frames": 2, "bits": 8, "qp": 32, "inter": True, "extra": ["--ScalingList=1"]},
     {"name": "lowdelay_P_aqps_q32", "seed": 54, "w": 128, "h": 128, "frames": 3, "bits": 8, "qp": 32, "inter": True, "extra": ["--AdaptiveQpSelection=1"]},
+    # explicit weighted prediction on a fading clip: addWeightUni in the motion compensation of the P slices and in the AMVP template of
+    # the motion search (TEncSearch.cpp:4092); the weights themselves are the encoder's own estimate (WeightPredAnalysis, on the host)
+    {"name": "lowdelay_P_wp_q32", "seed": 57, "w": 128, "h": 128, "frames": 3, "bits": 8, "qp": 32, "inter": True, "fade": True,
+     "extra": ["--weighted_pred_flag=1"]},
 ]
 
 
 def write_clip(case, path):
     with open(path, "wb") as f:
-        for planes in synthetic_clip(case["seed"], case["w"], case["h"], case["frames"], case["bits"], False, case["inter"]):
+        clip = fading_clip(case["seed"], case["w"], case["h"], case["frames"], case["bits"]) if case.get("fade") else \
+            synthetic_clip(case["seed"], case["w"], case["h"], case["frames"], case["bits"], False, case["inter"])
+        for planes in clip:
             for p in planes:
                 f.write(p.astype(np.uint8 if case["bits"] == 8 else "<u2").tobytes())
     return path

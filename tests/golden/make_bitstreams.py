@@ -15,7 +15,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, HERE)
-from make_stream_golden import synthetic_clip  # noqa: E402
+from make_stream_golden import fading_clip, synthetic_clip  # noqa: E402
 
 ENC = os.path.join(ROOT, "oracle", "_ref", "TAppEncoder")
 STREAMS = [
@@ -27,16 +27,23 @@ STREAMS = [
     # round 3: the default scaling lists (xDeQuant's scaling-list branch, TComTrQuant.cpp:1311-1342)
     ("lowdelay_P_scalinglist_q30", 35, 192, 128, 3, 8, 30, "encoder_lowdelay_P_main.cfg", ["--ScalingList=1"], True),
     ("intra_he10_scalinglist_q24", 36, 128, 128, 1, 10, 24, "encoder_intra_he10.cfg", ["--ScalingList=1"], False),
+    # explicit weighted prediction on a fading clip (motion = "fade": make_stream_golden.fading_clip): TComWeightPrediction's addWeightUni in
+    # P slices, addWeightBi and both addWeightUni branches in B slices
+    ("lowdelay_P_wp_q32", 37, 192, 128, 3, 8, 32, "encoder_lowdelay_P_main.cfg", ["-wpP", "1"], "fade"),
+    ("randomaccess_wp_q34", 38, 192, 128, 5, 8, 34, "encoder_randomaccess_main.cfg", ["-wpP", "1", "-wpB", "1"], "fade"),
+    ("randomaccess_he10_wp_q34", 39, 128, 128, 5, 10, 34, "encoder_randomaccess_he10.cfg", ["-wpP", "1", "-wpB", "1"], "fade"),
 ]
 
 
 def main():
     os.makedirs(os.path.join(HERE, "streams"), exist_ok=True)
     for (name, seed, w, h, n, B, qp, cfg, extra, motion) in STREAMS:
+        if sys.argv[1:] and name not in sys.argv[1:]:  # only the named streams
+            continue
         with tempfile.TemporaryDirectory() as d:
             yuv = os.path.join(d, "in.yuv")
             with open(yuv, "wb") as f:
-                for planes in synthetic_clip(seed, w, h, n, B, False, motion):
+                for planes in (fading_clip(seed, w, h, n, B) if motion == "fade" else synthetic_clip(seed, w, h, n, B, False, motion)):
                     for p in planes:
                         f.write(p.astype(np.uint8 if B == 8 else "<u2").tobytes())
             out = os.path.join(HERE, "streams", name + ".bin")

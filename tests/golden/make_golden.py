@@ -17,6 +17,8 @@ sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 import extreme_inputs as xi  # noqa: E402
 import oracle_lib as ol  # noqa: E402
+import wp_cases as wc  # noqa: E402
+import wp_oracle as wo  # noqa: E402
 from thevc_amd import workload  # noqa: E402
 
 REG_DCT = 65535
@@ -431,6 +433,44 @@ def inter(R, B, rng, edge=False):
     return out
 
 
+def wp(R, B):
+    """Explicit weighted prediction (inputs: tests/wp_cases.py).  blk_*: the reference's xWeightedPredictionBi on 14-bit source planes in
+    its three index patterns; blk_par rows = (w, h, pattern, start of the case in blk_s0, in blk_s1, in blk_out), a case's planes Y, Cb, Cr
+    one after the other, an unused list stored with length 0; blk_e = [case][list][weight, offset, log2 denominator][component].
+    pu_*: one unit list on a 136x72 picture with two stored reference pictures, refs[] = pu_order, tables pu_l0 / pu_l1 indexed like
+    refs[], expected pictures composed from the reference's interpolation (bi = true) and xWeightedPredictionBi."""
+    R.ref_init(B, 64, 64, 1)
+    par, ents, s0, s1, outs = [], [], [], [], []
+    n = [0, 0, 0]
+    for c in wc.block_cases(B, every_combination=False):
+        use0, use1 = c["pattern"] != wc.L1_ONLY, c["pattern"] != wc.L0_ONLY
+        o = ol.r_wp_bi(c["src0"], c["src1"], c["e0"] if use0 else None, c["e1"] if use1 else None)
+        par.append((c["w"], c["h"], c["pattern"], n[0], n[1], n[2]))
+        ents.append([[c["e0"][f] for f in range(3)], [c["e1"][f] for f in range(3)]])
+        for k, (used, planes, dst) in enumerate(((use0, c["src0"], s0), (use1, c["src1"], s1), (True, o, outs))):
+            if used:
+                flat = np.concatenate([p.reshape(-1) for p in planes])
+                dst.append(flat)
+                n[k] += len(flat)
+    out = {"blk_par": np.array(par, np.int32), "blk_e": np.array(ents, np.int16), "blk_s0": np.concatenate(s0), "blk_s1": np.concatenate(s1),
+           "blk_out": np.concatenate(outs)}
+    clip = [c for c in wo.CLIP_CASES if c[0] == B]  # the hand-computed rows are the last block cases: the reference gives the same
+    for (_, _, _, want), row in zip(clip, par[len(par) - len(clip):]):
+        assert (out["blk_out"][row[5]:row[5] + 24] == want).all()
+    S = wc.pu_scene(B)
+    counts = wc.check_pu_scene(S)
+    exp = ol.r_mc_frame_wp(S["pus"], S["pics"], S["order"], (S["l0"], S["l1"]), B)
+    mx = (1 << B) - 1
+    inside = np.mean([((p > 0) & (p < mx)).mean() for p in exp])
+    assert inside > 0.5, inside  # most samples off the clips
+    print(f"wp_b{B}: {len(par)} block cases, unit list {counts}, {inside:.2f} of the samples off the clips")
+    out.update({"pu": S["pus"], "pu_order": np.array(S["order"], np.int32), "pu_l0": np.array(S["l0"], np.int16), "pu_l1": np.array(S["l1"], np.int16),
+                "pu_oy": exp[0], "pu_ocb": exp[1], "pu_ocr": exp[2]})
+    for i, pic in enumerate(S["pics"]):
+        out.update({f"pic{i}_y": pic[0], f"pic{i}_cb": pic[1], f"pic{i}_cr": pic[2]})
+    return out
+
+
 def frame(R, B, qp, pic, tiling, seed):
     w, h = pic
     tus = workload.make_tus(seed, w, h, tiling)
@@ -454,6 +494,11 @@ def main():
     R = ol.ref()
     if sys.argv[1:] == ["edges"]:  # content at the range ends, 12 bit
         edges(R)
+        return
+    if sys.argv[1:] == ["wp"]:  # explicit weighted prediction: the members and one unit list
+        for B in (8, 10, 12):
+            np.savez_compressed(os.path.join(HERE, f"wp_b{B}.npz"), **wp(R, B))
+            print(f"wp_b{B}.npz", os.path.getsize(os.path.join(HERE, f"wp_b{B}.npz")))
         return
     if sys.argv[1:] == ["rdoq"]:  # added after the first set: generate only the RDOQ vectors
         for B in (8, 10):

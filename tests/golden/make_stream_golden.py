@@ -65,11 +65,28 @@ def synthetic_clip(seed, w, h, n, B, smooth=False, motion=False):
     return out
 
 
+def fading_clip(seed, w, h, n, B):
+    """synthetic_clip's panning clip under a fade: picture i has its contrast about mid-grey scaled by a gain and its brightness moved
+    by a step, luma and chroma each their own, so that an encoder with weighted prediction on codes non-default weights and offsets.
+    The slopes keep the reference encoder's estimates inside the coded range: it does not clip its luma offset to -128..127
+    (WeightPredAnalysis.cpp:228-232), and a steeper fade over four pictures made it write -129 and -136."""
+    mx = (1 << B) - 1
+    mid, unit = (mx + 1) / 2, 1 << (B - 8)
+    out = []
+    for i, planes in enumerate(synthetic_clip(seed, w, h, n, B, False, True)):
+        fade = []
+        for k, p in enumerate(planes):
+            gain, step = (1.0 - 0.08 * i, 5 * i * unit) if k == 0 else (1.0 - 0.06 * i, (-4 if k == 1 else 3) * i * unit)
+            fade.append(np.clip(np.rint((p.astype(np.float64) - mid) * gain + mid + step), 0, mx).astype(np.uint16))
+        out.append(fade)
+    return out
+
+
 def parse_hmxd(path):
     b = open(path, "rb").read()
     assert b[:4] == b"HMXD"
     ver, n = np.frombuffer(b, "<i4", 2, 4)
-    assert ver == 4
+    assert ver in (4, 5)  # 5 adds the weighted-prediction records behind every picture
     off, pics = 12, []
     for _ in range(n):
         poc, w, h, B, qp, ctu, slice_type, n_tu, n_pu, n_cu = (int(v) for v in np.frombuffer(b, "<i4", 10, off))
@@ -95,18 +112,64 @@ def parse_hmxd(path):
             pw, ph = w >> (1 if p else 0), h >> (1 if p else 0)
             rec.append(np.frombuffer(b, "<i2", pw * ph, off).reshape(ph, pw).copy())
             off += 2 * pw * ph
-        pics.append(dict(poc=poc, w=w, h=h, B=B, qp=qp, ctu=ctu, tus=tus, pus=pus, cus=cus, slice_type=slice_type, lev=lev, rec=rec, sao=sao, dbk=dbk))
+        # explicit weighted prediction: PPS flags, entries per list, per entry its POC and the rows [component][weight, offset, log2 denominator],
+        # the two reference indices of every prediction unit
+        wp = dict(flags=(0, 0), poc=[], tab=[], ridx=None)
+        if ver >= 5:
+            use_wp, wp_bipred, n0, n1 = (int(v) for v in np.frombuffer(b, "<i4", 4, off))
+            off += 16
+            wp_poc, wp_tab = [], []
+            for cnt in (n0, n1):
+                a = np.frombuffer(b, "<i4", 10 * cnt, off).reshape(cnt, 10)
+                off += 40 * cnt
+                wp_poc.append(a[:, 0].astype(np.int16))
+                wp_tab.append(a[:, 1:].reshape(cnt, 3, 3).astype(np.int16))
+            ridx = np.frombuffer(b, "i1", 2 * n_pu, off).reshape(n_pu, 2).copy()
+            off += 2 * n_pu
+            wp = dict(flags=(use_wp, wp_bipred), poc=wp_poc, tab=wp_tab, ridx=ridx)
+        pics.append(dict(wp=wp, poc=poc, w=w, h=h, B=B, qp=qp, ctu=ctu, tus=tus, pus=pus, cus=cus, slice_type=slice_type, lev=lev, rec=rec, sao=sao, dbk=dbk))
     assert off == len(b)
     return pics
 
 
-def make(name, seed, w, h, n, B, qp, cfg, extra=(), smooth=False, motion=False, keep_org=False, out_dir=HERE):
+def weighted(p):
+    """the slice is predicted with explicit weights (TComSlice::applyWP): P with the PPS's use-WP flag, B with its WP bi-pred flag"""
+    return bool((p["slice_type"] == 1 and p["wp"]["flags"][0]) or (p["slice_type"] == 0 and p["wp"]["flags"][1]))
+
+
+def check_weighted(pics):
+    """What a weighted fixture must hold, on what the tap recorded: a P slice and a B slice with a luma row and a chroma row that
+    are not the default, a bi-predicted unit on two rows that differ, a uni-predicted unit of a B slice on list 1; every row inside
+    the coded ranges.  Returns the counts."""
+    cnt = dict(rows_P=[0, 0], rows_B=[0, 0], bi_rows_differ=0, uni_list1_in_B=0)
+    for p in pics:
+        if not weighted(p):
+            continue
+        tab, ridx = p["wp"]["tab"], p["wp"]["ridx"]
+        for t in tab:
+            assert ((t[:, :, 0] >= -128) & (t[:, :, 0] <= 255) & (t[:, :, 1] >= -128) & (t[:, :, 1] <= 127) & (t[:, :, 2] >= 0) & (t[:, :, 2] <= 7)).all(), t
+        used = {(l, int(r[l])) for r in ridx for l in (0, 1) if r[l] >= 0}
+        for l, i in used:
+            off_default = (tab[l][i][:, 0] != (1 << tab[l][i][:, 2])) | (tab[l][i][:, 1] != 0)
+            key = "rows_P" if p["slice_type"] == 1 else "rows_B"
+            cnt[key][0] += int(off_default[0])
+            cnt[key][1] += int(off_default[1:].any())
+        if p["slice_type"] == 0:
+            for r in ridx:
+                if r[0] >= 0 and r[1] >= 0:
+                    cnt["bi_rows_differ"] += int(not np.array_equal(tab[0][r[0]], tab[1][r[1]]))
+                elif r[1] >= 0:
+                    cnt["uni_list1_in_B"] += int(((tab[1][r[1]][:, 0] != (1 << tab[1][r[1]][:, 2])) | (tab[1][r[1]][:, 1] != 0)).any())
+    return cnt
+
+
+def make(name, seed, w, h, n, B, qp, cfg, extra=(), smooth=False, motion=False, keep_org=False, out_dir=HERE, fade=False, need=("P",)):
     enc, tap = os.path.join(REFBIN, "TAppEncoder"), os.path.join(REFBIN, "hm_decision_tap")
     if not (os.path.exists(enc) and os.path.exists(tap)):
         subprocess.check_call(["bash", os.path.join(ROOT, "oracle", "build_ref_apps.sh")])
     with tempfile.TemporaryDirectory() as d:
         yuv, bit, out = (os.path.join(d, f) for f in ("in.yuv", "str.bin", "out.hmxd"))
-        clip = synthetic_clip(seed, w, h, n, B, smooth, motion)
+        clip = fading_clip(seed, w, h, n, B) if fade else synthetic_clip(seed, w, h, n, B, smooth, motion)
         with open(yuv, "wb") as f:
             for planes in clip:
                 for p in planes:
@@ -126,12 +189,23 @@ def make(name, seed, w, h, n, B, qp, cfg, extra=(), smooth=False, motion=False, 
         if keep_org:  # the encoder's input picture (all-intra: coding order = input order)
             for k in range(3):
                 arrays[f"org{i}_{k}"] = clip[p["poc"]][k].astype(np.int16)
+        if weighted(p):  # the slice's tables: per list the POC of every entry and its rows [entry][component][weight, offset, log2 denominator]; ridx: the units' reference indices
+            arrays[f"wpflags{i}"] = np.array(p["wp"]["flags"], np.int32)
+            for l in (0, 1):
+                arrays[f"wppoc{i}_{l}"], arrays[f"wptab{i}_{l}"] = p["wp"]["poc"][l], p["wp"]["tab"][l]
+            arrays[f"ridx{i}"] = p["wp"]["ridx"]
         arrays[f"tus{i}"] = p["tus"]
         arrays[f"sao{i}"] = p["sao"]
         arrays[f"dbk{i}"] = p["dbk"]
         for k in range(3):
             arrays[f"lev{i}_{k}"] = p["lev"][k]
             arrays[f"rec{i}_{k}"] = p["rec"][k]
+    if fade:
+        cnt = check_weighted(pics)
+        assert "P" not in need or min(cnt["rows_P"]) > 0, cnt
+        assert "B" not in need or (min(cnt["rows_B"]) > 0 and cnt["bi_rows_differ"] > 0 and cnt["uni_list1_in_B"] > 0), cnt
+        print(f"stream_{name}: non-default (luma, chroma) rows in use, P slices {cnt['rows_P']}, B slices {cnt['rows_B']}; bi units on two differing rows "
+              f"{cnt['bi_rows_differ']}; list-1 uni units of B slices on a non-default row {cnt['uni_list1_in_B']}")
     path = os.path.join(out_dir, f"stream_{name}.npz")
     np.savez_compressed(path, **arrays)
     sizes = np.bincount(np.concatenate([p["tus"]["log2n"][p["tus"]["plane"] == 0] for p in pics]), minlength=6)[2:]
@@ -179,3 +253,6 @@ if __name__ == "__main__":
     make("randomaccess_main_q34_full", 20, 256, 192, 9, 8, 34, "encoder_randomaccess_main.cfg", motion=True)
     # 10-bit low-delay B, 416x240 (coding units cut by the picture boundary, vectors that leave the picture), filters on
     make("lowdelay_he10_q33_416x240_full", 21, 416, 240, 3, 10, 33, "encoder_lowdelay_he10.cfg", motion=True)
+    # explicit weighted prediction on a fading clip: P slices (loop filters off), B slices with both flags (filters as shipped)
+    make("lowdelay_P_wp_q30", 25, 192, 128, 4, 8, 30, "encoder_lowdelay_P_main.cfg", PURE + ["-wpP", "1"], fade=True, need=("P",))
+    make("randomaccess_wp_q32", 26, 192, 128, 5, 8, 32, "encoder_randomaccess_main.cfg", ["-wpP", "1", "-wpB", "1"], fade=True, need=("B",))

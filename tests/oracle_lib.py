@@ -288,6 +288,94 @@ def r_intra_frame_encode(tus, w, h, B, qp, org, sign_hide=1):
     return rec, lev
 
 
+# ---- explicit weighted prediction through the compiled reference's own members (ref().ref_init(B, w, h, ...) with a picture first).
+# An entry is (weight[3], offset[3], log2_denom[3]) per component Y, Cb, Cr, as in tests/wp_oracle.py.
+
+def _ref_wp():
+    """ref() with the weighted-prediction taps bound (on first use, like r_rdoq's: a libhmref.so built before they existed still
+    serves everything else)"""
+    R, P3 = ref(), C.c_void_p * 3
+    R.ref_xWeightedPredictionUni.argtypes = [ci, ci, i32p, P3, P3, ci, ci]
+    R.ref_xWeightedPredictionBi.argtypes = [ci, ci, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, P3, ci, ci]
+    R.ref_getWpScaling.argtypes = [ci, ci, C.c_void_p, C.c_void_p, i32p]
+    return R
+
+
+def _wp_rows(e):
+    return None if e is None else np.array([[e[0][c], e[1][c], e[2][c]] for c in range(3)], np.int32).reshape(-1)
+
+
+def _p3(planes):
+    planes = None if planes is None else [np.ascontiguousarray(p, np.int16) for p in planes]
+    return planes, (None if planes is None else (C.c_void_p * 3)(*[p.ctypes.data for p in planes]))
+
+
+def r_wp_uni(src, e, lst, idx=0):
+    """xWeightedPredictionUni of list lst, reference index idx, on [Y, Cb, Cr] 14-bit planes"""
+    src, ps = _p3(src)
+    out, po = _p3([np.zeros_like(p) for p in src])
+    h, w = src[0].shape
+    assert _ref_wp().ref_xWeightedPredictionUni(lst, idx, _wp_rows(e), ps, po, w, h) == 0
+    return out
+
+
+def r_wp_bi(src0, src1, e0, e1, idx0=0, idx1=0):
+    """xWeightedPredictionBi; a list with e = None is unused (its reference index is passed as -1)"""
+    src0, p0 = _p3(None if e0 is None else src0)
+    src1, p1 = _p3(None if e1 is None else src1)
+    out, po = _p3([np.zeros_like(p) for p in (src0 if src0 is not None else src1)])
+    h, w = out[0].shape
+    r0, r1 = _wp_rows(e0), _wp_rows(e1)
+    assert _ref_wp().ref_xWeightedPredictionBi(-1 if e0 is None else idx0, -1 if e1 is None else idx1, _vp(r0), _vp(r1), p0, p1, po, w, h) == 0
+    return out
+
+
+def r_wp_scaling(e0, e1):
+    """the fields getWpScaling derives: per component a dict like wp_oracle.get_wp_scaling's, and the raw [list][component][5] array"""
+    raw = np.zeros(30, np.int32)
+    assert _ref_wp().ref_getWpScaling(-1 if e0 is None else 0, -1 if e1 is None else 0, _vp(_wp_rows(e0)), _vp(_wp_rows(e1)), raw) == 0
+    raw = raw.reshape(2, 3, 5)
+    out = []
+    for c in range(3):
+        a = raw[0 if e0 is not None else 1][c]
+        out.append(dict(w0=int(a[0]), w1=int(raw[1][c][0]) if (e0 is not None and e1 is not None) else None, offset=int(a[2]), shift=int(a[3]),
+                        round=int(a[4])))
+    return out, raw
+
+
+def r_mc_frame_wp(pus, pics, order, wp, B, b_slice=True):
+    """One picture's weighted prediction composed from the compiled reference alone, as TComPrediction::xPredInterBi composes it
+    (TComPrediction.cpp:497-535): xPredInterLumaBlk / xPredInterChromaBlk with bi = true per used list, then xWeightedPredictionBi
+    with the unit's two reference indices (B slice) or xWeightedPredictionUni on list 0 (P slice).  pics: reference pictures
+    ([Y, Cb, Cr] without margins; the reference extends them itself), order[r] = the picture of refs[] entry r, wp = (l0, l1) indexed
+    by r like hmx_mc_wp.  Vectors are used as given (no clipMv); units must lie inside the picture."""
+    R = ref()
+    H, W = pics[0][0].shape
+    R.ref_init(B, W, H, 1)
+    out = [np.zeros((H, W), np.int16), np.zeros((H // 2, W // 2), np.int16), np.zeros((H // 2, W // 2), np.int16)]
+    for u in pus:
+        x, y, w, h = int(u["x"]), int(u["y"]), int(u["w"]), int(u["h"])
+        assert x + w <= W and y + h <= H
+        inter, ent, idx = [None, None], [None, None], [0, 0]
+        for lst, (r, mvx, mvy) in enumerate(((int(u["ref0"]), int(u["mv0x"]), int(u["mv0y"])), (int(u["ref1"]), int(u["mv1x"]), int(u["mv1y"])))):
+            if r == 255:
+                continue
+            p = [np.ascontiguousarray(a, np.int16).reshape(-1) for a in pics[order[r]]]
+            R.ref_set_recon(p[0], p[1], p[2])
+            t = [np.zeros((h, w), np.int16), np.zeros((h // 2, w // 2), np.int16), np.zeros((h // 2, w // 2), np.int16)]
+            R.ref_predInterBlk(x, y, w, h, mvx, mvy, 1, t[0].reshape(-1), t[1].reshape(-1), t[2].reshape(-1), 0)
+            inter[lst], ent[lst], idx[lst] = t, wp[lst][r], r
+        if b_slice:
+            got = r_wp_bi(inter[0], inter[1], ent[0], ent[1], idx[0], idx[1])
+        else:
+            assert ent[1] is None
+            got = r_wp_uni(inter[0], ent[0], 0, idx[0])
+        for c in range(3):
+            s = 1 if c else 0
+            out[c][y >> s:(y + h) >> s, x >> s:(x + w) >> s] = got[c]
+    return out
+
+
 def o_rdoq(coef, N, B, cfg, est):
     coef = np.ascontiguousarray(coef, np.int32).reshape(-1)
     lvl = np.zeros(N * N, np.int32)

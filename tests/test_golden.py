@@ -8,6 +8,8 @@ import pytest
 
 import extreme_inputs as xi
 import oracle_lib as ol
+import wp_cases as wc
+import wp_oracle as wo
 
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 REG_DCT = 65535
@@ -273,6 +275,30 @@ def test_oracle_edge_vectors():
     _oracle_inter(f"inter_{EDGE}.npz", 12)
     _oracle_deblock(f"deblock_{EDGE}.npz", 12)
     _oracle_sao(f"sao_{EDGE}.npz", 12)
+
+
+@pytest.mark.parametrize("B", [8, 10, 12])
+def test_oracle_wp(B):
+    """tests/wp_oracle.py (both restatements, and mc_frame_wp over the pinned oracle's interpolation) against the reference's
+    xWeightedPredictionBi and its composition with xPredInter*Blk, as recorded in wp_b*.npz; no reference needed."""
+    blocks, S = wc.load_vectors(B)
+    assert {(b["w"], b["h"]) for b in blocks} == set(wc.SHAPES) and {b["pattern"] for b in blocks} == {wc.BI, wc.L0_ONLY, wc.L1_ONLY}
+    for k, b in enumerate(blocks):
+        if b["pattern"] == wc.BI:
+            got = [wo.add_weight_bi_loop(b["src0"], b["src1"], b["e0"], b["e1"], B), wo.add_weight_bi_vec(b["src0"], b["src1"], b["e0"], b["e1"], B)]
+        else:
+            src, e = (b["src0"], b["e0"]) if b["pattern"] == wc.L0_ONLY else (b["src1"], b["e1"])
+            got = [wo.add_weight_uni_loop(src, e, B), wo.add_weight_uni_vec(src, e, B)]
+        for g in got:
+            for c in range(3):
+                assert np.array_equal(g[c], b["out"][c]), (k, c, b["pattern"], b["e0"], b["e1"])
+    clip = [c for c in wo.CLIP_CASES if c[0] == B]  # the hand-computed rows close the block cases
+    for (_, _, _, want), b in zip(clip, blocks[len(blocks) - len(clip):]):
+        assert all((p == want).all() for p in b["out"])
+    wc.check_pu_scene(S)
+    got = wo.mc_frame_wp(S["pus"], S["ext"], (S["l0"], S["l1"]), B)
+    for c in range(3):
+        assert np.array_equal(got[c], S["want"][c]), ("unit list", c)
 
 
 FRAMES = [("frame_416x240_mix_b8.npz", 8), ("frame_200x136_mix_b10.npz", 10)]
@@ -575,5 +601,50 @@ def test_gpu_12bit_vectors(tag):
         _gpu_inter(ctx, f"inter_{tag}.npz")
         _gpu_deblock(ctx, f"deblock_{tag}.npz")
         _gpu_sao(ctx, f"sao_{tag}.npz")
+    finally:
+        ctx.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("B", [8, 10, 12])
+def test_gpu_wp(B):
+    """hmx_addWeightUni / hmx_addWeightBi per component and hmx_motionCompensation_wp per unit against the reference's results in
+    wp_b*.npz (the batch entry: tests/test_gpu_wp.py)."""
+    from thevc_amd import capi
+    blocks, S = wc.load_vectors(B)
+    ctx = capi.Context(bit_depth=B)
+    try:
+        for k, b in enumerate(blocks):
+            for c in range(3):
+                h, w = b["out"][c].shape
+                f = lambda e: (int(e[0][c]), int(e[1][c]), int(e[2][c]))
+                if b["pattern"] == wc.BI:
+                    (w0, o0, d0), (w1, o1, _) = f(b["e0"]), f(b["e1"])
+                    got = ctx.addWeightBi(b["src0"][c], b["src1"][c], w, h, w0, w1, o0, o1, d0)
+                else:
+                    src, e = (b["src0"], b["e0"]) if b["pattern"] == wc.L0_ONLY else (b["src1"], b["e1"])
+                    got = ctx.addWeightUni(src[c], w, h, *f(e))
+                assert np.array_equal(got.reshape(h, w), b["out"][c]), (k, c, b["pattern"], b["e0"], b["e1"])
+        M = wc.MARGIN
+
+        def pic_of(planes):
+            p = capi.Pic()
+            for k, a in enumerate(planes):
+                m = M >> (1 if k else 0)
+                p.plane[k], p.stride[k] = a.ctypes.data + 2 * (m * a.shape[1] + m), a.shape[1]
+            return p
+
+        for i, u in enumerate(S["pus"]):
+            x, y, w, h, r0, r1 = (int(u[n]) for n in ("x", "y", "w", "h", "ref0", "ref1"))
+            dst = [np.zeros((h, w), np.int16), np.zeros((h // 2, w // 2), np.int16), np.zeros((h // 2, w // 2), np.int16)]
+            dp = capi.Pic()
+            for k in range(3):
+                dp.plane[k], dp.stride[k] = dst[k].ctypes.data, dst[k].shape[1]
+            ctx.motion_compensation_wp(None if r0 == 255 else pic_of(S["ext"][r0][0]), (int(u["mv0x"]), int(u["mv0y"])),
+                                       None if r1 == 255 else pic_of(S["ext"][r1][0]), (int(u["mv1x"]), int(u["mv1y"])), x, y, w, h, dp,
+                                       None if r0 == 255 else capi.wp_entry(*S["l0"][r0]), None if r1 == 255 else capi.wp_entry(*S["l1"][r1]))
+            for k in range(3):
+                s = 1 if k else 0
+                assert np.array_equal(dst[k], S["want"][k][y >> s:(y + h) >> s, x >> s:(x + w) >> s]), ("unit", i, k, tuple(u))
     finally:
         ctx.close()

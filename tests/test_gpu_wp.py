@@ -1,6 +1,7 @@
 """Explicit weighted prediction on the GPU against tests/wp_oracle.py: the scalar drop-ins (hmx_addWeightUni / hmx_addWeightBi),
 one prediction unit (hmx_motionCompensation_wp), the batch entry in both schedules (cell map, one wave per PU), a call that
-mixes weighted and unweighted jobs, and the host-side argument checks."""
+mixes weighted and unweighted jobs, and the host-side argument checks.  The batch entry is also held directly on the reference's own
+results (tests/golden/wp_b*.npz, at 8, 10 and 12 bit); the scalar entries and the single unit on them: tests/test_golden.py."""
 import ctypes as C
 import functools
 
@@ -8,6 +9,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as ol
+import wp_cases as wc
 import wp_oracle as wo
 from thevc_amd import capi
 
@@ -177,9 +179,9 @@ class Device:
     """The scene on the device: references with extended borders; destinations WITH margins, so that the part of a unit
     beyond the picture edge, which the one-wave-per-PU schedule writes, lands in allocated memory."""
 
-    def __init__(self, ctx, S):
-        L, w, h, m = capi.lib(), PIC_W, PIC_H, MARGIN
-        self.ctx = ctx
+    def __init__(self, ctx, S, size=(PIC_W, PIC_H, MARGIN)):
+        L, (w, h, m) = capi.lib(), size
+        self.ctx, self.size = ctx, size
         self.pics = [capi.DevPicture(ctx, w, h, m, m).upload(p) for p in S["pics"]]
         for d in self.pics:
             ctx._chk(L.hmx_pic_extend_border(ctx.h, C.byref(d.as_pic()), w, h, m, m))
@@ -191,12 +193,13 @@ class Device:
         arr = (capi.McJob * len(counts))()
         self.dst_pics = (capi.Pic * len(counts))()
         self.keep.append(self.dst_pics)
+        w, h, m = self.size
         for q, n in enumerate(counts):
-            d = capi.DevPicture(self.ctx, PIC_W, PIC_H, MARGIN, MARGIN).zero()
+            d = capi.DevPicture(self.ctx, w, h, m, m).zero()
             self.dst.append(d)
             self.dst_pics[q] = d.as_pic()
             arr[q].d_pus, arr[q].n_pus, arr[q].refs, arr[q].n_refs = self.d_pus.ptr, n, self.refs, 4
-            arr[q].dst, arr[q].pic_w, arr[q].pic_h = C.pointer(self.dst_pics[q]), (PIC_W if mapped else 0), (PIC_H if mapped else 0)
+            arr[q].dst, arr[q].pic_w, arr[q].pic_h = C.pointer(self.dst_pics[q]), (w if mapped else 0), (h if mapped else 0)
         return arr, self.dst[-len(counts):]
 
     def free(self):
@@ -255,6 +258,42 @@ def test_mixed_call(ctx, mapped):
         assert np.array_equal(got[p], want[p]), ("P slice", p)
     dev.free()
     d_uni.free()
+
+
+# ---- the batch entry on the reference's results ----
+@pytest.mark.parametrize("mapped", [True, False], ids=["cell_map", "wave_per_pu"])
+@pytest.mark.parametrize("B", [8, 10, 12])
+def test_batch_vs_reference_vectors(B, mapped):
+    """The unit list of wp_b*.npz (136x72: partial tiles in both directions, AMP shapes, 64x64, height-4 pairs with different rows,
+    a picture entered in refs[] twice) with pic_w = 0 and with the picture size, and the same weighted job beside an unweighted job
+    of the same list in one call."""
+    _, S = wc.load_vectors(B)
+    L = capi.lib()
+    c = capi.Context(bit_depth=B)
+    try:
+        dev = Device(c, S, (wc.PIC_W, wc.PIC_H, wc.MARGIN))
+        tabs = (table(S["l0"]), table(S["l1"]))
+        n = len(S["pus"])
+        jobs, dst = dev.jobs([n], mapped)
+        c.batch_motion_compensation_wp(jobs, [tabs])
+        jobs3, dst3 = dev.jobs([n, n, n], mapped)
+        c.batch_motion_compensation_wp(jobs3, [None, tabs, None])
+        plain_jobs, plain_dst = dev.jobs([n], mapped)
+        c._chk(L.hmx_batch_motionCompensation_multi(c.h, 1, plain_jobs))
+        c.sync()
+        for what, d in (("alone", dst[0]), ("between unweighted jobs", dst3[1])):
+            got = d.download()
+            for p in range(3):
+                assert np.array_equal(got[p], S["want"][p]), (what, p, np.argwhere(got[p] != S["want"][p])[:4])
+        plain = plain_dst[0].download(with_margins=True)
+        assert any((a != b).any() for a, b in zip(plain_dst[0].download(), S["want"]))  # the weights matter on this list
+        for q in (0, 2):
+            got = dst3[q].download(with_margins=True)
+            for p in range(3):
+                assert np.array_equal(got[p], plain[p]), ("unweighted job", q, p)
+        dev.free()
+    finally:
+        c.close()
 
 
 # ---- 5. host validation ----

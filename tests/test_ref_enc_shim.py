@@ -1,6 +1,6 @@
 """The ENCODER side of the drop-in, shown: the REFERENCE's encoder application with the bodies of its hot-path members replaced by
 libhmx calls (oracle/build_ref_enc_shim.sh: xT, xIT, xTransformSkip / xITransformSkip, xQuant, xRateDistOptQuant, xDeQuant,
-predIntraLumaAng / ChromaAng, xPredInterLumaBlk / ChromaBlk, filterHor/Ver Luma/Chroma, addAvg, calcHAD -- the INTEGRATION.md
+predIntraLumaAng / ChromaAng, xPredInterLumaBlk / ChromaBlk, filterHor/Ver Luma/Chroma, addAvg, addWeightUni / addWeightBi, calcHAD -- the INTEGRATION.md
 section 3 bodies) encodes synthetic clips and writes the bitstream of the unmodified encoder, BYTE FOR BYTE.  Every decision of
 the encoder's search goes through these members -- 35 modes x calcHAD per prediction unit incl. the 64x64 one, RDOQ with the bit
 estimates of the live CABAC state (TEncSearch.cpp:1101, TEncSbac::estBit), the half- and quarter-sample planes of the motion
@@ -45,9 +45,10 @@ def test_fixtures_are_the_unmodified_encoders_streams(case, tmp_path):
 @pytest.mark.gpu
 @pytest.mark.parametrize("case", CASES, ids=[c["name"] for c in CASES])
 def test_reference_encoder_on_libhmx(case, tmp_path):
-    if not os.path.exists(os.path.join(REF, "TAppEncoder_hmx")):
-        pytest.skip("oracle/_ref/TAppEncoder_hmx not built (bash oracle/build_ref_enc_shim.sh in the build container)")
-    got, err = _encode("TAppEncoder_hmx", case, tmp_path, "hmx")
+    binary = "TAppEncoder_hmx_wp" if case.get("fade") else "TAppEncoder_hmx"  # _wp: addWeightUni / addWeightBi replaced as well
+    if not os.path.exists(os.path.join(REF, binary)):
+        pytest.skip(f"oracle/_ref/{binary} not built (bash oracle/build_ref_enc_shim.sh in the build container)")
+    got, err = _encode(binary, case, tmp_path, "hmx")
     want = open(os.path.join(HERE, "golden", "enc", case["name"] + ".bin"), "rb").read()
     calls = {u: int(n) for n, u in re.findall(r"libhmx shim: (\d+) calls from (\w+)", err)}
     assert got == want, (len(got), len(want), calls, err[-800:])
@@ -56,3 +57,5 @@ def test_reference_encoder_on_libhmx(case, tmp_path):
     assert calls.get("TComTrQuant", 0) > 1000 and calls.get("TComPrediction", 0) > 1000 and calls.get("TComRdCost", 0) > 1000, calls
     if case["inter"]:
         assert calls.get("TComInterpolationFilter", 0) > 100, calls
+    if case.get("fade"):  # weighted P slices: motion compensation and the AMVP template go through addWeightUni
+        assert calls.get("TComWeightPrediction", 0) > 100, calls

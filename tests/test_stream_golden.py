@@ -10,8 +10,10 @@ import numpy as np
 import pytest
 
 import oracle_lib as ol
+import wp_oracle as wo
 from thevc_amd.decisions import (MARGIN, TU_INTER, deblock_maps, has_sao, is_deblocked, levels_to_planes,  # noqa: F401
-                                 load_pictures as pictures, prediction_units, reference_pocs, split_blocks, strength_inputs, z_offset)
+                                 load_pictures as pictures, prediction_units, reference_pocs, split_blocks, strength_inputs, weighted,
+                                 weighted_prediction_units, z_offset)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 FIXTURES = sorted(glob.glob(os.path.join(HERE, "golden", "stream_*.npz")))
@@ -28,7 +30,12 @@ def oracle_decode_sequence(pics, hook=None):
         lev = levels_to_planes(p)
         rec = [np.zeros((h, w), np.int16), np.zeros((h // 2, w // 2), np.int16), np.zeros((h // 2, w // 2), np.int16)]
         intra_tus, inter_tus = split_blocks(p)
-        if len(p["pus"]):
+        if len(p["pus"]) and weighted(p):  # explicit weighted prediction: tests/wp_oracle.py, pinned by tests/test_oracle_vs_ref_wp.py
+            pus, pocs, l0, l1 = weighted_prediction_units(p)
+            planes = [([ext[poc][k].reshape((h >> (1 if k else 0)) + 2 * (m >> (1 if k else 0)), -1) for k in range(3)], m) for poc in pocs]
+            rows = [[(t["weight"].tolist(), t["offset"].tolist(), t["log2_denom"].tolist()) for t in tab] for tab in (l0, l1)]
+            rec = wo.mc_frame_wp(pus, planes, rows, B)
+        elif len(p["pus"]):
             pocs = reference_pocs(p)
             pus = prediction_units(p, {poc: i for i, poc in enumerate(pocs)})
             ptrs = (C.c_void_p * (3 * len(pocs)))()
@@ -37,6 +44,7 @@ def oracle_decode_sequence(pics, hook=None):
                     pm, pw = (m, w) if k == 0 else (m // 2, w // 2)
                     ptrs[i * 3 + k] = ext[poc][k].ctypes.data + 2 * (pm * (pw + 2 * pm) + pm)
             O.hmo_mc_frame(pus.ctypes.data, len(pus), B, ptrs, I3(w + 2 * m, w // 2 + m, w // 2 + m), P3(*[a.ctypes.data for a in rec]), st)
+        if len(p["pus"]):
             if hook:
                 hook(p, [a.copy() for a in rec], lev, inter_tus)
             mx = (1 << B) - 1

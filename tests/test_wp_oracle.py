@@ -1,6 +1,7 @@
-"""tests/wp_oracle.py, the yardstick of explicit weighted prediction, checked on the CPU: its two restatements agree, it is
-tied to the pinned oracle by the two identities (unit weights give the unweighted prediction / addAvg), and it gives the
-hand-computed samples at the clips.  No GPU."""
+"""tests/wp_oracle.py, the yardstick of explicit weighted prediction, checked on the CPU for its own consistency: its two
+restatements agree, unit weights give the pinned oracle's unweighted prediction / addAvg, and it gives the hand-computed samples at
+the clips.  What ties it to the reference is tests/test_oracle_vs_ref_wp.py (the compiled reference's own members) and, where the
+reference is absent, the reference's recorded results in tests/golden/wp_b*.npz (tests/test_golden.py::test_oracle_wp).  No GPU."""
 import numpy as np
 import pytest
 

@@ -2,7 +2,8 @@
 reference's, via oracle/ref_decision_tap.cpp) into libhmx calls, picture by picture in decoding
 order, with libhmx's own earlier outputs as reference pictures:
 
-    inter coding units   hmx_batch_motionCompensation_multi, hmx_batch_invtransformNxN_multi
+    inter coding units   hmx_batch_motionCompensation_multi (hmx_batch_motionCompensation_wp_multi for a slice under explicit
+                         weighted prediction), hmx_batch_invtransformNxN_multi
     intra coding units   hmx_frame_intra_decode (intra pictures) / hmx_frame_intra_decode_onto (inside inter pictures)
     loop filters         hmx_deblock_strengths_multi (inter pictures; intra pictures have strength 2 on every edge),
                          hmx_deblock_picture_multi, hmx_sao_picture_multi (a decoder holds one picture at a time: batches of 1);
@@ -17,7 +18,9 @@ tc_offset_div2]), and the layout of its slices, tiles and constrained intra pred
 raster order, or None: one region) and cip (constrained_intra_pred_flag).  For the loop filters: slice_id / tile_id (slice
 index in decoding order / tile index per CTU in raster order, or None: one slice / tile), lf_cross_slice (one
 slice_loop_filter_across_slices_enabled_flag per slice) and lf_cross_tile (loop_filter_across_tiles_enabled_flag); from these
-lf_border_avail() makes the byte per CTU that says which neighbour CTUs deblocking and SAO may read.  load_pictures() reads
+lf_border_avail() makes the byte per CTU that says which neighbour CTUs deblocking and SAO may read.  wp: None, or the slice's
+explicit weighted prediction: flags (the PPS's use WP, WP bi-pred), poc / tab (per list: the POC of every entry, its rows
+[entry][component][weight, offset, log2 denominator]) and ridx (the two reference indices of every prediction unit).  load_pictures() reads
 the .npz fixtures of tests/golden/make_stream_golden.py, make_stream_layout_golden.py and make_stream_lf_golden.py.  The
 numpy helpers import nothing of the GPU side; decode_sequence() needs libhmx."""
 import ctypes as C
@@ -54,7 +57,9 @@ def load_pictures(path):
                    slice_id=np.ascontiguousarray(d[f"slice_id{i}"], np.uint32) if f"slice_id{i}" in d else None,
                    tile_id=np.ascontiguousarray(d[f"tile_id{i}"], np.uint32) if f"tile_id{i}" in d else None,
                    lf_cross_slice=np.ascontiguousarray(d[f"lf_cross_slice{i}"], np.uint8) if f"lf_cross_slice{i}" in d else None,
-                   lf_cross_tile=bool(int(d[f"lf_cross_tile{i}"])) if f"lf_cross_tile{i}" in d else True)
+                   lf_cross_tile=bool(int(d[f"lf_cross_tile{i}"])) if f"lf_cross_tile{i}" in d else True,
+                   wp=dict(flags=tuple(int(v) for v in d[f"wpflags{i}"]), poc=[d[f"wppoc{i}_{l}"] for l in (0, 1)], tab=[d[f"wptab{i}_{l}"] for l in (0, 1)],
+                           ridx=d[f"ridx{i}"]) if f"wpflags{i}" in d else None)
 
 
 def tile_scan(cw, ch, col_bounds, row_bounds):
@@ -270,6 +275,51 @@ def prediction_units(p, slot):
     return out
 
 
+def weighted(p):
+    """The slice is predicted with explicit weights: a P slice under the PPS's use-WP flag, a B slice under its WP bi-pred flag
+    (TComPrediction.cpp:516-535; a B slice with use WP alone is NOT weighted)."""
+    wp = p.get("wp")
+    return bool(wp and ((p["slice_type"] == 1 and wp["flags"][0]) or (p["slice_type"] == 0 and wp["flags"][1])))
+
+
+def weighted_prediction_units(p):
+    """A weighted slice's units for hmx_batch_motionCompensation_wp_multi: (hmx_pu records, the POC of every refs[] entry, l0, l1).
+    refs[] gets one entry per distinct (picture, list-0 row, list-1 row), as include/hmx.h prescribes: the (list, refIdx) pairs
+    the units use, list 0's first; a pair of list 1 joins an entry of the same picture whose list-1 row is free or equal.  A
+    picture that sits in a list twice with different rows therefore has two entries.  l0 / l1: tables of capi.WP_DTYPE indexed
+    like refs[]; a row no unit addresses holds the default weight 1 << denominator, offset 0."""
+    from thevc_amd import capi
+    wp = p["wp"]
+    used = {}
+    for u, r in zip(p["pus"], wp["ridx"]):
+        for l in (0, 1):
+            if r[l] >= 0:
+                assert int(u[f"poc{l}"]) == int(wp["poc"][l][r[l]])
+                used[(l, int(r[l]))] = int(u[f"poc{l}"])
+    entries, index = [], {}  # [poc, row of list 0 or None, row of list 1 or None]
+    for (l, i), poc in sorted(used.items()):
+        row = tuple(int(v) for v in np.asarray(wp["tab"][l][i]).reshape(-1))
+        for k, e in enumerate(entries):
+            if e[0] == poc and e[1 + l] in (None, row) and (l == 1 or e[1] == row):
+                e[1 + l], index[(l, i)] = row, k
+                break
+        else:
+            index[(l, i)] = len(entries)
+            entries.append([poc, row if l == 0 else None, row if l == 1 else None])
+    denom = [int(v) for v in np.asarray(wp["tab"][0][0])[:, 2]]
+    default = tuple(v for d in denom for v in (1 << d, 0, d))
+    tabs = [np.zeros(len(entries), capi.WP_DTYPE), np.zeros(len(entries), capi.WP_DTYPE)]
+    for k, e in enumerate(entries):
+        for l in (0, 1):
+            row = np.array(e[1 + l] or default).reshape(3, 3)
+            tabs[l][k]["weight"], tabs[l][k]["offset"], tabs[l][k]["log2_denom"] = row[:, 0], row[:, 1], row[:, 2]
+    slot = [{poc: 0 for poc in used.values()}] * 2  # placeholders: the slots of a weighted slice come from the reference indices
+    out = prediction_units(p, slot[0])
+    for l in (0, 1):
+        out[f"ref{l}"] = [index[(l, int(r[l]))] if r[l] >= 0 else 255 for r in wp["ridx"]]
+    return out, [e[0] for e in entries], tabs[0], tabs[1]
+
+
 def reference_pocs(p):
     return sorted({int(v) for l in (0, 1) for v in p["pus"][f"poc{l}"] if v > -32768})
 
@@ -295,8 +345,15 @@ def decode_sequence(pics):
             rec_arr = (capi.Pic * 1)(d_rec.as_pic())
             keep = []
             if len(p["pus"]):
-                pocs = reference_pocs(p)
-                pus = prediction_units(p, {poc: i for i, poc in enumerate(pocs)})
+                # Without weighting a unit whose two lists name one picture and one vector is predicted from list 0 alone
+                # (xCheckIdenticalMotion, TComPrediction.cpp:392-407); the average of a 14-bit intermediate with itself rounds to the
+                # same sample, so the unweighted entry needs no such case.  Under WP bi-pred the shortcut is off (:394) and the weighted
+                # entry always takes the bi formula.
+                if weighted(p):
+                    pus, pocs, l0, l1 = weighted_prediction_units(p)
+                else:
+                    pocs = reference_pocs(p)
+                    pus = prediction_units(p, {poc: i for i, poc in enumerate(pocs)})
                 d_pus = ctx.to_device(pus)
                 ref_arr = (capi.Pic * len(pocs))(*[refs[poc].as_pic() for poc in pocs])
                 d_pred = capi.DevPicture(ctx, w, h).zero()
@@ -305,7 +362,10 @@ def decode_sequence(pics):
                     job = (capi.McJob * 1)()
                     job[0].d_pus, job[0].n_pus, job[0].refs, job[0].n_refs = d_pus.ptr, len(pus), ref_arr, len(pocs)
                     job[0].dst, job[0].pic_w, job[0].pic_h = C.pointer(dst[0]), w, h
-                    ctx._chk(L.hmx_batch_motionCompensation_multi(ctx.h, 1, job))
+                    if weighted(p):
+                        ctx.batch_motion_compensation_wp(job, [(l0, l1 if p["slice_type"] == 0 else None)])
+                    else:
+                        ctx._chk(L.hmx_batch_motionCompensation_multi(ctx.h, 1, job))
                 if len(inter_tus):
                     tl = ctx.tu_list(inter_tus)
                     d_lp = capi.DevPicture(ctx, w, h, dtype=np.int32).upload(levels_to_planes(p))
