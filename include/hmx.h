@@ -235,6 +235,19 @@ int hmx_getSSE(hmx_ctx *ctx, const hmx_pel *cur, int cur_stride, const hmx_pel *
  * sets under getUseFastEnc(), TEncSearch.cpp:4245-4251; the reference never sub-samples 8 rows or fewer: HMX_ERR_ARG). */
 int hmx_getSAD(hmx_ctx *ctx, const hmx_pel *cur, int cur_stride, const hmx_pel *org, int org_stride, int w, int h, int sub_shift,
                uint32_t *sad);
+/* TComRdCostWeightPrediction::xGetSADw (TComRdCostWeightPrediction.cpp:69-104) and xGetHADsw (:490-561), what xGetSAD* / xGetHADs
+ * return when DistParam::bApplyWeight is set (TComRdCost.cpp:492 ..., :2188).  Host pointers, sizes as hmx_getSAD.  (weight,
+ * offset, log2_denom) = the luma wpScalingParam of the reference searched (ranges as hmx_wp: anything else is HMX_ERR_ARG); with
+ * round = log2_denom ? 1 << (log2_denom - 1) : 0 every sample c of cur becomes
+ *   pred = (int16_t)(((weight * c + round) >> log2_denom) + offset * 2^(B-8))     -- product in int, wrapped to 16 bits, NOT clipped
+ * hmx_getSADw: *sad = (sum of |org - pred| over ALL rows) >> (B - 8); there is no sub_shift: xGetSADw ignores iSubShift.
+ * hmx_getHADsw: the Hadamard sum of org - pred over 8x8 sub-blocks when both sides are multiples of 8, else 4x4, each sub-block
+ * rounded on its own ((sum + 2) >> 2, (sum + 1) >> 1), the total >> (B - 8).  xCalcHADs4x4w / xCalcHADs8x8w (:204-423) were read
+ * against the unweighted functions: the same butterflies and the same roundings, only the difference is formed from pred. */
+int hmx_getSADw(hmx_ctx *ctx, const hmx_pel *cur, int cur_stride, const hmx_pel *org, int org_stride, int w, int h, int weight,
+                int offset, int log2_denom, uint32_t *sad);
+int hmx_getHADsw(hmx_ctx *ctx, const hmx_pel *cur, int cur_stride, const hmx_pel *org, int org_stride, int w, int h, int weight,
+                 int offset, int log2_denom, uint32_t *satd);
 
 /* ------------------------------------------------------------------------------------------------
  * Scalar drop-ins, TComInterpolationFilter (TLibCommon/TComInterpolationFilter.cpp:323-415) and
@@ -617,6 +630,10 @@ int hmx_batch_motionCompensation(hmx_ctx *ctx, const hmx_pu *d_pus, int n, const
  * refs / org: device pictures; the references with the reference's margins. */
 int hmx_batch_subpel_cost(hmx_ctx *ctx, const hmx_pu *pus, int n, const hmx_pic *refs, int n_refs, const hmx_pic *org,
                           const int8_t *offs, int n_cand, int use_had, uint32_t *d_cost);
+/* The same under weighted distortion (see "Weighted distortion in the motion search" below): unit i is weighted with
+ * wp[pus[i].ref0]; wp == NULL is hmx_batch_subpel_cost. */
+int hmx_batch_subpel_cost_wp(hmx_ctx *ctx, const hmx_pu *pus, int n, const hmx_pic *refs, int n_refs, const hmx_pic *org,
+                             const int8_t *offs, int n_cand, int use_had, uint32_t *d_cost, const hmx_wp *wp);
 
 /* ------------------------------------------------------------------------------------------------
  * Full-search integer motion estimation: the stage of TEncSearch::xMotionEstimation (TLibEncoder/TEncSearch.cpp:4120-4206)
@@ -651,7 +668,7 @@ typedef struct { int16_t mvx, mvy; uint32_t sad; uint32_t cost; } hmx_me_result;
  * of the box areas of units 0..i-1.  refs (n_refs <= 4) / org: device pictures, the references with margins of margin_x /
  * margin_y luma samples and samples in [0, 2^B); org may hold any value in [-2^B, 2^(B+1)) -- bi-prediction refinement
  * searches against 2 * org - other prediction (removeHighFreq, :4147), which the caller passes as org.  Weighted SAD
- * (xGetSADw) and chroma are not covered; xTZSearch is hmx_batch_tz_search below.
+ * (xGetSADw) is hmx_batch_fullpel_search_wp, xTZSearch is hmx_batch_tz_search, both below; chroma is not covered.
  * n >= 1 and the boxes together hold fewer than 2^32 candidates; anything else is HMX_ERR_ARG.
  * HMX_ERR_ARG, on the host before anything is launched, with the unit named in hmx_last_error: a size outside the set, ref >=
  * n_refs, sub_shift other than 0 or (1 with h > 8), an empty box, a box side above 129 (search range 64), the unit outside the
@@ -675,7 +692,7 @@ int hmx_batch_fullpel_search(hmx_ctx *ctx, const hmx_me_unit *units, int n, cons
  * that moves away from the pattern's centre stays on the box's side it moves towards: nothing else is tested, so a walk that
  * adopts a zero vector outside the box evaluates points outside the box, all of them inside the bounding rectangle of
  * box U {(0, 0)}.  The other predicted vectors, the zero-vector restart and the raster refinement are compiled off in the
- * reference and absent here; weighted SAD and chroma are not covered.
+ * reference and absent here; weighted SAD is hmx_batch_tz_search_wp below; chroma is not covered.
  * units: the HOST array hmx_batch_fullpel_search takes (pred_x / pred_y: the unclipped setPredictor values); tz: HOST array
  * parallel to it; range is uiSearchRange = m_iSearchRange (m_aaiAdaptSR: per reference picture, hence per unit).
  * d_result[i] (device) = {iBestX, iBestY, sad = uiBestSad - vector cost (ruiSAD, :4473), cost = uiBestSad}: d_int of
@@ -710,8 +727,8 @@ int hmx_batch_tz_search(hmx_ctx *ctx, const hmx_me_unit *units, const hmx_tz_uni
  * d_result[i] (device) = {the winning quarter-sample vector, dist = cost - hmx_mvCost(lambda, mvx, mvy, pred, 0), cost = the
  * winning quarter-stage cost}.  d_stage_cost (device, may be NULL): [i * 18 + k] = half-stage cost k, [i * 18 + 9 + k] =
  * quarter-stage cost k.  The tail of xMotionEstimation (:4197-4205: getBits, the fWeight floor) stays with the caller.
- * refs / org as for hmx_batch_fullpel_search (org may be 2 * org - other prediction).  Not covered: weighted distortion
- * (xGetSADw, bApplyWeight) and the non-square Hadamard shapes of NS_HAD with UseNSQT.
+ * refs / org as for hmx_batch_fullpel_search (org may be 2 * org - other prediction).  Weighted distortion (bApplyWeight) is
+ * hmx_batch_subpel_search_wp below.  Not covered: the non-square Hadamard shapes of NS_HAD with UseNSQT, and chroma.
  * The 18 candidates read the (w + 8) x (h + 8) window from 4 samples left of and above the displaced block.  The integer
  * vectors are device data the host cannot see, so the host checks the box: a unit whose integer vector lies OUTSIDE its own
  * box is not refined and reads no reference sample: its result is {4 * ix, 4 * iy truncated to int16_t, dist = cost =
@@ -724,6 +741,34 @@ typedef struct { int16_t mvx, mvy; uint32_t dist; uint32_t cost; } hmx_subpel_re
 int hmx_batch_subpel_search(hmx_ctx *ctx, const hmx_me_unit *units, int n, const hmx_me_result *d_int, const hmx_pic *refs,
                             int n_refs, const hmx_pic *org, int pic_w, int pic_h, int margin_x, int margin_y, uint32_t lambda,
                             int use_had, hmx_subpel_result *d_result, uint32_t *d_stage_cost);
+/* Weighted distortion in the motion search.  In a slice whose PPS has getUseWP() (P) or getWPBiPred() (B),
+ * TEncSearch::setWpScalingDistParam (TEncSearch.cpp:6183-6215) sets DistParam::bApplyWeight and wpCur before the integer stage
+ * (:4174), and every distortion of xMotionEstimation is then the weighted one: xGetSAD* return xGetSADw (TComRdCost.cpp:492 ...),
+ * xGetHADs returns xGetHADsw (:2188) -- TComRdCostWeightPrediction.cpp:69-104, :196-561, as hmx_getSADw / hmx_getHADsw state them.
+ * The _wp entries are the four entries above with one more argument:
+ *   wp: HOST array parallel to refs[], n_refs entries; wp[k] is the wpScalingParam row of the (list, reference) refs[k] stands for,
+ *   of which only component 0 is read.  Unit i is weighted with wp[units[i].ref].  A picture searched under two different
+ *   rows (twice in a list, or in both lists of a B slice) is passed twice in refs[].  Only one index is >= 0 in
+ *   setWpScalingDistParam, also for bBi calls, so getWpScaling's uni-directional branch (TComWeightPrediction.cpp:302-312) applies.
+ * wp == NULL is the unweighted call: the entries without _wp are exactly that.  With a table EVERY unit is weighted, default rows
+ * (weight 1 << log2_denom, offset 0) included, as bApplyWeight is per slice.  What changes against the unweighted entry:
+ *   integer stages (full search, TZ): SAD = hmx_getSADw.  units[i].sub_shift is validated as in the unweighted call and has NO
+ *   effect: xGetSADw ignores the iSubShift that xTZSearchHelp / xPatternSearch set under FEN, reads every row and does not shift;
+ *   sub-pel stages and hmx_batch_subpel_cost_wp: the difference is org - pred, pred formed from the final, clipped interpolated
+ *   sample; sub-block rule, per-sub-block rounding and >> (B - 8) as unweighted.
+ * Vector costs, tie rules, the TZ walk, ruiSAD = best - vector cost and the results' layout do not change.  All sums are uint32_t.
+ * HMX_ERR_ARG, on the host before anything is launched, with the entry and the row named in hmx_last_error: everything the
+ * unweighted entry refuses, and a row with weight[0] outside -128..255, offset[0] outside -128..127, log2_denom[0] above 7 or
+ * reserved != 0.  Not covered: xGetSSEw, chroma, NS_HAD shapes, the encoder's weight estimation (WeightPredAnalysis). */
+int hmx_batch_fullpel_search_wp(hmx_ctx *ctx, const hmx_me_unit *units, int n, const hmx_pic *refs, int n_refs, const hmx_pic *org,
+                                int pic_w, int pic_h, int margin_x, int margin_y, uint32_t lambda, hmx_me_result *d_result,
+                                uint32_t *d_cost_map, const hmx_wp *wp);
+int hmx_batch_tz_search_wp(hmx_ctx *ctx, const hmx_me_unit *units, const hmx_tz_unit *tz, int n, const hmx_pic *refs, int n_refs,
+                           const hmx_pic *org, int pic_w, int pic_h, int margin_x, int margin_y, uint32_t lambda,
+                           hmx_me_result *d_result, hmx_tz_point *d_trace, uint32_t *d_trace_count, int trace_cap, const hmx_wp *wp);
+int hmx_batch_subpel_search_wp(hmx_ctx *ctx, const hmx_me_unit *units, int n, const hmx_me_result *d_int, const hmx_pic *refs,
+                               int n_refs, const hmx_pic *org, int pic_w, int pic_h, int margin_x, int margin_y, uint32_t lambda,
+                               int use_had, hmx_subpel_result *d_result, uint32_t *d_stage_cost, const hmx_wp *wp);
 
 /* Deblocking filter, the application part (TLibCommon/TComLoopFilter.cpp:571-922: xEdgeFilterLuma, xEdgeFilterChroma,
  * the pel filters, the strong/weak decision), in place on a reconstructed picture whose size

@@ -128,6 +128,28 @@ def wp_entry(weight, offset, log2_denom):
     return e
 
 
+def me_wp_table(weight, offset, log2_denom):
+    """The wp table of the _wp motion-search entries from per-reference LUMA values: one WP_DTYPE row per reference, the chroma
+    components at their defaults (the searches read component 0 only).  This is for the wp= argument of the search wrappers, which
+    take a numpy array; wp_entry makes ONE ctypes hmx_wp with all three components, for hmx_motionCompensation_wp's two pointers,
+    and mc_wp_array the per-job tables of hmx_batch_motionCompensation_wp_multi.  A table made for motion compensation (WP_DTYPE,
+    all components) can be passed as wp= as it is."""
+    t = np.zeros(len(weight), WP_DTYPE)
+    t["weight"][:, 0], t["offset"][:, 0], t["log2_denom"][:, 0] = weight, offset, log2_denom
+    t["weight"][:, 1:] = 1
+    return t
+
+
+def _me_wp(wp, n_refs, who):
+    """wp= of a search wrapper: None, or one WP_DTYPE row per reference."""
+    if wp is None:
+        return None
+    wp = np.ascontiguousarray(wp, WP_DTYPE)
+    if len(wp) != n_refs:
+        raise ValueError(f"{who}: wp holds one entry per reference")
+    return wp
+
+
 def mc_wp_array(tables):
     """The hmx_mc_wp array of a hmx_batch_motionCompensation_wp_multi call.  tables: one item per job, None (the job is not
     weighted) or (l0, l1) with l1 possibly None; a table is a numpy array of WP_DTYPE, one entry per reference of the job.
@@ -353,6 +375,17 @@ def lib():
                 continue  # an older build loaded for an A/B run: calling the entry still raises
             getattr(L, name).argtypes = at
             getattr(L, name).restype = rt
+        me_full = [vp, vp, ci, C.POINTER(Pic), ci, C.POINTER(Pic), ci, ci, ci, ci, u32, vp, vp]
+        for name, at in (("hmx_getSADw", [vp, vp, ci, vp, ci, ci, ci, ci, ci, ci, C.POINTER(u32)]),
+                         ("hmx_getHADsw", [vp, vp, ci, vp, ci, ci, ci, ci, ci, ci, C.POINTER(u32)]),
+                         ("hmx_batch_fullpel_search_wp", me_full + [vp]),
+                         ("hmx_batch_subpel_search_wp", [vp, vp, ci, vp, C.POINTER(Pic), ci, C.POINTER(Pic), ci, ci, ci, ci, u32, ci, vp, vp, vp]),
+                         ("hmx_batch_tz_search_wp", [vp, vp, vp, ci, C.POINTER(Pic), ci, C.POINTER(Pic), ci, ci, ci, ci, u32, vp, vp, vp, ci, vp]),
+                         ("hmx_batch_subpel_cost_wp", [vp, vp, ci, C.POINTER(Pic), ci, C.POINTER(Pic), vp, ci, ci, vp, vp])):
+            if "HMX_LIB_PATH" in os.environ and not hasattr(L, name):
+                continue  # an older build loaded for an A/B run: calling the entry still raises
+            getattr(L, name).argtypes = at
+            getattr(L, name).restype = ci
         L.hmx_yuv_frame_bytes.argtypes = [ci, ci, ci]
         L.hmx_yuv_frame_bytes.restype = C.c_size_t
         L.hmx_yuv_unpack.argtypes = [vp, vp, ci, C.POINTER(Pic), ci, ci, ci, ci]
@@ -775,10 +808,45 @@ class Context:
         self._chk(lib().hmx_getSAD(self.h, _hp(cur), cur_stride, _hp(org), org_stride, w, h, sub_shift, C.byref(v)))
         return v.value
 
-    def batch_fullpel_search(self, units, refs, org, pic_w, pic_h, margin_x, margin_y, lambda_, want_map=False):
+    def getSADw(self, cur, cur_stride, org, org_stride, w, h, weight, offset, log2_denom):
+        """hmx_getSADw of one block (blocks as for getSAD); (weight, offset, log2_denom): the luma entry."""
+        cur, org = np.ascontiguousarray(cur, np.int16), np.ascontiguousarray(org, np.int16)
+        v = C.c_uint32()
+        self._chk(lib().hmx_getSADw(self.h, _hp(cur), cur_stride, _hp(org), org_stride, w, h, int(weight), int(offset), int(log2_denom), C.byref(v)))
+        return v.value
+
+    def getHADsw(self, cur, cur_stride, org, org_stride, w, h, weight, offset, log2_denom):
+        """hmx_getHADsw of one block (blocks as for getSAD); (weight, offset, log2_denom): the luma entry."""
+        cur, org = np.ascontiguousarray(cur, np.int16), np.ascontiguousarray(org, np.int16)
+        v = C.c_uint32()
+        self._chk(lib().hmx_getHADsw(self.h, _hp(cur), cur_stride, _hp(org), org_stride, w, h, int(weight), int(offset), int(log2_denom), C.byref(v)))
+        return v.value
+
+    def batch_subpel_cost(self, pus, refs, org, offs, use_had, wp=None):
+        """hmx_batch_subpel_cost (wp: hmx_batch_subpel_cost_wp): pus = array of PU_DTYPE (host, ref0 and the integer mv0), offs =
+        int8 (n_cand, 2).  Returns the costs, uint32 (n, n_cand)."""
+        pus, offs = np.ascontiguousarray(pus, PU_DTYPE), np.ascontiguousarray(offs, np.int8)
+        n, nc = len(pus), len(offs)
+        wp = _me_wp(wp, len(refs), "batch_subpel_cost")
+        ref_arr = (Pic * len(refs))(*[r.as_pic() for r in refs])
+        d_cost = self.alloc(max(1, n * nc) * 4)
+        try:
+            if wp is None:
+                self._chk(lib().hmx_batch_subpel_cost(self.h, pus.ctypes.data, n, ref_arr, len(refs), C.byref(org.as_pic()), offs.ctypes.data, nc,
+                                                      int(use_had), d_cost.ptr))
+            else:
+                self._chk(lib().hmx_batch_subpel_cost_wp(self.h, pus.ctypes.data, n, ref_arr, len(refs), C.byref(org.as_pic()), offs.ctypes.data,
+                                                         nc, int(use_had), d_cost.ptr, wp.ctypes.data))
+            self.sync()
+            return d_cost.download(np.uint32, n * nc).reshape(n, nc)
+        finally:
+            d_cost.free()
+
+    def batch_fullpel_search(self, units, refs, org, pic_w, pic_h, margin_x, margin_y, lambda_, want_map=False, wp=None):
         """hmx_batch_fullpel_search: units = array of ME_UNIT_DTYPE (host), refs = DevPictures with margins, org = DevPicture.
         Returns the results (ME_RESULT_DTYPE) and, with want_map, (results, map, first): the cost of every candidate, unit i's
-        box row by row at map[first[i]:first[i + 1]].  At least one unit: the entry refuses n = 0."""
+        box row by row at map[first[i]:first[i + 1]].  At least one unit: the entry refuses n = 0.  wp: one WP_DTYPE row per
+        reference (me_wp_table makes it) -> hmx_batch_fullpel_search_wp."""
         units = np.ascontiguousarray(units, ME_UNIT_DTYPE)
         n = len(units)
         if n == 0:
@@ -788,9 +856,11 @@ class Context:
         ref_arr = (Pic * len(refs))(*[r.as_pic() for r in refs])
         d_res = self.alloc(n * ME_RESULT_DTYPE.itemsize)
         d_map = self.alloc(int(first[-1]) * 4) if want_map else None
+        wp = _me_wp(wp, len(refs), "batch_fullpel_search")
         try:
-            self._chk(lib().hmx_batch_fullpel_search(self.h, units.ctypes.data, n, ref_arr, len(refs), C.byref(org.as_pic()), pic_w, pic_h,
-                                                     margin_x, margin_y, int(lambda_) & 0xFFFFFFFF, d_res.ptr, d_map.ptr if d_map else None))
+            args = (self.h, units.ctypes.data, n, ref_arr, len(refs), C.byref(org.as_pic()), pic_w, pic_h, margin_x, margin_y,
+                    int(lambda_) & 0xFFFFFFFF, d_res.ptr, d_map.ptr if d_map else None)
+            self._chk(lib().hmx_batch_fullpel_search(*args) if wp is None else lib().hmx_batch_fullpel_search_wp(*args, wp.ctypes.data))
             self.sync()
             res = d_res.download(ME_RESULT_DTYPE, n)
             return (res, d_map.download(np.uint32, int(first[-1])), first) if want_map else res
@@ -799,7 +869,7 @@ class Context:
             if d_map:
                 d_map.free()
 
-    def batch_fullpel_search_device(self, units, refs, org, pic_w, pic_h, margin_x, margin_y, lambda_):
+    def batch_fullpel_search_device(self, units, refs, org, pic_w, pic_h, margin_x, margin_y, lambda_, wp=None):
         """hmx_batch_fullpel_search with the results left on the device: returns the DevBuf of len(units) hmx_me_result (the
         caller frees it), issued on the context's stream and not waited for -- what batch_subpel_search takes as d_int."""
         units = np.ascontiguousarray(units, ME_UNIT_DTYPE)
@@ -809,21 +879,23 @@ class Context:
         ref_arr = (Pic * len(refs))(*[r.as_pic() for r in refs])
         d_res = self.alloc(n * ME_RESULT_DTYPE.itemsize)
         try:
-            self._chk(lib().hmx_batch_fullpel_search(self.h, units.ctypes.data, n, ref_arr, len(refs), C.byref(org.as_pic()), pic_w, pic_h,
-                                                     margin_x, margin_y, int(lambda_) & 0xFFFFFFFF, d_res.ptr, None))
+            wp = _me_wp(wp, len(refs), "batch_fullpel_search_device")
+            args = (self.h, units.ctypes.data, n, ref_arr, len(refs), C.byref(org.as_pic()), pic_w, pic_h, margin_x, margin_y,
+                    int(lambda_) & 0xFFFFFFFF, d_res.ptr, None)
+            self._chk(lib().hmx_batch_fullpel_search(*args) if wp is None else lib().hmx_batch_fullpel_search_wp(*args, wp.ctypes.data))
         except Exception:
             d_res.free()
             raise
         return d_res
 
     def batch_tz_search(self, units, tz, refs, org, pic_w, pic_h, margin_x, margin_y, lambda_, want_trace=False, trace_cap=256,
-                        keep_on_device=False):
+                        keep_on_device=False, wp=None):
         """hmx_batch_tz_search: units = array of ME_UNIT_DTYPE, tz = array of TZ_UNIT_DTYPE (tz_units makes it), both host.
         Returns the results (ME_RESULT_DTYPE) and, with want_trace, (results, counts, trace): counts uint32 (n), trace
         TZ_POINT_DTYPE (n, trace_cap), of which row i holds min(counts[i], trace_cap) entries (the rest is what the buffer held:
         zeros here).  keep_on_device: the results stay on the device -- the DevBuf of hmx_me_result comes back in place of the
         array (the caller frees it), issued on the context's stream and not waited for unless a trace is asked for: what
-        batch_subpel_search takes as d_int."""
+        batch_subpel_search takes as d_int.  wp: one WP_DTYPE row per reference -> hmx_batch_tz_search_wp."""
         units, tz = np.ascontiguousarray(units, ME_UNIT_DTYPE), np.ascontiguousarray(tz, TZ_UNIT_DTYPE)
         n = len(units)
         if n == 0 or len(tz) != n:
@@ -834,9 +906,11 @@ class Context:
         d_trace = self.alloc(n * int(trace_cap) * TZ_POINT_DTYPE.itemsize).zero() if want_trace else None
         keep = False
         try:
-            self._chk(lib().hmx_batch_tz_search(self.h, units.ctypes.data, tz.ctypes.data, n, ref_arr, len(refs), C.byref(org.as_pic()), pic_w, pic_h,
-                                                margin_x, margin_y, int(lambda_) & 0xFFFFFFFF, d_res.ptr, d_trace.ptr if d_trace else None,
-                                                d_cnt.ptr if d_cnt else None, int(trace_cap) if want_trace else 0))
+            wp = _me_wp(wp, len(refs), "batch_tz_search")
+            args = (self.h, units.ctypes.data, tz.ctypes.data, n, ref_arr, len(refs), C.byref(org.as_pic()), pic_w, pic_h, margin_x, margin_y,
+                    int(lambda_) & 0xFFFFFFFF, d_res.ptr, d_trace.ptr if d_trace else None, d_cnt.ptr if d_cnt else None,
+                    int(trace_cap) if want_trace else 0)
+            self._chk(lib().hmx_batch_tz_search(*args) if wp is None else lib().hmx_batch_tz_search_wp(*args, wp.ctypes.data))
             if want_trace or not keep_on_device:
                 self.sync()
             res = d_res if keep_on_device else d_res.download(ME_RESULT_DTYPE, n)
@@ -851,11 +925,13 @@ class Context:
                 if d:
                     d.free()
 
-    def batch_subpel_search(self, units, d_int, refs, org, pic_w, pic_h, margin_x, margin_y, lambda_, use_had, want_stage_costs=False):
+    def batch_subpel_search(self, units, d_int, refs, org, pic_w, pic_h, margin_x, margin_y, lambda_, use_had, want_stage_costs=False,
+                            wp=None):
         """hmx_batch_subpel_search: units = array of ME_UNIT_DTYPE (host); d_int = the integer vectors, either a device buffer
         of hmx_me_result (a DevBuf or a device address, used as it is: batch_fullpel_search_device's return) or an
         ME_RESULT_DTYPE array, which is uploaded.  Returns the results (SUBPEL_RESULT_DTYPE) and, with want_stage_costs,
-        (results, costs): uint32 (n, 18), the nine half-stage then the nine quarter-stage costs in table order."""
+        (results, costs): uint32 (n, 18), the nine half-stage then the nine quarter-stage costs in table order.  wp: one WP_DTYPE
+        row per reference -> hmx_batch_subpel_search_wp."""
         units = np.ascontiguousarray(units, ME_UNIT_DTYPE)
         n = len(units)
         if n == 0:
@@ -869,9 +945,10 @@ class Context:
         d_res = self.alloc(n * SUBPEL_RESULT_DTYPE.itemsize)
         d_costs = self.alloc(n * 18 * 4) if want_stage_costs else None
         try:
-            self._chk(lib().hmx_batch_subpel_search(self.h, units.ctypes.data, n, getattr(d_int, "ptr", d_int), ref_arr, len(refs),
-                                                    C.byref(org.as_pic()), pic_w, pic_h, margin_x, margin_y, int(lambda_) & 0xFFFFFFFF,
-                                                    int(use_had), d_res.ptr, d_costs.ptr if d_costs else None))
+            wp = _me_wp(wp, len(refs), "batch_subpel_search")
+            args = (self.h, units.ctypes.data, n, getattr(d_int, "ptr", d_int), ref_arr, len(refs), C.byref(org.as_pic()), pic_w, pic_h,
+                    margin_x, margin_y, int(lambda_) & 0xFFFFFFFF, int(use_had), d_res.ptr, d_costs.ptr if d_costs else None)
+            self._chk(lib().hmx_batch_subpel_search(*args) if wp is None else lib().hmx_batch_subpel_search_wp(*args, wp.ctypes.data))
             self.sync()
             res = d_res.download(SUBPEL_RESULT_DTYPE, n)
             return (res, d_costs.download(np.uint32, n * 18).reshape(n, 18)) if want_stage_costs else res

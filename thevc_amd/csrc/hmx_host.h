@@ -446,6 +446,22 @@ struct PackArgs;
 int packed_rdoq_max_blocks(int *nb);
 void launch_packed_rdoq(const PackArgs &A, bool sse, unsigned n_wg, hipStream_t st);
 
+// the luma entry of one hmx_wp in the searches' device form (setWpScalingDistParam, TEncSearch.cpp:6183-6215 -> getWpScaling's
+// uni-directional branch): false = outside the ranges hmx_wp documents
+inline bool me_wp_make(int weight, int offset, int log2_denom, int reserved, int B, MeWp *out) {
+  if (weight < -128 || weight > 255 || offset < -128 || offset > 127 || log2_denom < 0 || log2_denom > 7 || reserved != 0) return false;
+  out->w0 = weight, out->shift = log2_denom, out->round = log2_denom ? 1 << (log2_denom - 1) : 0, out->offset = offset * (1 << (B - 8));
+  return true;
+}
+// the table of a _wp search entry (host array parallel to refs[]), refused under the entry's name
+inline int me_wp_table(hmx_ctx *c, const char *entry, const hmx_wp *wp, int n_refs, MeWp *out) {
+  for (int r = 0; r < n_refs; r++)
+    if (!me_wp_make(wp[r].weight[0], wp[r].offset[0], wp[r].log2_denom[0], wp[r].reserved, c->cfg.bit_depth, &out[r]))
+      return fail(c, HMX_ERR_ARG, std::string(entry) + ": wp[" + std::to_string(r) +
+                                      "]: weight outside -128..255, offset outside -128..127, log2_denom above 7 or reserved not 0");
+  return HMX_OK;
+}
+
 // ---- scalar drop-ins: one block through the batch kernels (host pointers in and out) ----
 struct Scratch { // carve the context's device scratch (the budget: head of this file); the first failure sticks in r
   hmx_ctx *c;

@@ -217,8 +217,16 @@ struct SubpelArgs {
   const signed char *offs; // [n_cand][2]
   int n_cand, use_had, B;
   uint32_t *cost; // [n][n_cand]
+  static constexpr bool weighted = false;
 };
-__global__ __launch_bounds__(64) void k_subpel_cost(SubpelArgs A) {
+struct SubpelArgsWp : SubpelArgs { // the weighted launch's arguments (as MeArgsWp in hmx_me.hip): the unweighted kernel keeps its argument block
+  MeWp wp[4];                      // the luma entry of refs[k]
+  static constexpr bool weighted = true;
+};
+// ARGS::weighted (SubpelArgsWp, uniform over a launch): the weighted distortion of TComRdCostWeightPrediction.cpp (xGetSADw :69-104, xGetHADsw :490-561):
+// the difference is org - me_wp_pel(entry of the unit's reference, the final clipped sample); nothing else changes.
+template <class ARGS>
+__global__ __launch_bounds__(64) void k_subpel_cost(ARGS A) {
   const uint32_t sb = blockIdx.x * blockDim.x + threadIdx.x;
   const int cand = blockIdx.y;
   if (sb >= A.first[A.n]) return;
@@ -251,7 +259,8 @@ __global__ __launch_bounds__(64) void k_subpel_cost(SubpelArgs A) {
         for (int q = 0; q < 8; q++) sum += t[r + q] * luma_tap(yf, q);
         v = clip3(0, maxv, wrap16((sum + offset) >> shift));
       }
-      d[r * 8 + c] = org[(size_t)r * A.org.s[0] + c] - v;
+      if constexpr (ARGS::weighted) d[r * 8 + c] = org[(size_t)r * A.org.s[0] + c] - me_wp_pel(A.wp[pu.ref0 < 4 ? pu.ref0 : 0], v);
+      else d[r * 8 + c] = org[(size_t)r * A.org.s[0] + c] - v;
     }
   }
   int sum = 0;
@@ -283,21 +292,28 @@ __global__ void k_shift_u32(uint32_t *v, size_t n, int sh) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) v[i] >>= sh;
 }
-extern "C" int hmx_batch_subpel_cost(hmx_ctx *c, const hmx_pu *pus, int n, const hmx_pic *refs, int n_refs, const hmx_pic *org,
-                                     const int8_t *offs, int n_cand, int use_had, uint32_t *d_cost) {
+static int subpel_cost(hmx_ctx *c, const char *name, const hmx_pu *pus, int n, const hmx_pic *refs, int n_refs, const hmx_pic *org, const int8_t *offs,
+                       int n_cand, int use_had, uint32_t *d_cost, const hmx_wp *wp) {
+  const std::string nm = name;
   if (!c || !pus || n <= 0 || !refs || n_refs <= 0 || n_refs > 4 || !org || !offs || n_cand <= 0 || n_cand > 49 || !d_cost)
-    return fail(c, HMX_ERR_ARG, "hmx_batch_subpel_cost: bad argument");
+    return fail(c, HMX_ERR_ARG, nm + ": bad argument");
+  MeWp wpt[4] = {};
+  if (wp) {
+    const int wr = me_wp_table(c, name, wp, n_refs, wpt);
+    if (wr) return wr;
+  }
   std::vector<uint32_t> first((size_t)n + 1, 0);
   for (int i = 0; i < n; i++) {
     const int w = pus[i].w, h = pus[i].h;
     if (w <= 0 || h <= 0 || w > 64 || h > 64 || ((w | h) & 3) || pus[i].ref0 >= n_refs || ((pus[i].mv0x | pus[i].mv0y) & 3))
-      return fail(c, HMX_ERR_ARG, "hmx_batch_subpel_cost: unit size not a multiple of 4, reference index, or a vector that is not integer");
+      return fail(c, HMX_ERR_ARG, nm + ": unit size not a multiple of 4, reference index, or a vector that is not integer");
     const int nb = (w % 8 == 0 && h % 8 == 0) ? 8 : 4;
     first[i + 1] = first[i] + (uint32_t)((w / nb) * (h / nb));
   }
   for (int k = 0; k < 2 * n_cand; k++)
-    if (offs[k] < -3 || offs[k] > 3) return fail(c, HMX_ERR_ARG, "hmx_batch_subpel_cost: candidate further than 3 quarter samples");
-  SubpelArgs A{};
+    if (offs[k] < -3 || offs[k] > 3) return fail(c, HMX_ERR_ARG, nm + ": candidate further than 3 quarter samples");
+  SubpelArgsWp A{};
+  for (int r = 0; r < 4; r++) A.wp[r] = wpt[r];
   const size_t pu_bytes = sizeof(hmx_pu) * (size_t)n, first_bytes = sizeof(uint32_t) * ((size_t)n + 1);
   // unit list and prefix through the argument arena (they are the caller's host arrays)
   A.pus = static_cast<const hmx_pu *>(arena_push(c, pus, pu_bytes));
@@ -312,11 +328,20 @@ extern "C" int hmx_batch_subpel_cost(hmx_ctx *c, const hmx_pu *pus, int n, const
   A.B = c->cfg.bit_depth;
   A.cost = d_cost;
   HIPCHK(c, hipMemsetAsync(d_cost, 0, sizeof(uint32_t) * (size_t)n * n_cand, c->stream));
-  hipLaunchKernelGGL(k_subpel_cost, dim3((first[n] + 63) / 64, (unsigned)n_cand), dim3(64), 0, c->stream, A);
+  if (wp) hipLaunchKernelGGL(k_subpel_cost<SubpelArgsWp>, dim3((first[n] + 63) / 64, (unsigned)n_cand), dim3(64), 0, c->stream, A);
+  else hipLaunchKernelGGL(k_subpel_cost<SubpelArgs>, dim3((first[n] + 63) / 64, (unsigned)n_cand), dim3(64), 0, c->stream, static_cast<const SubpelArgs &>(A));
   if (c->cfg.bit_depth > 8) // xGetHADs / xGetSAD return uiSum >> g_uiBitIncrement
     hipLaunchKernelGGL(k_shift_u32, dim3((unsigned)(((size_t)n * n_cand + 255) / 256)), dim3(256), 0, c->stream, d_cost, (size_t)n * n_cand, c->cfg.bit_depth - 8);
   HIPCHK(c, hipGetLastError());
   return HMX_OK;
+}
+extern "C" int hmx_batch_subpel_cost(hmx_ctx *c, const hmx_pu *pus, int n, const hmx_pic *refs, int n_refs, const hmx_pic *org,
+                                     const int8_t *offs, int n_cand, int use_had, uint32_t *d_cost) {
+  return subpel_cost(c, "hmx_batch_subpel_cost", pus, n, refs, n_refs, org, offs, n_cand, use_had, d_cost, nullptr);
+}
+extern "C" int hmx_batch_subpel_cost_wp(hmx_ctx *c, const hmx_pu *pus, int n, const hmx_pic *refs, int n_refs, const hmx_pic *org,
+                                        const int8_t *offs, int n_cand, int use_had, uint32_t *d_cost, const hmx_wp *wp) {
+  return subpel_cost(c, "hmx_batch_subpel_cost_wp", pus, n, refs, n_refs, org, offs, n_cand, use_had, d_cost, wp);
 }
 
 __device__ __forceinline__ int add_avg(int a, int b, int B) { // TComYuv.cpp:539-540

@@ -651,6 +651,13 @@ __device__ __forceinline__ void wht_regs(int *v) {
         v[j + half] = a - b;
       }
 }
+// The weighted sample of the motion search's distortions (TComRdCostWeightPrediction.cpp:93, :213 ...): getWpScaling's
+// uni-directional branch (TComWeightPrediction.cpp:302-312) for luma, pred = (Pel)(((w0 * c + round) >> shift) + offset) -- the
+// product in Int, the assignment to Pel wraps to 16 bits, no clip.
+struct MeWp {
+  int w0, round, shift, offset;
+};
+__host__ __device__ __forceinline__ int me_wp_pel(const MeWp &p, int c) { return (int)(short)(((p.w0 * c + p.round) >> p.shift) + p.offset); }
 template <int N>
 __device__ __forceinline__ int satd_block(TuLds<N> &L, int gl, const int *d) {
   constexpr int S = N >= 8 ? 8 : 4, RND = S == 8 ? 2 : 1;

@@ -65,6 +65,80 @@ extern "C" int hmx_getSAD(hmx_ctx *c, const hmx_pel *cur, int cur_stride, const 
 }
 
 // =============================================================================================
+// TComRdCostWeightPrediction::xGetSADw (TComRdCostWeightPrediction.cpp:69-104) and xGetHADsw (:490-561) of ONE block, host pointers
+// =============================================================================================
+// xGetHADsw read against sp_stage: xCalcHADs4x4w (:204-302) and xCalcHADs8x8w (:311-423) form diff = org - pred with pred a Pel
+// (the weighted sample wrapped to 16 bits), then run the butterflies of xCalcHADs4x4 / xCalcHADs8x8 unchanged -- sums and
+// differences only, so the sum of magnitudes is that of the plain Walsh-Hadamard steps of wht_regs -- and round per sub-block
+// with (satd + 1) >> 1 and (sad + 2) >> 2, as the unweighted functions do; xGetHADsw picks 8x8 when both sides are multiples of
+// 8, else 4x4 (:516-545), and returns uiSum >> g_uiBitIncrement (:560).  Only the difference changes.
+__global__ void k_dist_w(const short *org, const short *cur, int w, int h, MeWp p, int hads, unsigned *out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (!hads) { // one thread per row: every row, whatever iSubShift says
+    if (i >= h) return;
+    unsigned sum = 0;
+    for (int k = 0; k < w; k++) sum += (unsigned)abs(org[i * w + k] - me_wp_pel(p, cur[i * w + k]));
+    atomicAdd(out, sum);
+    return;
+  }
+  const int n = (w % 8 == 0 && h % 8 == 0) ? 8 : 4, bw = w / n, nb = bw * (h / n);
+  if (i >= nb) return;
+  const short *o = org + (i / bw) * n * w + (i % bw) * n, *c = cur + (i / bw) * n * w + (i % bw) * n;
+  int d[64];
+  for (int r = 0; r < n; r++)
+    for (int k = 0; k < n; k++) d[r * 8 + k] = o[r * w + k] - me_wp_pel(p, c[r * w + k]);
+  int sum = 0;
+  if (n == 8) {
+    for (int r = 0; r < 8; r++) wht_regs<8>(d + r * 8);
+    for (int k = 0; k < 8; k++) {
+      int col[8];
+      for (int r = 0; r < 8; r++) col[r] = d[r * 8 + k];
+      wht_regs<8>(col);
+      for (int r = 0; r < 8; r++) sum += abs(col[r]);
+    }
+    sum = (sum + 2) >> 2;
+  } else {
+    for (int r = 0; r < 4; r++) wht_regs<4>(d + r * 8);
+    for (int k = 0; k < 4; k++) {
+      int col[4];
+      for (int r = 0; r < 4; r++) col[r] = d[r * 8 + k];
+      wht_regs<4>(col);
+      for (int r = 0; r < 4; r++) sum += abs(col[r]);
+    }
+    sum = (sum + 1) >> 1;
+  }
+  atomicAdd(out, (unsigned)sum);
+}
+static int dist_w(hmx_ctx *c, const char *name, const hmx_pel *cur, int cur_stride, const hmx_pel *org, int org_stride, int w, int h, int weight,
+                  int offset, int log2_denom, int hads, uint32_t *out) {
+  if (!c || !cur || !org || !out) return fail(c, HMX_ERR_ARG, std::string(name) + ": null argument");
+  if (!me_size_ok(w) || !me_size_ok(h)) return fail(c, HMX_ERR_ARG, std::string(name) + ": width and height come from {4, 8, 12, 16, 24, 32, 48, 64}");
+  MeWp p;
+  if (!me_wp_make(weight, offset, log2_denom, 0, c->cfg.bit_depth, &p))
+    return fail(c, HMX_ERR_ARG, std::string(name) + ": weight outside -128..255, offset outside -128..127 or log2_denom outside 0..7");
+  Scratch s{c};
+  short *d_o = s.up(org, w, h, org_stride), *d_c = s.up(cur, w, h, cur_stride);
+  unsigned *d_out = s.take<unsigned>(1);
+  if (s.r) return s.r;
+  HIPCHK(c, hipMemsetAsync(d_out, 0, 4, c->stream));
+  const int items = hads ? (w / 4) * (h / 4) : h;
+  hipLaunchKernelGGL(k_dist_w, dim3((items + 63) / 64), dim3(64), 0, c->stream, d_o, d_c, w, h, p, hads, d_out);
+  HIPCHK(c, hipGetLastError());
+  unsigned v = 0;
+  const int r = hmx_download(c, &v, d_out, 4);
+  *out = v >> (c->cfg.bit_depth - 8);
+  return r;
+}
+extern "C" int hmx_getSADw(hmx_ctx *c, const hmx_pel *cur, int cur_stride, const hmx_pel *org, int org_stride, int w, int h, int weight,
+                           int offset, int log2_denom, uint32_t *sad) {
+  return dist_w(c, "hmx_getSADw", cur, cur_stride, org, org_stride, w, h, weight, offset, log2_denom, 0, sad);
+}
+extern "C" int hmx_getHADsw(hmx_ctx *c, const hmx_pel *cur, int cur_stride, const hmx_pel *org, int org_stride, int w, int h, int weight,
+                            int offset, int log2_denom, uint32_t *satd) {
+  return dist_w(c, "hmx_getHADsw", cur, cur_stride, org, org_stride, w, h, weight, offset, log2_denom, 1, satd);
+}
+
+// =============================================================================================
 // xPatternSearch (TEncSearch.cpp:4227-4283) over unit lists
 // =============================================================================================
 // One workgroup (two waves) = one unit and one tile of 32 x 32 candidates of its box.  The unit's original block and the
@@ -78,6 +152,11 @@ extern "C" int hmx_getSAD(hmx_ctx *c, const hmx_pel *cur, int cur_stride, const 
 // registers: per eight samples one window read, one (broadcast) read of the original and 4 alignbit feed 32 v_sad_u16.
 // Window rows are kMeWinPitch samples = 12 sixteen-byte slots apart: the sixteen lanes of a 16-byte read's lane group
 // (MI355X: four groups of sixteen) then fall on different slots.
+// ARGS::weighted (MeArgsWp, uniform over a launch): weighted distortion, xGetSADw (TComRdCostWeightPrediction.cpp:69-104).  The window is weighted ONCE
+// while it is staged -- pred = me_wp_pel(entry of the unit's reference, sample) -- and the loop over rows is the unweighted one.
+// The bias: pred is any int16, [-2^15, 2^15), and the original lies in [-2^B, 2^(B+1)); with 2^15 added both are in [0, 2^16) as
+// long as 2^(B+1) + 2^15 <= 2^16, i.e. B <= 14, so they stay unsigned 16-bit values with the differences unchanged (2^B, the
+// unweighted bias, would leave a negative pred negative).  xGetSADw ignores iSubShift: every row is read, nothing is shifted left.
 constexpr int kMeTile = 32, kMeWinPitch = 96, kMeWinRows = 64 + kMeTile - 1, kMeThreads = 128;
 struct MeArgs {
   const hmx_me_unit *units;
@@ -90,6 +169,13 @@ struct MeArgs {
   uint32_t lambda;
   unsigned long long *keys; // [n]: (cost << 32) | raster index in the box, all ones before the launch
   uint32_t *cost_map;       // NULL = none
+  static constexpr bool weighted = false;
+};
+// The weighted launch's arguments.  The kernels below are templates over their argument type, so that the unweighted
+// instantiation has the argument block, and with it the code, it had before the weighted one existed.
+struct MeArgsWp : MeArgs {
+  MeWp wp[4]; // the luma entry of refs[k]
+  static constexpr bool weighted = true;
 };
 typedef unsigned u4v __attribute__((ext_vector_type(4)));
 
@@ -118,7 +204,8 @@ __device__ __forceinline__ void me_rows(const u4v *win, const u4v *org, int h, i
   }
 }
 
-__global__ __launch_bounds__(kMeThreads) void k_me_search(MeArgs A) {
+template <class ARGS>
+__global__ __launch_bounds__(kMeThreads) void k_me_search(ARGS A) {
   __shared__ __attribute__((aligned(16))) unsigned short s_win[kMeWinRows * kMeWinPitch];
   __shared__ __attribute__((aligned(16))) unsigned short s_org[64 * 64];
   __shared__ unsigned long long s_key[kMeThreads / 64];
@@ -133,7 +220,7 @@ __global__ __launch_bounds__(kMeThreads) void k_me_search(MeArgs A) {
   const int w = u.w, h = u.h, bw = u.right - u.left + 1, bh = u.bottom - u.top + 1, tiles_x = (bw + kMeTile - 1) / kMeTile;
   const int t = (int)(wg - A.tile_first[lo]), tx0 = (t % tiles_x) * kMeTile, ty0 = (t / tiles_x) * kMeTile;
   const int nx = min(kMeTile, bw - tx0), ny = min(kMeTile, bh - ty0); // candidates of this tile
-  const int tid = threadIdx.x, bias = 1 << A.B;
+  const int tid = threadIdx.x, bias = ARGS::weighted ? 32768 : 1 << A.B;
   typedef __attribute__((address_space(1))) const short gpel;
   { // the window: rows and columns no candidate of the tile reaches are zero and never read from memory
     const PlanesDev &R = A.refs[u.ref < 4 ? u.ref : 0];
@@ -141,7 +228,10 @@ __global__ __launch_bounds__(kMeThreads) void k_me_search(MeArgs A) {
     const int vx = nx + w - 1, vy = ny + h - 1, cols = min(kMeWinPitch, w + 40), rows = h + kMeTile - 1;
     for (int wy = tid >> 5; wy < rows; wy += kMeThreads / 32)
       for (int wx = tid & 31; wx < cols; wx += 32)
-        s_win[wy * kMeWinPitch + wx] = (wx < vx && wy < vy) ? (unsigned short)(src[(ptrdiff_t)wy * R.s[0] + wx] + bias) : (unsigned short)0;
+        if constexpr (ARGS::weighted)
+          s_win[wy * kMeWinPitch + wx] =
+              (wx < vx && wy < vy) ? (unsigned short)(me_wp_pel(A.wp[u.ref < 4 ? u.ref : 0], src[(ptrdiff_t)wy * R.s[0] + wx]) + bias) : (unsigned short)0;
+        else s_win[wy * kMeWinPitch + wx] = (wx < vx && wy < vy) ? (unsigned short)(src[(ptrdiff_t)wy * R.s[0] + wx] + bias) : (unsigned short)0;
   }
   const int op = ((w / 2 + 3) / 4 * 4) * 2; // samples per staged original row
   {
@@ -153,7 +243,7 @@ __global__ __launch_bounds__(kMeThreads) void k_me_search(MeArgs A) {
   const int row = tid >> 2, half = (tid >> 1) & 1, p = tid & 1;
   unsigned acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   const u4v *win = reinterpret_cast<const u4v *>(s_win + row * kMeWinPitch + 16 * half), *org = reinterpret_cast<const u4v *>(s_org);
-  const int step = 1 << u.sub_shift;
+  const int step = 1 << (ARGS::weighted ? 0 : u.sub_shift);
   const unsigned sh = p ? 16u : 0u;
   // a wave holds sixteen candidate rows: one whose rows all lie below the tile's last candidate row (the fifth tile row of a 129-high
   // box has one, a +-1 box three) sums nothing -- uniform over the wave; its lanes keep acc = 0 and are masked out below
@@ -179,7 +269,7 @@ __global__ __launch_bounds__(kMeThreads) void k_me_search(MeArgs A) {
     const int cx = 16 * half + p + 2 * j;
     if (cx < nx && row < ny) {
       const int bx = tx0 + cx, by = ty0 + row;
-      const uint32_t sad = (acc[j] << u.sub_shift) >> (A.B - 8);
+      const uint32_t sad = (acc[j] << (ARGS::weighted ? 0 : u.sub_shift)) >> (A.B - 8);
       const uint32_t cost = sad + me_mv_cost(A.lambda, u.left + bx, u.top + by, u.pred_x, u.pred_y, 2);
       const uint32_t idx = (uint32_t)(by * bw + bx);
       if (map) map[idx] = cost;
@@ -212,21 +302,28 @@ __global__ void k_me_unpack(const hmx_me_unit *units, const unsigned long long *
   out[i] = r;
 }
 
-extern "C" int hmx_batch_fullpel_search(hmx_ctx *c, const hmx_me_unit *units, int n, const hmx_pic *refs, int n_refs, const hmx_pic *org, int pic_w,
-                                        int pic_h, int margin_x, int margin_y, uint32_t lambda, hmx_me_result *d_result, uint32_t *d_cost_map) {
-  if (!c || !units || !refs || !org || !d_result) return fail(c, HMX_ERR_ARG, "hmx_batch_fullpel_search: null argument");
-  if (n <= 0) return fail(c, HMX_ERR_ARG, "hmx_batch_fullpel_search: n must be at least 1");
-  if (n_refs <= 0 || n_refs > 4) return fail(c, HMX_ERR_ARG, "hmx_batch_fullpel_search: n_refs must be 1 .. 4");
+// the four searches' entries: `name` is the entry the caller used (refusals are made under it), wp == NULL the unweighted call
+static int me_fullpel(hmx_ctx *c, const char *name, const hmx_me_unit *units, int n, const hmx_pic *refs, int n_refs, const hmx_pic *org, int pic_w,
+                      int pic_h, int margin_x, int margin_y, uint32_t lambda, hmx_me_result *d_result, uint32_t *d_cost_map, const hmx_wp *wp) {
+  const std::string nm = name;
+  if (!c || !units || !refs || !org || !d_result) return fail(c, HMX_ERR_ARG, nm + ": null argument");
+  if (n <= 0) return fail(c, HMX_ERR_ARG, nm + ": n must be at least 1");
+  if (n_refs <= 0 || n_refs > 4) return fail(c, HMX_ERR_ARG, nm + ": n_refs must be 1 .. 4");
   if (pic_w <= 0 || pic_h <= 0 || margin_x < 0 || margin_y < 0)
-    return fail(c, HMX_ERR_ARG, "hmx_batch_fullpel_search: picture size must be positive and margins not negative");
-  if (!org->plane[0]) return fail(c, HMX_ERR_ARG, "hmx_batch_fullpel_search: the original has no luma plane");
+    return fail(c, HMX_ERR_ARG, nm + ": picture size must be positive and margins not negative");
+  if (!org->plane[0]) return fail(c, HMX_ERR_ARG, nm + ": the original has no luma plane");
   for (int r = 0; r < n_refs; r++)
-    if (!refs[r].plane[0]) return fail(c, HMX_ERR_ARG, "hmx_batch_fullpel_search: a reference has no luma plane");
+    if (!refs[r].plane[0]) return fail(c, HMX_ERR_ARG, nm + ": a reference has no luma plane");
+  MeWp wpt[4] = {};
+  if (wp) {
+    const int wr = me_wp_table(c, name, wp, n_refs, wpt);
+    if (wr) return wr;
+  }
   std::vector<uint32_t> tile_first((size_t)n + 1, 0), map_first((size_t)n + 1, 0);
   uint64_t area = 0; // the kernel's offsets into the cost map are 32-bit
   for (int i = 0; i < n; i++) {
     const hmx_me_unit &u = units[i];
-    const std::string at = "hmx_batch_fullpel_search: unit " + std::to_string(i) + ": ";
+    const std::string at = nm + ": unit " + std::to_string(i) + ": ";
     if (!me_size_ok(u.w) || !me_size_ok(u.h)) return fail(c, HMX_ERR_ARG, at + "width and height come from {4, 8, 12, 16, 24, 32, 48, 64}");
     if (u.ref >= n_refs) return fail(c, HMX_ERR_ARG, at + "reference index outside refs[]");
     if (u.sub_shift > 1 || (u.sub_shift && u.h <= 8)) return fail(c, HMX_ERR_ARG, at + "sub_shift is 0, or 1 with more than 8 rows");
@@ -240,12 +337,13 @@ extern "C" int hmx_batch_fullpel_search(hmx_ctx *c, const hmx_me_unit *units, in
     map_first[i + 1] = map_first[i] + (uint32_t)(bw * bh);
     area += (uint64_t)(bw * bh);
   }
-  if (area > 0xffffffffull) return fail(c, HMX_ERR_ARG, "hmx_batch_fullpel_search: the boxes hold more than 2^32 - 1 candidates: split the call");
+  if (area > 0xffffffffull) return fail(c, HMX_ERR_ARG, nm + ": the boxes hold more than 2^32 - 1 candidates: split the call");
   void *keys = c->d_me_keys;
   const int gr = grow_dev(c, &keys, &c->me_keys_cap, sizeof(unsigned long long) * (size_t)n);
   c->d_me_keys = static_cast<unsigned long long *>(keys);
   if (gr) return gr;
-  MeArgs A{};
+  MeArgsWp A{};
+  for (int r = 0; r < 4; r++) A.wp[r] = wpt[r];
   const size_t prefix_bytes = sizeof(uint32_t) * ((size_t)n + 1);
   // unit list and prefixes through the argument arena (the caller's host array, and tables made from it)
   A.units = static_cast<const hmx_me_unit *>(arena_push(c, units, sizeof(hmx_me_unit) * (size_t)n));
@@ -260,10 +358,20 @@ extern "C" int hmx_batch_fullpel_search(hmx_ctx *c, const hmx_me_unit *units, in
   A.keys = c->d_me_keys;
   A.cost_map = d_cost_map;
   HIPCHK(c, hipMemsetAsync(c->d_me_keys, 0xff, sizeof(unsigned long long) * (size_t)n, c->stream));
-  hipLaunchKernelGGL(k_me_search, dim3(tile_first[n]), dim3(kMeThreads), 0, c->stream, A);
+  if (wp) hipLaunchKernelGGL(k_me_search<MeArgsWp>, dim3(tile_first[n]), dim3(kMeThreads), 0, c->stream, A);
+  else hipLaunchKernelGGL(k_me_search<MeArgs>, dim3(tile_first[n]), dim3(kMeThreads), 0, c->stream, static_cast<const MeArgs &>(A));
   hipLaunchKernelGGL(k_me_unpack, dim3((n + 255) / 256), dim3(256), 0, c->stream, A.units, (const unsigned long long *)c->d_me_keys, n, lambda, d_result);
   HIPCHK(c, hipGetLastError());
   return HMX_OK;
+}
+extern "C" int hmx_batch_fullpel_search(hmx_ctx *c, const hmx_me_unit *units, int n, const hmx_pic *refs, int n_refs, const hmx_pic *org, int pic_w,
+                                        int pic_h, int margin_x, int margin_y, uint32_t lambda, hmx_me_result *d_result, uint32_t *d_cost_map) {
+  return me_fullpel(c, "hmx_batch_fullpel_search", units, n, refs, n_refs, org, pic_w, pic_h, margin_x, margin_y, lambda, d_result, d_cost_map, nullptr);
+}
+extern "C" int hmx_batch_fullpel_search_wp(hmx_ctx *c, const hmx_me_unit *units, int n, const hmx_pic *refs, int n_refs, const hmx_pic *org,
+                                           int pic_w, int pic_h, int margin_x, int margin_y, uint32_t lambda, hmx_me_result *d_result,
+                                           uint32_t *d_cost_map, const hmx_wp *wp) {
+  return me_fullpel(c, "hmx_batch_fullpel_search_wp", units, n, refs, n_refs, org, pic_w, pic_h, margin_x, margin_y, lambda, d_result, d_cost_map, wp);
 }
 
 // =============================================================================================
@@ -284,6 +392,9 @@ extern "C" int hmx_batch_fullpel_search(hmx_ctx *c, const hmx_me_unit *units, in
 // general step with the taps {0, 0, 0, 64, 0, 0, 0, 0} for bit depths below 14: 64 * (t + 8192 + 2^(head-1)) >> (6 + head).
 // LDS (dynamic, sized for the largest unit of the call): window, original, planes 2, 1, 3 = 46352 bytes at 64 x 64: three
 // workgroups = twelve waves per CU (160 KB); 1440 bytes at 8 x 8, where the registers (eight workgroups per CU) bind first.
+// WP (uniform over a launch): weighted distortion, xGetSADw / xGetHADsw (TComRdCostWeightPrediction.cpp:69-104, :490-561): the
+// difference is org - me_wp_pel(entry, final clipped sample), what the reference forms from its m_filteredBlock planes; the
+// interpolation, the sub-block rule and the per-sub-block rounding do not change.
 constexpr int kSpThreads = 256;
 struct SpArgs {
   const hmx_me_unit *units;
@@ -294,6 +405,11 @@ struct SpArgs {
   uint32_t lambda;
   hmx_subpel_result *result;
   uint32_t *stage_cost; // [n][18], NULL = none
+  static constexpr bool weighted = false;
+};
+struct SpArgsWp : SpArgs { // as MeArgsWp
+  MeWp wp[4];
+  static constexpr bool weighted = true;
 };
 static size_t sp_lds_bytes(int w, int h) { return sizeof(short) * (size_t)((w + 8) * (h + 8) + w * h + (w + 1) * (h + 8) + 2 * w * (h + 8)); }
 struct SpDiv { // n / d for n < 4096 * d and n * d < 2^20, by one multiplication
@@ -343,8 +459,9 @@ struct SpLds {
   int w, h;
 };
 // the nine candidates of one stage: s_cost[k] += the sub-block sums of candidate k
-template <int S>
-__device__ __forceinline__ void sp_stage(const SpLds &L, int stage, int hx, int hy, int c1, int c3, int B, int use_had, unsigned *s_cost, int tid) {
+template <int S, bool WP>
+__device__ __forceinline__ void sp_stage(const SpLds &L, int stage, int hx, int hy, int c1, int c3, int B, int use_had, const MeWp *wp, unsigned *s_cost,
+                                         int tid) {
   const int w = L.w, bw = w / S, nsb = bw * (L.h / S), total = 9 * nsb, lane = tid & (S - 1);
   const SpDiv dn(nsb), db(bw);
   const int head = 14 - B, shift = 6 + head, offset = (1 << (shift - 1)) + (8192 << 6), maxv = (1 << B) - 1;
@@ -384,7 +501,8 @@ __device__ __forceinline__ void sp_stage(const SpLds &L, int stage, int hx, int 
       int sum = 0;
 #pragma unroll
       for (int q = 0; q < 8; q++) sum += t[r + q] * tap[q];
-      d[r] = o[r * w] - clip3(0, maxv, wrap16((sum + offset) >> shift));
+      if constexpr (WP) d[r] = o[r * w] - me_wp_pel(*wp, clip3(0, maxv, wrap16((sum + offset) >> shift)));
+      else d[r] = o[r * w] - clip3(0, maxv, wrap16((sum + offset) >> shift));
     }
     int s = 0;
     if (use_had) { // the sum of magnitudes of the 2-D transform: down the column here, then across the S lanes
@@ -425,7 +543,9 @@ __device__ __forceinline__ unsigned long long sp_decide(const unsigned *s_cost, 
   return key;
 }
 
-__global__ __launch_bounds__(kSpThreads) void k_subpel_search(SpArgs A) {
+template <class ARGS>
+__global__ __launch_bounds__(kSpThreads) void k_subpel_search(ARGS A) {
+  constexpr bool WP = ARGS::weighted;
   extern __shared__ __attribute__((aligned(16))) short s_sp[];
   __shared__ unsigned s_cost[18];
   __shared__ int s_half;
@@ -467,8 +587,10 @@ __global__ __launch_bounds__(kSpThreads) void k_subpel_search(SpArgs A) {
   __syncthreads();
   const bool s8 = (w % 8 == 0) && (h % 8 == 0);
   SpLds L{win, org, p1, p2, p3, w, h};
-  if (s8) sp_stage<8>(L, 0, 0, 0, 0, 0, B, A.use_had, s_cost, tid);
-  else sp_stage<4>(L, 0, 0, 0, 0, 0, B, A.use_had, s_cost, tid);
+  const MeWp *wpe = nullptr; // the unit's entry, WP only
+  if constexpr (WP) wpe = &A.wp[u.ref < 4 ? u.ref : 0];
+  if (s8) sp_stage<8, WP>(L, 0, 0, 0, 0, 0, B, A.use_had, wpe, s_cost, tid);
+  else sp_stage<4, WP>(L, 0, 0, 0, 0, 0, B, A.use_had, wpe, s_cost, tid);
   __syncthreads();
   if (tid < 16) {
     const int kb = (int)(uint32_t)sp_decide(s_cost, 0, 2 * ix, 2 * iy, u, A, (uint32_t *)costs, tid);
@@ -483,8 +605,8 @@ __global__ __launch_bounds__(kSpThreads) void k_subpel_search(SpArgs A) {
   sp_hor_plane<1>(win, wp, p1, w, w, 4 + c1, r0, r1, B, tid);
   sp_hor_plane<3>(win, wp, p3, w, w, 4 + c3, r0, r1, B, tid);
   __syncthreads();
-  if (s8) sp_stage<8>(L, 1, hx, hy, c1, c3, B, A.use_had, s_cost + 9, tid);
-  else sp_stage<4>(L, 1, hx, hy, c1, c3, B, A.use_had, s_cost + 9, tid);
+  if (s8) sp_stage<8, WP>(L, 1, hx, hy, c1, c3, B, A.use_had, wpe, s_cost + 9, tid);
+  else sp_stage<4, WP>(L, 1, hx, hy, c1, c3, B, A.use_had, wpe, s_cost + 9, tid);
   __syncthreads();
   if (tid < 16) {
     const int bx = 4 * ix + 2 * hx, by = 4 * iy + 2 * hy;
@@ -501,22 +623,28 @@ __global__ __launch_bounds__(kSpThreads) void k_subpel_search(SpArgs A) {
   }
 }
 
-extern "C" int hmx_batch_subpel_search(hmx_ctx *c, const hmx_me_unit *units, int n, const hmx_me_result *d_int, const hmx_pic *refs, int n_refs,
-                                       const hmx_pic *org, int pic_w, int pic_h, int margin_x, int margin_y, uint32_t lambda, int use_had,
-                                       hmx_subpel_result *d_result, uint32_t *d_stage_cost) {
-  if (!c || !units || !d_int || !refs || !org || !d_result) return fail(c, HMX_ERR_ARG, "hmx_batch_subpel_search: null argument");
-  if (n <= 0) return fail(c, HMX_ERR_ARG, "hmx_batch_subpel_search: n must be at least 1");
-  if (n_refs <= 0 || n_refs > 4) return fail(c, HMX_ERR_ARG, "hmx_batch_subpel_search: n_refs must be 1 .. 4");
-  if (use_had != 0 && use_had != 1) return fail(c, HMX_ERR_ARG, "hmx_batch_subpel_search: use_had is 0 or 1");
+static int me_subpel(hmx_ctx *c, const char *name, const hmx_me_unit *units, int n, const hmx_me_result *d_int, const hmx_pic *refs, int n_refs,
+                     const hmx_pic *org, int pic_w, int pic_h, int margin_x, int margin_y, uint32_t lambda, int use_had,
+                     hmx_subpel_result *d_result, uint32_t *d_stage_cost, const hmx_wp *wp) {
+  const std::string nm = name;
+  if (!c || !units || !d_int || !refs || !org || !d_result) return fail(c, HMX_ERR_ARG, nm + ": null argument");
+  if (n <= 0) return fail(c, HMX_ERR_ARG, nm + ": n must be at least 1");
+  if (n_refs <= 0 || n_refs > 4) return fail(c, HMX_ERR_ARG, nm + ": n_refs must be 1 .. 4");
+  if (use_had != 0 && use_had != 1) return fail(c, HMX_ERR_ARG, nm + ": use_had is 0 or 1");
   if (pic_w <= 0 || pic_h <= 0 || margin_x < 0 || margin_y < 0)
-    return fail(c, HMX_ERR_ARG, "hmx_batch_subpel_search: picture size must be positive and margins not negative");
-  if (!org->plane[0]) return fail(c, HMX_ERR_ARG, "hmx_batch_subpel_search: the original has no luma plane");
+    return fail(c, HMX_ERR_ARG, nm + ": picture size must be positive and margins not negative");
+  if (!org->plane[0]) return fail(c, HMX_ERR_ARG, nm + ": the original has no luma plane");
   for (int r = 0; r < n_refs; r++)
-    if (!refs[r].plane[0]) return fail(c, HMX_ERR_ARG, "hmx_batch_subpel_search: a reference has no luma plane");
+    if (!refs[r].plane[0]) return fail(c, HMX_ERR_ARG, nm + ": a reference has no luma plane");
+  MeWp wpt[4] = {};
+  if (wp) {
+    const int wr = me_wp_table(c, name, wp, n_refs, wpt);
+    if (wr) return wr;
+  }
   size_t lds = 0;
   for (int i = 0; i < n; i++) {
     const hmx_me_unit &u = units[i];
-    const std::string at = "hmx_batch_subpel_search: unit " + std::to_string(i) + ": ";
+    const std::string at = nm + ": unit " + std::to_string(i) + ": ";
     if (!me_size_ok(u.w) || !me_size_ok(u.h)) return fail(c, HMX_ERR_ARG, at + "width and height come from {4, 8, 12, 16, 24, 32, 48, 64}");
     if (u.ref >= n_refs) return fail(c, HMX_ERR_ARG, at + "reference index outside refs[]");
     if (u.right < u.left || u.bottom < u.top) return fail(c, HMX_ERR_ARG, at + "empty search box");
@@ -527,7 +655,8 @@ extern "C" int hmx_batch_subpel_search(hmx_ctx *c, const hmx_me_unit *units, int
       return fail(c, HMX_ERR_ARG, at + "the interpolation window of a vector of the box reaches outside the reference's margins");
     lds = std::max(lds, sp_lds_bytes(u.w, u.h));
   }
-  SpArgs A{};
+  SpArgsWp A{};
+  for (int r = 0; r < 4; r++) A.wp[r] = wpt[r];
   A.units = static_cast<const hmx_me_unit *>(arena_push(c, units, sizeof(hmx_me_unit) * (size_t)n)); // the caller's host array
   if (!A.units) return fail(c, HMX_ERR_NOMEM, "argument arena (unit list too long: split the call)");
   A.ints = d_int;
@@ -538,9 +667,22 @@ extern "C" int hmx_batch_subpel_search(hmx_ctx *c, const hmx_me_unit *units, int
   A.lambda = lambda;
   A.result = d_result;
   A.stage_cost = d_stage_cost;
-  hipLaunchKernelGGL(k_subpel_search, dim3((unsigned)n), dim3(kSpThreads), lds, c->stream, A);
+  if (wp) hipLaunchKernelGGL(k_subpel_search<SpArgsWp>, dim3((unsigned)n), dim3(kSpThreads), lds, c->stream, A);
+  else hipLaunchKernelGGL(k_subpel_search<SpArgs>, dim3((unsigned)n), dim3(kSpThreads), lds, c->stream, static_cast<const SpArgs &>(A));
   HIPCHK(c, hipGetLastError());
   return HMX_OK;
+}
+extern "C" int hmx_batch_subpel_search(hmx_ctx *c, const hmx_me_unit *units, int n, const hmx_me_result *d_int, const hmx_pic *refs, int n_refs,
+                                       const hmx_pic *org, int pic_w, int pic_h, int margin_x, int margin_y, uint32_t lambda, int use_had,
+                                       hmx_subpel_result *d_result, uint32_t *d_stage_cost) {
+  return me_subpel(c, "hmx_batch_subpel_search", units, n, d_int, refs, n_refs, org, pic_w, pic_h, margin_x, margin_y, lambda, use_had, d_result,
+                   d_stage_cost, nullptr);
+}
+extern "C" int hmx_batch_subpel_search_wp(hmx_ctx *c, const hmx_me_unit *units, int n, const hmx_me_result *d_int, const hmx_pic *refs, int n_refs,
+                                          const hmx_pic *org, int pic_w, int pic_h, int margin_x, int margin_y, uint32_t lambda, int use_had,
+                                          hmx_subpel_result *d_result, uint32_t *d_stage_cost, const hmx_wp *wp) {
+  return me_subpel(c, "hmx_batch_subpel_search_wp", units, n, d_int, refs, n_refs, org, pic_w, pic_h, margin_x, margin_y, lambda, use_had, d_result,
+                   d_stage_cost, wp);
 }
 
 // =============================================================================================
@@ -561,6 +703,10 @@ extern "C" int hmx_batch_subpel_search(hmx_ctx *c, const hmx_me_unit *units, int
 // order, and every border test of the diamonds and of xTZ2PointSearch is one rule: a coordinate that moves away from the centre
 // is tested against the side it moves towards.  So a pattern here is a table of (offset, point number, distance) and that rule.
 // Every loop is bounded in sight: iDist doubles up to range <= 64, the raster grid has at most 26 x 26 points, passes <= cap.
+// WP (uniform over a launch): weighted distortion, xGetSADw.  Each sample pair is weighted after the load (me_wp_pel) and both the
+// prediction and the original carry a bias of 2^15, not 2^B: pred is any int16 and the original lies in [-2^B, 2^(B+1)), so for
+// B <= 14 both are unsigned 16-bit values with the differences unchanged (see k_me_search).  xGetSADw ignores the iSubShift that
+// xTZSearchHelp sets under FEN (TEncSearch.cpp:324-330): every row is read and the sum is not shifted left.
 struct TzArgs {
   const hmx_me_unit *units;
   const hmx_tz_unit *tz;
@@ -572,6 +718,11 @@ struct TzArgs {
   hmx_tz_point *trace; // NULL = none
   uint32_t *trace_count;
   int trace_cap;
+  static constexpr bool weighted = false;
+};
+struct TzArgsWp : TzArgs { // as MeArgsWp
+  MeWp wp[4];
+  static constexpr bool weighted = true;
 };
 struct TzState {
   uint32_t best;                // uiBestSad
@@ -586,6 +737,9 @@ struct TzUnit {
   uint32_t lambda;
   __attribute__((address_space(1))) uint32_t *trace; // this unit's slice of hmx_tz_point as word pairs {x | y << 16, cost}, or NULL
   uint32_t trace_cap;
+};
+struct TzUnitWp : TzUnit {
+  MeWp wp; // the unit's entry
 };
 // 16 entries of 2 bits: component + 1
 __host__ __device__ constexpr unsigned tz_pack(int a0, int a1, int a2, int a3, int a4, int a5, int a6, int a7, int a8 = 0, int a9 = 0, int a10 = 0,
@@ -607,13 +761,14 @@ constexpr unsigned kTz2Y = tz_pack(0, -1, -1, -1, -1, 0, 1, -1, -1, 1, 0, 1, 1, 
 
 // One batch of xTZSearchHelp calls: the lanes [c * L, (c + 1) * L) hold candidate c = (cx, cy) of the batch, evaluated when
 // `valid`; candidates are in evaluation order.  L is a power of two, the same in all lanes.
-__device__ __forceinline__ void tz_eval(const TzUnit &U, TzState &S, int L, int cx, int cy, bool valid, int nr, int dist) {
+template <bool WP, class UNIT>
+__device__ __forceinline__ void tz_eval(const UNIT &U, TzState &S, int L, int cx, int cy, bool valid, int nr, int dist) {
   const int lane = threadIdx.x, sub = lane & (L - 1);
   unsigned acc = 0;
   if (valid) {
     const int segs = U.w >> 2, items = (U.h >> U.sub_shift) * segs;
     const unsigned inv = 65536u / (unsigned)segs + 1u; // it / segs for it < 1024
-    const unsigned bias2 = (1u << U.B) * 0x00010001u;
+    const unsigned bias2 = WP ? 0x80008000u : (1u << U.B) * 0x00010001u;
     const __attribute__((address_space(1))) short *base = U.ref + (ptrdiff_t)cy * U.stride + cx;
     for (int it = sub; it < items; it += L) { // at most 64 rows x 16 segments
       const int row = (int)(((unsigned)it * inv) >> 16), seg = it - row * segs, r = row << U.sub_shift;
@@ -621,7 +776,12 @@ __device__ __forceinline__ void tz_eval(const TzUnit &U, TzState &S, int L, int 
       const unsigned sh = (a & 2) ? 16u : 0u;
       const __attribute__((address_space(1))) unsigned *q = (const __attribute__((address_space(1))) unsigned *)(a & ~(uintptr_t)3);
       const unsigned d0 = q[0], d1 = q[1], d2 = sh ? q[2] : 0u; // the third word holds a sample of the segment only at odd parity
-      const unsigned e0 = __builtin_amdgcn_alignbit(d1, d0, sh) + bias2, e1 = __builtin_amdgcn_alignbit(d2, d1, sh) + bias2;
+      unsigned e0 = __builtin_amdgcn_alignbit(d1, d0, sh), e1 = __builtin_amdgcn_alignbit(d2, d1, sh);
+      if constexpr (WP) { // the two samples of a word weighted on their own; each result is an int16, so + 2^15 per half cannot carry across
+        e0 = ((unsigned)me_wp_pel(U.wp, (short)e0) & 0xffffu) | ((unsigned)me_wp_pel(U.wp, (short)(e0 >> 16)) << 16);
+        e1 = ((unsigned)me_wp_pel(U.wp, (short)e1) & 0xffffu) | ((unsigned)me_wp_pel(U.wp, (short)(e1 >> 16)) << 16);
+        e0 ^= bias2, e1 ^= bias2; // int16 + 2^15 as an unsigned 16-bit value = the sign bit flipped
+      } else e0 += bias2, e1 += bias2;
       const uint2 o = *reinterpret_cast<const uint2 *>(U.org + r * U.w + 4 * seg);
       acc = __builtin_amdgcn_sad_u16(e0, o.x, acc);
       acc = __builtin_amdgcn_sad_u16(e1, o.y, acc);
@@ -659,7 +819,8 @@ __device__ __forceinline__ bool tz_inside(const TzUnit &U, int x, int y, int dx,
   return (dx >= 0 || x >= U.left) && (dx <= 0 || x <= U.right) && (dy >= 0 || y >= U.top) && (dy <= 0 || y <= U.bottom);
 }
 // xTZ8PointDiamondSearch (:536-707) around (sx, sy)
-__device__ __forceinline__ void tz_diamond(const TzUnit &U, TzState &S, int sx, int sy, int d) {
+template <bool WP, class UNIT>
+__device__ __forceinline__ void tz_diamond(const UNIT &U, TzState &S, int sx, int sy, int d) {
   const int lane = threadIdx.x;
   S.round += 1;
   int L, dx, dy, nr, dist = d;
@@ -681,25 +842,28 @@ __device__ __forceinline__ void tz_diamond(const TzUnit &U, TzState &S, int sx, 
     }
   }
   const int cx = sx + dx, cy = sy + dy;
-  tz_eval(U, S, L, cx, cy, tz_inside(U, cx, cy, dx, dy), nr, dist);
+  tz_eval<WP>(U, S, L, cx, cy, tz_inside(U, cx, cy, dx, dy), nr, dist);
 }
 // xTZ2PointSearch (:351-479) around the best point; ucPointNr = 0 evaluates nothing (the reference asserts: it is unreachable,
 // because uiBestDistance == 1 is only ever set together with a point number of 1 .. 8)
-__device__ __forceinline__ void tz_two_point(const TzUnit &U, TzState &S) {
+template <bool WP, class UNIT>
+__device__ __forceinline__ void tz_two_point(const UNIT &U, TzState &S) {
   const int p = (int)threadIdx.x >> 5, e = S.nr > 0 ? 2 * (S.nr - 1) + p : 0;
   const int dx = tz_sign(kTz2X, e), dy = tz_sign(kTz2Y, e), cx = S.bx + dx, cy = S.by + dy;
-  tz_eval(U, S, 32, cx, cy, S.nr > 0 && tz_inside(U, cx, cy, dx, dy), 0, 2);
+  tz_eval<WP>(U, S, 32, cx, cy, S.nr > 0 && tz_inside(U, cx, cy, dx, dy), 0, 2);
 }
 
 constexpr int kTzThreads = 64, kTzRaster = 5, kTzPassCap = 1024;
-__global__ __launch_bounds__(kTzThreads) void k_tz_search(TzArgs A) {
+template <class ARGS>
+__global__ __launch_bounds__(kTzThreads) void k_tz_search(ARGS A) {
+  constexpr bool WP = ARGS::weighted;
   extern __shared__ __attribute__((aligned(16))) unsigned short s_tz_org[];
   const int i = blockIdx.x, lane = threadIdx.x;
   const hmx_me_unit u = A.units[i];
   const hmx_tz_unit z = A.tz[i];
   typedef __attribute__((address_space(1))) const short gpel;
   {
-    const int bias = 1 << A.B;
+    const int bias = WP ? 32768 : 1 << A.B;
     const gpel *src = (const gpel *)A.org.p[0] + (size_t)u.y * A.org.s[0] + u.x;
     const int lw = u.w == 4 ? 2 : u.w == 8 ? 3 : u.w == 16 ? 4 : u.w == 32 ? 5 : u.w == 64 ? 6 : -1;
     for (int k = lane; k < u.w * u.h; k += kTzThreads) { // at most 64 rounds
@@ -708,12 +872,13 @@ __global__ __launch_bounds__(kTzThreads) void k_tz_search(TzArgs A) {
     }
   }
   __syncthreads();
-  TzUnit U;
+  typename std::conditional<WP, TzUnitWp, TzUnit>::type U;
   const PlanesDev &R = A.refs[u.ref < 4 ? u.ref : 0];
   U.stride = R.s[0];
   U.ref = (gpel *)R.p[0] + (ptrdiff_t)u.y * R.s[0] + u.x;
   U.org = s_tz_org;
-  U.w = u.w, U.h = u.h, U.sub_shift = u.sub_shift, U.B = A.B;
+  U.w = u.w, U.h = u.h, U.sub_shift = WP ? 0 : u.sub_shift, U.B = A.B;
+  if constexpr (WP) U.wp = A.wp[u.ref < 4 ? u.ref : 0];
   U.left = u.left, U.top = u.top, U.right = u.right, U.bottom = u.bottom, U.pred_x = u.pred_x, U.pred_y = u.pred_y;
   U.lambda = A.lambda;
   U.trace = A.trace ? (__attribute__((address_space(1))) uint32_t *)A.trace + 2 * (size_t)i * (size_t)A.trace_cap : nullptr;
@@ -721,22 +886,22 @@ __global__ __launch_bounds__(kTzThreads) void k_tz_search(TzArgs A) {
   TzState S{0xffffffffu, 0, 0, 0, 0, 0, 0u};
   const int range = z.range;
   // the start point, then the zero vector (:4321, :4338): neither is tested against the box
-  tz_eval(U, S, 32, lane < 32 ? z.start_x : 0, lane < 32 ? z.start_y : 0, true, 0, 0);
+  tz_eval<WP>(U, S, 32, lane < 32 ? z.start_x : 0, lane < 32 ? z.start_y : 0, true, 0, 0);
   int sx = S.bx, sy = S.by;
   for (int d = 1; d <= range; d *= 2) { // first search (:4347-4362)
-    tz_diamond(U, S, sx, sy, d);
+    tz_diamond<WP>(U, S, sx, sy, d);
     if (S.round >= 3) break;
   }
   if (S.dist == 1) { // :4383-4387, no test of ucPointNr
     S.dist = 0;
-    tz_two_point(U, S);
+    tz_two_point<WP>(U, S);
   }
   if (S.dist > kTzRaster) { // :4390-4400
     S.dist = kTzRaster;
     const int nx = (U.right - U.left) / kTzRaster + 1, ny = (U.bottom - U.top) / kTzRaster + 1, total = nx * ny; // at most 26 x 26
     for (int c0 = 0; c0 < total; c0 += 16) {
       const int c = c0 + (lane >> 2), ry = c / nx, rx = c - ry * nx;
-      tz_eval(U, S, 4, U.left + kTzRaster * rx, U.top + kTzRaster * ry, c < total, 0, kTzRaster);
+      tz_eval<WP>(U, S, 4, U.left + kTzRaster * rx, U.top + kTzRaster * ry, c < total, 0, kTzRaster);
     }
   }
   int passes = 0;
@@ -749,10 +914,10 @@ __global__ __launch_bounds__(kTzThreads) void k_tz_search(TzArgs A) {
     passes++;
     sx = S.bx, sy = S.by;
     S.dist = 0, S.nr = 0;
-    for (int d = 1; d <= range; d *= 2) tz_diamond(U, S, sx, sy, d);
+    for (int d = 1; d <= range; d *= 2) tz_diamond<WP>(U, S, sx, sy, d);
     if (S.dist == 1) {
       S.dist = 0;
-      if (S.nr != 0) tz_two_point(U, S);
+      if (S.nr != 0) tz_two_point<WP>(U, S);
     }
   }
   if (lane == 0) {
@@ -765,24 +930,30 @@ __global__ __launch_bounds__(kTzThreads) void k_tz_search(TzArgs A) {
   }
 }
 
-extern "C" int hmx_batch_tz_search(hmx_ctx *c, const hmx_me_unit *units, const hmx_tz_unit *tz, int n, const hmx_pic *refs, int n_refs,
-                                   const hmx_pic *org, int pic_w, int pic_h, int margin_x, int margin_y, uint32_t lambda, hmx_me_result *d_result,
-                                   hmx_tz_point *d_trace, uint32_t *d_trace_count, int trace_cap) {
-  if (!c || !units || !tz || !refs || !org || !d_result) return fail(c, HMX_ERR_ARG, "hmx_batch_tz_search: null argument");
-  if ((d_trace == nullptr) != (d_trace_count == nullptr)) return fail(c, HMX_ERR_ARG, "hmx_batch_tz_search: d_trace and d_trace_count go together");
-  if (d_trace && trace_cap < 1) return fail(c, HMX_ERR_ARG, "hmx_batch_tz_search: trace_cap must be at least 1");
-  if (n <= 0) return fail(c, HMX_ERR_ARG, "hmx_batch_tz_search: n must be at least 1");
-  if (n_refs <= 0 || n_refs > 4) return fail(c, HMX_ERR_ARG, "hmx_batch_tz_search: n_refs must be 1 .. 4");
+static int me_tz(hmx_ctx *c, const char *name, const hmx_me_unit *units, const hmx_tz_unit *tz, int n, const hmx_pic *refs, int n_refs,
+                 const hmx_pic *org, int pic_w, int pic_h, int margin_x, int margin_y, uint32_t lambda, hmx_me_result *d_result,
+                 hmx_tz_point *d_trace, uint32_t *d_trace_count, int trace_cap, const hmx_wp *wp) {
+  const std::string nm = name;
+  if (!c || !units || !tz || !refs || !org || !d_result) return fail(c, HMX_ERR_ARG, nm + ": null argument");
+  if ((d_trace == nullptr) != (d_trace_count == nullptr)) return fail(c, HMX_ERR_ARG, nm + ": d_trace and d_trace_count go together");
+  if (d_trace && trace_cap < 1) return fail(c, HMX_ERR_ARG, nm + ": trace_cap must be at least 1");
+  if (n <= 0) return fail(c, HMX_ERR_ARG, nm + ": n must be at least 1");
+  if (n_refs <= 0 || n_refs > 4) return fail(c, HMX_ERR_ARG, nm + ": n_refs must be 1 .. 4");
   if (pic_w <= 0 || pic_h <= 0 || margin_x < 0 || margin_y < 0)
-    return fail(c, HMX_ERR_ARG, "hmx_batch_tz_search: picture size must be positive and margins not negative");
-  if (!org->plane[0]) return fail(c, HMX_ERR_ARG, "hmx_batch_tz_search: the original has no luma plane");
+    return fail(c, HMX_ERR_ARG, nm + ": picture size must be positive and margins not negative");
+  if (!org->plane[0]) return fail(c, HMX_ERR_ARG, nm + ": the original has no luma plane");
   for (int r = 0; r < n_refs; r++)
-    if (!refs[r].plane[0]) return fail(c, HMX_ERR_ARG, "hmx_batch_tz_search: a reference has no luma plane");
+    if (!refs[r].plane[0]) return fail(c, HMX_ERR_ARG, nm + ": a reference has no luma plane");
+  MeWp wpt[4] = {};
+  if (wp) {
+    const int wr = me_wp_table(c, name, wp, n_refs, wpt);
+    if (wr) return wr;
+  }
   size_t lds = 0;
   for (int i = 0; i < n; i++) {
     const hmx_me_unit &u = units[i];
     const hmx_tz_unit &z = tz[i];
-    const std::string at = "hmx_batch_tz_search: unit " + std::to_string(i) + ": ";
+    const std::string at = nm + ": unit " + std::to_string(i) + ": ";
     if (!me_size_ok(u.w) || !me_size_ok(u.h)) return fail(c, HMX_ERR_ARG, at + "width and height come from {4, 8, 12, 16, 24, 32, 48, 64}");
     if (u.ref >= n_refs) return fail(c, HMX_ERR_ARG, at + "reference index outside refs[]");
     if (u.sub_shift > 1 || (u.sub_shift && u.h <= 8)) return fail(c, HMX_ERR_ARG, at + "sub_shift is 0, or 1 with more than 8 rows");
@@ -799,7 +970,8 @@ extern "C" int hmx_batch_tz_search(hmx_ctx *c, const hmx_me_unit *units, const h
       return fail(c, HMX_ERR_ARG, at + "a block of the box or the zero vector's rectangle reaches outside the reference's margins");
     lds = std::max(lds, sizeof(short) * (size_t)u.w * (size_t)u.h);
   }
-  TzArgs A{};
+  TzArgsWp A{};
+  for (int r = 0; r < 4; r++) A.wp[r] = wpt[r];
   A.units = static_cast<const hmx_me_unit *>(arena_push(c, units, sizeof(hmx_me_unit) * (size_t)n)); // the caller's host arrays
   A.tz = static_cast<const hmx_tz_unit *>(arena_push(c, tz, sizeof(hmx_tz_unit) * (size_t)n));
   if (!A.units || !A.tz) return fail(c, HMX_ERR_NOMEM, "argument arena (unit list too long: split the call)");
@@ -812,7 +984,20 @@ extern "C" int hmx_batch_tz_search(hmx_ctx *c, const hmx_me_unit *units, const h
   A.trace = d_trace;
   A.trace_count = d_trace_count;
   A.trace_cap = d_trace ? trace_cap : 0;
-  hipLaunchKernelGGL(k_tz_search, dim3((unsigned)n), dim3(kTzThreads), lds, c->stream, A);
+  if (wp) hipLaunchKernelGGL(k_tz_search<TzArgsWp>, dim3((unsigned)n), dim3(kTzThreads), lds, c->stream, A);
+  else hipLaunchKernelGGL(k_tz_search<TzArgs>, dim3((unsigned)n), dim3(kTzThreads), lds, c->stream, static_cast<const TzArgs &>(A));
   HIPCHK(c, hipGetLastError());
   return HMX_OK;
+}
+extern "C" int hmx_batch_tz_search(hmx_ctx *c, const hmx_me_unit *units, const hmx_tz_unit *tz, int n, const hmx_pic *refs, int n_refs,
+                                   const hmx_pic *org, int pic_w, int pic_h, int margin_x, int margin_y, uint32_t lambda, hmx_me_result *d_result,
+                                   hmx_tz_point *d_trace, uint32_t *d_trace_count, int trace_cap) {
+  return me_tz(c, "hmx_batch_tz_search", units, tz, n, refs, n_refs, org, pic_w, pic_h, margin_x, margin_y, lambda, d_result, d_trace, d_trace_count,
+               trace_cap, nullptr);
+}
+extern "C" int hmx_batch_tz_search_wp(hmx_ctx *c, const hmx_me_unit *units, const hmx_tz_unit *tz, int n, const hmx_pic *refs, int n_refs,
+                                      const hmx_pic *org, int pic_w, int pic_h, int margin_x, int margin_y, uint32_t lambda, hmx_me_result *d_result,
+                                      hmx_tz_point *d_trace, uint32_t *d_trace_count, int trace_cap, const hmx_wp *wp) {
+  return me_tz(c, "hmx_batch_tz_search_wp", units, tz, n, refs, n_refs, org, pic_w, pic_h, margin_x, margin_y, lambda, d_result, d_trace,
+               d_trace_count, trace_cap, wp);
 }

@@ -206,8 +206,15 @@ static int frac_main(int argc, char **argv) {
 // luma plane with its margins as int16, then per call 13 words {CU x, CU y, unit x, y, width, height, bBi, predictor hor, ver,
 // rcMv hor, ver as it comes in, search range, ruiBits as it comes in} and the unit's original block as int16 (for bBi it is
 // 2 * org - other).  Prints "mvHor mvVer bits cost" per call.
+// hm_mirror_test calls_wp <file>: the same for calls recorded in weighted slices (tests/test_me_wp_enc_tap.py).  Per call 17
+// words: the 13 above, then {iWeight, iOffset, uiLog2WeightDenom of the luma row of the reference searched, 1 if the slice was
+// searched weighted}; the mirror runs setWpScalingDistParam with that row (or none) before xMotionEstimation.  Prints "mvHor
+// mvVer bits cost sadw hadsw" per call: the last two are TComRdCostWeightPrediction::xGetSADw / xGetHADsw with the row between
+// the original block and the reference block at the integer part of the vector found.
 static int calls_main(int argc, char **argv) {
   if (argc < 3) return 2;
+  const bool weighted = std::string(argv[1]) == "calls_wp";
+  const int words = weighted ? 17 : 13;
   FILE *f = fopen(argv[2], "rb");
   if (!f) return 2;
   int hd[11];
@@ -218,6 +225,7 @@ static int calls_main(int argc, char **argv) {
   hmx_hm::Context ctx(B);
   hmx_hm::TComRdCost rd(ctx);
   hmx_hm::TEncSearch search(ctx, rd, {W, H, MX, MY, hd[5]}, hd[6] != 0, hd[7] != 0, hd[8]);
+  hmx_hm::TComRdCostWeightPrediction rdw(ctx);
   const double root = ((double)(unsigned)hd[9] + 0.5) / 65536.0; // setLambda floors 65536 * sqrt(lambda): aim at the middle of the step
   rd.setLambda(root * root);
   rd.getMotionCost(true, 0);
@@ -230,8 +238,8 @@ static int calls_main(int argc, char **argv) {
   po.plane[0] = d_org, po.stride[0] = W;
   pr.plane[0] = d_ref + MY * S + MX, pr.stride[0] = S;
   for (int k = 0; k < hd[10]; k++) {
-    int c[13];
-    if (fread(c, sizeof(int), 13, f) != 13) return 2;
+    int c[17];
+    if (fread(c, sizeof(int), words, f) != (size_t)words) return 2;
     const int x = c[2], y = c[3], w = c[4], h = c[5];
     if (x < 0 || y < 0 || w <= 0 || h <= 0 || x + w > W || y + h > H) return 2;
     std::vector<short> blk((size_t)w * h);
@@ -243,8 +251,17 @@ static int calls_main(int argc, char **argv) {
     const int pred[2] = {c[7], c[8]};
     int mv[2] = {c[9], c[10]};
     hmx_hm::UInt bits = (hmx_hm::UInt)c[12], cost = 0;
+    hmx_hm::wpScalingParam row[3] = {};
+    if (weighted) {
+      for (int yuv = 0; yuv < 3; yuv++) row[yuv].bPresentFlag = true, row[yuv].iWeight = 1;
+      row[0].iWeight = c[13], row[0].iOffset = c[14], row[0].uiLog2WeightDenom = (hmx_hm::UInt)c[15];
+      search.setWpScalingDistParam(c[16] ? row : nullptr);
+    }
     search.xMotionEstimation(&po, &pr, c[0], c[1], x, y, w, h, pred, c[11], c[6] != 0, mv, bits, cost);
-    printf("%d %d %u %u\n", mv[0], mv[1], bits, cost);
+    if (weighted) {
+      short *cur = ref.data() + (size_t)(MY + y + (mv[1] >> 2)) * S + MX + x + (mv[0] >> 2);
+      printf("%d %d %u %u %u %u\n", mv[0], mv[1], bits, cost, rdw.xGetSADw(blk.data(), w, cur, S, w, h, row), rdw.xGetHADsw(blk.data(), w, cur, S, w, h, row));
+    } else printf("%d %d %u %u\n", mv[0], mv[1], bits, cost);
   }
   fclose(f);
   hmx_free(ctx.get(), d_org);
@@ -253,7 +270,7 @@ static int calls_main(int argc, char **argv) {
 }
 
 int main(int argc, char **argv) {
-  if (argc >= 2 && std::string(argv[1]) == "calls") {
+  if (argc >= 2 && (std::string(argv[1]) == "calls" || std::string(argv[1]) == "calls_wp")) {
     try {
       return calls_main(argc, argv);
     } catch (const std::exception &e) {

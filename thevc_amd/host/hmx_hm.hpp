@@ -328,9 +328,34 @@ private:
   Int m_iPredHor = 0, m_iPredVer = 0, m_iCostScale = 0;
 };
 
-// TEncSearch, xMotionEstimation (TEncSearch.cpp:4120-4514) for ONE unit: the integer stage over hmx_batch_fullpel_search
-// (xPatternSearch) or hmx_batch_tz_search (xPatternSearchFast -> xTZSearch, m_iFastSearch = 1), the fractional stage over
-// hmx_batch_subpel_search.
+// TComRdCostWeightPrediction (TComRdCostWeightPrediction.cpp:69-104, :490-561): the distortions xGetSAD* / xGetHADs return when
+// DistParam::bApplyWeight is set.  wpCur: the luma row of the reference searched (what DistParam::wpCur[0] is after
+// setWpScalingDistParam); iWeight, iOffset and uiLog2WeightDenom are read, the derived fields are the entry's own.
+class TComRdCostWeightPrediction {
+public:
+  explicit TComRdCostWeightPrediction(Context &c) : m_c(c) {}
+  // xGetSADw: every row, whatever DistParam::iSubShift says
+  UInt xGetSADw(Pel *piOrg, Int iStrideOrg, Pel *piCur, Int iStrideCur, Int iCols, Int iRows, const wpScalingParam *wpCur) {
+    uint32_t v = 0;
+    m_c.check(hmx_getSADw(m_c.get(), piCur, iStrideCur, piOrg, iStrideOrg, iCols, iRows, wpCur->iWeight, wpCur->iOffset, (int)wpCur->uiLog2WeightDenom, &v),
+              "xGetSADw");
+    return v;
+  }
+  // xGetHADsw with iStep = 1
+  UInt xGetHADsw(Pel *piOrg, Int iStrideOrg, Pel *piCur, Int iStrideCur, Int iCols, Int iRows, const wpScalingParam *wpCur) {
+    uint32_t v = 0;
+    m_c.check(hmx_getHADsw(m_c.get(), piCur, iStrideCur, piOrg, iStrideOrg, iCols, iRows, wpCur->iWeight, wpCur->iOffset, (int)wpCur->uiLog2WeightDenom, &v),
+              "xGetHADsw");
+    return v;
+  }
+
+private:
+  Context &m_c;
+};
+
+// TEncSearch, xMotionEstimation (TEncSearch.cpp:4120-4514) for ONE unit: the integer stage over hmx_batch_fullpel_search_wp
+// (xPatternSearch) or hmx_batch_tz_search_wp (xPatternSearchFast -> xTZSearch, m_iFastSearch = 1), the fractional stage over
+// hmx_batch_subpel_search_wp -- each with the table setWpScalingDistParam left, or none: the unweighted call.
 // What the reference reads through pcCU, the pattern key and the slice is explicit: the unit's position and size, the
 // pictures (DEVICE pictures: the original, and the reference with its margins) and their geometry.
 class TEncSearch {
@@ -349,6 +374,15 @@ public:
   }
   TEncSearch(const TEncSearch &) = delete;
   TEncSearch &operator=(const TEncSearch &) = delete;
+  // setWpScalingDistParam (:6183-6215), which xMotionEstimation runs before the integer stage (:4174) and whose result stays in
+  // m_cDistParam for every distortion of the call.  Here the CALLER runs it before xMotionEstimation, with what the reference reads
+  // through pcCU: wp = the wpScalingParam[3] row of (eRefPicListCur, iRefIdx) when the slice is weighted -- a P slice whose PPS has
+  // getUseWP(), a B slice whose PPS has getWPBiPred() -- and NULL otherwise, as for iRefIdx < 0: bApplyWeight = false.  Only one
+  // index is >= 0 in the reference's call, so the row is used as getWpScaling's uni-directional branch leaves it, also for bBi.
+  void setWpScalingDistParam(const wpScalingParam *wp) {
+    m_bApplyWeight = wp != nullptr;
+    if (wp) m_wpCur = TComWeightPrediction::entry(wp);
+  }
   // xSetSearchRange (:4209-4225): cMvPred in quarter samples, the corners in integer samples
   void xSetSearchRange(Int cuX, Int cuY, Int mvPredHor, Int mvPredVer, Int iSrchRng, Int rcMvSrchRngLT[2], Int rcMvSrchRngRB[2]) const {
     hmx_setSearchRange(mvPredHor, mvPredVer, iSrchRng, cuX, cuY, m_g.picWidth, m_g.picHeight, m_g.ctuSize, &rcMvSrchRngLT[0], &rcMvSrchRngLT[1],
@@ -365,8 +399,8 @@ public:
     u.sub_shift = (m_fastEnc && iRoiHeight > 8) ? 1 : 0; // :4245-4251
     u.pred_x = (int16_t)m_rd.predictorHor(), u.pred_y = (int16_t)m_rd.predictorVer();
     u.left = (int16_t)pcMvSrchRngLT[0], u.top = (int16_t)pcMvSrchRngLT[1], u.right = (int16_t)pcMvSrchRngRB[0], u.bottom = (int16_t)pcMvSrchRngRB[1];
-    m_c.check(hmx_batch_fullpel_search(m_c.get(), &u, 1, pcRef, 1, pcOrg, m_g.picWidth, m_g.picHeight, m_g.marginX, m_g.marginY,
-                                       m_rd.motionCostMultiplier(), m_dResult, nullptr),
+    m_c.check(hmx_batch_fullpel_search_wp(m_c.get(), &u, 1, pcRef, 1, pcOrg, m_g.picWidth, m_g.picHeight, m_g.marginX, m_g.marginY,
+                                          m_rd.motionCostMultiplier(), m_dResult, nullptr, wpCur()),
               "xPatternSearch");
     hmx_me_result r;
     m_c.check(hmx_download(m_c.get(), &r, m_dResult, sizeof(r)), "xPatternSearch");
@@ -395,8 +429,8 @@ public:
     hmx_clipMv(&sx, &sy, cuX, cuY, m_g.picWidth, m_g.picHeight, m_g.ctuSize);
     hmx_tz_unit z{};
     z.start_x = (int16_t)(sx >> 2), z.start_y = (int16_t)(sy >> 2), z.range = (uint16_t)iSearchRange;
-    m_c.check(hmx_batch_tz_search(m_c.get(), &u, &z, 1, pcRef, 1, pcOrg, m_g.picWidth, m_g.picHeight, m_g.marginX, m_g.marginY,
-                                  m_rd.motionCostMultiplier(), m_dResult, nullptr, nullptr, 0),
+    m_c.check(hmx_batch_tz_search_wp(m_c.get(), &u, &z, 1, pcRef, 1, pcOrg, m_g.picWidth, m_g.picHeight, m_g.marginX, m_g.marginY,
+                                     m_rd.motionCostMultiplier(), m_dResult, nullptr, nullptr, 0, wpCur()),
               "xTZSearch");
     hmx_me_result r;
     m_c.check(hmx_download(m_c.get(), &r, m_dResult, sizeof(r)), "xTZSearch");
@@ -419,8 +453,8 @@ public:
     in.mvx = (int16_t)pcMvInt[0], in.mvy = (int16_t)pcMvInt[1];
     m_c.check(hmx_upload(m_c.get(), m_dResult, &in, sizeof(in)), "xPatternSearchFracDIF");
     uint32_t *dCosts = reinterpret_cast<uint32_t *>(m_dFrac + 1);
-    m_c.check(hmx_batch_subpel_search(m_c.get(), &u, 1, m_dResult, pcRef, 1, pcOrg, m_g.picWidth, m_g.picHeight, m_g.marginX, m_g.marginY,
-                                      m_rd.motionCostMultiplier(), m_useHADME ? 1 : 0, m_dFrac, dCosts),
+    m_c.check(hmx_batch_subpel_search_wp(m_c.get(), &u, 1, m_dResult, pcRef, 1, pcOrg, m_g.picWidth, m_g.picHeight, m_g.marginX, m_g.marginY,
+                                         m_rd.motionCostMultiplier(), m_useHADME ? 1 : 0, m_dFrac, dCosts, wpCur()),
               "xPatternSearchFracDIF");
     struct {
       hmx_subpel_result r;
@@ -472,9 +506,12 @@ public:
   }
 
 private:
+  const hmx_wp *wpCur() const { return m_bApplyWeight ? &m_wpCur : nullptr; } // the one-entry table of refs[0]
   Context &m_c;
   TComRdCost &m_rd;
   Geometry m_g;
+  Bool m_bApplyWeight = false; // DistParam::bApplyWeight / wpCur
+  hmx_wp m_wpCur{};
   Bool m_fastEnc, m_useHADME;
   Int m_iFastSearch; // 1: xTZSearch for uni-predictive units
   hmx_me_result *m_dResult = nullptr;

@@ -3,7 +3,10 @@
 (device time between two events on the context's stream, after one warm-up call) with their min..max, the absolute differences
 per second, and that figure as a fraction of the VALU issue bound of v_sad_u16: two differences per lane and instruction, one
 wave64 instruction per --sad-cycles cycles per SIMD, 4 SIMDs x 256 CUs at --ghz.  Both figures are arguments without a default:
-they come from a run of tools/bin/issue_probe on the same device (ISSUE_FROM=60 prints the clock and the v_sad_u16 lines)."""
+they come from a run of tools/bin/issue_probe on the same device (ISSUE_FROM=60 prints the clock and the v_sad_u16 lines).
+--wp: every case is also timed through hmx_batch_fullpel_search_wp with a non-default table (weight 45, offset -20, denominator
+2^5), the two calls alternated on the same units; the weighted line follows the unweighted one.  The weighted call reads every
+row whatever sub_shift says, and its line counts the differences it forms."""
 import argparse
 import ctypes as C
 import os
@@ -20,6 +23,7 @@ ap.add_argument("--repeats", type=int, default=5)
 ap.add_argument("--sad-cycles", type=float, required=True, help="measured SIMD cycles per v_sad_u16 wave instruction (tools/issue_probe)")
 ap.add_argument("--ghz", type=float, required=True, help="the device clock tools/issue_probe prints")
 ap.add_argument("--once", action="store_true", help="one call per case and no timing lines (for profiler runs)")
+ap.add_argument("--wp", action="store_true", help="also time the weighted entry on the same units, alternated with the unweighted call")
 args = ap.parse_args()
 B, w, h, M, RANGE = 10, 3840, 2160, 80, 64
 ctx = capi.Context(bit_depth=B)
@@ -29,6 +33,7 @@ refs = [capi.DevPicture(ctx, w, h, M, M).upload(workload.make_planes(3, w, h, B,
 ctx._chk(L.hmx_pic_extend_border(ctx.h, C.byref(refs[0].as_pic()), w, h, M, M))
 org = capi.DevPicture(ctx, w, h).upload(workload.make_planes(4, w, h, B, "texture"))
 bound = 2 * 64 / args.sad_cycles * 4 * 256 * args.ghz * 1e9  # absolute differences per second
+WP = capi.me_wp_table([45], [-20], [5])
 
 
 def units_of(size, sub_shift):
@@ -52,20 +57,26 @@ for size in (16, 64, 0):  # 0: mixed sizes, sub_shift drawn per unit
         d_res = ctx.alloc(len(u) * capi.ME_RESULT_DTYPE.itemsize)
         o = org.as_pic()
         call = lambda: ctx._chk(L.hmx_batch_fullpel_search(ctx.h, u.ctypes.data, len(u), ref_arr, 1, C.byref(o), w, h, M, M, 2000000, d_res.ptr, None))
-        call()
+        call_wp = lambda: ctx._chk(L.hmx_batch_fullpel_search_wp(ctx.h, u.ctypes.data, len(u), ref_arr, 1, C.byref(o), w, h, M, M, 2000000, d_res.ptr,
+                                                                 None, WP.ctypes.data))
+        calls = [(call, name, diffs)] + ([(call_wp, name.rstrip() + " WEIGHTED", int((per_unit * u["w"] * u["h"].astype(np.int64)).sum()))] if args.wp else [])
+        for fn, _, _ in calls:
+            fn()
         ctx.sync()
         if not args.once:
             e0, e1 = ctx.event(), ctx.event()
-            ts = []
+            ts = [[] for _ in calls]
             for _ in range(args.repeats):
-                ctx.record(e0)
-                call()
-                ctx.record(e1)
-                ctx.sync()
-                ts.append(ctx.elapsed_ms(e0, e1))
-            t = float(np.median(ts))
-            rate = diffs / (t * 1e-3)
-            print(f"{name}: {len(u):6d} units, {cands / 1e6:7.1f} M candidates  {t:8.2f} ms/picture (min {min(ts):.2f}, max {max(ts):.2f}; "
-                  f"{len(ts)} repeats)  {rate / 1e12:6.2f} T absolute differences/s = {100 * rate / bound:5.1f} % of the v_sad_u16 issue bound "
-                  f"({bound / 1e12:.1f} T/s at {args.sad_cycles} cycles and {args.ghz} GHz)", flush=True)
+                for k, (fn, _, _) in enumerate(calls):  # alternated
+                    ctx.record(e0)
+                    fn()
+                    ctx.record(e1)
+                    ctx.sync()
+                    ts[k].append(ctx.elapsed_ms(e0, e1))
+            for (_, label, nd), tk in zip(calls, ts):
+                t = float(np.median(tk))
+                rate = nd / (t * 1e-3)
+                print(f"{label}: {len(u):6d} units, {cands / 1e6:7.1f} M candidates  {t:8.2f} ms/picture (min {min(tk):.2f}, max {max(tk):.2f}; "
+                      f"{len(tk)} repeats)  {rate / 1e12:6.2f} T absolute differences/s = {100 * rate / bound:5.1f} % of the v_sad_u16 issue bound "
+                      f"({bound / 1e12:.1f} T/s at {args.sad_cycles} cycles and {args.ghz} GHz)", flush=True)
         d_res.free()

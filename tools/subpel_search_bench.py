@@ -7,7 +7,9 @@ units and winners, alternated, --repeats timings each after one warm-up:
       the host (numpy, the vector bits through capi.mv_cost).
 Per path: the device time between two events on the context's stream (the kernels alone) and the wall time of the whole path,
 as median with min..max.  Then (a) per size class (units up to 8 x 8, 16 to 32, 48 to 64), so that a weak small-unit shape
-shows.  The two paths' results are compared before anything is timed."""
+shows.  The two paths' results are compared before anything is timed.
+--wp: hmx_batch_subpel_search_wp with a non-default table (weights 45 and 90, offsets -20 and 33, denominators 2^5 and 2^6) is
+timed on the same units and winners, alternated with (a), and gets a line of its own."""
 import argparse
 import ctypes as C
 import os
@@ -24,6 +26,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--repeats", type=int, default=7)
 ap.add_argument("--range", type=int, default=16, help="search range of the integer stage that supplies the winners")
 ap.add_argument("--sad", action="store_true", help="SAD instead of the Hadamard sum")
+ap.add_argument("--wp", action="store_true", help="also time the weighted entry on the same units, alternated with (a)")
 args = ap.parse_args()
 B, w, h, M, LAM = 10, 1920, 1080, 80, 2000000
 use_had = 0 if args.sad else 1
@@ -39,6 +42,7 @@ o = org.as_pic()
 REFINE_H = ((0, 0), (0, -1), (0, 1), (-1, 0), (1, 0), (-1, -1), (1, -1), (-1, 1), (1, 1))
 REFINE_Q = ((0, 0), (0, -1), (0, 1), (-1, -1), (1, -1), (-1, 0), (1, 0), (-1, 1), (1, 1))
 OFFS = [(dx, dy) for dy in range(-3, 4) for dx in range(-3, 4)]
+WP = capi.me_wp_table([45, 90], [-20, 33], [5, 6])
 offs = np.array(OFFS, np.int8)
 IDX_H = [OFFS.index((2 * dx, 2 * dy)) for dx, dy in REFINE_H]
 
@@ -72,6 +76,13 @@ def run(u, label):
         ctx.sync()
         return d_res.download(capi.SUBPEL_RESULT_DTYPE, n)
 
+    def path_w():
+        ctx._chk(L.hmx_batch_subpel_search_wp(ctx.h, u.ctypes.data, n, d_int.ptr, ref_arr, 2, C.byref(o), w, h, M, M, LAM, use_had, d_res.ptr, None,
+                                              WP.ctypes.data))
+        ctx.record(e1)
+        ctx.sync()
+        return d_res.download(capi.SUBPEL_RESULT_DTYPE, n)
+
     def path_b():
         ctx._chk(L.hmx_batch_subpel_cost(ctx.h, pus.ctypes.data, n, ref_arr, 2, C.byref(o), offs.ctypes.data, 49, use_had, d_cost.ptr))
         ctx.record(e1)
@@ -92,14 +103,22 @@ def run(u, label):
     ra, rb = path_a(), (path_b() if label == "all units" else None)  # warm-up, and the two paths agree
     if rb is not None and not np.array_equal(ra, rb):
         raise SystemExit(f"{label}: the two paths disagree on {int((ra != rb).sum())} units")
-    ta, tb = [], []
+    ta, tb, tw = [], [], []
+    if args.wp:
+        path_w()  # warm-up
     for _ in range(args.repeats):
         ta.append(timed(path_a, e0, e1)[1:])
+        if args.wp:
+            tw.append(timed(path_w, e0, e1)[1:])
         if rb is not None:
             tb.append(timed(path_b, e0, e1)[1:])
     ga = [t[0] for t in ta]
     print(f"{label:14s} {n:6d} units  (a) hmx_batch_subpel_search   GPU {stats(ga)}  whole {stats([t[1] for t in ta])}  "
           f"{n / np.median(ga) / 1e3:7.2f} M units/s", flush=True)
+    if args.wp:
+        gw = [t[0] for t in tw]
+        print(f"{label:14s} {n:6d} units  (w) hmx_batch_subpel_search_wp GPU {stats(gw)}  whole {stats([t[1] for t in tw])}  "
+              f"{n / np.median(gw) / 1e3:7.2f} M units/s", flush=True)
     if rb is not None:
         gb = [t[0] for t in tb]
         print(f"{label:14s} {n:6d} units  (b) subpel_cost x 49 + host   GPU {stats(gb)}  whole {stats([t[1] for t in tb])}", flush=True)
