@@ -941,6 +941,70 @@ typedef struct {            /* the tables of one hmx_mc_job; both NULL = this jo
                                when no unit of the job uses list 1 (P slice) */
 } hmx_mc_wp;
 int hmx_batch_motionCompensation_wp_multi(hmx_ctx *ctx, int n_jobs, const hmx_mc_job *jobs, const hmx_mc_wp *wp);
+
+/* ------------------------------------------------------------------------------------------------
+ * Prediction error of complete motion candidates: TEncSearch::xGetInterPredictionError (TLibEncoder/TEncSearch.cpp:3059-3081),
+ * the call predInterSearch makes per merge candidate (xMergeEstimation, :3096-3149), for the search result the merge winner is
+ * compared with (:3771-3796) and -- as xGetTemplateCost (:4057-4118) -- per AMVP candidate (xEstimateMvPredAMVP, :3839-3926).
+ * One fused launch: the original block of a unit is read once, every candidate's luma prediction is formed in LDS and never
+ * written, costed, and the winner of each group decided on the device.  All arithmetic is uint32_t, wrapping like UInt.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct { uint32_t index, dist, cost; } hmx_pred_choice;   /* 12 bytes */
+/* cands: HOST array of n candidates (hmx_pu; an unused list has ref0 / ref1 = 255; vectors in quarter samples, clipped with
+ * hmx_clipMv).  bits: HOST array parallel to it (uiBitsCand, uiMEBits, m_auiMVPIdxCost[i][n]); NULL = 0 for every candidate.
+ * group_first: HOST prefix array of n_groups + 1 entries, group_first[0] = 0, group_first[n_groups] = n; the candidates of a
+ * group share x, y, w, h (the kernel stages that original block once).  group_first = NULL with n_groups = 0 and d_best = NULL:
+ * costs only.  refs (n_refs <= 4) / org: device pictures, the references with margins of margin_x / margin_y luma samples.
+ * Prediction: the luma part of TComPrediction::motionCompensation(..., REF_PIC_LIST_X, iPartIdx) (TLibCommon/TComPrediction.cpp:
+ * 410-540): one list = xPredInterLumaBlk with the final rounding; two lists = both into the 14-bit intermediate, then addAvg.
+ * The identical-motion shortcut (xCheckIdenticalMotion, :392-407) needs POCs the library does not see: the caller passes such a
+ * candidate with one list.  Distortion, always UNWEIGHTED (bApplyWeight = false, TEncSearch.cpp:3070): use_had = 1 xGetHADs
+ * (TComRdCost.cpp:2186-2283; 8x8 sub-blocks when both sides are multiples of 8, else 4x4, rounded per sub-block as
+ * hmx_batch_subpel_cost documents), use_had = 0 the SAD over every row (iSubShift = 0, :397); both >> (bit depth - 8).
+ * d_dist[i] (device) = the distortion; d_cost[i] (device) = d_dist[i] + ((lambda * bits[i]) >> 16) (getCost(UInt), TComRdCost.h:
+ * 204); d_best[g] (device) = the first candidate of group g, in array order, whose cost is strictly smaller than a running best
+ * that starts at 0xFFFFFFFF (ruiCost = MAX_UINT, :3120, :3139), index counted inside the group; an empty group, or one whose
+ * every cost is 0xFFFFFFFF, gives {0xFFFFFFFF, 0xFFFFFFFF, 0xFFFFFFFF}.
+ * xGetTemplateCost: with ZERO_MVD_EST 0 (TypeDef.h:183) it costs with SAD whatever UseHADME says (:4111-4115) -- call with
+ * use_had = 0 -- and adds the bits through calcRdCost(..., DF_SAD) (TComRdCost.cpp:94-98), a double product floored: that equals
+ * getCost(UInt) exactly while lambda * bits < 2^31, which the caller must hold.  Its running best starts at MAX_INT with index 0
+ * (:3850, :3906), not 0xFFFFFFFF: decide from d_cost.
+ * HMX_ERR_ARG, on the host before anything is launched, with the candidate or group named in hmx_last_error: a NULL pointer other
+ * than bits, group_first / d_best as allowed above, and wp; n < 1; n_refs outside 1..4; use_had other than 0 or 1; a size outside
+ * {4, 8, 12, 16, 24, 32, 48, 64}; a candidate with no list; a used reference index >= n_refs; the unit outside the picture; a
+ * prefix array that is not monotonic or does not end at n; a group whose candidates differ in x, y, w, h; for any used list the
+ * displaced block grown by the tap window -- columns x + (mvx >> 2) - 3 .. + w + 3, rows likewise, whatever the fraction --
+ * reaching outside [-margin, pic + margin) in either direction (conservative; never refuses a vector hmx_clipMv produced for a
+ * unit inside a 64x64 CTU with 80-sample margins: the reach is at most 74 samples).  Not covered: chroma, the NS_HAD shapes. */
+int hmx_batch_inter_pred_error(hmx_ctx *ctx, const hmx_pu *cands, const uint32_t *bits, int n, const uint32_t *group_first,
+                               int n_groups, const hmx_pic *refs, int n_refs, const hmx_pic *org, int pic_w, int pic_h,
+                               int margin_x, int margin_y, uint32_t lambda, int use_had, uint32_t *d_dist, uint32_t *d_cost,
+                               hmx_pred_choice *d_best);
+/* The same in a weighted slice (TComPrediction.cpp:421-432, :516-535): wp = ONE hmx_mc_wp with the meaning
+ * hmx_batch_motionCompensation_wp_multi gives it, luma rows only.  Every used list goes to the 14-bit intermediate; one list is
+ * weighted uni-directionally, two lists bi-directionally.  The distortion stays unweighted.  wp == NULL, or both tables NULL, is
+ * the unweighted entry.  Also HMX_ERR_ARG: what hmx_batch_motionCompensation_wp_multi refuses for its tables. */
+int hmx_batch_inter_pred_error_wp(hmx_ctx *ctx, const hmx_pu *cands, const uint32_t *bits, int n, const uint32_t *group_first,
+                                  int n_groups, const hmx_pic *refs, int n_refs, const hmx_pic *org, int pic_w, int pic_h,
+                                  int margin_x, int margin_y, uint32_t lambda, int use_had, uint32_t *d_dist, uint32_t *d_cost,
+                                  hmx_pred_choice *d_best, const hmx_mc_wp *wp);
+/* xGetInterPredictionError for ONE unit with host pointers, as hmx_motionCompensation[_wp] takes them: ref0 / ref1 HOST planes
+ * (NULL = list unused), (x, y, w, h) the unit, org the original block at the unit's first sample; wp0 / wp1 both NULL =
+ * unweighted, else the entry of every used list.  A batch of one through the same kernel; *err = the distortion. */
+int hmx_getInterPredictionError(hmx_ctx *ctx, const hmx_pic *ref0, const int *mv0, const hmx_pic *ref1, const int *mv1, int x,
+                                int y, int w, int h, const hmx_pel *org, int org_stride, int use_had, const hmx_wp *wp0,
+                                const hmx_wp *wp1, uint32_t *err);
+/* Host helpers, no context.  TEncSearch::xGetMvpIdxBits (TEncSearch.cpp:3928-3952), 0 <= idx < num. */
+uint32_t hmx_mvpIdxBits(int idx, int num);
+/* uiBitsCand of xMergeEstimation (:3133-3137): cand + 1, less 1 for cand == max_signaled - 1 (MRG_MAX_NUM_CANDS_SIGNALED). */
+uint32_t hmx_mergeIdxBits(int cand, int max_signaled);
+/* TEncSearch::xCheckBestMVP (:4012-4055): (mvx, mvy) the found vector, mvp_cands the AMVP list as n_cands {hor, ver} pairs
+ * (n_cands <= AMVP_MAX_NUM_CANDS = 2), *mvp_idx the predictor the search ran with.  n_cands < 2 changes nothing.  Otherwise the
+ * candidate with strictly fewer bits -- hmx_mvBits(mv, candidate, 0) + hmx_mvpIdxBits(i, 2) -- replaces it, first such in order,
+ * and *bits / *cost are updated as :4051-4053 (uint32_t, wrapping; getCost(UInt) with lambda).  HMX_ERR_ARG: a NULL pointer,
+ * n_cands outside 0..2, *mvp_idx outside the list. */
+int hmx_checkBestMVP(uint32_t lambda, int mvx, int mvy, const int16_t *mvp_cands, int n_cands, int *mvp_idx, uint32_t *bits,
+                     uint32_t *cost);
 int hmx_batch_residual_transformNxN_multi(hmx_ctx *ctx, const hmx_tu_list *list, int n_pics, const hmx_pic *org,
                                           const hmx_pic *pred, const hmx_levels *lev, uint32_t *d_abs_sum,
                                           const hmx_pic_param *pp);

@@ -117,6 +117,14 @@ TZ_UNIT_DTYPE = np.dtype([("start_x", "<i2"), ("start_y", "<i2"), ("range", "<u2
 TZ_POINT_DTYPE = np.dtype([("x", "<i2"), ("y", "<i2"), ("cost", "<u4")])  # hmx_tz_point
 SUBPEL_RESULT_DTYPE = np.dtype([("mvx", "<i2"), ("mvy", "<i2"), ("dist", "<u4"), ("cost", "<u4")])  # hmx_subpel_result, quarter samples
 
+
+
+class PredChoice(C.Structure):  # hmx_pred_choice
+    _fields_ = [("index", C.c_uint32), ("dist", C.c_uint32), ("cost", C.c_uint32)]
+
+
+PRED_CHOICE_DTYPE = np.dtype([("index", "<u4"), ("dist", "<u4"), ("cost", "<u4")])  # hmx_pred_choice
+
 WP_DTYPE = np.dtype([("weight", "<i2", 3), ("offset", "<i2", 3), ("log2_denom", "u1", 3), ("reserved", "u1")])  # hmx_wp
 
 
@@ -386,6 +394,16 @@ def lib():
                 continue  # an older build loaded for an A/B run: calling the entry still raises
             getattr(L, name).argtypes = at
             getattr(L, name).restype = ci
+        pe = [vp, vp, vp, ci, vp, ci, C.POINTER(Pic), ci, C.POINTER(Pic), ci, ci, ci, ci, u32, ci, vp, vp, vp]
+        for name, at, rt in (("hmx_batch_inter_pred_error", pe, ci), ("hmx_batch_inter_pred_error_wp", pe + [C.POINTER(McWp)], ci),
+                             ("hmx_getInterPredictionError", [vp, C.POINTER(Pic), C.POINTER(ci), C.POINTER(Pic), C.POINTER(ci), ci, ci, ci, ci, vp,
+                                                              ci, ci, C.POINTER(Wp), C.POINTER(Wp), C.POINTER(u32)], ci),
+                             ("hmx_mvpIdxBits", [ci, ci], u32), ("hmx_mergeIdxBits", [ci, ci], u32),
+                             ("hmx_checkBestMVP", [u32, ci, ci, vp, ci, C.POINTER(ci), C.POINTER(u32), C.POINTER(u32)], ci)):
+            if "HMX_LIB_PATH" in os.environ and not hasattr(L, name):
+                continue  # an older build loaded for an A/B run: calling the entry still raises
+            getattr(L, name).argtypes = at
+            getattr(L, name).restype = rt
         L.hmx_yuv_frame_bytes.argtypes = [ci, ci, ci]
         L.hmx_yuv_frame_bytes.restype = C.c_size_t
         L.hmx_yuv_unpack.argtypes = [vp, vp, ci, C.POINTER(Pic), ci, ci, ci, ci]
@@ -959,6 +977,57 @@ class Context:
             if own_int:
                 d_int.free()
 
+    def batch_inter_pred_error_into(self, cands, bits, group_first, refs, org, pic_w, pic_h, margin_x, margin_y, lambda_, use_had, d_dist,
+                                    d_cost, d_best, wp=None):
+        """hmx_batch_inter_pred_error (wp: hmx_batch_inter_pred_error_wp) into device buffers the caller owns (DevBufs or None),
+        issued on the context's stream and not waited for.  cands = array of PU_DTYPE (host), bits = uint32 array or None,
+        group_first = uint32 prefix array or None (costs only: d_best None), refs = DevPictures with margins, org = DevPicture;
+        wp = None or (l0, l1), WP_DTYPE tables with one row per reference, either possibly None."""
+        cands = np.ascontiguousarray(cands, PU_DTYPE)
+        bits = None if bits is None else np.ascontiguousarray(bits, np.uint32)
+        first = None if group_first is None else np.ascontiguousarray(group_first, np.uint32)
+        ref_arr = (Pic * max(1, len(refs)))(*[r.as_pic() for r in refs])
+        args = (self.h, cands.ctypes.data, None if bits is None else bits.ctypes.data, len(cands), None if first is None else first.ctypes.data,
+                0 if first is None else len(first) - 1, ref_arr, len(refs), C.byref(org.as_pic()), pic_w, pic_h, margin_x, margin_y,
+                int(lambda_) & 0xFFFFFFFF, int(use_had), getattr(d_dist, "ptr", d_dist), getattr(d_cost, "ptr", d_cost),
+                getattr(d_best, "ptr", d_best))
+        if wp is None:
+            self._chk(lib().hmx_batch_inter_pred_error(*args))
+        else:
+            arr, keep = mc_wp_array([tuple(wp)])
+            self._chk(lib().hmx_batch_inter_pred_error_wp(*args, arr))
+            del keep  # the call has copied the tables
+
+    def batch_inter_pred_error(self, cands, bits, group_first, refs, org, pic_w, pic_h, margin_x, margin_y, lambda_, use_had, wp=None):
+        """hmx_batch_inter_pred_error[_wp], arguments as for batch_inter_pred_error_into.  Returns (dist, cost, best): uint32 (n),
+        uint32 (n) and PRED_CHOICE_DTYPE (n_groups), best None for a costs-only call (group_first None)."""
+        n = len(cands)
+        ng = 0 if group_first is None else len(group_first) - 1
+        d_dist, d_cost = self.alloc(max(1, n) * 4), self.alloc(max(1, n) * 4)
+        d_best = self.alloc(max(1, ng) * PRED_CHOICE_DTYPE.itemsize) if group_first is not None else None
+        try:
+            self.batch_inter_pred_error_into(cands, bits, group_first, refs, org, pic_w, pic_h, margin_x, margin_y, lambda_, use_had, d_dist,
+                                             d_cost, d_best, wp)
+            self.sync()
+            return (d_dist.download(np.uint32, n), d_cost.download(np.uint32, n),
+                    d_best.download(PRED_CHOICE_DTYPE, ng) if d_best else None)
+        finally:
+            for d in (d_dist, d_cost, d_best):
+                if d:
+                    d.free()
+
+    def getInterPredictionError(self, ref0, mv0, ref1, mv1, x, y, w, h, org, org_stride, use_had, wp0=None, wp1=None):
+        """hmx_getInterPredictionError: ref0 / ref1 = Pic of host planes (None = list unused), mv = (hor, ver), org = int16 array
+        holding the original block at its start with org_stride, wp0 / wp1 = Wp or None.  Returns the distortion."""
+        org = np.ascontiguousarray(org, np.int16)
+        m0 = None if mv0 is None else (C.c_int * 2)(*mv0)
+        m1 = None if mv1 is None else (C.c_int * 2)(*mv1)
+        v = C.c_uint32()
+        self._chk(lib().hmx_getInterPredictionError(self.h, None if ref0 is None else C.byref(ref0), m0, None if ref1 is None else C.byref(ref1),
+                                                    m1, x, y, w, h, _hp(org), org_stride, int(use_had), None if wp0 is None else C.byref(wp0),
+                                                    None if wp1 is None else C.byref(wp1), C.byref(v)))
+        return v.value
+
     def sao_stats(self, orgs, recs, w, h, lcu_based=True, avail=None):
         """hmx_sao_stats_multi: the encoder's SAO statistics of n pictures (DevPictures, org and deblocked rec) as an int32
         array (n, 3 components, n_lcu, SAO_STAT_BINS, 2): [..., 0] = sum of org - rec, [..., 1] = count; bins as in
@@ -1086,6 +1155,26 @@ def clip_mv(mvx, mvy, cu_x, cu_y, pic_w, pic_h, ctu_size=64):
     x, y = C.c_int(mvx), C.c_int(mvy)
     lib().hmx_clipMv(C.byref(x), C.byref(y), cu_x, cu_y, pic_w, pic_h, ctu_size)
     return x.value, y.value
+
+
+def mvp_idx_bits(idx, num):
+    """hmx_mvpIdxBits: TEncSearch::xGetMvpIdxBits, 0 <= idx < num."""
+    return lib().hmx_mvpIdxBits(idx, num)
+
+
+def merge_idx_bits(cand, max_signaled=5):
+    """hmx_mergeIdxBits: uiBitsCand of xMergeEstimation."""
+    return lib().hmx_mergeIdxBits(cand, max_signaled)
+
+
+def check_best_mvp(lambda_, mvx, mvy, mvp_cands, mvp_idx, bits, cost):
+    """hmx_checkBestMVP (TEncSearch::xCheckBestMVP): mvp_cands = (n, 2) quarter-sample predictors.  Returns (mvp_idx, bits, cost)."""
+    cands = np.ascontiguousarray(mvp_cands, np.int16).reshape(-1, 2)
+    i, b, c = C.c_int(mvp_idx), C.c_uint32(int(bits) & 0xFFFFFFFF), C.c_uint32(int(cost) & 0xFFFFFFFF)
+    rc = lib().hmx_checkBestMVP(int(lambda_) & 0xFFFFFFFF, mvx, mvy, cands.ctypes.data, len(cands), C.byref(i), C.byref(b), C.byref(c))
+    if rc != 0:
+        raise HmxError(f"hmx_checkBestMVP refused its arguments ({rc})")
+    return i.value, b.value, c.value
 
 
 def tz_units(units, range_, pic_w, pic_h, ctu_size=64):

@@ -7,7 +7,8 @@
 //   hmx_chain.hip       whole-picture all-intra chain: level / wave / packed schedules, resident pools
 //   hmx_chain_rdoq.hip  the packed schedule's kernel with xRateDistOptQuant as its quantiser (a translation unit of its own:
 //                       its instantiations take as long to compile as everything else together)
-//   hmx_inter.hip       interpolation filters, motion compensation, sub-pel cost fan-out, border extension
+//   hmx_inter.hip       interpolation filters, motion compensation, sub-pel cost fan-out, border extension, prediction error of
+//                       complete motion candidates (k_pred_error)
 //   hmx_me.hip          full-search integer motion estimation (SAD, vector-bits cost, search box)
 //   hmx_loop.hip        deblocking, SAO, YUV file formats
 // and hmx_lib.hip includes all of them for a single-translation-unit build (-DHMX_PACK_PROFILE builds read device

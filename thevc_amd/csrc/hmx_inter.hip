@@ -887,3 +887,418 @@ extern "C" int hmx_pic_extend_border(hmx_ctx *c, const hmx_pic *pic, int pic_w, 
   return hmx_pic_extend_border_multi(c, 1, pic, pic_w, pic_h, mx, my);
 }
 
+
+// =============================================================================================
+// Prediction error of complete motion candidates: TEncSearch::xGetInterPredictionError (TEncSearch.cpp:3059-3081), fused
+// =============================================================================================
+// predInterSearch compares complete candidates -- the merge candidates of xMergeEstimation (:3096-3149), the search result the
+// merge winner meets (:3771-3796), the AMVP candidates of xGetTemplateCost (:4057-4118) -- and each comparison is the luma part
+// of motionCompensation (TComPrediction.cpp:410-540) followed by xGetHADs / xGetSAD against the original, UNWEIGHTED
+// (bApplyWeight = false, :3070) also in a weighted slice.  One workgroup owns one GROUP of candidates of one unit: the original
+// block goes to LDS once; per candidate and used list the (w + 7) x (h + 7) reference window is staged with coalesced row loads,
+// xPredInterLumaBlk's three cases run on it (horizontal only, vertical only, horizontal into a 14-bit LDS intermediate then
+// vertical), the second pass hands each finished sample straight to the combination (final sample; addAvg with the first list's
+// 14-bit block, which waits in LDS; weightUnidir / weightBidir) and the difference, and S lanes (S = 8, or 4 when a side is no
+// multiple of 8) form one sub-block: Hadamard down the lane's column in registers and across the lanes by shuffles, or the SAD.
+// No prediction sample leaves the workgroup.  Thread 0 adds the bits term and keeps the running best of the group (:3139).
+// LDS rows are padded to an odd number of dwords (pe_pitch): the sub-blocks of a wave that lie below each other start 8 (4)
+// rows apart, and with an even pitch their columns would walk the same banks.
+constexpr int kPeThreads = 256;
+struct PeWp { // the luma entry of one (reference, list): getWpScaling's fields, o at the bit depth
+  short w, o;
+  int d;
+};
+struct PeArgs {
+  const hmx_pu *cands;
+  const uint32_t *bits;  // NULL: 0 for every candidate
+  const uint32_t *first; // [n_groups + 1]
+  PlanesDev refs[4];
+  PlanesDev org;
+  int B, use_had;
+  uint32_t lambda;
+  uint32_t *dist, *cost;
+  hmx_pred_choice *best; // NULL: costs only
+  static constexpr bool weighted = false;
+};
+struct PeArgsWp : PeArgs { // as SubpelArgsWp: the unweighted kernel keeps its argument block
+  PeWp wp[4][2];           // [reference][list]
+  static constexpr bool weighted = true;
+};
+__host__ __device__ constexpr int pe_pitch(int n) { return (((n + 1) >> 1) | 1) << 1; } // >= n samples, an odd number of dwords
+static size_t pe_lds_bytes(int w, int h) { // original, window, intermediate, the first list's 14-bit block
+  return sizeof(short) * (size_t)(w * h + pe_pitch(w + 7) * (h + 7) + pe_pitch(w) * (h + 7) + w * h);
+}
+enum PeMode { PE_FINAL, PE_KEEP, PE_AVG, PE_WUNI, PE_WBI };
+// One filter stage with everything that is uniform over a pass taken out of the sample loop: the taps (luma_tap) in registers and
+// the shift, offset and clip of interp_sample<8>'s filter branch (TComInterpolationFilter::filter, :160-244).  A zero fraction runs
+// as the filter {.., 64, ..}: with these offsets and shifts that is bit-identical to filterCopy (:91-145) in the three cases
+// xPredInterLumaBlk uses (see mc_cell above), so a pass has no branch per sample and no table load per tap.
+struct PeFilter {
+  int tap[8], shift, offset, lo, hi;
+};
+__device__ __forceinline__ PeFilter pe_filter(int frac, bool first, bool last, int B) {
+  PeFilter f;
+#pragma unroll
+  for (int q = 0; q < 8; q++) f.tap[q] = luma_tap(frac, q);
+  const int head = 14 - B;
+  f.shift = 6;
+  if (last) {
+    f.shift += first ? 0 : head;
+    f.offset = (1 << (f.shift - 1)) + (first ? 0 : 8192 << 6);
+  } else {
+    f.shift -= first ? head : 0;
+    f.offset = first ? -(8192 << f.shift) : 0;
+  }
+  f.lo = last ? 0 : -32768, f.hi = last ? (1 << B) - 1 : 32767; // narrowed to Short before the clip (:232-236); not last: no clip
+  return f;
+}
+__device__ __forceinline__ int pe_sample(const PeFilter &f, const int *s) { // s[0..7]: the samples under the taps
+  int sum = f.offset;
+#pragma unroll
+  for (int q = 0; q < 8; q++) sum += s[q] * f.tap[q];
+  return clip3(f.lo, f.hi, wrap16(sum >> f.shift));
+}
+// k = tid, tid + nt, ... as (row, column) of a `cols`-wide block without a division per element
+struct PeWalk {
+  int r, c, dr, dc, cols;
+  __device__ __forceinline__ PeWalk(int tid, int nt, int cols_) : r(tid / cols_), c(tid - (tid / cols_) * cols_), dr(nt / cols_), dc(nt - (nt / cols_) * cols_), cols(cols_) {}
+  __device__ __forceinline__ void next() {
+    r += dr, c += dc;
+    if (c >= cols) c -= cols, r++;
+  }
+};
+// The last filter pass of one list over the whole block, and what follows it.  src: the block's first sample in the window
+// (first) or in the intermediate (!first), rows `pitch` apart; ver: the taps run down the column.  PE_KEEP stores the 14-bit
+// samples in p0 and costs nothing; every other mode adds the block's distortion to *s_sum.
+template <int S>
+__device__ __forceinline__ void pe_cost_pass(const short *src, int pitch, bool ver, int frac, bool first, int mode, short *p0, const short *org, int w,
+                                             int h, int B, int use_had, int w0, int w1, int woff, int wshift, unsigned *s_sum, int tid, int nthreads) {
+  const int bw = w / S, nsb = bw * (h / S), lane = tid & (S - 1);
+  const PeFilter f = pe_filter(frac, first, mode == PE_FINAL, B);
+  for (int base = 0; base < nsb; base += nthreads / S) {
+    if (base + (tid & ~63) / S >= nsb) break; // no sub-block left for this wave (uniform over the wave)
+    int g = base + tid / S;
+    const bool act = g < nsb; // idle lanes of a busy wave redo the last sub-block and add nothing
+    g = act ? g : nsb - 1;
+    const int sby = g / bw, sx = (g - sby * bw) * S + lane, sy = sby * S;
+    const short *s = src + sy * pitch + sx;
+    int d[S];
+    if (ver) { // the column this lane filters, read once
+      int col[S + 7];
+#pragma unroll
+      for (int q = 0; q < S + 7; q++) col[q] = s[(q - 3) * pitch];
+#pragma unroll
+      for (int r = 0; r < S; r++) d[r] = pe_sample(f, col + r);
+    } else {
+#pragma unroll
+      for (int r = 0; r < S; r++) {
+        int row[8];
+#pragma unroll
+        for (int q = 0; q < 8; q++) row[q] = s[r * pitch + q - 3];
+        d[r] = pe_sample(f, row);
+      }
+    }
+    short *k0 = p0 + sy * w + sx;
+    if (mode == PE_KEEP) {
+#pragma unroll
+      for (int r = 0; r < S; r++) k0[r * w] = (short)d[r];
+      continue;
+    }
+    if (mode == PE_AVG) {
+#pragma unroll
+      for (int r = 0; r < S; r++) d[r] = add_avg(k0[r * w], d[r], B);
+    } else if (mode == PE_WUNI) {
+#pragma unroll
+      for (int r = 0; r < S; r++) d[r] = weight_uni(d[r], w0, woff, wshift, B);
+    } else if (mode == PE_WBI) {
+#pragma unroll
+      for (int r = 0; r < S; r++) d[r] = weight_bi(k0[r * w], d[r], w0, w1, woff, wshift, B);
+    }
+    const short *o = org + sy * w + sx;
+#pragma unroll
+    for (int r = 0; r < S; r++) d[r] = o[r * w] - d[r];
+    if (use_had) { // the 2-D transform's sum of magnitudes: down the column here, then across the S lanes (as sp_stage, hmx_me.hip)
+      wht_regs<S>(d);
+#pragma unroll
+      for (int m = 1; m < S; m <<= 1)
+#pragma unroll
+        for (int r = 0; r < S; r++) {
+          const int other = __shfl_xor(d[r], m, 64);
+          d[r] = (lane & m) ? other - d[r] : d[r] + other;
+        }
+    }
+    int sum = 0;
+#pragma unroll
+    for (int r = 0; r < S; r++) sum += abs(d[r]);
+    sum = group_sum(sum, S);
+    if (use_had) sum = S == 8 ? (sum + 2) >> 2 : (sum + 1) >> 1; // rounded per sub-block (TComRdCost.cpp:2083, :1991)
+    if (act && lane == 0) atomicAdd(s_sum, (unsigned)sum);
+  }
+}
+template <class ARGS>
+__global__ __launch_bounds__(kPeThreads) void k_pred_error(ARGS A) {
+  constexpr bool WP = ARGS::weighted;
+  extern __shared__ __attribute__((aligned(16))) short s_pe[];
+  __shared__ unsigned s_sum;
+  typedef __attribute__((address_space(1))) const short gpel;
+  const int grp = blockIdx.x, tid = threadIdx.x, nt = blockDim.x, B = A.B;
+  const uint32_t c0 = A.first[grp], c1 = A.first[grp + 1];
+  hmx_pred_choice best{0xffffffffu, 0xffffffffu, 0xffffffffu};
+  if (c0 == c1) { // uniform over the workgroup
+    if (tid == 0 && A.best) A.best[grp] = best;
+    return;
+  }
+  const hmx_pu u0 = A.cands[c0];
+  const int x = u0.x, y = u0.y, w = u0.w, h = u0.h, wp = pe_pitch(w + 7), tp = pe_pitch(w), ww = w + 7, rows = h + 7;
+  short *org = s_pe, *win = org + w * h, *tmp = win + wp * rows, *p0 = tmp + tp * rows;
+  const PeWalk walk_w(tid, nt, w), walk_ww(tid, nt, ww);
+  {
+    const gpel *so = (const gpel *)A.org.p[0] + (size_t)y * A.org.s[0] + x;
+    PeWalk k = walk_w;
+    for (int i = tid; i < w * h; i += nt, k.next()) org[i] = so[(size_t)k.r * A.org.s[0] + k.c];
+  }
+  if (tid == 0) s_sum = 0;
+  const bool s8 = (w % 8 == 0) && (h % 8 == 0);
+  for (uint32_t i = c0; i < c1; i++) {
+    const hmx_pu u = A.cands[i];
+    const bool bi = u.ref0 != 255 && u.ref1 != 255, mid = WP || bi; // mid: the lists' predictions are 14-bit samples
+    int w0 = 0, w1 = 0, woff = 0, wshift = 0;
+    if constexpr (WP) { // getWpScaling (TComWeightPrediction.cpp:286-312): two lists share list 0's denominator and sum the offsets
+      const int head = 14 - B;
+      if (bi) {
+        const PeWp e0 = A.wp[u.ref0 & 3][0], e1 = A.wp[u.ref1 & 3][1];
+        w0 = e0.w, w1 = e1.w, woff = e0.o + e1.o, wshift = e0.d + 1 + head;
+      } else {
+        const PeWp e = u.ref0 != 255 ? A.wp[u.ref0 & 3][0] : A.wp[u.ref1 & 3][1];
+        w0 = e.w, woff = e.o, wshift = e.d + head;
+      }
+    }
+    for (int l = 0; l < 2; l++) {
+      const int ref = l ? u.ref1 : u.ref0;
+      if (ref == 255) continue;
+      const int mvx = l ? u.mv1x : u.mv0x, mvy = l ? u.mv1y : u.mv0y, xf = mvx & 3, yf = mvy & 3;
+      const PlanesDev &R = A.refs[ref & 3];
+      const gpel *sr = (const gpel *)R.p[0] + (ptrdiff_t)(y + (mvy >> 2) - 3) * R.s[0] + (x + (mvx >> 2) - 3);
+      __syncthreads(); // the previous pass has read the window and the intermediate (the first time: the original is staged)
+      {
+        PeWalk k = walk_ww;
+        for (int j = tid; j < ww * rows; j += nt, k.next()) win[k.r * wp + k.c] = sr[(ptrdiff_t)k.r * R.s[0] + k.c];
+      }
+      __syncthreads();
+      const short *src = win + 3 * wp + 3;
+      int pitch = wp, frac = xf;
+      bool first = true, ver = false;
+      if (xf && yf) { // filterHorLuma(isLast = false) of rows -3 .. h + 3, then filterVerLuma(isFirst = false) (TComPrediction.cpp:583-600)
+        const PeFilter f = pe_filter(xf, true, false, B);
+        PeWalk k = walk_w;
+        for (int j = tid; j < w * rows; j += nt, k.next()) {
+          const short *s = win + k.r * wp + k.c;
+          int row[8];
+#pragma unroll
+          for (int q = 0; q < 8; q++) row[q] = s[q];
+          tmp[k.r * tp + k.c] = (short)pe_sample(f, row);
+        }
+        __syncthreads();
+        src = tmp + 3 * tp, pitch = tp, frac = yf, first = false, ver = true;
+      } else if (yf) {
+        frac = yf, ver = true;
+      }
+      const int mode = !mid ? PE_FINAL : (bi && l == 0) ? PE_KEEP : bi ? (WP ? PE_WBI : PE_AVG) : PE_WUNI;
+      if (s8) pe_cost_pass<8>(src, pitch, ver, frac, first, mode, p0, org, w, h, B, A.use_had, w0, w1, woff, wshift, &s_sum, tid, nt);
+      else pe_cost_pass<4>(src, pitch, ver, frac, first, mode, p0, org, w, h, B, A.use_had, w0, w1, woff, wshift, &s_sum, tid, nt);
+    }
+    __syncthreads();
+    if (tid == 0) { // getCost(UInt) (TComRdCost.h:204), all of it uint32_t; the next sum starts two barriers from here
+      const uint32_t dist = s_sum >> (B - 8), cost = dist + ((A.lambda * (A.bits ? A.bits[i] : 0u)) >> 16);
+      s_sum = 0;
+      A.dist[i] = dist, A.cost[i] = cost;
+      if (cost < best.cost) best = hmx_pred_choice{i - c0, dist, cost};
+    }
+  }
+  if (tid == 0 && A.best) A.best[grp] = best;
+}
+
+static bool pe_size_ok(int v) { return v == 4 || v == 8 || v == 12 || v == 16 || v == 24 || v == 32 || v == 48 || v == 64; }
+// the launch: every argument has been checked; first (host): n_groups + 1 prefix entries
+static int pe_launch(hmx_ctx *c, const hmx_pu *cands, const uint32_t *bits, int n, const uint32_t *first, int n_groups, const PlanesDev *refs, int n_refs,
+                     const PlanesDev &org, uint32_t lambda, int use_had, uint32_t *d_dist, uint32_t *d_cost, hmx_pred_choice *d_best, const PeWp (*wp)[2]) {
+  size_t lds = 0;
+  int threads = 64;
+  for (int i = 0; i < n; i++) {
+    const int w = cands[i].w, h = cands[i].h, s = (w % 8 == 0 && h % 8 == 0) ? 8 : 4;
+    lds = std::max(lds, pe_lds_bytes(w, h));
+    threads = std::max(threads, std::min(kPeThreads, (w * h / s + 63) & ~63)); // one lane per sub-block column
+  }
+  PeArgsWp A{};
+  A.cands = static_cast<const hmx_pu *>(arena_push(c, cands, sizeof(hmx_pu) * (size_t)n)); // the caller's host arrays
+  A.bits = bits ? static_cast<const uint32_t *>(arena_push(c, bits, sizeof(uint32_t) * (size_t)n)) : nullptr;
+  A.first = static_cast<const uint32_t *>(arena_push(c, first, sizeof(uint32_t) * ((size_t)n_groups + 1)));
+  if (!A.cands || (bits && !A.bits) || !A.first) return fail(c, HMX_ERR_NOMEM, "argument arena (candidate list too long: split the call)");
+  for (int r = 0; r < n_refs; r++) A.refs[r] = refs[r];
+  A.org = org;
+  A.B = c->cfg.bit_depth, A.use_had = use_had, A.lambda = lambda;
+  A.dist = d_dist, A.cost = d_cost, A.best = d_best;
+  if (wp) {
+    memcpy(A.wp, wp, sizeof(A.wp));
+    hipLaunchKernelGGL(k_pred_error<PeArgsWp>, dim3((unsigned)n_groups), dim3(threads), lds, c->stream, A);
+  } else {
+    hipLaunchKernelGGL(k_pred_error<PeArgs>, dim3((unsigned)n_groups), dim3(threads), lds, c->stream, static_cast<const PeArgs &>(A));
+  }
+  HIPCHK(c, hipGetLastError());
+  return HMX_OK;
+}
+static int pred_error(hmx_ctx *c, const char *name, const hmx_pu *cands, const uint32_t *bits, int n, const uint32_t *group_first, int n_groups,
+                      const hmx_pic *refs, int n_refs, const hmx_pic *org, int pic_w, int pic_h, int margin_x, int margin_y, uint32_t lambda, int use_had,
+                      uint32_t *d_dist, uint32_t *d_cost, hmx_pred_choice *d_best, const hmx_mc_wp *wp) {
+  const std::string nm = name;
+  if (!c || !cands || !refs || !org || !d_dist || !d_cost) return fail(c, HMX_ERR_ARG, nm + ": null argument");
+  if (n <= 0) return fail(c, HMX_ERR_ARG, nm + ": n must be at least 1");
+  if (n_refs <= 0 || n_refs > 4) return fail(c, HMX_ERR_ARG, nm + ": n_refs must be 1 .. 4");
+  if (use_had != 0 && use_had != 1) return fail(c, HMX_ERR_ARG, nm + ": use_had is 0 or 1");
+  if (n_groups < 0 || (n_groups == 0) != (group_first == nullptr) || (n_groups == 0) != (d_best == nullptr))
+    return fail(c, HMX_ERR_ARG, nm + ": group_first, n_groups and d_best are given together (groups) or NULL, 0, NULL (costs only)");
+  if (pic_w <= 0 || pic_h <= 0 || margin_x < 0 || margin_y < 0)
+    return fail(c, HMX_ERR_ARG, nm + ": picture size must be positive and margins not negative");
+  if (!org->plane[0]) return fail(c, HMX_ERR_ARG, nm + ": the original has no luma plane");
+  for (int r = 0; r < n_refs; r++)
+    if (!refs[r].plane[0]) return fail(c, HMX_ERR_ARG, nm + ": a reference has no luma plane");
+  const bool weighted = wp && (wp->l0 || wp->l1);
+  PeWp wpt[4][2] = {};
+  if (weighted) {
+    if (!wp->l0) return fail(c, HMX_ERR_ARG, nm + ": a weighted call needs the list 0 table (l0 NULL, l1 not)");
+    const hmx_wp unit = {{1, 1, 1}, {0, 0, 0}, {0, 0, 0}, 0}; // a missing list 1 table holds the unit weight
+    for (int r = 0; r < n_refs; r++)
+      for (int l = 0; l < 2; l++) {
+        const hmx_wp *t = l ? wp->l1 : wp->l0;
+        WpDev e;
+        if (!wp_entry(t ? t[r] : unit, c->cfg.bit_depth, &e))
+          return fail(c, HMX_ERR_ARG, nm + ": wp list " + std::to_string(l) + " row " + std::to_string(r) +
+                                          ": weight outside -128..255, offset outside -128..127 or log2_denom > 7");
+        wpt[r][l] = PeWp{e.w[0], e.o[0], e.d[0]};
+      }
+  }
+  for (int i = 0; i < n; i++) {
+    const hmx_pu &u = cands[i];
+    auto refuse = [&](const std::string &why) { return fail(c, HMX_ERR_ARG, nm + ": candidate " + std::to_string(i) + ": " + why); }; // text only when refused
+    if (!pe_size_ok(u.w) || !pe_size_ok(u.h)) return refuse("width and height come from {4, 8, 12, 16, 24, 32, 48, 64}");
+    if (u.ref0 == 255 && u.ref1 == 255) return refuse("no list is used");
+    if (u.x + u.w > pic_w || u.y + u.h > pic_h) return refuse("the unit lies outside the picture");
+    for (int l = 0; l < 2; l++) {
+      const int ref = l ? u.ref1 : u.ref0, ix = (l ? u.mv1x : u.mv0x) >> 2, iy = (l ? u.mv1y : u.mv0y) >> 2;
+      if (ref == 255) continue;
+      if (ref >= n_refs) return refuse("reference index of list " + std::to_string(l) + " outside refs[]");
+      // the tap window, whatever the fraction: columns x + ix - 3 .. x + ix + w + 3, rows likewise
+      if (u.x + ix - 3 < -margin_x || u.x + ix + u.w + 4 > pic_w + margin_x || u.y + iy - 3 < -margin_y || u.y + iy + u.h + 4 > pic_h + margin_y)
+        return refuse("the interpolation window of list " + std::to_string(l) + " reaches outside the reference's margins");
+    }
+  }
+  std::vector<uint32_t> ones;
+  if (!n_groups) { // costs only: groups of one
+    ones.resize((size_t)n + 1);
+    for (int i = 0; i <= n; i++) ones[i] = (uint32_t)i;
+    group_first = ones.data();
+  } else {
+    if (group_first[0] != 0) return fail(c, HMX_ERR_ARG, nm + ": group 0: group_first[0] must be 0");
+    for (int g = 0; g < n_groups; g++) // the prefix first: the geometry pass below indexes cands[] with it
+      if (group_first[g + 1] < group_first[g] || group_first[g + 1] > (uint32_t)n)
+        return fail(c, HMX_ERR_ARG, nm + ": group " + std::to_string(g) + ": group_first is not monotonic or passes n");
+    if (group_first[n_groups] != (uint32_t)n) return fail(c, HMX_ERR_ARG, nm + ": group " + std::to_string(n_groups - 1) + ": group_first does not end at n");
+    for (int g = 0; g < n_groups; g++)
+      for (uint32_t i = group_first[g] + 1; i < group_first[g + 1]; i++) {
+        const hmx_pu &a = cands[group_first[g]], &b = cands[i];
+        if (a.x != b.x || a.y != b.y || a.w != b.w || a.h != b.h)
+          return fail(c, HMX_ERR_ARG, nm + ": group " + std::to_string(g) + ": its candidates differ in x, y, w or h");
+      }
+  }
+  PlanesDev dr[4] = {};
+  for (int r = 0; r < n_refs; r++) dr[r] = to_dev(&refs[r]);
+  return pe_launch(c, cands, bits, n, group_first, n_groups ? n_groups : n, dr, n_refs, to_dev(org), lambda, use_had, d_dist, d_cost, d_best,
+                   weighted ? wpt : nullptr);
+}
+extern "C" int hmx_batch_inter_pred_error(hmx_ctx *c, const hmx_pu *cands, const uint32_t *bits, int n, const uint32_t *group_first, int n_groups,
+                                          const hmx_pic *refs, int n_refs, const hmx_pic *org, int pic_w, int pic_h, int margin_x, int margin_y,
+                                          uint32_t lambda, int use_had, uint32_t *d_dist, uint32_t *d_cost, hmx_pred_choice *d_best) {
+  return pred_error(c, "hmx_batch_inter_pred_error", cands, bits, n, group_first, n_groups, refs, n_refs, org, pic_w, pic_h, margin_x, margin_y, lambda,
+                    use_had, d_dist, d_cost, d_best, nullptr);
+}
+extern "C" int hmx_batch_inter_pred_error_wp(hmx_ctx *c, const hmx_pu *cands, const uint32_t *bits, int n, const uint32_t *group_first, int n_groups,
+                                             const hmx_pic *refs, int n_refs, const hmx_pic *org, int pic_w, int pic_h, int margin_x, int margin_y,
+                                             uint32_t lambda, int use_had, uint32_t *d_dist, uint32_t *d_cost, hmx_pred_choice *d_best,
+                                             const hmx_mc_wp *wp) {
+  return pred_error(c, "hmx_batch_inter_pred_error_wp", cands, bits, n, group_first, n_groups, refs, n_refs, org, pic_w, pic_h, margin_x, margin_y, lambda,
+                    use_had, d_dist, d_cost, d_best, wp);
+}
+// The scalar drop-in: the tap windows of the used lists and the original go up into the context scratch, the candidate is
+// re-based on them (unit at (3, 3) of each window, the vectors' fractions kept) and runs through k_pred_error as a batch of one.
+extern "C" int hmx_getInterPredictionError(hmx_ctx *c, const hmx_pic *ref0, const int *mv0, const hmx_pic *ref1, const int *mv1, int x, int y, int w, int h,
+                                           const hmx_pel *org, int org_stride, int use_had, const hmx_wp *wp0, const hmx_wp *wp1, uint32_t *err) {
+  const std::string nm = "hmx_getInterPredictionError";
+  if (!c || !org || !err || (!ref0 && !ref1) || (ref0 && !mv0) || (ref1 && !mv1)) return fail(c, HMX_ERR_ARG, nm + ": null argument, or no list is used");
+  if ((ref0 && !ref0->plane[0]) || (ref1 && !ref1->plane[0])) return fail(c, HMX_ERR_ARG, nm + ": a reference has no luma plane");
+  if (use_had != 0 && use_had != 1) return fail(c, HMX_ERR_ARG, nm + ": use_had is 0 or 1");
+  if (!pe_size_ok(w) || !pe_size_ok(h)) return fail(c, HMX_ERR_ARG, nm + ": width and height come from {4, 8, 12, 16, 24, 32, 48, 64}");
+  const bool weighted = wp0 || wp1;
+  if (weighted && ((ref0 && !wp0) || (ref1 && !wp1))) return fail(c, HMX_ERR_ARG, nm + ": a weighted call needs the entry of every used list");
+  PeWp wpt[4][2] = {};
+  for (int l = 0; l < 2 && weighted; l++) {
+    WpDev e;
+    if (!(l ? ref1 : ref0)) continue;
+    if (!wp_entry(l ? *wp1 : *wp0, c->cfg.bit_depth, &e))
+      return fail(c, HMX_ERR_ARG, nm + ": wp" + std::to_string(l) + ": weight outside -128..255, offset outside -128..127 or log2_denom > 7");
+    wpt[l][l] = PeWp{e.w[0], e.o[0], e.d[0]};
+  }
+  const int ww = w + 7, wh = h + 7;
+  Scratch s{c};
+  uint32_t *d_out = s.take_tail<uint32_t>(2);
+  short *d_org = s.take<short>((size_t)ww * wh); // the original at (3, 3) of a buffer shaped like the windows
+  if (s.r) return s.r;
+  HIPCHK(c, hipMemcpy2DAsync(d_org + 3 * ww + 3, ww * sizeof(short), org, (size_t)org_stride * sizeof(short), w * sizeof(short), h, hipMemcpyHostToDevice,
+                             c->stream));
+  hmx_pu u{};
+  u.x = u.y = 3, u.w = (uint8_t)w, u.h = (uint8_t)h, u.ref0 = u.ref1 = 255;
+  PlanesDev dr[4] = {}, dorg{};
+  dorg.p[0] = d_org, dorg.s[0] = ww;
+  for (int l = 0; l < 2; l++) {
+    const hmx_pic *rp = l ? ref1 : ref0;
+    const int *mv = l ? mv1 : mv0;
+    if (!rp) continue;
+    dr[l].p[0] = s.up(rp->plane[0] + (ptrdiff_t)(y + (mv[1] >> 2) - 3) * rp->stride[0] + (x + (mv[0] >> 2) - 3), ww, wh, rp->stride[0]);
+    dr[l].s[0] = ww;
+    if (s.r) return s.r;
+    (l ? u.ref1 : u.ref0) = (uint8_t)l;
+    (l ? u.mv1x : u.mv0x) = (int16_t)(mv[0] & 3), (l ? u.mv1y : u.mv0y) = (int16_t)(mv[1] & 3);
+  }
+  const uint32_t first[2] = {0, 1};
+  const int r = pe_launch(c, &u, nullptr, 1, first, 1, dr, 2, dorg, 0, use_had, d_out, d_out + 1, nullptr, weighted ? wpt : nullptr);
+  if (r) return r;
+  HIPCHK(c, hipMemcpyAsync(err, d_out, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return HMX_OK;
+}
+// xGetMvpIdxBits (TEncSearch.cpp:3928-3952); the reference asserts 0 <= idx < num
+extern "C" uint32_t hmx_mvpIdxBits(int idx, int num) {
+  if (num == 1 || idx == 0) return num == 1 ? 0 : 1;
+  return 1 + (uint32_t)(idx - 1) + (num - 1 > idx ? 1 : 0);
+}
+// uiBitsCand of xMergeEstimation (:3133-3137)
+extern "C" uint32_t hmx_mergeIdxBits(int cand, int max_signaled) { return (uint32_t)cand + 1 - (cand == max_signaled - 1 ? 1 : 0); }
+// xCheckBestMVP (:4012-4055): vector bits at cost scale 0 plus m_auiMVPIdxCost[idx][AMVP_MAX_NUM_CANDS] (= xGetMvpIdxBits(idx, 2), :219-227)
+extern "C" int hmx_checkBestMVP(uint32_t lambda, int mvx, int mvy, const int16_t *mvp_cands, int n_cands, int *mvp_idx, uint32_t *bits, uint32_t *cost) {
+  if (!mvp_cands || !mvp_idx || !bits || !cost || n_cands < 0 || n_cands > 2 || *mvp_idx < 0 || (n_cands && *mvp_idx >= n_cands)) return HMX_ERR_ARG;
+  if (n_cands < 2) return HMX_OK;
+  const int cur = *mvp_idx;
+  const int org_bits = (int)(hmx_mvBits(mvx, mvy, mvp_cands[2 * cur], mvp_cands[2 * cur + 1], 0) + hmx_mvpIdxBits(cur, 2));
+  int best_bits = org_bits, best = cur;
+  for (int i = 0; i < n_cands; i++) {
+    if (i == cur) continue;
+    const int b = (int)(hmx_mvBits(mvx, mvy, mvp_cands[2 * i], mvp_cands[2 * i + 1], 0) + hmx_mvpIdxBits(i, 2));
+    if (b < best_bits) best_bits = b, best = i;
+  }
+  if (best != cur) { // UInt arithmetic, wrapping (:4051-4053)
+    const uint32_t org = *bits;
+    *mvp_idx = best;
+    *bits = org - (uint32_t)org_bits + (uint32_t)best_bits;
+    *cost = (*cost - ((lambda * org) >> 16)) + ((lambda * *bits) >> 16);
+  }
+  return HMX_OK;
+}

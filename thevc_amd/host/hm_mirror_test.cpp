@@ -269,7 +269,107 @@ static int calls_main(int argc, char **argv) {
   return 0;
 }
 
+// Usage: hm_mirror_test pred <file>: the complete-candidate members of TEncSearch (xGetInterPredictionError, xMergeEstimation,
+// xGetTemplateCost, the candidate loop of xEstimateMvPredAMVP, xCheckBestMVP) on inputs somebody else made
+// (tests/test_gpu_pred_error.py writes the file and compares with tests/pred_error_oracle.py).  The file is int32 words
+// {bit depth, picture width, height, margin x, margin y, CTU size, HadamardME, m_uiLambdaMotionSAD, number of reference
+// pictures, 1 for a B slice, 1 for a weighted slice, number of operations}, then 16 words {refs[] entry, POC} of reference
+// index 0..3 of list 0, then of list 1, in a weighted slice 3 words {iWeight, iOffset, uiLog2WeightDenom} (luma) per picture for
+// list 0, then for list 1, the pictures' luma planes with margins and the original's luma plane as int16, and per operation:
+//   1 (merge)  {CU x, CU y, unit x, y, width, height, numValidMergeCand}, 5 x 2 x {mv hor, ver, refIdx}, 5 x interDir
+//              prints "M uiInterDir uiMergeIndex ruiCost {mv hor ver refIdx} x 2 err0": uiInterDir and uiMergeIndex start at 99 and
+//              the fields at (0, 0, -1); err0 = xGetInterPredictionError of candidate 0 as xMergeEstimation left it (0 without one)
+//   2 (AMVP)   {CU x, CU y, unit x, y, width, height, list, refIdx, iN}, 2 x {mv hor, ver}
+//              prints "A iBestIdx pred hor ver uiDistBiP cost0": uiDistBiP starts at 4294967295; cost0 = xGetTemplateCost of candidate 0
+//   3 (MVP)    {iN}, 2 x {mv hor, ver}, {cMv hor, ver, riMVPIdx, ruiBits, ruiCost}
+//              prints "C riMVPIdx pred hor ver ruiBits ruiCost"
+static int pred_main(int argc, char **argv) {
+  if (argc < 3) return 2;
+  FILE *f = fopen(argv[2], "rb");
+  if (!f) return 2;
+  int hd[12], tab[16];
+  if (fread(hd, sizeof(int), 12, f) != 12 || fread(tab, sizeof(int), 16, f) != 16) return 2;
+  const int B = hd[0], W = hd[1], H = hd[2], MX = hd[3], MY = hd[4], S = W + 2 * MX, nRefs = hd[8];
+  if (nRefs < 1 || nRefs > 4) return 2;
+  int entry[2][4], poc[2][4];
+  for (int l = 0; l < 2; l++)
+    for (int i = 0; i < 4; i++) entry[l][i] = tab[l * 8 + 2 * i], poc[l][i] = tab[l * 8 + 2 * i + 1];
+  hmx_wp wp[2][4] = {};
+  if (hd[10])
+    for (int l = 0; l < 2; l++)
+      for (int r = 0; r < nRefs; r++) {
+        int e[3];
+        if (fread(e, sizeof(int), 3, f) != 3) return 2;
+        for (int c = 0; c < 3; c++) wp[l][r].weight[c] = 1;
+        wp[l][r].weight[0] = (int16_t)e[0], wp[l][r].offset[0] = (int16_t)e[1], wp[l][r].log2_denom[0] = (uint8_t)e[2];
+      }
+  hmx_hm::Context ctx(B);
+  hmx_hm::TComRdCost rd(ctx);
+  hmx_hm::TEncSearch search(ctx, rd, {W, H, MX, MY, hd[5]}, false, hd[6] != 0, 0);
+  const double root = ((double)(unsigned)hd[7] + 0.5) / 65536.0; // setLambda floors 65536 * sqrt(lambda): aim at the middle of the step
+  rd.setLambda(root * root);
+  if (rd.lambdaMotionSAD() != (unsigned)hd[7]) return 3;
+  std::vector<short> plane((size_t)S * (H + 2 * MY));
+  short *d_ref[4] = {}, *d_org = nullptr;
+  hmx_pic refs[4] = {}, po{};
+  for (int r = 0; r < nRefs; r++) {
+    if (fread(plane.data(), sizeof(short), plane.size(), f) != plane.size()) return 2;
+    ctx.check(hmx_malloc(ctx.get(), plane.size() * 2, (void **)&d_ref[r]), "malloc");
+    ctx.check(hmx_upload(ctx.get(), d_ref[r], plane.data(), plane.size() * 2), "upload");
+    refs[r].plane[0] = d_ref[r] + (size_t)MY * S + MX, refs[r].stride[0] = S;
+  }
+  if (fread(plane.data(), sizeof(short), (size_t)W * H, f) != (size_t)W * H) return 2;
+  ctx.check(hmx_malloc(ctx.get(), (size_t)W * H * 2, (void **)&d_org), "malloc");
+  ctx.check(hmx_upload(ctx.get(), d_org, plane.data(), (size_t)W * H * 2), "upload");
+  po.plane[0] = d_org, po.stride[0] = W;
+  search.setRefLists({refs, nRefs, {entry[0], entry[1]}, {poc[0], poc[1]}, hd[9] != 0, hd[10] ? wp[0] : nullptr, hd[10] ? wp[1] : nullptr});
+  for (int k = 0; k < hd[11]; k++) {
+    int kind, c[42];
+    if (fread(&kind, sizeof(int), 1, f) != 1) return 2;
+    if (kind == 1) {
+      if (fread(c, sizeof(int), 42, f) != 42) return 2;
+      hmx_hm::TComMvField nb[10], out[2];
+      unsigned char dir[5];
+      for (int i = 0; i < 10; i++) nb[i].setMvField(c[7 + 3 * i], c[8 + 3 * i], c[9 + 3 * i]);
+      for (int i = 0; i < 5; i++) dir[i] = (unsigned char)c[37 + i];
+      hmx_hm::UInt interDir = 99, mergeIndex = 99, cost = 0, err0 = 0;
+      search.xMergeEstimation(&po, c[0], c[1], c[2], c[3], c[4], c[5], interDir, out, mergeIndex, cost, nb, dir, c[6]);
+      if (c[6] > 0) search.xGetInterPredictionError(&po, c[0], c[1], c[2], c[3], c[4], c[5], nb, err0, hd[6] != 0);
+      printf("M %u %u %u %d %d %d %d %d %d %u\n", interDir, mergeIndex, cost, out[0].mvHor, out[0].mvVer, out[0].refIdx, out[1].mvHor, out[1].mvVer,
+             out[1].refIdx, err0);
+    } else if (kind == 2) {
+      if (fread(c, sizeof(int), 13, f) != 13) return 2;
+      const int cand[2][2] = {{c[9], c[10]}, {c[11], c[12]}};
+      int pred[2] = {0, 0}, idx = -1;
+      hmx_hm::UInt distBiP = 0xFFFFFFFFu;
+      search.xEstimateMvPredAMVP(&po, c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7], cand, c[8], pred, idx, &distBiP);
+      const hmx_hm::UInt cost0 = search.xGetTemplateCost(&po, c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7], cand[0], 0, hmx_hm::TEncSearch::AMVP_MAX_NUM_CANDS);
+      printf("A %d %d %d %u %u\n", idx, pred[0], pred[1], distBiP, cost0);
+    } else if (kind == 3) {
+      if (fread(c, sizeof(int), 10, f) != 10) return 2;
+      const int cand[2][2] = {{c[1], c[2]}, {c[3], c[4]}}, mv[2] = {c[5], c[6]};
+      int idx = c[7], pred[2] = {c[0] > 0 ? cand[c[7]][0] : 0, c[0] > 0 ? cand[c[7]][1] : 0};
+      hmx_hm::UInt bits = (hmx_hm::UInt)c[8], cost = (hmx_hm::UInt)c[9];
+      search.xCheckBestMVP(cand, c[0], mv, pred, idx, bits, cost);
+      printf("C %d %d %d %u %u\n", idx, pred[0], pred[1], bits, cost);
+    } else
+      return 2;
+  }
+  fclose(f);
+  for (int r = 0; r < nRefs; r++) hmx_free(ctx.get(), d_ref[r]);
+  hmx_free(ctx.get(), d_org);
+  return 0;
+}
+
 int main(int argc, char **argv) {
+  if (argc >= 2 && std::string(argv[1]) == "pred") {
+    try {
+      return pred_main(argc, argv);
+    } catch (const std::exception &e) {
+      fprintf(stderr, "error: %s\n", e.what());
+      return 1;
+    }
+  }
   if (argc >= 2 && (std::string(argv[1]) == "calls" || std::string(argv[1]) == "calls_wp")) {
     try {
       return calls_main(argc, argv);

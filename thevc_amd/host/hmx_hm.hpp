@@ -302,6 +302,7 @@ public:
   UInt getCost(UInt b) const { return (m_uiCost * b) >> 16; }
   UInt getBits(Int x, Int y) const { return hmx_mvBits(x, y, m_iPredHor, m_iPredVer, m_iCostScale); }
   UInt motionCostMultiplier() const { return m_uiCost; }
+  UInt lambdaMotionSAD() const { return m_uiLambdaMotionSAD; } // what calcRdCost(..., DF_SAD) multiplies with (TComRdCost.cpp:70)
   Int predictorHor() const { return m_iPredHor; }
   Int predictorVer() const { return m_iPredVer; }
   // xGetSAD4..64 with DistParam::iSubShift (TComRdCost.cpp:518-...), bApplyWeight false
@@ -353,6 +354,12 @@ private:
   Context &m_c;
 };
 
+// TComMvField (TComMotionInfo.h): a vector in quarter samples and a reference index, < 0 = the list is unused
+struct TComMvField {
+  Int mvHor = 0, mvVer = 0, refIdx = -1;
+  void setMvField(Int hor, Int ver, Int idx) { mvHor = hor, mvVer = ver, refIdx = idx; }
+};
+
 // TEncSearch, xMotionEstimation (TEncSearch.cpp:4120-4514) for ONE unit: the integer stage over hmx_batch_fullpel_search_wp
 // (xPatternSearch) or hmx_batch_tz_search_wp (xPatternSearchFast -> xTZSearch, m_iFastSearch = 1), the fractional stage over
 // hmx_batch_subpel_search_wp -- each with the table setWpScalingDistParam left, or none: the unweighted call.
@@ -367,8 +374,12 @@ public:
       : m_c(c), m_rd(rd), m_g(g), m_fastEnc(useFastEnc), m_useHADME(useHADME), m_iFastSearch(iFastSearch) {
     m_c.check(hmx_malloc(m_c.get(), sizeof(hmx_me_result), (void **)&m_dResult), "TEncSearch");
     m_c.check(hmx_malloc(m_c.get(), sizeof(hmx_subpel_result) + 18 * sizeof(uint32_t), (void **)&m_dFrac), "TEncSearch");
+    m_c.check(hmx_malloc(m_c.get(), sizeof(PredOut), (void **)&m_dPred), "TEncSearch");
+    for (Int iNum = 0; iNum < AMVP_MAX_NUM_CANDS + 1; iNum++) // :219-227
+      for (Int iIdx = 0; iIdx < AMVP_MAX_NUM_CANDS; iIdx++) m_auiMVPIdxCost[iIdx][iNum] = iIdx < iNum ? xGetMvpIdxBits(iIdx, iNum) : (UInt)0x7FFFFFFF;
   }
   ~TEncSearch() {
+    hmx_free(m_c.get(), m_dPred);
     hmx_free(m_c.get(), m_dResult);
     hmx_free(m_c.get(), m_dFrac);
   }
@@ -505,8 +516,165 @@ public:
     ruiCost = (UInt)(std::floor(fWeight * ((Double)ruiCost - (Double)m_rd.getCost(uiMvBits))) + (Double)m_rd.getCost(ruiBits));
   }
 
+  // ---- complete candidates: xGetInterPredictionError and the loops around it, over hmx_batch_inter_pred_error_wp ----
+  static const Int AMVP_MAX_NUM_CANDS = 2, MRG_MAX_NUM_CANDS = 5, MRG_MAX_NUM_CANDS_SIGNALED = 5;
+  // What motionCompensation reads through the slice: per list, for every reference index, the picture (an entry of `refs`, DEVICE
+  // pictures with margins, at most four) and its POC; whether the slice is B; and the weighted-prediction tables when the PPS has
+  // getUseWP() (P slice: wpL0) / getWPBiPred() (B slice: wpL0 and wpL1), indexed like `refs` as hmx_mc_wp documents, else NULL.
+  struct RefLists {
+    const hmx_pic *refs;
+    Int numRefs;
+    const Int *entry[2]; // [list][refIdx] -> index into refs
+    const Int *poc[2];   // [list][refIdx] -> getRefPic(list, refIdx)->getPOC()
+    Bool isInterB;
+    const hmx_wp *wpL0, *wpL1;
+  };
+  void setRefLists(const RefLists &r) { m_refs = r; }
+  // xGetMvpIdxBits (:3928-3952)
+  static UInt xGetMvpIdxBits(Int iIdx, Int iNum) { return hmx_mvpIdxBits(iIdx, iNum); }
+  // xGetInterPredictionError (:3059-3081): motionCompensation(REF_PIC_LIST_X) of the unit with the motion in cMvField[2], then the
+  // unweighted Hadamard (bHadamard) or SAD against the original.  (cuX, cuY): the origin of the unit's coding unit, which
+  // xPredInterUni clips the vectors against (:487).
+  void xGetInterPredictionError(const hmx_pic *pcOrg, Int cuX, Int cuY, Int x, Int y, Int iWidth, Int iHeight, const TComMvField cMvField[2],
+                                UInt &ruiErr, Bool bHadamard) {
+    hmx_pu u = candidate(cuX, cuY, x, y, iWidth, iHeight, cMvField);
+    predError(pcOrg, &u, nullptr, 1, false, 0, bHadamard, sliceWp());
+    ruiErr = m_out.dist[0];
+  }
+  // xRestrictBipredMergeCand (:3159-3172); isBipredRestriction: an 8x4 or 4x8 unit of an 8x8 coding unit
+  static void xRestrictBipredMergeCand(Int iWidth, Int iHeight, TComMvField *mvFieldNeighbours, unsigned char *interDirNeighbours, Int numValidMergeCand) {
+    if (iWidth + iHeight != 12) return;
+    for (Int mergeCand = 0; mergeCand < numValidMergeCand; ++mergeCand)
+      if (interDirNeighbours[mergeCand] == 3) {
+        interDirNeighbours[mergeCand] = 1;
+        mvFieldNeighbours[(mergeCand << 1) + 1].setMvField(0, 0, -1);
+      }
+  }
+  // xMergeEstimation (:3096-3149) behind getInterMergeCandidates, which walks the CU tree and stays with the caller: the candidate
+  // list (cMvFieldNeighbours[2 * cand + list], uhInterDirNeighbours, numValidMergeCand) comes in, is restricted for 8x4 / 4x8,
+  // and ALL candidates are costed and compared in one device call.  uiInterDir, pacMvField and uiMergeIndex are written only
+  // when a candidate's cost gets below MAX_UINT, as in the reference.
+  void xMergeEstimation(const hmx_pic *pcOrg, Int cuX, Int cuY, Int x, Int y, Int iWidth, Int iHeight, UInt &uiInterDir, TComMvField pacMvField[2],
+                        UInt &uiMergeIndex, UInt &ruiCost, TComMvField *cMvFieldNeighbours, unsigned char *uhInterDirNeighbours, Int numValidMergeCand) {
+    xRestrictBipredMergeCand(iWidth, iHeight, cMvFieldNeighbours, uhInterDirNeighbours, numValidMergeCand);
+    ruiCost = 0xFFFFFFFFu;
+    if (numValidMergeCand <= 0) return;
+    if (numValidMergeCand > MRG_MAX_NUM_CANDS) throw std::runtime_error("xMergeEstimation: more than MRG_MAX_NUM_CANDS candidates");
+    hmx_pu u[MRG_MAX_NUM_CANDS];
+    uint32_t bits[MRG_MAX_NUM_CANDS];
+    for (Int c = 0; c < numValidMergeCand; c++) {
+      u[c] = candidate(cuX, cuY, x, y, iWidth, iHeight, cMvFieldNeighbours + 2 * c);
+      bits[c] = hmx_mergeIdxBits(c, MRG_MAX_NUM_CANDS_SIGNALED);
+    }
+    m_rd.getMotionCost(true, 0);
+    predError(pcOrg, u, bits, numValidMergeCand, true, m_rd.motionCostMultiplier(), m_useHADME, sliceWp());
+    if (m_out.best.index == 0xFFFFFFFFu) return;
+    ruiCost = m_out.best.cost;
+    uiMergeIndex = m_out.best.index;
+    pacMvField[0] = cMvFieldNeighbours[0 + 2 * uiMergeIndex];
+    pacMvField[1] = cMvFieldNeighbours[1 + 2 * uiMergeIndex];
+    uiInterDir = uhInterDirNeighbours[uiMergeIndex];
+  }
+  // xGetTemplateCost (:4057-4118) as this reference compiles it (ZERO_MVD_EST 0): the candidate vector clipped, the luma
+  // prediction from (eRefPicList, iRefIdx) -- weighted uni-directionally only in a P slice with getUseWP() (:4081-4093) --, the
+  // SAD whatever UseHADME says (:4111-4115), and the bits through calcRdCost(..., DF_SAD): (Int)(bits * lambdaMotionSAD + .5) >> 16,
+  // which is getCost(UInt) while the product stays below 2^31; a larger one is refused.
+  UInt xGetTemplateCost(const hmx_pic *pcOrg, Int cuX, Int cuY, Int x, Int y, Int iSizeX, Int iSizeY, Int eRefPicList, Int iRefIdx, const Int cMvCand[2],
+                        Int iMVPIdx, Int iMVPNum) {
+    TComMvField f[2];
+    f[eRefPicList].setMvField(cMvCand[0], cMvCand[1], iRefIdx);
+    hmx_pu u = candidate(cuX, cuY, x, y, iSizeX, iSizeY, f);
+    const uint32_t bits = templateBits(iMVPIdx, iMVPNum);
+    predError(pcOrg, &u, &bits, 1, false, m_rd.lambdaMotionSAD(), false, templateWp());
+    return m_out.cost[0];
+  }
+  // The candidate loop of xEstimateMvPredAMVP (:3893-3924) for AM_EXPL with an unfilled list: every candidate of pcAMVPInfo
+  // (iN vectors of m_acMvCand) through xGetTemplateCost in ONE device call, then the reference's own comparison -- uiBestCost
+  // starts at MAX_INT with iBestIdx = 0, so it is made here from the costs and not by the library, whose best starts at MAX_UINT.
+  // rcMvPred / riMVPIdx: the winner; *puiDistBiP as the reference leaves it (untouched when no cost is below MAX_INT).
+  void xEstimateMvPredAMVP(const hmx_pic *pcOrg, Int cuX, Int cuY, Int x, Int y, Int iRoiWidth, Int iRoiHeight, Int eRefPicList, Int iRefIdx,
+                           const Int (*m_acMvCand)[2], Int iN, Int rcMvPred[2], Int &riMVPIdx, UInt *puiDistBiP) {
+    if (iN < 1 || iN > AMVP_MAX_NUM_CANDS) throw std::runtime_error("xEstimateMvPredAMVP: 1 .. AMVP_MAX_NUM_CANDS candidates");
+    hmx_pu u[AMVP_MAX_NUM_CANDS];
+    uint32_t bits[AMVP_MAX_NUM_CANDS];
+    for (Int i = 0; i < iN; i++) {
+      TComMvField f[2];
+      f[eRefPicList].setMvField(m_acMvCand[i][0], m_acMvCand[i][1], iRefIdx);
+      u[i] = candidate(cuX, cuY, x, y, iRoiWidth, iRoiHeight, f);
+      bits[i] = templateBits(i, AMVP_MAX_NUM_CANDS);
+    }
+    predError(pcOrg, u, bits, iN, false, m_rd.lambdaMotionSAD(), false, templateWp());
+    UInt uiBestCost = 0x7FFFFFFF;
+    Int iBestIdx = 0;
+    for (Int i = 0; i < iN; i++)
+      if (uiBestCost > m_out.cost[i]) {
+        uiBestCost = m_out.cost[i];
+        iBestIdx = i;
+        *puiDistBiP = m_out.cost[i];
+      }
+    rcMvPred[0] = m_acMvCand[iBestIdx][0], rcMvPred[1] = m_acMvCand[iBestIdx][1];
+    riMVPIdx = iBestIdx;
+  }
+  // xCheckBestMVP (:4012-4055): cMv the vector found, the AMVP list, rcMvPred / riMVPIdx the predictor the search ran with
+  void xCheckBestMVP(const Int (*m_acMvCand)[2], Int iN, const Int cMv[2], Int rcMvPred[2], Int &riMVPIdx, UInt &ruiBits, UInt &ruiCost) {
+    int16_t c[AMVP_MAX_NUM_CANDS][2];
+    if (iN < 0 || iN > AMVP_MAX_NUM_CANDS) throw std::runtime_error("xCheckBestMVP: at most AMVP_MAX_NUM_CANDS candidates");
+    for (Int i = 0; i < iN; i++) c[i][0] = (int16_t)m_acMvCand[i][0], c[i][1] = (int16_t)m_acMvCand[i][1];
+    m_rd.getMotionCost(true, 0);
+    m_rd.setCostScale(0);
+    uint32_t b = ruiBits, k = ruiCost;
+    if (hmx_checkBestMVP(m_rd.motionCostMultiplier(), cMv[0], cMv[1], &c[0][0], iN, &riMVPIdx, &b, &k) != HMX_OK)
+      throw std::runtime_error("xCheckBestMVP: the predictor index lies outside the list");
+    ruiBits = b, ruiCost = k;
+    if (iN >= 2) rcMvPred[0] = m_acMvCand[riMVPIdx][0], rcMvPred[1] = m_acMvCand[riMVPIdx][1];
+  }
+
 private:
   const hmx_wp *wpCur() const { return m_bApplyWeight ? &m_wpCur : nullptr; } // the one-entry table of refs[0]
+  struct PredOut {
+    uint32_t dist[MRG_MAX_NUM_CANDS], cost[MRG_MAX_NUM_CANDS];
+    hmx_pred_choice best;
+  };
+  // the tables motionCompensation(REF_PIC_LIST_X) weights with (TComPrediction.cpp:528-535), and xGetTemplateCost's (:4081-4093)
+  hmx_mc_wp sliceWp() const { return hmx_mc_wp{m_refs.wpL0, m_refs.isInterB ? m_refs.wpL1 : nullptr}; }
+  hmx_mc_wp templateWp() const { return hmx_mc_wp{m_refs.isInterB ? nullptr : m_refs.wpL0, nullptr}; }
+  uint32_t templateBits(Int iMVPIdx, Int iMVPNum) const {
+    const uint32_t bits = m_auiMVPIdxCost[iMVPIdx][iMVPNum];
+    if ((unsigned long long)bits * m_rd.lambdaMotionSAD() >= (1ull << 31))
+      throw std::runtime_error("xGetTemplateCost: lambda * bits reaches 2^31, where calcRdCost(DF_SAD) and getCost(UInt) part");
+    return bits;
+  }
+  // One candidate in the library's form: the vectors clipped for the coding unit (xPredInterUni, :487), the lists mapped to refs[],
+  // and the identical-motion shortcut (xCheckIdenticalMotion, :392-407: B slice without WPBiPred, both lists, equal POCs, equal
+  // UNCLIPPED vectors) resolved to list 0 alone.
+  hmx_pu candidate(Int cuX, Int cuY, Int x, Int y, Int w, Int h, const TComMvField f[2]) const {
+    hmx_pu u{};
+    u.x = (uint16_t)x, u.y = (uint16_t)y, u.w = (uint8_t)w, u.h = (uint8_t)h, u.ref0 = u.ref1 = 255;
+    Bool use[2] = {f[0].refIdx >= 0, f[1].refIdx >= 0};
+    if (use[0] && use[1] && m_refs.isInterB && !(m_refs.wpL0 || m_refs.wpL1) && m_refs.poc[0][f[0].refIdx] == m_refs.poc[1][f[1].refIdx] &&
+        f[0].mvHor == f[1].mvHor && f[0].mvVer == f[1].mvVer)
+      use[1] = false;
+    for (Int l = 0; l < 2; l++) {
+      if (!use[l]) continue;
+      int mx = f[l].mvHor, my = f[l].mvVer;
+      hmx_clipMv(&mx, &my, cuX, cuY, m_g.picWidth, m_g.picHeight, m_g.ctuSize);
+      (l ? u.ref1 : u.ref0) = (uint8_t)m_refs.entry[l][f[l].refIdx];
+      (l ? u.mv1x : u.mv0x) = (int16_t)mx, (l ? u.mv1y : u.mv0y) = (int16_t)my;
+    }
+    return u;
+  }
+  void predError(const hmx_pic *pcOrg, const hmx_pu *u, const uint32_t *bits, Int n, Bool decide, UInt lambda, Bool bHadamard, const hmx_mc_wp &wp) {
+    const uint32_t first[2] = {0, (uint32_t)n};
+    m_c.check(hmx_batch_inter_pred_error_wp(m_c.get(), u, bits, n, decide ? first : nullptr, decide ? 1 : 0, m_refs.refs, m_refs.numRefs, pcOrg,
+                                            m_g.picWidth, m_g.picHeight, m_g.marginX, m_g.marginY, lambda, bHadamard ? 1 : 0, m_dPred->dist, m_dPred->cost,
+                                            decide ? &m_dPred->best : nullptr, &wp),
+              "xGetInterPredictionError");
+    m_c.check(hmx_download(m_c.get(), &m_out, m_dPred, sizeof(m_out)), "xGetInterPredictionError");
+  }
+  RefLists m_refs{};
+  UInt m_auiMVPIdxCost[AMVP_MAX_NUM_CANDS][AMVP_MAX_NUM_CANDS + 1];
+  PredOut *m_dPred = nullptr;
+  PredOut m_out{};
   Context &m_c;
   TComRdCost &m_rd;
   Geometry m_g;
