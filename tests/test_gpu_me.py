@@ -235,17 +235,18 @@ def test_workload_units(ctx, textured):
 def test_host_validation(ctx, textured):
     good = unit(64, 32, 16, 16, 0, 0, 0, 0, -4, -4, 4, 4)
 
-    def bad(msg, **kw):
-        u = good.copy()
+    def bad(msg, n=1, **kw):
+        u = np.concatenate([good] * n)  # the last of n units is the bad one
         for k, v in kw.items():
-            u[0][k] = v
+            u[n - 1][k] = v
         sentinel = np.full(3, 0x5A5A5A5A, np.uint32)
         d_res = ctx.to_device(sentinel)
         ref_arr = (capi.Pic * 2)(*[r.as_pic() for r in textured.refs])
-        rc = capi.lib().hmx_batch_fullpel_search(ctx.h, u.ctypes.data, 1, ref_arr, 2, C.byref(textured.org.as_pic()), W, H, M, M, 0,
+        rc = capi.lib().hmx_batch_fullpel_search(ctx.h, u.ctypes.data, n, ref_arr, 2, C.byref(textured.org.as_pic()), W, H, M, M, 0,
                                                  d_res.ptr, None)
         assert rc == -1, (msg, rc)  # HMX_ERR_ARG
         assert msg in capi.lib().hmx_last_error(ctx.h).decode(), (msg, capi.lib().hmx_last_error(ctx.h).decode())
+        assert f"unit {n - 1}: " in capi.lib().hmx_last_error(ctx.h).decode()  # the unit is named
         ctx.sync()
         assert np.array_equal(d_res.download(np.uint32), sentinel), msg  # nothing was launched
         d_res.free()
@@ -265,6 +266,7 @@ def test_host_validation(ctx, textured):
     bad("outside the reference's margins", x=W - 16, right=M + 1)
     bad("outside the reference's margins", y=0, top=-M - 1)
     bad("outside the reference's margins", y=H - 16, bottom=M + 1)
+    bad("sub_shift", n=3, sub_shift=2)  # only unit 2 of three is bad: the prefix names it
     # the margins themselves are legal, and the context still works
     edge = np.concatenate([unit(0, 0, 16, 16, 0, 0, 0, 0, -M, -M, -M + 3, -M + 3), unit(W - 16, H - 16, 16, 16, 1, 1, 0, 0, M - 2, M - 2, M, M), good])
     textured.check(edge, 99999, "after refused calls")

@@ -268,6 +268,11 @@ def test_refusals_and_sentinel(ctx, textured):
     bad("outside the reference's margins", x=W - 16, right=M - 3)
     bad("outside the reference's margins", y=0, top=-M + 3)
     bad("outside the reference's margins", y=H - 16, bottom=M - 3)
+    three = np.concatenate([good] * 3)  # only the last of three is bad: the prefix names it
+    three[2]["bottom"] = M - 3
+    three[2]["y"] = H - 16
+    refused("outside the reference's margins", three, n=3)
+    assert "unit 2: " in L.hmx_last_error(ctx.h).decode()
     d_int.free()
     d_res.free()
     # sub_shift is ignored, the margin's last sample is legal, and the context still works; then the same call with the vector of

@@ -295,6 +295,10 @@ def test_host_validation(ctx, staged):
     bad("outside the reference's margins", x=W - 16, right=M + 1)
     bad("outside the reference's margins", y=0, top=-M - 1)
     bad("outside the reference's margins", y=H - 16, bottom=M + 1)
+    u3, z3 = np.concatenate([good_u] * 3), np.concatenate([good_z] * 3)  # only the last of three is bad: the prefix names it
+    u3[2]["w"] = 20
+    call("width and height", units=u3, tz=z3, n=3, named=False)
+    assert "unit 2: " in L.hmx_last_error(ctx.h).decode()
     call("null argument", units=None, named=False)
     call("null argument", tz=None, named=False)
     call("null argument", refs=None, named=False)

@@ -462,6 +462,59 @@ inline int me_wp_table(hmx_ctx *c, const char *entry, const hmx_wp *wp, int n_re
                                       "]: weight outside -128..255, offset outside -128..127, log2_denom above 7 or reserved not 0");
   return HMX_OK;
 }
+// ---- what the entries over unit and candidate lists share: the three searches, the sub-pel fan-out, the prediction error ----
+inline bool me_size_ok(int v) { return v == 4 || v == 8 || v == 12 || v == 16 || v == 24 || v == 32 || v == 48 || v == 64; }
+// The call-level checks, refused under the entry's name: null_arg is the entry's own pointer test (it is reported first, and
+// nothing is dereferenced before it), then n, n_refs, the picture, the luma planes and, for wp != NULL, the table of a _wp entry
+// into out[] (me_wp_table).
+inline int me_call_check(hmx_ctx *c, const char *entry, bool null_arg, int n, const hmx_pic *refs, int n_refs, const hmx_pic *org, int pic_w, int pic_h,
+                         int margin_x, int margin_y, const hmx_wp *wp, MeWp *out) {
+  const char *why = nullptr;
+  if (null_arg) why = ": null argument";
+  else if (n <= 0) why = ": n must be at least 1";
+  else if (n_refs <= 0 || n_refs > 4) why = ": n_refs must be 1 .. 4";
+  else if (pic_w <= 0 || pic_h <= 0 || margin_x < 0 || margin_y < 0) why = ": picture size must be positive and margins not negative";
+  else if (!org->plane[0]) why = ": the original has no luma plane";
+  else
+    for (int r = 0; r < n_refs; r++)
+      if (!refs[r].plane[0]) why = ": a reference has no luma plane";
+  if (why) return fail(c, HMX_ERR_ARG, std::string(entry) + why);
+  return wp ? me_wp_table(c, entry, wp, n_refs, out) : HMX_OK;
+}
+// One hmx_me_unit against the call: the tail of the refusal, or NULL.  boxed: the search walks the box (sub_shift is honoured, and
+// a side is at most 129 = search range 64); the sub-pel refinement only needs the box to hold the integer vector.
+inline const char *me_unit_check(const hmx_me_unit &u, int n_refs, int pic_w, int pic_h, bool boxed) {
+  if (!me_size_ok(u.w) || !me_size_ok(u.h)) return "width and height come from {4, 8, 12, 16, 24, 32, 48, 64}";
+  if (u.ref >= n_refs) return "reference index outside refs[]";
+  if (boxed && (u.sub_shift > 1 || (u.sub_shift && u.h <= 8))) return "sub_shift is 0, or 1 with more than 8 rows";
+  if (u.right < u.left || u.bottom < u.top) return "empty search box";
+  if (boxed && (u.right - u.left + 1 > 129 || u.bottom - u.top + 1 > 129)) return "search box side above 129 (search range 64)";
+  if (u.x + u.w > pic_w || u.y + u.h > pic_h) return "the unit lies outside the picture";
+  return nullptr;
+}
+// the margin test, a unit's last: the unit's block displaced by every vector of [l, r] x [t, b] lies inside the reference's margins
+inline bool me_reach_ok(const hmx_me_unit &u, int l, int t, int r, int b, int pic_w, int pic_h, int margin_x, int margin_y) {
+  return u.x + l >= -margin_x && u.x + r + u.w <= pic_w + margin_x && u.y + t >= -margin_y && u.y + b + u.h <= pic_h + margin_y;
+}
+inline int me_unit_refuse(hmx_ctx *c, const char *entry, int i, const char *why) { // the text is built only here
+  return fail(c, HMX_ERR_ARG, std::string(entry) + ": unit " + std::to_string(i) + ": " + why);
+}
+// The launch tail.  The kernels are templates over their argument type and the weighted struct derives from the plain one, so that
+// the unweighted instantiation keeps the argument block it had before the weighted one existed: launch(A) as ARGSWP or as PLAIN.
+template <class PLAIN, class ARGSWP, typename F>
+inline void launch_plain_or_wp(bool weighted, const ARGSWP &A, F &&launch) {
+  if (weighted) launch(A);
+  else launch(static_cast<const PLAIN &>(A));
+}
+// the same for the searches' structs, with the fields they share filled first: refs[], org, B and the table me_call_check made
+template <class PLAIN, class ARGSWP, typename F>
+inline void me_launch(const hmx_ctx *c, ARGSWP &A, const hmx_pic *refs, int n_refs, const hmx_pic *org, bool weighted, const MeWp *wpt, F &&launch) {
+  for (int r = 0; r < n_refs; r++) A.refs[r] = to_dev(&refs[r]);
+  A.org = to_dev(org);
+  A.B = c->cfg.bit_depth;
+  for (int r = 0; r < 4; r++) A.wp[r] = wpt[r];
+  launch_plain_or_wp<PLAIN>(weighted, A, launch);
+}
 
 // ---- scalar drop-ins: one block through the batch kernels (host pointers in and out) ----
 struct Scratch { // carve the context's device scratch (the budget: head of this file); the first failure sticks in r

@@ -263,30 +263,7 @@ __global__ __launch_bounds__(64) void k_subpel_cost(ARGS A) {
       else d[r * 8 + c] = org[(size_t)r * A.org.s[0] + c] - v;
     }
   }
-  int sum = 0;
-  if (!A.use_had) {
-    for (int r = 0; r < n; r++)
-      for (int c = 0; c < n; c++) sum += abs(d[r * 8 + c]);
-  } else if (n == 8) {
-    for (int r = 0; r < 8; r++) wht_regs<8>(d + r * 8);
-    for (int c = 0; c < 8; c++) {
-      int col[8];
-      for (int r = 0; r < 8; r++) col[r] = d[r * 8 + c];
-      wht_regs<8>(col);
-      for (int r = 0; r < 8; r++) sum += abs(col[r]);
-    }
-    sum = (sum + 2) >> 2;
-  } else {
-    for (int r = 0; r < 4; r++) wht_regs<4>(d + r * 8);
-    for (int c = 0; c < 4; c++) {
-      int col[4];
-      for (int r = 0; r < 4; r++) col[r] = d[r * 8 + c];
-      wht_regs<4>(col);
-      for (int r = 0; r < 4; r++) sum += abs(col[r]);
-    }
-    sum = (sum + 1) >> 1;
-  }
-  atomicAdd(&A.cost[(size_t)lo * A.n_cand + cand], (unsigned)sum);
+  atomicAdd(&A.cost[(size_t)lo * A.n_cand + cand], (unsigned)subblock_dist(d, n, A.use_had != 0));
 }
 __global__ void k_shift_u32(uint32_t *v, size_t n, int sh) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -294,26 +271,22 @@ __global__ void k_shift_u32(uint32_t *v, size_t n, int sh) {
 }
 static int subpel_cost(hmx_ctx *c, const char *name, const hmx_pu *pus, int n, const hmx_pic *refs, int n_refs, const hmx_pic *org, const int8_t *offs,
                        int n_cand, int use_had, uint32_t *d_cost, const hmx_wp *wp) {
-  const std::string nm = name;
   if (!c || !pus || n <= 0 || !refs || n_refs <= 0 || n_refs > 4 || !org || !offs || n_cand <= 0 || n_cand > 49 || !d_cost)
-    return fail(c, HMX_ERR_ARG, nm + ": bad argument");
+    return fail(c, HMX_ERR_ARG, std::string(name) + ": bad argument");
   MeWp wpt[4] = {};
-  if (wp) {
-    const int wr = me_wp_table(c, name, wp, n_refs, wpt);
-    if (wr) return wr;
-  }
+  if (wp)
+    if (const int r = me_wp_table(c, name, wp, n_refs, wpt)) return r;
   std::vector<uint32_t> first((size_t)n + 1, 0);
   for (int i = 0; i < n; i++) {
     const int w = pus[i].w, h = pus[i].h;
     if (w <= 0 || h <= 0 || w > 64 || h > 64 || ((w | h) & 3) || pus[i].ref0 >= n_refs || ((pus[i].mv0x | pus[i].mv0y) & 3))
-      return fail(c, HMX_ERR_ARG, nm + ": unit size not a multiple of 4, reference index, or a vector that is not integer");
+      return fail(c, HMX_ERR_ARG, std::string(name) + ": unit size not a multiple of 4, reference index, or a vector that is not integer");
     const int nb = (w % 8 == 0 && h % 8 == 0) ? 8 : 4;
     first[i + 1] = first[i] + (uint32_t)((w / nb) * (h / nb));
   }
   for (int k = 0; k < 2 * n_cand; k++)
-    if (offs[k] < -3 || offs[k] > 3) return fail(c, HMX_ERR_ARG, nm + ": candidate further than 3 quarter samples");
+    if (offs[k] < -3 || offs[k] > 3) return fail(c, HMX_ERR_ARG, std::string(name) + ": candidate further than 3 quarter samples");
   SubpelArgsWp A{};
-  for (int r = 0; r < 4; r++) A.wp[r] = wpt[r];
   const size_t pu_bytes = sizeof(hmx_pu) * (size_t)n, first_bytes = sizeof(uint32_t) * ((size_t)n + 1);
   // unit list and prefix through the argument arena (they are the caller's host arrays)
   A.pus = static_cast<const hmx_pu *>(arena_push(c, pus, pu_bytes));
@@ -321,15 +294,13 @@ static int subpel_cost(hmx_ctx *c, const char *name, const hmx_pu *pus, int n, c
   A.offs = static_cast<const signed char *>(arena_push(c, offs, (size_t)2 * n_cand));
   if (!A.pus || !A.first || !A.offs) return fail(c, HMX_ERR_NOMEM, "argument arena (unit list too long: split the call)");
   A.n = n;
-  for (int r = 0; r < n_refs; r++) A.refs[r] = to_dev(&refs[r]);
-  A.org = to_dev(org);
   A.n_cand = n_cand;
   A.use_had = use_had;
-  A.B = c->cfg.bit_depth;
   A.cost = d_cost;
   HIPCHK(c, hipMemsetAsync(d_cost, 0, sizeof(uint32_t) * (size_t)n * n_cand, c->stream));
-  if (wp) hipLaunchKernelGGL(k_subpel_cost<SubpelArgsWp>, dim3((first[n] + 63) / 64, (unsigned)n_cand), dim3(64), 0, c->stream, A);
-  else hipLaunchKernelGGL(k_subpel_cost<SubpelArgs>, dim3((first[n] + 63) / 64, (unsigned)n_cand), dim3(64), 0, c->stream, static_cast<const SubpelArgs &>(A));
+  me_launch<SubpelArgs>(c, A, refs, n_refs, org, wp != nullptr, wpt, [&](const auto &a) {
+    hipLaunchKernelGGL(k_subpel_cost<std::decay_t<decltype(a)>>, dim3((first[n] + 63) / 64, (unsigned)n_cand), dim3(64), 0, c->stream, a);
+  });
   if (c->cfg.bit_depth > 8) // xGetHADs / xGetSAD return uiSum >> g_uiBitIncrement
     hipLaunchKernelGGL(k_shift_u32, dim3((unsigned)(((size_t)n * n_cand + 255) / 256)), dim3(256), 0, c->stream, d_cost, (size_t)n * n_cand, c->cfg.bit_depth - 8);
   HIPCHK(c, hipGetLastError());
@@ -1017,21 +988,7 @@ __device__ __forceinline__ void pe_cost_pass(const short *src, int pitch, bool v
     const short *o = org + sy * w + sx;
 #pragma unroll
     for (int r = 0; r < S; r++) d[r] = o[r * w] - d[r];
-    if (use_had) { // the 2-D transform's sum of magnitudes: down the column here, then across the S lanes (as sp_stage, hmx_me.hip)
-      wht_regs<S>(d);
-#pragma unroll
-      for (int m = 1; m < S; m <<= 1)
-#pragma unroll
-        for (int r = 0; r < S; r++) {
-          const int other = __shfl_xor(d[r], m, 64);
-          d[r] = (lane & m) ? other - d[r] : d[r] + other;
-        }
-    }
-    int sum = 0;
-#pragma unroll
-    for (int r = 0; r < S; r++) sum += abs(d[r]);
-    sum = group_sum(sum, S);
-    if (use_had) sum = S == 8 ? (sum + 2) >> 2 : (sum + 1) >> 1; // rounded per sub-block (TComRdCost.cpp:2083, :1991)
+    const int sum = subblock_dist_lanes<S>(d, lane, use_had);
     if (act && lane == 0) atomicAdd(s_sum, (unsigned)sum);
   }
 }
@@ -1118,7 +1075,6 @@ __global__ __launch_bounds__(kPeThreads) void k_pred_error(ARGS A) {
   if (tid == 0 && A.best) A.best[grp] = best;
 }
 
-static bool pe_size_ok(int v) { return v == 4 || v == 8 || v == 12 || v == 16 || v == 24 || v == 32 || v == 48 || v == 64; }
 // the launch: every argument has been checked; first (host): n_groups + 1 prefix entries
 static int pe_launch(hmx_ctx *c, const hmx_pu *cands, const uint32_t *bits, int n, const uint32_t *first, int n_groups, const PlanesDev *refs, int n_refs,
                      const PlanesDev &org, uint32_t lambda, int use_had, uint32_t *d_dist, uint32_t *d_cost, hmx_pred_choice *d_best, const PeWp (*wp)[2]) {
@@ -1138,49 +1094,43 @@ static int pe_launch(hmx_ctx *c, const hmx_pu *cands, const uint32_t *bits, int 
   A.org = org;
   A.B = c->cfg.bit_depth, A.use_had = use_had, A.lambda = lambda;
   A.dist = d_dist, A.cost = d_cost, A.best = d_best;
-  if (wp) {
-    memcpy(A.wp, wp, sizeof(A.wp));
-    hipLaunchKernelGGL(k_pred_error<PeArgsWp>, dim3((unsigned)n_groups), dim3(threads), lds, c->stream, A);
-  } else {
-    hipLaunchKernelGGL(k_pred_error<PeArgs>, dim3((unsigned)n_groups), dim3(threads), lds, c->stream, static_cast<const PeArgs &>(A));
-  }
+  if (wp) memcpy(A.wp, wp, sizeof(A.wp));
+  launch_plain_or_wp<PeArgs>(wp != nullptr, A, [&](const auto &a) {
+    hipLaunchKernelGGL(k_pred_error<std::decay_t<decltype(a)>>, dim3((unsigned)n_groups), dim3(threads), lds, c->stream, a);
+  });
   HIPCHK(c, hipGetLastError());
   return HMX_OK;
 }
 static int pred_error(hmx_ctx *c, const char *name, const hmx_pu *cands, const uint32_t *bits, int n, const uint32_t *group_first, int n_groups,
                       const hmx_pic *refs, int n_refs, const hmx_pic *org, int pic_w, int pic_h, int margin_x, int margin_y, uint32_t lambda, int use_had,
                       uint32_t *d_dist, uint32_t *d_cost, hmx_pred_choice *d_best, const hmx_mc_wp *wp) {
-  const std::string nm = name;
-  if (!c || !cands || !refs || !org || !d_dist || !d_cost) return fail(c, HMX_ERR_ARG, nm + ": null argument");
-  if (n <= 0) return fail(c, HMX_ERR_ARG, nm + ": n must be at least 1");
-  if (n_refs <= 0 || n_refs > 4) return fail(c, HMX_ERR_ARG, nm + ": n_refs must be 1 .. 4");
-  if (use_had != 0 && use_had != 1) return fail(c, HMX_ERR_ARG, nm + ": use_had is 0 or 1");
+  // the tables of this entry are per list (hmx_mc_wp) and go through wp_entry below, not through the searches' table
+  if (const int r = me_call_check(c, name, !c || !cands || !refs || !org || !d_dist || !d_cost, n, refs, n_refs, org, pic_w, pic_h, margin_x, margin_y, nullptr,
+                                  nullptr))
+    return r;
+  const auto nm = [name] { return std::string(name); }; // refusals only
+  if (use_had != 0 && use_had != 1) return fail(c, HMX_ERR_ARG, nm() + ": use_had is 0 or 1");
   if (n_groups < 0 || (n_groups == 0) != (group_first == nullptr) || (n_groups == 0) != (d_best == nullptr))
-    return fail(c, HMX_ERR_ARG, nm + ": group_first, n_groups and d_best are given together (groups) or NULL, 0, NULL (costs only)");
-  if (pic_w <= 0 || pic_h <= 0 || margin_x < 0 || margin_y < 0)
-    return fail(c, HMX_ERR_ARG, nm + ": picture size must be positive and margins not negative");
-  if (!org->plane[0]) return fail(c, HMX_ERR_ARG, nm + ": the original has no luma plane");
-  for (int r = 0; r < n_refs; r++)
-    if (!refs[r].plane[0]) return fail(c, HMX_ERR_ARG, nm + ": a reference has no luma plane");
+    return fail(c, HMX_ERR_ARG, nm() + ": group_first, n_groups and d_best are given together (groups) or NULL, 0, NULL (costs only)");
   const bool weighted = wp && (wp->l0 || wp->l1);
   PeWp wpt[4][2] = {};
   if (weighted) {
-    if (!wp->l0) return fail(c, HMX_ERR_ARG, nm + ": a weighted call needs the list 0 table (l0 NULL, l1 not)");
+    if (!wp->l0) return fail(c, HMX_ERR_ARG, nm() + ": a weighted call needs the list 0 table (l0 NULL, l1 not)");
     const hmx_wp unit = {{1, 1, 1}, {0, 0, 0}, {0, 0, 0}, 0}; // a missing list 1 table holds the unit weight
     for (int r = 0; r < n_refs; r++)
       for (int l = 0; l < 2; l++) {
         const hmx_wp *t = l ? wp->l1 : wp->l0;
         WpDev e;
         if (!wp_entry(t ? t[r] : unit, c->cfg.bit_depth, &e))
-          return fail(c, HMX_ERR_ARG, nm + ": wp list " + std::to_string(l) + " row " + std::to_string(r) +
+          return fail(c, HMX_ERR_ARG, nm() + ": wp list " + std::to_string(l) + " row " + std::to_string(r) +
                                           ": weight outside -128..255, offset outside -128..127 or log2_denom > 7");
         wpt[r][l] = PeWp{e.w[0], e.o[0], e.d[0]};
       }
   }
   for (int i = 0; i < n; i++) {
     const hmx_pu &u = cands[i];
-    auto refuse = [&](const std::string &why) { return fail(c, HMX_ERR_ARG, nm + ": candidate " + std::to_string(i) + ": " + why); }; // text only when refused
-    if (!pe_size_ok(u.w) || !pe_size_ok(u.h)) return refuse("width and height come from {4, 8, 12, 16, 24, 32, 48, 64}");
+    auto refuse = [&](const std::string &why) { return fail(c, HMX_ERR_ARG, nm() + ": candidate " + std::to_string(i) + ": " + why); }; // text only when refused
+    if (!me_size_ok(u.w) || !me_size_ok(u.h)) return refuse("width and height come from {4, 8, 12, 16, 24, 32, 48, 64}");
     if (u.ref0 == 255 && u.ref1 == 255) return refuse("no list is used");
     if (u.x + u.w > pic_w || u.y + u.h > pic_h) return refuse("the unit lies outside the picture");
     for (int l = 0; l < 2; l++) {
@@ -1198,16 +1148,16 @@ static int pred_error(hmx_ctx *c, const char *name, const hmx_pu *cands, const u
     for (int i = 0; i <= n; i++) ones[i] = (uint32_t)i;
     group_first = ones.data();
   } else {
-    if (group_first[0] != 0) return fail(c, HMX_ERR_ARG, nm + ": group 0: group_first[0] must be 0");
+    if (group_first[0] != 0) return fail(c, HMX_ERR_ARG, nm() + ": group 0: group_first[0] must be 0");
     for (int g = 0; g < n_groups; g++) // the prefix first: the geometry pass below indexes cands[] with it
       if (group_first[g + 1] < group_first[g] || group_first[g + 1] > (uint32_t)n)
-        return fail(c, HMX_ERR_ARG, nm + ": group " + std::to_string(g) + ": group_first is not monotonic or passes n");
-    if (group_first[n_groups] != (uint32_t)n) return fail(c, HMX_ERR_ARG, nm + ": group " + std::to_string(n_groups - 1) + ": group_first does not end at n");
+        return fail(c, HMX_ERR_ARG, nm() + ": group " + std::to_string(g) + ": group_first is not monotonic or passes n");
+    if (group_first[n_groups] != (uint32_t)n) return fail(c, HMX_ERR_ARG, nm() + ": group " + std::to_string(n_groups - 1) + ": group_first does not end at n");
     for (int g = 0; g < n_groups; g++)
       for (uint32_t i = group_first[g] + 1; i < group_first[g + 1]; i++) {
         const hmx_pu &a = cands[group_first[g]], &b = cands[i];
         if (a.x != b.x || a.y != b.y || a.w != b.w || a.h != b.h)
-          return fail(c, HMX_ERR_ARG, nm + ": group " + std::to_string(g) + ": its candidates differ in x, y, w or h");
+          return fail(c, HMX_ERR_ARG, nm() + ": group " + std::to_string(g) + ": its candidates differ in x, y, w or h");
       }
   }
   PlanesDev dr[4] = {};
@@ -1236,7 +1186,7 @@ extern "C" int hmx_getInterPredictionError(hmx_ctx *c, const hmx_pic *ref0, cons
   if (!c || !org || !err || (!ref0 && !ref1) || (ref0 && !mv0) || (ref1 && !mv1)) return fail(c, HMX_ERR_ARG, nm + ": null argument, or no list is used");
   if ((ref0 && !ref0->plane[0]) || (ref1 && !ref1->plane[0])) return fail(c, HMX_ERR_ARG, nm + ": a reference has no luma plane");
   if (use_had != 0 && use_had != 1) return fail(c, HMX_ERR_ARG, nm + ": use_had is 0 or 1");
-  if (!pe_size_ok(w) || !pe_size_ok(h)) return fail(c, HMX_ERR_ARG, nm + ": width and height come from {4, 8, 12, 16, 24, 32, 48, 64}");
+  if (!me_size_ok(w) || !me_size_ok(h)) return fail(c, HMX_ERR_ARG, nm + ": width and height come from {4, 8, 12, 16, 24, 32, 48, 64}");
   const bool weighted = wp0 || wp1;
   if (weighted && ((ref0 && !wp0) || (ref1 && !wp1))) return fail(c, HMX_ERR_ARG, nm + ": a weighted call needs the entry of every used list");
   PeWp wpt[4][2] = {};

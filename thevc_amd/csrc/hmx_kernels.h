@@ -651,6 +651,51 @@ __device__ __forceinline__ void wht_regs(int *v) {
         v[j + half] = a - b;
       }
 }
+// The distortion of ONE S x S sub-block (S = 8, or 4 when a side of the block is no multiple of 8: xGetHADs, TComRdCost.cpp:2186-2283)
+// of differences org - pred: its SAD, or (use_had) the sum of magnitudes of its 2-D Hadamard transform, rounded per sub-block as
+// xCalcHADs8x8 and xCalcHADs4x4 round it: (sum + 2) >> 2 (TComRdCost.cpp:2083) and (sum + 1) >> 1 (:1991).  Their butterflies are
+// sums and differences only, and a sum of magnitudes does not depend on the order or signs of the transform's rows, so the plain
+// Walsh-Hadamard steps of wht_regs suffice.  Two layouts:
+// one thread holds the sub-block, d[8 * r + c] (the pitch is 8 for both sides); d is overwritten
+template <int S>
+__device__ __forceinline__ int subblock_dist(int *d, bool use_had) {
+  int sum = 0;
+  if (!use_had) {
+    for (int r = 0; r < S; r++)
+      for (int c = 0; c < S; c++) sum += abs(d[r * 8 + c]);
+    return sum;
+  }
+  for (int r = 0; r < S; r++) wht_regs<S>(d + r * 8);
+  for (int c = 0; c < S; c++) {
+    int col[S];
+    for (int r = 0; r < S; r++) col[r] = d[r * 8 + c];
+    wht_regs<S>(col);
+    for (int r = 0; r < S; r++) sum += abs(col[r]);
+  }
+  return S == 8 ? (sum + 2) >> 2 : (sum + 1) >> 1;
+}
+__device__ __forceinline__ int subblock_dist(int *d, int n, bool use_had) { return n == 8 ? subblock_dist<8>(d, use_had) : subblock_dist<4>(d, use_had); }
+// S consecutive lanes hold the sub-block, lane `lane` of the S its column in d[]: the transform runs down the column in registers
+// and across the S lanes by lane exchange; every lane of the group returns the sub-block's value; d is overwritten
+template <int S>
+__device__ __forceinline__ int subblock_dist_lanes(int (&d)[S], int lane, int use_had) {
+  if (use_had) {
+    wht_regs<S>(d);
+#pragma unroll
+    for (int m = 1; m < S; m <<= 1)
+#pragma unroll
+      for (int r = 0; r < S; r++) {
+        const int other = __shfl_xor(d[r], m, 64);
+        d[r] = (lane & m) ? other - d[r] : d[r] + other;
+      }
+  }
+  int s = 0;
+#pragma unroll
+  for (int r = 0; r < S; r++) s += abs(d[r]);
+  s = group_sum(s, S);
+  if (use_had) s = S == 8 ? (s + 2) >> 2 : (s + 1) >> 1;
+  return s;
+}
 // The weighted sample of the motion search's distortions (TComRdCostWeightPrediction.cpp:93, :213 ...): getWpScaling's
 // uni-directional branch (TComWeightPrediction.cpp:302-312) for luma, pred = (Pel)(((w0 * c + round) >> shift) + offset) -- the
 // product in Int, the assignment to Pel wraps to 16 bits, no clip.

@@ -34,8 +34,6 @@ extern "C" void hmx_setSearchRange(int pred_x, int pred_y, int range, int cu_x, 
   *left = lx >> 2, *top = ty >> 2, *right = rx >> 2, *bottom = by >> 2;
 }
 
-static bool me_size_ok(int v) { return v == 4 || v == 8 || v == 12 || v == 16 || v == 24 || v == 32 || v == 48 || v == 64; }
-
 // =============================================================================================
 // xGetSAD4 .. xGetSAD64 (TComRdCost.cpp:518-..., dispatch :298-329) of ONE block, host pointers
 // =============================================================================================
@@ -67,11 +65,10 @@ extern "C" int hmx_getSAD(hmx_ctx *c, const hmx_pel *cur, int cur_stride, const 
 // =============================================================================================
 // TComRdCostWeightPrediction::xGetSADw (TComRdCostWeightPrediction.cpp:69-104) and xGetHADsw (:490-561) of ONE block, host pointers
 // =============================================================================================
-// xGetHADsw read against sp_stage: xCalcHADs4x4w (:204-302) and xCalcHADs8x8w (:311-423) form diff = org - pred with pred a Pel
-// (the weighted sample wrapped to 16 bits), then run the butterflies of xCalcHADs4x4 / xCalcHADs8x8 unchanged -- sums and
-// differences only, so the sum of magnitudes is that of the plain Walsh-Hadamard steps of wht_regs -- and round per sub-block
-// with (satd + 1) >> 1 and (sad + 2) >> 2, as the unweighted functions do; xGetHADsw picks 8x8 when both sides are multiples of
-// 8, else 4x4 (:516-545), and returns uiSum >> g_uiBitIncrement (:560).  Only the difference changes.
+// xGetHADsw read against subblock_dist (hmx_kernels.h): xCalcHADs4x4w (:204-302) and xCalcHADs8x8w (:311-423) form diff = org - pred
+// with pred a Pel (the weighted sample wrapped to 16 bits), then run the butterflies of xCalcHADs4x4 / xCalcHADs8x8 unchanged and
+// round per sub-block with (satd + 1) >> 1 and (sad + 2) >> 2, as the unweighted functions do; xGetHADsw picks 8x8 when both sides
+// are multiples of 8, else 4x4 (:516-545), and returns uiSum >> g_uiBitIncrement (:560).  Only the difference changes.
 __global__ void k_dist_w(const short *org, const short *cur, int w, int h, MeWp p, int hads, unsigned *out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (!hads) { // one thread per row: every row, whatever iSubShift says
@@ -87,27 +84,7 @@ __global__ void k_dist_w(const short *org, const short *cur, int w, int h, MeWp 
   int d[64];
   for (int r = 0; r < n; r++)
     for (int k = 0; k < n; k++) d[r * 8 + k] = o[r * w + k] - me_wp_pel(p, c[r * w + k]);
-  int sum = 0;
-  if (n == 8) {
-    for (int r = 0; r < 8; r++) wht_regs<8>(d + r * 8);
-    for (int k = 0; k < 8; k++) {
-      int col[8];
-      for (int r = 0; r < 8; r++) col[r] = d[r * 8 + k];
-      wht_regs<8>(col);
-      for (int r = 0; r < 8; r++) sum += abs(col[r]);
-    }
-    sum = (sum + 2) >> 2;
-  } else {
-    for (int r = 0; r < 4; r++) wht_regs<4>(d + r * 8);
-    for (int k = 0; k < 4; k++) {
-      int col[4];
-      for (int r = 0; r < 4; r++) col[r] = d[r * 8 + k];
-      wht_regs<4>(col);
-      for (int r = 0; r < 4; r++) sum += abs(col[r]);
-    }
-    sum = (sum + 1) >> 1;
-  }
-  atomicAdd(out, (unsigned)sum);
+  atomicAdd(out, (unsigned)subblock_dist(d, n, true));
 }
 static int dist_w(hmx_ctx *c, const char *name, const hmx_pel *cur, int cur_stride, const hmx_pel *org, int org_stride, int w, int h, int weight,
                   int offset, int log2_denom, int hads, uint32_t *out) {
@@ -305,45 +282,27 @@ __global__ void k_me_unpack(const hmx_me_unit *units, const unsigned long long *
 // the four searches' entries: `name` is the entry the caller used (refusals are made under it), wp == NULL the unweighted call
 static int me_fullpel(hmx_ctx *c, const char *name, const hmx_me_unit *units, int n, const hmx_pic *refs, int n_refs, const hmx_pic *org, int pic_w,
                       int pic_h, int margin_x, int margin_y, uint32_t lambda, hmx_me_result *d_result, uint32_t *d_cost_map, const hmx_wp *wp) {
-  const std::string nm = name;
-  if (!c || !units || !refs || !org || !d_result) return fail(c, HMX_ERR_ARG, nm + ": null argument");
-  if (n <= 0) return fail(c, HMX_ERR_ARG, nm + ": n must be at least 1");
-  if (n_refs <= 0 || n_refs > 4) return fail(c, HMX_ERR_ARG, nm + ": n_refs must be 1 .. 4");
-  if (pic_w <= 0 || pic_h <= 0 || margin_x < 0 || margin_y < 0)
-    return fail(c, HMX_ERR_ARG, nm + ": picture size must be positive and margins not negative");
-  if (!org->plane[0]) return fail(c, HMX_ERR_ARG, nm + ": the original has no luma plane");
-  for (int r = 0; r < n_refs; r++)
-    if (!refs[r].plane[0]) return fail(c, HMX_ERR_ARG, nm + ": a reference has no luma plane");
   MeWp wpt[4] = {};
-  if (wp) {
-    const int wr = me_wp_table(c, name, wp, n_refs, wpt);
-    if (wr) return wr;
-  }
+  if (const int r = me_call_check(c, name, !c || !units || !refs || !org || !d_result, n, refs, n_refs, org, pic_w, pic_h, margin_x, margin_y, wp, wpt)) return r;
   std::vector<uint32_t> tile_first((size_t)n + 1, 0), map_first((size_t)n + 1, 0);
   uint64_t area = 0; // the kernel's offsets into the cost map are 32-bit
   for (int i = 0; i < n; i++) {
     const hmx_me_unit &u = units[i];
-    const std::string at = nm + ": unit " + std::to_string(i) + ": ";
-    if (!me_size_ok(u.w) || !me_size_ok(u.h)) return fail(c, HMX_ERR_ARG, at + "width and height come from {4, 8, 12, 16, 24, 32, 48, 64}");
-    if (u.ref >= n_refs) return fail(c, HMX_ERR_ARG, at + "reference index outside refs[]");
-    if (u.sub_shift > 1 || (u.sub_shift && u.h <= 8)) return fail(c, HMX_ERR_ARG, at + "sub_shift is 0, or 1 with more than 8 rows");
-    if (u.right < u.left || u.bottom < u.top) return fail(c, HMX_ERR_ARG, at + "empty search box");
+    const char *why = me_unit_check(u, n_refs, pic_w, pic_h, true);
+    if (!why && !me_reach_ok(u, u.left, u.top, u.right, u.bottom, pic_w, pic_h, margin_x, margin_y))
+      why = "a candidate block reaches outside the reference's margins";
+    if (why) return me_unit_refuse(c, name, i, why);
     const int bw = u.right - u.left + 1, bh = u.bottom - u.top + 1;
-    if (bw > 129 || bh > 129) return fail(c, HMX_ERR_ARG, at + "search box side above 129 (search range 64)");
-    if (u.x + u.w > pic_w || u.y + u.h > pic_h) return fail(c, HMX_ERR_ARG, at + "the unit lies outside the picture");
-    if (u.x + u.left < -margin_x || u.x + u.right + u.w > pic_w + margin_x || u.y + u.top < -margin_y || u.y + u.bottom + u.h > pic_h + margin_y)
-      return fail(c, HMX_ERR_ARG, at + "a candidate block reaches outside the reference's margins");
     tile_first[i + 1] = tile_first[i] + (uint32_t)(((bw + kMeTile - 1) / kMeTile) * ((bh + kMeTile - 1) / kMeTile));
     map_first[i + 1] = map_first[i] + (uint32_t)(bw * bh);
     area += (uint64_t)(bw * bh);
   }
-  if (area > 0xffffffffull) return fail(c, HMX_ERR_ARG, nm + ": the boxes hold more than 2^32 - 1 candidates: split the call");
+  if (area > 0xffffffffull) return fail(c, HMX_ERR_ARG, std::string(name) + ": the boxes hold more than 2^32 - 1 candidates: split the call");
   void *keys = c->d_me_keys;
   const int gr = grow_dev(c, &keys, &c->me_keys_cap, sizeof(unsigned long long) * (size_t)n);
   c->d_me_keys = static_cast<unsigned long long *>(keys);
   if (gr) return gr;
   MeArgsWp A{};
-  for (int r = 0; r < 4; r++) A.wp[r] = wpt[r];
   const size_t prefix_bytes = sizeof(uint32_t) * ((size_t)n + 1);
   // unit list and prefixes through the argument arena (the caller's host array, and tables made from it)
   A.units = static_cast<const hmx_me_unit *>(arena_push(c, units, sizeof(hmx_me_unit) * (size_t)n));
@@ -351,15 +310,13 @@ static int me_fullpel(hmx_ctx *c, const char *name, const hmx_me_unit *units, in
   A.map_first = static_cast<const uint32_t *>(arena_push(c, map_first.data(), prefix_bytes));
   if (!A.units || !A.tile_first || !A.map_first) return fail(c, HMX_ERR_NOMEM, "argument arena (unit list too long: split the call)");
   A.n = n;
-  for (int r = 0; r < n_refs; r++) A.refs[r] = to_dev(&refs[r]);
-  A.org = to_dev(org);
-  A.B = c->cfg.bit_depth;
   A.lambda = lambda;
   A.keys = c->d_me_keys;
   A.cost_map = d_cost_map;
   HIPCHK(c, hipMemsetAsync(c->d_me_keys, 0xff, sizeof(unsigned long long) * (size_t)n, c->stream));
-  if (wp) hipLaunchKernelGGL(k_me_search<MeArgsWp>, dim3(tile_first[n]), dim3(kMeThreads), 0, c->stream, A);
-  else hipLaunchKernelGGL(k_me_search<MeArgs>, dim3(tile_first[n]), dim3(kMeThreads), 0, c->stream, static_cast<const MeArgs &>(A));
+  me_launch<MeArgs>(c, A, refs, n_refs, org, wp != nullptr, wpt, [&](const auto &a) {
+    hipLaunchKernelGGL(k_me_search<std::decay_t<decltype(a)>>, dim3(tile_first[n]), dim3(kMeThreads), 0, c->stream, a);
+  });
   hipLaunchKernelGGL(k_me_unpack, dim3((n + 255) / 256), dim3(256), 0, c->stream, A.units, (const unsigned long long *)c->d_me_keys, n, lambda, d_result);
   HIPCHK(c, hipGetLastError());
   return HMX_OK;
@@ -504,21 +461,7 @@ __device__ __forceinline__ void sp_stage(const SpLds &L, int stage, int hx, int 
       if constexpr (WP) d[r] = o[r * w] - me_wp_pel(*wp, clip3(0, maxv, wrap16((sum + offset) >> shift)));
       else d[r] = o[r * w] - clip3(0, maxv, wrap16((sum + offset) >> shift));
     }
-    int s = 0;
-    if (use_had) { // the sum of magnitudes of the 2-D transform: down the column here, then across the S lanes
-      wht_regs<S>(d);
-#pragma unroll
-      for (int m = 1; m < S; m <<= 1)
-#pragma unroll
-        for (int r = 0; r < S; r++) {
-          const int other = __shfl_xor(d[r], m, 64);
-          d[r] = (lane & m) ? other - d[r] : d[r] + other;
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < S; r++) s += abs(d[r]);
-    s = group_sum(s, S);
-    if (use_had) s = S == 8 ? (s + 2) >> 2 : (s + 1) >> 1; // rounded per sub-block (TComRdCost.cpp:2083, :1991)
+    const int s = subblock_dist_lanes<S>(d, lane, use_had);
     if (act && lane == 0) atomicAdd(&s_cost[k], (unsigned)s);
   }
 }
@@ -626,49 +569,31 @@ __global__ __launch_bounds__(kSpThreads) void k_subpel_search(ARGS A) {
 static int me_subpel(hmx_ctx *c, const char *name, const hmx_me_unit *units, int n, const hmx_me_result *d_int, const hmx_pic *refs, int n_refs,
                      const hmx_pic *org, int pic_w, int pic_h, int margin_x, int margin_y, uint32_t lambda, int use_had,
                      hmx_subpel_result *d_result, uint32_t *d_stage_cost, const hmx_wp *wp) {
-  const std::string nm = name;
-  if (!c || !units || !d_int || !refs || !org || !d_result) return fail(c, HMX_ERR_ARG, nm + ": null argument");
-  if (n <= 0) return fail(c, HMX_ERR_ARG, nm + ": n must be at least 1");
-  if (n_refs <= 0 || n_refs > 4) return fail(c, HMX_ERR_ARG, nm + ": n_refs must be 1 .. 4");
-  if (use_had != 0 && use_had != 1) return fail(c, HMX_ERR_ARG, nm + ": use_had is 0 or 1");
-  if (pic_w <= 0 || pic_h <= 0 || margin_x < 0 || margin_y < 0)
-    return fail(c, HMX_ERR_ARG, nm + ": picture size must be positive and margins not negative");
-  if (!org->plane[0]) return fail(c, HMX_ERR_ARG, nm + ": the original has no luma plane");
-  for (int r = 0; r < n_refs; r++)
-    if (!refs[r].plane[0]) return fail(c, HMX_ERR_ARG, nm + ": a reference has no luma plane");
   MeWp wpt[4] = {};
-  if (wp) {
-    const int wr = me_wp_table(c, name, wp, n_refs, wpt);
-    if (wr) return wr;
-  }
+  if (const int r = me_call_check(c, name, !c || !units || !d_int || !refs || !org || !d_result, n, refs, n_refs, org, pic_w, pic_h, margin_x, margin_y, wp, wpt))
+    return r;
+  if (use_had != 0 && use_had != 1) return fail(c, HMX_ERR_ARG, std::string(name) + ": use_had is 0 or 1");
   size_t lds = 0;
   for (int i = 0; i < n; i++) {
     const hmx_me_unit &u = units[i];
-    const std::string at = nm + ": unit " + std::to_string(i) + ": ";
-    if (!me_size_ok(u.w) || !me_size_ok(u.h)) return fail(c, HMX_ERR_ARG, at + "width and height come from {4, 8, 12, 16, 24, 32, 48, 64}");
-    if (u.ref >= n_refs) return fail(c, HMX_ERR_ARG, at + "reference index outside refs[]");
-    if (u.right < u.left || u.bottom < u.top) return fail(c, HMX_ERR_ARG, at + "empty search box");
-    if (u.x + u.w > pic_w || u.y + u.h > pic_h) return fail(c, HMX_ERR_ARG, at + "the unit lies outside the picture");
+    const char *why = me_unit_check(u, n_refs, pic_w, pic_h, false);
     // the window of every integer vector of the box: columns x + left - 4 .. x + right + w + 3, rows likewise
-    if (u.x + u.left - 4 < -margin_x || u.x + u.right + u.w + 4 > pic_w + margin_x || u.y + u.top - 4 < -margin_y ||
-        u.y + u.bottom + u.h + 4 > pic_h + margin_y)
-      return fail(c, HMX_ERR_ARG, at + "the interpolation window of a vector of the box reaches outside the reference's margins");
+    if (!why && !me_reach_ok(u, u.left - 4, u.top - 4, u.right + 4, u.bottom + 4, pic_w, pic_h, margin_x, margin_y))
+      why = "the interpolation window of a vector of the box reaches outside the reference's margins";
+    if (why) return me_unit_refuse(c, name, i, why);
     lds = std::max(lds, sp_lds_bytes(u.w, u.h));
   }
   SpArgsWp A{};
-  for (int r = 0; r < 4; r++) A.wp[r] = wpt[r];
   A.units = static_cast<const hmx_me_unit *>(arena_push(c, units, sizeof(hmx_me_unit) * (size_t)n)); // the caller's host array
   if (!A.units) return fail(c, HMX_ERR_NOMEM, "argument arena (unit list too long: split the call)");
   A.ints = d_int;
-  for (int r = 0; r < n_refs; r++) A.refs[r] = to_dev(&refs[r]);
-  A.org = to_dev(org);
-  A.B = c->cfg.bit_depth;
   A.use_had = use_had;
   A.lambda = lambda;
   A.result = d_result;
   A.stage_cost = d_stage_cost;
-  if (wp) hipLaunchKernelGGL(k_subpel_search<SpArgsWp>, dim3((unsigned)n), dim3(kSpThreads), lds, c->stream, A);
-  else hipLaunchKernelGGL(k_subpel_search<SpArgs>, dim3((unsigned)n), dim3(kSpThreads), lds, c->stream, static_cast<const SpArgs &>(A));
+  me_launch<SpArgs>(c, A, refs, n_refs, org, wp != nullptr, wpt, [&](const auto &a) {
+    hipLaunchKernelGGL(k_subpel_search<std::decay_t<decltype(a)>>, dim3((unsigned)n), dim3(kSpThreads), lds, c->stream, a);
+  });
   HIPCHK(c, hipGetLastError());
   return HMX_OK;
 }
@@ -933,59 +858,41 @@ __global__ __launch_bounds__(kTzThreads) void k_tz_search(ARGS A) {
 static int me_tz(hmx_ctx *c, const char *name, const hmx_me_unit *units, const hmx_tz_unit *tz, int n, const hmx_pic *refs, int n_refs,
                  const hmx_pic *org, int pic_w, int pic_h, int margin_x, int margin_y, uint32_t lambda, hmx_me_result *d_result,
                  hmx_tz_point *d_trace, uint32_t *d_trace_count, int trace_cap, const hmx_wp *wp) {
-  const std::string nm = name;
-  if (!c || !units || !tz || !refs || !org || !d_result) return fail(c, HMX_ERR_ARG, nm + ": null argument");
-  if ((d_trace == nullptr) != (d_trace_count == nullptr)) return fail(c, HMX_ERR_ARG, nm + ": d_trace and d_trace_count go together");
-  if (d_trace && trace_cap < 1) return fail(c, HMX_ERR_ARG, nm + ": trace_cap must be at least 1");
-  if (n <= 0) return fail(c, HMX_ERR_ARG, nm + ": n must be at least 1");
-  if (n_refs <= 0 || n_refs > 4) return fail(c, HMX_ERR_ARG, nm + ": n_refs must be 1 .. 4");
-  if (pic_w <= 0 || pic_h <= 0 || margin_x < 0 || margin_y < 0)
-    return fail(c, HMX_ERR_ARG, nm + ": picture size must be positive and margins not negative");
-  if (!org->plane[0]) return fail(c, HMX_ERR_ARG, nm + ": the original has no luma plane");
-  for (int r = 0; r < n_refs; r++)
-    if (!refs[r].plane[0]) return fail(c, HMX_ERR_ARG, nm + ": a reference has no luma plane");
   MeWp wpt[4] = {};
-  if (wp) {
-    const int wr = me_wp_table(c, name, wp, n_refs, wpt);
-    if (wr) return wr;
-  }
+  if (const int r = me_call_check(c, name, !c || !units || !tz || !refs || !org || !d_result, n, refs, n_refs, org, pic_w, pic_h, margin_x, margin_y, wp, wpt))
+    return r;
+  if ((d_trace == nullptr) != (d_trace_count == nullptr)) return fail(c, HMX_ERR_ARG, std::string(name) + ": d_trace and d_trace_count go together");
+  if (d_trace && trace_cap < 1) return fail(c, HMX_ERR_ARG, std::string(name) + ": trace_cap must be at least 1");
   size_t lds = 0;
   for (int i = 0; i < n; i++) {
     const hmx_me_unit &u = units[i];
     const hmx_tz_unit &z = tz[i];
-    const std::string at = nm + ": unit " + std::to_string(i) + ": ";
-    if (!me_size_ok(u.w) || !me_size_ok(u.h)) return fail(c, HMX_ERR_ARG, at + "width and height come from {4, 8, 12, 16, 24, 32, 48, 64}");
-    if (u.ref >= n_refs) return fail(c, HMX_ERR_ARG, at + "reference index outside refs[]");
-    if (u.sub_shift > 1 || (u.sub_shift && u.h <= 8)) return fail(c, HMX_ERR_ARG, at + "sub_shift is 0, or 1 with more than 8 rows");
-    if (u.right < u.left || u.bottom < u.top) return fail(c, HMX_ERR_ARG, at + "empty search box");
-    if (u.right - u.left + 1 > 129 || u.bottom - u.top + 1 > 129) return fail(c, HMX_ERR_ARG, at + "search box side above 129 (search range 64)");
-    if (u.x + u.w > pic_w || u.y + u.h > pic_h) return fail(c, HMX_ERR_ARG, at + "the unit lies outside the picture");
-    if (z.range < 1 || z.range > 64) return fail(c, HMX_ERR_ARG, at + "range must be 1 .. 64");
-    if (z.reserved != 0) return fail(c, HMX_ERR_ARG, at + "reserved must be 0");
-    if (z.start_x < u.left || z.start_x > u.right || z.start_y < u.top || z.start_y > u.bottom)
-      return fail(c, HMX_ERR_ARG, at + "the start point lies outside the search box");
+    const char *why = me_unit_check(u, n_refs, pic_w, pic_h, true);
     // every evaluated point lies in the bounding rectangle of box U {(0, 0)}: the zero vector is evaluated unconditionally
     const int rl = std::min<int>(u.left, 0), rr = std::max<int>(u.right, 0), rt = std::min<int>(u.top, 0), rb = std::max<int>(u.bottom, 0);
-    if (u.x + rl < -margin_x || u.x + rr + u.w > pic_w + margin_x || u.y + rt < -margin_y || u.y + rb + u.h > pic_h + margin_y)
-      return fail(c, HMX_ERR_ARG, at + "a block of the box or the zero vector's rectangle reaches outside the reference's margins");
+    if (!why)
+      why = z.range < 1 || z.range > 64 ? "range must be 1 .. 64"
+            : z.reserved != 0           ? "reserved must be 0"
+            : z.start_x < u.left || z.start_x > u.right || z.start_y < u.top || z.start_y > u.bottom ? "the start point lies outside the search box"
+            : !me_reach_ok(u, rl, rt, rr, rb, pic_w, pic_h, margin_x, margin_y)
+                ? "a block of the box or the zero vector's rectangle reaches outside the reference's margins"
+                : nullptr;
+    if (why) return me_unit_refuse(c, name, i, why);
     lds = std::max(lds, sizeof(short) * (size_t)u.w * (size_t)u.h);
   }
   TzArgsWp A{};
-  for (int r = 0; r < 4; r++) A.wp[r] = wpt[r];
   A.units = static_cast<const hmx_me_unit *>(arena_push(c, units, sizeof(hmx_me_unit) * (size_t)n)); // the caller's host arrays
   A.tz = static_cast<const hmx_tz_unit *>(arena_push(c, tz, sizeof(hmx_tz_unit) * (size_t)n));
   if (!A.units || !A.tz) return fail(c, HMX_ERR_NOMEM, "argument arena (unit list too long: split the call)");
-  for (int r = 0; r < n_refs; r++) A.refs[r] = to_dev(&refs[r]);
-  A.org = to_dev(org);
-  A.B = c->cfg.bit_depth;
   A.max_passes = std::min(kTzPassCap, std::max(1, c->knob.tz_max_passes));
   A.lambda = lambda;
   A.result = d_result;
   A.trace = d_trace;
   A.trace_count = d_trace_count;
   A.trace_cap = d_trace ? trace_cap : 0;
-  if (wp) hipLaunchKernelGGL(k_tz_search<TzArgsWp>, dim3((unsigned)n), dim3(kTzThreads), lds, c->stream, A);
-  else hipLaunchKernelGGL(k_tz_search<TzArgs>, dim3((unsigned)n), dim3(kTzThreads), lds, c->stream, static_cast<const TzArgs &>(A));
+  me_launch<TzArgs>(c, A, refs, n_refs, org, wp != nullptr, wpt, [&](const auto &a) {
+    hipLaunchKernelGGL(k_tz_search<std::decay_t<decltype(a)>>, dim3((unsigned)n), dim3(kTzThreads), lds, c->stream, a);
+  });
   HIPCHK(c, hipGetLastError());
   return HMX_OK;
 }

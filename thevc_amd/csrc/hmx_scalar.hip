@@ -739,27 +739,7 @@ __global__ void k_dist(const short *org, int so, const short *cur, int sc, int w
     int d[64];
     for (int r = 0; r < n; r++)
       for (int k = 0; k < n; k++) d[r * 8 + k] = o[r * so + k] - c[r * sc + k];
-    int sum = 0;
-    if (n == 8) {
-      for (int r = 0; r < 8; r++) wht_regs<8>(d + r * 8);
-      for (int k = 0; k < 8; k++) {
-        int col[8];
-        for (int r = 0; r < 8; r++) col[r] = d[r * 8 + k];
-        wht_regs<8>(col);
-        for (int r = 0; r < 8; r++) sum += abs(col[r]);
-      }
-      sum = (sum + 2) >> 2;
-    } else {
-      for (int r = 0; r < 4; r++) wht_regs<4>(d + r * 8);
-      for (int k = 0; k < 4; k++) {
-        int col[4];
-        for (int r = 0; r < 4; r++) col[r] = d[r * 8 + k];
-        wht_regs<4>(col);
-        for (int r = 0; r < 4; r++) sum += abs(col[r]);
-      }
-      sum = (sum + 1) >> 1;
-    }
-    atomicAdd(out, (unsigned)sum);
+    atomicAdd(out, (unsigned)subblock_dist(d, n, true));
   } else {
     if (i >= h) return;
     unsigned sum = 0;
