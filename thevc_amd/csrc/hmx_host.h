@@ -447,10 +447,15 @@ struct PackArgs;
 int packed_rdoq_max_blocks(int *nb);
 void launch_packed_rdoq(const PackArgs &A, bool sse, unsigned n_wg, hipStream_t st);
 
-// the luma entry of one hmx_wp in the searches' device form (setWpScalingDistParam, TEncSearch.cpp:6183-6215 -> getWpScaling's
+// the ranges hmx_wp documents for one component of an entry, whichever way it arrives
+inline bool wp_range_ok(int weight, int offset, int log2_denom) {
+  return weight >= -128 && weight <= 255 && offset >= -128 && offset <= 127 && log2_denom >= 0 && log2_denom <= 7;
+}
+// one component in the form the prediction weights take (WpEntry, hmx_kernels.h): the offset goes to the bit depth (getWpScaling :286-312)
+inline WpEntry wp_entry_make(int weight, int offset, int log2_denom, int B) { return WpEntry{(short)weight, (short)(offset * (1 << (B - 8))), log2_denom}; }// the luma entry of one hmx_wp in the searches' device form (setWpScalingDistParam, TEncSearch.cpp:6183-6215 -> getWpScaling's
 // uni-directional branch): false = outside the ranges hmx_wp documents
 inline bool me_wp_make(int weight, int offset, int log2_denom, int reserved, int B, MeWp *out) {
-  if (weight < -128 || weight > 255 || offset < -128 || offset > 127 || log2_denom < 0 || log2_denom > 7 || reserved != 0) return false;
+  if (!wp_range_ok(weight, offset, log2_denom) || reserved != 0) return false;
   out->w0 = weight, out->shift = log2_denom, out->round = log2_denom ? 1 << (log2_denom - 1) : 0, out->offset = offset * (1 << (B - 8));
   return true;
 }

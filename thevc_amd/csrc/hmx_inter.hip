@@ -4,42 +4,24 @@
 // =============================================================================================
 // Interpolation (TComInterpolationFilter.cpp), addAvg, motion compensation, border extension
 // =============================================================================================
-__device__ __forceinline__ int luma_tap(int frac, int t) {
-  constexpr signed char k[4][8] = {{0, 0, 0, 64, 0, 0, 0, 0}, {-1, 4, -10, 58, 17, -5, 1, 0}, {-1, 4, -11, 40, 40, -11, 4, -1},
-                                   {0, 1, -5, 17, 58, -10, 4, -1}};
-  return k[frac][t];
+// filterCopy (:91-145) of one sample, the reference's three cases as it writes them
+__device__ __forceinline__ int interp_copy(int v, bool first, bool last, int B) {
+  const int head = 14 - B;
+  if (first == last) return v;
+  if (first) return wrap16(wrap16(v << head) - 8192);
+  int off = wrap16(8192 + (head ? (1 << (head - 1)) : 0));
+  return clip3(0, (1 << B) - 1, wrap16((v + off) >> head));
 }
-__device__ __forceinline__ int chroma_tap(int frac, int t) {
-  constexpr signed char k[8][4] = {{0, 64, 0, 0},   {-2, 58, 10, -2}, {-4, 54, 16, -2}, {-6, 46, 28, -4},
-                                   {-4, 36, 36, -4}, {-4, 28, 46, -6}, {-2, 16, 54, -4}, {-2, 10, 58, -2}};
-  return k[frac][t];
-}
-
-// One output sample of filterHor*/filterVer* incl. the frac == 0 filterCopy cases (:91-244).
-// src points at the sample co-located with the output; step = 1 (horizontal) or the stride.
+// One output sample of filterHor*/filterVer* incl. the frac == 0 filterCopy cases (:91-244): the drop-in for the reference's
+// function, first == last included.  src points at the sample co-located with the output; step = 1 (horizontal) or the stride.
 template <int NTAP>
 __device__ __forceinline__ int interp_sample(const short *src, int step, int frac, bool first, bool last, int B) {
-  const int head = 14 - B, maxv = (1 << B) - 1;
-  if (frac == 0) {
-    int v = src[0];
-    if (first == last) return v;
-    if (first) return wrap16(wrap16(v << head) - 8192);
-    int off = wrap16(8192 + (head ? (1 << (head - 1)) : 0));
-    return clip3(0, maxv, wrap16((v + off) >> head));
-  }
-  int shift = 6, offset;
-  if (last) {
-    shift += first ? 0 : head;
-    offset = (1 << (shift - 1)) + (first ? 0 : 8192 << 6);
-  } else {
-    shift -= first ? head : 0;
-    offset = first ? -(8192 << shift) : 0;
-  }
-  int sum = 0;
+  if (frac == 0) return interp_copy(src[0], first, last, B);
+  const InterpStage st = interp_stage(first, last, B);
+  int acc = st.offset;
 #pragma unroll
-  for (int t = 0; t < NTAP; t++) sum += src[(t - (NTAP / 2 - 1)) * step] * (NTAP == 8 ? luma_tap(frac, t) : chroma_tap(frac, t));
-  int v = wrap16((sum + offset) >> shift); // narrowed to Short before the clip (:232-236)
-  return last ? clip3(0, maxv, v) : v;
+  for (int t = 0; t < NTAP; t++) acc += src[(t - (NTAP / 2 - 1)) * step] * (NTAP == 8 ? luma_tap(frac, t) : chroma_tap(frac, t));
+  return interp_end(st, acc);
 }
 
 __global__ void k_filter(const short *src, int ss, short *dst, int ds, int w, int h, int frac, int chroma, int vertical,
@@ -124,11 +106,18 @@ extern "C" int hmx_xPredInterChromaBlk(hmx_ctx *c, const hmx_pel *ref, int ref_s
   Scratch s{c};
   return pred_inter_blk(c, s, ref, ref_stride, mv_hor, mv_ver, w >> 1, h >> 1, dst, dst_stride, bi, 1);
 }
-__global__ void k_addavg(const short *a, const short *b, short *d, int n, int B);
-__global__ void k_weight_uni(const short *a, short *d, int n, int w, int off, int shift, int B);
-__global__ void k_weight_bi(const short *a, const short *b, short *d, int n, int w0, int w1, int off, int shift, int B);
-static bool wp_ok(int weight, int offset, int log2_denom) {
-  return weight >= -128 && weight <= 255 && offset >= -128 && offset <= 127 && log2_denom >= 0 && log2_denom <= 7;
+// TComYuv::addAvg and TComWeightPrediction::addWeightUni / addWeightBi (TComWeightPrediction.cpp:61-237) of n 14-bit intermediates
+__global__ void k_addavg(const short *a, const short *b, short *d, int n, int B) {
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) d[i] = (short)add_avg(a[i], b[i], B);
+}
+__global__ void k_weight_uni(const short *a, short *d, int n, WpPair q, int B) {
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) d[i] = (short)weight_uni(a[i], q, B);
+}
+__global__ void k_weight_bi(const short *a, const short *b, short *d, int n, WpPair q, int B) {
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) d[i] = (short)weight_bi(a[i], b[i], q, B);
 }
 // motionCompensation of ONE prediction unit (TComPrediction.cpp:410-552): xPredInterUni per used list (isLast = uni-prediction),
 // TComYuv::addAvg when both lists are used.  ref0 / ref1: planes of the reference pictures (plane[i] at sample (0,0), margins
@@ -161,14 +150,12 @@ static int mc_one(hmx_ctx *c, const hmx_pic *ref0, const int *mv0, const hmx_pic
       const dim3 grid((pw * ph + 255) / 256), blk(256);
       if (!weighted) {
         hipLaunchKernelGGL(k_addavg, grid, blk, 0, c->stream, d_pred[0], d_pred[1], d_out, pw * ph, B);
-      } else if (bi) { // getWpScaling :286-300: list 0's denominator, the sum of both offsets
-        const int off = (wp0->offset[p] + wp1->offset[p]) * (1 << (B - 8));
-        hipLaunchKernelGGL(k_weight_bi, grid, blk, 0, c->stream, d_pred[0], d_pred[1], d_out, pw * ph, (int)wp0->weight[p], (int)wp1->weight[p], off,
-                           wp0->log2_denom[p] + 1 + head, B);
       } else {
-        const hmx_wp *e = ref0 ? wp0 : wp1;
-        hipLaunchKernelGGL(k_weight_uni, grid, blk, 0, c->stream, d_pred[ref0 ? 0 : 1], d_out, pw * ph, (int)e->weight[p], e->offset[p] * (1 << (B - 8)),
-                           e->log2_denom[p] + head, B);
+        const auto at = [&](const hmx_wp &e) { return wp_entry_make(e.weight[p], e.offset[p], e.log2_denom[p], B); };
+        const WpEntry e0 = at(ref0 ? *wp0 : *wp1), e1 = bi ? at(*wp1) : e0;
+        const WpPair q = wp_pair(e0, e1, bi, head);
+        if (bi) hipLaunchKernelGGL(k_weight_bi, grid, blk, 0, c->stream, d_pred[0], d_pred[1], d_out, pw * ph, q, B);
+        else hipLaunchKernelGGL(k_weight_uni, grid, blk, 0, c->stream, d_pred[ref0 ? 0 : 1], d_out, pw * ph, q, B);
       }
       HIPCHK(c, hipGetLastError());
       int r = down2d(c, dst->plane[p], dst->stride[p], d_out, 2, pw, ph);
@@ -192,7 +179,7 @@ extern "C" int hmx_motionCompensation_wp(hmx_ctx *c, const hmx_pic *ref0, const 
   for (int l = 0; l < 2; l++)
     for (int p = 0; p < 3; p++) {
       const hmx_wp *e = l ? wp1 : wp0;
-      if ((l ? ref1 : ref0) && !wp_ok(e->weight[p], e->offset[p], e->log2_denom[p]))
+      if ((l ? ref1 : ref0) && !wp_range_ok(e->weight[p], e->offset[p], e->log2_denom[p]))
         return fail(c, HMX_ERR_ARG, "hmx_motionCompensation_wp: weight outside -128..255, offset outside -128..127 or log2_denom > 7");
     }
   return mc_one(c, ref0, mv0, ref1, mv1, x, y, w, h, dst, true, wp0, wp1);
@@ -240,7 +227,8 @@ __global__ __launch_bounds__(64) void k_subpel_cost(ARGS A) {
   const int w = pu.w, h = pu.h, n = (w % 8 == 0 && h % 8 == 0) ? 8 : 4, bw = w / n, k = (int)(sb - A.first[lo]);
   const int bx = pu.x + (k % bw) * n, by = pu.y + (k / bw) * n;
   const int mvx = pu.mv0x + A.offs[2 * cand], mvy = pu.mv0y + A.offs[2 * cand + 1];
-  const int xf = mvx & 3, yf = mvy & 3, B = A.B, head = 14 - B, maxv = (1 << B) - 1;
+  const int xf = mvx & 3, yf = mvy & 3, B = A.B;
+  const InterpStage st2 = interp_stage(false, true, B); // filterVerLuma(isFirst = false, isLast = true)
   const PlanesDev &R = A.refs[pu.ref0 < 4 ? pu.ref0 : 0];
   const short *ref = R.p[0] + (ptrdiff_t)(by + (mvy >> 2)) * R.s[0] + bx + (mvx >> 2);
   const short *org = A.org.p[0] + (size_t)by * A.org.s[0] + bx;
@@ -251,13 +239,11 @@ __global__ __launch_bounds__(64) void k_subpel_cost(ARGS A) {
     for (int r = 0; r < n; r++) {
       int v;
       if (yf == 0) { // filterCopy, last only (:124-145)
-        const int off = wrap16(8192 + (head ? (1 << (head - 1)) : 0));
-        v = clip3(0, maxv, wrap16((t[r + 3] + off) >> head));
+        v = interp_copy(t[r + 3], false, true, B);
       } else {
-        const int shift = 6 + head, offset = (1 << (shift - 1)) + (8192 << 6);
         int sum = 0;
         for (int q = 0; q < 8; q++) sum += t[r + q] * luma_tap(yf, q);
-        v = clip3(0, maxv, wrap16((sum + offset) >> shift));
+        v = clip3(st2.lo, st2.hi, wrap16((sum + st2.offset) >> st2.shift));
       }
       if constexpr (ARGS::weighted) d[r * 8 + c] = org[(size_t)r * A.org.s[0] + c] - me_wp_pel(A.wp[pu.ref0 < 4 ? pu.ref0 : 0], v);
       else d[r * 8 + c] = org[(size_t)r * A.org.s[0] + c] - v;
@@ -315,23 +301,6 @@ extern "C" int hmx_batch_subpel_cost_wp(hmx_ctx *c, const hmx_pu *pus, int n, co
   return subpel_cost(c, "hmx_batch_subpel_cost_wp", pus, n, refs, n_refs, org, offs, n_cand, use_had, d_cost, wp);
 }
 
-__device__ __forceinline__ int add_avg(int a, int b, int B) { // TComYuv.cpp:539-540
-  const int sh = 15 - B, off = (1 << (sh - 1)) + 2 * 8192;
-  return clip3(0, (1 << B) - 1, (a + b + off) >> sh);
-}
-// weightUnidir / weightBidir (TComWeightPrediction.h:82-89) on 14-bit intermediates; shift = log2 denominator + (14 - B)
-// (+ 1 for two lists), off = the offset(s) at the bit depth.  The reference's offset << (shift - 1) is a product here.
-__device__ __forceinline__ int weight_uni(int p, int w, int off, int shift, int B) {
-  const int round = shift ? 1 << (shift - 1) : 0;
-  return clip3(0, (1 << B) - 1, ((w * (p + 8192) + round) >> shift) + off);
-}
-__device__ __forceinline__ int weight_bi(int p0, int p1, int w0, int w1, int off, int shift, int B) {
-  return clip3(0, (1 << B) - 1, (w0 * (p0 + 8192) + w1 * (p1 + 8192) + (1 + off) * (1 << (shift - 1))) >> shift);
-}
-__global__ void k_addavg(const short *a, const short *b, short *d, int n, int B) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) d[i] = (short)add_avg(a[i], b[i], B);
-}
 extern "C" int hmx_addAvg(hmx_ctx *c, const hmx_pel *s0, int s0s, const hmx_pel *s1, int s1s, hmx_pel *dst, int ds, int w,
                           int h) {
   if (!c || !s0 || !s1 || !dst || w <= 0 || h <= 0 || w > 128 || h > 128) return fail(c, HMX_ERR_ARG, "hmx_addAvg: bad argument");
@@ -343,41 +312,33 @@ extern "C" int hmx_addAvg(hmx_ctx *c, const hmx_pel *s0, int s0s, const hmx_pel 
   return down2d(c, dst, ds, dd, 2, w, h);
 }
 
-// TComWeightPrediction::addWeightUni / addWeightBi (TComWeightPrediction.cpp:61-237) of one component: src = 14-bit intermediates,
-// weight / offset / log2_denom = iWeight / iOffset (8-bit units) / uiLog2WeightDenom of the entries getWpScaling derives from
-__global__ void k_weight_uni(const short *a, short *d, int n, int w, int off, int shift, int B) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) d[i] = (short)weight_uni(a[i], w, off, shift, B);
-}
-__global__ void k_weight_bi(const short *a, const short *b, short *d, int n, int w0, int w1, int off, int shift, int B) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) d[i] = (short)weight_bi(a[i], b[i], w0, w1, off, shift, B);
-}
+// The scalar entries of one component: src = 14-bit intermediates, weight / offset / log2_denom = iWeight / iOffset (8-bit units) /
+// uiLog2WeightDenom of the entries getWpScaling derives from
 extern "C" int hmx_addWeightUni(hmx_ctx *c, const hmx_pel *src, int ss, hmx_pel *dst, int ds, int w, int h, int weight, int offset,
                                 int log2_denom) {
   if (!c || !src || !dst || w <= 0 || h <= 0 || w > 128 || h > 128) return fail(c, HMX_ERR_ARG, "hmx_addWeightUni: bad argument");
-  if (!wp_ok(weight, offset, log2_denom))
+  if (!wp_range_ok(weight, offset, log2_denom))
     return fail(c, HMX_ERR_ARG, "hmx_addWeightUni: weight outside -128..255, offset outside -128..127 or log2_denom > 7");
   const int B = c->cfg.bit_depth;
   Scratch s{c};
   short *da = s.up(src, w, h, ss), *dd = s.take<short>((size_t)w * h);
   if (s.r) return s.r;
-  hipLaunchKernelGGL(k_weight_uni, dim3((w * h + 255) / 256), dim3(256), 0, c->stream, da, dd, w * h, weight, offset * (1 << (B - 8)),
-                     log2_denom + 14 - B, B);
+  hipLaunchKernelGGL(k_weight_uni, dim3((w * h + 255) / 256), dim3(256), 0, c->stream, da, dd, w * h,
+                     wp_pair(wp_entry_make(weight, offset, log2_denom, B), WpEntry{}, false, 14 - B), B);
   HIPCHK(c, hipGetLastError());
   return down2d(c, dst, ds, dd, 2, w, h);
 }
 extern "C" int hmx_addWeightBi(hmx_ctx *c, const hmx_pel *s0, int s0s, const hmx_pel *s1, int s1s, hmx_pel *dst, int ds, int w, int h,
                                int weight0, int weight1, int offset0, int offset1, int log2_denom) {
   if (!c || !s0 || !s1 || !dst || w <= 0 || h <= 0 || w > 128 || h > 128) return fail(c, HMX_ERR_ARG, "hmx_addWeightBi: bad argument");
-  if (!wp_ok(weight0, offset0, log2_denom) || !wp_ok(weight1, offset1, log2_denom))
+  if (!wp_range_ok(weight0, offset0, log2_denom) || !wp_range_ok(weight1, offset1, log2_denom))
     return fail(c, HMX_ERR_ARG, "hmx_addWeightBi: weight outside -128..255, offset outside -128..127 or log2_denom > 7");
   const int B = c->cfg.bit_depth;
   Scratch s{c};
   short *da = s.up(s0, w, h, s0s), *db = s.up(s1, w, h, s1s), *dd = s.take<short>((size_t)w * h);
   if (s.r) return s.r;
-  hipLaunchKernelGGL(k_weight_bi, dim3((w * h + 255) / 256), dim3(256), 0, c->stream, da, db, dd, w * h, weight0, weight1,
-                     (offset0 + offset1) * (1 << (B - 8)), log2_denom + 1 + 14 - B, B);
+  hipLaunchKernelGGL(k_weight_bi, dim3((w * h + 255) / 256), dim3(256), 0, c->stream, da, db, dd, w * h,
+                     wp_pair(wp_entry_make(weight0, offset0, log2_denom, B), wp_entry_make(weight1, offset1, log2_denom, B), true, 14 - B), B);
   HIPCHK(c, hipGetLastError());
   return down2d(c, dst, ds, dd, 2, w, h);
 }
@@ -400,6 +361,7 @@ struct McArgs {
 struct alignas(16) WpDev { // one 16-byte load
   short w[3], o[3];
   unsigned char d[3], pad;
+  __host__ __device__ WpEntry at(int pl) const { return WpEntry{w[pl], o[pl], d[pl]}; }
 };
 struct McArgsWp : McArgs {
   const WpDev *wp;
@@ -419,9 +381,7 @@ using McArgsOf = std::conditional_t<WP, McArgsWp, McArgs>;
 // even c, T1 for odd c, one of them padded with a zero pair -- so no lane ever re-aligns samples and the
 // lanes of a wave (different PUs, fractions and parities) run the same instructions.  Every cell takes the
 // two-stage route (horizontal into the 14-bit intermediate, then vertical), a zero fraction being the filter
-// {0,..,64,..,0}: with the reference's offsets and shifts that is bit-identical to its one-stage and copy
-// cases (xPredInterLumaBlk :554-601 -- for a first-and-last stage (sum + 32) >> 6 ==
-// ((sum >> (6-head)) + (1 << (head-1))) >> head because 8192 << (6-head) is a multiple of the first shift).
+// {0,..,64,..,0}: bit-identical to the reference's one-stage and copy cases (interp_stage, hmx_kernels.h).
 template <int NTAP>
 __device__ __forceinline__ int tap_pair(int frac, int k) { // the pair (t[k], t[k+1]); taps outside 0..NTAP-1 are 0
   auto tap = [&](int t) { return (t < 0 || t >= NTAP) ? 0 : (NTAP == 8 ? luma_tap(frac, t) : chroma_tap(frac, t)); };
@@ -475,9 +435,9 @@ __device__ __forceinline__ void mc_cell(const int *lds_taps, const short *ref, i
   for (int j = 0; j < NO; j++) t0[j] = tx[j], t1[j] = tx[NO + j], oy[j] = ty[NO + j];
 #pragma unroll
   for (int j = 0; j < NE; j++) ey[j] = ty[j];
-  const int head = 14 - B, maxv = (1 << B) - 1;
-  // stage 1, first and not last (:206-221): shift 6 - head, offset -(8192 << shift); narrowed to 16 bits
-  const int sh1 = 6 - head, off1 = -(8192 << sh1);
+  // stage 1, first and not last; narrowed to 16 bits by the packing below.  Stage 2, not first: the last stage of a lane with one
+  // list, clipped; else the 14-bit sample addAvg or the weighting takes
+  const InterpStage st1 = interp_stage(true, false, B), st2 = interp_stage(false, !bi, B);
   int P[NP][W]; // the intermediate, rows 2k and 2k+1 packed per column
   int lo[W];
   // The rows are fetched four at a time, one chunk ahead of the arithmetic: a wave spends its life waiting for
@@ -501,10 +461,10 @@ __device__ __forceinline__ void mc_cell(const int *lds_taps, const short *ref, i
         const int *d = buf[k & 1][i];
 #pragma unroll
         for (int c = 0; c < W; c++) {
-          int s = off1;
+          int s = st1.offset;
 #pragma unroll
           for (int j = 0; j < NO; j++) s = dot2(d[c / 2 + j], c % 2 ? t1[j] : t0[j], s);
-          s >>= sh1;
+          s >>= st1.shift;
           if (r % 2 == 0) lo[c] = s;
           else P[r / 2][c] = (int)__builtin_amdgcn_perm((unsigned)s, (unsigned)lo[c], 0x05040100u);
         }
@@ -514,15 +474,12 @@ __device__ __forceinline__ void mc_cell(const int *lds_taps, const short *ref, i
   if (R % 2)
 #pragma unroll
     for (int c = 0; c < W; c++) P[NP - 1][c] = lo[c] & 0xffff;
-  // stage 2, not first: last -> shift 6 + head, offset (1 << (shift-1)) + (8192 << 6), clipped; else shift 6
-  const bool last = !bi;
-  const int sh2 = last ? 6 + head : 6, off2 = last ? (1 << (5 + head)) + (8192 << 6) : 0;
 #pragma unroll
   for (int r = 0; r < H; r++) {
     int v[W];
 #pragma unroll
     for (int c = 0; c < W; c++) {
-      int s = off2;
+      int s = st2.offset;
       if (r % 2 == 0) {
 #pragma unroll
         for (int j = 0; j < NE; j++) s = dot2(P[r / 2 + j][c], ey[j], s);
@@ -530,8 +487,7 @@ __device__ __forceinline__ void mc_cell(const int *lds_taps, const short *ref, i
 #pragma unroll
         for (int j = 0; j < NO; j++) s = dot2(P[r / 2 + j][c], oy[j], s);
       }
-      const int w16 = wrap16(s >> sh2);
-      v[c] = last ? clip3(0, maxv, w16) : w16;
+      v[c] = interp_end(st2, s);
     }
     emit(r, v);
   }
@@ -549,19 +505,14 @@ __device__ __forceinline__ void mc_cell_plane(const int *lds_taps, const McArgsO
   gpel *d = (gpel *)J.dst.p[pl] + (size_t)y * J.dst.s[pl] + x;
   const int ds = J.dst.s[pl];
   unsigned keep[H * W / 2];
-  int w0 = 0, w1 = 0, woff = 0, wshift = 0; // this plane's weights (WP only)
+  WpPair wq{}; // this plane's weights (WP only)
   if constexpr (WP) {
     typedef int i4v __attribute__((ext_vector_type(4)));
     typedef __attribute__((address_space(1))) const i4v gwp;
     const gwp *tab = (const gwp *)A.wp + 2 * J.ref_off;
-    const int head = 14 - A.B;
-    if (bi) { // list 0's denominator serves both lists (getWpScaling :295-299)
-      const WpDev e0 = __builtin_bit_cast(WpDev, (i4v)tab[2 * u.ref0]), e1 = __builtin_bit_cast(WpDev, (i4v)tab[2 * u.ref1 + 1]);
-      w0 = e0.w[pl], w1 = e1.w[pl], woff = e0.o[pl] + e1.o[pl], wshift = e0.d[pl] + 1 + head;
-    } else {
-      const WpDev e = __builtin_bit_cast(WpDev, (i4v)tab[first1 ? 2 * u.ref1 + 1 : 2 * u.ref0]);
-      w0 = e.w[pl], woff = e.o[pl], wshift = e.d[pl] + head;
-    }
+    const auto entry = [&](int k) { return __builtin_bit_cast(WpDev, (i4v)tab[k]).at(pl); }; // one 16-byte load
+    const WpEntry e0 = entry(first1 ? 2 * u.ref1 + 1 : 2 * u.ref0), e1 = bi ? entry(2 * u.ref1 + 1) : e0;
+    wq = wp_pair(e0, e1, bi, 14 - A.B);
   }
   {
     const PlanesDev &R = A.refs[J.ref_off + (first1 ? u.ref1 : u.ref0)];
@@ -575,7 +526,7 @@ __device__ __forceinline__ void mc_cell_plane(const int *lds_taps, const McArgsO
                           if constexpr (WP) {
                             if (!bi) {
 #pragma unroll
-                              for (int c = 0; c < W; c++) row[c] = (short)weight_uni(v[c], w0, woff, wshift, A.B);
+                              for (int c = 0; c < W; c++) row[c] = (short)weight_uni(v[c], wq, A.B);
                             }
                           }
                           if (!bi) __builtin_memcpy(d + (size_t)r * ds, row, W * 2); // one 8-byte (4-byte) store per row
@@ -589,8 +540,8 @@ __device__ __forceinline__ void mc_cell_plane(const int *lds_taps, const McArgsO
       for (int c = 0; c < W; c += 2) {
         const unsigned k = keep[(r * W + c) / 2];
         if constexpr (WP) {
-          row[c] = (short)weight_bi((int)(short)(k & 0xffff), v[c], w0, w1, woff, wshift, A.B);
-          row[c + 1] = (short)weight_bi((int)(short)(k >> 16), v[c + 1], w0, w1, woff, wshift, A.B);
+          row[c] = (short)weight_bi((int)(short)(k & 0xffff), v[c], wq, A.B);
+          row[c + 1] = (short)weight_bi((int)(short)(k >> 16), v[c + 1], wq, A.B);
         } else {
           row[c] = (short)add_avg((int)(short)(k & 0xffff), v[c], A.B);
           row[c + 1] = (short)add_avg((int)(short)(k >> 16), v[c + 1], A.B);
@@ -673,7 +624,7 @@ __global__ __launch_bounds__(64) void k_mc(McArgsOf<WP> A) {
 // One table entry checked and brought to the device form (getWpScaling :286-312: o = iOffset * (1 << (B - 8))).
 static bool wp_entry(const hmx_wp &e, int B, WpDev *out) {
   for (int k = 0; k < 3; k++) {
-    if (e.weight[k] < -128 || e.weight[k] > 255 || e.offset[k] < -128 || e.offset[k] > 127 || e.log2_denom[k] > 7) return false;
+    if (!wp_range_ok(e.weight[k], e.offset[k], e.log2_denom[k])) return false;
     out->w[k] = e.weight[k];
     out->o[k] = (short)(e.offset[k] * (1 << (B - 8)));
     out->d[k] = e.log2_denom[k];
@@ -875,10 +826,6 @@ extern "C" int hmx_pic_extend_border(hmx_ctx *c, const hmx_pic *pic, int pic_w, 
 // LDS rows are padded to an odd number of dwords (pe_pitch): the sub-blocks of a wave that lie below each other start 8 (4)
 // rows apart, and with an even pitch their columns would walk the same banks.
 constexpr int kPeThreads = 256;
-struct PeWp { // the luma entry of one (reference, list): getWpScaling's fields, o at the bit depth
-  short w, o;
-  int d;
-};
 struct PeArgs {
   const hmx_pu *cands;
   const uint32_t *bits;  // NULL: 0 for every candidate
@@ -892,7 +839,7 @@ struct PeArgs {
   static constexpr bool weighted = false;
 };
 struct PeArgsWp : PeArgs { // as SubpelArgsWp: the unweighted kernel keeps its argument block
-  PeWp wp[4][2];           // [reference][list]
+  WpEntry wp[4][2];        // the luma entry of [reference][list]
   static constexpr bool weighted = true;
 };
 __host__ __device__ constexpr int pe_pitch(int n) { return (((n + 1) >> 1) | 1) << 1; } // >= n samples, an odd number of dwords
@@ -900,35 +847,8 @@ static size_t pe_lds_bytes(int w, int h) { // original, window, intermediate, th
   return sizeof(short) * (size_t)(w * h + pe_pitch(w + 7) * (h + 7) + pe_pitch(w) * (h + 7) + w * h);
 }
 enum PeMode { PE_FINAL, PE_KEEP, PE_AVG, PE_WUNI, PE_WBI };
-// One filter stage with everything that is uniform over a pass taken out of the sample loop: the taps (luma_tap) in registers and
-// the shift, offset and clip of interp_sample<8>'s filter branch (TComInterpolationFilter::filter, :160-244).  A zero fraction runs
-// as the filter {.., 64, ..}: with these offsets and shifts that is bit-identical to filterCopy (:91-145) in the three cases
-// xPredInterLumaBlk uses (see mc_cell above), so a pass has no branch per sample and no table load per tap.
-struct PeFilter {
-  int tap[8], shift, offset, lo, hi;
-};
-__device__ __forceinline__ PeFilter pe_filter(int frac, bool first, bool last, int B) {
-  PeFilter f;
-#pragma unroll
-  for (int q = 0; q < 8; q++) f.tap[q] = luma_tap(frac, q);
-  const int head = 14 - B;
-  f.shift = 6;
-  if (last) {
-    f.shift += first ? 0 : head;
-    f.offset = (1 << (f.shift - 1)) + (first ? 0 : 8192 << 6);
-  } else {
-    f.shift -= first ? head : 0;
-    f.offset = first ? -(8192 << f.shift) : 0;
-  }
-  f.lo = last ? 0 : -32768, f.hi = last ? (1 << B) - 1 : 32767; // narrowed to Short before the clip (:232-236); not last: no clip
-  return f;
-}
-__device__ __forceinline__ int pe_sample(const PeFilter &f, const int *s) { // s[0..7]: the samples under the taps
-  int sum = f.offset;
-#pragma unroll
-  for (int q = 0; q < 8; q++) sum += s[q] * f.tap[q];
-  return clip3(f.lo, f.hi, wrap16(sum >> f.shift));
-}
+// Every pass is a LumaFilter (hmx_kernels.h), a zero fraction included (interp_stage: the filter {.., 64, ..}), so a pass has no
+// branch per sample and no table load per tap.
 // k = tid, tid + nt, ... as (row, column) of a `cols`-wide block without a division per element
 struct PeWalk {
   int r, c, dr, dc, cols;
@@ -943,14 +863,10 @@ struct PeWalk {
 // samples in p0 and costs nothing; every other mode adds the block's distortion to *s_sum.
 template <int S>
 __device__ __forceinline__ void pe_cost_pass(const short *src, int pitch, bool ver, int frac, bool first, int mode, short *p0, const short *org, int w,
-                                             int h, int B, int use_had, int w0, int w1, int woff, int wshift, unsigned *s_sum, int tid, int nthreads) {
-  const int bw = w / S, nsb = bw * (h / S), lane = tid & (S - 1);
-  const PeFilter f = pe_filter(frac, first, mode == PE_FINAL, B);
-  for (int base = 0; base < nsb; base += nthreads / S) {
-    if (base + (tid & ~63) / S >= nsb) break; // no sub-block left for this wave (uniform over the wave)
-    int g = base + tid / S;
-    const bool act = g < nsb; // idle lanes of a busy wave redo the last sub-block and add nothing
-    g = act ? g : nsb - 1;
+                                             int h, int B, int use_had, const WpPair &wq, unsigned *s_sum, int tid, int nthreads) {
+  const int bw = w / S, lane = tid & (S - 1);
+  const LumaFilter f = luma_filter(frac, first, mode == PE_FINAL, B);
+  subblock_walk<S>(bw * (h / S), tid, nthreads, [&](int g, bool act) {
     const int sby = g / bw, sx = (g - sby * bw) * S + lane, sy = sby * S;
     const short *s = src + sy * pitch + sx;
     int d[S];
@@ -958,39 +874,34 @@ __device__ __forceinline__ void pe_cost_pass(const short *src, int pitch, bool v
       int col[S + 7];
 #pragma unroll
       for (int q = 0; q < S + 7; q++) col[q] = s[(q - 3) * pitch];
-#pragma unroll
-      for (int r = 0; r < S; r++) d[r] = pe_sample(f, col + r);
+      luma_column<S>(f, col, d);
     } else {
 #pragma unroll
       for (int r = 0; r < S; r++) {
         int row[8];
 #pragma unroll
         for (int q = 0; q < 8; q++) row[q] = s[r * pitch + q - 3];
-        d[r] = pe_sample(f, row);
+        d[r] = luma_sample(f, row);
       }
     }
     short *k0 = p0 + sy * w + sx;
     if (mode == PE_KEEP) {
 #pragma unroll
       for (int r = 0; r < S; r++) k0[r * w] = (short)d[r];
-      continue;
+      return;
     }
     if (mode == PE_AVG) {
 #pragma unroll
       for (int r = 0; r < S; r++) d[r] = add_avg(k0[r * w], d[r], B);
     } else if (mode == PE_WUNI) {
 #pragma unroll
-      for (int r = 0; r < S; r++) d[r] = weight_uni(d[r], w0, woff, wshift, B);
+      for (int r = 0; r < S; r++) d[r] = weight_uni(d[r], wq, B);
     } else if (mode == PE_WBI) {
 #pragma unroll
-      for (int r = 0; r < S; r++) d[r] = weight_bi(k0[r * w], d[r], w0, w1, woff, wshift, B);
+      for (int r = 0; r < S; r++) d[r] = weight_bi(k0[r * w], d[r], wq, B);
     }
-    const short *o = org + sy * w + sx;
-#pragma unroll
-    for (int r = 0; r < S; r++) d[r] = o[r * w] - d[r];
-    const int sum = subblock_dist_lanes<S>(d, lane, use_had);
-    if (act && lane == 0) atomicAdd(s_sum, (unsigned)sum);
-  }
+    column_cost<S>(d, org + sy * w + sx, w, lane, use_had, act, s_sum);
+  });
 }
 template <class ARGS>
 __global__ __launch_bounds__(kPeThreads) void k_pred_error(ARGS A) {
@@ -1019,17 +930,8 @@ __global__ __launch_bounds__(kPeThreads) void k_pred_error(ARGS A) {
   for (uint32_t i = c0; i < c1; i++) {
     const hmx_pu u = A.cands[i];
     const bool bi = u.ref0 != 255 && u.ref1 != 255, mid = WP || bi; // mid: the lists' predictions are 14-bit samples
-    int w0 = 0, w1 = 0, woff = 0, wshift = 0;
-    if constexpr (WP) { // getWpScaling (TComWeightPrediction.cpp:286-312): two lists share list 0's denominator and sum the offsets
-      const int head = 14 - B;
-      if (bi) {
-        const PeWp e0 = A.wp[u.ref0 & 3][0], e1 = A.wp[u.ref1 & 3][1];
-        w0 = e0.w, w1 = e1.w, woff = e0.o + e1.o, wshift = e0.d + 1 + head;
-      } else {
-        const PeWp e = u.ref0 != 255 ? A.wp[u.ref0 & 3][0] : A.wp[u.ref1 & 3][1];
-        w0 = e.w, woff = e.o, wshift = e.d + head;
-      }
-    }
+    WpPair wq{};
+    if constexpr (WP) wq = wp_pair(u.ref0 != 255 ? A.wp[u.ref0 & 3][0] : A.wp[u.ref1 & 3][1], A.wp[u.ref1 & 3][1], bi, 14 - B);
     for (int l = 0; l < 2; l++) {
       const int ref = l ? u.ref1 : u.ref0;
       if (ref == 255) continue;
@@ -1046,14 +948,14 @@ __global__ __launch_bounds__(kPeThreads) void k_pred_error(ARGS A) {
       int pitch = wp, frac = xf;
       bool first = true, ver = false;
       if (xf && yf) { // filterHorLuma(isLast = false) of rows -3 .. h + 3, then filterVerLuma(isFirst = false) (TComPrediction.cpp:583-600)
-        const PeFilter f = pe_filter(xf, true, false, B);
+        const LumaFilter f = luma_filter(xf, true, false, B);
         PeWalk k = walk_w;
         for (int j = tid; j < w * rows; j += nt, k.next()) {
           const short *s = win + k.r * wp + k.c;
           int row[8];
 #pragma unroll
           for (int q = 0; q < 8; q++) row[q] = s[q];
-          tmp[k.r * tp + k.c] = (short)pe_sample(f, row);
+          tmp[k.r * tp + k.c] = (short)luma_sample(f, row);
         }
         __syncthreads();
         src = tmp + 3 * tp, pitch = tp, frac = yf, first = false, ver = true;
@@ -1061,8 +963,8 @@ __global__ __launch_bounds__(kPeThreads) void k_pred_error(ARGS A) {
         frac = yf, ver = true;
       }
       const int mode = !mid ? PE_FINAL : (bi && l == 0) ? PE_KEEP : bi ? (WP ? PE_WBI : PE_AVG) : PE_WUNI;
-      if (s8) pe_cost_pass<8>(src, pitch, ver, frac, first, mode, p0, org, w, h, B, A.use_had, w0, w1, woff, wshift, &s_sum, tid, nt);
-      else pe_cost_pass<4>(src, pitch, ver, frac, first, mode, p0, org, w, h, B, A.use_had, w0, w1, woff, wshift, &s_sum, tid, nt);
+      if (s8) pe_cost_pass<8>(src, pitch, ver, frac, first, mode, p0, org, w, h, B, A.use_had, wq, &s_sum, tid, nt);
+      else pe_cost_pass<4>(src, pitch, ver, frac, first, mode, p0, org, w, h, B, A.use_had, wq, &s_sum, tid, nt);
     }
     __syncthreads();
     if (tid == 0) { // getCost(UInt) (TComRdCost.h:204), all of it uint32_t; the next sum starts two barriers from here
@@ -1077,7 +979,7 @@ __global__ __launch_bounds__(kPeThreads) void k_pred_error(ARGS A) {
 
 // the launch: every argument has been checked; first (host): n_groups + 1 prefix entries
 static int pe_launch(hmx_ctx *c, const hmx_pu *cands, const uint32_t *bits, int n, const uint32_t *first, int n_groups, const PlanesDev *refs, int n_refs,
-                     const PlanesDev &org, uint32_t lambda, int use_had, uint32_t *d_dist, uint32_t *d_cost, hmx_pred_choice *d_best, const PeWp (*wp)[2]) {
+                     const PlanesDev &org, uint32_t lambda, int use_had, uint32_t *d_dist, uint32_t *d_cost, hmx_pred_choice *d_best, const WpEntry (*wp)[2]) {
   size_t lds = 0;
   int threads = 64;
   for (int i = 0; i < n; i++) {
@@ -1113,7 +1015,7 @@ static int pred_error(hmx_ctx *c, const char *name, const hmx_pu *cands, const u
   if (n_groups < 0 || (n_groups == 0) != (group_first == nullptr) || (n_groups == 0) != (d_best == nullptr))
     return fail(c, HMX_ERR_ARG, nm() + ": group_first, n_groups and d_best are given together (groups) or NULL, 0, NULL (costs only)");
   const bool weighted = wp && (wp->l0 || wp->l1);
-  PeWp wpt[4][2] = {};
+  WpEntry wpt[4][2] = {};
   if (weighted) {
     if (!wp->l0) return fail(c, HMX_ERR_ARG, nm() + ": a weighted call needs the list 0 table (l0 NULL, l1 not)");
     const hmx_wp unit = {{1, 1, 1}, {0, 0, 0}, {0, 0, 0}, 0}; // a missing list 1 table holds the unit weight
@@ -1124,7 +1026,7 @@ static int pred_error(hmx_ctx *c, const char *name, const hmx_pu *cands, const u
         if (!wp_entry(t ? t[r] : unit, c->cfg.bit_depth, &e))
           return fail(c, HMX_ERR_ARG, nm() + ": wp list " + std::to_string(l) + " row " + std::to_string(r) +
                                           ": weight outside -128..255, offset outside -128..127 or log2_denom > 7");
-        wpt[r][l] = PeWp{e.w[0], e.o[0], e.d[0]};
+        wpt[r][l] = e.at(0);
       }
   }
   for (int i = 0; i < n; i++) {
@@ -1189,13 +1091,13 @@ extern "C" int hmx_getInterPredictionError(hmx_ctx *c, const hmx_pic *ref0, cons
   if (!me_size_ok(w) || !me_size_ok(h)) return fail(c, HMX_ERR_ARG, nm + ": width and height come from {4, 8, 12, 16, 24, 32, 48, 64}");
   const bool weighted = wp0 || wp1;
   if (weighted && ((ref0 && !wp0) || (ref1 && !wp1))) return fail(c, HMX_ERR_ARG, nm + ": a weighted call needs the entry of every used list");
-  PeWp wpt[4][2] = {};
+  WpEntry wpt[4][2] = {};
   for (int l = 0; l < 2 && weighted; l++) {
     WpDev e;
     if (!(l ? ref1 : ref0)) continue;
     if (!wp_entry(l ? *wp1 : *wp0, c->cfg.bit_depth, &e))
       return fail(c, HMX_ERR_ARG, nm + ": wp" + std::to_string(l) + ": weight outside -128..255, offset outside -128..127 or log2_denom > 7");
-    wpt[l][l] = PeWp{e.w[0], e.o[0], e.d[0]};
+    wpt[l][l] = e.at(0);
   }
   const int ww = w + 7, wh = h + 7;
   Scratch s{c};

@@ -703,6 +703,108 @@ struct MeWp {
   int w0, round, shift, offset;
 };
 __host__ __device__ __forceinline__ int me_wp_pel(const MeWp &p, int c) { return (int)(short)(((p.w0 * c + p.round) >> p.shift) + p.offset); }
+// The walk of a workgroup over `total` items that S consecutive lanes share: body(item, act).  A wave leaves when no item is left for
+// it (uniform over the wave: subblock_dist_lanes exchanges lanes); idle lanes of a busy wave redo the last item with act = false.
+template <int S, typename Body>
+__device__ __forceinline__ void subblock_walk(int total, int tid, int nthreads, Body body) {
+  for (int base = 0; base < total; base += nthreads / S) {
+    if (base + (tid & ~63) / S >= total) break;
+    const int g = base + tid / S;
+    body(g < total ? g : total - 1, g < total);
+  }
+}
+// the end of a lane's column: pred[] against the original's column o (rows ow apart), the sub-block's distortion added to *acc once
+template <int S>
+__device__ __forceinline__ void column_cost(int (&pred)[S], const short *o, int ow, int lane, int use_had, bool act, unsigned *acc) {
+#pragma unroll
+  for (int r = 0; r < S; r++) pred[r] = o[r * ow] - pred[r];
+  const int s = subblock_dist_lanes<S>(pred, lane, use_had);
+  if (act && lane == 0) atomicAdd(acc, (unsigned)s);
+}
+
+// ---- interpolation (TComInterpolationFilter.cpp): the taps, and the parameters of one filter stage ----
+__host__ __device__ constexpr int luma_tap(int frac, int t) { // m_lumaFilter
+  constexpr signed char k[4][8] = {{0, 0, 0, 64, 0, 0, 0, 0}, {-1, 4, -10, 58, 17, -5, 1, 0}, {-1, 4, -11, 40, 40, -11, 4, -1},
+                                   {0, 1, -5, 17, 58, -10, 4, -1}};
+  return k[frac][t];
+}
+__host__ __device__ constexpr int chroma_tap(int frac, int t) { // m_chromaFilter
+  constexpr signed char k[8][4] = {{0, 64, 0, 0},   {-2, 58, 10, -2}, {-4, 54, 16, -2}, {-6, 46, 28, -4},
+                                   {-4, 36, 36, -4}, {-4, 28, 46, -6}, {-2, 16, 54, -4}, {-2, 10, 58, -2}};
+  return k[frac][t];
+}
+// TComInterpolationFilter::filter (:160-244) behind the tap sum: out = clip(lo, hi, (Short)((sum + offset) >> shift)); the narrowing
+// to Short comes before the clip (:232-236) and only a last stage clips.  With head = 14 - B and 8192 = IF_INTERNAL_OFFS:
+//   first, not last    shift 6 - head, offset -(8192 << shift)                   the 14-bit intermediate
+//   not first, last    shift 6 + head, offset (1 << (shift - 1)) + (8192 << 6)   the second stage of a prediction that ends there
+//   neither            shift 6, offset 0                                         the second stage before addAvg or the weighting
+//   first and last     shift 6, offset 32                                        one stage from samples to samples
+// A ZERO FRACTION, the reference's filterCopy (:91-145), may run as the filter {.., 64, ..} for B < 14 wherever a fused kernel follows
+// xPredInterLumaBlk / xPredInterChromaBlk (TComPrediction.cpp:554-642).  The sum is then 64 * v, and with t = (v << head) - 8192:
+// first-not-last gives (64 * v - (8192 << (6 - head))) >> (6 - head) = t, nothing being shifted out; not-first-last gives
+// (64 * t + (1 << (5 + head)) + (8192 << 6)) >> (6 + head) = (t + 8192 + (1 << (head - 1))) >> head, 64 being shifted out whole;
+// neither gives t: filterCopy's three cases.  First-and-last never meets a zero fraction, and a kernel may take the two-stage route
+// in its place (mc_cell does): ((sum >> (6 - head)) + (1 << (head - 1))) >> head and ((sum << head) + (1 << (5 + head))) >> (6 + head)
+// both equal (sum + 32) >> 6, 32 being a multiple of what the first shift drops.  interp_sample (hmx_inter.hip) keeps filterCopy.
+struct InterpStage {
+  int shift, offset, lo, hi;
+};
+__host__ __device__ __forceinline__ InterpStage interp_stage(bool first, bool last, int B) {
+  const int head = 14 - B, shift = 6 + (first == last ? 0 : last ? head : -head);
+  const int offset = last ? (1 << (shift - 1)) + (first ? 0 : 8192 << 6) : first ? -(8192 << shift) : 0;
+  return InterpStage{shift, offset, last ? 0 : -32768, last ? (1 << B) - 1 : 32767};
+}
+__device__ __forceinline__ int interp_end(const InterpStage &st, int acc) { return clip3(st.lo, st.hi, wrap16(acc >> st.shift)); } // acc started at st.offset
+// One luma stage with everything that is uniform over a pass taken out of the sample loop: the taps in registers beside the stage
+struct LumaFilter {
+  int tap[8];
+  InterpStage st;
+};
+__device__ __forceinline__ LumaFilter luma_filter(int frac, bool first, bool last, int B) {
+  LumaFilter f;
+#pragma unroll
+  for (int q = 0; q < 8; q++) f.tap[q] = luma_tap(frac, q);
+  f.st = interp_stage(first, last, B);
+  return f;
+}
+__device__ __forceinline__ int luma_sample(const LumaFilter &f, const int *s) { // s[0..7]: the samples under the taps
+  int acc = f.st.offset;
+#pragma unroll
+  for (int q = 0; q < 8; q++) acc += s[q] * f.tap[q];
+  return interp_end(f.st, acc);
+}
+// the vertical pass of a lane's column: S + 7 samples (rows -3 .. S + 3) into S outputs
+template <int S>
+__device__ __forceinline__ void luma_column(const LumaFilter &f, const int (&t)[S + 7], int (&out)[S]) {
+#pragma unroll
+  for (int r = 0; r < S; r++) out[r] = luma_sample(f, t + r);
+}
+
+// ---- explicit weighted prediction of 14-bit intermediates (TComWeightPrediction.cpp:61-313) ----
+struct WpEntry { // one component of the wpScalingParam of one (reference, list); o = iOffset at the bit depth, iOffset * (1 << (B - 8))
+  short w, o;
+  int d;
+};
+// getWpScaling (:286-312) for the one list (e0; e1 is not read) or the two lists a unit uses: two lists share list 0's denominator and
+// sum their offsets; shift = the denominator + head (+ 1 for two lists), head = 14 - B
+struct WpPair {
+  int w0, w1, off, shift;
+};
+__host__ __device__ __forceinline__ WpPair wp_pair(const WpEntry &e0, const WpEntry &e1, bool two, int head) {
+  return two ? WpPair{e0.w, e1.w, e0.o + e1.o, e0.d + 1 + head} : WpPair{e0.w, 0, e0.o, e0.d + head};
+}
+__device__ __forceinline__ int add_avg(int a, int b, int B) { // TComYuv.cpp:539-540
+  const int sh = 15 - B, off = (1 << (sh - 1)) + 2 * 8192;
+  return clip3(0, (1 << B) - 1, (a + b + off) >> sh);
+}
+// weightUnidir / weightBidir (TComWeightPrediction.h:82-89).  The reference's offset << (shift - 1) is a product here.
+__device__ __forceinline__ int weight_uni(int p, const WpPair &q, int B) {
+  const int round = q.shift ? 1 << (q.shift - 1) : 0;
+  return clip3(0, (1 << B) - 1, ((q.w0 * (p + 8192) + round) >> q.shift) + q.off);
+}
+__device__ __forceinline__ int weight_bi(int p0, int p1, const WpPair &q, int B) {
+  return clip3(0, (1 << B) - 1, (q.w0 * (p0 + 8192) + q.w1 * (p1 + 8192) + (1 + q.off) * (1 << (q.shift - 1))) >> q.shift);
+}
 template <int N>
 __device__ __forceinline__ int satd_block(TuLds<N> &L, int gl, const int *d) {
   constexpr int S = N >= 8 ? 8 : 4, RND = S == 8 ? 2 : 1;

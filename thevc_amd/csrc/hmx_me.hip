@@ -345,8 +345,8 @@ extern "C" int hmx_batch_fullpel_search_wp(hmx_ctx *c, const hmx_me_unit *units,
 // differences; the Hadamard sum runs down the column in registers and across the S lanes by lane exchange -- and the
 // sub-block sums meet in LDS counters (integer adds: the order does not matter).  Wave 0 adds the vector cost and takes the
 // minimum of (cost, table index) -- the tables of the two stages differ, so the index is the table's, never a raster
-// position -- and writes costs and result with plain stores.  The zero-fraction vertical step (filterCopy, isLast) equals the
-// general step with the taps {0, 0, 0, 64, 0, 0, 0, 0} for bit depths below 14: 64 * (t + 8192 + 2^(head-1)) >> (6 + head).
+// position -- and writes costs and result with plain stores.  The zero-fraction vertical step (filterCopy, isLast) runs as the
+// general step with the taps {0, 0, 0, 64, 0, 0, 0, 0} (interp_stage, hmx_kernels.h).
 // LDS (dynamic, sized for the largest unit of the call): window, original, planes 2, 1, 3 = 46352 bytes at 64 x 64: three
 // workgroups = twelve waves per CU (160 KB); 1440 bytes at 8 x 8, where the registers (eight workgroups per CU) bind first.
 // WP (uniform over a launch): weighted distortion, xGetSADw / xGetHADsw (TComRdCostWeightPrediction.cpp:69-104, :490-561): the
@@ -374,14 +374,9 @@ struct SpDiv { // n / d for n < 4096 * d and n * d < 2^20, by one multiplication
   __device__ __forceinline__ explicit SpDiv(int dd) : d((unsigned)dd), m(((1u << 20) + (unsigned)dd - 1) / (unsigned)dd) {}
   __device__ __forceinline__ int div(int n) const { return (int)(((unsigned)n * m) >> 20); }
 };
-__host__ __device__ constexpr int sp_luma_tap(int frac, int q) {
-  constexpr signed char k[4][8] = {{0, 0, 0, 64, 0, 0, 0, 0}, {-1, 4, -10, 58, 17, -5, 1, 0}, {-1, 4, -11, 40, 40, -11, 4, -1},
-                                   {0, 1, -5, 17, 58, -10, 4, -1}};
-  return k[frac][q];
-}
 __host__ __device__ constexpr unsigned sp_tap_word(int frac, int half) { // four taps as signed bytes
-  return ((unsigned)sp_luma_tap(frac, 4 * half) & 255u) | (((unsigned)sp_luma_tap(frac, 4 * half + 1) & 255u) << 8) |
-         (((unsigned)sp_luma_tap(frac, 4 * half + 2) & 255u) << 16) | (((unsigned)sp_luma_tap(frac, 4 * half + 3) & 255u) << 24);
+  return ((unsigned)luma_tap(frac, 4 * half) & 255u) | (((unsigned)luma_tap(frac, 4 * half + 1) & 255u) << 8) |
+         (((unsigned)luma_tap(frac, 4 * half + 2) & 255u) << 16) | (((unsigned)luma_tap(frac, 4 * half + 3) & 255u) << 24);
 }
 // s_acMvRefineH / s_acMvRefineQ (TEncSearch.cpp:47-71), component + 1 in two bits per entry; the x components agree
 __host__ __device__ constexpr unsigned sp_pack9(int a0, int a1, int a2, int a3, int a4, int a5, int a6, int a7, int a8) {
@@ -399,15 +394,16 @@ __device__ __forceinline__ void sp_cand(int stage, int k, int &dx, int &dy) {
 // column wc0 + c, into dst (pitch dp)
 template <int FRAC>
 __device__ __forceinline__ void sp_hor_plane(const short *win, int wp, short *dst, int dp, int cols, int wc0, int r0, int r1, int B, int tid) {
-  const int shift = B - 8, offset = -(8192 << shift), n = (r1 - r0) * cols;
+  const LumaFilter f = luma_filter(FRAC, true, false, B); // the taps fold to constants
+  const int n = (r1 - r0) * cols;
   const SpDiv dc(cols);
   for (int i = tid; i < n; i += kSpThreads) {
     const int r = dc.div(i), c = i - r * cols;
     const short *s = win + (r0 + r) * wp + wc0 + c - 3;
-    int sum = 0;
+    int row[8];
 #pragma unroll
-    for (int q = 0; q < 8; q++) sum += s[q] * sp_luma_tap(FRAC, q);
-    dst[(r0 + r) * dp + c] = (short)((sum + offset) >> shift);
+    for (int q = 0; q < 8; q++) row[q] = s[q];
+    dst[(r0 + r) * dp + c] = (short)luma_sample(f, row);
   }
 }
 
@@ -419,14 +415,11 @@ struct SpLds {
 template <int S, bool WP>
 __device__ __forceinline__ void sp_stage(const SpLds &L, int stage, int hx, int hy, int c1, int c3, int B, int use_had, const MeWp *wp, unsigned *s_cost,
                                          int tid) {
-  const int w = L.w, bw = w / S, nsb = bw * (L.h / S), total = 9 * nsb, lane = tid & (S - 1);
+  const int w = L.w, bw = w / S, nsb = bw * (L.h / S), lane = tid & (S - 1);
   const SpDiv dn(nsb), db(bw);
-  const int head = 14 - B, shift = 6 + head, offset = (1 << (shift - 1)) + (8192 << 6), maxv = (1 << B) - 1;
-  for (int base = 0; base < total; base += kSpThreads / S) {
-    if (base + (tid & ~63) / S >= total) break; // no sub-block left for this wave (uniform over the wave)
-    int g = base + tid / S;
-    const bool act = g < total; // idle lanes of a busy wave redo the last item and add nothing
-    g = act ? g : total - 1;
+  const int head = 14 - B;
+  LumaFilter f{{}, interp_stage(false, true, B)}; // filterVerLuma(isFirst = false, isLast = true); the taps are the item's
+  subblock_walk<S>(9 * nsb, tid, kSpThreads, [&](int g, bool act) { // an item: one sub-block of one candidate
     const int k = dn.div(g), sb = g - k * nsb, sby = db.div(sb), sx = (sb - sby * bw) * S, sy = sby * S;
     int dx, dy;
     sp_cand(stage, k, dx, dy);
@@ -448,22 +441,16 @@ __device__ __forceinline__ void sp_stage(const SpLds &L, int stage, int hx, int 
     unsigned tw[2];
     tw[0] = yf == 0 ? sp_tap_word(0, 0) : yf == 1 ? sp_tap_word(1, 0) : yf == 2 ? sp_tap_word(2, 0) : sp_tap_word(3, 0);
     tw[1] = yf == 0 ? sp_tap_word(0, 1) : yf == 1 ? sp_tap_word(1, 1) : yf == 2 ? sp_tap_word(2, 1) : sp_tap_word(3, 1);
-    int tap[8];
 #pragma unroll
-    for (int q = 0; q < 8; q++) tap[q] = (int)(signed char)(tw[q >> 2] >> (8 * (q & 3)));
-    const short *o = L.org + sy * w + sx + lane;
+    for (int q = 0; q < 8; q++) f.tap[q] = (int)(signed char)(tw[q >> 2] >> (8 * (q & 3)));
     int d[S];
+    luma_column<S>(f, t, d);
+    if constexpr (WP) {
 #pragma unroll
-    for (int r = 0; r < S; r++) {
-      int sum = 0;
-#pragma unroll
-      for (int q = 0; q < 8; q++) sum += t[r + q] * tap[q];
-      if constexpr (WP) d[r] = o[r * w] - me_wp_pel(*wp, clip3(0, maxv, wrap16((sum + offset) >> shift)));
-      else d[r] = o[r * w] - clip3(0, maxv, wrap16((sum + offset) >> shift));
+      for (int r = 0; r < S; r++) d[r] = me_wp_pel(*wp, d[r]);
     }
-    const int s = subblock_dist_lanes<S>(d, lane, use_had);
-    if (act && lane == 0) atomicAdd(&s_cost[k], (unsigned)s);
-  }
+    column_cost<S>(d, L.org + sy * w + sx + lane, w, lane, use_had, act, &s_cost[k]);
+  });
 }
 
 // xPatternRefinement's loop (:725-757) over the nine costs of a stage, by the first 16 lanes of wave 0: the costs to the
