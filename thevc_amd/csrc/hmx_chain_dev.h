@@ -164,7 +164,7 @@ __device__ __forceinline__ void wave_chain_valu(char *smem, const SRC &src, cons
     }
     // inverse of all-zero levels is exactly zero, so the reference's "if (uiAbsSum)" needs no branch
     HMX_MARK(N, 6);
-    inv_tq_block<N>(L, gl, active, ts, luma, luma, true, P, row);
+    inv_tq_block<N, (SRC::kPredOpt & kLdsBatch) != 0>(L, gl, active, ts, luma, luma, true, P, row);
     HMX_MARK(N, 7);
     if (active) {
       const int mx = (1 << P.bit_depth) - 1;
@@ -334,11 +334,18 @@ __device__ __forceinline__ void wave_chain_8x2(char *smem, const SRC &src, const
     HMX_MARK(82, 6);
     if (active) {
       if (V.lev_stride == 0) { // four lanes, 16 bytes each, in the order of the addresses: an instruction writes one whole 64-byte line
+        int lw[16]; // the reads of all four pieces, one wait, then the stores
 #pragma unroll
         for (int j = 0; j < 4; j++) {
           const int p = 4 * j + gl, r = p >> 1, c0 = 4 * (p & 1);
-          const i4v o = {level_of(L.tile[r][c0]), level_of(L.tile[r][c0 + 1]), level_of(L.tile[r][c0 + 2]), level_of(L.tile[r][c0 + 3])};
-          piece_store(reinterpret_cast<i4v *>(lev_blk + 4 * p), o);
+#pragma unroll
+          for (int k = 0; k < 4; k++) lw[4 * j + k] = L.tile[r][c0 + k];
+        }
+        if constexpr (SRC::kPredOpt & kLdsBatch) pin_regs<16>(lw);
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+          const i4v o = {level_of(lw[4 * j]), level_of(lw[4 * j + 1]), level_of(lw[4 * j + 2]), level_of(lw[4 * j + 3])};
+          piece_store(reinterpret_cast<i4v *>(lev_blk + 4 * (4 * j + gl)), o);
         }
       } else {
 #pragma unroll
@@ -354,12 +361,15 @@ __device__ __forceinline__ void wave_chain_8x2(char *smem, const SRC &src, const
   } else {
     if (active) {
       if (V.lev_stride == 0) {
+        i4v o[4]; // the four loads back to back, then the tile's words
+#pragma unroll
+        for (int j = 0; j < 4; j++) o[j] = *reinterpret_cast<const i4v *>(lev_blk + 4 * (4 * j + gl));
+        if constexpr (SRC::kPredOpt & kLdsBatch) pin_regs<4>(o);
 #pragma unroll
         for (int j = 0; j < 4; j++) {
           const int p = 4 * j + gl, r = p >> 1, c0 = 4 * (p & 1);
-          const i4v o = *reinterpret_cast<const i4v *>(lev_blk + 4 * p);
 #pragma unroll
-          for (int k = 0; k < 4; k++) L.tile[r][c0 + k] = clip3(-32768, 32767, o[k]) & 0xffff;
+          for (int k = 0; k < 4; k++) L.tile[r][c0 + k] = clip3(-32768, 32767, o[j][k]) & 0xffff;
         }
       } else {
 #pragma unroll
@@ -379,18 +389,25 @@ __device__ __forceinline__ void wave_chain_8x2(char *smem, const SRC &src, const
   const int dshift = 6 - tshift;
   int out[16];
   if (ts) {
+    int in[16];
+#pragma unroll
+    for (int k = 0; k < 16; k++) in[k] = L.tile[r0 + (k >> 3)][k & 7];
+    if constexpr (SRC::kPredOpt & kLdsBatch) pin_regs<16>(in);
 #pragma unroll
     for (int k = 0; k < 16; k++) {
-      const int c = dequant_one(level_of(L.tile[r0 + (k >> 3)][k & 7]), qd.iq_scale, dshift);
+      const int c = dequant_one(level_of(in[k]), qd.iq_scale, dshift);
       out[k] = wrap16(tshift > 0 ? (c + (1 << (tshift - 1))) >> tshift : c << (-tshift));
     }
   } else {
-    int mid[16];
+    int mid[16], in[16]; // the sixteen reads of a pass back to back, one wait per pass
+#pragma unroll
+    for (int k = 0; k < 16; k++) in[k] = L.tile[k & 7][r0 + (k >> 3)];
+    if constexpr (SRC::kPredOpt & kLdsBatch) pin_regs<16>(in);
 #pragma unroll
     for (int h = 0; h < 2; h++) {
       int c[N];
 #pragma unroll
-      for (int k = 0; k < N; k++) c[k] = wrap16(dequant_one(level_of(L.tile[k][r0 + h]), qd.iq_scale, dshift));
+      for (int k = 0; k < N; k++) c[k] = wrap16(dequant_one(level_of(in[8 * h + k]), qd.iq_scale, dshift));
       inv_pass<N>(c, mid + 8 * h, 7, false);
     }
     wave_sync(); // every lane has read its levels
@@ -400,12 +417,10 @@ __device__ __forceinline__ void wave_chain_8x2(char *smem, const SRC &src, const
     }
     wave_sync();
 #pragma unroll
-    for (int h = 0; h < 2; h++) {
-      int u[N];
+    for (int k = 0; k < 16; k++) in[k] = L.tile[k & 7][r0 + (k >> 3)];
+    if constexpr (SRC::kPredOpt & kLdsBatch) pin_regs<16>(in);
 #pragma unroll
-      for (int k = 0; k < N; k++) u[k] = L.tile[k][r0 + h];
-      inv_pass<N>(u, out + 8 * h, 12 - (B - 8), false);
-    }
+    for (int h = 0; h < 2; h++) inv_pass<N>(in + 8 * h, out + 8 * h, 12 - (B - 8), false);
     wave_sync();
   }
   HMX_MARK(82, 8);
@@ -924,9 +939,14 @@ __device__ __forceinline__ void wave_chain_32(char *smem, const SRC &src, const 
         HMX_MARK(32, 5);
         quant_sbh_diag<32, 16>(L, lane, lane, true, coef, [&](int k) { return mrow(k, h); }, [&](int) { return r; }, luma, diag_group_org<32>(lane), P);
       }
+      // the lane's sixteen words back to back and ONE wait (pin_regs), then the stores: word by word, each store stood behind the
+      // wait for its own read
+#pragma unroll
+      for (int g = 0; g < 16; g++) v[g] = L.tile[mrow(g, h)][r];
+      if constexpr (SRC::kPredOpt & kLdsBatch) pin_regs<16>(v);
 #pragma unroll
       for (int g = 0; g < 16; g++) {
-        v[g] = level_of(L.tile[mrow(g, h)][r]);
+        v[g] = level_of(v[g]);
         stream_store(&lev0[__umul24((unsigned)mrow(g, h), (unsigned)lstep)], v[g]);
       }
     } else {
@@ -1471,7 +1491,9 @@ struct PackedSrc {
   static constexpr bool kRdoq = RDOQ;          // likewise (doubles, and the 4x4 lane's private arrays)
   // the batched general angular path (kPredPairs, intra_pred_samples) and main reference (kPredMainRef, build_main_ref); the SSE and RDOQ variants have no register to spare and spill with
   // them (vgpr_spill_count 0 -> 2 and 0 -> 4): they keep the plain forms
-  static constexpr int kPredOpt = (RDOQ || SSE) ? 0 : kPredPairs | kPredMainRef;
+  // (kLdsBatch, the batched level and inverse-pass reads of the chains, goes with them: a batch holds sixteen registers at once, and the
+  // two variants were not tried with it)
+  static constexpr int kPredOpt = (RDOQ || SSE) ? 0 : kPredPairs | kPredMainRef | kLdsBatch;
   static constexpr bool kPadClamp = true;
   __device__ __forceinline__ bool want_sse() const { return SSE; }
   __device__ __forceinline__ int picture() const { return pic0 + (int)(ft.t.plane >> 2); }

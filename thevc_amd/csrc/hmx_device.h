@@ -649,7 +649,9 @@ __device__ __forceinline__ AngParam ang_param(int mode) {
 //   kPredMainRef  this routine fully unrolled in three phases, as the padding pass of refs_gather_pad: every source index without a
 //                 branch, all the reads back to back (lds_gather), then the writes, predicated for the entries outside (lim, last];
 //                 an entry that is not written reads the corner, R[2N].  As a run-time loop every entry is a read, a wait and a write.
-constexpr int kPredPairs = 1, kPredMainRef = 2;
+//   kLdsBatch     (the chains themselves, hmx_chain_dev.h) the LDS reads of the level read-back, the level store and the inverse
+//                 passes back to back with one wait per batch (pin_regs), where the compiler waits for every word or pair
+constexpr int kPredPairs = 1, kPredMainRef = 2, kLdsBatch = 4;
 template <int N, int NL, int OPT = 0>
 __device__ __forceinline__ void build_main_ref(const int *R, int *ME, int mode, int gl) {
   if (mode < 2) return;

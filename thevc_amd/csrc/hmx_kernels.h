@@ -180,8 +180,29 @@ __device__ __forceinline__ void wave_global_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 }
 
-__device__ __forceinline__ int group_sum(int v, int width) { // sum over `width` consecutive lanes
-  for (int off = width >> 1; off > 0; off >>= 1) v += __shfl_xor(v, off, width);
+// Sum over `width` consecutive lanes (an aligned group), the result in every lane of the group.  Widths up to 16 stay inside a DPP
+// row: each step adds the partner lane's value through the VALU's own lane crossbar (quad_perm [1,0,3,2] and [2,3,0,1]: lane ^ 1 and
+// lane ^ 2; row_half_mirror: lane 7 - i of the half row, which holds the other quad's total; row_mirror: lane 15 - i, the other half
+// row's) -- no address, no LDS crossbar, no lgkmcnt wait.  Widths 32 and 64 add the row totals, read from the first lane of each row
+// into scalar registers.  A DPP read from a lane outside EXEC returns 0 (bound_ctrl is set) and v_readlane returns whatever the
+// register holds; no caller depends on either: every lane of a group runs the sum (idle lanes pass 0) and the partners all lie inside the
+// aligned group; a group of 64 is the wave, whose callers stand in wave-uniform control flow, and a group of 32 picks between two
+// scalars of which a half that does not execute could only spoil its own.
+template <int CTRL>
+__device__ __forceinline__ int dpp_add(int v) { return v + __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, true); }
+__device__ __forceinline__ int group_sum(int v, int width) {
+  if (width > 64 || (width & (width - 1))) __builtin_trap(); // (a constant in every caller)
+  if (width >= 2) v = dpp_add<0xB1>(v);  // quad_perm [1,0,3,2]
+  if (width >= 4) v = dpp_add<0x4E>(v);  // quad_perm [2,3,0,1]
+  if (width >= 8) v = dpp_add<0x141>(v); // row_half_mirror
+  if (width >= 16) v = dpp_add<0x140>(v); // row_mirror
+  if (width == 32) {
+    const int a = __builtin_amdgcn_readlane(v, 0) + __builtin_amdgcn_readlane(v, 16);
+    const int b = __builtin_amdgcn_readlane(v, 32) + __builtin_amdgcn_readlane(v, 48);
+    v = (__lane_id() & 32) ? b : a; // a half whose lanes do not execute hands over stale registers that only it would pick
+  } else if (width == 64) {
+    v = __builtin_amdgcn_readlane(v, 0) + __builtin_amdgcn_readlane(v, 16) + __builtin_amdgcn_readlane(v, 32) + __builtin_amdgcn_readlane(v, 48);
+  }
   return v;
 }
 
@@ -324,6 +345,8 @@ __device__ __forceinline__ int quant_sbh_diag(LT &L, int gl, int lane, bool acti
         const int p = (int)((kDiag4 >> (4 * i)) & 15);
         return go[(p >> 2) * (N + 1) + (p & 3)];
       };
+      // (the first and the chosen word are fetched again at run time: taken from w[] with select16 the two trips go, but the thirty
+      // selects cost more -- 98.74 against 98.19 ms on the default bench, profiles/lds_trips_bench_ab.txt)
       const int bi = sbh_pick(w, ScanOrder(), last, [&](int i) { return at(i); });
       if (bi >= 0) at(bi) = sbh_apply(at(bi));
     }
@@ -403,7 +426,9 @@ __device__ __forceinline__ int dequant_one(int v, int iq_scale, int dshift) { //
 }
 
 // invtransformNxN core: levels in L.tile[row][col] -> residual row gl in out[N].
-template <int N>
+// BATCH: the N reads of each pass back to back with one wait behind them (pin_regs); left to itself the compiler waits for a
+// column in pieces (16x16: three waits over sixteen reads).  The whole-picture chains ask for it, the list kernels do not.
+template <int N, bool BATCH = false>
 __device__ __forceinline__ void inv_tq_block(TuLds<N> &L, int gl, bool active, bool ts, bool use_dst, bool luma,
                                              bool do_dequant, const PicDev &P, int *out) {
   constexpr int LG = Log2<N>::v;
@@ -412,10 +437,10 @@ __device__ __forceinline__ void inv_tq_block(TuLds<N> &L, int gl, bool active, b
   const int dshift = 6 - tshift;
   int c[N], t[N];
 #pragma unroll
-  for (int k = 0; k < N; k++) {
-    int v = ts ? L.tile[gl][k] : L.tile[k][gl];
-    c[k] = do_dequant ? dequant_one(level_of(v), qd.iq_scale, dshift) : v;
-  }
+  for (int k = 0; k < N; k++) c[k] = ts ? L.tile[gl][k] : L.tile[k][gl];
+  if constexpr (BATCH) pin_regs<N>(c);
+#pragma unroll
+  for (int k = 0; k < N; k++) c[k] = do_dequant ? dequant_one(level_of(c[k]), qd.iq_scale, dshift) : c[k];
   if (ts) { // xITransformSkip (:1667-1704)
 #pragma unroll
     for (int k = 0; k < N; k++) out[k] = wrap16(tshift > 0 ? (c[k] + (1 << (tshift - 1))) >> tshift : c[k] << (-tshift));
@@ -433,6 +458,7 @@ __device__ __forceinline__ void inv_tq_block(TuLds<N> &L, int gl, bool active, b
   int u[N];
 #pragma unroll
   for (int k = 0; k < N; k++) u[k] = L.tile[k][gl];
+  if constexpr (BATCH) pin_regs<N>(u);
   inv_pass<N>(u, out, 12 - (B - 8), use_dst);
   wave_sync();
 }
