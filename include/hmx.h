@@ -759,7 +759,7 @@ int hmx_batch_subpel_search(hmx_ctx *ctx, const hmx_me_unit *units, int n, const
  * Vector costs, tie rules, the TZ walk, ruiSAD = best - vector cost and the results' layout do not change.  All sums are uint32_t.
  * HMX_ERR_ARG, on the host before anything is launched, with the entry and the row named in hmx_last_error: everything the
  * unweighted entry refuses, and a row with weight[0] outside -128..255, offset[0] outside -128..127, log2_denom[0] above 7 or
- * reserved != 0.  Not covered: xGetSSEw, chroma, NS_HAD shapes, the encoder's weight estimation (WeightPredAnalysis). */
+ * reserved != 0.  Not covered: xGetSSEw, chroma, NS_HAD shapes.  The rows themselves: hmx_wp_estimate_slices below. */
 int hmx_batch_fullpel_search_wp(hmx_ctx *ctx, const hmx_me_unit *units, int n, const hmx_pic *refs, int n_refs, const hmx_pic *org,
                                 int pic_w, int pic_h, int margin_x, int margin_y, uint32_t lambda, hmx_me_result *d_result,
                                 uint32_t *d_cost_map, const hmx_wp *wp);
@@ -769,6 +769,93 @@ int hmx_batch_tz_search_wp(hmx_ctx *ctx, const hmx_me_unit *units, const hmx_tz_
 int hmx_batch_subpel_search_wp(hmx_ctx *ctx, const hmx_me_unit *units, int n, const hmx_me_result *d_int, const hmx_pic *refs,
                                int n_refs, const hmx_pic *org, int pic_w, int pic_h, int margin_x, int margin_y, uint32_t lambda,
                                int use_had, hmx_subpel_result *d_result, uint32_t *d_stage_cost, const hmx_wp *wp);
+
+/* ------------------------------------------------------------------------------------------------
+ * The encoder's estimation of the rows: WeightPredAnalysis (TLibEncoder/WeightPredAnalysis.cpp), which TEncSlice::compressSlice
+ * runs per slice (TEncSlice.cpp:688-711) when the PPS has getUseWP() or getWPBiPred(), as this reference is built
+ * (WP_PARAM_RANGE_LIMIT 1).  The reductions over whole pictures are device entries; the arithmetic per (list, reference,
+ * component) is host code without a context, because every consumer above takes its hmx_wp tables as host arrays.  B = the
+ * context's bit depth; chroma planes are (pic_w >> 1) x (pic_h >> 1).  Picture sizes: any positive even pic_w, pic_h up to 65536.
+ * ---------------------------------------------------------------------------------------------- */
+/* xCalcACDCParamSlice (WeightPredAnalysis.cpp:71-108 -> xCalcDCValue :451-464, xCalcACValue :474-487) for n_pics (1..65535)
+ * ORIGINAL pictures in one launch per pass: per component dc = (sum of x + (n >> 1)) / n and ac = sum of |x - dc|, n = samples of
+ * the plane.  The reference computes them for every picture of a sequence with either PPS flag set, intra pictures included
+ * (TEncSlice.cpp:689-692).  pics: host array [n_pics] of descriptors of device planes (each picture its own planes and strides;
+ * margins and unaligned planes allowed); d_out (device): [n_pics].  The DC of the second pass is formed on the device from the
+ * first pass's sums: nothing returns to the host in between.  Samples lie in [0, 2^15).
+ * HMX_ERR_ARG, before anything is launched: a null pointer, a null plane, n_pics out of range, an odd or non-positive size. */
+typedef struct hmx_wp_acdc_param {
+  int64_t ac[3], dc[3]; /* wpACDCParam::iAC, iDC (TLibCommon/TComSlice.h) of Y, Cb, Cr */
+} hmx_wp_acdc_param;
+int hmx_wp_acdc_multi(hmx_ctx *ctx, int n_pics, const hmx_pic *pics, int pic_w, int pic_h, hmx_wp_acdc_param *d_out);
+int hmx_wp_acdc(hmx_ctx *ctx, const hmx_pic *pic, int pic_w, int pic_h, hmx_wp_acdc_param *d_out); /* = _multi with n_pics = 1 */
+/* xCalcSADvalueWP (WeightPredAnalysis.cpp:501-517) as xSelectWP calls it (:333-350), for n_jobs (1..65535) pairs of an original
+ * and a reference picture's RECONSTRUCTION in one launch.  Job j reads org[jobs[j].org] and rec[jobs[j].rec] ONCE and gives, per
+ * component c with (w, o, d) = the job's row and rd = d + B - 8,
+ *   d_out[(j * 3 + c) * 2 + 0] = sum of |(org << d) - (rec * w + (o << rd))|      (the row)
+ *   d_out[(j * 3 + c) * 2 + 1] = sum of |(org << d) - (rec << d)|                 (the default row of the same denominator)
+ * in Int64, BEFORE the division by the sample count of :516 (hmx_wp_select divides).  org / rec: host arrays of descriptors of
+ * device planes as for hmx_wp_acdc_multi; jobs may share pictures.  d_out (device): n_jobs * 6 values.  Samples lie in [0, 2^B).
+ * Rows: weight -128..255, log2_denom 0..7, chroma offset -128..127 as for the other _wp entries; the LUMA offset may be any
+ * int16, because the reference does not clip it (:279).
+ * HMX_ERR_ARG, on the host before anything is launched, with the job named in hmx_last_error: a null pointer, a null plane,
+ * n_jobs, n_org or n_rec out of range, an odd or non-positive size, an index outside org[] / rec[], a row outside these ranges or
+ * with reserved != 0. */
+typedef struct hmx_wp_sad_job {
+  uint32_t org, rec; /* indices into org[] / rec[] */
+  hmx_wp wp;
+} hmx_wp_sad_job;    /* 24 bytes */
+int hmx_wp_sad_multi(hmx_ctx *ctx, int n_jobs, const hmx_wp_sad_job *jobs, const hmx_pic *org, int n_org, const hmx_pic *rec,
+                     int n_rec, int pic_w, int pic_h, int64_t *d_out);
+/* Host helpers, no context, no launch; int64_t and double in the reference's order of operations.
+ * hmx_wp_update_params: xUpdatingWPParameters under the denominator loop of xEstimateWPParamSlice (WeightPredAnalysis.cpp:176-204,
+ * :252-304).  cur: the slice's AC/DC; refs_l0 / refs_l1: those of the ORIGINALS of the reference pictures of the two lists
+ * (getRefPic(...)->getSlice(0)->getWpAcDcParam, :265), n_l1 = 0 for a P slice.  One denominator serves the slice: 6, or 7 when
+ * n_l0 > 3, lowered by one while any weight w has (1 << d) - w outside -128..127.  Per row: weight = (int)(0.5 + (refAC == 0 ? 1.0 :
+ * Clip3(-16.0, 15.0, curAC / refAC)) * (1 << d)), offset = ((curDC << d) - weight * refDC + (1 << (rd - 1))) >> rd, the chroma
+ * offset limited as :282-288, the luma offset NOT clipped.  rows_l0 / rows_l1 [n]: the rows; present_l0 / present_l1 [n]: 1
+ * (bPresentFlag, one per entry: the reference sets its three components together); *log2_denom: the denominator reached.
+ * A weight of 256 at denominator 7 or a luma offset outside -128..127 can come out, as in the reference, whose encoder then
+ * writes a stream outside the coded range; the consumers above refuse such a row.  HMX_ERR_ARG: a null pointer for a list that
+ * has entries, a negative list size, bit_depth outside 8..12. */
+int hmx_wp_update_params(const hmx_wp_acdc_param *cur, const hmx_wp_acdc_param *refs_l0, int n_l0, const hmx_wp_acdc_param *refs_l1,
+                         int n_l1, int bit_depth, hmx_wp *rows_l0, hmx_wp *rows_l1, uint8_t *present_l0, uint8_t *present_l1,
+                         int *log2_denom);
+/* The decision of xSelectWP for one (list, reference) (WeightPredAnalysis.cpp:333-362).  sums: the six values of one job of
+ * hmx_wp_sad_multi; n_luma / n_chroma: samples per plane.  SADWP / SADnoWP = the three components' sums, each divided by its
+ * sample count first (:516); when (double)SADWP / (double)SADnoWP >= 0.99 the three components of *row become (1 << log2_denom,
+ * 0, log2_denom) and *present 0.  0 / 0 is NaN and keeps the row; x / 0 is +inf and resets it. */
+int hmx_wp_select(const int64_t *sums, int64_t n_luma, int64_t n_chroma, int log2_denom, hmx_wp *row, uint8_t *present);
+/* xCheckWPEnable (WeightPredAnalysis.cpp:135-170) for the tables of one slice: *weighted = some entry is present; if none is,
+ * every row becomes (1, 0, 0) (and the reference clears both PPS flags for the slice).  The reference counts the flags of all of
+ * m_wp, entries that an earlier slice with longer lists left behind included; this entry sees the slice's own lists only
+ * (hmx_hm::WeightPredAnalysis keeps m_wp across slices as the reference does). */
+int hmx_wp_check_enable(hmx_wp *rows_l0, uint8_t *present_l0, int n_l0, hmx_wp *rows_l1, uint8_t *present_l1, int n_l1,
+                        int *weighted);
+/* xEstimateWPParamSlice + xCheckWPEnable (TEncSlice.cpp:706-710) for n_slices P / B slices of one picture size: hmx_wp_update_params
+ * per slice, ONE hmx_wp_sad_multi launch and one download for all (list, reference) entries of the call, then hmx_wp_select and
+ * hmx_wp_check_enable.  A random-access pipeline calls it once per GOP position over all its segments.  The call synchronises
+ * the context's stream.  The rows are reported as the reference computes them (see hmx_wp_update_params for what may leave the
+ * consumers' ranges; the call's own SAD step takes the weight 256 that hmx_wp_sad_multi refuses); rows[] / present[] are what
+ * hmx_batch_*_wp, hmx_mc_wp and hmx_wp_sad_multi take.
+ * HMX_ERR_ARG: what the parts refuse; a slice type other than P or B; list 0 empty, a list above HMX_WP_MAX_REFS, list 1 in a P
+ * slice; slices of different sizes; more than 65535 entries in all. */
+#define HMX_WP_MAX_REFS 16 /* MAX_NUM_REF (TLibCommon/CommonDef.h) */
+typedef struct hmx_wp_slice {
+  int slice_type;                          /* HMX_P_SLICE or HMX_B_SLICE */
+  int pic_w, pic_h;
+  const hmx_pic *org;                      /* the slice's original (device planes) */
+  const hmx_wp_acdc_param *acdc, *d_acdc;        /* its AC/DC: a host value, or (acdc NULL) an entry of a device array */
+  int n_refs[2];                           /* getNumRefIdx of list 0 / 1 */
+  const hmx_pic *rec[2];                   /* host arrays [n_refs[l]]: the reference pictures' reconstructions (device planes) */
+  const hmx_wp_acdc_param *ref_acdc[2];          /* host arrays [n_refs[l]] of the AC/DC of their ORIGINALS, or NULL with */
+  const hmx_wp_acdc_param *const *d_ref_acdc[2]; /* host arrays [n_refs[l]] of pointers to device entries */
+  hmx_wp *rows[2];                         /* out, host arrays [n_refs[l]] */
+  uint8_t *present[2];                     /* out, host arrays [n_refs[l]] */
+  int log2_denom;                          /* out: the denominator hmx_wp_update_params reached */
+  int weighted;                            /* out: 0 = no entry present, the slice is predicted without weights */
+} hmx_wp_slice;
+int hmx_wp_estimate_slices(hmx_ctx *ctx, int n_slices, hmx_wp_slice *slices);
 
 /* Deblocking filter, the application part (TLibCommon/TComLoopFilter.cpp:571-922: xEdgeFilterLuma, xEdgeFilterChroma,
  * the pel filters, the strong/weak decision), in place on a reconstructed picture whose size

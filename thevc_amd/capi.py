@@ -126,6 +126,19 @@ class PredChoice(C.Structure):  # hmx_pred_choice
 PRED_CHOICE_DTYPE = np.dtype([("index", "<u4"), ("dist", "<u4"), ("cost", "<u4")])  # hmx_pred_choice
 
 WP_DTYPE = np.dtype([("weight", "<i2", 3), ("offset", "<i2", 3), ("log2_denom", "u1", 3), ("reserved", "u1")])  # hmx_wp
+WP_ACDC_DTYPE = np.dtype([("ac", "<i8", 3), ("dc", "<i8", 3)])  # hmx_wp_acdc_param
+WP_SAD_JOB_DTYPE = np.dtype([("org", "<u4"), ("rec", "<u4"), ("wp", WP_DTYPE)])  # hmx_wp_sad_job
+
+
+class WpAcdc(C.Structure):  # hmx_wp_acdc_param
+    _fields_ = [("ac", C.c_int64 * 3), ("dc", C.c_int64 * 3)]
+
+
+class WpSlice(C.Structure):  # hmx_wp_slice
+    _fields_ = [("slice_type", C.c_int), ("pic_w", C.c_int), ("pic_h", C.c_int), ("org", C.POINTER(Pic)), ("acdc", C.POINTER(WpAcdc)),
+                ("d_acdc", C.c_void_p), ("n_refs", C.c_int * 2), ("rec", C.POINTER(Pic) * 2), ("ref_acdc", C.POINTER(WpAcdc) * 2),
+                ("d_ref_acdc", C.POINTER(C.c_void_p) * 2), ("rows", C.POINTER(Wp) * 2), ("present", C.POINTER(C.c_uint8) * 2),
+                ("log2_denom", C.c_int), ("weighted", C.c_int)]
 
 
 def wp_entry(weight, offset, log2_denom):
@@ -404,6 +417,16 @@ def lib():
                 continue  # an older build loaded for an A/B run: calling the entry still raises
             getattr(L, name).argtypes = at
             getattr(L, name).restype = rt
+        i64 = C.c_int64
+        for name, at in (("hmx_wp_acdc_multi", [vp, ci, C.POINTER(Pic), ci, ci, vp]), ("hmx_wp_acdc", [vp, C.POINTER(Pic), ci, ci, vp]),
+                         ("hmx_wp_sad_multi", [vp, ci, vp, C.POINTER(Pic), ci, C.POINTER(Pic), ci, ci, ci, vp]),
+                         ("hmx_wp_update_params", [vp, vp, ci, vp, ci, ci, vp, vp, vp, vp, C.POINTER(ci)]),
+                         ("hmx_wp_select", [vp, i64, i64, ci, vp, vp]), ("hmx_wp_check_enable", [vp, vp, ci, vp, vp, ci, C.POINTER(ci)]),
+                         ("hmx_wp_estimate_slices", [vp, ci, C.POINTER(WpSlice)])):
+            if "HMX_LIB_PATH" in os.environ and not hasattr(L, name):
+                continue  # an older build loaded for an A/B run: calling the entry still raises
+            getattr(L, name).argtypes = at
+            getattr(L, name).restype = ci
         L.hmx_yuv_frame_bytes.argtypes = [ci, ci, ci]
         L.hmx_yuv_frame_bytes.restype = C.c_size_t
         L.hmx_yuv_unpack.argtypes = [vp, vp, ci, C.POINTER(Pic), ci, ci, ci, ci]
@@ -1055,6 +1078,91 @@ class Context:
             if d_av is not None:
                 d_av.free()
 
+    def wp_acdc(self, pics, w, h, out=None):
+        """hmx_wp_acdc_multi: xCalcACDCParamSlice of n original pictures (DevPictures) as a WP_ACDC_DTYPE array (n,).  out: a DevBuf
+        of n hmx_wp_acdc_param that keeps the values on the device (entry i at out.ptr + 48 * i, what wp_estimate_slices takes as
+        a device entry); the array is returned all the same."""
+        n = len(pics)
+        p = (Pic * n)(*[d.as_pic() for d in pics])
+        buf = out if out is not None else self.alloc(max(n, 1) * WP_ACDC_DTYPE.itemsize)
+        try:
+            self._chk(lib().hmx_wp_acdc_multi(self.h, n, p, w, h, buf.ptr))
+            self.sync()
+            return buf.download(WP_ACDC_DTYPE, n)
+        finally:
+            if out is None:
+                buf.free()
+
+    def wp_sad(self, jobs, orgs, recs, w, h):
+        """hmx_wp_sad_multi: jobs = WP_SAD_JOB_DTYPE array (or (org index, rec index, WP_DTYPE row) triples) over the DevPictures
+        orgs / recs.  Returns int64 (n_jobs, 3, 2): per component the raw sum under the job's row and under the default row."""
+        if not isinstance(jobs, np.ndarray):
+            t = np.zeros(len(jobs), WP_SAD_JOB_DTYPE)
+            for i, (o, r, row) in enumerate(jobs):
+                t[i] = (o, r, row)
+            jobs = t
+        jobs = np.ascontiguousarray(jobs, WP_SAD_JOB_DTYPE)
+        n = len(jobs)
+        o, r = (Pic * len(orgs))(*[d.as_pic() for d in orgs]), (Pic * len(recs))(*[d.as_pic() for d in recs])
+        out = self.alloc(max(n, 1) * 48)
+        try:
+            self._chk(lib().hmx_wp_sad_multi(self.h, n, _hp(jobs), o, len(orgs), r, len(recs), w, h, out.ptr))
+            self.sync()
+            return out.download(np.int64, 6 * n).reshape(n, 3, 2)
+        finally:
+            out.free()
+
+    def wp_estimate_slices(self, slices, w, h):
+        """hmx_wp_estimate_slices.  slices: dicts with slice_type (P_SLICE / B_SLICE), org (DevPicture), acdc (a WP_ACDC_DTYPE value, or
+        a device address of one) and refs: per list a sequence of (rec DevPicture, acdc of the reference's original, value or device
+        address).  Returns per slice a dict: rows (per list a WP_DTYPE array), present (per list uint8), log2_denom, weighted."""
+        n = len(slices)
+        arr, keep, outs = (WpSlice * n)(), [], []
+
+        def host(v):
+            a = WpAcdc()
+            a.ac[:], a.dc[:] = [int(x) for x in v["ac"]], [int(x) for x in v["dc"]]
+            return a
+
+        for i, sl in enumerate(slices):
+            S = arr[i]
+            S.slice_type, S.pic_w, S.pic_h = sl["slice_type"], w, h
+            org = sl["org"].as_pic()
+            keep.append(org)
+            S.org = C.pointer(org)
+            if isinstance(sl["acdc"], int):
+                S.d_acdc = sl["acdc"]
+            else:
+                a = host(sl["acdc"])
+                keep.append(a)
+                S.acdc = C.pointer(a)
+            out = dict(rows=[], present=[])
+            for l, refs in enumerate(list(sl["refs"]) + [()] * (2 - len(sl["refs"]))):
+                m = len(refs)
+                S.n_refs[l] = m
+                rows, present = np.zeros(m, WP_DTYPE), np.zeros(m, np.uint8)
+                out["rows"].append(rows), out["present"].append(present)
+                if not m:
+                    continue
+                rec = (Pic * m)(*[r.as_pic() for r, _ in refs])
+                S.rec[l] = C.cast(rec, C.POINTER(Pic))
+                if all(isinstance(a, int) for _, a in refs):
+                    dev = (C.c_void_p * m)(*[a for _, a in refs])
+                    S.d_ref_acdc[l] = C.cast(dev, C.POINTER(C.c_void_p))
+                    keep.append(dev)
+                else:
+                    vals = (WpAcdc * m)(*[host(a) for _, a in refs])
+                    S.ref_acdc[l] = C.cast(vals, C.POINTER(WpAcdc))
+                    keep.append(vals)
+                S.rows[l] = C.cast(rows.ctypes.data, C.POINTER(Wp))
+                S.present[l] = C.cast(present.ctypes.data, C.POINTER(C.c_uint8))
+                keep.append(rec)
+            outs.append(out)
+        self._chk(lib().hmx_wp_estimate_slices(self.h, n, arr))
+        for i, out in enumerate(outs):
+            out["log2_denom"], out["weighted"] = arr[i].log2_denom, arr[i].weighted
+        return outs
+
     def deblock_strengths(self, n, d_units, d_edge_ver, d_edge_hor, w, h, is_b, d_bs_ver, d_bs_hor):
         """hmx_deblock_strengths_multi: the boundary strengths of n pictures in one launch.  The maps are DevBufs (or device
         addresses) laid out [pic][4x4 unit]; is_b: one flag per picture (B slice)."""
@@ -1096,6 +1204,45 @@ class Context:
         a, b = (Pic * n)(*[p.as_pic() for p in ins]), (Pic * n)(*[p.as_pic() for p in outs])
         self._chk(lib().hmx_sao_picture_multi_avail(self.h, n, a, b, w, h, getattr(d_params, "ptr", d_params), n_lcu,
                                                     getattr(d_avail, "ptr", d_avail)))
+
+
+def wp_update_params(cur, refs_l0, refs_l1, bit_depth):
+    """hmx_wp_update_params: cur a WP_ACDC_DTYPE value, refs_l0 / refs_l1 WP_ACDC_DTYPE arrays (refs_l1 empty for a P slice).
+    Returns (rows_l0, rows_l1, present_l0, present_l1, log2_denom)."""
+    cur = np.ascontiguousarray(cur, WP_ACDC_DTYPE).reshape(1)
+    refs = [np.ascontiguousarray(r, WP_ACDC_DTYPE).reshape(-1) for r in (refs_l0, refs_l1)]
+    rows = [np.zeros(len(r), WP_DTYPE) for r in refs]
+    present = [np.zeros(len(r), np.uint8) for r in refs]
+    d = C.c_int()
+    ptr = lambda a: _hp(a) if len(a) else None
+    rc = lib().hmx_wp_update_params(_hp(cur), ptr(refs[0]), len(refs[0]), ptr(refs[1]), len(refs[1]), bit_depth, ptr(rows[0]), ptr(rows[1]),
+                                    ptr(present[0]), ptr(present[1]), C.byref(d))
+    if rc != 0:
+        raise HmxError(f"hmx_wp_update_params refused its arguments ({rc})")
+    return rows[0], rows[1], present[0], present[1], d.value
+
+
+def wp_select(sums, n_luma, n_chroma, log2_denom, row):
+    """hmx_wp_select: sums int64 [3][2] of one job of wp_sad, row a WP_DTYPE value.  Returns (row, present)."""
+    sums = np.ascontiguousarray(sums, np.int64).reshape(6)
+    row = np.array(row, WP_DTYPE).reshape(1)
+    present = np.ones(1, np.uint8)
+    rc = lib().hmx_wp_select(_hp(sums), n_luma, n_chroma, log2_denom, _hp(row), _hp(present))
+    if rc != 0:
+        raise HmxError(f"hmx_wp_select refused its arguments ({rc})")
+    return row[0], int(present[0])
+
+
+def wp_check_enable(rows_l0, present_l0, rows_l1, present_l1):
+    """hmx_wp_check_enable: the tables of one slice.  Returns (rows_l0, rows_l1, weighted)."""
+    rows = [np.array(r, WP_DTYPE).reshape(-1) for r in (rows_l0, rows_l1)]
+    present = [np.array(p, np.uint8).reshape(-1) for p in (present_l0, present_l1)]
+    w = C.c_int()
+    ptr = lambda a: _hp(a) if len(a) else None
+    rc = lib().hmx_wp_check_enable(ptr(rows[0]), ptr(present[0]), len(rows[0]), ptr(rows[1]), ptr(present[1]), len(rows[1]), C.byref(w))
+    if rc != 0:
+        raise HmxError(f"hmx_wp_check_enable refused its arguments ({rc})")
+    return rows[0], rows[1], w.value
 
 
 def lf_border_avail(w, h, ctu, slice_id, slice_lf_cross, tile_id=None, lf_cross_tiles=True):

@@ -137,6 +137,7 @@ extern "C" void hmx_destroy(hmx_ctx *c) {
   hipFree(c->arena_d);
   hipFree(c->d_mcmap);
   hipFree(c->d_me_keys);
+  hipFree(c->d_wpest);
   hipFree(c->rdoq_wd);
   hipFree(c->rdoq_wi);
   hipFree(c->rdoq_blocks);

@@ -11,6 +11,7 @@
 //                       complete motion candidates (k_pred_error)
 //   hmx_me.hip          full-search integer motion estimation (SAD, vector-bits cost, search box)
 //   hmx_loop.hip        deblocking, SAO, YUV file formats
+//   hmx_wpest.hip       the encoder's weight estimation (WeightPredAnalysis): AC/DC and weighted SAD reductions, host arithmetic
 // and hmx_lib.hip includes all of them for a single-translation-unit build (-DHMX_PACK_PROFILE builds read device
 // symbols of several parts).  Build: __graft_entry__.build() compiles the parts in parallel and links libhmx.so.
 //
@@ -260,6 +261,8 @@ struct hmx_ctx {
   size_t mcmap_cap = 0;
   unsigned long long *d_me_keys = nullptr; // hmx_batch_fullpel_search: one (cost, raster index) word per unit
   size_t me_keys_cap = 0;
+  void *d_wpest = nullptr; // hmx_wp_acdc_multi: the sample sums between its passes; hmx_wp_estimate_slices: the sums it downloads
+  size_t wpest_cap = 0;
   char *arena_h = nullptr, *arena_d = nullptr;
   size_t arena_cap = 0, arena_head = 0;
   // packed schedule (k_intra_packed): tables of the last call; rebuilt on the device when the pictures / plans change

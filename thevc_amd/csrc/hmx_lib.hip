@@ -14,3 +14,4 @@
 #include "hmx_inter.hip"
 #include "hmx_me.hip"
 #include "hmx_loop.hip"
+#include "hmx_wpest.hip"

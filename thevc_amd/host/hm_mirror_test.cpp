@@ -361,7 +361,79 @@ static int pred_main(int argc, char **argv) {
   return 0;
 }
 
+// Usage: hm_mirror_test wpest <file>: WeightPredAnalysis on recorded slices (tests/test_gpu_wp_estimate.py writes the file and
+// compares with the tables the reference encoder wrote).  The file is int32 words {bit depth, width, height, number of pictures,
+// number of slices}, per picture its original and its reconstruction (three planes each, int16), then per slice {picture, 1 for a
+// P slice, entries of list 0, of list 1} and the picture index of every entry.  Every picture's AC/DC comes from
+// xCalcACDCParamSlice; the slices run through one WeightPredAnalysis in file order.  Prints per slice "useWP wpBiPred" and one
+// line per list with "present weight offset log2denom" of every entry and component.
+static int wpest_main(int argc, char **argv) {
+  if (argc < 3) return 2;
+  FILE *f = fopen(argv[2], "rb");
+  if (!f) return 2;
+  int hd[5];
+  if (fread(hd, sizeof(int), 5, f) != 5) return 2;
+  const int B = hd[0], W = hd[1], H = hd[2], nPics = hd[3], nSlices = hd[4];
+  if (W <= 0 || H <= 0 || (W | H) & 1 || nPics <= 0 || nPics > 64) return 2;
+  hmx_hm::Context ctx(B);
+  hmx_hm::WeightPredAnalysis wpa(ctx);
+  const size_t elems = (size_t)W * H * 3 / 2;
+  std::vector<short> buf(elems);
+  std::vector<hmx_pic> org((size_t)nPics), rec((size_t)nPics);
+  std::vector<hmx_hm::WpSlice> stat((size_t)nPics);
+  std::vector<void *> owned;
+  for (int i = 0; i < nPics; i++)
+    for (hmx_pic *p : {&org[(size_t)i], &rec[(size_t)i]}) {
+      if (fread(buf.data(), sizeof(short), elems, f) != elems) return 2;
+      short *d = nullptr;
+      ctx.check(hmx_malloc(ctx.get(), elems * 2, (void **)&d), "malloc");
+      ctx.check(hmx_upload(ctx.get(), d, buf.data(), elems * 2), "upload");
+      owned.push_back(d);
+      p->plane[0] = d, p->plane[1] = d + (size_t)W * H, p->plane[2] = d + (size_t)W * H * 5 / 4;
+      p->stride[0] = W, p->stride[1] = p->stride[2] = W / 2;
+    }
+  for (int i = 0; i < nPics; i++) { // TEncSlice.cpp:689-692: every picture of the sequence
+    stat[(size_t)i].picYuvOrg = &org[(size_t)i], stat[(size_t)i].width = W, stat[(size_t)i].height = H;
+    wpa.xCalcACDCParamSlice(&stat[(size_t)i]);
+  }
+  for (int s = 0; s < nSlices; s++) {
+    int sh[4];
+    if (fread(sh, sizeof(int), 4, f) != 4) return 2;
+    if (sh[0] < 0 || sh[0] >= nPics || sh[2] < 1 || sh[2] > hmx_hm::MAX_NUM_REF || sh[3] < 0 || sh[3] > hmx_hm::MAX_NUM_REF) return 2;
+    hmx_hm::WpSlice slice = stat[(size_t)sh[0]];
+    slice.isInterP = sh[1] != 0, slice.numRefIdx[0] = sh[2], slice.numRefIdx[1] = sh[3];
+    for (int l = 0; l < 2; l++)
+      for (int i = 0; i < sh[2 + l]; i++) {
+        int q;
+        if (fread(&q, sizeof(int), 1, f) != 1 || q < 0 || q >= nPics) return 2;
+        slice.refPicYuvRec[l][i] = &rec[(size_t)q], slice.refAcdc[l][i] = stat[(size_t)q].acdc;
+      }
+    wpa.xEstimateWPParamSlice(&slice); // TEncSlice.cpp:706-710
+    wpa.xCheckWPEnable(&slice);
+    printf("%d %d\n", slice.useWP ? 1 : 0, slice.wpBiPred ? 1 : 0);
+    for (int l = 0; l < 2; l++) {
+      for (int i = 0; i < sh[2 + l]; i++)
+        for (int yuv = 0; yuv < 3; yuv++) {
+          const hmx_hm::wpScalingParam &w = slice.wpScaling[l][i][yuv];
+          printf("%d %d %d %u ", w.bPresentFlag ? 1 : 0, w.iWeight, w.iOffset, w.uiLog2WeightDenom);
+        }
+      printf("\n");
+    }
+  }
+  fclose(f);
+  for (void *d : owned) hmx_free(ctx.get(), d);
+  return 0;
+}
+
 int main(int argc, char **argv) {
+  if (argc >= 2 && std::string(argv[1]) == "wpest") {
+    try {
+      return wpest_main(argc, argv);
+    } catch (const std::exception &e) {
+      fprintf(stderr, "hm_mirror_test: %s\n", e.what());
+      return 1;
+    }
+  }
   if (argc >= 2 && std::string(argv[1]) == "pred") {
     try {
       return pred_main(argc, argv);

@@ -762,4 +762,128 @@ private:
   Bool m_bUseNIF = false;
 };
 
+// WeightPredAnalysis (TLibEncoder/WeightPredAnalysis.h, .cpp), the estimation of the explicit weights TEncSlice::compressSlice runs
+// per slice (TEncSlice.cpp:688-711).  What the reference reads through TComSlice / TComPic is the WpSlice below: the slice's
+// original and, per entry of its lists, the reference picture's reconstruction and the wpACDCParam of that picture's original
+// (getRefPic(...)->getSlice(0)->getWpAcDcParam).  Pictures are device planes.  The sums over pictures run on the device
+// (hmx_wp_acdc, hmx_wp_sad_multi); the arithmetic per row is libhmx's host code (hmx_wp_update_params, hmx_wp_select,
+// hmx_wp_check_enable).  m_wp persists from slice to slice as in the reference: xCheckWPEnable counts every entry of it.
+static const Int MAX_NUM_REF = 16; // CommonDef.h
+struct wpACDCParam { // TComSlice.h
+  Int64 iAC, iDC;
+};
+struct WpSlice {
+  Bool isInterP = true;                    // TComSlice::isInterP
+  Int numRefIdx[2] = {0, 0};               // getNumRefIdx
+  const hmx_pic *picYuvOrg = nullptr;      // getPic()->getPicYuvOrg()
+  Int width = 0, height = 0;
+  wpACDCParam acdc[3] = {};                // getWpAcDcParam / setWpAcDcParam
+  const hmx_pic *refPicYuvRec[2][MAX_NUM_REF] = {};   // getRefPic(list, idx)->getPicYuvRec()
+  const wpACDCParam *refAcdc[2][MAX_NUM_REF] = {};    // getRefPic(list, idx)->getSlice(0)->getWpAcDcParam
+  Bool useWP = true, wpBiPred = true;      // the PPS flags; xCheckWPEnable clears them
+  wpScalingParam wpScaling[2][MAX_NUM_REF][3] = {}; // setWpScaling
+};
+class WeightPredAnalysis {
+public:
+  explicit WeightPredAnalysis(Context &c) : m_c(c) { // :47-65
+    for (Int iList = 0; iList < 2; iList++)
+      for (Int iRefIdx = 0; iRefIdx < MAX_NUM_REF; iRefIdx++)
+        for (Int comp = 0; comp < 3; comp++) m_wp[iList][iRefIdx][comp] = wpScalingParam{false, 0, 1, 0, 0, 0, 0, 0, 0};
+  }
+  // :71-108
+  Bool xCalcACDCParamSlice(WpSlice *slice) {
+    hmx_wp_acdc_param *d = nullptr, h;
+    m_c.check(hmx_malloc(m_c.get(), sizeof(h), (void **)&d), "xCalcACDCParamSlice");
+    int rc = hmx_wp_acdc(m_c.get(), slice->picYuvOrg, slice->width, slice->height, d);
+    if (rc == HMX_OK) rc = hmx_download(m_c.get(), &h, d, sizeof(h));
+    hmx_free(m_c.get(), d);
+    m_c.check(rc, "xCalcACDCParamSlice");
+    for (Int comp = 0; comp < 3; comp++) slice->acdc[comp] = wpACDCParam{h.ac[comp], h.dc[comp]};
+    return true;
+  }
+  // :176-245 with WP_PARAM_RANGE_LIMIT: the denominator loop over xUpdatingWPParameters, then xSelectWP
+  Bool xEstimateWPParamSlice(WpSlice *slice) {
+    const Int n[2] = {slice->numRefIdx[0], slice->isInterP ? 0 : slice->numRefIdx[1]};
+    hmx_wp_acdc_param cur, refs[2][MAX_NUM_REF];
+    hmx_wp rows[2][MAX_NUM_REF];
+    uint8_t present[2][MAX_NUM_REF];
+    pack(slice->acdc, &cur);
+    for (Int l = 0; l < 2; l++)
+      for (Int i = 0; i < n[l]; i++) pack(slice->refAcdc[l][i], &refs[l][i]);
+    Int iDenom = 0;
+    if (hmx_wp_update_params(&cur, refs[0], n[0], refs[1], n[1], m_c.bitDepth(), rows[0], rows[1], present[0], present[1], &iDenom) != HMX_OK)
+      throw std::runtime_error("xEstimateWPParamSlice: hmx_wp_update_params refused its arguments");
+    for (Int l = 0; l < 2; l++)
+      for (Int i = 0; i < n[l]; i++)
+        for (Int comp = 0; comp < 3; comp++)
+          m_wp[l][i][comp] = wpScalingParam{true, rows[l][i].log2_denom[comp], rows[l][i].weight[comp], rows[l][i].offset[comp], 0, 0, 0, 0, 0};
+    xSelectWP(slice, m_wp, iDenom);
+    setWpScaling(slice);
+    return true;
+  }
+  // :313-366: one launch for every (list, reference) of the slice.  hmx_wp_sad_multi refuses the weight 256 that :293 lets through
+  // at denominator 7: the mirror throws there (hmx_wp_estimate_slices costs such a row).
+  Bool xSelectWP(WpSlice *slice, wpScalingParam weightPredTable[2][MAX_NUM_REF][3], Int iDenom) {
+    const Int n[2] = {slice->numRefIdx[0], slice->isInterP ? 0 : slice->numRefIdx[1]};
+    hmx_wp_sad_job jobs[2 * MAX_NUM_REF];
+    hmx_pic recs[2 * MAX_NUM_REF];
+    Int nJobs = 0;
+    for (Int l = 0; l < 2; l++)
+      for (Int i = 0; i < n[l]; i++, nJobs++) {
+        recs[nJobs] = *slice->refPicYuvRec[l][i];
+        jobs[nJobs] = hmx_wp_sad_job{0u, (uint32_t)nJobs, row(weightPredTable[l][i])};
+      }
+    if (!nJobs) return true;
+    int64_t *d = nullptr, sums[2 * MAX_NUM_REF][6];
+    m_c.check(hmx_malloc(m_c.get(), sizeof(int64_t) * 6 * nJobs, (void **)&d), "xSelectWP");
+    int rc = hmx_wp_sad_multi(m_c.get(), nJobs, jobs, slice->picYuvOrg, 1, recs, nJobs, slice->width, slice->height, d);
+    if (rc == HMX_OK) rc = hmx_download(m_c.get(), sums, d, sizeof(int64_t) * 6 * nJobs);
+    hmx_free(m_c.get(), d);
+    m_c.check(rc, "xSelectWP");
+    const Int64 nLuma = (Int64)slice->width * slice->height, nChroma = (Int64)(slice->width >> 1) * (slice->height >> 1);
+    Int j = 0;
+    for (Int l = 0; l < 2; l++)
+      for (Int i = 0; i < n[l]; i++, j++) {
+        hmx_wp r = jobs[j].wp;
+        uint8_t present = 1;
+        hmx_wp_select(sums[j], nLuma, nChroma, iDenom, &r, &present);
+        for (Int comp = 0; comp < 3; comp++)
+          weightPredTable[l][i][comp] = wpScalingParam{present != 0, r.log2_denom[comp], r.weight[comp], r.offset[comp], 0, 0, 0, 0, 0};
+      }
+    return true;
+  }
+  // :135-170
+  void xCheckWPEnable(WpSlice *slice) {
+    Int iPresentCnt = 0;
+    for (Int iList = 0; iList < 2; iList++)
+      for (Int iRefIdx = 0; iRefIdx < MAX_NUM_REF; iRefIdx++)
+        for (Int iComp = 0; iComp < 3; iComp++) iPresentCnt += (Int)m_wp[iList][iRefIdx][iComp].bPresentFlag;
+    if (iPresentCnt == 0) {
+      slice->useWP = false, slice->wpBiPred = false;
+      for (Int iList = 0; iList < 2; iList++)
+        for (Int iRefIdx = 0; iRefIdx < MAX_NUM_REF; iRefIdx++)
+          for (Int iComp = 0; iComp < 3; iComp++) m_wp[iList][iRefIdx][iComp] = wpScalingParam{false, 0, 1, 0, 0, 0, 0, 0, 0};
+      setWpScaling(slice);
+    }
+  }
+
+private:
+  static void pack(const wpACDCParam *a, hmx_wp_acdc_param *o) {
+    for (Int comp = 0; comp < 3; comp++) o->ac[comp] = a[comp].iAC, o->dc[comp] = a[comp].iDC;
+  }
+  static hmx_wp row(const wpScalingParam *w) {
+    hmx_wp r{};
+    for (Int comp = 0; comp < 3; comp++)
+      r.weight[comp] = (int16_t)w[comp].iWeight, r.offset[comp] = (int16_t)w[comp].iOffset, r.log2_denom[comp] = (uint8_t)w[comp].uiLog2WeightDenom;
+    return r;
+  }
+  void setWpScaling(WpSlice *slice) {
+    for (Int l = 0; l < 2; l++)
+      for (Int i = 0; i < MAX_NUM_REF; i++)
+        for (Int comp = 0; comp < 3; comp++) slice->wpScaling[l][i][comp] = m_wp[l][i][comp];
+  }
+  Context &m_c;
+  wpScalingParam m_wp[2][MAX_NUM_REF][3];
+};
+
 } // namespace hmx_hm
