@@ -35,7 +35,8 @@ enum hmx_status {
   HMX_OK = 0,
   HMX_ERR_ARG = -1,     /* unsupported size / null pointer (the reference asserts or falls through) */
   HMX_ERR_DEVICE = -2,  /* HIP runtime error */
-  HMX_ERR_NOMEM = -3
+  HMX_ERR_NOMEM = -3,
+  HMX_ERR_INTERNAL = -4 /* a self-check of the library failed (hmx_aq_thresholds) */
 };
 
 #define HMX_REG_DCT 65535u /* TLibCommon/TypeDef.h:239 */
@@ -856,6 +857,64 @@ typedef struct hmx_wp_slice {
   int weighted;                            /* out: 0 = no entry present, the slice is predicted without weights */
 } hmx_wp_slice;
 int hmx_wp_estimate_slices(hmx_ctx *ctx, int n_slices, hmx_wp_slice *slices);
+
+/* ------------------------------------------------------------------------------------------------
+ * Adaptive QP (--AdaptiveQP=1): TEncPreanalyzer::xPreanalyze (TLibEncoder/TEncPreanalyzer.cpp:64-139), which TEncTop::encode
+ * runs on every input picture (TEncTop.cpp:383-386), and TEncCu::xComputeQP (TEncCu.cpp:1114-1136), which turns its result into
+ * the QP of every coding unit.  The analysis has depths = MaxCuDQPDepth + 1 layers (TEncTop.cpp:440); layer d has units of
+ * part[d] = ctu >> d samples, nx[d] = ceil(pic_w / part[d]) by ny[d] = ceil(pic_h / part[d]) of them in raster order
+ * (TEncPic.cpp:82-89, :135-138).  Arrays per picture: the layers one after the other, layer d at first[d], units row-major;
+ * total units per picture.
+ * Size domain of every entry below (anything else is HMX_ERR_ARG, before anything is launched): ctu 16, 32 or 64; depths >= 1
+ * with ctu >> (depths - 1) >= 8; pic_w and pic_h positive multiples of 8 (what the encoder's padding to the minimum CU size gives
+ * it) up to 16384; n_pics 1..65535; the context's bit depth B 8..12.
+ * ---------------------------------------------------------------------------------------------- */
+#define HMX_AQ_MAX_DEPTHS 4
+typedef struct hmx_aq_geom {
+  int pic_w, pic_h, ctu, depths;
+  int part[HMX_AQ_MAX_DEPTHS];  /* getAQPartWidth = getAQPartHeight */
+  int nx[HMX_AQ_MAX_DEPTHS];    /* getNumAQPartInWidth = getAQPartStride */
+  int ny[HMX_AQ_MAX_DEPTHS];    /* getNumAQPartInHeight */
+  int first[HMX_AQ_MAX_DEPTHS]; /* index of the layer's first unit in a picture's arrays */
+  int total;                    /* units of all layers of one picture */
+} hmx_aq_geom;
+/* The layout of one picture's arrays (host, no context). */
+int hmx_aq_layout(int pic_w, int pic_h, int ctu, int depths, hmx_aq_geom *out);
+/* xPreanalyze (TEncPreanalyzer.cpp:64-139) for n_pics ORIGINAL pictures: every luma sample is read once for all layers.  Per
+ * unit, cut by the picture edge to cw x ch, the four quadrants split at cw >> 1 and ch >> 1; per quadrant avg = double(sum) / N
+ * and var = double(sumsq) / N - avg * avg with N = cw * ch, the samples of the WHOLE unit (:94-126: uiNumPixInAQPart counts every
+ * sample of the unit); activity = 1.0 + min(var) (:129); the layer's average = the activities added in raster order, in double,
+ * over nx * ny (:131-136).  pics: host array [n_pics] of descriptors of device planes as for hmx_wp_acdc_multi (own strides,
+ * margins, unaligned planes); only plane[0] is read.  Samples lie in [0, 2^B).  d_act (device): [n_pics][total] doubles; d_avg
+ * (device): [n_pics][depths] doubles; both are the reference's doubles bit for bit.
+ * HMX_ERR_ARG: a null pointer, a null luma plane, anything outside the size domain. */
+int hmx_aq_activity_multi(hmx_ctx *ctx, int n_pics, const hmx_pic *pics, int pic_w, int pic_h, int ctu, int depths, double *d_act,
+                          double *d_avg);
+int hmx_aq_activity(hmx_ctx *ctx, const hmx_pic *pic, int pic_w, int pic_h, int ctu, int depths, double *d_act, double *d_avg); /* = _multi with n_pics = 1 */
+/* The second half of hmx_aq_activity_multi on its own: the layers' averages (TEncPreanalyzer.cpp:79, :131-137) of activities that
+ * lie on the device, the same ordered sums (tools/aq_bench.py times them through this entry).  HMX_ERR_ARG as above. */
+int hmx_aq_average_multi(hmx_ctx *ctx, int n_pics, int pic_w, int pic_h, int ctu, int depths, const double *d_act, double *d_avg);
+/* xComputeQP (TEncCu.cpp:1114-1136) for every unit of every layer of n_pics pictures: d_qp (device) [n_pics][total], unit u of
+ * layer d = Clip3(-qp_bd_offset, 51, slice_qp[pic] + offset) with S = pow(2.0, range / 6.0) (:1128, formed on the host),
+ * norm = (S * act + avg) / (act + S * avg) (:1131, on the device, not contracted) and offset = Int(floor(log(norm) / log(2.0) * 6.0
+ * + 0.49999)) (:1132-1133).  The logarithm is the HOST's: the device counts the entries of hmx_aq_thresholds(range) that are <=
+ * norm.  A CU at depth D reads layer min(D, depths - 1), unit (cuX / part, cuY / part) (:1121-1124).  range =
+ * getQPAdaptationRange() 1..64; slice_qp: host array [n_pics], each -qp_bd_offset..51; qp_bd_offset = getQpBDOffsetY() 0..48.
+ * HMX_ERR_ARG: a null pointer, anything outside these ranges or the size domain; HMX_ERR_INTERNAL: the threshold table did not
+ * verify (hmx_last_error names the offset). */
+int hmx_aq_qp_map_multi(hmx_ctx *ctx, int n_pics, int pic_w, int pic_h, int ctu, int depths, const double *d_act, const double *d_avg,
+                        const int *slice_qp, int range, int qp_bd_offset, int8_t *d_qp);
+/* out[k + range], k = -range .. range: the smallest double at which floor(log(n) / log(2.0) * 6.0 + 0.49999), evaluated on the host
+ * with libm, reaches k; found by bisection over the doubles and held against the 64 doubles on either side of it (a
+ * disagreement is HMX_ERR_INTERNAL).  Built once per range (1..64). */
+int hmx_aq_thresholds(int range, double *out);
+/* Host scalars, no context.  hmx_aq_offset: iQpOffset of TEncCu.cpp:1128-1133, the literal expression with libm.
+ * hmx_aq_compute_qp: xComputeQP on downloaded data (act: one picture's [total], avg: its [depths]) for the CU at luma position
+ * (cu_x, cu_y) and depth cu_depth; HMX_AQ_NO_QP for a null pointer or a position outside the picture. */
+#define HMX_AQ_NO_QP (-128)
+int hmx_aq_offset(double act, double avg_act, int range);
+int hmx_aq_compute_qp(const hmx_aq_geom *geom, const double *act, const double *avg, int cu_x, int cu_y, int cu_depth, int slice_qp,
+                      int range, int qp_bd_offset);
 
 /* Deblocking filter, the application part (TLibCommon/TComLoopFilter.cpp:571-922: xEdgeFilterLuma, xEdgeFilterChroma,
  * the pel filters, the strong/weak decision), in place on a reconstructed picture whose size

@@ -130,6 +130,28 @@ WP_ACDC_DTYPE = np.dtype([("ac", "<i8", 3), ("dc", "<i8", 3)])  # hmx_wp_acdc_pa
 WP_SAD_JOB_DTYPE = np.dtype([("org", "<u4"), ("rec", "<u4"), ("wp", WP_DTYPE)])  # hmx_wp_sad_job
 
 
+class AqGeom(C.Structure):  # hmx_aq_geom
+    _fields_ = [("pic_w", C.c_int), ("pic_h", C.c_int), ("ctu", C.c_int), ("depths", C.c_int), ("part", C.c_int * 4), ("nx", C.c_int * 4),
+                ("ny", C.c_int * 4), ("first", C.c_int * 4), ("total", C.c_int)]
+
+
+def aq_layout(w, h, ctu, depths):
+    """hmx_aq_layout: the layers of one picture's adaptive-QP arrays"""
+    g = AqGeom()
+    if lib().hmx_aq_layout(w, h, ctu, depths, C.byref(g)) != 0:
+        raise HmxError(f"hmx_aq_layout refused {w}x{h}, ctu {ctu}, {depths} depths")
+    return g
+
+
+def aq_thresholds(qp_range):
+    """hmx_aq_thresholds: float64 (2 * range + 1,), entry k + range = the smallest norm whose offset reaches k"""
+    out = np.zeros(2 * qp_range + 1, np.float64)
+    rc = lib().hmx_aq_thresholds(qp_range, out.ctypes.data)
+    if rc != 0:
+        raise HmxError(f"hmx_aq_thresholds({qp_range}) failed ({rc})")
+    return out
+
+
 class WpAcdc(C.Structure):  # hmx_wp_acdc_param
     _fields_ = [("ac", C.c_int64 * 3), ("dc", C.c_int64 * 3)]
 
@@ -423,6 +445,18 @@ def lib():
                          ("hmx_wp_update_params", [vp, vp, ci, vp, ci, ci, vp, vp, vp, vp, C.POINTER(ci)]),
                          ("hmx_wp_select", [vp, i64, i64, ci, vp, vp]), ("hmx_wp_check_enable", [vp, vp, ci, vp, vp, ci, C.POINTER(ci)]),
                          ("hmx_wp_estimate_slices", [vp, ci, C.POINTER(WpSlice)])):
+            if "HMX_LIB_PATH" in os.environ and not hasattr(L, name):
+                continue  # an older build loaded for an A/B run: calling the entry still raises
+            getattr(L, name).argtypes = at
+            getattr(L, name).restype = ci
+        dbl = C.c_double
+        for name, at in (("hmx_aq_layout", [ci, ci, ci, ci, C.POINTER(AqGeom)]),
+                         ("hmx_aq_activity_multi", [vp, ci, C.POINTER(Pic), ci, ci, ci, ci, vp, vp]),
+                         ("hmx_aq_activity", [vp, C.POINTER(Pic), ci, ci, ci, ci, vp, vp]),
+                         ("hmx_aq_average_multi", [vp, ci, ci, ci, ci, ci, vp, vp]),
+                         ("hmx_aq_qp_map_multi", [vp, ci, ci, ci, ci, ci, vp, vp, vp, ci, ci, vp]),
+                         ("hmx_aq_thresholds", [ci, vp]), ("hmx_aq_offset", [dbl, dbl, ci]),
+                         ("hmx_aq_compute_qp", [C.POINTER(AqGeom), vp, vp, ci, ci, ci, ci, ci, ci])):
             if "HMX_LIB_PATH" in os.environ and not hasattr(L, name):
                 continue  # an older build loaded for an A/B run: calling the entry still raises
             getattr(L, name).argtypes = at
@@ -1092,6 +1126,36 @@ class Context:
         finally:
             if out is None:
                 buf.free()
+
+    def aq_activity(self, pics, w, h, ctu, depths, d_act=None, d_avg=None):
+        """hmx_aq_activity_multi: xPreanalyze of n original pictures (DevPictures).  Returns (act float64 (n, total), avg float64
+        (n, depths)); d_act / d_avg: DevBufs that keep the values on the device for aq_qp_map (the arrays are returned all the same)."""
+        n, g = len(pics), aq_layout(w, h, ctu, depths)
+        p = (Pic * n)(*[d.as_pic() for d in pics])
+        act = d_act if d_act is not None else self.alloc(8 * n * g.total)
+        avg = d_avg if d_avg is not None else self.alloc(8 * n * depths)
+        try:
+            self._chk(lib().hmx_aq_activity_multi(self.h, n, p, w, h, ctu, depths, act.ptr, avg.ptr))
+            self.sync()
+            return act.download(np.float64, n * g.total).reshape(n, g.total), avg.download(np.float64, n * depths).reshape(n, depths)
+        finally:
+            if d_act is None:
+                act.free()
+            if d_avg is None:
+                avg.free()
+
+    def aq_qp_map(self, n, w, h, ctu, depths, d_act, d_avg, slice_qp, qp_range, qp_bd_offset):
+        """hmx_aq_qp_map_multi over the device arrays of aq_activity: int8 (n, total), the xComputeQP result of every unit."""
+        g = aq_layout(w, h, ctu, depths)
+        sq = np.ascontiguousarray(slice_qp, np.int32)
+        assert sq.shape == (n,)
+        out = self.alloc(n * g.total)
+        try:
+            self._chk(lib().hmx_aq_qp_map_multi(self.h, n, w, h, ctu, depths, d_act.ptr, d_avg.ptr, _hp(sq), qp_range, qp_bd_offset, out.ptr))
+            self.sync()
+            return out.download(np.int8, n * g.total).reshape(n, g.total)
+        finally:
+            out.free()
 
     def wp_sad(self, jobs, orgs, recs, w, h):
         """hmx_wp_sad_multi: jobs = WP_SAD_JOB_DTYPE array (or (org index, rec index, WP_DTYPE row) triples) over the DevPictures

@@ -12,6 +12,7 @@
 //   hmx_me.hip          full-search integer motion estimation (SAD, vector-bits cost, search box)
 //   hmx_loop.hip        deblocking, SAO, YUV file formats
 //   hmx_wpest.hip       the encoder's weight estimation (WeightPredAnalysis): AC/DC and weighted SAD reductions, host arithmetic
+//   hmx_aq.hip          adaptive QP (TEncPreanalyzer, TEncCu::xComputeQP): block activities of all layers, layer averages, QP maps
 // and hmx_lib.hip includes all of them for a single-translation-unit build (-DHMX_PACK_PROFILE builds read device
 // symbols of several parts).  Build: __graft_entry__.build() compiles the parts in parallel and links libhmx.so.
 //

@@ -15,3 +15,4 @@
 #include "hmx_me.hip"
 #include "hmx_loop.hip"
 #include "hmx_wpest.hip"
+#include "hmx_aq.hip"

@@ -6,6 +6,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -425,7 +426,61 @@ static int wpest_main(int argc, char **argv) {
   return 0;
 }
 
+// Usage: hm_mirror_test aq <file>: TEncPreanalyzer::xPreanalyze and TEncCu::xComputeQP on one picture (tests/test_gpu_aq.py writes the
+// file and compares with tests/aq_oracle.py).  The file is int32 words {bit depth, width, height, CTU size, AQ depths, slice QP,
+// adaptation range}, then the luma plane (int16).  Prints one line with every layer's average activity as the bits of the double
+// (hex), then per CU depth 0..3 one line with the QP of every CU position of that depth (CU size max(ctu >> depth, 8)) in raster
+// order.
+static int aq_main(int argc, char **argv) {
+  if (argc < 3) return 2;
+  FILE *f = fopen(argv[2], "rb");
+  if (!f) return 2;
+  int hd[7];
+  if (fread(hd, sizeof(int), 7, f) != 7) return 2;
+  const int B = hd[0], W = hd[1], H = hd[2], ctu = hd[3], depths = hd[4], sliceQp = hd[5], range = hd[6];
+  if (W <= 0 || H <= 0 || W > 4096 || H > 4096) return 2;
+  std::vector<short> luma((size_t)W * H);
+  if (fread(luma.data(), sizeof(short), luma.size(), f) != luma.size()) return 2;
+  fclose(f);
+  hmx_hm::Context ctx(B);
+  short *d = nullptr;
+  ctx.check(hmx_malloc(ctx.get(), luma.size() * 2, (void **)&d), "malloc");
+  ctx.check(hmx_upload(ctx.get(), d, luma.data(), luma.size() * 2), "upload");
+  hmx_pic org{};
+  org.plane[0] = d, org.stride[0] = W;
+  hmx_hm::TEncPic pic;
+  pic.create(&org, W, H, (unsigned)ctu, (unsigned)depths);
+  hmx_hm::TEncPreanalyzer pre(ctx);
+  pre.xPreanalyze(&pic);
+  for (unsigned l = 0; l < pic.getMaxAQDepth(); l++) {
+    const double a = pic.getAQLayer(l)->getAvgActivity();
+    unsigned long long bits;
+    memcpy(&bits, &a, 8);
+    printf("%016llx ", bits);
+  }
+  printf("\n");
+  hmx_hm::TEncCu cu;
+  cu.setAdaptiveQP(true, range);
+  cu.setSlice(&pic, sliceQp, 6 * (B - 8));
+  for (unsigned depth = 0; depth < 4; depth++) {
+    const int size = std::max(ctu >> depth, 8);
+    for (int y = 0; y < H; y += size)
+      for (int x = 0; x < W; x += size) printf("%d ", cu.xComputeQP((unsigned)x, (unsigned)y, depth));
+    printf("\n");
+  }
+  hmx_free(ctx.get(), d);
+  return 0;
+}
+
 int main(int argc, char **argv) {
+  if (argc >= 2 && std::string(argv[1]) == "aq") {
+    try {
+      return aq_main(argc, argv);
+    } catch (const std::exception &e) {
+      fprintf(stderr, "hm_mirror_test: %s\n", e.what());
+      return 1;
+    }
+  }
   if (argc >= 2 && std::string(argv[1]) == "wpest") {
     try {
       return wpest_main(argc, argv);

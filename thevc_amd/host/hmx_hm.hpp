@@ -6,9 +6,11 @@
 // explicit state here (setBlockState(), the context).  Every call goes to libhmx (HIP); nothing is
 // computed on the host.  Errors: the reference returns Void and asserts; these wrappers throw.
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <stdexcept>
 #include <string>
+#include <vector>
 
 #include "hmx.h"
 
@@ -884,6 +886,93 @@ private:
   }
   Context &m_c;
   wpScalingParam m_wp[2][MAX_NUM_REF][3];
+};
+
+// Adaptive QP: TEncPic's layers (TLibEncoder/TEncPic.h, .cpp), TEncPreanalyzer::xPreanalyze (TEncPreanalyzer.cpp:64-139) and
+// TEncCu::xComputeQP (TEncCu.cpp:1114-1136).  The picture is device planes; xPreanalyze is one hmx_aq_activity call and ONE
+// download that fills the layers' host arrays, which xComputeQP then reads like the reference's (hmx_aq_compute_qp).
+class TEncPicQPAdaptationLayer {
+public:
+  UInt getAQPartWidth() const { return m_uiAQPartWidth; }
+  UInt getAQPartHeight() const { return m_uiAQPartHeight; }
+  UInt getNumAQPartInWidth() const { return m_uiNumAQPartInWidth; }
+  UInt getNumAQPartInHeight() const { return m_uiNumAQPartInHeight; }
+  UInt getAQPartStride() const { return m_uiNumAQPartInWidth; }
+  const Double *getQPAdaptationUnit() const { return m_acTEncAQU; } // the units' activities (TEncQPAdaptationUnit::getActivity), row-major
+  Double getAvgActivity() const { return m_dAvgActivity; }
+
+private:
+  friend class TEncPic;
+  friend class TEncPreanalyzer;
+  UInt m_uiAQPartWidth = 0, m_uiAQPartHeight = 0, m_uiNumAQPartInWidth = 0, m_uiNumAQPartInHeight = 0;
+  const Double *m_acTEncAQU = nullptr;
+  Double m_dAvgActivity = 0.0;
+};
+class TEncPic {
+public:
+  // TEncPic::create (TEncPic.cpp:128-139); uiMaxAQDepth = MaxCuDQPDepth + 1 (TEncTop.cpp:440)
+  void create(const hmx_pic *picYuvOrg, Int iWidth, Int iHeight, UInt uiMaxWidth, UInt uiMaxAQDepth) {
+    if (hmx_aq_layout(iWidth, iHeight, (int)uiMaxWidth, (int)uiMaxAQDepth, &m_geom) != HMX_OK)
+      throw std::runtime_error("TEncPic::create: picture size, CTU size or AQ depth outside hmx_aq_layout's domain");
+    m_picYuvOrg = picYuvOrg;
+    m_act.assign((size_t)m_geom.total + (size_t)m_geom.depths, 0.0);
+    for (Int d = 0; d < m_geom.depths; d++) {
+      TEncPicQPAdaptationLayer &l = m_acAQLayer[d];
+      l.m_uiAQPartWidth = l.m_uiAQPartHeight = (UInt)m_geom.part[d];
+      l.m_uiNumAQPartInWidth = (UInt)m_geom.nx[d], l.m_uiNumAQPartInHeight = (UInt)m_geom.ny[d];
+      l.m_acTEncAQU = m_act.data() + m_geom.first[d];
+    }
+  }
+  const hmx_pic *getPicYuvOrg() const { return m_picYuvOrg; }
+  UInt getMaxAQDepth() const { return (UInt)m_geom.depths; }
+  TEncPicQPAdaptationLayer *getAQLayer(UInt uiDepth) { return &m_acAQLayer[uiDepth]; }
+  const hmx_aq_geom &geom() const { return m_geom; }
+
+private:
+  friend class TEncPreanalyzer;
+  friend class TEncCu;
+  const hmx_pic *m_picYuvOrg = nullptr;
+  hmx_aq_geom m_geom = {};
+  std::vector<Double> m_act; // the activities of all layers, then the layers' averages: what one download brings
+  TEncPicQPAdaptationLayer m_acAQLayer[HMX_AQ_MAX_DEPTHS];
+};
+class TEncPreanalyzer {
+public:
+  explicit TEncPreanalyzer(Context &c) : m_c(c) {}
+  void xPreanalyze(TEncPic *pcEPic) {
+    const hmx_aq_geom &g = pcEPic->m_geom;
+    const size_t n = (size_t)g.total + (size_t)g.depths;
+    Double *d = nullptr;
+    m_c.check(hmx_malloc(m_c.get(), sizeof(Double) * n, (void **)&d), "xPreanalyze");
+    int rc = hmx_aq_activity(m_c.get(), pcEPic->m_picYuvOrg, g.pic_w, g.pic_h, g.ctu, g.depths, d, d + g.total);
+    if (rc == HMX_OK) rc = hmx_download(m_c.get(), pcEPic->m_act.data(), d, sizeof(Double) * n);
+    hmx_free(m_c.get(), d);
+    m_c.check(rc, "xPreanalyze");
+    for (Int l = 0; l < g.depths; l++) pcEPic->m_acAQLayer[l].m_dAvgActivity = pcEPic->m_act[(size_t)g.total + (size_t)l];
+  }
+
+private:
+  Context &m_c;
+};
+class TEncCu {
+public:
+  // what xComputeQP reads through m_pcEncCfg, the slice and the SPS
+  void setAdaptiveQP(Bool bUseAdaptiveQP, Int iQPAdaptationRange) { m_bUseAdaptiveQP = bUseAdaptiveQP, m_iQPAdaptationRange = iQPAdaptationRange; }
+  void setSlice(TEncPic *pcPic, Int iSliceQp, Int iQpBDOffsetY) { m_pcPic = pcPic, m_iSliceQp = iSliceQp, m_iQpBDOffsetY = iQpBDOffsetY; }
+  // :1114-1136 for the CU at luma position (cuPelX, cuPelY)
+  Int xComputeQP(UInt uiCUPelX, UInt uiCUPelY, UInt uiDepth) const {
+    if (!m_bUseAdaptiveQP) return std::min(51, std::max(-m_iQpBDOffsetY, m_iSliceQp));
+    const hmx_aq_geom &g = m_pcPic->m_geom;
+    const Int qp = hmx_aq_compute_qp(&g, m_pcPic->m_act.data(), m_pcPic->m_act.data() + g.total, (int)uiCUPelX, (int)uiCUPelY, (int)uiDepth, m_iSliceQp,
+                                     m_iQPAdaptationRange, m_iQpBDOffsetY);
+    if (qp == HMX_AQ_NO_QP) throw std::runtime_error("xComputeQP: the CU lies outside the picture");
+    return qp;
+  }
+
+private:
+  TEncPic *m_pcPic = nullptr;
+  Bool m_bUseAdaptiveQP = false;
+  Int m_iQPAdaptationRange = 6, m_iSliceQp = 0, m_iQpBDOffsetY = 0;
 };
 
 } // namespace hmx_hm
