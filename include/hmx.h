@@ -461,7 +461,8 @@ int hmx_intra_plan_level(const hmx_intra_plan *plan, int level, uint32_t counts[
  * picture groups whose launches ran concurrently on separate streams (launches per level). */
 int hmx_last_call_shape(const hmx_ctx *ctx, int *schedule, int *stream_groups);
 /* Optional stage timing of whole-picture calls (HIP events on the context's stream): layout conversion
- * in, dependency chain, layout conversion out, of the LAST call issued after hmx_set_timing(ctx, 1). */
+ * in, dependency chain, layout conversion out, of the LAST call issued after hmx_set_timing(ctx, 1).  After
+ * hmx_sao_decide_multi the three values are its candidate kernel, its decision kernel and 0. */
 int hmx_set_timing(hmx_ctx *ctx, int enable);
 int hmx_last_call_timing(hmx_ctx *ctx, float *to_tiled_ms, float *chain_ms, float *from_tiled_ms);
 /* Packed schedule: the part of chain_ms the LAST timed call spent building its schedule tables on the device (0 when it re-used
@@ -1026,9 +1027,9 @@ int hmx_sao_picture_multi_avail(hmx_ctx *ctx, int n_pics, const hmx_pic *in, con
  * Edge class = m_auiEoTable[sign(c - a) + sign(c - b) + 2] (TComSampleAdaptiveOffset.cpp:94; {1, 2, 0, 3, 4}), class 0
  * ("no edge") included; neighbours a, b: (x-1,y),(x+1,y) | (x,y-1),(x,y+1) | (x-1,y-1),(x+1,y+1) | (x+1,y-1),(x-1,y+1), read
  * from the picture across CTU edges.  The NIF path (calcSaoStatsBlock: slice / tile boundaries not crossed,
- * TComSampleAdaptiveOffset.cpp:500) is hmx_sao_stats_multi_avail below.  Not covered: everything after the statistics (offset
- * estimation, estSaoDist, merge, CABAC rates,
- * the quadtree part sums of SAOLcuBasedOptimization = 0: the host sums these per-CTU bins).  |diff| <= 64*64*(2^12 - 1)
+ * TComSampleAdaptiveOffset.cpp:500) is hmx_sao_stats_multi_avail below.  What follows the statistics with SAOLcuBasedOptimization = 1
+ * (offset estimation, estSaoDist, merge, CABAC rates) is hmx_sao_decide_multi further down, which takes d_out as it is.  Not
+ * covered: the quadtree part sums of SAOLcuBasedOptimization = 0 (the host sums these per-CTU bins).  |diff| <= 64*64*(2^12 - 1)
  * fits int32.  HMX_ERR_ARG: a null pointer, n_pics < 1, pic_w or pic_h not a positive multiple of 8. */
 typedef struct hmx_sao_stat {
   int32_t diff, count;
@@ -1045,6 +1046,90 @@ int hmx_sao_stats(hmx_ctx *ctx, const hmx_pic *org, const hmx_pic *rec, int pic_
  * gives what hmx_sao_stats_multi gives with lcu_based = 0.  HMX_ERR_ARG as for hmx_sao_stats_multi, and for a null d_avail. */
 int hmx_sao_stats_multi_avail(hmx_ctx *ctx, int n_pics, const hmx_pic *org, const hmx_pic *rec, int pic_w, int pic_h,
                               const uint8_t *d_avail, hmx_sao_stat *d_out);
+
+/* Sample adaptive offset, the encoder's parameter search with SAOLcuBasedOptimization = 1 (the default, TAppEncCfg.cpp:271):
+ * TEncSampleAdaptiveOffset::rdoSaoUnitAll (TLibEncoder/TEncSampleAdaptiveOffset.cpp:1466-1799) for n_pics pictures, from the bins
+ * of hmx_sao_stats_multi[_avail] to the table hmx_sao_picture_multi[_avail] takes, device to device.  Restated: the constants of
+ * SAOProcess (:1253-1263: m_uiSaoBitIncrease = B - min(B, 10), m_iOffsetTh = 1 << min(B - 5, 5), shift = 2 * (B - 8)); the CTU
+ * walk with allowMergeLeft / allowMergeUp (:1536-1562) and the choice between new parameters, merge left and merge up
+ * (compDistortion[k] + (Double)rate, strict <, in the reference's order, :1663-1748); estSaoTypeDist (:1808-1852: the xRoundIbdi
+ * quotient, the clip to +-(m_iOffsetTh - 1), the sign rule of the edge classes), estSaoDist (:1854) and estIterOffset (:1858-1893:
+ * the (Int) of the band distortions, the rate decrement at the clip value); saoComponentParamDist (:1897-2062) and
+ * sao2ChromaParamDist (:2064-2240): the "off" cost, the band-start search (sums of four doubles in index order, first minimum),
+ * Cb and Cr sharing one type with their own band starts, bestDist / lambda, and the merge candidates' distortions from the
+ * neighbours' final parameters, whose offsets enter estSaoDist as stored, without << m_uiSaoBitIncrease (:2046-2047, :2224-2225;
+ * shows at 12 bit only).  Rates: TEncEntropy::encodeSaoOffset (TEncEntropy.cpp:759-838, with its write to subTypeIdx of edge
+ * types of components 0 and 1, :785), TEncSbac::codeSaoTypeIdx / codeSaoMerge / codeSaoMaxUvlc / codeSAOSign / codeSaoUflc
+ * (TEncSbac.cpp:1562-1716) under TEncBinCABACCounter (TEncBinCoderCABACCounter.cpp:61-101: fractional bits from
+ * ContextModel::getEntropyBits, 32768 per bypass bin, written bits = fracBits >> 15; resetBits keeps the low 15 bits,
+ * TEncBinCoderCABAC.cpp:193; load / store copy them, :178), with the loads and stores between CI_CURR_BEST and CI_TEMP_BEST as the
+ * reference sequences them.  Macros as the fork sets them (TypeDef.h:87-91, 121-130, 147, 218): SAO_SINGLE_MERGE,
+ * SAO_TYPE_SHARING, SAO_TYPE_CODING, SAO_MERGE_ONE_CTX, SAO_ABS_BY_PASS, SAO_ENCODING_CHOICE[_CHROMA], SAO_CHROMA_LAMBDA,
+ * FAST_BIT_EST, FULL_NBIT 0.  CTU size and bit depth (8..12) come from the context.
+ * Not covered: the quadtree search of SAOLcuBasedOptimization = 0 (rdoSaoOnePart, runQuadTreeDecision), SaoLcuBoundary /
+ * interleaved SAO, writing the bitstream.
+ * d_stats (device): what hmx_sao_stats_multi[_avail] wrote, [pic][3][CTU][HMX_SAO_STAT_BINS]; count >= 0 and |diff| <= count *
+ * (2^B - 1), as every real picture gives.  params: HOST array [n_pics].  d_merge_allow (device, may be NULL): [pic][CTU] bytes,
+ * bit 0 = merge left allowed, bit 1 = merge up allowed (hmx_sao_merge_allow); NULL = geometry only.  The first column never
+ * merges left and the first row never merges up, whatever the byte says (:1548-1562).
+ * d_units (device): [pic][3][CTU], the parameters as rdoSaoUnitAll leaves them in saoLcuParam.  d_apply (device, may be NULL):
+ * [pic][3][CTU], the same as hmx_sao_picture_multi takes it: offsets << (B - min(B, 10)), band = sub where type is 4, type -1
+ * everywhere for a component whose enable flag is 0.  d_result (device): [pic].
+ * HMX_ERR_ARG, before anything is launched: a null pointer other than d_merge_allow and d_apply, n_pics outside 1..65535, a size
+ * that is not a positive multiple of 8, a lambda that is not finite and positive, a context state above 127, a fraction
+ * above 32767. */
+typedef struct hmx_sao_decide_param {
+  double lambda_luma, lambda_chroma; /* m_dLambdaLuma / m_dLambdaChroma (SAOProcess :1241-1242) */
+  uint8_t enable[2];                 /* bSaoFlag of luma / chroma after :1503-1513 (hmx_sao_rate_flags) */
+  uint8_t ctx_state[2];              /* ContextModel::m_ucState of the merge and the type context at the picture's start
+                                        (hmx_sao_ctx_init) */
+  uint32_t frac;                     /* the fractional bits the coder holds when startSaoEnc runs, below 32768: 0 for a fresh coder.
+                                        Inside the reference encoder they are what the picture's last rate estimate left, because
+                                        TEncBinCABAC::start (TEncBinCoderCABAC.cpp:69-76) does not clear m_fracBits and resetBits
+                                        (:193) keeps its low 15 bits */
+} hmx_sao_decide_param; /* 24 bytes */
+typedef struct hmx_sao_unit { /* SaoLcuParam as coded: 8 bytes */
+  int8_t type;       /* typeIdx: -1 off, 0..3 edge, 4 band */
+  uint8_t sub;       /* subTypeIdx: the band start for type 4; for edge types the type (luma, Cb) or 0 (Cr), TEncEntropy.cpp:780-786 */
+  int8_t offset[4];  /* unscaled */
+  uint8_t merge_left, merge_up;
+} hmx_sao_unit;
+typedef struct hmx_sao_result {
+  uint32_t num_no_sao[2]; /* numNoSao of :1751-1759 (chroma counts 2 per CTU) */
+  uint8_t ctx_state[2];   /* the two context states after the last CTU */
+  uint8_t reserved[2];
+  uint32_t frac;          /* m_fracBits after the last CTU (below 32768) */
+} hmx_sao_result; /* 16 bytes */
+int hmx_sao_decide_multi(hmx_ctx *ctx, int n_pics, const hmx_sao_stat *d_stats, int pic_w, int pic_h,
+                         const hmx_sao_decide_param *params, const uint8_t *d_merge_allow, hmx_sao_unit *d_units,
+                         hmx_sao_lcu *d_apply, hmx_sao_result *d_result);
+int hmx_sao_decide(hmx_ctx *ctx, const hmx_sao_stat *d_stats, int pic_w, int pic_h, const hmx_sao_decide_param *param,
+                   const uint8_t *d_merge_allow, hmx_sao_unit *d_units, hmx_sao_lcu *d_apply,
+                   hmx_sao_result *d_result); /* = _multi with n_pics = 1 */
+/* Statistics, decision and application of a batch in order on the context's stream, device buffers only: hmx_sao_stats_multi
+ * (lcu_based = 1) -> hmx_sao_decide_multi -> hmx_sao_picture_multi from rec to out, or with d_avail (device, [pic][CTU] bytes of
+ * hmx_lf_border_avail; NULL = the plain path) the three _avail entries.  d_stats, d_units, d_apply, d_result: device buffers of
+ * the sizes above, all required.  HMX_ERR_ARG as for the three entries, before anything is launched. */
+int hmx_sao_encode_multi(hmx_ctx *ctx, int n_pics, const hmx_pic *org, const hmx_pic *rec, const hmx_pic *out, int pic_w, int pic_h,
+                         const hmx_sao_decide_param *params, const uint8_t *d_merge_allow, const uint8_t *d_avail,
+                         hmx_sao_stat *d_stats, hmx_sao_unit *d_units, hmx_sao_lcu *d_apply, hmx_sao_result *d_result);
+/* Host helpers, no context.  hmx_sao_ctx_init: the two context states startSaoEnc (:530-546) leaves after resetEntropy
+ * (TEncSbac.cpp:112-160): ContextModel::init (ContextModel.cpp:56-65) of INIT_SAO_MERGE_FLAG and INIT_SAO_TYPE_IDX
+ * (ContextTables.h:383, 414) for slice_type (the reference's SliceType: 0 B, 1 P, 2 I; with cabac_init_flag the table index
+ * resetEntropy substitutes, TEncSbac.cpp:117-121) and the slice QP; state[0] = merge, state[1] = type.  The fraction is hmx_sao_decide_param::frac. */
+int hmx_sao_ctx_init(int slice_type, int qp, uint8_t *state);
+/* m_depthSaoRate (:1503-1513, :1788-1789): flags gives bSaoFlag of luma and chroma for a picture of hierarchy depth `depth`
+ * (off when depth > 0 and the rate of depth - 1 exceeds SAO_ENCODING_RATE 0.75 / SAO_ENCODING_RATE_CHROMA 0.5, TypeDef.h:127-130);
+ * update stores num_no_sao / n_ctu and num_no_sao / (2 n_ctu) of a decided picture.  A zeroed state is the encoder's start. */
+#define HMX_SAO_RATE_DEPTHS 4
+typedef struct hmx_sao_rate_state {
+  double rate[2][HMX_SAO_RATE_DEPTHS];
+} hmx_sao_rate_state;
+int hmx_sao_rate_flags(const hmx_sao_rate_state *state, int depth, uint8_t *enable);
+int hmx_sao_rate_update(hmx_sao_rate_state *state, int depth, const uint32_t *num_no_sao, int n_ctu);
+/* allowMergeLeft / allowMergeUp of :1536-1562 from the CTU maps hmx_lf_border_avail takes (tile_id may be NULL: one tile):
+ * out[CTU] bit 0 = the left CTU exists and shares slice and tile, bit 1 = the same for the CTU above. */
+int hmx_sao_merge_allow(int pic_w, int pic_h, int ctu_size, const uint32_t *slice_id, const uint32_t *tile_id, uint8_t *out);
 
 /* Planar 4:2:0 YUV frames, the format either side of the path (TLibVideoIO/TVideoIOYuv.cpp:226-480, SURVEY.md
  * 8f rank 4).  d_file (device) holds one frame as the file does: 8-bit or 16-bit little-endian samples, Y then

@@ -461,6 +461,15 @@ def lib():
                 continue  # an older build loaded for an A/B run: calling the entry still raises
             getattr(L, name).argtypes = at
             getattr(L, name).restype = ci
+        for name, at in (("hmx_sao_decide_multi", [vp, ci, vp, ci, ci, vp, vp, vp, vp, vp]),
+                         ("hmx_sao_decide", [vp, vp, ci, ci, vp, vp, vp, vp, vp]),
+                         ("hmx_sao_encode_multi", [vp, ci, C.POINTER(Pic), C.POINTER(Pic), C.POINTER(Pic), ci, ci, vp, vp, vp, vp, vp, vp, vp]),
+                         ("hmx_sao_ctx_init", [ci, ci, vp]), ("hmx_sao_rate_flags", [vp, ci, vp]),
+                         ("hmx_sao_rate_update", [vp, ci, vp, ci]), ("hmx_sao_merge_allow", [ci, ci, ci, vp, vp, vp])):
+            if "HMX_LIB_PATH" in os.environ and not hasattr(L, name):
+                continue  # an older build loaded for an A/B run: calling the entry still raises
+            getattr(L, name).argtypes = at
+            getattr(L, name).restype = ci
         L.hmx_yuv_frame_bytes.argtypes = [ci, ci, ci]
         L.hmx_yuv_frame_bytes.restype = C.c_size_t
         L.hmx_yuv_unpack.argtypes = [vp, vp, ci, C.POINTER(Pic), ci, ci, ci, ci]
@@ -1269,6 +1278,71 @@ class Context:
         self._chk(lib().hmx_sao_picture_multi_avail(self.h, n, a, b, w, h, getattr(d_params, "ptr", d_params), n_lcu,
                                                     getattr(d_avail, "ptr", d_avail)))
 
+    def sao_decide(self, d_stats, n, w, h, params, merge_allow=None, want_apply=True, keep=False):
+        """hmx_sao_decide_multi: the encoder's SAO parameter search of n pictures from the device bins of hmx_sao_stats_multi
+        (d_stats: a DevBuf or device address).  params: SAO_DECIDE_PARAM_DTYPE (n,) (sao_decide_params builds it); merge_allow:
+        uint8 (n, n_lcu) bytes of sao_merge_allow, or None (geometry only).  Returns (units SAO_UNIT_DTYPE (n, 3, n_lcu), apply
+        SAO_LCU_DTYPE (n, 3, n_lcu) or None, result SAO_RESULT_DTYPE (n,)).  keep=True returns the three DevBufs instead (apply is
+        what sao_pictures takes as d_params); the caller frees them."""
+        ctu = self.ctu_size
+        n_lcu = -(-w // ctu) * -(-h // ctu)
+        params = np.ascontiguousarray(params, SAO_DECIDE_PARAM_DTYPE).reshape(-1)
+        assert len(params) == n
+        d_units = self.alloc(n * 3 * n_lcu * SAO_UNIT_DTYPE.itemsize)
+        d_apply = self.alloc(n * 3 * n_lcu * SAO_LCU_DTYPE.itemsize) if want_apply else None
+        d_res = self.alloc(n * SAO_RESULT_DTYPE.itemsize)
+        d_ma = None
+        try:
+            if merge_allow is not None:
+                merge_allow = np.ascontiguousarray(merge_allow, np.uint8)
+                assert merge_allow.shape == (n, n_lcu), merge_allow.shape
+                d_ma = self.to_device(merge_allow)
+            self._chk(lib().hmx_sao_decide_multi(self.h, n, getattr(d_stats, "ptr", d_stats), w, h, _hp(params),
+                                                 None if d_ma is None else d_ma.ptr, d_units.ptr,
+                                                 None if d_apply is None else d_apply.ptr, d_res.ptr))
+            self.sync()
+            if keep:
+                bufs = (d_units, d_apply, d_res)
+                d_units = d_apply = d_res = None
+                return bufs
+            return (d_units.download(SAO_UNIT_DTYPE).reshape(n, 3, n_lcu),
+                    None if d_apply is None else d_apply.download(SAO_LCU_DTYPE).reshape(n, 3, n_lcu),
+                    d_res.download(SAO_RESULT_DTYPE))
+        finally:
+            for b in (d_units, d_apply, d_res, d_ma):
+                if b is not None:
+                    b.free()
+
+    def sao_encode(self, orgs, recs, outs, w, h, params, merge_allow=None, avail=None):
+        """hmx_sao_encode_multi: statistics, decision and application of n pictures (DevPictures: originals, deblocked pictures,
+        outputs) in order on the context's stream.  avail: uint8 (n, n_lcu) bytes of lf_border_avail for the availability path.
+        Returns (units, apply, result) as sao_decide does."""
+        n = len(orgs)
+        assert n == len(recs) == len(outs) and n > 0
+        ctu = self.ctu_size
+        n_lcu = -(-w // ctu) * -(-h // ctu)
+        params = np.ascontiguousarray(params, SAO_DECIDE_PARAM_DTYPE).reshape(-1)
+        assert len(params) == n
+        o, r, t = [(Pic * n)(*[p.as_pic() for p in ps]) for ps in (orgs, recs, outs)]
+        bufs = [self.alloc(n * 3 * n_lcu * SAO_STAT_BINS * 8), self.alloc(n * 3 * n_lcu * SAO_UNIT_DTYPE.itemsize),
+                self.alloc(n * 3 * n_lcu * SAO_LCU_DTYPE.itemsize), self.alloc(n * SAO_RESULT_DTYPE.itemsize)]
+        try:
+            for a in (merge_allow, avail):
+                if a is not None:
+                    a = np.ascontiguousarray(a, np.uint8)
+                    assert a.shape == (n, n_lcu), a.shape
+                bufs.append(None if a is None else self.to_device(a))
+            ptr = lambda b: None if b is None else b.ptr  # noqa: E731
+            self._chk(lib().hmx_sao_encode_multi(self.h, n, o, r, t, w, h, _hp(params), ptr(bufs[4]), ptr(bufs[5]), bufs[0].ptr,
+                                                 bufs[1].ptr, bufs[2].ptr, bufs[3].ptr))
+            self.sync()
+            return (bufs[1].download(SAO_UNIT_DTYPE).reshape(n, 3, n_lcu), bufs[2].download(SAO_LCU_DTYPE).reshape(n, 3, n_lcu),
+                    bufs[3].download(SAO_RESULT_DTYPE))
+        finally:
+            for b in bufs:
+                if b is not None:
+                    b.free()
+
 
 def wp_update_params(cur, refs_l0, refs_l1, bit_depth):
     """hmx_wp_update_params: cur a WP_ACDC_DTYPE value, refs_l0 / refs_l1 WP_ACDC_DTYPE arrays (refs_l1 empty for a P slice).
@@ -1328,6 +1402,68 @@ def lf_border_avail(w, h, ctu, slice_id, slice_lf_cross, tile_id=None, lf_cross_
 
 SAO_STAT_BINS = 52  # HMX_SAO_STAT_BINS
 SAO_EO_TABLE = (1, 2, 0, 3, 4)  # m_auiEoTable (TComSampleAdaptiveOffset.cpp:94): sign(c - a) + sign(c - b) + 2 -> class
+
+
+SAO_LCU_DTYPE = np.dtype([("type", "i1"), ("band", "u1"), ("offset", "i1", 4)])  # hmx_sao_lcu
+SAO_UNIT_DTYPE = np.dtype([("type", "i1"), ("sub", "u1"), ("offset", "i1", 4), ("merge_left", "u1"), ("merge_up", "u1")])  # hmx_sao_unit
+SAO_DECIDE_PARAM_DTYPE = np.dtype([("lambda_luma", "<f8"), ("lambda_chroma", "<f8"), ("enable", "u1", 2), ("ctx_state", "u1", 2),
+                                   ("frac", "<u4")])  # hmx_sao_decide_param
+SAO_RESULT_DTYPE = np.dtype([("num_no_sao", "<u4", 2), ("ctx_state", "u1", 2), ("reserved", "u1", 2), ("frac", "<u4")])  # hmx_sao_result
+SAO_RATE_DEPTHS = 4  # HMX_SAO_RATE_DEPTHS
+
+
+def sao_ctx_init(slice_type, qp):
+    """hmx_sao_ctx_init: the merge and type context states at the start of a picture; slice_type 0 B, 1 P, 2 I."""
+    st = np.zeros(2, np.uint8)
+    rc = lib().hmx_sao_ctx_init(slice_type, qp, _hp(st))
+    if rc != 0:
+        raise HmxError(f"hmx_sao_ctx_init refused its arguments ({rc})")
+    return st
+
+
+def sao_decide_params(lambdas, enables, states, fracs=None):
+    """SAO_DECIDE_PARAM_DTYPE (n,) from per-picture (lambda_luma, lambda_chroma), (luma, chroma) flags, (merge, type) states and
+    starting fractions (None: 0, a fresh coder)"""
+    p = np.zeros(len(lambdas), SAO_DECIDE_PARAM_DTYPE)
+    for i, (lam, en, st) in enumerate(zip(lambdas, enables, states)):
+        p[i]["lambda_luma"], p[i]["lambda_chroma"] = lam
+        p[i]["enable"], p[i]["ctx_state"] = (1 if en[0] else 0, 1 if en[1] else 0), st
+        p[i]["frac"] = 0 if fracs is None else fracs[i]
+    return p
+
+
+class SaoRateState:
+    """hmx_sao_rate_state with hmx_sao_rate_flags / hmx_sao_rate_update: m_depthSaoRate across the pictures of a sequence"""
+
+    def __init__(self):
+        self.rate = np.zeros((2, SAO_RATE_DEPTHS), np.float64)
+
+    def flags(self, depth):
+        en = np.zeros(2, np.uint8)
+        rc = lib().hmx_sao_rate_flags(_hp(self.rate), depth, _hp(en))
+        if rc != 0:
+            raise HmxError(f"hmx_sao_rate_flags refused its arguments ({rc})")
+        return en
+
+    def update(self, depth, num_no_sao, n_ctu):
+        nn = np.ascontiguousarray(num_no_sao, np.uint32).reshape(2)
+        rc = lib().hmx_sao_rate_update(_hp(self.rate), depth, _hp(nn), n_ctu)
+        if rc != 0:
+            raise HmxError(f"hmx_sao_rate_update refused its arguments ({rc})")
+
+
+def sao_merge_allow(w, h, ctu, slice_id, tile_id=None):
+    """hmx_sao_merge_allow: one byte per CTU, bit 0 = merge left allowed, bit 1 = merge up allowed"""
+    sid = np.ascontiguousarray(slice_id, np.uint32).reshape(-1)
+    tid = None if tile_id is None else np.ascontiguousarray(tile_id, np.uint32).reshape(-1)
+    n_ctu = -(-w // ctu) * -(-h // ctu) if w > 0 and h > 0 and ctu > 0 else 0
+    if len(sid) != n_ctu or (tid is not None and len(tid) != n_ctu):
+        raise ValueError("sao_merge_allow: one slice id (and tile id) per CTU")
+    out = np.zeros(n_ctu, np.uint8)
+    rc = lib().hmx_sao_merge_allow(w, h, ctu, _hp(sid), None if tid is None else _hp(tid), _hp(out))
+    if rc != 0:
+        raise HmxError(f"hmx_sao_merge_allow: error {rc}")
+    return out
 
 
 def sao_stats_to_hm(a):

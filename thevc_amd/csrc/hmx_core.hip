@@ -138,6 +138,7 @@ extern "C" void hmx_destroy(hmx_ctx *c) {
   hipFree(c->d_mcmap);
   hipFree(c->d_me_keys);
   hipFree(c->d_wpest);
+  hipFree(c->d_saodec);
   hipFree(c->rdoq_wd);
   hipFree(c->rdoq_wi);
   hipFree(c->rdoq_blocks);

@@ -13,6 +13,7 @@
 //   hmx_loop.hip        deblocking, SAO, YUV file formats
 //   hmx_wpest.hip       the encoder's weight estimation (WeightPredAnalysis): AC/DC and weighted SAD reductions, host arithmetic
 //   hmx_aq.hip          adaptive QP (TEncPreanalyzer, TEncCu::xComputeQP): block activities of all layers, layer averages, QP maps
+//   hmx_saodec.hip      the encoder's SAO parameter search (rdoSaoUnitAll, LCU-based): candidates per CTU, the serial decision per picture
 // and hmx_lib.hip includes all of them for a single-translation-unit build (-DHMX_PACK_PROFILE builds read device
 // symbols of several parts).  Build: __graft_entry__.build() compiles the parts in parallel and links libhmx.so.
 //
@@ -264,6 +265,8 @@ struct hmx_ctx {
   size_t me_keys_cap = 0;
   void *d_wpest = nullptr; // hmx_wp_acdc_multi: the sample sums between its passes; hmx_wp_estimate_slices: the sums it downloads
   size_t wpest_cap = 0;
+  void *d_saodec = nullptr; // hmx_sao_decide_multi: the candidate records between its two kernels
+  size_t saodec_cap = 0;
   char *arena_h = nullptr, *arena_d = nullptr;
   size_t arena_cap = 0, arena_head = 0;
   // packed schedule (k_intra_packed): tables of the last call; rebuilt on the device when the pictures / plans change

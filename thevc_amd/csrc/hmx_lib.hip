@@ -16,3 +16,4 @@
 #include "hmx_loop.hip"
 #include "hmx_wpest.hip"
 #include "hmx_aq.hip"
+#include "hmx_saodec.hip"

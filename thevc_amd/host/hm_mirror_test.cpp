@@ -472,7 +472,58 @@ static int aq_main(int argc, char **argv) {
   return 0;
 }
 
+// Usage: hm_mirror_test sao_decide <file>: TEncSampleAdaptiveOffset::rdoSaoUnitAll on two pictures in a row, the second at
+// hierarchy depth 1 under the rate state the first left (tests/test_gpu_sao_decide.py writes the file and compares with
+// tests/sao_decision_oracle.py).  The file is int32 words {bit depth, width, height, CTU size, slice type, slice QP, fraction}, two
+// doubles {lambda, lambda chroma}, then the bins of the two pictures (int32 [2][3][CTU][52][2]).  Prints per picture one line
+// "bSaoFlag bSaoFlag numNoSao numNoSao state state frac" and per component and CTU "type sub o0 o1 o2 o3 left up".
+static int sao_decide_main(int argc, char **argv) {
+  if (argc < 3) return 2;
+  FILE *f = fopen(argv[2], "rb");
+  if (!f) return 2;
+  int hd[7];
+  double lam[2];
+  if (fread(hd, sizeof(int), 7, f) != 7 || fread(lam, sizeof(double), 2, f) != 2) return 2;
+  const int B = hd[0], W = hd[1], H = hd[2], ctu = hd[3];
+  if (W <= 0 || H <= 0 || W > 4096 || H > 4096 || ctu < 16) return 2;
+  const int n = ((W + ctu - 1) / ctu) * ((H + ctu - 1) / ctu);
+  std::vector<hmx_sao_stat> bins((size_t)2 * 3 * n * HMX_SAO_STAT_BINS);
+  if (fread(bins.data(), sizeof(hmx_sao_stat), bins.size(), f) != bins.size()) return 2;
+  fclose(f);
+  hmx_hm::Context ctx(B, 0, ctu);
+  hmx_sao_stat *d_stats = nullptr;
+  hmx_sao_unit *d_units = nullptr;
+  hmx_sao_result *d_res = nullptr;
+  ctx.check(hmx_malloc(ctx.get(), bins.size() * sizeof(hmx_sao_stat), (void **)&d_stats), "malloc");
+  ctx.check(hmx_malloc(ctx.get(), (size_t)3 * n * sizeof(hmx_sao_unit), (void **)&d_units), "malloc");
+  ctx.check(hmx_malloc(ctx.get(), sizeof(hmx_sao_result), (void **)&d_res), "malloc");
+  ctx.check(hmx_upload(ctx.get(), d_stats, bins.data(), bins.size() * sizeof(hmx_sao_stat)), "upload");
+  hmx_hm::TEncSampleAdaptiveOffset sao(ctx);
+  std::vector<hmx_sao_unit> units((size_t)3 * n);
+  for (int pic = 0; pic < 2; pic++) {
+    hmx_hm::TEncSampleAdaptiveOffset::SAOParam sp;
+    sao.startSaoEnc(hd[4], hd[5], (unsigned)hd[6]);
+    sao.rdoSaoUnitAll(&sp, d_stats + (size_t)pic * 3 * n * HMX_SAO_STAT_BINS, W, H, n, lam[0], lam[1], pic, nullptr, d_units, nullptr, d_res);
+    ctx.check(hmx_download(ctx.get(), units.data(), d_units, units.size() * sizeof(hmx_sao_unit)), "download");
+    printf("%d %d %u %u %u %u %u\n", (int)sp.bSaoFlag[0], (int)sp.bSaoFlag[1], sp.result.num_no_sao[0], sp.result.num_no_sao[1],
+           (unsigned)sp.result.ctx_state[0], (unsigned)sp.result.ctx_state[1], sp.result.frac);
+    for (const hmx_sao_unit &u : units)
+      printf("%d %d %d %d %d %d %d %d\n", (int)u.type, (int)u.sub, (int)u.offset[0], (int)u.offset[1], (int)u.offset[2], (int)u.offset[3],
+             (int)u.merge_left, (int)u.merge_up);
+  }
+  hmx_free(ctx.get(), d_stats), hmx_free(ctx.get(), d_units), hmx_free(ctx.get(), d_res);
+  return 0;
+}
+
 int main(int argc, char **argv) {
+  if (argc >= 2 && std::string(argv[1]) == "sao_decide") {
+    try {
+      return sao_decide_main(argc, argv);
+    } catch (const std::exception &e) {
+      fprintf(stderr, "hm_mirror_test: %s\n", e.what());
+      return 1;
+    }
+  }
   if (argc >= 2 && std::string(argv[1]) == "aq") {
     try {
       return aq_main(argc, argv);

@@ -733,9 +733,9 @@ private:
 };
 
 // TEncSampleAdaptiveOffset, the statistics pass (TEncSampleAdaptiveOffset.cpp:859-1124, calcSaoStatsCuOrg with SAO_SKIP_RIGHT;
-// :571-854, calcSaoStatsBlock, when m_bUseNIF): one call for every CTU and component of a picture, on the device; the parameter
-// search (rdoSaoUnitAll's offset estimation, distortion, merge and rates) stays with the caller and reads the downloaded bins
-// through ctuStats.
+// :571-854, calcSaoStatsBlock, when m_bUseNIF): one call for every CTU and component of a picture, on the device; and the
+// parameter search with SAOLcuBasedOptimization = 1, rdoSaoUnitAll (:1466-1799), on the bins where they lie.  A caller that
+// runs a search of its own (the quadtree of SAOLcuBasedOptimization = 0) reads the downloaded bins through ctuStats.
 typedef long long Int64;
 class TEncSampleAdaptiveOffset {
 public:
@@ -757,11 +757,39 @@ public:
       for (int c = 0; c < 5; c++) stats[t][c] += ctuBins[5 * t + c].diff, count[t][c] += ctuBins[5 * t + c].count;
     for (int k = 1; k <= 32; k++) stats[4][k] += ctuBins[20 + k - 1].diff, count[4][k] += ctuBins[20 + k - 1].count;
   }
+  // What rdoSaoUnitAll reads through m_pcPic and the coder startSaoEnc (:530-546) prepared: the slice type (or the table
+  // resetEntropy substitutes, TEncSbac.cpp:117-121) and QP that initialise the two contexts, and the fractional bits the rate
+  // coder holds at that moment (0 for a fresh coder).
+  void startSaoEnc(Int sliceType, Int sliceQp, UInt fracBits = 0) {
+    uint8_t st[2];
+    m_c.check(hmx_sao_ctx_init(sliceType, sliceQp, st), "startSaoEnc");
+    m_param.ctx_state[0] = st[0], m_param.ctx_state[1] = st[1], m_param.frac = fracBits;
+  }
+  // rdoSaoUnitAll (:1466-1799) for one picture, device to device: d_stats as calcSaoStatsPicture wrote them, d_units /
+  // d_apply (may be nullptr) / d_result as hmx_sao_decide documents them; d_mergeAllow: the bytes of hmx_sao_merge_allow or
+  // nullptr.  bSaoFlag comes from m_depthSaoRate (:1503-1513), which is updated from the downloaded counts (:1788-1789);
+  // the flags and the result are returned through saoParam.
+  struct SAOParam {
+    Bool bSaoFlag[2];
+    hmx_sao_result result;
+  };
+  void rdoSaoUnitAll(SAOParam *saoParam, const hmx_sao_stat *d_stats, Int picWidth, Int picHeight, Int numLcu, Double lambda,
+                     Double lambdaChroma, Int depth, const uint8_t *d_mergeAllow, hmx_sao_unit *d_units, hmx_sao_lcu *d_apply,
+                     hmx_sao_result *d_result) {
+    m_c.check(hmx_sao_rate_flags(&m_depthSaoRate, depth, m_param.enable), "rdoSaoUnitAll (rate flags)");
+    m_param.lambda_luma = lambda, m_param.lambda_chroma = lambdaChroma;
+    m_c.check(hmx_sao_decide(m_c.get(), d_stats, picWidth, picHeight, &m_param, d_mergeAllow, d_units, d_apply, d_result), "rdoSaoUnitAll");
+    m_c.check(hmx_download(m_c.get(), &saoParam->result, d_result, sizeof(hmx_sao_result)), "rdoSaoUnitAll (result)");
+    saoParam->bSaoFlag[0] = m_param.enable[0] != 0, saoParam->bSaoFlag[1] = m_param.enable[1] != 0;
+    m_c.check(hmx_sao_rate_update(&m_depthSaoRate, depth, saoParam->result.num_no_sao, numLcu), "rdoSaoUnitAll (rate update)");
+  }
 
 private:
   Context &m_c;
   const uint8_t *m_dAvail = nullptr;
   Bool m_bUseNIF = false;
+  hmx_sao_rate_state m_depthSaoRate = {};
+  hmx_sao_decide_param m_param = {};
 };
 
 // WeightPredAnalysis (TLibEncoder/WeightPredAnalysis.h, .cpp), the estimation of the explicit weights TEncSlice::compressSlice runs
