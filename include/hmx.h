@@ -629,11 +629,18 @@ int hmx_batch_motionCompensation(hmx_ctx *ctx, const hmx_pu *d_pus, int n, const
  * whole 7 x 7 neighbourhood at once): d_cost[i * n_cand + k] (device) = sum over the unit's 8x8 (4x4 when a side is not a
  * multiple of 8) sub-blocks of the Hadamard sum (use_had) or the SAD, >> (bit depth - 8).  The vector-bits term of
  * xPatternRefinement (TComRdCost::getCost(x, y)) and the choice among candidates stay with the caller.
- * refs / org: device pictures; the references with the reference's margins. */
+ * refs / org: device pictures; the references with the reference's margins.
+ * LIST LENGTH (this entry and the seven others that say "longest list" below).  The host tables of a call travel through the
+ * context's argument arena, 8 MiB = 8388608 bytes, each table rounded up to 256 bytes: R(b) = (b + 255) & ~255.  One call takes
+ * the lists whose rounded tables fit the arena TOGETHER; a longer list is refused with HMX_ERR_NOMEM ("... list too long: split
+ * the call" in hmx_last_error) on the host, before anything is copied, set or launched: the outputs are untouched, the context
+ * goes on working, and the caller splits the list.  Lists up to the limit are served from any state of the context.
+ * Longest list here: R(16 n) + R(4 (n + 1)) + R(2 n_cand) <= 8388608 -- sizeof(hmx_pu) = 16, a prefix entry per unit, the
+ * offsets: n <= 419408. */
 int hmx_batch_subpel_cost(hmx_ctx *ctx, const hmx_pu *pus, int n, const hmx_pic *refs, int n_refs, const hmx_pic *org,
                           const int8_t *offs, int n_cand, int use_had, uint32_t *d_cost);
 /* The same under weighted distortion (see "Weighted distortion in the motion search" below): unit i is weighted with
- * wp[pus[i].ref0]; wp == NULL is hmx_batch_subpel_cost. */
+ * wp[pus[i].ref0]; wp == NULL is hmx_batch_subpel_cost.  Longest list: as hmx_batch_subpel_cost, n <= 419408. */
 int hmx_batch_subpel_cost_wp(hmx_ctx *ctx, const hmx_pu *pus, int n, const hmx_pic *refs, int n_refs, const hmx_pic *org,
                              const int8_t *offs, int n_cand, int use_had, uint32_t *d_cost, const hmx_wp *wp);
 
@@ -672,6 +679,8 @@ typedef struct { int16_t mvx, mvy; uint32_t sad; uint32_t cost; } hmx_me_result;
  * searches against 2 * org - other prediction (removeHighFreq, :4147), which the caller passes as org.  Weighted SAD
  * (xGetSADw) is hmx_batch_fullpel_search_wp, xTZSearch is hmx_batch_tz_search, both below; chroma is not covered.
  * n >= 1 and the boxes together hold fewer than 2^32 candidates; anything else is HMX_ERR_ARG.
+ * Longest list (see LIST LENGTH at hmx_batch_subpel_cost): R(20 n) + 2 R(4 (n + 1)) <= 8388608 -- sizeof(hmx_me_unit) = 20 and
+ * two prefix tables: n <= 299583; a longer one is HMX_ERR_NOMEM before anything is launched.
  * HMX_ERR_ARG, on the host before anything is launched, with the unit named in hmx_last_error: a size outside the set, ref >=
  * n_refs, sub_shift other than 0 or (1 with h > 8), an empty box, a box side above 129 (search range 64), the unit outside the
  * picture, a candidate block reaching outside [-margin, pic + margin) of the reference in either direction. */
@@ -708,7 +717,9 @@ int hmx_batch_fullpel_search(hmx_ctx *ctx, const hmx_me_unit *units, int n, cons
  * refuses for a unit (size, ref, sub_shift, empty box, side above 129, unit outside the picture); a NULL pointer other than the
  * two trace pointers, exactly one of those NULL, trace_cap < 1 with a trace, n < 1, n_refs outside 1..4, range outside 1..64,
  * reserved != 0, a start point outside the box, and the bounding rectangle of box U {(0, 0)} grown by the block reaching outside
- * [-margin, pic + margin) of the reference in either direction. */
+ * [-margin, pic + margin) of the reference in either direction.
+ * Longest list (see LIST LENGTH at hmx_batch_subpel_cost): R(20 n) + R(8 n) <= 8388608 -- sizeof(hmx_me_unit) = 20,
+ * sizeof(hmx_tz_unit) = 8: n <= 299584; a longer one is HMX_ERR_NOMEM before anything is launched. */
 typedef struct { int16_t start_x, start_y; uint16_t range; uint16_t reserved; } hmx_tz_unit; /* 8 bytes */
 typedef struct { int16_t x, y; uint32_t cost; } hmx_tz_point; /* 8 bytes */
 int hmx_batch_tz_search(hmx_ctx *ctx, const hmx_me_unit *units, const hmx_tz_unit *tz, int n, const hmx_pic *refs, int n_refs,
@@ -738,7 +749,9 @@ int hmx_batch_tz_search(hmx_ctx *ctx, const hmx_me_unit *units, const hmx_tz_uni
  * HMX_ERR_ARG, on the host before anything is launched, with the unit named in hmx_last_error: a NULL pointer other than
  * d_stage_cost, n < 1, n_refs outside 1..4, use_had other than 0 or 1, a size outside the set, ref >= n_refs, an empty box, the
  * unit outside the picture, the box grown by the window (columns x + left - 4 .. x + right + w + 3, rows likewise) reaching
- * outside [-margin, pic + margin) in either direction. */
+ * outside [-margin, pic + margin) in either direction.
+ * Longest list: the unit list is the call's only table, R(20 n) <= 8388608: n <= 419430; a longer one is HMX_ERR_NOMEM before
+ * anything is launched. */
 typedef struct { int16_t mvx, mvy; uint32_t dist; uint32_t cost; } hmx_subpel_result; /* quarter samples; 12 bytes */
 int hmx_batch_subpel_search(hmx_ctx *ctx, const hmx_me_unit *units, int n, const hmx_me_result *d_int, const hmx_pic *refs,
                             int n_refs, const hmx_pic *org, int pic_w, int pic_h, int margin_x, int margin_y, uint32_t lambda,
@@ -761,7 +774,10 @@ int hmx_batch_subpel_search(hmx_ctx *ctx, const hmx_me_unit *units, int n, const
  * Vector costs, tie rules, the TZ walk, ruiSAD = best - vector cost and the results' layout do not change.  All sums are uint32_t.
  * HMX_ERR_ARG, on the host before anything is launched, with the entry and the row named in hmx_last_error: everything the
  * unweighted entry refuses, and a row with weight[0] outside -128..255, offset[0] outside -128..127, log2_denom[0] above 7 or
- * reserved != 0.  Not covered: xGetSSEw, chroma, NS_HAD shapes.  The rows themselves: hmx_wp_estimate_slices below. */
+ * reserved != 0.  Not covered: xGetSSEw, chroma, NS_HAD shapes.  The rows themselves: hmx_wp_estimate_slices below.
+ * Longest list: that of the unweighted entry (the table of rows travels as a kernel argument): n <= 299583 for
+ * hmx_batch_fullpel_search_wp, 299584 for hmx_batch_tz_search_wp, 419430 for hmx_batch_subpel_search_wp; a longer one is
+ * HMX_ERR_NOMEM before anything is launched. */
 int hmx_batch_fullpel_search_wp(hmx_ctx *ctx, const hmx_me_unit *units, int n, const hmx_pic *refs, int n_refs, const hmx_pic *org,
                                 int pic_w, int pic_h, int margin_x, int margin_y, uint32_t lambda, hmx_me_result *d_result,
                                 uint32_t *d_cost_map, const hmx_wp *wp);
@@ -1206,7 +1222,10 @@ typedef struct { uint32_t index, dist, cost; } hmx_pred_choice;   /* 12 bytes */
  * prefix array that is not monotonic or does not end at n; a group whose candidates differ in x, y, w, h; for any used list the
  * displaced block grown by the tap window -- columns x + (mvx >> 2) - 3 .. + w + 3, rows likewise, whatever the fraction --
  * reaching outside [-margin, pic + margin) in either direction (conservative; never refuses a vector hmx_clipMv produced for a
- * unit inside a 64x64 CTU with 80-sample margins: the reach is at most 74 samples).  Not covered: chroma, the NS_HAD shapes. */
+ * unit inside a 64x64 CTU with 80-sample margins: the reach is at most 74 samples).  Not covered: chroma, the NS_HAD shapes.
+ * Longest list (see LIST LENGTH at hmx_batch_subpel_cost): R(16 n) + R(4 n) + R(4 (n_groups + 1)) <= 8388608 -- sizeof(hmx_pu) =
+ * 16; the middle term only with bits; costs only counts as n_groups = n.  With bits: n <= 403280 in groups of five, 349504 in
+ * groups of one or costs only; without bits: n <= 419424 costs only.  A longer one is HMX_ERR_NOMEM before anything is launched. */
 int hmx_batch_inter_pred_error(hmx_ctx *ctx, const hmx_pu *cands, const uint32_t *bits, int n, const uint32_t *group_first,
                                int n_groups, const hmx_pic *refs, int n_refs, const hmx_pic *org, int pic_w, int pic_h,
                                int margin_x, int margin_y, uint32_t lambda, int use_had, uint32_t *d_dist, uint32_t *d_cost,
@@ -1214,7 +1233,8 @@ int hmx_batch_inter_pred_error(hmx_ctx *ctx, const hmx_pu *cands, const uint32_t
 /* The same in a weighted slice (TComPrediction.cpp:421-432, :516-535): wp = ONE hmx_mc_wp with the meaning
  * hmx_batch_motionCompensation_wp_multi gives it, luma rows only.  Every used list goes to the 14-bit intermediate; one list is
  * weighted uni-directionally, two lists bi-directionally.  The distortion stays unweighted.  wp == NULL, or both tables NULL, is
- * the unweighted entry.  Also HMX_ERR_ARG: what hmx_batch_motionCompensation_wp_multi refuses for its tables. */
+ * the unweighted entry.  Also HMX_ERR_ARG: what hmx_batch_motionCompensation_wp_multi refuses for its tables.  Longest list: as
+ * hmx_batch_inter_pred_error (the weights travel as a kernel argument). */
 int hmx_batch_inter_pred_error_wp(hmx_ctx *ctx, const hmx_pu *cands, const uint32_t *bits, int n, const uint32_t *group_first,
                                   int n_groups, const hmx_pic *refs, int n_refs, const hmx_pic *org, int pic_w, int pic_h,
                                   int margin_x, int margin_y, uint32_t lambda, int use_had, uint32_t *d_dist, uint32_t *d_cost,

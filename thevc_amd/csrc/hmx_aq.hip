@@ -303,9 +303,11 @@ extern "C" int hmx_aq_qp_map_multi(hmx_ctx *c, int n_pics, int pic_w, int pic_h,
       return fail(c, HMX_ERR_ARG, "hmx_aq_qp_map_multi: slice_qp[" + std::to_string(i) + "] outside -qp_bd_offset..51");
   const AqTable &T = aq_thresholds(range);
   if (!T.why.empty()) return fail(c, HMX_ERR_INTERNAL, "hmx_aq_qp_map_multi: " + T.why);
-  const double *d_thr = static_cast<const double *>(arena_push(c, T.t.data(), sizeof(double) * T.t.size()));
-  const int *d_sqp = static_cast<const int *>(arena_push(c, slice_qp, sizeof(int) * (size_t)n_pics));
-  if (!d_thr || !d_sqp) return fail(c, HMX_ERR_NOMEM, "argument arena");
+  const size_t thr_bytes = sizeof(double) * T.t.size(), sqp_bytes = sizeof(int) * (size_t)n_pics; // two tables, one launch: reserved together
+  if (const int r = arena_reserve(c, {thr_bytes, sqp_bytes}, "argument arena")) return r;
+  const double *d_thr = static_cast<const double *>(arena_place(c, T.t.data(), thr_bytes));
+  const int *d_sqp = static_cast<const int *>(arena_place(c, slice_qp, sqp_bytes));
+  if (!d_thr || !d_sqp) return fail(c, HMX_ERR_INTERNAL, kArenaOutside);
   const AqQpArgs A{d_act, d_avg, d_thr, d_sqp, d_qp, G, pow(2.0, range / 6.0), (int)T.t.size(), range, -qp_bd_offset};
   hipLaunchKernelGGL(k_aq_qp, dim3((unsigned)((G.total + 255) / 256), (unsigned)n_pics), dim3(256), 0, c->stream, A);
   HIPCHK(c, hipGetLastError());

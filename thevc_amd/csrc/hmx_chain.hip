@@ -584,7 +584,9 @@ static int tpool_convert(hmx_ctx *c, const hmx_tpool *t, int first, int n, const
   for (int i = 0; i < n; i++)
     for (int p = 0; p < 3; p++)
       jobs[(size_t)i * 3 + p] = ConvJob{planes[i].plane[p], planes[i].stride[p], t->geom.pic_w >> (p ? 1 : 0), t->geom.pic_h >> (p ? 1 : 0), tpool_plane(t, first + i, p)};
-  for (size_t done = 0; done < jobs.size();) { // through the argument arena, a few thousand jobs at a time
+  // through the argument arena, a few thousand jobs at a time.  Each part is launched before the next is pushed, so arena_push's
+  // own one-table reservation is enough: a part that wraps waits for the launches of the parts before it (hmx_arena.h)
+  for (size_t done = 0; done < jobs.size();) {
     const size_t part = std::min(jobs.size() - done, (size_t)3 * 8192);
     const ConvJob *d = static_cast<const ConvJob *>(arena_push(c, jobs.data() + done, sizeof(ConvJob) * part));
     if (!d) return fail(c, HMX_ERR_NOMEM, "argument arena");

@@ -232,26 +232,44 @@ LevelsDev to_dev(const hmx_levels *p) {
   return d;
 }
 
-// device copy of a small host table, valid for the kernels issued after it on the context's stream
-void *arena_push(hmx_ctx *c, const void *src, size_t bytes) {
+// ---- argument arena: device copies of small host tables, valid for the kernels issued after them on the context's stream ----
+// A pinned host ring mirrored by a device ring; where a table goes is ArenaCursor's business (hmx_arena.h).  This is the shell
+// around it: the allocation, the wait at a wrap, the two copies.
+static int arena_open(hmx_ctx *c, size_t total, const char *too_long) { // total: of rounded sizes
   const size_t kCap = 8u << 20;
   if (!c->arena_h) {
-    if (hipHostMalloc((void **)&c->arena_h, kCap, hipHostMallocDefault) != hipSuccess) return nullptr;
-    if (hipMalloc((void **)&c->arena_d, kCap) != hipSuccess) return nullptr;
-    c->arena_cap = kCap;
+    if (hipHostMalloc((void **)&c->arena_h, kCap, hipHostMallocDefault) != hipSuccess) return fail(c, HMX_ERR_NOMEM, "argument arena: hipHostMalloc");
+    if (hipMalloc((void **)&c->arena_d, kCap) != hipSuccess) return fail(c, HMX_ERR_NOMEM, "argument arena: hipMalloc");
+    c->arena.cap = kCap;
   }
-  const size_t raw = bytes;
-  bytes = (bytes + 255) & ~(size_t)255;
-  if (bytes > c->arena_cap) return nullptr;
-  if (c->arena_head + bytes > c->arena_cap) { // wrap: everything issued so far has consumed its tables after this
-    if (hipStreamSynchronize(c->stream) != hipSuccess) return nullptr;
-    c->arena_head = 0;
+  switch (c->arena.reserve(total)) {
+  case ArenaCursor::kRefused: return fail(c, HMX_ERR_NOMEM, too_long);
+  case ArenaCursor::kWrap:
+    // The call's tables start at offset 0 again.  The wait is for the EARLIER calls: every kernel issued so far has read its
+    // tables once it returns.  It says nothing about the tables of this call, whose kernel is not launched yet -- they are safe
+    // because all of them were reserved together and lie side by side behind the new head, not because of the wait.
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    break;
+  case ArenaCursor::kStay: break;
   }
-  char *h = c->arena_h + c->arena_head, *d = c->arena_d + c->arena_head;
-  memcpy(h, src, raw);
-  if (hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) return nullptr;
-  c->arena_head += bytes;
+  return HMX_OK;
+}
+int arena_reserve(hmx_ctx *c, std::initializer_list<size_t> sizes, const char *too_long) {
+  size_t total = 0;
+  for (size_t b : sizes) total += ArenaCursor::rounded(b);
+  return arena_open(c, total, too_long);
+}
+void *arena_place(hmx_ctx *c, const void *src, size_t bytes) {
+  const size_t at = c->arena.place(bytes);
+  if (at == ArenaCursor::kNone) return nullptr;
+  char *h = c->arena_h + at, *d = c->arena_d + at;
+  memcpy(h, src, bytes);
+  if (hipMemcpyAsync(d, h, ArenaCursor::rounded(bytes), hipMemcpyHostToDevice, c->stream) != hipSuccess) return nullptr;
   return d;
+}
+void *arena_push(hmx_ctx *c, const void *src, size_t bytes) {
+  if (arena_open(c, ArenaCursor::rounded(bytes), "argument arena (list too long: split the call)")) return nullptr;
+  return arena_place(c, src, bytes);
 }
 
 int grow_dev(hmx_ctx *c, void **p, size_t *cap, size_t need) {

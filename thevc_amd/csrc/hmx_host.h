@@ -38,6 +38,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "hmx_arena.h"
 #include "hmx_kernels.h"
 #include "hmx_rdoq.h"
 
@@ -268,7 +269,7 @@ struct hmx_ctx {
   void *d_saodec = nullptr; // hmx_sao_decide_multi: the candidate records between its two kernels
   size_t saodec_cap = 0;
   char *arena_h = nullptr, *arena_d = nullptr;
-  size_t arena_cap = 0, arena_head = 0;
+  ArenaCursor arena; // where the next table goes (hmx_arena.h)
   // packed schedule (k_intra_packed): tables of the last call; rebuilt on the device when the pictures / plans change
   struct Packed {
     PackPic *d_pics = nullptr;
@@ -431,7 +432,15 @@ QuantDev make_qd(const hmx_qp &qp, int per_base, int slice_type);               
 PicDev make_picdev(const hmx_ctx *c, const hmx_pic_param *pp);
 PlanesDev to_dev(const hmx_pic *p);
 LevelsDev to_dev(const hmx_levels *p);
-void *arena_push(hmx_ctx *c, const void *src, size_t bytes);
+// The argument arena (placement rule: hmx_arena.h).  A call that puts ONE table before its launch uses arena_push.  A call that puts
+// several reserves all of them first -- sizes: the byte counts of its tables, 0 for one it leaves out -- and then places each:
+// arena_reserve refuses a call whose tables do not fit the arena together with HMX_ERR_NOMEM and `too_long` as the text, before
+// anything is copied; arena_place returns NULL for a table the reservation does not cover, which the entry reports as
+// HMX_ERR_INTERNAL (kArenaOutside) -- it is never served by wrapping onto the call's own tables.
+int arena_reserve(hmx_ctx *c, std::initializer_list<size_t> sizes, const char *too_long);
+void *arena_place(hmx_ctx *c, const void *src, size_t bytes);
+void *arena_push(hmx_ctx *c, const void *src, size_t bytes); // NULL: the table alone exceeds the arena, or the copy failed
+constexpr const char *kArenaOutside = "argument arena: a table outside what the call reserved";
 void drop_graphs(hmx_ctx *c); // destroy every recorded whole-picture graph (the stream is idle)
 int grow_dev(hmx_ctx *c, void **p, size_t *cap, size_t need);
 int check_packed_abort(hmx_ctx *c);                                               // hmx_chain.hip

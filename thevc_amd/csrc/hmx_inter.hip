@@ -274,11 +274,12 @@ static int subpel_cost(hmx_ctx *c, const char *name, const hmx_pu *pus, int n, c
     if (offs[k] < -3 || offs[k] > 3) return fail(c, HMX_ERR_ARG, std::string(name) + ": candidate further than 3 quarter samples");
   SubpelArgsWp A{};
   const size_t pu_bytes = sizeof(hmx_pu) * (size_t)n, first_bytes = sizeof(uint32_t) * ((size_t)n + 1);
-  // unit list and prefix through the argument arena (they are the caller's host arrays)
-  A.pus = static_cast<const hmx_pu *>(arena_push(c, pus, pu_bytes));
-  A.first = static_cast<const uint32_t *>(arena_push(c, first.data(), first_bytes));
-  A.offs = static_cast<const signed char *>(arena_push(c, offs, (size_t)2 * n_cand));
-  if (!A.pus || !A.first || !A.offs) return fail(c, HMX_ERR_NOMEM, "argument arena (unit list too long: split the call)");
+  // unit list, prefix and offsets through the argument arena (the caller's host arrays, and a table made from them), reserved together
+  if (const int r = arena_reserve(c, {pu_bytes, first_bytes, (size_t)2 * n_cand}, "argument arena (unit list too long: split the call)")) return r;
+  A.pus = static_cast<const hmx_pu *>(arena_place(c, pus, pu_bytes));
+  A.first = static_cast<const uint32_t *>(arena_place(c, first.data(), first_bytes));
+  A.offs = static_cast<const signed char *>(arena_place(c, offs, (size_t)2 * n_cand));
+  if (!A.pus || !A.first || !A.offs) return fail(c, HMX_ERR_INTERNAL, kArenaOutside);
   A.n = n;
   A.n_cand = n_cand;
   A.use_had = use_had;
@@ -988,10 +989,13 @@ static int pe_launch(hmx_ctx *c, const hmx_pu *cands, const uint32_t *bits, int 
     threads = std::max(threads, std::min(kPeThreads, (w * h / s + 63) & ~63)); // one lane per sub-block column
   }
   PeArgsWp A{};
-  A.cands = static_cast<const hmx_pu *>(arena_push(c, cands, sizeof(hmx_pu) * (size_t)n)); // the caller's host arrays
-  A.bits = bits ? static_cast<const uint32_t *>(arena_push(c, bits, sizeof(uint32_t) * (size_t)n)) : nullptr;
-  A.first = static_cast<const uint32_t *>(arena_push(c, first, sizeof(uint32_t) * ((size_t)n_groups + 1)));
-  if (!A.cands || (bits && !A.bits) || !A.first) return fail(c, HMX_ERR_NOMEM, "argument arena (candidate list too long: split the call)");
+  // the caller's host arrays, reserved together (no bits: no table)
+  const size_t cand_bytes = sizeof(hmx_pu) * (size_t)n, bits_bytes = bits ? sizeof(uint32_t) * (size_t)n : 0, first_bytes = sizeof(uint32_t) * ((size_t)n_groups + 1);
+  if (const int r = arena_reserve(c, {cand_bytes, bits_bytes, first_bytes}, "argument arena (candidate list too long: split the call)")) return r;
+  A.cands = static_cast<const hmx_pu *>(arena_place(c, cands, cand_bytes));
+  A.bits = bits ? static_cast<const uint32_t *>(arena_place(c, bits, bits_bytes)) : nullptr;
+  A.first = static_cast<const uint32_t *>(arena_place(c, first, first_bytes));
+  if (!A.cands || (bits && !A.bits) || !A.first) return fail(c, HMX_ERR_INTERNAL, kArenaOutside);
   for (int r = 0; r < n_refs; r++) A.refs[r] = refs[r];
   A.org = org;
   A.B = c->cfg.bit_depth, A.use_had = use_had, A.lambda = lambda;

@@ -298,17 +298,19 @@ static int me_fullpel(hmx_ctx *c, const char *name, const hmx_me_unit *units, in
     area += (uint64_t)(bw * bh);
   }
   if (area > 0xffffffffull) return fail(c, HMX_ERR_ARG, std::string(name) + ": the boxes hold more than 2^32 - 1 candidates: split the call");
+  // unit list and prefixes through the argument arena (the caller's host array, and tables made from it): the three are reserved
+  // together, so a list they do not fit is refused here, before the key buffer grows and before anything is copied
+  const size_t unit_bytes = sizeof(hmx_me_unit) * (size_t)n, prefix_bytes = sizeof(uint32_t) * ((size_t)n + 1);
+  if (const int r = arena_reserve(c, {unit_bytes, prefix_bytes, prefix_bytes}, "argument arena (unit list too long: split the call)")) return r;
   void *keys = c->d_me_keys;
   const int gr = grow_dev(c, &keys, &c->me_keys_cap, sizeof(unsigned long long) * (size_t)n);
   c->d_me_keys = static_cast<unsigned long long *>(keys);
   if (gr) return gr;
   MeArgsWp A{};
-  const size_t prefix_bytes = sizeof(uint32_t) * ((size_t)n + 1);
-  // unit list and prefixes through the argument arena (the caller's host array, and tables made from it)
-  A.units = static_cast<const hmx_me_unit *>(arena_push(c, units, sizeof(hmx_me_unit) * (size_t)n));
-  A.tile_first = static_cast<const uint32_t *>(arena_push(c, tile_first.data(), prefix_bytes));
-  A.map_first = static_cast<const uint32_t *>(arena_push(c, map_first.data(), prefix_bytes));
-  if (!A.units || !A.tile_first || !A.map_first) return fail(c, HMX_ERR_NOMEM, "argument arena (unit list too long: split the call)");
+  A.units = static_cast<const hmx_me_unit *>(arena_place(c, units, unit_bytes));
+  A.tile_first = static_cast<const uint32_t *>(arena_place(c, tile_first.data(), prefix_bytes));
+  A.map_first = static_cast<const uint32_t *>(arena_place(c, map_first.data(), prefix_bytes));
+  if (!A.units || !A.tile_first || !A.map_first) return fail(c, HMX_ERR_INTERNAL, kArenaOutside);
   A.n = n;
   A.lambda = lambda;
   A.keys = c->d_me_keys;
@@ -868,9 +870,11 @@ static int me_tz(hmx_ctx *c, const char *name, const hmx_me_unit *units, const h
     lds = std::max(lds, sizeof(short) * (size_t)u.w * (size_t)u.h);
   }
   TzArgsWp A{};
-  A.units = static_cast<const hmx_me_unit *>(arena_push(c, units, sizeof(hmx_me_unit) * (size_t)n)); // the caller's host arrays
-  A.tz = static_cast<const hmx_tz_unit *>(arena_push(c, tz, sizeof(hmx_tz_unit) * (size_t)n));
-  if (!A.units || !A.tz) return fail(c, HMX_ERR_NOMEM, "argument arena (unit list too long: split the call)");
+  const size_t unit_bytes = sizeof(hmx_me_unit) * (size_t)n, tz_bytes = sizeof(hmx_tz_unit) * (size_t)n; // the caller's host arrays
+  if (const int r = arena_reserve(c, {unit_bytes, tz_bytes}, "argument arena (unit list too long: split the call)")) return r;
+  A.units = static_cast<const hmx_me_unit *>(arena_place(c, units, unit_bytes));
+  A.tz = static_cast<const hmx_tz_unit *>(arena_place(c, tz, tz_bytes));
+  if (!A.units || !A.tz) return fail(c, HMX_ERR_INTERNAL, kArenaOutside);
   A.max_passes = std::min(kTzPassCap, std::max(1, c->knob.tz_max_passes));
   A.lambda = lambda;
   A.result = d_result;

@@ -168,12 +168,15 @@ const char *layout_pack(const hmx_avail_layout *L, int pic_w, int pic_h, int ctu
 }
 int layout_to_device(hmx_ctx *c, const LayoutHost &H, AvailDev &D) {
   D = H.D;
+  const auto bytes = [](const std::vector<uint32_t> &v) { return v.size() * sizeof(uint32_t); };
+  // up to three maps for one launch of the caller's: reserved together (an empty map takes no room and is not placed)
+  if (const int r = arena_reserve(c, {bytes(H.region), bytes(H.rows), bytes(H.cols)}, "argument arena (layout maps)")) return r;
   auto put = [&](const std::vector<uint32_t> &v, const uint32_t *&dst) -> bool {
     if (v.empty()) return true;
-    dst = static_cast<const uint32_t *>(arena_push(c, v.data(), v.size() * sizeof(uint32_t)));
+    dst = static_cast<const uint32_t *>(arena_place(c, v.data(), bytes(v)));
     return dst != nullptr;
   };
-  if (!put(H.region, D.region) || !put(H.rows, D.rows) || !put(H.cols, D.cols)) return fail(c, HMX_ERR_NOMEM, "argument arena (layout maps)");
+  if (!put(H.region, D.region) || !put(H.rows, D.rows) || !put(H.cols, D.cols)) return fail(c, HMX_ERR_INTERNAL, kArenaOutside);
   return HMX_OK;
 }
 

@@ -173,16 +173,19 @@ __global__ __launch_bounds__(kWpThreads) void k_wp_sad(WpSadArgs A) {
 // ---- what the entries share on the host ----
 const char *const kWpSizeRule = "picture size must be positive and even, at most 65536";
 bool wp_size_ok(int pic_w, int pic_h) { return pic_w > 0 && pic_h > 0 && pic_w % 2 == 0 && pic_h % 2 == 0 && pic_w <= 65536 && pic_h <= 65536; }
-// a table of n pictures in the argument arena; every plane must be there
-int wp_pics(hmx_ctx *c, const char *fn, const hmx_pic *pics, int n, const PlanesDev **d) {
+// a table of n pictures in the argument arena; every plane must be there.  reserved: the caller puts further tables before its
+// launch and has reserved this one with them (arena_reserve)
+int wp_pics(hmx_ctx *c, const char *fn, const hmx_pic *pics, int n, const PlanesDev **d, bool reserved = false) {
   std::vector<PlanesDev> t((size_t)n);
   for (int i = 0; i < n; i++) {
     for (int p = 0; p < 3; p++)
       if (!pics[i].plane[p]) return fail(c, HMX_ERR_ARG, std::string(fn) + ": null plane");
     t[i] = to_dev(&pics[i]);
   }
-  *d = static_cast<const PlanesDev *>(arena_push(c, t.data(), sizeof(PlanesDev) * t.size()));
-  return *d ? HMX_OK : fail(c, HMX_ERR_NOMEM, "argument arena");
+  const size_t bytes = sizeof(PlanesDev) * t.size();
+  *d = static_cast<const PlanesDev *>(reserved ? arena_place(c, t.data(), bytes) : arena_push(c, t.data(), bytes));
+  if (*d) return HMX_OK;
+  return reserved ? fail(c, HMX_ERR_INTERNAL, kArenaOutside) : fail(c, HMX_ERR_NOMEM, "argument arena");
 }
 unsigned wp_grid_x(int pic_h) { return (unsigned)((pic_h + kWpWaves * kWpRowsPerWave - 1) / (kWpWaves * kWpRowsPerWave)); }
 // the rows hmx_wp_sad_multi takes: those of the other _wp entries, but any int16 as the luma offset (WeightPredAnalysis.cpp:279
@@ -241,10 +244,12 @@ static int wp_sad_run(hmx_ctx *c, const char *entry, int max_weight, int n_jobs,
       t[i].w[k] = j.wp.weight[k], t[i].d[k] = j.wp.log2_denom[k], t[i].c[k] = -(j.wp.offset[k] * (1 << (j.wp.log2_denom[k] + B - 8)));
   }
   const PlanesDev *d_org, *d_rec;
-  if (int r = wp_pics(c, entry, org, n_org, &d_org)) return r;
-  if (int r = wp_pics(c, entry, rec, n_rec, &d_rec)) return r;
-  const WpSadJob *d_jobs = static_cast<const WpSadJob *>(arena_push(c, t.data(), sizeof(WpSadJob) * t.size()));
-  if (!d_jobs) return fail(c, HMX_ERR_NOMEM, "argument arena");
+  const size_t job_bytes = sizeof(WpSadJob) * t.size(); // three tables, one launch: reserved together
+  if (int r = arena_reserve(c, {sizeof(PlanesDev) * (size_t)n_org, sizeof(PlanesDev) * (size_t)n_rec, job_bytes}, "argument arena")) return r;
+  if (int r = wp_pics(c, entry, org, n_org, &d_org, true)) return r;
+  if (int r = wp_pics(c, entry, rec, n_rec, &d_rec, true)) return r;
+  const WpSadJob *d_jobs = static_cast<const WpSadJob *>(arena_place(c, t.data(), job_bytes));
+  if (!d_jobs) return fail(c, HMX_ERR_INTERNAL, kArenaOutside);
   HIPCHK(c, hipMemsetAsync(d_out, 0, sizeof(int64_t) * 6 * (size_t)n_jobs, c->stream));
   const WpSadArgs A{d_jobs, d_org, d_rec, reinterpret_cast<u64 *>(d_out), pic_w, pic_h};
   hipLaunchKernelGGL(k_wp_sad, dim3(wp_grid_x(pic_h), 3, (unsigned)n_jobs), dim3(kWpThreads), 0, c->stream, A);
