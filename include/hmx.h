@@ -292,7 +292,7 @@ typedef struct {
 
 typedef struct {
   int pic_w, pic_h;      /* luma size of the picture */
-  int qp;                /* CU QP (pcCU->getQP(0)); one QP per call */
+  int qp;                /* CU QP (pcCU->getQP(0)); one QP per call -- not used for quantisation while a map is set (hmx_set_qp_map) */
   int chroma_qp_offset;  /* PPS cb/cr offset */
   int slice_type;        /* hmx_slice_type */
   int sign_hide;
@@ -500,7 +500,8 @@ int hmx_frame_intra_encode(hmx_ctx *ctx, const hmx_intra_plan *plan, int n_pics,
 int hmx_frame_intra_decode(hmx_ctx *ctx, const hmx_intra_plan *plan, int n_pics, const hmx_pic *rec,
                            const hmx_levels *lev);
 /* The general form: picture i follows plans[i] (every picture its own block structure and modes, as in a
- * real stream); all plans of one call share picture size, QP and slice settings. */
+ * real stream); all plans of one call share picture size, QP and slice settings (the QP of a block comes from the map instead
+ * while hmx_set_qp_map is in force). */
 int hmx_frame_intra_encode_multi(hmx_ctx *ctx, const hmx_intra_plan *const *plans, int n_pics, const hmx_pic *org,
                                  const hmx_pic *rec, const hmx_levels *lev);
 /* The same for the intra blocks of an INTER picture: the plan lists only the intra-coded blocks, and they are
@@ -548,6 +549,39 @@ typedef struct {
   uint32_t *plane[3];
 } hmx_sse;
 int hmx_set_sse_output(hmx_ctx *ctx, const hmx_sse *sse, int n_pics);
+/* A QP per block (cu_qp_delta: adaptive QP, rate control, MaxDeltaQP > 0).  In the reference the QP of a transform block is its
+ * coding unit's, TComDataCU::getQP, applied through TComTrQuant::setQPforQuant; the chroma QP comes from it through
+ * g_aucChromaScale and the PPS offset; the encoder sets it per coding unit in TEncCu::xCompressCU / xComputeQP (TEncCu.cpp:1114-1136).
+ * hmx_set_qp_map sticks until it is changed, like hmx_set_rdoq and hmx_set_sse_output.  d_qp: DEVICE memory, [n_pics][uh][uw] with
+ * uw = ceil(pic_w / 4), uh = ceil(pic_h / 4): one luma QP per 4x4 luma unit in raster order, contiguous per picture -- the layout
+ * hmx_deblock_picture_multi reads as d_qp, so a caller keeps ONE map per picture for the transforms and for deblocking.  Values are
+ * getQP's, -QpBDOffsetY .. 51.  n_pics == 1: one map for every picture of the following calls; otherwise picture i reads map i and a
+ * call with more pictures than maps is HMX_ERR_ARG.  d_qp == NULL switches back to hmx_pic_param.qp, and every call behaves exactly
+ * as without this entry.  The memory stays the caller's and must stay valid until the calls that use it have completed.
+ *   A transform block takes the QP of the unit at its first sample (a chroma block at (x, y): the unit at luma (2x, 2y));
+ * hmx_pic_param.qp is then not used for quantisation; chroma_qp_offset (-12..12), slice_type (rounding 171 / 85) and sign_hide keep
+ * their meaning.  The host cannot see the bytes: the kernels clamp what they read to -QpBDOffsetY .. 51 before it indexes their
+ * table (built per call on the host, entry [QP + QpBDOffset][luma, chroma], the chroma entry through hmx_setQPforQuant), and the
+ * unit to the map.  A bad byte gives a meaningless block, never an access outside a table.
+ *   Honoured by: the whole-picture chain on the PACKED schedule -- hmx_frame_intra_encode / _decode, _multi, _onto, _resident, with
+ * hmx_set_sse_output beside them -- and the block-list transform entries hmx_batch_transformNxN,
+ * hmx_batch_residual_transformNxN[_multi], hmx_batch_residual_transform_recon[_sse]_multi and hmx_batch_invtransformNxN[_multi]
+ * (picture i of a _multi call reads map i).  With a map set a whole-picture call that resolves to the level or the wave schedule is
+ * HMX_ERR_ARG, and so is one with RDOQ set (lambda and the bit estimates are per picture there, and the reference changes lambda
+ * with the QP); both before anything is launched, hmx_last_error says which.  The map kernel has one wave-item shape per size class
+ * (64 4x4 blocks, eight 8x8 blocks): HMX_PACK_SLOTS4 / HMX_PACK_SLOTS8 do not apply to it.
+ *   NOT covered: hmx_batch_xRateDistOptQuant and the scalar drop-ins (they take their QP per call), RDOQ with a map, the level and
+ * wave schedules, and the deblocking QP of coding units without a coded residual in real streams (they carry the PREDICTED QP,
+ * which only a parser knows). */
+int hmx_set_qp_map(hmx_ctx *ctx, const int8_t *d_qp, int n_pics);
+/* The reference ENCODER's flat quantiser (xQuant, built with ADAPTIVE_QP_SELECTION) takes its scale from the block's QP but its right
+ * shift iQBits from the SLICE's base QP (TComTrQuant.cpp:1161-1231: cQpBase from getSliceQpBase(); chroma: the base through
+ * g_aucChromaScale without the PPS offset, :1175-1190); dequantisation uses the block's QP alone.  With one QP per call the two are
+ * the same number.  With a map they are not: hmx_set_qp_map_base(ctx, 1, slice_qp_base) makes the forward quantiser of the calls that
+ * honour the map shift by the base QP's period, which reproduces the levels the reference encoder writes under --AdaptiveQP=1;
+ * (ctx, 0, 0), the default, shifts by the block's own QP (per of the block's QP: what a quantiser that follows the block QP alone
+ * does).  The decoder direction is not affected.  slice_qp_base: -QpBDOffsetY .. 51, else HMX_ERR_ARG.  Sticks like hmx_set_qp_map. */
+int hmx_set_qp_map_base(hmx_ctx *ctx, int on, int slice_qp_base);
 
 /* Pictures RESIDENT in the library's working layout: CTU blocks in raster order, 4x4 tiles in
  * Z-order inside a CTU, groups of up to 64 pictures interleaved 8x8 quad by quad.  The whole-picture entry points above
@@ -921,6 +955,13 @@ int hmx_aq_average_multi(hmx_ctx *ctx, int n_pics, int pic_w, int pic_h, int ctu
  * verify (hmx_last_error names the offset). */
 int hmx_aq_qp_map_multi(hmx_ctx *ctx, int n_pics, int pic_w, int pic_h, int ctu, int depths, const double *d_act, const double *d_avg,
                         const int *slice_qp, int range, int qp_bd_offset, int8_t *d_qp);
+/* From the layers to the map hmx_set_qp_map and hmx_deblock_picture_multi read, on the device: d_qp [n_pics][pic_h / 4][pic_w / 4]
+ * (device) gets, for every 4x4 luma unit, the QP of the coding unit that covers it -- d_cu_depth [n_pics][pic_h / 4][pic_w / 4]
+ * (device) holds that CU's depth D, and the unit reads layer min(D, depths - 1) of d_layer_qp (hmx_aq_qp_map_multi's output), unit
+ * (x / part, y / part) (TEncCu.cpp:1121-1124).  A depth byte above the last layer is clamped like any other.  Size domain and
+ * refusals as above: HMX_ERR_ARG for a null pointer or anything outside the domain, before anything is launched. */
+int hmx_aq_unit_qp_multi(hmx_ctx *ctx, int n_pics, int pic_w, int pic_h, int ctu, int depths, const int8_t *d_layer_qp,
+                         const uint8_t *d_cu_depth, int8_t *d_qp);
 /* out[k + range], k = -range .. range: the smallest double at which floor(log(n) / log(2.0) * 6.0 + 0.49999), evaluated on the host
  * with libm, reaches k; found by bisection over the doubles and held against the 64 doubles on either side of it (a
  * disagreement is HMX_ERR_INTERNAL).  Built once per range (1..64). */

@@ -455,6 +455,7 @@ def lib():
                          ("hmx_aq_activity", [vp, C.POINTER(Pic), ci, ci, ci, ci, vp, vp]),
                          ("hmx_aq_average_multi", [vp, ci, ci, ci, ci, ci, vp, vp]),
                          ("hmx_aq_qp_map_multi", [vp, ci, ci, ci, ci, ci, vp, vp, vp, ci, ci, vp]),
+                         ("hmx_aq_unit_qp_multi", [vp, ci, ci, ci, ci, ci, vp, vp, vp]), ("hmx_set_qp_map", [vp, vp, ci]), ("hmx_set_qp_map_base", [vp, ci, ci]),
                          ("hmx_aq_thresholds", [ci, vp]), ("hmx_aq_offset", [dbl, dbl, ci]),
                          ("hmx_aq_compute_qp", [C.POINTER(AqGeom), vp, vp, ci, ci, ci, ci, ci, ci])):
             if "HMX_LIB_PATH" in os.environ and not hasattr(L, name):
@@ -568,6 +569,26 @@ class Context:
                 C.memmove(C.byref(arr[i].est[k]), C.byref(ests[k]), C.sizeof(EstBits))
             arr[i].lambda_luma, arr[i].lambda_chroma = ll, lc
         self._chk(lib().hmx_set_rdoq(self.h, arr, len(pics)))
+
+    def set_qp_map(self, d_qp, n_pics=1):
+        """hmx_set_qp_map: d_qp = a DevBuf (or device address) of int8 [n_pics][ceil(h / 4)][ceil(w / 4)], one luma QP per 4x4 luma
+        unit, for the following whole-picture calls (packed schedule) and block-list transform calls; n_pics = 1: one map for every
+        picture.  None switches back to PicParam.qp.  The memory stays the caller's and must outlive the calls that read it."""
+        if d_qp is None:
+            self._chk(lib().hmx_set_qp_map(self.h, None, 0))
+        else:
+            self._chk(lib().hmx_set_qp_map(self.h, getattr(d_qp, "ptr", d_qp), n_pics))
+
+    def set_qp_map_base(self, slice_qp_base):
+        """hmx_set_qp_map_base: the slice's base QP, from which the reference encoder's flat quantiser takes its right shift (the levels
+        of a stream coded under --AdaptiveQP=1); None: the shift follows the block's own QP (the default)."""
+        self._chk(lib().hmx_set_qp_map_base(self.h, 0 if slice_qp_base is None else 1, 0 if slice_qp_base is None else int(slice_qp_base)))
+
+    def aq_unit_qp(self, n, w, h, ctu, depths, d_layer_qp, d_cu_depth, d_qp):
+        """hmx_aq_unit_qp_multi: the layer QPs of aq_qp_map(..., out=) and a depth per 4x4 luma unit (uint8 [n][h / 4][w / 4], DevBufs)
+        -> the unit map hmx_set_qp_map and the deblocking calls read, written to the DevBuf d_qp.  Nothing is downloaded."""
+        self._chk(lib().hmx_aq_unit_qp_multi(self.h, n, w, h, ctu, depths, getattr(d_layer_qp, "ptr", d_layer_qp),
+                                             getattr(d_cu_depth, "ptr", d_cu_depth), getattr(d_qp, "ptr", d_qp)))
 
     def alloc(self, nbytes):
         return DevBuf(self, nbytes)
@@ -1153,11 +1174,16 @@ class Context:
             if d_avg is None:
                 avg.free()
 
-    def aq_qp_map(self, n, w, h, ctu, depths, d_act, d_avg, slice_qp, qp_range, qp_bd_offset):
-        """hmx_aq_qp_map_multi over the device arrays of aq_activity: int8 (n, total), the xComputeQP result of every unit."""
+    def aq_qp_map(self, n, w, h, ctu, depths, d_act, d_avg, slice_qp, qp_range, qp_bd_offset, out=None):
+        """hmx_aq_qp_map_multi over the device arrays of aq_activity: int8 (n, total), the xComputeQP result of every unit.
+        out: a DevBuf of n * total bytes that keeps the result on the device for aq_unit_qp; then nothing is downloaded and the
+        call returns None."""
         g = aq_layout(w, h, ctu, depths)
         sq = np.ascontiguousarray(slice_qp, np.int32)
         assert sq.shape == (n,)
+        if out is not None:
+            self._chk(lib().hmx_aq_qp_map_multi(self.h, n, w, h, ctu, depths, d_act.ptr, d_avg.ptr, _hp(sq), qp_range, qp_bd_offset, out.ptr))
+            return None
         out = self.alloc(n * g.total)
         try:
             self._chk(lib().hmx_aq_qp_map_multi(self.h, n, w, h, ctu, depths, d_act.ptr, d_avg.ptr, _hp(sq), qp_range, qp_bd_offset, out.ptr))

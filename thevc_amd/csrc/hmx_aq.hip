@@ -184,6 +184,28 @@ __global__ __launch_bounds__(256) void k_aq_qp(AqQpArgs A) {
   A.qp[(size_t)pic * A.G.total + u] = (int8_t)min(51, max(A.qp_min, qp));
 }
 
+struct AqUnitArgs {
+  const int8_t *layer_qp;  // [n_pics][G.total]: hmx_aq_qp_map_multi
+  const uint8_t *cu_depth; // [n_pics][uh][uw]
+  int8_t *qp;              // [n_pics][uh][uw]
+  hmx_aq_geom G;
+  int uw, uh;
+};
+// The QP of every 4x4 luma unit: its CU at depth D reads layer min(D, depths - 1), unit (x / part, y / part) (TEncCu.cpp:1121-1124).
+// The depth byte is clamped before it picks a layer, so whatever it holds the read stays inside the picture's layer array.
+__global__ __launch_bounds__(256) void k_aq_unit_qp(AqUnitArgs A) {
+  const int u = blockIdx.x * 256 + threadIdx.x, pic = blockIdx.y, n = A.uw * A.uh;
+  if (u >= n) return;
+  const int uy = u / A.uw, ux = u - uy * A.uw;
+  const int D = min((int)A.cu_depth[(size_t)pic * n + u], A.G.depths - 1);
+  int first = A.G.first[0], nx = A.G.nx[0], part = A.G.part[0];
+#pragma unroll
+  for (int k = 1; k < HMX_AQ_MAX_DEPTHS; k++)
+    if (k == D) first = A.G.first[k], nx = A.G.nx[k], part = A.G.part[k];
+  const int lp = 31 - __builtin_clz(part);
+  A.qp[(size_t)pic * n + u] = A.layer_qp[(size_t)pic * A.G.total + first + ((4 * uy) >> lp) * nx + ((4 * ux) >> lp)];
+}
+
 // ---- host ----
 const char *const kAqDomain = "ctu must be 16, 32 or 64, depths at least 1 with ctu >> (depths - 1) >= 8, the picture size positive multiples of 8 up to 16384";
 bool aq_domain_ok(int pic_w, int pic_h, int ctu, int depths) {
@@ -310,6 +332,19 @@ extern "C" int hmx_aq_qp_map_multi(hmx_ctx *c, int n_pics, int pic_w, int pic_h,
   if (!d_thr || !d_sqp) return fail(c, HMX_ERR_INTERNAL, kArenaOutside);
   const AqQpArgs A{d_act, d_avg, d_thr, d_sqp, d_qp, G, pow(2.0, range / 6.0), (int)T.t.size(), range, -qp_bd_offset};
   hipLaunchKernelGGL(k_aq_qp, dim3((unsigned)((G.total + 255) / 256), (unsigned)n_pics), dim3(256), 0, c->stream, A);
+  HIPCHK(c, hipGetLastError());
+  return HMX_OK;
+}
+
+extern "C" int hmx_aq_unit_qp_multi(hmx_ctx *c, int n_pics, int pic_w, int pic_h, int ctu, int depths, const int8_t *d_layer_qp,
+                                    const uint8_t *d_cu_depth, int8_t *d_qp) {
+  if (!c || !d_layer_qp || !d_cu_depth || !d_qp) return fail(c, HMX_ERR_ARG, "hmx_aq_unit_qp_multi: null argument");
+  if (n_pics < 1 || n_pics > 65535) return fail(c, HMX_ERR_ARG, "hmx_aq_unit_qp_multi: n_pics must be 1..65535");
+  hmx_aq_geom G;
+  if (hmx_aq_layout(pic_w, pic_h, ctu, depths, &G)) return fail(c, HMX_ERR_ARG, std::string("hmx_aq_unit_qp_multi: ") + kAqDomain);
+  const int uw = pic_w / 4, uh = pic_h / 4; // multiples of 8
+  const AqUnitArgs A{d_layer_qp, d_cu_depth, d_qp, G, uw, uh};
+  hipLaunchKernelGGL(k_aq_unit_qp, dim3((unsigned)((uw * uh + 255) / 256), (unsigned)n_pics), dim3(256), 0, c->stream, A);
   HIPCHK(c, hipGetLastError());
   return HMX_OK;
 }

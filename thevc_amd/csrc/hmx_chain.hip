@@ -81,6 +81,8 @@ struct IntraCall {
   short *pool_org, *pool_rec;         // the context's own pools or the caller's (hmx_tpool)
   const PicWork *d_work;
   const ConvJob *d_jobs;              // [2][n_pics * 3]: to-tiled jobs, then from-tiled jobs
+  bool qmap;                          // a QP per block (hmx_set_qp_map): qm is the map in its device form
+  QpMapDev qm;
   bool packed() const { return schedule == 3; }
   bool use_level() const { return schedule == 1 || schedule == 2; }
   const hmx_intra_plan *plan(int i) const { return plans[i * plan_stride]; }
@@ -116,6 +118,7 @@ static int issue_packed(hmx_ctx *c, const IntraCall &k, hipStream_t st) {
   // (measured with the mode-aware dependency order, 2160p mix: 64 lanes/wave-item ahead at 8..128 and from 384 pictures,
   // 16 ahead at 192 and 256)
   G.slots4 = c->knob.slots4 ? c->knob.slots4 : ((n_pics >= 160 && n_pics < 320) ? 16 : 64);
+  if (k.qmap) G.slots4 = 64; // the kernel with a QP per block has one wave-item shape per size class (HMX_PACK_SLOTS4 / 8 do not apply)
   const bool rdoq = enc && c->crq.n > 0;
   if (rdoq) {
     if (c->crq.n != 1 && c->crq.n != n_pics) return fail(c, HMX_ERR_ARG, "frame_intra: hmx_set_rdoq described another number of pictures");
@@ -138,7 +141,7 @@ static int issue_packed(hmx_ctx *c, const IntraCall &k, hipStream_t st) {
   }
   // 8x8 blocks: sixteen per wave-item on four lanes each (wave_chain_8x2) where throughput counts, eight on eight lanes where a
   // wave-item's latency does (and under RDOQ, whose rounds are laid out for eight)
-  G.slots8 = rdoq || G.slots4 != 64 ? 8 : c->knob.slots8 ? c->knob.slots8 : (n_pics >= 640 ? 16 : 8); // measured, 2160p mix: 512 pictures -3 %, 768 +4 %, 1024 +8 %, 2048 +11 %
+  G.slots8 = rdoq || k.qmap || G.slots4 != 64 ? 8 : c->knob.slots8 ? c->knob.slots8 : (n_pics >= 640 ? 16 : 8); // measured, 2160p mix: 512 pictures -3 %, 768 +4 %, 1024 +8 %, 2048 +11 %
   const uint64_t n_rows = (uint64_t)G.max_levels * G.n_groups;
   uint64_t waves_bound = 4 * n_rows + 4;
   for (int s = 0; s < 4; s++) waves_bound += sz[s] / pack_slots(s, G.slots4, G.slots8);
@@ -213,6 +216,16 @@ static int issue_packed(hmx_ctx *c, const IntraCall &k, hipStream_t st) {
       c->crq.max_waves = std::max(64, nb * prop.multiProcessorCount);
     }
     resident = c->crq.max_waves;
+  }
+  if (k.qmap) {
+    if (!c->qm_max_waves) {
+      int nb = 0;
+      hipDeviceProp_t prop;
+      HIPCHK(c, hipGetDeviceProperties(&prop, c->cfg.device));
+      if (packed_qmap_max_blocks(&nb)) return fail(c, HMX_ERR_DEVICE, "hipOccupancyMaxActiveBlocksPerMultiprocessor(k_intra_packed_qmap)");
+      c->qm_max_waves = std::max(64, nb * prop.multiProcessorCount);
+    }
+    resident = c->qm_max_waves;
   }
   const uint64_t want = std::max<uint64_t>(256, 2 * wpl);
   pk.n_wg = c->knob.pack_waves ? std::min(c->knob.pack_waves, resident) : (int)std::min<uint64_t>((uint64_t)resident, want);
@@ -292,6 +305,11 @@ static int issue_packed(hmx_ctx *c, const IntraCall &k, hipStream_t st) {
   const dim3 grid((unsigned)pk.n_wg), blk(64);
   if (rdoq) {
     launch_packed_rdoq(A, A.want_sse != 0, grid.x, st); // hmx_chain_rdoq.hip
+  } else if (k.qmap) {
+    PackArgsQ AQ{};
+    static_cast<PackArgs &>(AQ) = A;
+    AQ.qm = k.qm;
+    launch_packed_qmap(AQ, enc, A.want_sse != 0, grid.x, st); // hmx_chain_qmap.hip
   } else {
     with_bool(enc, [&](auto enc_t) {
       with_bool(A.want_sse != 0, [&](auto sse_t) {
@@ -738,6 +756,10 @@ static int table_key_of(hmx_ctx *c, const IntraCall &k, const std::vector<PicWor
     if (!k.packed()) return fail(c, HMX_ERR_ARG, "frame_intra: RDOQ as the quantiser (hmx_set_rdoq) needs the packed schedule");
     mix(&c->crq.serial, sizeof(c->crq.serial)); // 4x4 blocks then always go one per lane: another table
   }
+  if (k.qmap) { // another wave-item shape, another kernel: never the tables of a call without a map by accident
+    const int on = 1;
+    mix(&on, sizeof(on));
+  }
   if (k.enc && (int)c->sse_out.size() >= k.n_pics) {
     if (!k.packed()) return fail(c, HMX_ERR_ARG, "frame_intra: the distortion output (hmx_set_sse_output) needs the packed schedule");
     mix(c->sse_out.data(), sizeof(hmx_sse) * k.n_pics);
@@ -838,6 +860,16 @@ static int frame_intra(hmx_ctx *c, const hmx_intra_plan *const *plans, int plan_
   k.enc = enc, k.onto = onto, k.resident = resident;
   k.plans = plans, k.plan_stride = plan_stride, k.n_pics = n_pics, k.lev = lev;
   if (int r = resolve_call(c, k, torg, trec)) return r;
+  if (c->qm.d) { // a QP per block (hmx_set_qp_map): refused here, before anything is launched, where the call cannot honour the map
+    if (enc && c->crq.n > 0)
+      return fail(c, HMX_ERR_ARG, "frame_intra: a QP map (hmx_set_qp_map) with RDOQ (hmx_set_rdoq): lambda and the bit estimates are per picture, the reference changes lambda with the QP");
+    if (!k.packed())
+      return fail(c, HMX_ERR_ARG, k.use_level() ? "frame_intra: a QP map (hmx_set_qp_map) needs the packed schedule; this call resolved to the level schedule, which takes one QP per call"
+                                                : "frame_intra: a QP map (hmx_set_qp_map) needs the packed schedule; this call resolved to the wave schedule, which takes one QP per call");
+    const hmx_intra_plan *p0 = plans[0];
+    if (int r = qp_map_for_call(c, n_pics, p0->P.pic_w, p0->P.pic_h, p0->chroma_qp_offset, p0->slice_type, k.qm)) return r;
+    k.qmap = true;
+  }
   if (int r = ensure_pools(c, k, torg, trec)) return r;
   std::vector<PicWork> hw;
   std::vector<ConvJob> jobs;

@@ -1,7 +1,7 @@
 // hmx_chain_dev.h -- device side of the whole-picture all-intra chain: the block chains (wave_chain_*), the
 // level-synchronous kernels, the layout conversion and the packed schedule (tables' prep kernels, k_intra_packed).
 // Included by hmx_chain.hip (defines HMX_CHAIN_MAIN: also gets the non-template kernels), hmx_chain_rdoq.hip (the RDOQ
-// instantiations of k_intra_packed) and hmx_list.hip (the one-lane 4x4 transform halves).
+// instantiations of k_intra_packed), hmx_chain_qmap.hip (those with a QP per block) and hmx_list.hip (the one-lane 4x4 transform halves).
 #pragma once
 #include "hmx_host.h"
 
@@ -94,8 +94,8 @@ __device__ __forceinline__ unsigned lev_row_off(const PlaneView &V, int x, int y
 #else
 #define HMX_MARK(n, id)
 #endif
-template <int N, bool ENC, bool ONCE = false, typename SRC>
-__device__ __forceinline__ void wave_chain_valu(char *smem, const SRC &src, const PicDev &P, int count) {
+template <int N, bool ENC, bool ONCE = false, typename SRC, typename PD>
+__device__ __forceinline__ void wave_chain_valu(char *smem, const SRC &src, const PD &P, int count) {
   constexpr int SL = 64 / N;
   const int lane = lane_id(), slot = lane / N, gl = lane % N;
   TuLds<N> &L = reinterpret_cast<TuLds<N> *>(smem)[slot];
@@ -196,8 +196,8 @@ __device__ __forceinline__ void wave_chain_valu(char *smem, const SRC &src, cons
 // PMC before: 3526 VALU instructions per 1024 samples of 8x8 blocks against 1972 / 2573 / 2158 for 4x4 / 16x16 / 32x32, and 37 % of
 // the mixed workload's instructions.  Packed schedule, large batches (a wave-item's chain is longer: not for latency-bound ones).
 // ---------------------------------------------------------------------------------------------
-template <bool ENC, typename SRC>
-__device__ __forceinline__ void wave_chain_8x2(char *smem, const SRC &src, const PicDev &P, int count) {
+template <bool ENC, typename SRC, typename PD>
+__device__ __forceinline__ void wave_chain_8x2(char *smem, const SRC &src, const PD &P, int count) {
   constexpr int N = 8, NL = 4, LG = 3;
   HMX_MARK(82, 0);
   const int lane = lane_id(), slot = lane >> 2, gl = lane & 3, r0 = 2 * gl;
@@ -490,7 +490,8 @@ __device__ __forceinline__ void lane4_coef(const int *resid, bool use_dst, bool 
     }
   }
 }
-__device__ __forceinline__ void lane4_forward(const int *resid, bool use_dst, bool ts, bool luma, int scan_idx, const PicDev &P, int *w) {
+template <typename PD>
+__device__ __forceinline__ void lane4_forward(const int *resid, bool use_dst, bool ts, bool luma, int scan_idx, const PD &P, int *w) {
   const int B = P.bit_depth, tshift = 15 - B - 2;
   int coef[16];
   lane4_coef(resid, use_dst, ts, P, coef);
@@ -519,7 +520,8 @@ __device__ __forceinline__ void lane4_forward(const int *resid, bool use_dst, bo
   }
 }
 // lane4_inverse: levels (row-major) -> residual
-__device__ __forceinline__ void lane4_inverse(const int *lv, bool use_dst, bool ts, bool luma, const PicDev &P, int *out) {
+template <typename PD>
+__device__ __forceinline__ void lane4_inverse(const int *lv, bool use_dst, bool ts, bool luma, const PD &P, int *out) {
   const int B = P.bit_depth, tshift = 15 - B - 2;
   const QuantDev qd = pick_qd(P, luma);
   int c[16];
@@ -558,8 +560,8 @@ __device__ __forceinline__ void clamp_positions(int *q, int lo, int hi) { // q[p
   q[P] = med3k<P>(lo, hi);
   if constexpr (P > 0) clamp_positions<P - 1>(q, lo, hi);
 }
-template <bool ENC, bool ONCE = false, typename SRC>
-__device__ __forceinline__ void wave_chain_4_lane(char *smem, const SRC &src, const PicDev &P, int count) {
+template <bool ENC, bool ONCE = false, typename SRC, typename PD>
+__device__ __forceinline__ void wave_chain_4_lane(char *smem, const SRC &src, const PD &P, int count) {
   Lane4Lds &LS = *reinterpret_cast<Lane4Lds *>(smem);
   const int lane = lane_id();
   const int B = P.bit_depth, mx = (1 << B) - 1;
@@ -878,8 +880,8 @@ __device__ __forceinline__ void wave_chain_4_lane(char *smem, const SRC &src, co
   }
 }
 
-template <bool ENC, bool ONCE = false, typename SRC>
-__device__ __forceinline__ void wave_chain_32(char *smem, const SRC &src, const PicDev &P, int count) {
+template <bool ENC, bool ONCE = false, typename SRC, typename PD>
+__device__ __forceinline__ void wave_chain_32(char *smem, const SRC &src, const PD &P, int count) {
   const int lane = lane_id(), r = lane & 31, h = lane >> 5;
   TuLds<32> &L = *reinterpret_cast<TuLds<32> *>(smem);
   constexpr int LG = 5;
@@ -1587,12 +1589,32 @@ __device__ __forceinline__ int pack_lane_item(int lane, int s) {
   return s == 0 ? (SL4 == 64 ? lane : lane >> 2) : s == 1 ? (SL8 == 16 ? lane >> 2 : lane >> 3) : s == 2 ? lane >> 4 : 0;
 }
 
-template <bool ENC, int SL4, bool SSE = false, bool RDOQ = false, int SL8 = 8>
+// With a QP per block (hmx_set_qp_map) the kernel's arguments carry the map, and a lane keeps the quantiser constants of its item
+// beside the item: both are fetched together, for the next wave-item while the current one runs.
+struct PackArgsQ : PackArgs {
+  QpMapDev qm;
+};
+struct NoQuant {};
+template <bool QMAP, typename ARGS>
+__device__ __forceinline__ auto pack_item_qd(const ARGS &A, const FTu &ft, uint32_t row) {
+  if constexpr (QMAP) { // the picture: the row's group, the item's slot in it
+    const int pl = ft.t.plane & 3, sh = pl ? 1 : 0;
+    const int pic = (int)(row % (uint32_t)A.n_groups) * A.I + (int)(ft.t.plane >> 2);
+    return qp_map_qd(A.qm, pic, (int)ft.t.x << sh, (int)ft.t.y << sh, pl == 0);
+  } else {
+    return NoQuant{};
+  }
+}
+// QMAP = false is the kernel as it was before the map existed (the chains get the call's PicDev, wave-uniform constants); QMAP = true
+// hands them a PicDevLane per wave-item.  One wave-item shape per size class then: 64 4x4 blocks (one per lane), eight 8x8 blocks
+// (eight lanes each); no RDOQ (hmx_chain.hip refuses the call: lambda and the bit estimates are per picture).
+template <bool ENC, int SL4, bool SSE = false, bool RDOQ = false, int SL8 = 8, bool QMAP = false>
 #ifndef HMX_PACKED_OCC
 #define HMX_PACKED_OCC 4 /* waves per SIMD the register allocation is held to (A/B: -DHMX_PACKED_OCC=5 | 6 spill) */
 #endif
-__global__ __launch_bounds__(64, RDOQ ? 2 : HMX_PACKED_OCC) void k_intra_packed(PackArgs A) {
+__global__ __launch_bounds__(64, RDOQ ? 2 : HMX_PACKED_OCC) void k_intra_packed(std::conditional_t<QMAP, PackArgsQ, PackArgs> A) {
   static_assert(!RDOQ || (ENC && SL4 == 64 && SL8 == 8), "RDOQ: encoder direction, 4x4 blocks one per lane, 8x8 blocks on eight lanes (rdoq_wave_tiles)");
+  static_assert(!QMAP || (!RDOQ && SL4 == 64 && SL8 == 8), "a QP per block: one wave-item shape per size class, the flat quantiser");
   static_assert(SL8 == 8 || (SL8 == 16 && 16 * sizeof(TuLds8x2) <= HMX_WAVE_SMEM), "8x8 blocks per wave-item");
   // RDOQ variant: every byte of LDS decides how many waves a CU holds (the walks are latency chains); the lane-per-block 4x4
   // chain, the largest user of the common scratch, borrows the round buffer its RDOQ does not need
@@ -1650,6 +1672,7 @@ __global__ __launch_bounds__(64, RDOQ ? 2 : HMX_PACKED_OCC) void k_intra_packed(
       const int s = (int)((uint32_t)__builtin_amdgcn_readfirstlane((int)d.n_s) >> 28), n = (int)((uint32_t)__builtin_amdgcn_readfirstlane((int)d.n_s) & 0x0fffffffu);
       ft = A.items[(uint32_t)__builtin_amdgcn_readfirstlane((int)d.item_off) + (uint32_t)min(pack_lane_item<SL4, SL8>(lane_id(), s), n - 1)];
     }
+    auto qd = pack_item_qd<QMAP>(A, ft, (uint32_t)__builtin_amdgcn_readfirstlane((int)d.row));
     PROF_T(p1);
 #ifdef HMX_PACK_PROFILE
     acc[0] += p1 - p0;
@@ -1675,21 +1698,26 @@ __global__ __launch_bounds__(64, RDOQ ? 2 : HMX_PACKED_OCC) void k_intra_packed(
       wave_sync(); // the LDS scratch is re-interpreted per block size
       if constexpr (RDOQ) rdoq_stage_tables(*rq_lds, A.rq, g, s, A.I, lane_id());
       PROF_T(p3);
+      PicDevLane PL;
+      if constexpr (QMAP) PL = lane_picdev(A.P, qd);
+      const auto &P = pick_pd<QMAP>(A.P, PL);
       if (s == 0) {
-        if constexpr (SL4 == 64) wave_chain_4_lane<ENC, true>(smem4, src, A.P, n);
-        else wave_chain_valu<4, ENC, true>(smem, src, A.P, n);
+        if constexpr (SL4 == 64) wave_chain_4_lane<ENC, true>(smem4, src, P, n);
+        else wave_chain_valu<4, ENC, true>(smem, src, P, n);
       } else if (s == 1) {
-        if constexpr (SL8 == 16) wave_chain_8x2<ENC>(smem, src, A.P, n);
-        else wave_chain_valu<8, ENC, true>(smem, src, A.P, n);
-      } else if (s == 2) wave_chain_valu<16, ENC, true>(smem, src, A.P, n);
-      else wave_chain_32<ENC, true>(smem, src, A.P, n);
+        if constexpr (SL8 == 16) wave_chain_8x2<ENC>(smem, src, P, n);
+        else wave_chain_valu<8, ENC, true>(smem, src, P, n);
+      } else if (s == 2) wave_chain_valu<16, ENC, true>(smem, src, P, n);
+      else wave_chain_32<ENC, true>(smem, src, P, n);
       // the next wave-item's items, behind this one's stores (its descriptor was fetched behind the dependency poll)
       const bool more = nx.t < nx.total;
       FTu ftn = ft;
+      auto qdn = qd;
       if (more) {
         const uint32_t ns = (uint32_t)__builtin_amdgcn_readfirstlane((int)nx.d.n_s);
         ftn = A.items[(uint32_t)__builtin_amdgcn_readfirstlane((int)nx.d.item_off) +
                       (uint32_t)min(pack_lane_item<SL4, SL8>(lane_id(), (int)(ns >> 28)), (int)(ns & 0x0fffffffu) - 1)];
+        qdn = pack_item_qd<QMAP>(A, ftn, (uint32_t)__builtin_amdgcn_readfirstlane((int)nx.d.row));
       }
       // publish: every store of this wave has reached the L2 before the row's count moves
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -1702,7 +1730,7 @@ __global__ __launch_bounds__(64, RDOQ ? 2 : HMX_PACKED_OCC) void k_intra_packed(
       acc[1] += p3 - p2, acc[2] += pt[0] - p3, acc[3] += pt[1] - pt[0], acc[4] += p4 - pt[1], acc[5] += p5 - p4, acc[6] += p6 - p5, acc[7] += 1;
 #endif
       if (!more) break;
-      d = nx.d, ft = ftn;
+      d = nx.d, ft = ftn, qd = qdn;
     }
   }
 #ifdef HMX_PACK_PROFILE

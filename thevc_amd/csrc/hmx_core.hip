@@ -50,6 +50,54 @@ PicDev make_picdev(const hmx_ctx *c, const hmx_pic_param *pp) {
   return P;
 }
 
+extern "C" int hmx_set_qp_map(hmx_ctx *c, const int8_t *d_qp, int n_pics) {
+  if (!c) return HMX_ERR_ARG;
+  if (d_qp && (n_pics < 1 || n_pics > 65535)) return fail(c, HMX_ERR_ARG, "hmx_set_qp_map: n_pics must be 1..65535");
+  c->qm.d = d_qp;
+  c->qm.n = d_qp ? n_pics : 0;
+  c->qm.serial++;
+  return HMX_OK;
+}
+extern "C" int hmx_set_qp_map_base(hmx_ctx *c, int on, int slice_qp_base) {
+  if (!c) return HMX_ERR_ARG;
+  const int off = 6 * (c->cfg.bit_depth - 8);
+  if (on && (slice_qp_base < -off || slice_qp_base > 51)) return fail(c, HMX_ERR_ARG, "hmx_set_qp_map_base: slice_qp_base outside -QpBDOffset..51");
+  c->qm.base_on = on != 0;
+  c->qm.base_qp = on ? slice_qp_base : 0;
+  return HMX_OK;
+}
+int qp_map_for_call(hmx_ctx *c, int n_pics, int pic_w, int pic_h, int chroma_qp_offset, int slice_type, QpMapDev &M) {
+  auto &q = c->qm;
+  if (q.n != 1 && q.n < n_pics) return fail(c, HMX_ERR_ARG, "hmx_set_qp_map described fewer pictures than the call has");
+  if (chroma_qp_offset < -12 || chroma_qp_offset > 12) return fail(c, HMX_ERR_ARG, "QP map: chroma_qp_offset outside -12..12");
+  if (pic_w <= 0 || pic_h <= 0 || pic_w > 16384 || pic_h > 16384) return fail(c, HMX_ERR_ARG, "QP map: the picture size must be 1..16384");
+  const int off = 6 * (c->cfg.bit_depth - 8), n = 52 + off;
+  // (the slice type's rounding factor travels in the call's PicDev)
+  const int key = (chroma_qp_offset + 12) | (q.base_on ? 0x100 | ((q.base_qp + 64) << 12) : 0);
+  // hmx_set_qp_map_base: iQBits of xQuant from the slice's base QP (TComTrQuant.cpp:1161-1231, ADAPTIVE_QP_SELECTION): luma base + offset,
+  // chroma the base through g_aucChromaScale WITHOUT the PPS offset (:1175-1190)
+  const int base_per[2] = {hmx_setQPforQuant(q.base_qp, HMX_TEXT_LUMA, off, 0).per, hmx_setQPforQuant(q.base_qp, HMX_TEXT_CHROMA, off, 0).per};
+  if (!q.d_tab || q.tab_key != key) {
+    std::vector<QuantPk> t((size_t)n * 2);
+    for (int i = 0; i < n; i++) // entry i: luma QP i - off; the chroma QP through g_aucChromaScale and the negative-QP branch
+      for (int ch = 0; ch < 2; ch++) {
+        const QuantDev d = make_qd(hmx_setQPforQuant(i - off, ch ? HMX_TEXT_CHROMA : HMX_TEXT_LUMA, off, ch ? chroma_qp_offset : 0), -1, slice_type);
+        t[2 * i + ch] = QuantPk{d.q | (q.base_on ? base_per[ch] : d.per_qbits) << 16, d.iq_scale};
+      }
+    HIPCHK(c, hipStreamSynchronize(c->stream)); // a queued call may still read the previous table
+    if (!q.d_tab && hipMalloc((void **)&q.d_tab, sizeof(QuantPk) * 2 * (52 + 48)) != hipSuccess) return fail(c, HMX_ERR_NOMEM, "hipMalloc QP table");
+    q.tab_key = -1;
+    HIPCHK(c, hipMemcpy(q.d_tab, t.data(), sizeof(QuantPk) * t.size(), hipMemcpyHostToDevice));
+    q.tab_key = key;
+  }
+  M.map = reinterpret_cast<const signed char *>(q.d);
+  M.tab = q.d_tab;
+  M.uw = (pic_w + 3) / 4, M.uh = (pic_h + 3) / 4;
+  M.pic_elems = q.n == 1 ? 0 : (long long)M.uw * M.uh;
+  M.off = off;
+  return HMX_OK;
+}
+
 // Tuning knobs: read from the environment ONCE, in hmx_create; hmx_set_option changes one afterwards (A/B runs, and the
 // parity tests that hold the schedules against each other).  value == NULL restores the default.
 static const char *const kKnobNames[] = {"HMX_INTRA_SCHEDULE", "HMX_INTRA_ACROSS", "HMX_INTRA_STREAMS", "HMX_PIPELINE_CONV", "HMX_GRAPH",
@@ -136,6 +184,7 @@ extern "C" void hmx_destroy(hmx_ctx *c) {
   if (c->arena_h) hipHostFree(c->arena_h);
   hipFree(c->arena_d);
   hipFree(c->d_mcmap);
+  hipFree(c->qm.d_tab);
   hipFree(c->d_me_keys);
   hipFree(c->d_wpest);
   hipFree(c->d_saodec);

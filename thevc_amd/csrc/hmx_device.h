@@ -193,6 +193,48 @@ __device__ __forceinline__ QuantDev pick_qd(const PicDev &P, bool luma) {
   return QuantDev{luma ? a0 : b0, luma ? a1 : b1, luma ? a2 : b2, luma ? a3 : b3};
 }
 
+// A QP per block (hmx_set_qp_map): the caller's map holds one luma QP per 4x4 luma unit, a block takes the unit at its first sample
+// (TComDataCU::getQP of its coding unit).  The host builds tab[qp + off][0 luma, 1 chroma] for every legal QP of the call, the chroma
+// entry through hmx_setQPforQuant, and a block reads its map byte and its table entry ONCE, next to its descriptor.  The byte is
+// clamped to -off .. 51 before it indexes the table, and the unit to the map: device memory the host cannot validate.
+// The block routines are templates over the type of their picture parameters.  PicDev: the constants are wave-uniform (pick_qd
+// above), the form every call without a map instantiates.  PicDevLane: a copy whose qd[0] holds the constants of this lane's block.
+struct QuantPk { // a table entry, and what a lane of the persistent kernel keeps beside its item: two registers
+  int q_per; // g_quantScales[rem] | per << 16
+  int iq_scale;
+};
+struct QpMapDev {
+  const signed char *map; // [n][uh][uw]
+  const QuantPk *tab;     // [52 + off][2]; the rounding factor is the slice's, PicDev::qd[0].rnd_factor
+  long long pic_elems;    // uh * uw, or 0: one map for every picture
+  int uw, uh, off;        // units per row and column, QpBDOffset
+};
+struct PicDevLane : PicDev {};
+__device__ __forceinline__ QuantDev pick_qd(const PicDevLane &P, bool) { return P.qd[0]; }
+// (lx, ly): the block's first sample in luma coordinates
+__device__ __forceinline__ QuantPk qp_map_qd(const QpMapDev &M, int pic, int lx, int ly, bool luma) {
+  typedef __attribute__((address_space(1))) const signed char gbyte;
+  typedef int i2 __attribute__((ext_vector_type(2)));
+  typedef __attribute__((address_space(1))) const i2 gq;
+  const int ux = min(max(lx >> 2, 0), M.uw - 1), uy = min(max(ly >> 2, 0), M.uh - 1);
+  const int qp = ((gbyte *)M.map)[(long long)pic * M.pic_elems + uy * M.uw + ux];
+  const int e = (min(max(qp, -M.off), 51) + M.off) * 2 + (luma ? 0 : 1);
+  const i2 v = ((gq *)M.tab)[e];
+  return QuantPk{v[0], v[1]};
+}
+// the parameters a kernel hands its block routines: the call's own (no map), or the lane's copy
+template <bool QMAP>
+__device__ __forceinline__ const auto &pick_pd(const PicDev &call, const PicDevLane &lane) {
+  if constexpr (QMAP) return lane;
+  else return call;
+}
+__device__ __forceinline__ PicDevLane lane_picdev(const PicDev &P, const QuantPk &k) {
+  PicDevLane L;
+  L.pic_w = P.pic_w, L.pic_h = P.pic_h, L.ctu = P.ctu, L.bit_depth = P.bit_depth, L.sign_hide = P.sign_hide; // (field by field: a struct copy leaves a stack object behind)
+  L.qd[0] = L.qd[1] = QuantDev{k.q_per & 0xffff, k.q_per >> 16, k.iq_scale, wave_uniform(P.qd[0].rnd_factor)};
+  return L;
+}
+
 // Scan tables g_auiSigLastScan (TComRom.cpp:564-698 with REMOVAL_8x2_2x8_CG): coefficient groups
 // of 4x4, groups ordered like the samples inside a group.  Index 0 = diagonal (also used for the
 // reference's "zigzag" index, TComTrQuant.cpp:1135), 1 = horizontal, 2 = vertical.  Entry = raster

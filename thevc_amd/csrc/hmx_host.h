@@ -7,6 +7,7 @@
 //   hmx_chain.hip       whole-picture all-intra chain: level / wave / packed schedules, resident pools
 //   hmx_chain_rdoq.hip  the packed schedule's kernel with xRateDistOptQuant as its quantiser (a translation unit of its own:
 //                       its instantiations take as long to compile as everything else together)
+//   hmx_chain_qmap.hip  the packed schedule's kernel with a QP per block (hmx_set_qp_map), likewise a unit of its own
 //   hmx_inter.hip       interpolation filters, motion compensation, sub-pel cost fan-out, border extension, prediction error of
 //                       complete motion candidates (k_pred_error)
 //   hmx_me.hip          full-search integer motion estimation (SAD, vector-bits cost, search box)
@@ -286,6 +287,7 @@ struct hmx_ctx {
     uint64_t waves_bound = 0;
   } pk;
   int max_resident_waves = 0; // of k_intra_packed on this device
+  int qm_max_waves = 0;       // of k_intra_packed_qmap
   bool pk_pending = false;    // a packed launch was issued since the last check of its abort word
   // hmx_set_rdoq: xRateDistOptQuant as the quantiser of the next whole-picture encode calls
   struct ChainRdoq {
@@ -309,6 +311,16 @@ struct hmx_ctx {
     std::vector<std::pair<void *, size_t>> slabs;
   } pd;
   std::vector<hmx_sse> sse_out; // hmx_set_sse_output: per-picture distortion arrays of the next whole-picture encode calls
+  // hmx_set_qp_map: a QP per 4x4 luma unit for the whole-picture chain (packed schedule) and the block-list transform entries
+  struct QpMap {
+    const int8_t *d = nullptr; // the caller's device memory, [n][uh][uw]; NULL = off (hmx_pic_param::qp)
+    int n = 0;                 // maps (1: one for every picture of a call)
+    uint64_t serial = 0;       // counts hmx_set_qp_map calls (part of the packed schedule's key)
+    QuantPk *d_tab = nullptr;  // [52 + QpBDOffset][luma, chroma], built for tab_key
+    int tab_key = -1;          // the chroma_qp_offset and the base QP the table was built for
+    bool base_on = false;      // hmx_set_qp_map_base: the forward quantiser's right shift follows the slice's base QP
+    int base_qp = 0;
+  } qm;
   uint64_t table_key = 0;     // of the picture table resident in d_jobs (whole-picture calls)
   bool table_valid = false;
   std::vector<unsigned char> table_bytes; // what table_key was hashed from (the table is re-used only when these bytes are equal)
@@ -443,6 +455,9 @@ void *arena_push(hmx_ctx *c, const void *src, size_t bytes); // NULL: the table 
 constexpr const char *kArenaOutside = "argument arena: a table outside what the call reserved";
 void drop_graphs(hmx_ctx *c); // destroy every recorded whole-picture graph (the stream is idle)
 int grow_dev(hmx_ctx *c, void **p, size_t *cap, size_t need);
+// the device form of the map set by hmx_set_qp_map for a call over n_pics pictures of pic_w x pic_h: refuses a call with more pictures
+// than maps, (re)builds the quantiser table when the chroma offset or the slice type changed                    // hmx_core.hip
+int qp_map_for_call(hmx_ctx *c, int n_pics, int pic_w, int pic_h, int chroma_qp_offset, int slice_type, QpMapDev &M);
 int check_packed_abort(hmx_ctx *c);                                               // hmx_chain.hip
 int pack_group_size(const hmx_ctx *c, int n_pics);
 int launch_op(hmx_ctx *c, int op, int log2n, const ListArgs &A);                  // hmx_list.hip
@@ -462,6 +477,10 @@ int layout_to_device(hmx_ctx *c, const LayoutHost &H, AvailDev &D);
 struct PackArgs;
 int packed_rdoq_max_blocks(int *nb);
 void launch_packed_rdoq(const PackArgs &A, bool sse, unsigned n_wg, hipStream_t st);
+// and the one with a QP per block (hmx_set_qp_map) in hmx_chain_qmap.hip
+struct PackArgsQ;
+int packed_qmap_max_blocks(int *nb);
+void launch_packed_qmap(const PackArgsQ &A, bool enc, bool sse, unsigned n_wg, hipStream_t st);
 
 // the ranges hmx_wp documents for one component of an entry, whichever way it arrives
 inline bool wp_range_ok(int weight, int offset, int log2_denom) {

@@ -225,9 +225,9 @@ __device__ __forceinline__ unsigned sse_samples(const int *org, const int *rec, 
 // Leaves packed words (level in the low half) in L.tile[row][col]; returns uiAbsSum (before sign-bit
 // hiding, :1256).  WIDE: see quant_one.
 // ---------------------------------------------------------------------------------------------
-template <int N, int NL, int NCOEF, bool WIDE, typename LT, typename RowFn, typename ColFn>
+template <int N, int NL, int NCOEF, bool WIDE, typename LT, typename RowFn, typename ColFn, typename PD>
 __device__ __forceinline__ int quant_sbh_block(LT &L, int gl, bool active, const int *coef, RowFn row_of, ColFn col_of,
-                                               bool luma, int scan_idx, const PicDev &P, const int *qtab = nullptr) {
+                                               bool luma, int scan_idx, const PD &P, const int *qtab = nullptr) {
   constexpr int LG = Log2<N>::v;
   const int tshift = 15 - P.bit_depth - LG;
   const QuantDev qd = pick_qd(P, luma);
@@ -302,9 +302,9 @@ __device__ __forceinline__ int quant_sbh_block(LT &L, int gl, bool active, const
 // (diag_group_org).  What quant_sbh_block spends on a run-time scan -- a table load, byte extraction and an address per
 // coefficient, the LDS atomic of the group mask and a third pass -- becomes sixteen loads at compile-time offsets, a ballot
 // shifted by the lane ("a later group holds a level": the reference's lastCG) and one store of the changed word.
-template <int N, int NCOEF, typename LT, typename RowFn, typename ColFn>
+template <int N, int NCOEF, typename LT, typename RowFn, typename ColFn, typename PD>
 __device__ __forceinline__ int quant_sbh_diag(LT &L, int gl, int lane, bool active, const int *coef, RowFn row_of, ColFn col_of,
-                                              bool luma, int g_org, const PicDev &P) {
+                                              bool luma, int g_org, const PD &P) {
   constexpr int LG = Log2<N>::v, NL = (N / 4) * (N / 4);
   static_assert(NL == 16 || NL == 64, "one lane per coefficient group");
   const int tshift = 15 - P.bit_depth - LG;
@@ -372,9 +372,9 @@ __device__ __forceinline__ int diag_group_org(int g) {
 // transformNxN core: residual row -> final levels in L.tile.  ts = transform skip (:1622),
 // use_dst = 4x4 luma intra.  do_quant = false leaves the Int coefficients (xT / xTransformSkip).
 // ---------------------------------------------------------------------------------------------
-template <int N>
+template <int N, typename PD>
 __device__ __forceinline__ int fwd_tq_block(TuLds<N> &L, int gl, bool active, const int *x, bool ts, bool use_dst,
-                                            bool luma, int scan_idx, bool do_quant, const PicDev &P, int diag_lane = -1) {
+                                            bool luma, int scan_idx, bool do_quant, const PD &P, int diag_lane = -1) {
   // everything quantised here went through a forward pass (int16) or transform skip (|x| << shift
   // with |x| < 2^(B+1)), so the 32-bit quantiser is exact
   constexpr int LG = Log2<N>::v;
@@ -428,9 +428,9 @@ __device__ __forceinline__ int dequant_one(int v, int iq_scale, int dshift) { //
 // invtransformNxN core: levels in L.tile[row][col] -> residual row gl in out[N].
 // BATCH: the N reads of each pass back to back with one wait behind them (pin_regs); left to itself the compiler waits for a
 // column in pieces (16x16: three waits over sixteen reads).  The whole-picture chains ask for it, the list kernels do not.
-template <int N, bool BATCH = false>
+template <int N, bool BATCH = false, typename PD>
 __device__ __forceinline__ void inv_tq_block(TuLds<N> &L, int gl, bool active, bool ts, bool use_dst, bool luma,
-                                             bool do_dequant, const PicDev &P, int *out) {
+                                             bool do_dequant, const PD &P, int *out) {
   constexpr int LG = Log2<N>::v;
   const int B = P.bit_depth, tshift = 15 - B - LG;
   const QuantDev qd = pick_qd(P, luma);

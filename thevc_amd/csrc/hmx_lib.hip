@@ -11,6 +11,7 @@
 #include "hmx_plan.hip"
 #include "hmx_chain.hip"
 #include "hmx_chain_rdoq.hip"
+#include "hmx_chain_qmap.hip"
 #include "hmx_inter.hip"
 #include "hmx_me.hip"
 #include "hmx_loop.hip"

@@ -1,9 +1,15 @@
 // hmx_list.hip: block-list kernels and the hmx_batch_* entry points over lists -- part of libhmx (include/hmx.h), gfx950.  See hmx_host.h for how the library is cut into translation units.
 #include "hmx_chain_dev.h"
 
-// One kernel per (operation, block size): every block of the launch has size N.
-template <int N, int OP>
-__global__ __launch_bounds__(256) void k_list(ListArgs A) {
+// One kernel per (operation, block size): every block of the launch has size N.  QMAP (hmx_set_qp_map, the three transform
+// operations): the arguments carry the map, and P is a copy of the call's parameters with the quantiser constants of this lane's
+// block, read once behind its descriptor; without it P is A.P and the kernel is the one it was before the map existed.
+struct ListArgsQ : ListArgs {
+  QpMapDev qm;
+};
+template <int N, int OP, bool QMAP = false>
+__global__ __launch_bounds__(256) void k_list(std::conditional_t<QMAP, ListArgsQ, ListArgs> A) {
+  static_assert(!QMAP || OP == OP_TRANSFORM_NXN || OP == OP_INVTRANSFORM_NXN || OP == OP_TRANSFORM_RECON, "the entries that quantise or dequantise with the picture's QP");
   __shared__ __attribute__((aligned(16))) char smem[HMX_SMEM_BYTES];
   constexpr int SL = Slots<N>::v;
   const int tid = threadIdx.x, slot = tid / N, gl = tid % N;
@@ -14,6 +20,9 @@ __global__ __launch_bounds__(256) void k_list(ListArgs A) {
   const DTu d = load_dtu(A.tus + (active ? i : 0));
   const hmx_tu t = d.t;
   const int pl = t.plane, x = t.x, y = t.y;
+  PicDevLane PL;
+  if constexpr (QMAP) PL = lane_picdev(A.P, qp_map_qd(A.qm, (int)blockIdx.y, pl ? x << 1 : x, pl ? y << 1 : y, pl == 0));
+  const auto &P = pick_pd<QMAP>(A.P, PL);
   // blockIdx.y = picture of a multi-picture call (planes from the table); single calls carry theirs inline
   const ListPic *Q = A.pics ? A.pics + blockIdx.y : nullptr;
   // (members of the by-value argument struct are picked with constant indices: a run-time index into it makes
@@ -40,7 +49,7 @@ __global__ __launch_bounds__(256) void k_list(ListArgs A) {
         for (int k = 0; k < N; k++) row[k] = wrap16(row[k] - pr[k]);
       }
     }
-    int sum = fwd_tq_block<N>(L, gl, active, row, ts, use_dst, luma, scan_idx, OP != OP_XT, A.P);
+    int sum = fwd_tq_block<N>(L, gl, active, row, ts, use_dst, luma, scan_idx, OP != OP_XT, P);
     if (active) {
       load_row32<N>(&L.tile[gl][0], row);
       if (OP != OP_XT) {
@@ -51,9 +60,9 @@ __global__ __launch_bounds__(256) void k_list(ListArgs A) {
       if (OP != OP_XT && gl == 0 && abs_sum) abs_sum[d.idx] = (uint32_t)sum;
     }
     if constexpr (OP == OP_TRANSFORM_RECON) { // the packed words are still in the tile: IQ, IT, Clip(pred + resi) in the same pass
-      inv_tq_block<N>(L, gl, active, ts, use_dst, luma, true, A.P, row);
+      inv_tq_block<N>(L, gl, active, ts, use_dst, luma, true, P, row);
       if (active) {
-        const int mx = (1 << A.P.bit_depth) - 1;
+        const int mx = (1 << P.bit_depth) - 1;
 #pragma unroll
         for (int k = 0; k < N; k++) row[k] = clip3(0, mx, pr[k] + row[k]);
         store_row16<N>(uniform3(Q->rec.p, pl) + (size_t)(y + gl) * uniform3(Q->rec.s, pl) + x, row);
@@ -63,7 +72,7 @@ __global__ __launch_bounds__(256) void k_list(ListArgs A) {
         if (active) {
           int o[N];
           load_row16<N>(a_p + (size_t)(y + gl) * a_s + x, o); // the original row again: it went into the residual
-          dsum = sse_samples<N>(o, row, A.P.bit_depth);
+          dsum = sse_samples<N>(o, row, P.bit_depth);
         }
         dsum = (unsigned)group_sum((int)dsum, N);
         if (active && gl == 0) A.sse[(size_t)blockIdx.y * A.abs_stride + d.idx] = dsum;
@@ -73,7 +82,7 @@ __global__ __launch_bounds__(256) void k_list(ListArgs A) {
     // Int coefficients in lev -> levels in lev2 (the quantiser half of transformNxN on its own)
     if (active) load_row32<N>(lev_p + (size_t)(y + gl) * lev_s + x, row);
     int sum = quant_sbh_block<N, N, N, true>(
-        L, gl, active, row, [&](int) { return gl; }, [&](int k) { return k; }, luma, scan_idx, A.P);
+        L, gl, active, row, [&](int) { return gl; }, [&](int k) { return k; }, luma, scan_idx, P);
     if (active) {
       load_row32<N>(&L.tile[gl][0], row);
 #pragma unroll
@@ -91,12 +100,12 @@ __global__ __launch_bounds__(256) void k_list(ListArgs A) {
       store_row32<N>(&L.tile[gl][0], row);
     }
     wave_sync();
-    inv_tq_block<N>(L, gl, active, ts, use_dst, luma, OP == OP_INVTRANSFORM_NXN, A.P, row);
+    inv_tq_block<N>(L, gl, active, ts, use_dst, luma, OP == OP_INVTRANSFORM_NXN, P, row);
     if (active) {
       if (A.have_pred) {
         int pr[N];
         load_row16<N>(a_p + (size_t)(y + gl) * a_s + x, pr);
-        const int mx = (1 << A.P.bit_depth) - 1;
+        const int mx = (1 << P.bit_depth) - 1;
 #pragma unroll
         for (int k = 0; k < N; k++) row[k] = clip3(0, mx, pr[k] + row[k]);
       }
@@ -104,8 +113,8 @@ __global__ __launch_bounds__(256) void k_list(ListArgs A) {
     }
   } else if constexpr (OP == OP_XDEQUANT) {
     constexpr int LG = Log2<N>::v;
-    const int tshift = 15 - A.P.bit_depth - LG, dshift = 6 - tshift, dadd = 1 << (dshift - 1);
-    const QuantDev qd = pick_qd(A.P, luma);
+    const int tshift = 15 - P.bit_depth - LG, dshift = 6 - tshift, dadd = 1 << (dshift - 1);
+    const QuantDev qd = pick_qd(P, luma);
     if (active) {
       load_row32<N>(lev_p + (size_t)(y + gl) * lev_s + x, row);
 #pragma unroll
@@ -118,25 +127,25 @@ __global__ __launch_bounds__(256) void k_list(ListArgs A) {
   } else { // OP_PRED, OP_PRED_LAYOUT
     const int sh = luma ? 0 : 1;
     unsigned long long avail = 0;
-    if constexpr (N == 64) avail = active ? intra_avail_mask_ctu(x, y, A.P) : 0; // a whole CTU, luma (hmx_tu_list_create checks)
-    else avail = active ? intra_avail_mask(x << sh, y << sh, N << sh, A.P) : 0;
+    if constexpr (N == 64) avail = active ? intra_avail_mask_ctu(x, y, P) : 0; // a whole CTU, luma (hmx_tu_list_create checks)
+    else avail = active ? intra_avail_mask(x << sh, y << sh, N << sh, P) : 0;
     if constexpr (OP == OP_PRED_LAYOUT) // slices, tiles, constrained intra pred: a subset of the geometric mask
       avail = active ? intra_avail_mask_layout(avail, x << sh, y << sh, N << sh, N == 64 ? 3 : 2, A.lay) : 0;
     const short *rec0 = a_p + (size_t)y * a_s + x;
     const int rst = a_s;
-    intra_refs<N, N>(L, gl, active, [&](int dx, int dy) { return (int)rec0[(ptrdiff_t)dy * rst + dx]; }, luma, avail, A.P);
+    intra_refs<N, N>(L, gl, active, [&](int dx, int dy) { return (int)rec0[(ptrdiff_t)dy * rst + dx]; }, luma, avail, P);
     if (active) {
       int org_row[N];
       if (A.cost) load_row16<N>(pick3(A.org.p, pl) + (size_t)(y + gl) * pick3(A.org.s, pl) + x, org_row);
       const int nm = A.n_modes <= 0 ? 1 : A.n_modes;
       for (int m = 0; m < nm; m++) {
-        intra_pred_block<N>(L, gl, A.n_modes <= 0 ? (int)t.mode : (int)A.modes[m], luma, A.P, row);
+        intra_pred_block<N>(L, gl, A.n_modes <= 0 ? (int)t.mode : (int)A.modes[m], luma, P, row);
         if (b_p) store_row16<N>(b_p + (A.n_modes <= 0 ? 0 : m * pick3(A.mode_elems, pl)) + (size_t)(y + gl) * b_s + x, row);
         if (A.cost) { // the prediction never leaves the registers: estIntraPredQT's calcHAD(org, pred) fused in
 #pragma unroll
           for (int k = 0; k < N; k++) row[k] = org_row[k] - row[k];
           const int satd = satd_block<N>(L, gl, row);
-          if (gl == 0) A.cost[(size_t)d.idx * nm + m] = (uint32_t)satd >> (A.P.bit_depth - 8);
+          if (gl == 0) A.cost[(size_t)d.idx * nm + m] = (uint32_t)satd >> (P.bit_depth - 8);
         }
       }
     }
@@ -273,6 +282,19 @@ __global__ __launch_bounds__(256) void k_inter4(ListArgs A) {
   }
 }
 
+// the launch of one size class with a QP map (run_list): the three transform operations only
+template <int OP>
+static int launch_list_qmap(hmx_ctx *c, int log2n, const ListArgsQ &A) {
+  if (A.n <= 0) return HMX_OK;
+  const unsigned ny = A.pics ? (unsigned)A.n_pics : 1u;
+  const bool known = with_size<32>(log2n < 2 || log2n > 5 ? 0 : 1 << log2n, [&](auto n) {
+    constexpr int N = n;
+    hipLaunchKernelGGL((k_list<N, OP, true>), dim3((A.n + Slots<N>::v - 1) / Slots<N>::v, ny), dim3(256), 0, c->stream, A);
+  });
+  if (!known) return fail(c, HMX_ERR_ARG, "unsupported block size");
+  HIPCHK(c, hipGetLastError());
+  return HMX_OK;
+}
 template <int OP>
 static int launch_list(hmx_ctx *c, int log2n, const ListArgs &A) {
   if (A.n <= 0) return HMX_OK;
@@ -352,12 +374,26 @@ extern "C" void hmx_tu_list_destroy(hmx_ctx *c, hmx_tu_list *l) {
   delete l;
 }
 
-static int run_list(hmx_ctx *c, int op, const hmx_tu_list *l, ListArgs A) {
+// pp != NULL: one of the transform entries that honour hmx_set_qp_map; with a map set every size class goes through k_list_qmap
+// (the one-lane 4x4 and the matrix-core 32x32 kernels keep the single QP they were written for)
+static int run_list(hmx_ctx *c, int op, const hmx_tu_list *l, ListArgs A, const hmx_pic_param *pp = nullptr) {
   if (l->cnt[4] && op != OP_PRED && op != OP_PRED_LAYOUT) return fail(c, HMX_ERR_ARG, "the list holds 64x64 blocks: intra prediction only (the largest transform is 32x32)");
+  ListArgsQ AQ{};
+  const bool qmap = pp && c->qm.d;
+  if (qmap)
+    if (int r = qp_map_for_call(c, A.pics ? A.n_pics : 1, pp->pic_w, pp->pic_h, pp->chroma_qp_offset, pp->slice_type, AQ.qm)) return r;
   for (int s = 0; s < 5; s++) {
     if (!l->cnt[s]) continue;
     A.tus = l->d + l->off[s];
     A.n = l->cnt[s];
+    if (qmap) {
+      static_cast<ListArgs &>(AQ) = A;
+      const int r = op == OP_TRANSFORM_NXN ? launch_list_qmap<OP_TRANSFORM_NXN>(c, s + 2, AQ)
+                    : op == OP_INVTRANSFORM_NXN ? launch_list_qmap<OP_INVTRANSFORM_NXN>(c, s + 2, AQ)
+                                                : launch_list_qmap<OP_TRANSFORM_RECON>(c, s + 2, AQ);
+      if (r) return r;
+      continue;
+    }
     if (op == OP_TRANSFORM_RECON && s == 0 && A.pics && !A.abs_sum) { // 4x4 blocks: one lane per block
       hipLaunchKernelGGL(k_inter4, dim3((unsigned)((A.n + 255) / 256), (unsigned)A.n_pics), dim3(256), 0, c->stream, A);
       HIPCHK(c, hipGetLastError());
@@ -382,7 +418,7 @@ extern "C" int hmx_batch_transformNxN(hmx_ctx *c, const hmx_tu_list *l, const hm
   A.lev = to_dev(lev);
   A.abs_sum = d_abs_sum;
   A.P = make_picdev(c, pp);
-  return run_list(c, OP_TRANSFORM_NXN, l, A);
+  return run_list(c, OP_TRANSFORM_NXN, l, A, pp);
 }
 
 extern "C" int hmx_batch_residual_transformNxN(hmx_ctx *c, const hmx_tu_list *l, const hmx_pic *org, const hmx_pic *pred,
@@ -395,7 +431,7 @@ extern "C" int hmx_batch_residual_transformNxN(hmx_ctx *c, const hmx_tu_list *l,
   A.lev = to_dev(lev);
   A.abs_sum = d_abs_sum;
   A.P = make_picdev(c, pp);
-  return run_list(c, OP_TRANSFORM_NXN, l, A);
+  return run_list(c, OP_TRANSFORM_NXN, l, A, pp);
 }
 
 extern "C" int hmx_batch_invtransformNxN(hmx_ctx *c, const hmx_tu_list *l, const hmx_levels *lev, const hmx_pic *pred,
@@ -407,7 +443,7 @@ extern "C" int hmx_batch_invtransformNxN(hmx_ctx *c, const hmx_tu_list *l, const
   A.b = to_dev(out);
   A.lev = to_dev(lev);
   A.P = make_picdev(c, pp);
-  return run_list(c, OP_INVTRANSFORM_NXN, l, A);
+  return run_list(c, OP_INVTRANSFORM_NXN, l, A, pp);
 }
 
 static int run_list_multi(hmx_ctx *c, int op, const hmx_tu_list *l, int n_pics, const hmx_pic *a, const hmx_pic *b,
@@ -429,7 +465,7 @@ static int run_list_multi(hmx_ctx *c, int op, const hmx_tu_list *l, int n_pics, 
   A.abs_stride = l->n;
   A.have_pred = have_pred;
   A.P = make_picdev(c, pp);
-  return run_list(c, op, l, A);
+  return run_list(c, op, l, A, pp);
 }
 
 extern "C" int hmx_batch_residual_transformNxN_multi(hmx_ctx *c, const hmx_tu_list *l, int n_pics, const hmx_pic *org,

@@ -18,7 +18,10 @@ tc_offset_div2]), and the layout of its slices, tiles and constrained intra pred
 raster order, or None: one region) and cip (constrained_intra_pred_flag).  For the loop filters: slice_id / tile_id (slice
 index in decoding order / tile index per CTU in raster order, or None: one slice / tile), lf_cross_slice (one
 slice_loop_filter_across_slices_enabled_flag per slice) and lf_cross_tile (loop_filter_across_tiles_enabled_flag); from these
-lf_border_avail() makes the byte per CTU that says which neighbour CTUs deblocking and SAO may read.  wp: None, or the slice's
+lf_border_avail() makes the byte per CTU that says which neighbour CTUs deblocking and SAO may read.  qp_map (optional): int8
+[ceil(h / 4)][ceil(w / 4)], the luma QP of every 4x4 luma unit (TComDataCU::getQP; a stream with cu_qp_delta, adaptive QP) -- when
+present, decode_sequence() sets it (hmx_set_qp_map) for the whole-picture and block-list calls of the picture, which then do not
+quantise with qp, and deblock_maps() returns it as the deblocking QP map; when absent nothing changes.  wp: None, or the slice's
 explicit weighted prediction: flags (the PPS's use WP, WP bi-pred), poc / tab (per list: the POC of every entry, its rows
 [entry][component][weight, offset, log2 denominator]) and ridx (the two reference indices of every prediction unit).  load_pictures() reads
 the .npz fixtures of tests/golden/make_stream_golden.py, make_stream_layout_golden.py and make_stream_lf_golden.py.  The
@@ -196,7 +199,18 @@ def deblock_maps(p):
         if y and y % 2 == 0:
             bsh[y, x:x + n] = 2
     _drop_closed_edges(p, bsv, bsh)
-    return bsv, bsh, np.full((uh, uw), p["qp"], np.int8)
+    return bsv, bsh, qp_unit_map(p)[:uh, :uw]
+
+
+def qp_unit_map(p):
+    """The luma QP of every 4x4 luma unit, int8 [ceil(h / 4)][ceil(w / 4)]: the picture's qp_map, or its one QP everywhere."""
+    uw, uh = -(-p["w"] // 4), -(-p["h"] // 4)
+    if p.get("qp_map") is None:
+        return np.full((uh, uw), p["qp"], np.int8)
+    m = np.ascontiguousarray(p["qp_map"], np.int8)
+    if m.shape != (uh, uw):
+        raise ValueError(f"qp_map: shape {m.shape}, the picture has {(uh, uw)} units")
+    return m
 
 
 DBK_UNIT = np.dtype([("intra", "u1"), ("cbf", "u1"), ("ref", "i1", 2), ("mv", "<i2", (2, 2))])
@@ -344,6 +358,12 @@ def decode_sequence(pics):
             d_rec = capi.DevPicture(ctx, w, h, m, m).zero()
             rec_arr = (capi.Pic * 1)(d_rec.as_pic())
             keep = []
+            if p.get("qp_map") is not None:  # a QP per block for this picture's transform calls (synchronised before it is freed)
+                d_qm = ctx.to_device(qp_unit_map(p))
+                ctx.set_qp_map(d_qm, 1)
+                keep += [d_qm]
+            else:
+                ctx.set_qp_map(None)
             if len(p["pus"]):
                 # Without weighting a unit whose two lists name one picture and one vector is predicted from list 0 alone
                 # (xCheckIdenticalMotion, TComPrediction.cpp:392-407); the average of a 14-bit intermediate with itself rounds to the
@@ -388,7 +408,7 @@ def decode_sequence(pics):
                 d_lev.free()
             if is_deblocked(p):
                 bsv, bsh, qpm = deblock_maps(p)
-                d_bv, d_bh, d_qp = ctx.to_device(bsv), ctx.to_device(bsh), ctx.to_device(qpm)
+                d_bv, d_bh, d_qp = ctx.to_device(bsv), ctx.to_device(bsh), ctx.to_device(np.ascontiguousarray(qpm))
                 if len(p["pus"]):
                     units, ev, eh = strength_inputs(p)
                     d_u, d_ev, d_eh = ctx.to_device(units), ctx.to_device(ev), ctx.to_device(eh)
