@@ -94,224 +94,201 @@ struct IntraCall {
 // stream capture to record the call as a HIP graph.
 static int issue_chain_launches(hmx_ctx *c, const IntraCall &k, hipStream_t main);
 
-// ---- packed schedule, host side ----
-static int issue_packed(hmx_ctx *c, const IntraCall &k, hipStream_t st) {
-  auto &pk = c->pk;
-  const hmx_intra_plan *p0 = k.plans[0];
-  const int n_pics = k.n_pics;
-  const bool enc = k.enc;
-  PackGeom G{};
-  G.n_pics = n_pics;
-  G.I = k.I;
-  G.n_groups = (n_pics + G.I - 1) / G.I;
-  G.n_shards = std::min(8, G.n_groups);
+// ---- packed schedule, host side: the steps of one call around the rules of hmx_call_rules.h (issue_packed puts them together) ----
+enum PackVariant { kPackPlain = 0, kPackRdoq = 1, kPackQmap = 2 }; // which instantiation family of k_intra_packed the call launches
+struct PackedCall { // what the packed call decides
+  PackVariant variant;
+  PackShape S;        // pack_shape over the totals of the call's plans
+  uint32_t tex_sizes; // hmx_intra_plan::tex_sizes of all plans, or-ed
+  bool want_sse;      // the distortion output (hmx_set_sse_output) covers this call
+};
+static PackedCall packed_shape(const hmx_ctx *c, const IntraCall &k) {
+  PackedCall pc{};
+  pc.variant = k.enc && c->crq.n > 0 ? kPackRdoq : k.qmap ? kPackQmap : kPackPlain;
+  pc.want_sse = k.enc && (int)c->sse_out.size() >= k.n_pics;
   uint64_t items = 0, sz[4] = {0, 0, 0, 0};
-  uint32_t tex_sizes = 0;
-  for (int i = 0; i < n_pics; i++) {
+  int max_levels = 0;
+  for (int i = 0; i < k.n_pics; i++) {
     const hmx_intra_plan *pl = k.plan(i);
-    G.max_levels = std::max(G.max_levels, pl->n_levels);
+    max_levels = std::max(max_levels, pl->n_levels);
     items += (uint64_t)pl->n_tu;
     for (int s = 0; s < 4; s++) sz[s] += pl->size_total[s];
-    tex_sizes |= pl->tex_sizes;
+    pc.tex_sizes |= pl->tex_sizes;
   }
-  // one lane per 4x4 block is the throughput shape, four lanes per block make more, shorter waves (small batches)
-  // (measured with the mode-aware dependency order, 2160p mix: 64 lanes/wave-item ahead at 8..128 and from 384 pictures,
-  // 16 ahead at 192 and 256)
-  G.slots4 = c->knob.slots4 ? c->knob.slots4 : ((n_pics >= 160 && n_pics < 320) ? 16 : 64);
-  if (k.qmap) G.slots4 = 64; // the kernel with a QP per block has one wave-item shape per size class (HMX_PACK_SLOTS4 / 8 do not apply)
-  const bool rdoq = enc && c->crq.n > 0;
-  if (rdoq) {
-    if (c->crq.n != 1 && c->crq.n != n_pics) return fail(c, HMX_ERR_ARG, "frame_intra: hmx_set_rdoq described another number of pictures");
-    if (G.I > kRdoqMaxGroup) return fail(c, HMX_ERR_ARG, "frame_intra: RDOQ keeps the bit-estimate tables of a packing group in LDS: at most 2 pictures per group (HMX_PACK_GROUP)");
-    G.slots4 = 64; // a 4x4 block's RDOQ runs inside one lane
-    // Inside the kernel RDOQ's levels travel as 16-bit words (hmx_rdoq.h); the reference keeps TCoeff = Int.  A level can reach
-    // (32768 * q) >> qbits: at the lowest QPs of deep bit depths that exceeds 32767 for the large transforms (10 bit, per = 0, 32x32:
-    // ~52000) and would wrap silently -- refuse the call instead (the scalar and block-list entries send such calls through the
-    // one-lane-per-block kernel, whose levels are 32-bit: include/hmx.h).  Luma and chroma have QPs of their own: a size counts
-    // for the texture type that holds a block of it (32x32 luma beside a lower chroma QP does not make a 32x32 chroma block).
-    // The plans of a call share the picture parameters (the kernel takes them from the first): so does this check, over the
-    // sizes of all of them.  (sz[] sizes the tables below.)
-    for (int t = 0; t < 2; t++)
-      for (int lg = 2; lg <= 5; lg++) {
-        if (!((tex_sizes >> (4 * t + lg - 2)) & 1)) continue;
-        const int qbits = 14 + p0->P.qd[t].per_qbits + (15 - p0->P.bit_depth - lg);
-        if (((32768ll * p0->P.qd[t].q) >> qbits) > 32767)
-          return fail(c, HMX_ERR_ARG, "frame_intra: RDOQ in the chain keeps levels in 16 bits; this QP / bit depth / block size can exceed them (raise the QP or use the flat quantiser)");
-      }
+  pc.S = pack_shape(k.n_pics, k.I, c->knob.slots4, c->knob.slots8, pc.variant == kPackRdoq, k.qmap, max_levels, sz, items);
+  return pc;
+}
+// RDOQ as the quantiser: what hmx_set_rdoq described fits the call, and no level can leave the 16-bit words it travels in
+static int packed_rdoq_checks(hmx_ctx *c, const IntraCall &k, const PackedCall &pc) {
+  const PicDev &P = k.plans[0]->P;
+  if (c->crq.n != 1 && c->crq.n != k.n_pics) return fail(c, HMX_ERR_ARG, "frame_intra: hmx_set_rdoq described another number of pictures");
+  if (pc.S.G.I > kRdoqMaxGroup) return fail(c, HMX_ERR_ARG, "frame_intra: RDOQ keeps the bit-estimate tables of a packing group in LDS: at most 2 pictures per group (HMX_PACK_GROUP)");
+  // Inside the kernel RDOQ's levels travel as 16-bit words (hmx_rdoq.h): a call in which one can exceed them (rdoq_levels_fit16) is
+  // refused (the scalar and block-list entries send such calls through the one-lane-per-block kernel, whose levels are 32-bit:
+  // include/hmx.h).  Luma and chroma have QPs of their own: a size counts for the texture type that holds a block of it (32x32
+  // luma beside a lower chroma QP does not make a 32x32 chroma block).  The plans of a call share the picture parameters (the
+  // kernel takes them from the first): so does this check, over the sizes of all of them.
+  for (int t = 0; t < 2; t++)
+    for (int lg = 2; lg <= 5; lg++)
+      if (((pc.tex_sizes >> (4 * t + lg - 2)) & 1) && !rdoq_levels_fit16(P.qd[t].q, P.qd[t].per_qbits, P.bit_depth, lg))
+        return fail(c, HMX_ERR_ARG, "frame_intra: RDOQ in the chain keeps levels in 16 bits; this QP / bit depth / block size can exceed them (raise the QP or use the flat quantiser)");
+  return HMX_OK;
+}
+// The per-picture table of the prep kernels and of the chain: where a picture's levels and distortions go, the plan it follows
+static int upload_pack_pics(hmx_ctx *c, const IntraCall &k, const PackedCall &pc, hipStream_t st) {
+  std::vector<PackPic> hp(k.n_pics);
+  for (int i = 0; i < k.n_pics; i++) {
+    const hmx_intra_plan *pl = k.plan(i);
+    for (int p = 0; p < 3; p++) hp[i].lev[p] = k.lev[i].plane[p], hp[i].lev_stride[p] = k.lev[i].stride[p];
+    hp[i].n_levels = pl->n_levels;
+    hp[i].ltab = pl->d_ltab;
+    hp[i].ltus = pl->d_ltus;
+    for (int p = 0; p < 3; p++) hp[i].sse[p] = pc.want_sse ? c->sse_out[i].plane[p] : nullptr;
   }
-  // 8x8 blocks: sixteen per wave-item on four lanes each (wave_chain_8x2) where throughput counts, eight on eight lanes where a
-  // wave-item's latency does (and under RDOQ, whose rounds are laid out for eight)
-  G.slots8 = rdoq || k.qmap || G.slots4 != 64 ? 8 : c->knob.slots8 ? c->knob.slots8 : (n_pics >= 640 ? 16 : 8); // measured, 2160p mix: 512 pictures -3 %, 768 +4 %, 1024 +8 %, 2048 +11 %
-  const uint64_t n_rows = (uint64_t)G.max_levels * G.n_groups;
-  uint64_t waves_bound = 4 * n_rows + 4;
-  for (int s = 0; s < 4; s++) waves_bound += sz[s] / pack_slots(s, G.slots4, G.slots8);
-  if (items >= 0xffffffffull || waves_bound >= 0x0fffffffull || n_rows >= 0x7fffffffull / 4)
-    return fail(c, HMX_ERR_ARG, "frame_intra: batch too large for one packed call (split it)");
+  HIPCHK(c, hipMemcpyAsync(c->pk.d_pics, hp.data(), sizeof(PackPic) * k.n_pics, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipStreamSynchronize(st)); // hp goes out of scope
+  return HMX_OK;
+}
+// The tables: kept while the call's pictures, plans and shape are the last call's, else sized and rebuilt on the device
+static int packed_tables(hmx_ctx *c, const IntraCall &k, const PackedCall &pc, hipStream_t st) {
+  auto &pk = c->pk;
+  const PackGeom &G = pc.S.G;
+  const uint64_t n_rows = pc.S.n_rows;
   c->tev_prep_valid = false;
-  const bool same = pk.valid && pk.key == c->table_key && pk.G.n_pics == G.n_pics && pk.G.I == G.I && pk.G.slots4 == G.slots4 && pk.G.slots8 == G.slots8 &&
-                    pk.G.max_levels == G.max_levels;
-  if (!same) {
-    pk.valid = false;
-    int r = grow_dev(c, (void **)&pk.d_pics, &pk.cap_pics, sizeof(PackPic) * n_pics);
-    if (!r) r = grow_dev(c, (void **)&pk.d_descs, &pk.cap_descs, sizeof(PackDesc) * waves_bound);
-    if (!r) r = grow_dev(c, (void **)&pk.d_items, &pk.cap_items, sizeof(FTu) * items);
-    if (!r) r = grow_dev(c, (void **)&pk.d_rows, &pk.cap_rows, sizeof(PackRow) * n_rows);
-    if (!r) r = grow_dev(c, (void **)&pk.d_done, &pk.cap_done, std::max<size_t>(sizeof(uint32_t) * kDoneStride * n_rows, sizeof(uint32_t) * 2 * kPackScanWgs)); // (also k_pack_scan's scratch)
-    if (!r && !pk.d_hdr) {
-      if (hipMalloc((void **)&pk.d_hdr, sizeof(PackHdr)) != hipSuccess) r = fail(c, HMX_ERR_NOMEM, "hipMalloc packed header");
-      else if (hipMemsetAsync(pk.d_hdr, 0, sizeof(PackHdr), st) != hipSuccess) r = fail(c, HMX_ERR_DEVICE, "hipMemsetAsync packed header");
-    }
-    if (r) return r;
-    std::vector<PackPic> hp(n_pics);
-    for (int i = 0; i < n_pics; i++) {
-      const hmx_intra_plan *pl = k.plan(i);
-      for (int p = 0; p < 3; p++) hp[i].lev[p] = k.lev[i].plane[p], hp[i].lev_stride[p] = k.lev[i].stride[p];
-      hp[i].n_levels = pl->n_levels;
-      hp[i].ltab = pl->d_ltab;
-      hp[i].ltus = pl->d_ltus;
-      for (int p = 0; p < 3; p++) hp[i].sse[p] = (enc && (int)c->sse_out.size() >= n_pics) ? c->sse_out[i].plane[p] : nullptr;
-    }
-    HIPCHK(c, hipMemcpyAsync(pk.d_pics, hp.data(), sizeof(PackPic) * n_pics, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipStreamSynchronize(st)); // hp goes out of scope
-    HIPCHK(c, hipMemsetAsync(pk.d_hdr, 0, offsetof(PackHdr, abort), st)); // everything but the sticky abort word (below)
-    const unsigned prep_waves = (unsigned)((n_rows + (uint64_t)(64 / G.I) - 1) / (uint64_t)(64 / G.I));
-    hipLaunchKernelGGL(k_pack_count, dim3(prep_waves), dim3(64), 0, st, pk.d_pics, pk.d_rows, G, (int)n_rows);
-    // (the completion counters are cleared behind the prep kernels: their array doubles as the scan's scratch)
-    hipLaunchKernelGGL(k_pack_scan<false>, dim3(kPackScanWgs), dim3(1024), 0, st, pk.d_rows, pk.d_hdr, G, pk.d_done);
-    hipLaunchKernelGGL(k_pack_scan<true>, dim3(kPackScanWgs), dim3(1024), 0, st, pk.d_rows, pk.d_hdr, G, pk.d_done);
-    hipLaunchKernelGGL(k_pack_fill, dim3((unsigned)((G.max_levels + kPackFillLevels - 1) / kPackFillLevels), (unsigned)G.n_groups), dim3(256), 0, st, pk.d_pics, pk.d_rows, pk.d_descs, pk.d_items, G);
-    HIPCHK(c, hipGetLastError());
-    if (c->timing && c->tev_prep) {
-      HIPCHK(c, hipEventRecord(c->tev_prep, st));
-      c->tev_prep_valid = true;
-    }
-    pk.key = c->table_key;
-    pk.G = G;
-    pk.waves_bound = waves_bound;
-    pk.valid = true;
+  if (pk.valid && pk.key == c->table_key && pk.G.n_pics == G.n_pics && pk.G.I == G.I && pk.G.slots4 == G.slots4 && pk.G.slots8 == G.slots8 &&
+      pk.G.max_levels == G.max_levels)
+    return HMX_OK;
+  pk.valid = false;
+  const char *what = "packed schedule tables";
+  int r = grow_dev(c, (void **)&pk.d_pics, &pk.cap_pics, sizeof(PackPic) * k.n_pics, what);
+  if (!r) r = grow_dev(c, (void **)&pk.d_descs, &pk.cap_descs, sizeof(PackDesc) * pc.S.waves_bound, what);
+  if (!r) r = grow_dev(c, (void **)&pk.d_items, &pk.cap_items, sizeof(FTu) * pc.S.items, what);
+  if (!r) r = grow_dev(c, (void **)&pk.d_rows, &pk.cap_rows, sizeof(PackRow) * n_rows, what);
+  if (!r) r = grow_dev(c, (void **)&pk.d_done, &pk.cap_done, std::max<size_t>(sizeof(uint32_t) * kDoneStride * n_rows, sizeof(uint32_t) * 2 * kPackScanWgs), what); // (also k_pack_scan's scratch)
+  if (!r && !pk.d_hdr) {
+    if (hipMalloc((void **)&pk.d_hdr, sizeof(PackHdr)) != hipSuccess) r = fail(c, HMX_ERR_NOMEM, "hipMalloc packed header");
+    else if (hipMemsetAsync(pk.d_hdr, 0, sizeof(PackHdr), st) != hipSuccess) r = fail(c, HMX_ERR_DEVICE, "hipMemsetAsync packed header");
   }
-  // counters and ticket words start from zero every call
-  HIPCHK(c, hipMemsetAsync(pk.d_done, 0, sizeof(uint32_t) * kDoneStride * n_rows, st));
+  if (r) return r;
+  if (int e = upload_pack_pics(c, k, pc, st)) return e;
+  HIPCHK(c, hipMemsetAsync(pk.d_hdr, 0, offsetof(PackHdr, abort), st)); // everything but the sticky abort word (packed_clear)
+  const unsigned prep_waves = (unsigned)((n_rows + (uint64_t)(64 / G.I) - 1) / (uint64_t)(64 / G.I));
+  hipLaunchKernelGGL(k_pack_count, dim3(prep_waves), dim3(64), 0, st, pk.d_pics, pk.d_rows, G, (int)n_rows);
+  // (the completion counters are cleared behind the prep kernels: their array doubles as the scan's scratch)
+  hipLaunchKernelGGL(k_pack_scan<false>, dim3(kPackScanWgs), dim3(1024), 0, st, pk.d_rows, pk.d_hdr, G, pk.d_done);
+  hipLaunchKernelGGL(k_pack_scan<true>, dim3(kPackScanWgs), dim3(1024), 0, st, pk.d_rows, pk.d_hdr, G, pk.d_done);
+  hipLaunchKernelGGL(k_pack_fill, dim3((unsigned)((G.max_levels + kPackFillLevels - 1) / kPackFillLevels), (unsigned)G.n_groups), dim3(256), 0, st, pk.d_pics, pk.d_rows, pk.d_descs, pk.d_items, G);
+  HIPCHK(c, hipGetLastError());
+  if (c->timing && c->tev_prep) {
+    HIPCHK(c, hipEventRecord(c->tev_prep, st));
+    c->tev_prep_valid = true;
+  }
+  pk.key = c->table_key;
+  pk.G = G;
+  pk.waves_bound = pc.S.waves_bound;
+  pk.valid = true;
+  return HMX_OK;
+}
+// What starts from zero every call: the completion counters and the ticket and owner words
+static int packed_clear(hmx_ctx *c, const PackedCall &pc, hipStream_t st) {
+  HIPCHK(c, hipMemsetAsync(c->pk.d_done, 0, sizeof(uint32_t) * kDoneStride * pc.S.n_rows, st));
   // The abort word is STICKY: it is cleared only by check_packed_abort after the host has read it (hmx_sync / hmx_download).
   // Calls queued behind a call whose dependency wait timed out see it set, leave at once and the next hmx_sync reports it --
   // a per-call clear would let call k+1 erase the failure of call k.
-  HIPCHK(c, hipMemsetAsync(pk.d_hdr->ticket, 0, sizeof(PackHdr) - offsetof(PackHdr, ticket), st));
-  const uint64_t wpl = waves_bound / (uint64_t)std::max(1, G.max_levels); // wave-items per dependency level, all groups
-  if (!c->max_resident_waves) {
+  HIPCHK(c, hipMemsetAsync(c->pk.d_hdr->ticket, 0, sizeof(PackHdr) - offsetof(PackHdr, ticket), st));
+  return HMX_OK;
+}
+// Resident waves of a variant of the packed kernel on this device: the runtime is asked once per context and variant.  (The RDOQ and
+// QP-map instantiations live in units of their own, which answer for them.)
+static int resident_waves(hmx_ctx *c, PackVariant v, int &resident) {
+  if (!c->pk_resident[v]) {
     int nb = 0;
     hipDeviceProp_t prop;
     HIPCHK(c, hipGetDeviceProperties(&prop, c->cfg.device));
-    HIPCHK(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_intra_packed<true, 64>, 64, 0));
-    c->max_resident_waves = std::max(64, nb * prop.multiProcessorCount);
+    if (v == kPackPlain) HIPCHK(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_intra_packed<true, 64>, 64, 0));
+    if (v == kPackRdoq && packed_rdoq_max_blocks(&nb)) return fail(c, HMX_ERR_DEVICE, "hipOccupancyMaxActiveBlocksPerMultiprocessor(k_intra_packed, RDOQ)");
+    if (v == kPackQmap && packed_qmap_max_blocks(&nb)) return fail(c, HMX_ERR_DEVICE, "hipOccupancyMaxActiveBlocksPerMultiprocessor(k_intra_packed_qmap)");
+    c->pk_resident[v] = std::max(64, nb * prop.multiProcessorCount);
   }
-  // Enough persistent waves to hold about two levels' worth of wave-items (the waves of the next row load their
-  // descriptors and originals while the current row finishes), never more than the device keeps resident.
-  int resident = c->max_resident_waves;
-  if (rdoq) {
-    if (!c->crq.max_waves) {
-      int nb = 0;
-      hipDeviceProp_t prop;
-      HIPCHK(c, hipGetDeviceProperties(&prop, c->cfg.device));
-      if (packed_rdoq_max_blocks(&nb)) return fail(c, HMX_ERR_DEVICE, "hipOccupancyMaxActiveBlocksPerMultiprocessor(k_intra_packed, RDOQ)");
-      c->crq.max_waves = std::max(64, nb * prop.multiProcessorCount);
-    }
-    resident = c->crq.max_waves;
-  }
-  if (k.qmap) {
-    if (!c->qm_max_waves) {
-      int nb = 0;
-      hipDeviceProp_t prop;
-      HIPCHK(c, hipGetDeviceProperties(&prop, c->cfg.device));
-      if (packed_qmap_max_blocks(&nb)) return fail(c, HMX_ERR_DEVICE, "hipOccupancyMaxActiveBlocksPerMultiprocessor(k_intra_packed_qmap)");
-      c->qm_max_waves = std::max(64, nb * prop.multiProcessorCount);
-    }
-    resident = c->qm_max_waves;
-  }
-  const uint64_t want = std::max<uint64_t>(256, 2 * wpl);
-  pk.n_wg = c->knob.pack_waves ? std::min(c->knob.pack_waves, resident) : (int)std::min<uint64_t>((uint64_t)resident, want);
+  resident = c->pk_resident[v];
+  return HMX_OK;
+}
+// The kernel's arguments but for RDOQ's.  The level planes of the call are addressed as ONE slab when they lie at equal distances
+// with equal strides (a picture's planes then come from a multiply-add instead of the picture table)
+static PackArgs packed_args(const hmx_ctx *c, const IntraCall &k, const PackedCall &pc) {
+  const auto &pk = c->pk;
   PackArgs A{};
-  A.pics = pk.d_pics;
-  A.rows = pk.d_rows;
-  A.descs = pk.d_descs;
-  A.items = pk.d_items;
-  A.done = pk.d_done;
-  A.hdr = pk.d_hdr;
-  A.pool_org = k.pool_org;
-  A.pool_rec = k.pool_rec;
+  A.pics = pk.d_pics, A.rows = pk.d_rows, A.descs = pk.d_descs, A.items = pk.d_items, A.done = pk.d_done, A.hdr = pk.d_hdr;
+  A.pool_org = k.pool_org, A.pool_rec = k.pool_rec;
   A.pic_elems = k.geom.pic_elems;
   for (int p = 0; p < 3; p++) A.plane_off[p] = k.geom.plane_off[p];
   A.ctu_w = k.geom.cw;
   A.clog = ilog2i(k.geom.ctu);
-  A.n_groups = G.n_groups;
-  A.n_shards = G.n_shards;
-  A.I = G.I;
-  A.want_sse = enc && (int)c->sse_out.size() >= n_pics;
-  {
-    const hmx_levels *lv = k.lev;
-    bool slab = true;
-    for (int p = 0; p < 3 && slab; p++) {
-      const ptrdiff_t d = n_pics > 1 ? (const char *)lv[1].plane[p] - (const char *)lv[0].plane[p] : 0;
-      slab = d >= 0 && d % (ptrdiff_t)sizeof(int) == 0;
-      for (int i = 0; i < n_pics && slab; i++)
-        slab = (const char *)lv[i].plane[p] == (const char *)lv[0].plane[p] + (ptrdiff_t)i * d && lv[i].stride[p] == lv[0].stride[p];
-      A.lev_base[p] = lv[0].plane[p];
-      A.lev_pic_elems[p] = d / (ptrdiff_t)sizeof(int);
-      A.lev_stride[p] = lv[0].stride[p];
-    }
-    A.lev_slab = slab ? 1 : 0;
+  A.n_groups = pc.S.G.n_groups, A.n_shards = pc.S.G.n_shards, A.I = pc.S.G.I;
+  A.want_sse = pc.want_sse;
+  const hmx_levels *lv = k.lev;
+  bool slab = true;
+  for (int p = 0; p < 3 && slab; p++) {
+    const ptrdiff_t d = k.n_pics > 1 ? (const char *)lv[1].plane[p] - (const char *)lv[0].plane[p] : 0;
+    slab = d >= 0 && d % (ptrdiff_t)sizeof(int) == 0;
+    for (int i = 0; i < k.n_pics && slab; i++)
+      slab = (const char *)lv[i].plane[p] == (const char *)lv[0].plane[p] + (ptrdiff_t)i * d && lv[i].stride[p] == lv[0].stride[p];
+    A.lev_base[p] = lv[0].plane[p];
+    A.lev_pic_elems[p] = d / (ptrdiff_t)sizeof(int);
+    A.lev_stride[p] = lv[0].stride[p];
   }
+  A.lev_slab = slab ? 1 : 0;
   A.sleep0 = c->knob.pack_sleep0 >= 0 ? c->knob.pack_sleep0 : 16;
   A.sleep1 = c->knob.pack_sleep1 >= 0 ? c->knob.pack_sleep1 : 2;
-  A.P = p0->P;
-  if (rdoq) {
-#pragma clang fp contract(off)
-    auto &q = c->crq;
-    // lambda and the factor of the sign-hiding cost per picture, the error scale per size: the quotients are formed here, in
-    // the reference's operation order (setErrScaleCoeff TComTrQuant.cpp:2794-2818, :2205)
-    const int B = A.P.bit_depth, inc = B - 8;
-    std::vector<double> up((size_t)q.n * 4);
-    for (int t = 0; t < 2; t++) {
-      const int qs = A.P.qd[t].q, per = A.P.qd[t].per_qbits, iq = A.P.qd[t].iq_scale >> per;
-      for (int lg = 2; lg <= 5; lg++) {
-        const int tshift = 15 - B - lg;
-        double e = (double)(1 << 15);
-        e = e * ldexp(1.0, -2 * tshift);
-        e = e / (double)qs / (double)qs / (double)(1 << (2 * inc));
-        A.rq.err_scale[t][lg - 2] = e;
-      }
-      for (int i = 0; i < q.n; i++) {
-        const double lam = q.lambda[(size_t)i * 2 + t];
-        up[(size_t)i * 2 + t] = lam;
-        const long long f = (long long)((double)iq * (double)iq * (double)(1 << (2 * per)) / lam / 16 / (double)(1 << (2 * inc)) + 0.5);
-        memcpy(&up[(size_t)q.n * 2 + (size_t)i * 2 + t], &f, sizeof(f));
-      }
+  A.P = k.plans[0]->P;
+  return A;
+}
+// RDOQ's arguments: the error scale per size, and per picture lambda and the factor of the sign-hiding cost (rdoq_err_scale,
+// rdoq_rd_factor: the quotients in the reference's operation order)
+static int packed_rdoq_args(hmx_ctx *c, const IntraCall &k, PackArgs &A, hipStream_t st) {
+  auto &q = c->crq;
+  const int B = A.P.bit_depth;
+  std::vector<double> up((size_t)q.n * 4);
+  for (int t = 0; t < 2; t++) {
+    const int per = A.P.qd[t].per_qbits, iq = A.P.qd[t].iq_scale >> per;
+    for (int lg = 2; lg <= 5; lg++) A.rq.err_scale[t][lg - 2] = rdoq_err_scale(B, A.P.qd[t].q, lg);
+    for (int i = 0; i < q.n; i++) {
+      const double lam = q.lambda[(size_t)i * 2 + t];
+      up[(size_t)i * 2 + t] = lam;
+      const long long f = rdoq_rd_factor(iq, per, lam, B);
+      memcpy(&up[(size_t)q.n * 2 + (size_t)i * 2 + t], &f, sizeof(f));
     }
-    // The table depends on hmx_set_rdoq's multipliers and the call's quantiser parameters only: it goes up when one of them changed
-    // (the first call after hmx_set_rdoq, or another QP), so that steady-state calls queue behind each other without a host wait.
-    uint64_t lkey = 1469598103934665603ull ^ q.serial;
-    for (int t = 0; t < 2; t++)
-      for (int v : {A.P.qd[t].q, A.P.qd[t].per_qbits, A.P.qd[t].iq_scale, B, q.n}) lkey = (lkey ^ (uint64_t)(uint32_t)v) * 1099511628211ull;
-    if (!q.lambda_valid || q.lambda_key != lkey) {
-      HIPCHK(c, hipMemcpyAsync(q.d_lambda, up.data(), up.size() * sizeof(double), hipMemcpyHostToDevice, st));
-      HIPCHK(c, hipStreamSynchronize(st)); // `up` goes out of scope
-      q.lambda_key = lkey, q.lambda_valid = true;
-    }
-    A.rq.est = q.d_est;
-    A.rq.lambda = q.d_lambda;
-    A.rq.rd_factor = reinterpret_cast<const long long *>(q.d_lambda + (size_t)q.n * 2);
-    A.rq.pic_mul = q.n == 1 ? 0 : 1;
-    A.rq.n_pics = n_pics;
   }
-  const dim3 grid((unsigned)pk.n_wg), blk(64);
-  if (rdoq) {
+  // The table depends on hmx_set_rdoq's multipliers and the call's quantiser parameters only: it goes up when one of them changed
+  // (the first call after hmx_set_rdoq, or another QP), so that steady-state calls queue behind each other without a host wait.
+  uint64_t lkey = 1469598103934665603ull ^ q.serial;
+  for (int t = 0; t < 2; t++)
+    for (int v : {A.P.qd[t].q, A.P.qd[t].per_qbits, A.P.qd[t].iq_scale, B, q.n}) lkey = (lkey ^ (uint64_t)(uint32_t)v) * 1099511628211ull;
+  if (!q.lambda_valid || q.lambda_key != lkey) {
+    HIPCHK(c, hipMemcpyAsync(q.d_lambda, up.data(), up.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipStreamSynchronize(st)); // `up` goes out of scope
+    q.lambda_key = lkey, q.lambda_valid = true;
+  }
+  A.rq.est = q.d_est;
+  A.rq.lambda = q.d_lambda;
+  A.rq.rd_factor = reinterpret_cast<const long long *>(q.d_lambda + (size_t)q.n * 2);
+  A.rq.pic_mul = q.n == 1 ? 0 : 1;
+  A.rq.n_pics = k.n_pics;
+  return HMX_OK;
+}
+// The launch: n_wg persistent waves of the call's variant
+static int packed_launch(hmx_ctx *c, const IntraCall &k, const PackedCall &pc, const PackArgs &A, hipStream_t st) {
+  const PackGeom &G = pc.S.G;
+  const dim3 grid((unsigned)c->pk.n_wg), blk(64);
+  if (pc.variant == kPackRdoq) {
     launch_packed_rdoq(A, A.want_sse != 0, grid.x, st); // hmx_chain_rdoq.hip
-  } else if (k.qmap) {
+  } else if (pc.variant == kPackQmap) {
     PackArgsQ AQ{};
     static_cast<PackArgs &>(AQ) = A;
     AQ.qm = k.qm;
-    launch_packed_qmap(AQ, enc, A.want_sse != 0, grid.x, st); // hmx_chain_qmap.hip
+    launch_packed_qmap(AQ, k.enc, A.want_sse != 0, grid.x, st); // hmx_chain_qmap.hip
   } else {
-    with_bool(enc, [&](auto enc_t) {
+    with_bool(k.enc, [&](auto enc_t) {
       with_bool(A.want_sse != 0, [&](auto sse_t) {
         constexpr bool E = decltype(enc_t)::value, S = decltype(sse_t)::value;
         if constexpr (E || !S) { // the distortion output exists in the encoder direction only
@@ -325,6 +302,21 @@ static int issue_packed(hmx_ctx *c, const IntraCall &k, hipStream_t st) {
   HIPCHK(c, hipGetLastError());
   c->pk_pending = true;
   return HMX_OK;
+}
+static int issue_packed(hmx_ctx *c, const IntraCall &k, hipStream_t st) {
+  const PackedCall pc = packed_shape(c, k);
+  if (pc.variant == kPackRdoq)
+    if (int r = packed_rdoq_checks(c, k, pc)) return r;
+  if (pc.S.too_large) return fail(c, HMX_ERR_ARG, "frame_intra: batch too large for one packed call (split it)");
+  if (int r = packed_tables(c, k, pc, st)) return r;
+  if (int r = packed_clear(c, pc, st)) return r;
+  int resident = 0;
+  if (int r = resident_waves(c, pc.variant, resident)) return r;
+  c->pk.n_wg = pack_wave_count(c->knob.pack_waves, resident, pc.S.waves_bound, pc.S.G.max_levels);
+  PackArgs A = packed_args(c, k, pc);
+  if (pc.variant == kPackRdoq)
+    if (int r = packed_rdoq_args(c, k, A, st)) return r;
+  return packed_launch(c, k, pc, A, st);
 }
 // The packed schedule's tables of the last call, copied out for the test that checks them against the plans (include/hmx.h has
 // the record layouts).  Reads only: neither the tables nor the cache key nor the sticky abort word change.
@@ -560,17 +552,8 @@ static int issue_chain_launches(hmx_ctx *c, const IntraCall &k, hipStream_t main
   return HMX_OK;
 }
 
-// Pictures per group of the packed schedule.  A group is an interleave domain of the pool and the unit that advances level
-// by level: its pictures move in lockstep, and a row is complete only when its slowest wave-item is.  Small groups keep
-// that coupling small (measured at 2048 pictures of 2160p, 64 distinct plans: 70 / 79 / 86 / 93 / 94 / 93 Gpx/s with groups
-// of 64 / 32 / 16 / 8 / 4 / 2); what is left of "packing across pictures" at 4 is enough to fill the waves of the large
-// batches, and small batches are latency-bound whatever the packing (256 pictures: 29 / 32 Gpx/s with 4 / 2; 64
-// pictures: 9.5 / 9.9 with 2 / 1).  Groups are dealt to the 8 XCDs round-robin.
-int pack_group_size(const hmx_ctx *c, int n_pics) {
-  if (c && c->knob.pack_group > 0) return std::min(c->knob.pack_group, n_pics);
-  if (c && c->crq.n > 0) return n_pics >= 512 ? kRdoqMaxGroup : 1; // RDOQ on (hmx_set_rdoq): the tables of a group wait in LDS
-  return n_pics >= 1536 ? 4 : n_pics >= 512 ? 2 : 1;
-}
+// Pictures per group of the packed schedule for this context's knob and RDOQ setting (the rule: pack_group_rule, hmx_call_rules.h)
+int pack_group_size(const hmx_ctx *c, int n_pics) { return pack_group_rule(c ? c->knob.pack_group : 0, c && c->crq.n > 0, n_pics); }
 // ---- pictures resident in the working layout (include/hmx.h: hmx_tpool) ----
 extern "C" int hmx_tpool_create(hmx_ctx *c, int pic_w, int pic_h, int n_pics, hmx_tpool **out) {
   if (!c || !out || pic_w <= 0 || pic_h <= 0 || n_pics <= 0) return fail(c, HMX_ERR_ARG, "hmx_tpool_create: bad argument");
@@ -622,19 +605,9 @@ extern "C" int hmx_tpool_export(hmx_ctx *c, const hmx_tpool *t, int first, int n
 // What the call resolves to -- schedule, groups, group size, geometry -- and whether its pools and plans fit that.
 static int resolve_call(hmx_ctx *c, IntraCall &k, const hmx_tpool *torg, const hmx_tpool *trec) {
   const hmx_intra_plan *p0 = k.plans[0];
-  // Schedules.  "packed" (default): ONE persistent launch, blocks of equal size and dependency level
-  // packed into waves across pictures, each picture following its own plan, the dependency order kept by counters in
-  // memory.  The level-synchronous schedules stay as cross-checks and for A/B runs (HMX_INTRA_SCHEDULE=level|wave):
-  // "level" = one launch per picture-wide dependency level (pictures that share ONE plan run it across pictures on a
-  // pool interleaved per stream group), "wave" = one launch per CTU diagonal with autonomous waves.
-  const int sched_base = k.resident ? 3 : c->knob.schedule >= 0 ? c->knob.schedule : 3;
-  const bool packed = sched_base == 3, use_level = sched_base == 1;
-  k.across = use_level && k.plan_stride == 0 && c->knob.across != 0;
-  k.schedule = packed ? 3 : !use_level ? 0 : (k.across ? 2 : 1);
-  // Picture groups of the across schedule on separate streams: measured at 1024 pictures 64.8 / 73.6 / 76.1 / 51.8 Gpx/s
-  // with 1 / 2 / 3 / 4 groups.
-  k.groups = !k.across ? 1 : k.n_pics >= 640 ? 3 : k.n_pics >= 384 ? 2 : 1;
-  if (use_level && c->knob.streams > 0) k.groups = std::min(std::max(c->knob.streams, 1), std::min(k.n_pics, (int)hmx_ctx::kMaxSide));
+  const CallSchedule s = resolve_schedule(k.resident, k.plan_stride, k.n_pics, k.onto, c->knob); // the rule: hmx_call_rules.h
+  const bool packed = s.schedule == 3, use_level = s.schedule == 1 || s.schedule == 2;
+  k.schedule = s.schedule, k.across = s.across, k.groups = s.groups, k.pipeline_conv = s.pipeline_conv;
   // packed: groups of I pictures are the interleave domains of the pool and the lanes of the tables' prep kernels
   k.I = k.resident ? trec->I : packed ? pack_group_size(c, k.n_pics) : 1;
   k.geom = tiled_geom(p0->P.pic_w, p0->P.pic_h, p0->P.ctu);
@@ -642,8 +615,6 @@ static int resolve_call(hmx_ctx *c, IntraCall &k, const hmx_tpool *torg, const h
     for (const hmx_tpool *t : {trec, k.enc ? torg : trec})
       if (!(t->geom == k.geom) || t->n_pics < k.n_pics || t->I != k.I)
         return fail(c, HMX_ERR_ARG, "frame_intra: resident pool does not match the call (picture size, CTU size, pictures, group size)");
-  // Conversions pipelined with the chain, CTU row by CTU row (issue_across_pipelined): opt-in, across schedule only.
-  k.pipeline_conv = c->knob.pipeline_conv && k.across && !c->knob.graph && !k.onto;
   c->last_schedule = k.schedule;
   c->last_groups = k.groups;
   for (int i = 0; i < k.n_pics; i++) {
@@ -777,14 +748,10 @@ static int table_key_of(hmx_ctx *c, const IntraCall &k, const std::vector<PicWor
 static int upload_table(hmx_ctx *c, IntraCall &k, const std::vector<PicWork> &hw, const std::vector<ConvJob> &jobs, uint64_t key,
                         std::vector<unsigned char> &kb) {
   const size_t work_bytes = sizeof(PicWork) * k.n_pics, table_bytes = work_bytes + sizeof(ConvJob) * jobs.size();
-  if ((int)table_bytes > c->jobs_cap) {
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    hipFree(c->d_jobs);
-    c->jobs_cap = 0;
-    c->table_valid = false;
-    if (hipMalloc((void **)&c->d_jobs, table_bytes) != hipSuccess) return fail(c, HMX_ERR_NOMEM, "hipMalloc picture table");
-    c->jobs_cap = (int)table_bytes;
-  }
+  bool grew = false;
+  const int r = grow_dev(c, (void **)&c->d_jobs, &c->jobs_cap, table_bytes, "picture table", &grew);
+  if (grew) c->table_valid = false;
+  if (r) return r;
   char *base = reinterpret_cast<char *>(c->d_jobs);
   if (!c->table_valid || c->table_key != key) {
     // earlier calls may still read the table: the copies are ordered behind them on the stream; the host vectors go
@@ -927,8 +894,8 @@ extern "C" int hmx_set_rdoq(hmx_ctx *c, const hmx_rdoq_pic *pics, int n_pics) {
   static_assert(sizeof(hmx_rdoq_pic) == 8 * sizeof(EstBitsDev) + 2 * sizeof(double), "hmx_rdoq_pic: eight tables and two multipliers");
   q.n = 0; // from here on a failure (device memory, copy) leaves RDOQ OFF, never a half-written table set
   HIPCHK(c, hipStreamSynchronize(c->stream)); // a queued call may still read the previous tables
-  int r = grow_dev(c, (void **)&q.d_est, &q.cap_est, sizeof(EstBitsDev) * 8 * (size_t)n_pics);
-  if (!r) r = grow_dev(c, (void **)&q.d_lambda, &q.cap_lambda, sizeof(double) * 4 * (size_t)n_pics);
+  int r = grow_dev(c, (void **)&q.d_est, &q.cap_est, sizeof(EstBitsDev) * 8 * (size_t)n_pics, "RDOQ bit-estimate tables of the chain");
+  if (!r) r = grow_dev(c, (void **)&q.d_lambda, &q.cap_lambda, sizeof(double) * 4 * (size_t)n_pics, "RDOQ multipliers of the chain");
   if (r) return r;
   q.lambda.resize((size_t)n_pics * 2);
   for (int i = 0; i < n_pics; i++) {

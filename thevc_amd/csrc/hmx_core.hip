@@ -321,14 +321,15 @@ void *arena_push(hmx_ctx *c, const void *src, size_t bytes) {
   return arena_place(c, src, bytes);
 }
 
-int grow_dev(hmx_ctx *c, void **p, size_t *cap, size_t need) {
+int grow_dev(hmx_ctx *c, void **p, size_t *cap, size_t need, const char *what, bool *grew) {
   if (need <= *cap) return HMX_OK;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   hipFree(*p);
   *p = nullptr;
   *cap = 0;
+  if (grew) *grew = true; // the old contents are gone, whether the allocation below succeeds or not
   const size_t want = need + need / 16 + 256;
-  if (hipMalloc(p, want) != hipSuccess) return fail(c, HMX_ERR_NOMEM, "hipMalloc packed schedule tables");
+  if (hipMalloc(p, want) != hipSuccess) return fail(c, HMX_ERR_NOMEM, std::string("hipMalloc ") + what);
   *cap = want;
   return HMX_OK;
 }

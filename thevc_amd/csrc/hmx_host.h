@@ -15,6 +15,11 @@
 //   hmx_wpest.hip       the encoder's weight estimation (WeightPredAnalysis): AC/DC and weighted SAD reductions, host arithmetic
 //   hmx_aq.hip          adaptive QP (TEncPreanalyzer, TEncCu::xComputeQP): block activities of all layers, layer averages, QP maps
 //   hmx_saodec.hip      the encoder's SAO parameter search (rdoSaoUnitAll, LCU-based): candidates per CTU, the serial decision per picture
+// Beside them stand three headers of host arithmetic with no HIP in them, which the library uses and tests/native/*.cpp runs on the CPU:
+//   hmx_arena.h         where a call's tables go in the argument arena
+//   hmx_rdoq_core.h     xRateDistOptQuant decomposed for the lanes of a wave (host and device)
+//   hmx_call_rules.h    what a whole-picture call decides before it touches the device: packing group, shape and limits of the packed
+//                       tables, persistent waves, the schedule it resolves to, RDOQ's per-call constants
 // and hmx_lib.hip includes all of them for a single-translation-unit build (-DHMX_PACK_PROFILE builds read device
 // symbols of several parts).  Build: __graft_entry__.build() compiles the parts in parallel and links libhmx.so.
 //
@@ -40,6 +45,7 @@
 #include <vector>
 
 #include "hmx_arena.h"
+#include "hmx_call_rules.h"
 #include "hmx_kernels.h"
 #include "hmx_rdoq.h"
 
@@ -199,10 +205,7 @@ struct PackPic { // per picture: where its levels go, and the plan it follows
   const FTu *ltus;
   uint32_t *sse[3]; // distortion output per plane (hmx_set_sse_output), NULL = none
 };
-struct PackGeom {
-  int n_pics, I, n_groups, n_shards, max_levels, slots4, slots8;
-};
-__host__ __device__ __forceinline__ uint32_t pack_slots(int s, int slots4, int slots8) { return s == 0 ? (uint32_t)slots4 : s == 1 ? (uint32_t)slots8 : s == 2 ? 4u : 1u; }
+// (PackGeom and pack_slots: hmx_call_rules.h)
 
 struct hmx_ctx {
   hmx_config cfg;
@@ -218,7 +221,7 @@ struct hmx_ctx {
   int pool_pics = 0;
   int own_cw = 0, own_ch = 0;     // CTU grid the pools were sized for
   ConvJob *d_jobs = nullptr;      // [2][n_pics*3]: to-tiled jobs, then from-tiled jobs
-  int jobs_cap = 0;
+  size_t jobs_cap = 0;            // bytes
   // whole-picture calls recorded as HIP graphs (run_graph, hmx_chain.hip)
   struct GraphEntry {
     uint64_t key;
@@ -237,7 +240,7 @@ struct hmx_ctx {
   bool tev_prep_valid = false;
   bool tev_valid = false;
   // level schedule: picture groups run on side streams so that launches of different groups overlap
-  static const int kMaxSide = 8;
+  static const int kMaxSide = kMaxSideStreams;
   hipStream_t side[kMaxSide] = {};
   // layout conversions pipelined with the chain (across schedule): one stream for the conversions, one event per CTU row
   // and direction, one per (group, CTU row) for "this row is final"
@@ -252,7 +255,8 @@ struct hmx_ctx {
   int *rdoq_wi = nullptr;
   RdoqBlock *rdoq_blocks = nullptr;
   EstBitsDev *rdoq_est = nullptr;
-  int rdoq_T = 0, rdoq_est_cap = 0, rdoq_blocks_cap = 0;
+  int rdoq_T = 0;
+  size_t rdoq_est_cap = 0, rdoq_blocks_cap = 0; // bytes
   uint64_t rdoq_key = 0;      // of the block list and tables resident on the device
   bool rdoq_resident = false;
   size_t rdoq_class_n[4] = {0, 0, 0, 0}; // blocks of 32, 16, 8, 4 in the resident list
@@ -262,7 +266,7 @@ struct hmx_ctx {
   bool rdoq_consts_valid = false;
   double *rdoq_consts = nullptr; // k_rdoq_tiles: lambda [luma, chroma], then the Int64 factors of sign hiding
   int *d_mcmap = nullptr; // cell -> PU maps of the last motion-compensation call
-  size_t mcmap_cap = 0;
+  size_t mcmap_cap = 0; // bytes
   unsigned long long *d_me_keys = nullptr; // hmx_batch_fullpel_search: one (cost, raster index) word per unit
   size_t me_keys_cap = 0;
   void *d_wpest = nullptr; // hmx_wp_acdc_multi: the sample sums between its passes; hmx_wp_estimate_slices: the sums it downloads
@@ -286,8 +290,7 @@ struct hmx_ctx {
     int n_wg = 0;
     uint64_t waves_bound = 0;
   } pk;
-  int max_resident_waves = 0; // of k_intra_packed on this device
-  int qm_max_waves = 0;       // of k_intra_packed_qmap
+  int pk_resident[3] = {0, 0, 0}; // resident waves of the packed kernel's variants on this device, by PackVariant (0: not asked yet)
   bool pk_pending = false;    // a packed launch was issued since the last check of its abort word
   // hmx_set_rdoq: xRateDistOptQuant as the quantiser of the next whole-picture encode calls
   struct ChainRdoq {
@@ -297,7 +300,6 @@ struct hmx_ctx {
     std::vector<double> lambda;   // [n][2]
     double *d_lambda = nullptr;   // [n][2], then the Int64 factors [n][2]
     size_t cap_lambda = 0;
-    int max_waves = 0;            // resident waves of the RDOQ kernel variant
     uint64_t serial = 0;          // counts hmx_set_rdoq calls (part of the schedule key)
     uint64_t lambda_key = 0;      // of the multiplier table resident in d_lambda (serial + quantiser parameters)
     bool lambda_valid = false;
@@ -454,7 +456,10 @@ void *arena_place(hmx_ctx *c, const void *src, size_t bytes);
 void *arena_push(hmx_ctx *c, const void *src, size_t bytes); // NULL: the table alone exceeds the arena, or the copy failed
 constexpr const char *kArenaOutside = "argument arena: a table outside what the call reserved";
 void drop_graphs(hmx_ctx *c); // destroy every recorded whole-picture graph (the stream is idle)
-int grow_dev(hmx_ctx *c, void **p, size_t *cap, size_t need);
+// a grow-only device buffer of the context: at least `need` bytes behind *p.  Growing waits for the stream, frees the old buffer and
+// allocates with some headroom; `what` names the buffer in the HMX_ERR_NOMEM text ("hipMalloc <what>"), *grew (if given) is set when
+// the buffer moved, so that the caller drops whatever it believed to be resident in it
+int grow_dev(hmx_ctx *c, void **p, size_t *cap, size_t need, const char *what, bool *grew = nullptr);
 // the device form of the map set by hmx_set_qp_map for a call over n_pics pictures of pic_w x pic_h: refuses a call with more pictures
 // than maps, (re)builds the quantiser table when the chroma offset or the slice type changed                    // hmx_core.hip
 int qp_map_for_call(hmx_ctx *c, int n_pics, int pic_w, int pic_h, int chroma_qp_offset, int slice_type, QpMapDev &M);

@@ -676,14 +676,7 @@ static int mc_multi(hmx_ctx *c, int n_jobs, const hmx_mc_job *jobs, const hmx_mc
   }
   if (!max_n[0] && !max_n[1]) return HMX_OK;
   if (mapped) { // cell maps of all jobs, back to back, in a grow-only scratch buffer
-    if (map_cells > c->mcmap_cap) {
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-      hipFree(c->d_mcmap);
-      c->d_mcmap = nullptr;
-      c->mcmap_cap = 0;
-      if (hipMalloc((void **)&c->d_mcmap, map_cells * sizeof(int)) != hipSuccess) return fail(c, HMX_ERR_NOMEM, "hipMalloc cell map");
-      c->mcmap_cap = map_cells;
-    }
+    if (int r = grow_dev(c, (void **)&c->d_mcmap, &c->mcmap_cap, map_cells * sizeof(int), "cell map")) return r;
     HIPCHK(c, hipMemsetAsync(c->d_mcmap, 0xff, map_cells * sizeof(int), c->stream));
     size_t off = 0;
     for (int i = 0; i < n_jobs; i++) {

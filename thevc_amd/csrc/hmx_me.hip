@@ -303,7 +303,7 @@ static int me_fullpel(hmx_ctx *c, const char *name, const hmx_me_unit *units, in
   const size_t unit_bytes = sizeof(hmx_me_unit) * (size_t)n, prefix_bytes = sizeof(uint32_t) * ((size_t)n + 1);
   if (const int r = arena_reserve(c, {unit_bytes, prefix_bytes, prefix_bytes}, "argument arena (unit list too long: split the call)")) return r;
   void *keys = c->d_me_keys;
-  const int gr = grow_dev(c, &keys, &c->me_keys_cap, sizeof(unsigned long long) * (size_t)n);
+  const int gr = grow_dev(c, &keys, &c->me_keys_cap, sizeof(unsigned long long) * (size_t)n, "motion search keys");
   c->d_me_keys = static_cast<unsigned long long *>(keys);
   if (gr) return gr;
   MeArgsWp A{};

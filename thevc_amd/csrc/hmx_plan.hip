@@ -537,8 +537,8 @@ extern "C" int hmx_intra_plan_level(const hmx_intra_plan *pl, int level, uint32_
   return HMX_OK;
 }
 extern "C" int hmx_intra_schedule_for(const hmx_ctx *c, int n_pics) { // 3 = packed, 1 = level, 0 = wave
-  (void)n_pics;
-  return c->knob.schedule >= 0 ? c->knob.schedule : 3;
+  const int s = resolve_schedule(false, 0, n_pics, false, c->knob).schedule; // a call on planes: resident pools are packed whatever the knob says
+  return s == 2 ? 1 : s;
 }
 
 static void plan_release(hmx_ctx *c, hmx_intra_plan *pl);
@@ -1032,7 +1032,7 @@ __global__ __launch_bounds__(256) void k_plan_gather(PlanTabArgs A, uint32_t per
   }
 }
 
-int plan_grow(hmx_ctx *c, int slot, size_t need) { return grow_dev(c, &c->pd.buf[slot], &c->pd.cap[slot], need); }
+int plan_grow(hmx_ctx *c, int slot, size_t need) { return grow_dev(c, &c->pd.buf[slot], &c->pd.cap[slot], need, "plan builder work buffers"); }
 void *plan_slab(hmx_ctx *c, size_t bytes, size_t *got) { // a cached slab that fits (at most 1.5x), or a new allocation
   auto &v = c->pd.slabs;
   for (size_t i = 0; i < v.size(); i++)

@@ -19,6 +19,7 @@
 // contraction is switched off for this file, and the two quotients (error scale, sign-hiding factor) are
 // formed on the host.
 #pragma once
+#include "hmx_call_rules.h"
 #include "hmx_device.h"
 #include "hmx_kernels.h"
 #include "hmx_rdoq_core.h"
@@ -48,7 +49,7 @@ struct RdoqArgs {
   int per[2], rem[2], q[2];
   double lambda[2];
   double err_scale[2][4]; // [plane type][log2n - 2]: 2^15 * 2^(-2 tshift) / q / q / 2^(2 inc)
-  long long rd_factor[2]; // (Int64)(invq * invq * 2^(2 per) / lambda / 16 / 2^(2 inc) + 0.5)
+  long long rd_factor[2]; // the Int64 factor of sign hiding's cost (rdoq_rd_factor, hmx_call_rules.h)
   // scaling list (hmx_xRateDistOptQuant_scaled; k_rdoq only): getQuantCoeff / getErrScaleCoeff of the launch's ONE block per position
   // (row-major N x N), NULL = the flat values above
   const int *qtab;
@@ -386,7 +387,7 @@ struct RdoqChain {
   int n_pics;
   double err_scale[2][4];
 };
-constexpr int kRdoqMaxGroup = 2; // pictures per packing group with RDOQ: 2 x 2 tables of 1016 bytes in LDS
+// (kRdoqMaxGroup, pictures per packing group with RDOQ: hmx_call_rules.h)
 template <int NEST>
 struct RdoqWaveLdsT {
   union {

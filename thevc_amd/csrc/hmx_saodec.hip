@@ -388,7 +388,7 @@ extern "C" int hmx_sao_decide_multi(hmx_ctx *c, int n_pics, const hmx_sao_stat *
   if (!c || !d_stats || !params || !d_units || !d_result) return fail(c, HMX_ERR_ARG, "hmx_sao_decide_multi: null argument");
   if (int r = sao_decide_check(c, "hmx_sao_decide_multi", n_pics, pic_w, pic_h, params)) return r;
   const int ctu = c->cfg.ctu_size, cw = (pic_w + ctu - 1) / ctu, n_lcu = cw * ((pic_h + ctu - 1) / ctu);
-  if (int r = grow_dev(c, &c->d_saodec, &c->saodec_cap, sizeof(SaoCand) * 3 * (size_t)n_lcu * (size_t)n_pics)) return r;
+  if (int r = grow_dev(c, &c->d_saodec, &c->saodec_cap, sizeof(SaoCand) * 3 * (size_t)n_lcu * (size_t)n_pics, "SAO candidate records")) return r;
   const hmx_sao_decide_param *d_pp =
       static_cast<const hmx_sao_decide_param *>(arena_push(c, params, sizeof(hmx_sao_decide_param) * (size_t)n_pics));
   if (!d_pp) return fail(c, HMX_ERR_NOMEM, "argument arena");

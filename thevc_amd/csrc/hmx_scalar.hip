@@ -144,24 +144,15 @@ static int rdoq_scan_index(int n, bool luma, bool intra, int mode) { // getCoefS
   return 0;
 }
 
-// the per-call constants; the two quotients are formed here, in the reference's operation order
+// the per-call constants; the two quotients are the whole-picture chain's (hmx_call_rules.h)
 static void rdoq_constants(RdoqArgs &A, int B, const hmx_qp qp[2], const double lambda[2]) {
-#pragma clang fp contract(off)
-  const int inc = B - 8;
   for (int t = 0; t < 2; t++) {
     A.per[t] = qp[t].per;
     A.rem[t] = qp[t].rem;
     A.q[t] = kQuantScales[qp[t].rem];
     A.lambda[t] = lambda[t];
-    for (int lg = 2; lg <= 5; lg++) { // setErrScaleCoeff, TComTrQuant.cpp:2794-2818 (flat quantiser coefficients)
-      const int tshift = 15 - B - lg;
-      double e = (double)(1 << 15);
-      e = e * ldexp(1.0, -2 * tshift);
-      e = e / (double)A.q[t] / (double)A.q[t] / (double)(1 << (2 * inc));
-      A.err_scale[t][lg - 2] = e;
-    }
-    const int iq = kInvQuantScales[qp[t].rem];
-    A.rd_factor[t] = (long long)((double)iq * (double)iq * (double)(1 << (2 * qp[t].per)) / lambda[t] / 16 / (double)(1 << (2 * inc)) + 0.5); // :2205
+    for (int lg = 2; lg <= 5; lg++) A.err_scale[t][lg - 2] = rdoq_err_scale(B, A.q[t], lg);
+    A.rd_factor[t] = rdoq_rd_factor(kInvQuantScales[qp[t].rem], qp[t].per, lambda[t], B);
   }
   A.bit_depth = B;
 }
@@ -175,15 +166,10 @@ static uint64_t hash_words(uint64_t h, const void *p, size_t bytes) {
   return h;
 }
 static int rdoq_launch(hmx_ctx *c, RdoqArgs A, const std::vector<RdoqBlock> &blocks, const hmx_est_bits *est, int n_est) {
-  if (n_est > c->rdoq_est_cap) {
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    hipFree(c->rdoq_est);
-    c->rdoq_est = nullptr;
-    c->rdoq_est_cap = 0;
-    if (hipMalloc((void **)&c->rdoq_est, sizeof(EstBitsDev) * n_est) != hipSuccess) return fail(c, HMX_ERR_NOMEM, "hipMalloc bit-estimate tables");
-    c->rdoq_est_cap = n_est;
-    c->rdoq_resident = false;
-  }
+  bool grew = false; // a buffer that moved holds nothing: whatever the call fails on afterwards, the list is not resident any more
+  int r = grow_dev(c, (void **)&c->rdoq_est, &c->rdoq_est_cap, sizeof(EstBitsDev) * n_est, "bit-estimate tables", &grew);
+  if (grew) c->rdoq_resident = false;
+  if (r) return r;
   if (!c->rdoq_wd) {
     const size_t T = kRdoqChunk;
     if (hipMalloc((void **)&c->rdoq_wd, sizeof(double) * (3 * 1024 + 64) * T) != hipSuccess ||
@@ -191,16 +177,10 @@ static int rdoq_launch(hmx_ctx *c, RdoqArgs A, const std::vector<RdoqBlock> &blo
       return fail(c, HMX_ERR_NOMEM, "hipMalloc RDOQ workspace");
     c->rdoq_T = (int)T;
   }
-  if ((int)blocks.size() > c->rdoq_blocks_cap) { // the whole list goes up once; the launches below follow without a synchronisation
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    hipFree(c->rdoq_blocks);
-    c->rdoq_blocks = nullptr;
-    c->rdoq_blocks_cap = 0;
-    const size_t cap = blocks.size() + blocks.size() / 8 + 1024;
-    if (hipMalloc((void **)&c->rdoq_blocks, sizeof(RdoqBlock) * cap) != hipSuccess) return fail(c, HMX_ERR_NOMEM, "hipMalloc RDOQ block list");
-    c->rdoq_blocks_cap = (int)cap;
-    c->rdoq_resident = false;
-  }
+  // the whole list goes up once; the launches below follow without a synchronisation
+  r = grow_dev(c, (void **)&c->rdoq_blocks, &c->rdoq_blocks_cap, sizeof(RdoqBlock) * blocks.size(), "RDOQ block list", &grew);
+  if (grew) c->rdoq_resident = false;
+  if (r) return r;
   // a pipeline quantises the same block structure picture after picture: when the list and the tables are the ones already
   // resident (64-bit hash over both), nothing is uploaded and nothing synchronises
   uint64_t key = hash_words(0x243f6a8885a308d3ull ^ blocks.size(), blocks.data(), sizeof(RdoqBlock) * blocks.size());
@@ -226,15 +206,13 @@ static int rdoq_issue(hmx_ctx *c, RdoqArgs A) {
   // blocks arrive sorted by size, largest first: 8x8 and larger go through the wave-cooperative routine (the decomposition
   // of hmx_rdoq_core.h), 4x4 blocks -- a single coefficient group, nothing to decompose -- one LANE per block (k_rdoq)
   const size_t n_wave = c->rdoq_class_n[0] + c->rdoq_class_n[1] + c->rdoq_class_n[2], n_all = n_wave + c->rdoq_class_n[3];
-  // The wave-cooperative routine keeps levels as 16-bit words; the reference's are Int.  At the lowest QPs of deep bit depths a
-  // level of an 8x8 or larger block can reach (32768 * q) >> qbits > 32767 (10 bit, per 0, 32x32: ~52000): those calls go through
-  // the sequential kernel, whose levels are 32-bit (the bound of the whole-picture chain, hmx_chain.hip, which refuses instead)
+  // The wave-cooperative routine keeps levels as 16-bit words; the reference's are Int.  Calls in which a level of an 8x8 or larger
+  // block can exceed them (rdoq_levels_fit16, hmx_call_rules.h) go through the sequential kernel, whose levels are 32-bit (the
+  // whole-picture chain, hmx_chain.hip, refuses instead)
   bool wide_levels = false;
   for (int t = 0; t < 2; t++)
-    for (int lg = 3; lg <= 5; lg++) {
-      const int qbits = 14 + A.per[t] + 15 - A.bit_depth - lg;
-      if (c->rdoq_class_n[5 - lg] && (qbits < 0 || ((32768ll * A.q[t]) >> qbits) > 32767)) wide_levels = true;
-    }
+    for (int lg = 3; lg <= 5; lg++)
+      if (c->rdoq_class_n[5 - lg] && !rdoq_levels_fit16(A.q[t], A.per[t], A.bit_depth, lg)) wide_levels = true;
   const bool lane_only = c->knob.rdoq_lane_only || A.qtab || wide_levels; // per-position tables: the sequential kernel reads them
   if (n_wave && !lane_only) {
     // 8x8 and larger: the wave-cooperative routine of the whole-picture chain (rdoq_wave_tiles), a wave per 8 / 4 / 1 blocks

@@ -207,7 +207,7 @@ extern "C" int hmx_wp_acdc_multi(hmx_ctx *c, int n_pics, const hmx_pic *pics, in
   const PlanesDev *d;
   if (int r = wp_pics(c, "hmx_wp_acdc_multi", pics, n_pics, &d)) return r;
   const size_t sums_bytes = sizeof(u64) * 3 * (size_t)n_pics;
-  if (int r = grow_dev(c, &c->d_wpest, &c->wpest_cap, sums_bytes)) return r;
+  if (int r = grow_dev(c, &c->d_wpest, &c->wpest_cap, sums_bytes, "weight estimation sums")) return r;
   HIPCHK(c, hipMemsetAsync(c->d_wpest, 0, sums_bytes, c->stream));
   const WpAcdcArgs A{d, static_cast<u64 *>(c->d_wpest), d_out, pic_w, pic_h};
   const dim3 grid(wp_grid_x(pic_h), 3, (unsigned)n_pics);
@@ -398,7 +398,7 @@ extern "C" int hmx_wp_estimate_slices(hmx_ctx *c, int n_slices, hmx_wp_slice *sl
   }
   // step 3: one launch, one download
   const size_t out_bytes = sizeof(int64_t) * 6 * jobs.size();
-  if (int r = grow_dev(c, &c->d_wpest, &c->wpest_cap, out_bytes)) return r;
+  if (int r = grow_dev(c, &c->d_wpest, &c->wpest_cap, out_bytes, "weight estimation sums")) return r;
   if (int r = wp_sad_run(c, "hmx_wp_estimate_slices", 256, (int)jobs.size(), jobs.data(), orgs.data(), (int)orgs.size(), recs.data(), (int)recs.size(),
                          pic_w, pic_h, static_cast<int64_t *>(c->d_wpest)))
     return r;
