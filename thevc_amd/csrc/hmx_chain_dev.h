@@ -42,6 +42,8 @@ struct OwnPicture {
   static constexpr bool kRdoq = false; // RDOQ as the chain's quantiser: packed schedule only
   static constexpr int kPredOpt = 0;   // kPredPairs | kPredMainRef, the batched forms of intra_pred_samples and build_main_ref (hmx_device.h): packed schedule only
   static constexpr bool kPadClamp = true; // the index-clamp form of the padding pass (refs_gather_pad)
+  static constexpr int kTrForms = kTrDefault; // the forms of the transform passes (hmx_transform.h) in the encoder direction
+  static constexpr int kTrFormsDec = kTrDefault; // and in the decoder direction
   const PicWork &W;
   const FTu *tus;
   __device__ __forceinline__ void wait() const {}
@@ -63,6 +65,7 @@ struct AcrossPictures {
   static constexpr bool kRdoq = false;
   static constexpr int kPredOpt = 0;
   static constexpr bool kPadClamp = true;
+  static constexpr int kTrForms = kTrDefault, kTrFormsDec = kTrDefault;
   __device__ __forceinline__ void wait() const {}
   const PicWork *pics;
   const FTu *ft; // the one block this wave works on (wave-uniform address: scalar loads)
@@ -88,6 +91,10 @@ template <int N>
 __device__ __forceinline__ unsigned lev_row_off(const PlaneView &V, int x, int y, int r) {
   return V.lev_stride ? __umul24((unsigned)(y + r), (unsigned)V.lev_stride) + x : tile_base(V.rec.ctu_w, V.rec.clog, x, y) + (unsigned)r * N;
 }
+
+// the forms of a chain's passes by direction (the inverse passes run in both)
+template <bool ENC, typename SRC>
+constexpr int chain_forms = ENC ? SRC::kTrForms : SRC::kTrFormsDec;
 
 #ifdef HMX_MARKS /* tools/section_mix.py: section boundaries as comments in the ISA */
 #define HMX_MARK(n, id) asm volatile("; HMXMARK %0 %1" ::"n"(n), "n"(id) : "memory")
@@ -134,12 +141,12 @@ __device__ __forceinline__ void wave_chain_valu(char *smem, const SRC &src, cons
         wave_sync(); // the prediction has read the reference line
         if (gl == 0)
           L.line[0] = active && !ts, L.line[1] = src.picture(), L.line[2] = luma, L.line[3] = scan_idx, L.line[4] = src.cbf_ctx(), L.line[9] = src.group_slot() * 2 + (luma ? 0 : 1), L.line[10] = 0;
-        fwd_tq_block<N>(L, gl, active, row, ts, luma, luma, scan_idx, ts, P);
+        fwd_tq_block<N, SRC::kTrForms>(L, gl, active, row, ts, luma, luma, scan_idx, ts, P);
         rdoq_wave_tiles<N, SL>(reinterpret_cast<TuLds<N> *>(smem), src.rdoq_lds(), src.rdoq(), P, lane);
       } else {
         // 16x16: the scan is diagonal, the quantiser decides sign-bit hiding in the lane that holds the group (transform-skip
         // blocks keep the general routine)
-        fwd_tq_block<N>(L, gl, active, row, ts, luma, luma, scan_idx, true, P, (N == 16 && !__any(ts)) ? lane : -1);
+        fwd_tq_block<N, SRC::kTrForms>(L, gl, active, row, ts, luma, luma, scan_idx, true, P, (N == 16 && !__any(ts)) ? lane : -1);
       }
       HMX_MARK(N, 5);
       if (active) {
@@ -164,7 +171,7 @@ __device__ __forceinline__ void wave_chain_valu(char *smem, const SRC &src, cons
     }
     // inverse of all-zero levels is exactly zero, so the reference's "if (uiAbsSum)" needs no branch
     HMX_MARK(N, 6);
-    inv_tq_block<N, (SRC::kPredOpt & kLdsBatch) != 0>(L, gl, active, ts, luma, luma, true, P, row);
+    inv_tq_block<N, (SRC::kPredOpt & kLdsBatch) != 0, chain_forms<ENC, SRC>>(L, gl, active, ts, luma, luma, true, P, row);
     HMX_MARK(N, 7);
     if (active) {
       const int mx = (1 << P.bit_depth) - 1;
@@ -249,7 +256,7 @@ __device__ __forceinline__ void wave_chain_8x2(char *smem, const SRC &src, const
 #pragma unroll
       for (int h = 0; h < 2; h++) {
         int y1[N];
-        fwd_pass<N>(v + 8 * h, y1, LG - 1 + (B - 8), false);
+        fwd_pass<N, SRC::kTrForms>(v + 8 * h, y1, LG - 1 + (B - 8), false);
         if (active) {
 #pragma unroll
           for (int k = 0; k < N; k++) L.tile[k][r0 + h] = y1[k]; // transposed store
@@ -261,7 +268,7 @@ __device__ __forceinline__ void wave_chain_8x2(char *smem, const SRC &src, const
         int z[N];
 #pragma unroll
         for (int n = 0; n < N; n++) z[n] = L.tile[r0 + h][n];
-        fwd_pass<N>(z, coef + 8 * h, LG + 6, false); // coef[8h + k] = coefficient (row k, column r0 + h)
+        fwd_pass<N, SRC::kTrForms>(z, coef + 8 * h, LG + 6, false); // coef[8h + k] = coefficient (row k, column r0 + h)
       }
       wave_sync();
     }
@@ -408,7 +415,7 @@ __device__ __forceinline__ void wave_chain_8x2(char *smem, const SRC &src, const
       int c[N];
 #pragma unroll
       for (int k = 0; k < N; k++) c[k] = wrap16(dequant_one(level_of(in[8 * h + k]), qd.iq_scale, dshift));
-      inv_pass<N>(c, mid + 8 * h, 7, false);
+      inv_pass<N, chain_forms<ENC, SRC>>(c, mid + 8 * h, 7, false);
     }
     wave_sync(); // every lane has read its levels
     if (active) {
@@ -420,7 +427,7 @@ __device__ __forceinline__ void wave_chain_8x2(char *smem, const SRC &src, const
     for (int k = 0; k < 16; k++) in[k] = L.tile[k & 7][r0 + (k >> 3)];
     if constexpr (SRC::kPredOpt & kLdsBatch) pin_regs<16>(in);
 #pragma unroll
-    for (int h = 0; h < 2; h++) inv_pass<N>(in + 8 * h, out + 8 * h, 12 - (B - 8), false);
+    for (int h = 0; h < 2; h++) inv_pass<N, chain_forms<ENC, SRC>>(in + 8 * h, out + 8 * h, 12 - (B - 8), false);
     wave_sync();
   }
   HMX_MARK(82, 8);
@@ -467,6 +474,7 @@ __device__ __forceinline__ int scan4_pos(int scan_idx, int i) { // raster positi
 
 // The transform half of a 4x4 block held by ONE lane (used by the lane-per-block chain and by the inter list kernel).
 // lane4_forward: residual (row-major) -> packed words (level | neg << 16 | deltaU << 17) after sign-bit hiding.
+template <int F = kTrDefault>
 __device__ __forceinline__ void lane4_coef(const int *resid, bool use_dst, bool ts, const PicDev &P, int *coef) {
   const int B = P.bit_depth, tshift = 15 - B - 2;
   if (ts) {
@@ -477,24 +485,24 @@ __device__ __forceinline__ void lane4_coef(const int *resid, bool use_dst, bool 
 #pragma unroll
     for (int r = 0; r < 4; r++) { // tmp[k][r] = pass1(row r)[k]
       int yk[4];
-      fwd_pass<4>(resid + 4 * r, yk, 1 + (B - 8), use_dst);
+      fwd_pass<4, F>(resid + 4 * r, yk, 1 + (B - 8), use_dst);
 #pragma unroll
       for (int k = 0; k < 4; k++) t1[4 * k + r] = yk[k];
     }
 #pragma unroll
     for (int r = 0; r < 4; r++) { // coeff[k][r] = pass2(row r of tmp)[k]
       int yk[4];
-      fwd_pass<4>(t1 + 4 * r, yk, 8, use_dst);
+      fwd_pass<4, F>(t1 + 4 * r, yk, 8, use_dst);
 #pragma unroll
       for (int k = 0; k < 4; k++) coef[4 * k + r] = yk[k];
     }
   }
 }
-template <typename PD>
+template <int F = kTrDefault, typename PD>
 __device__ __forceinline__ void lane4_forward(const int *resid, bool use_dst, bool ts, bool luma, int scan_idx, const PD &P, int *w) {
   const int B = P.bit_depth, tshift = 15 - B - 2;
   int coef[16];
-  lane4_coef(resid, use_dst, ts, P, coef);
+  lane4_coef<F>(resid, use_dst, ts, P, coef);
   const QuantDev qd = pick_qd(P, luma);
   const int qbits = 14 + qd.per_qbits + tshift;
   int sum = 0;
@@ -520,7 +528,7 @@ __device__ __forceinline__ void lane4_forward(const int *resid, bool use_dst, bo
   }
 }
 // lane4_inverse: levels (row-major) -> residual
-template <typename PD>
+template <int F = kTrDefault, typename PD>
 __device__ __forceinline__ void lane4_inverse(const int *lv, bool use_dst, bool ts, bool luma, const PD &P, int *out) {
   const int B = P.bit_depth, tshift = 15 - B - 2;
   const QuantDev qd = pick_qd(P, luma);
@@ -540,7 +548,7 @@ __device__ __forceinline__ void lane4_inverse(const int *lv, bool use_dst, bool 
     int col[4], yn[4];
 #pragma unroll
     for (int k = 0; k < 4; k++) col[k] = c[4 * k + j];
-    inv_pass<4>(col, yn, 7, use_dst);
+    inv_pass<4, F>(col, yn, 7, use_dst);
 #pragma unroll
     for (int nn = 0; nn < 4; nn++) t1[4 * j + nn] = yn[nn];
   }
@@ -549,7 +557,7 @@ __device__ __forceinline__ void lane4_inverse(const int *lv, bool use_dst, bool 
     int col[4], yn[4];
 #pragma unroll
     for (int k = 0; k < 4; k++) col[k] = t1[4 * k + j];
-    inv_pass<4>(col, yn, 12 - (B - 8), use_dst);
+    inv_pass<4, F>(col, yn, 12 - (B - 8), use_dst);
 #pragma unroll
     for (int nn = 0; nn < 4; nn++) out[4 * j + nn] = yn[nn];
   }
@@ -775,7 +783,7 @@ __device__ __forceinline__ void wave_chain_4_lane(char *smem, const SRC &src, co
       if constexpr (SRC::kRdoq) {
         if (!ts) { // transform-skip blocks keep the flat quantiser
           int coef[16];
-          lane4_coef(v, luma, false, P, coef);
+          lane4_coef<SRC::kTrForms>(v, luma, false, P, coef);
           // the lane's coefficients in scan order and its levels go through its LDS rows (the reference line and the main
           // reference are spent): no private array is indexed at run time
           const int scan_idx = coef_scan_idx(4, luma, true, mode);
@@ -792,7 +800,7 @@ __device__ __forceinline__ void wave_chain_4_lane(char *smem, const SRC &src, co
         }
       }
       if (flat) {
-        lane4_forward(v, luma, ts, luma, coef_scan_idx(4, luma, true, mode), P, w);
+        lane4_forward<SRC::kTrForms>(v, luma, ts, luma, coef_scan_idx(4, luma, true, mode), P, w);
 #pragma unroll
         for (int k = 0; k < 16; k++) w[k] = level_of(w[k]);
       }
@@ -830,7 +838,7 @@ __device__ __forceinline__ void wave_chain_4_lane(char *smem, const SRC &src, co
     }
     HMX_MARK(4, 4);
     int out[16];
-    lane4_inverse(w, luma, ts, luma, P, out);
+    lane4_inverse<chain_forms<ENC, SRC>>(w, luma, ts, luma, P, out);
     i4v r0, r1;
 #pragma unroll
     for (int k = 0; k < 4; k++) {
@@ -1497,6 +1505,11 @@ struct PackedSrc {
   // two variants were not tried with it)
   static constexpr int kPredOpt = (RDOQ || SSE) ? 0 : kPredPairs | kPredMainRef | kLdsBatch;
   static constexpr bool kPadClamp = true;
+  // the 16-point FORWARD pass keeps the matrix loops here: as multiply-add chains (seeded or not, signed constants or magnitudes) it
+  // cost encoder kernels of this schedule one to eight spilled registers; every other pass takes the chains.
+  // The DECODER kernels keep the loops in their inverse passes: they are nearer the memory limit than the issue limit, gained
+  // nothing from the chains and measured 1.2 % slower with them in one of two sessions; the butterflies stay.
+  static constexpr int kTrForms = kTrDefault & ~kTrMadFwd16, kTrFormsDec = kTrDefault & kTrFastDst;
   __device__ __forceinline__ bool want_sse() const { return SSE; }
   __device__ __forceinline__ int picture() const { return pic0 + (int)(ft.t.plane >> 2); }
   __device__ __forceinline__ int cbf_ctx() const { return (ft.t.flags >> 4) & 15; } // hmx_tu::flags bits 4..7

@@ -9,40 +9,16 @@
 // Arithmetic contract (bit-exact with the reference, see include/hmx.h for file:line):
 //   forward pass  y[k] = wrap16((sum_n M[k][n] x[n] + rnd) >> shift)      TComTrQuant.cpp:417-795
 //   inverse pass  y[n] = clip16((sum_k M[k][n] c[k] + rnd) >> shift)
-// The even/odd recursion below is an exact integer factorisation of those sums (no overflow:
+// The even/odd recursion (hmx_transform.h) is an exact integer factorisation of those sums (no overflow:
 // |sum| < 2^27), so the result equals the reference's partial butterflies.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "hmx_sbh.h"
+#include "hmx_transform.h"
 
 namespace hmx {
-
-// ---------------------------------------------------------------------------------------------
-// Tables
-// ---------------------------------------------------------------------------------------------
-// integer chosen by HEVC for cos(p*pi/64), p = 0..32 (first column of the 32-point matrix)
-__host__ __device__ constexpr int cos64(int p) {
-  constexpr int t[33] = {64, 90, 90, 90, 89, 88, 87, 85, 83, 82, 80, 78, 75, 73, 70, 67, 64,
-                         61, 57, 54, 50, 46, 43, 38, 36, 31, 25, 22, 18, 13, 9,  4,  0};
-  return t[p];
-}
-// M_N[k][n]: fold the angle (2n+1)k*(32/N)*pi/64 into the first quadrant
-__host__ __device__ constexpr int dct_coef(int N, int k, int n) {
-  int p = ((2 * n + 1) * k * (32 / N)) & 127;
-  int s = 1;
-  if (p > 64) p = 128 - p;
-  if (p > 32) {
-    p = 64 - p;
-    s = -1;
-  }
-  return s * cos64(p);
-}
-__host__ __device__ constexpr int dst_coef(int k, int n) {
-  constexpr int t[4][4] = {{29, 55, 74, 84}, {74, 74, 0, -74}, {84, -29, -74, 55}, {55, -84, 74, -29}};
-  return t[k][n];
-}
 
 __device__ __forceinline__ int clip3(int lo, int hi, int v) { return min(max(v, lo), hi); }
 // The median of three in one instruction (v_med3_i32): with lo <= hi it is clip3(lo, hi, v).  The compiler forms it from min(max())
@@ -69,93 +45,7 @@ __device__ __forceinline__ int wrap16(int v) { return (int)(short)v; }
 // selector knows to fit 24 bits, whatever the words hold
 __device__ __forceinline__ int diff17(int a, int b) { return (int)(((unsigned)a - (unsigned)b) << 15) >> 15; }
 
-// ---------------------------------------------------------------------------------------------
-// 1-D transforms on register arrays (raw sums, no rounding)
-// ---------------------------------------------------------------------------------------------
-template <int N>
-__device__ __forceinline__ void dct_fwd_raw(const int *x, int *y) {
-  if constexpr (N == 2) {
-    y[0] = 64 * (x[0] + x[1]);
-    y[1] = 64 * (x[0] - x[1]);
-  } else {
-    int e[N / 2], o[N / 2], ye[N / 2];
-#pragma unroll
-    for (int n = 0; n < N / 2; n++) {
-      e[n] = x[n] + x[N - 1 - n];
-      o[n] = x[n] - x[N - 1 - n];
-    }
-    dct_fwd_raw<N / 2>(e, ye);
-#pragma unroll
-    for (int m = 0; m < N / 2; m++) {
-      y[2 * m] = ye[m];
-      int acc = 0;
-#pragma unroll
-      for (int n = 0; n < N / 2; n++) acc += mul24(dct_coef(N, 2 * m + 1, n), o[n]); // |o| < 2^21: sums of int16 inputs
-      y[2 * m + 1] = acc;
-    }
-  }
-}
-
-template <int N>
-__device__ __forceinline__ void dct_inv_raw(const int *c, int *out) {
-  if constexpr (N == 2) {
-    out[0] = 64 * (c[0] + c[1]);
-    out[1] = 64 * (c[0] - c[1]);
-  } else {
-    int ce[N / 2], ee[N / 2];
-#pragma unroll
-    for (int m = 0; m < N / 2; m++) ce[m] = c[2 * m];
-    dct_inv_raw<N / 2>(ce, ee);
-#pragma unroll
-    for (int n = 0; n < N / 2; n++) {
-      int acc = 0;
-#pragma unroll
-      for (int m = 0; m < N / 2; m++) acc += mul24(dct_coef(N, 2 * m + 1, n), c[2 * m + 1]); // c: int16 inputs
-      out[n] = ee[n] + acc;
-      out[N - 1 - n] = ee[n] - acc;
-    }
-  }
-}
-
-// forward pass with the reference's rounding and implicit store-to-short wrap
-template <int N>
-__device__ __forceinline__ void fwd_pass(const int *x, int *y, int shift, bool use_dst) {
-  int rnd = 1 << (shift - 1);
-  if (N == 4 && use_dst) {
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-      int acc = 0;
-#pragma unroll
-      for (int n = 0; n < 4; n++) acc += mul24(dst_coef(k, n), x[n]); // x: int16-range residuals
-      y[k] = wrap16((acc + rnd) >> shift);
-    }
-  } else {
-    int raw[N];
-    dct_fwd_raw<N>(x, raw);
-#pragma unroll
-    for (int k = 0; k < N; k++) y[k] = wrap16((raw[k] + rnd) >> shift);
-  }
-}
-
-// inverse pass with Clip3(-32768, 32767)
-template <int N>
-__device__ __forceinline__ void inv_pass(const int *c, int *y, int shift, bool use_dst) {
-  int rnd = 1 << (shift - 1);
-  if (N == 4 && use_dst) {
-#pragma unroll
-    for (int n = 0; n < 4; n++) {
-      int acc = 0;
-#pragma unroll
-      for (int k = 0; k < 4; k++) acc += mul24(dst_coef(k, n), c[k]); // c: int16 coefficients
-      y[n] = clip3(-32768, 32767, (acc + rnd) >> shift);
-    }
-  } else {
-    int raw[N];
-    dct_inv_raw<N>(c, raw);
-#pragma unroll
-    for (int n = 0; n < N; n++) y[n] = clip3(-32768, 32767, (raw[n] + rnd) >> shift);
-  }
-}
+// The 1-D transforms on register arrays (dct_coef, dst_coef, fwd_pass, inv_pass): hmx_transform.h, shared with the host.
 
 // ---------------------------------------------------------------------------------------------
 // Quantiser parameters (host-prepared, one set per plane type) and scan tables

@@ -372,7 +372,7 @@ __device__ __forceinline__ int diag_group_org(int g) {
 // transformNxN core: residual row -> final levels in L.tile.  ts = transform skip (:1622),
 // use_dst = 4x4 luma intra.  do_quant = false leaves the Int coefficients (xT / xTransformSkip).
 // ---------------------------------------------------------------------------------------------
-template <int N, typename PD>
+template <int N, int F = kTrDefault, typename PD> // F: the forms of the passes (hmx_transform.h)
 __device__ __forceinline__ int fwd_tq_block(TuLds<N> &L, int gl, bool active, const int *x, bool ts, bool use_dst,
                                             bool luma, int scan_idx, bool do_quant, const PD &P, int diag_lane = -1) {
   // everything quantised here went through a forward pass (int16) or transform skip (|x| << shift
@@ -385,7 +385,7 @@ __device__ __forceinline__ int fwd_tq_block(TuLds<N> &L, int gl, bool active, co
     for (int k = 0; k < N; k++) coef[k] = tshift >= 0 ? x[k] << tshift : (x[k] + (1 << (-tshift - 1))) >> (-tshift);
   } else {
     int y1[N];
-    fwd_pass<N>(x, y1, LG - 1 + (B - 8), use_dst);
+    fwd_pass<N, F>(x, y1, LG - 1 + (B - 8), use_dst);
     if (active) {
 #pragma unroll
       for (int k = 0; k < N; k++) L.tile[k][gl] = y1[k]; // transposed store, like dst[k*line + j]
@@ -394,7 +394,7 @@ __device__ __forceinline__ int fwd_tq_block(TuLds<N> &L, int gl, bool active, co
     int z[N];
 #pragma unroll
     for (int n = 0; n < N; n++) z[n] = L.tile[gl][n];
-    fwd_pass<N>(z, coef, LG + 6, use_dst); // coef[k] is coefficient (row k, col gl)
+    fwd_pass<N, F>(z, coef, LG + 6, use_dst); // coef[k] is coefficient (row k, col gl)
     wave_sync();
   }
   if (!do_quant) {
@@ -428,7 +428,7 @@ __device__ __forceinline__ int dequant_one(int v, int iq_scale, int dshift) { //
 // invtransformNxN core: levels in L.tile[row][col] -> residual row gl in out[N].
 // BATCH: the N reads of each pass back to back with one wait behind them (pin_regs); left to itself the compiler waits for a
 // column in pieces (16x16: three waits over sixteen reads).  The whole-picture chains ask for it, the list kernels do not.
-template <int N, bool BATCH = false, typename PD>
+template <int N, bool BATCH = false, int F = kTrDefault, typename PD>
 __device__ __forceinline__ void inv_tq_block(TuLds<N> &L, int gl, bool active, bool ts, bool use_dst, bool luma,
                                              bool do_dequant, const PD &P, int *out) {
   constexpr int LG = Log2<N>::v;
@@ -448,7 +448,7 @@ __device__ __forceinline__ void inv_tq_block(TuLds<N> &L, int gl, bool active, b
   }
 #pragma unroll
   for (int k = 0; k < N; k++) c[k] = wrap16(c[k]); // coeff[j] = (short)plCoef[j], :1602
-  inv_pass<N>(c, t, 7, use_dst);                    // row gl of the intermediate block
+  inv_pass<N, F>(c, t, 7, use_dst);                   // row gl of the intermediate block
   wave_sync();                                      // every lane has read its levels
   if (active) {
 #pragma unroll
@@ -459,7 +459,7 @@ __device__ __forceinline__ void inv_tq_block(TuLds<N> &L, int gl, bool active, b
 #pragma unroll
   for (int k = 0; k < N; k++) u[k] = L.tile[k][gl];
   if constexpr (BATCH) pin_regs<N>(u);
-  inv_pass<N>(u, out, 12 - (B - 8), use_dst);
+  inv_pass<N, F>(u, out, 12 - (B - 8), use_dst);
   wave_sync();
 }
 

@@ -21,7 +21,8 @@
 template <int KIND>
 __global__ __launch_bounds__(64) void k_issue(int *out, int a0, int b0, int iters) {
   int x[8];
-  for (int i = 0; i < 8; i++) x[i] = a0 + threadIdx.x + i;
+  unsigned long long w[8]; // the 64-bit accumulators of KIND 64
+  for (int i = 0; i < 8; i++) x[i] = a0 + threadIdx.x + i, w[i] = (unsigned long long)(a0 + i) << 20;
   int b = b0;
   unsigned long long msk = 0x5555555555555555ull + (unsigned)b0;
   int sc = b0 * 3;
@@ -96,10 +97,15 @@ __global__ __launch_bounds__(64) void k_issue(int *out, int a0, int b0, int iter
         if (KIND == 60) asm volatile("v_sad_u16 %0, %1, %2, %0" : "+v"(x[i]) : "v"(b), "v"(x[(i + 1) & 7]));
         if (KIND == 61) asm volatile("v_sad_u8 %0, %1, %2, %0" : "+v"(x[i]) : "v"(b), "v"(x[(i + 1) & 7]));
         if (KIND == 62) asm volatile("v_alignbit_b32 %0, %0, %1, %2" : "+v"(x[i]) : "v"(b), "v"(x[(i + 1) & 7]));
+        // the transform chains (thevc_amd/csrc/hmx_transform.h): a multiply-add with the coefficient in an SGPR, against the
+        // multiply with a literal it replaces (56) and the multiply-add with an inline constant (57); and the 64-bit multiply-add the
+        // compiler picks for products whose operands it cannot bound
+        if (KIND == 63) asm volatile("v_mad_i32_i24 %0, %1, %0, %2" : "+v"(x[i]) : "s"(sc), "v"(b));
+        if (KIND == 64) asm volatile("v_mad_u64_u32 %0, vcc, %1, %2, %0" : "+v"(w[i]) : "v"(b), "v"(x[i]) : "vcc");
       }
   }
   int s = 0;
-  for (int i = 0; i < 8; i++) s += x[i];
+  for (int i = 0; i < 8; i++) s += x[i] + (KIND == 64 ? (int)(w[i] >> 32) : 0);
   if (s == 0x7fffffff) out[0] = s; // keeps the chain alive without a store per wave
 }
 
@@ -174,7 +180,7 @@ static void run_issue() {
   int *d;
   hipMalloc(&d, 64);
   const int iters = 4000;
-  const char *names[63] = {"v_add_u32", "v_mul_i32_i24", "v_mad_i32_i24", "v_mul_lo_u32", "v_bfi_b32", "v_max_i32", "v_and_b32", "v_lshlrev_b32",
+  const char *names[65] = {"v_add_u32", "v_mul_i32_i24", "v_mad_i32_i24", "v_mul_lo_u32", "v_bfi_b32", "v_max_i32", "v_and_b32", "v_lshlrev_b32",
                            "v_ashrrev_i32", "v_sub_u32", "v_cndmask_b32", "v_add3_u32", "v_lshl_add_u32", "v_med3_i32", "v_pk_add_i16", "v_pk_mad_i16",
                            "v_dot2_i32_i16", "v_perm_b32", "v_mov_b32", "v_bfe_i32", "v_xor_b32", "v_cmp_gt_i32", "v_mad_u32_u24", "v_pk_mul_lo_u16",
                            "v_pk_max_i16", "v_sad_u32", "v_add_lshl_u32", "v_and_or_b32", "v_min3_i32", "v_alignbit_b32", "v_add_f32", "v_fma_f32",
@@ -182,21 +188,21 @@ static void run_issue() {
                            "v_mul_hi_u32", "cmp+cndmask(2)", "v_cndmask_e64_sgpr", "v_mov_b32_dpp", "v_add_u32_dpp", "v_cmp_e64_sgpr", "v_max_i16", "v_or_b32",
                            "v_lshrrev_b32", "v_lshlrev_b32_vv", "v_min_i32", "v_subrev_u32", "v_mul_f32", "v_cvt_f32_i32", "v_readfirstlane", "v_add_u32_sgpr",
                            "v_add_u32_lit", "v_mul_i24_const", "v_mad_i24_const", "v_sub_u32_rev", "v_not_b32", "v_sad_u16", "v_sad_u8",
-                           "v_alignbit_vshift"};
+                           "v_alignbit_vshift", "v_mad_i24_sgpr", "v_mad_u64_u32"};
   hipDeviceProp_t prop;
   hipGetDeviceProperties(&prop, 0);
   const double ghz = prop.clockRate / 1e6;
   printf("device clock %.3f GHz, %d CUs\n", ghz, prop.multiProcessorCount);
   const int simds = prop.multiProcessorCount * 4;
   typedef void (*kern_t)(int *, int, int, int);
-  kern_t kerns[63] = {k_issue<0>,  k_issue<1>,  k_issue<2>,  k_issue<3>,  k_issue<4>,  k_issue<5>,  k_issue<6>,  k_issue<7>,  k_issue<8>,  k_issue<9>,
+  kern_t kerns[65] = {k_issue<0>,  k_issue<1>,  k_issue<2>,  k_issue<3>,  k_issue<4>,  k_issue<5>,  k_issue<6>,  k_issue<7>,  k_issue<8>,  k_issue<9>,
                       k_issue<10>, k_issue<11>, k_issue<12>, k_issue<13>, k_issue<14>, k_issue<15>, k_issue<16>, k_issue<17>, k_issue<18>, k_issue<19>,
                       k_issue<20>, k_issue<21>, k_issue<22>, k_issue<23>, k_issue<24>, k_issue<25>, k_issue<26>, k_issue<27>, k_issue<28>, k_issue<29>,
                       k_issue<30>, k_issue<31>, k_issue<32>, k_issue<33>, k_issue<34>, k_issue<35>, k_issue<36>, k_issue<37>, k_issue<38>, k_issue<39>,
                       k_issue<40>, k_issue<41>, k_issue<42>, k_issue<43>, k_issue<44>, k_issue<45>, k_issue<46>, k_issue<47>, k_issue<48>, k_issue<49>,
                       k_issue<50>, k_issue<51>, k_issue<52>, k_issue<53>, k_issue<54>, k_issue<55>, k_issue<56>, k_issue<57>, k_issue<58>, k_issue<59>,
-                      k_issue<60>, k_issue<61>, k_issue<62>};
-  for (int kind = (getenv("ISSUE_FROM") ? atoi(getenv("ISSUE_FROM")) : 0); kind < 63; kind++)
+                      k_issue<60>, k_issue<61>, k_issue<62>, k_issue<63>, k_issue<64>};
+  for (int kind = (getenv("ISSUE_FROM") ? atoi(getenv("ISSUE_FROM")) : 0); kind < 65; kind++)
     for (int W : {1, 2, 4, 8}) {
       hipEvent_t e0, e1;
       hipEventCreate(&e0);
